@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the ray_color hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -30,6 +30,12 @@ pipelined throughput.  The latency of ONE frame with nothing overlapped (render,
 permutation on rank 0) is measured separately after the timed region: `frame_latency_ms`, next
 to `n1_kernel_ms` (rank 0 rendering the whole frame alone) and their ratio.
 Rank 0 prints ONE JSON line.
+
+--steps K sets the number of timed frames; `ms_per_step` is the timed region's wall time / K.  --dump-outputs DIR writes,
+after the timed region, the RGB8 frame of the last timed step (what a caller of the hot path receives) to
+DIR/frame_rgb8.npy as float32 [H, W, 3] — at most 64 MB in all, beyond that a fixed sample (see _dump_outputs).  The scene
+and its Philox seed come from the scene file, so the same arguments give the same inputs in every run: two builds can be
+compared output for output.
 
 Extra objects on that line (N = 1):
   roofline      the megakernel against the roof that binds it: vector-ALU issue (no dense contraction -> no MFMA;
@@ -106,11 +112,53 @@ def _args():
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--cpu-row-stride", type=int, default=16,
                     help="cpu_baseline renders every k-th scanline (default: chosen for ~10 s of CPU wall time)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step to DIR/frame_rgb8.npy (float32)")
     return ap.parse_args()
 
 
 class BenchError(RuntimeError):
     pass
+
+
+DUMP_BYTES_MAX = 64_000_000
+
+
+def _dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32 (RGB8 values are exact in float32).  Whatever does not fit
+    its share of DUMP_BYTES_MAX is written as a fixed sample instead: <name>.npy holds the elements at the flat indices in
+    <name>_sample_index.npy (float64), drawn with seed 0 — the same for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            k = (share - 1024) // 12             # 4 B value + 8 B index per element, room for the two .npy headers
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
+def _group_frame_to_host(hip, grp, height, width):
+    """the group's frame collected last (RGB8, in HBM of its first device) copied to a host array, outside any timed region"""
+    import ctypes as C
+    import numpy as np
+    ptr, _ = grp.frame_ptr()
+    if not ptr:
+        raise BenchError("the group holds no collected frame")
+    frame = np.empty((height, width, 3), np.uint8)
+    hip_memcpy = C.CDLL(hip.LIB_PATH).hipMemcpy     # (the HIP runtime librt_hip.so is linked against)
+    hip_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip_memcpy.restype = C.c_int
+    rc = hip_memcpy(frame.ctypes.data, ptr, frame.nbytes, 2)   # 2 = hipMemcpyDeviceToHost
+    if rc != 0:
+        raise BenchError(f"hipMemcpy of the group's frame failed: {rc}")
+    return frame
 
 
 def _pmc_head(pmc):
@@ -152,6 +200,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     try:
+        if args.steps < 1 or args.warmup < 0:
+            raise BenchError(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
         if world == 1 and args.gpus > 1:
             line = run_group(args)          # ONE process, the in-library group (the product's multi-GPU path)
         else:
@@ -231,6 +281,7 @@ def run_group(args):
     kern.append(st["kernel_ms"]); gath.append(st["gather_ms"])
     sync_all()
     elapsed = time.perf_counter() - t0
+    dumped = _dump_outputs(args.dump_outputs, {"frame_rgb8": _group_frame_to_host(hip, grp, H, W)}) if args.dump_outputs else None
     # ---- ONE frame at a time, nothing overlapped (the north star's case: G launches -> ONE gather -> de-interleave -> frame
     # on the first device): latency, and where its non-kernel time goes (RtStats.group_us: host clock since submit)
     lat, lkern, lgath, stages = [], [], [], []
@@ -294,6 +345,8 @@ def run_group(args):
                      "peer_to_root": [r["peer_to_root"] for r in ranks]},
         "git_head": _git_head(),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     # the N > 1 line parses like the N = 1 line: the roofline of the dominant kernel per rank, and the CPU baseline (a pointer)
     out["roofline"] = _group_roofline("cfg2", args.gpus, out["per_rank"]["kernel_ms"]) if headline else None
     out["cpu_baseline"] = _n1_cpu_baseline_pointer()
@@ -508,9 +561,13 @@ def run_ranks(args):
         gs.render(buf.data_ptr(), 0, tiles, stream.cuda_stream)
         ev1[i].record(stream)
         pipe.submit(i)                       # N > 1: ONE gather over RCCL, asynchronous
-    n_frames += sum(f is not None for f in pipe.drain())
+    tail = pipe.drain()                      # the frames still in flight, in order: tail[-1] is the last timed step's (rank 0)
+    n_frames += sum(f is not None for f in tail)
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = _dump_outputs(args.dump_outputs, {"frame_rgb8": tail[-1].cpu().numpy()})
     kernel_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / max(1, args.steps)
     st = gs.wait()                                  # counters of the last launch (this rank's shard)
 
@@ -637,6 +694,8 @@ def run_ranks(args):
             "grid_steps_per_segment": round(steps / max(1.0, segments), 3),
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if collective:
             out["rccl_ranks"] = dist.get_world_size() if transport == "rccl" else 0
             out["visible_gpus"] = torch.cuda.device_count()

@@ -1445,6 +1445,25 @@ def test_bench_more_gpus_than_visible_is_a_json_error_line():
     assert d["value"] is None and d["n_gpus"] == n and "device" in d["error"]
 
 
+def test_bench_dump_outputs_is_the_frame_of_the_timed_path(gpu_render, load_scene, tmp_path):
+    """`bench.py --dump-outputs DIR`: the RGB8 frame of the last timed step as float32 [H, W, 3], equal to a direct render of the
+    same scene — from the one-process path and from the in-library group (two ranks sharing the GPU) alike."""
+    frames = {}
+    for name, args, env in (("n1", ["--gpus", "1"], None), ("g2", ["--gpus", "2"], {"RT_GPUS_EMULATE": "1"})):
+        r = _run_bench(args + ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(tmp_path / name)], env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["dumped_outputs"] == {"frame_rgb8": [800, 1200, 3]}
+        assert sorted(os.listdir(tmp_path / name)) == ["frame_rgb8.npy"]
+        frames[name] = np.load(tmp_path / name / "frame_rgb8.npy")
+        assert frames[name].dtype == np.float32 and frames[name].shape == (800, 1200, 3)
+    rgb, _, _ = gpu_render(load_scene("cover"), want_linear=False)
+    assert np.array_equal(frames["n1"], rgb.astype(np.float32))
+    assert np.array_equal(frames["g2"], frames["n1"])
+
+
 def test_scene_may_change_streams_once_the_first_stream_is_drained(pkg, load_scene, torch_cuda):
     """a caller that synchronises the first stream ITSELF (no rt_hip_wait) may launch on another stream — the
     in-flight guard asks hipStreamQuery instead of insisting on rt_hip_wait (the ABI v2 behaviour)."""
