@@ -281,6 +281,28 @@ int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 int rt_hip_set_camera(RtHipScene*, const double origin[3], const double lower_left[3], const double horizontal[3],
                       const double vertical[3]);
 int rt_hip_render_to_host(RtHipScene*, uint8_t* out_rgb8, RtStats* stats);
+/* Progressive rendering: a frame's samples in passes, and the image resolved at any point.  Sample s of pixel p traces the same
+ * path whatever the frame's sample count, and pixel sums are exact 2^-40 fixed point, so the passes of any split of [0, N) — any
+ * sizes, any order — added up and resolved over N give the frame rt_hip_render makes at samples_per_pixel = N, bit for bit
+ * (RGB8, linear radiance, NaN pixels).  An ACCUMULATOR is rt_tiles_local_rows()*width*3 u64 words, packed by RtRowTiles exactly
+ * like d_rgb8, 8-byte aligned, zeroed by the caller before its first pass: per pixel channel, bits 0-62 hold the fixed-point sum
+ * (value * 2^40, rounded), bit 63 is set if any sample of that channel was NaN.  Two accumulators of disjoint sample ranges merge
+ * as ((a | b) & F) | ((a & ~F) + (b & ~F)), F = bit 63.  One accumulator holds at most 2^23 - 1 samples per pixel.
+ *
+ * Render samples [sample_begin, sample_begin + sample_count) of every pixel of `tiles` and ADD their exact fixed-point sums to
+ * d_accum (caller-zeroed device buffer, rt_tiles_local_rows()*width*3 u64, 8-byte aligned); asynchronous like rt_hip_render,
+ * rt_hip_wait reports it.  The same rules as rt_hip_render (one stream per scene at a time); passes into one accumulator are
+ * ordered on one stream.  sample_count 0 or a misaligned accumulator: RT_ERR_INVALID; sample_begin + sample_count above
+ * 2^23 - 1: RT_ERR_UNSUPPORTED — and no work is enqueued. */
+int rt_hip_accumulate(RtHipScene*, const RtRowTiles* tiles, uint32_t sample_begin, uint32_t sample_count, void* d_accum, void* stream);
+/* d_accum holding n_samples samples per pixel -> d_rgb8 / d_linear (either may be NULL), same packing; asynchronous.
+ * n_samples 0: RT_ERR_INVALID; above 2^23 - 1: RT_ERR_UNSUPPORTED.  Not reported by rt_hip_wait. */
+int rt_hip_resolve(RtHipScene*, const RtRowTiles* tiles, const void* d_accum, uint32_t n_samples, void* d_rgb8, void* d_linear, void* stream);
+/* host-buffer form (the CLI; consumers without a HIP allocator): the next sample_count samples of the whole frame into the scene's own
+ * accumulator, resolved over everything it holds, RGB8 copied to out_rgb8; blocking.  The accumulator (width*height*24 bytes) is
+ * allocated at first use and starts over after rt_hip_set_camera, rt_hip_set_option "max_depth" / "seed" / "accum_reset";
+ * rt_hip_scene_query "accum_samples" says how many samples per pixel it holds.  stats: the pass's kernel. */
+int rt_hip_refine_to_host(RtHipScene*, uint32_t sample_count, uint8_t* out_rgb8, RtStats* stats);
 /* A frame over the GPUs of one node, scene resident (the parallel loop of raytracer.rs:254-262 spread over devices;
  * animation: README.md:43-57).  n_gpus = 0 takes scene->n_gpus, then RT_GPUS, then 1.  Each rank renders
  * interleaved 2-scanline tiles (RtRowTiles{2, r, G}) on its own host thread and stream; ONE gather per frame

@@ -1725,4 +1725,10 @@ RT_HD uint8_t f32_to_u8(float x) {
 #endif
 }
 
+// Progressive accumulators (rt_hip_accumulate): per pixel channel one u64, bits 0-62 the fixed-point sum, bit 63 sticky NaN.
+// A sample adds at most 2^40, so 2^23 - 1 samples never carry into the flag.  They are resolved (rt_kernel.hip rt_resolve) with
+// the functions above, in the order the megakernel's tile flush applies them: fixed_to_mean, rt_nanf, f32_to_u8 of the sqrt.
+constexpr unsigned long long ACCUM_NAN_BIT = 1ull << 63;
+constexpr uint32_t ACCUM_MAX_SAMPLES = (1u << 23) - 1u;
+
 }  // namespace rtc

@@ -144,6 +144,12 @@ struct RtHipScene {
   uint64_t last_waves = 0;
   uint32_t last_tiles_x = 0;
   int variant = 0;
+  // progressive rendering, host form (rt_hip_refine_to_host): the scene's own accumulator (width x height x 3 u64, allocated at
+  // first use) and the samples per pixel it holds; accum_zero: it must be cleared before the next pass adds to it
+  unsigned long long* d_accum = nullptr; size_t accum_bytes = 0;
+  uint32_t accum_samples = 0;
+  bool accum_zero = true;
+  void reset_accum() { accum_samples = 0; accum_zero = true; }
   Slot& last_slot() { return slot[(n_launches + 1) & 1]; }  // the slot of the most recent launch
 };
 constexpr uint32_t RT_SLOT_COUNTERS = 32;  // segments, exact tests, tex_oob, grid steps, 4 x wave trip counts, 8 x section cycles, profile clocks, (the tile-queue cursors,) [28] repeated segments
@@ -209,7 +215,7 @@ extern "C" void rt_hip_scene_destroy(RtHipScene* s) {
     for (void* p : {s->d_geom, s->d_mat, s->d_lights, s->d_tex, s->d_sky, s->d_tex4, s->d_sky4, s->d_matc, s->d_cell_word, s->d_cell_items, s->d_large,
                     s->d_all, s->d_large_geom})
       if (p) (void)hipFree(p);
-  for (void* p : {(void*)s->d_counters, s->d_frame, (void*)s->d_tile_depth, (void*)s->d_tile_order, s->d_light_overflow})
+  for (void* p : {(void*)s->d_counters, s->d_frame, (void*)s->d_tile_depth, (void*)s->d_tile_order, s->d_light_overflow, (void*)s->d_accum})
     if (p) (void)hipFree(p);
   for (auto& sl : s->slot) {
     for (hipEvent_t e : {sl.ev_start, sl.ev_stop, sl.ev_copied}) if (e) (void)hipEventDestroy(e);
@@ -391,10 +397,11 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
   if (!std::strcmp(key, "samples_per_pixel") || !std::strcmp(key, "max_depth")) {
     if (value < 0 || value > (int64_t)0xFFFFFFFFll) return fail(RT_ERR_INVALID, std::string(key) + " must be in 0 .. 2^32-1");
     if (key[0] == 's') s->host.samples_per_pixel = s->dev.spp = (uint32_t)value;
-    else s->host.max_depth = s->dev.max_depth = (uint32_t)value;
+    else { s->host.max_depth = s->dev.max_depth = (uint32_t)value; s->reset_accum(); }
     return RT_OK;
   }
-  if (!std::strcmp(key, "seed")) { s->host.seed = (uint64_t)value; s->dev.seed_lo = (uint32_t)value; s->dev.seed_hi = (uint32_t)((uint64_t)value >> 32); return RT_OK; }
+  if (!std::strcmp(key, "seed")) { s->host.seed = (uint64_t)value; s->dev.seed_lo = (uint32_t)value; s->dev.seed_hi = (uint32_t)((uint64_t)value >> 32); s->reset_accum(); return RT_OK; }
+  if (!std::strcmp(key, "accum_reset")) { if (value != 1) return fail(RT_ERR_INVALID, "accum_reset takes the value 1"); s->reset_accum(); return RT_OK; }
   return fail(RT_ERR_INVALID, std::string("unknown option ") + key);
 }
 
@@ -405,10 +412,10 @@ namespace {
 // launch's start event is recorded — a first frame used to carry the 147 MB hipMalloc of a lit scene and the runtime's
 // first look at the kernel inside its kernel_ms (one-shot CLI frames: 8.4 ms for a 0.9 ms kernel, profiles/r05_run5_cli_stats_before_warmup.log)
 // — and once at scene creation for the scene's default configuration (warm_up).
-template <bool HL, bool SIMPLE, bool LDS, bool WIDE>
+template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM>
 int prepare_grid_t(RtHipScene* s, size_t lds_bytes, hipStream_t stream) {
-  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE>;
-  const int key = (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
+  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM>;
+  const int key = (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
   if (s->cfg_key != key || s->cfg_lds != lds_bytes) {
     if (lds_bytes > 48 * 1024) RT_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int per_cu_q = 0;
@@ -428,9 +435,9 @@ int prepare_grid_t(RtHipScene* s, size_t lds_bytes, hipStream_t stream) {
   }
   return RT_OK;
 }
-template <bool HL, bool SIMPLE, bool LDS, bool WIDE>
+template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM>
 int launch_grid_t(RtHipScene* s, const rtk::KArgs& ka_in, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
-  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE>;
+  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM>;
   // persistent: exactly the resident set, never more workgroups than there are wave-sized items
   uint32_t wgs = (uint32_t)s->cfg_per_cu * (uint32_t)s->num_cus;
   const uint32_t need = (n_items + rtk::WAVES - 1) / rtk::WAVES;
@@ -441,10 +448,11 @@ int launch_grid_t(RtHipScene* s, const rtk::KArgs& ka_in, size_t lds_bytes, uint
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(rtk::BLOCK), lds_bytes, stream, ka);
   return RT_OK;
 }
-// (lights, every albedo in [0, 1], tables in LDS, wide cell tables) -> the instantiation's prepare / launch
-int dispatch_grid(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
+// (lights, every albedo in [0, 1], tables in LDS, wide cell tables, accumulating) -> the instantiation's prepare / launch
+template <bool ACCUM>
+int dispatch_grid_t(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
   int rc;
-#define RT_GO(HL, SIMPLE, LDS, WIDE) rc = prepare_only ? prepare_grid_t<HL, SIMPLE, LDS, WIDE>(s, lds_bytes, stream) : launch_grid_t<HL, SIMPLE, LDS, WIDE>(s, *ka, lds_bytes, n_items, stream)
+#define RT_GO(HL, SIMPLE, LDS, WIDE) rc = prepare_only ? prepare_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM>(s, lds_bytes, stream) : launch_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM>(s, *ka, lds_bytes, n_items, stream)
   const bool simple = s->simple_colour;
   if (wide) {  // (the launch's grid has 32-bit item lists — more than 65 535 spheres; tables in L2: plan_lds never puts them in LDS)
     if (lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
@@ -457,6 +465,11 @@ int dispatch_grid(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bo
   else { if (simple) RT_GO(false, true, false, false); else RT_GO(false, false, false, false); }
 #undef RT_GO
   return rc;
+}
+int dispatch_grid(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream,
+                  bool accum = false) {
+  return accum ? dispatch_grid_t<true>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream)
+               : dispatch_grid_t<false>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream);
 }
 
 // LDS budget of a launch: do the tables fit, how big are the light pools, how much dynamic LDS does a workgroup ask for.
@@ -524,10 +537,13 @@ int warm_up(RtHipScene* s) {
 
 }  // namespace
 
-extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_linear, void* stream_) {
-  if (!s) return fail(RT_ERR_INVALID, "null argument");
+namespace {
+// One launch of the megakernel over the given row tiles: samples [sample_base, sample_base + spp) of every pixel.  accum == nullptr:
+// the one-shot frame (rt_hip_render: sample_base 0, the scene's samples per pixel, pixels into d_rgb8 / d_linear); else the
+// accumulating kernels add the pass's sums to accum (rt_hip_accumulate).  The caller has checked its own arguments.
+int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_linear, unsigned long long* accum, uint32_t sample_base,
+                 uint32_t spp, void* stream_) {
   const uint32_t local_rows = rt_tiles_local_rows(s->host.height, tiles);
-  if (!d_rgb8 && local_rows != 0) return fail(RT_ERR_INVALID, "null framebuffer");
   hipStream_t stream = (hipStream_t)stream_;
   const bool has_lights = s->has_lights || s->force_lit != 0;
   // one tile-queue cursor / counter block per scene: launches of a scene are ordered on ONE stream
@@ -540,14 +556,12 @@ extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb
   if (s->in_flight && stream != s->last_stream)
     return fail(RT_ERR_INVALID, "rt_hip_render: this scene has a launch in flight on another stream (call rt_hip_wait first, "
                                 "or use one RtHipScene per concurrent stream)");
-  // the exact pixel sums are 2^-40 fixed point in 64 bits: spp * 2^40 must stay below 2^63
-  if (s->host.samples_per_pixel > (1u << 22)) return fail(RT_ERR_UNSUPPORTED, "more than 2^22 samples per pixel");
   if (s->host.width > 524280u) return fail(RT_ERR_UNSUPPORTED, "frames wider than 524280 pixels");
   RT_HIP_TRY(hipSetDevice(s->device));
   RtHipScene::Slot& sl = s->slot[s->n_launches & 1];
   s->n_launches++;
   sl.rows = local_rows; sl.waves = 0; sl.launched = false;
-  sl.samples = (uint64_t)local_rows * s->host.width * s->host.samples_per_pixel;
+  sl.samples = (uint64_t)local_rows * s->host.width * spp;
   s->last_stream = stream;
   sl.t_launch = std::chrono::steady_clock::now();
   RT_HIP_TRY(hipMemsetAsync(s->d_counters, 0, 32 * sizeof(unsigned long long), stream));
@@ -571,6 +585,8 @@ extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb
     ka.sc.large_geom = (const rtc::SphereGeom*)s->d_geom;
   }
   ka.out_rgb8 = (uint8_t*)d_rgb8; ka.out_linear = (float*)d_linear; ka.counters = s->d_counters;
+  ka.accum = accum; ka.sample_base = sample_base;
+  ka.sc.spp = spp;  // (the kernel's sample count: the pass's, for an accumulating launch)
   ka.queue = (uint32_t*)(s->d_counters + 24);
   ka.local_rows = local_rows;
   const bool tiled = tiles && tiles->tile_rows && tiles->tile_stride;
@@ -612,7 +628,6 @@ extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb
   // 4x4 -> 16, 2x2 -> 32, 1x1 -> 128 — give or take a factor of two so that a frame has about 60
   // items per wave (measured on the whole frame and its 1/2, 1/4, 1/8 shards, profiles/r01_run11_tiles.log:
   // both fewer, larger items and more, smaller ones lose up to 5 %).
-  const uint32_t spp = s->host.samples_per_pixel;
   uint32_t chunk_spp = (uint32_t)s->chunk_spp;
   if (chunk_spp == 0) {
     static const uint32_t by_tile[4] = {128u, 32u, 16u, 8u};
@@ -710,12 +725,12 @@ extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb
 
   int rc;
   auto launch = [&](const rtk::KArgs& ka, uint32_t n_items) -> int {
-    const int rc = dispatch_grid(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, false, &ka, lds_bytes, n_items, stream);
+    const int rc = dispatch_grid(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, false, &ka, lds_bytes, n_items, stream, accum != nullptr);
     if (rc != RT_OK) return rc;
     RT_HIP_TRY(hipGetLastError());
     return RT_OK;
   };
-  if ((rc = dispatch_grid(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, true, nullptr, lds_bytes, 0, stream)) != RT_OK) return rc;  // (host-side set-up: before the start event)
+  if ((rc = dispatch_grid(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, true, nullptr, lds_bytes, 0, stream, accum != nullptr)) != RT_OK) return rc;  // (host-side set-up: before the start event)
   RT_HIP_TRY(hipEventRecord(sl.ev_start, stream));
   // A frame without a measured order (the first of a scene, a one-shot render) leaves the queue bottom row first and ends on
   // whatever deep path started last: 13.3 instead of 12.8 ms on the headline frame.  Two ways to SEED an order — a depth guess
@@ -726,6 +741,53 @@ extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb
   RT_HIP_TRY(hipEventRecord(sl.ev_stop, stream));
   if (ka.tile_depth) { s->order_age++; s->depth_fresh = true; }  // (the NEXT frame of this view sorts them into its order)
   return finish_launch(true);
+}
+}  // namespace
+
+extern "C" int rt_hip_render(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_linear, void* stream_) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (!d_rgb8 && rt_tiles_local_rows(s->host.height, tiles) != 0) return fail(RT_ERR_INVALID, "null framebuffer");
+  // the exact pixel sums are 2^-40 fixed point in 64 bits: spp * 2^40 must stay below 2^63
+  if (s->host.samples_per_pixel > (1u << 22)) return fail(RT_ERR_UNSUPPORTED, "more than 2^22 samples per pixel");
+  return launch_frame(s, tiles, d_rgb8, d_linear, nullptr, 0u, s->host.samples_per_pixel, stream_);
+}
+
+// Progressive rendering.  Sample s of pixel p traces the same path whatever the frame's sample count (Philox is addressed by
+// (pixel, sample index, node, slot)), and a pixel's sum is exact fixed point (integer adds: any order, any grouping), so the sums
+// of any set of passes covering [0, N) resolved over N are the one-shot frame at N samples, bit for bit.
+namespace {
+int check_accum(const RtHipScene* s, const RtRowTiles* tiles, const void* d_accum) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (rt_tiles_local_rows(s->host.height, tiles) == 0) return RT_OK;
+  if (!d_accum) return fail(RT_ERR_INVALID, "null accumulator");
+  if (reinterpret_cast<uintptr_t>(d_accum) & 7u) return fail(RT_ERR_INVALID, "the accumulator must be 8-byte aligned");
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_hip_accumulate(RtHipScene* s, const RtRowTiles* tiles, uint32_t sample_begin, uint32_t sample_count, void* d_accum, void* stream) {
+  const int rc = check_accum(s, tiles, d_accum);
+  if (rc != RT_OK) return rc;
+  if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
+  if ((uint64_t)sample_begin + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  return launch_frame(s, tiles, nullptr, nullptr, (unsigned long long*)d_accum, sample_begin, sample_count, stream);
+}
+
+extern "C" int rt_hip_resolve(RtHipScene* s, const RtRowTiles* tiles, const void* d_accum, uint32_t n_samples, void* d_rgb8, void* d_linear, void* stream) {
+  int rc = check_accum(s, tiles, d_accum);
+  if (rc != RT_OK) return rc;
+  if (n_samples == 0) return fail(RT_ERR_INVALID, "n_samples must be at least 1");
+  if (n_samples > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  const uint64_t n_px = (uint64_t)rt_tiles_local_rows(s->host.height, tiles) * s->host.width;
+  if (n_px == 0 || (!d_rgb8 && !d_linear)) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const uint64_t blocks = ((n_px + 3u) / 4u + 255u) / 256u;
+  if (blocks > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "frame too large to resolve");
+  hipLaunchKernelGGL(rtk::rt_resolve, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_accum, n_samples, n_px,
+                     (uint8_t*)d_rgb8, (float*)d_linear);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
 }
 
 #ifdef RT_TEST_PROBES
@@ -814,6 +876,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
+  if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;  // samples per pixel in the scene's accumulator (rt_hip_refine_to_host)
   if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->grid.n_cells * (s->grid.wide ? 16u : 8u) + (size_t)s->grid.n_items * (s->grid.wide ? 4u : 2u));
   return -1;
 }
@@ -821,6 +884,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
 extern "C" int rt_hip_set_camera(RtHipScene* s, const double origin[3], const double lower_left[3], const double horizontal[3],
                                  const double vertical[3]) {
   if (!s || !origin || !lower_left || !horizontal || !vertical) return fail(RT_ERR_INVALID, "null argument");
+  s->reset_accum();  // (whatever the camera: a progressive frame starts over)
   bool same = true;
   for (int i = 0; i < 3; ++i)
     same = same && s->host.cam_origin[i] == origin[i] && s->host.cam_lower_left[i] == lower_left[i] && s->host.cam_horizontal[i] == horizontal[i] &&
@@ -857,6 +921,42 @@ extern "C" int rt_hip_render_to_host(RtHipScene* s, uint8_t* out_rgb8, RtStats* 
   RtStats st;
   if (rc == RT_OK) rc = rt_hip_wait(s, &st);
   if (rc != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(out_rgb8, s->d_frame, bytes, hipMemcpyDeviceToHost));
+  if (stats) {
+    *stats = st;
+    stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return RT_OK;
+}
+
+// Progressive rendering into the scene's own accumulator, blocking: the next sample_count samples of every pixel, then the whole
+// accumulator resolved to RGB8 in out_rgb8.  Passes and the resolve run on the NULL stream, like rt_hip_render_to_host.
+extern "C" int rt_hip_refine_to_host(RtHipScene* s, uint32_t sample_count, uint8_t* out_rgb8, RtStats* stats) {
+  if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
+  if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
+  if ((uint64_t)s->accum_samples + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  auto t0 = std::chrono::steady_clock::now();
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 3;
+  if (px * 24 > s->accum_bytes) {
+    if (s->d_accum) { RT_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->d_accum); s->d_accum = nullptr; s->accum_bytes = 0; }
+    RT_HIP_TRY(hipMalloc((void**)&s->d_accum, px * 24));
+    s->accum_bytes = px * 24;
+    s->reset_accum();
+  }
+  if (bytes > s->frame_bytes) {
+    if (s->d_frame) { (void)hipFree(s->d_frame); s->d_frame = nullptr; s->frame_bytes = 0; }
+    RT_HIP_TRY(hipMalloc(&s->d_frame, bytes));
+    s->frame_bytes = bytes;
+  }
+  if (s->accum_zero && px) { RT_HIP_TRY(hipMemsetAsync(s->d_accum, 0, px * 24, nullptr)); s->accum_zero = false; }
+  const uint32_t n = s->accum_samples + sample_count;
+  int rc = rt_hip_accumulate(s, nullptr, s->accum_samples, sample_count, s->d_accum, nullptr);
+  if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->d_accum, n, s->d_frame, nullptr, nullptr);
+  RtStats st;
+  if (rc == RT_OK) rc = rt_hip_wait(s, &st);
+  if (rc != RT_OK) { s->reset_accum(); return rc; }  // (a pass that did not complete leaves the accumulator unknown: start over)
+  s->accum_samples = n;
   RT_HIP_TRY(hipMemcpy(out_rgb8, s->d_frame, bytes, hipMemcpyDeviceToHost));
   if (stats) {
     *stats = st;

@@ -58,6 +58,10 @@ struct KArgs {
   // when its own is empty.  The lines of a run then collect all their bytes in one L2 before they are written back.
   uint32_t aff_group_log2;
   uint32_t xcd_cnt[8], xcd_off[8];
+  // Accumulating launches (rt_hip_accumulate, ACCUM kernels): tiles ADD their fixed-point sums to accum (rows x width x 3 u64,
+  // packed like out_rgb8; bit 63 = a NaN sample) instead of writing pixels, and trace samples sample_base + [0, sc.spp).
+  unsigned long long* accum;
+  uint32_t sample_base;
 };
 // tiles of XCD x in image order: the j-th one (aff_group_log2 = gl)
 __host__ __device__ inline uint32_t xcd_tile(uint32_t x, uint32_t j, uint32_t gl) { return ((((j >> gl) << 3) + x) << gl) + (j & ((1u << gl) - 1u)); }
@@ -307,7 +311,10 @@ struct LdsTables {  // per-lane gathers from the workgroup's LDS copies
 // The two forms stand side by side as `if constexpr` blocks in hit_world: the packed path is textually what it was before the
 // wide one existed, and compiles to the same code (helper functions over a common cell type did not: three instructions and a
 // different register assignment in every instantiation, +0.4 % on the headline frame, profiles/r05_run19_ab_wide_tables.log).
-template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false>
+// ACCUM: the accumulating form of progressive rendering (rt_hip_accumulate): a finished tile adds its exact sums to the caller's
+// accumulator (KArgs.accum) instead of writing pixels, and its samples are numbered from KArgs.sample_base.  Everything else —
+// the queue, the pools, the paths — is the one-shot kernel's, which is why a frame made of passes is the one-shot frame.
+template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false>
 __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs ka) {
   static_assert(!(LDS_TABLES && WIDE), "wide tables (more than 65 535 spheres) never fit LDS");
   const DevScene& sc = ka.sc;
@@ -428,7 +435,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
   auto lds_store = [&](uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); };
 
   // every sample of tile slot k is in its pixel sums: mean, sqrt gamma, f32 -> u8, store
-  // (raytracer.rs:207-216), then free the slot
+  // (raytracer.rs:207-216) — ACCUM kernels: add the sums to the accumulator instead — then free the slot
   auto flush_tile = [&](uint32_t k) {
     const KArgs& ka = fresh_args();
     const DevScene& sc = ka.sc;
@@ -439,31 +446,44 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     const unsigned long long* acc = tile_acc + k * (3u << (2u * tl));
     const bool valid = lane < (1u << (2u * tl)) && px < sc.width && lr < ka.local_rows;
     const size_t o = ((size_t)lr * sc.width + px) * 3;
-    uint32_t rgb = 0u;  // R | G << 8 | B << 16
-    if (valid) {
+    if constexpr (ACCUM) {
+      // add the tile's sums to the accumulator; a NaN sample sets the channel's sticky bit 63.  No atomics: one flush of one
+      // launch owns a pixel, and launches into one accumulator are ordered on one stream.
+      if (valid) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        float lin = fixed_to_mean(__hip_atomic_load(&acc[lane * 3u + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), sc.spp);
-        if ((__hip_atomic_load(&hdr[k].nan_mask[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> lane) & 1ull) lin = rt_nanf();
-        if (ka.out_linear) ka.out_linear[o + c] = lin;
-        rgb |= (uint32_t)f32_to_u8(__builtin_sqrtf(lin)) << (8 * c);
+        for (int c = 0; c < 3; ++c) {
+          unsigned long long v = ka.accum[o + c] + __hip_atomic_load(&acc[lane * 3u + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if ((__hip_atomic_load(&hdr[k].nan_mask[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> lane) & 1ull) v |= ACCUM_NAN_BIT;
+          ka.accum[o + c] = v;
+        }
       }
-    }
-    // Framebuffer write.  Tiles at least 4 pixels wide in a frame whose width is a multiple of 4: every aligned group
-    // of 4 pixels of a tile row is 12 contiguous, 4-byte-aligned bytes, written as three dwords by its first three
-    // lanes (R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3; the neighbour's bytes arrive by a lane shift) — one store
-    // instruction per flush instead of three byte stores.  Otherwise: bytes.
-    const bool packed = wl >= 2u && (sc.width & 3u) == 0u && (reinterpret_cast<uintptr_t>(ka.out_rgb8) & 3u) == 0u;
-    if (packed) {
-      const uint32_t nxt = (uint32_t)__shfl_down((int)rgb, 1);
-      uint32_t i = lane & 3u;
-      // (made HERE: hoisted out of the path loop, i, 8 i, 24 - 8 i and a zero-extended copy hold four registers for good — spilled in
-      //  the lit kernels and with the general colour map: <lights=0, simple=0> 12 -> 0 spilled registers.  The unlit short-map
-      //  kernel has them to spare; measured both ways three times, it is 0.0 - 0.9 % faster with this form, profiles/r05_run6_ab_takes_and_flush.log)
-      asm volatile("" : "+v"(i));
-      if (valid && i < 3u) *reinterpret_cast<uint32_t*>(ka.out_rgb8 + o + i) = (rgb >> (8u * i)) | (nxt << (24u - 8u * i));
-    } else if (valid) {
-      ka.out_rgb8[o] = (uint8_t)rgb; ka.out_rgb8[o + 1] = (uint8_t)(rgb >> 8); ka.out_rgb8[o + 2] = (uint8_t)(rgb >> 16);
+    } else {
+      uint32_t rgb = 0u;  // R | G << 8 | B << 16
+      if (valid) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          float lin = fixed_to_mean(__hip_atomic_load(&acc[lane * 3u + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), sc.spp);
+          if ((__hip_atomic_load(&hdr[k].nan_mask[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> lane) & 1ull) lin = rt_nanf();
+          if (ka.out_linear) ka.out_linear[o + c] = lin;
+          rgb |= (uint32_t)f32_to_u8(__builtin_sqrtf(lin)) << (8 * c);
+        }
+      }
+      // Framebuffer write.  Tiles at least 4 pixels wide in a frame whose width is a multiple of 4: every aligned group
+      // of 4 pixels of a tile row is 12 contiguous, 4-byte-aligned bytes, written as three dwords by its first three
+      // lanes (R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3; the neighbour's bytes arrive by a lane shift) — one store
+      // instruction per flush instead of three byte stores.  Otherwise: bytes.
+      const bool packed = wl >= 2u && (sc.width & 3u) == 0u && (reinterpret_cast<uintptr_t>(ka.out_rgb8) & 3u) == 0u;
+      if (packed) {
+        const uint32_t nxt = (uint32_t)__shfl_down((int)rgb, 1);
+        uint32_t i = lane & 3u;
+        // (made HERE: hoisted out of the path loop, i, 8 i, 24 - 8 i and a zero-extended copy hold four registers for good — spilled in
+        //  the lit kernels and with the general colour map: <lights=0, simple=0> 12 -> 0 spilled registers.  The unlit short-map
+        //  kernel has them to spare; measured both ways three times, it is 0.0 - 0.9 % faster with this form, profiles/r05_run6_ab_takes_and_flush.log)
+        asm volatile("" : "+v"(i));
+        if (valid && i < 3u) *reinterpret_cast<uint32_t*>(ka.out_rgb8 + o + i) = (rgb >> (8u * i)) | (nxt << (24u - 8u * i));
+      } else if (valid) {
+        ka.out_rgb8[o] = (uint8_t)rgb; ka.out_rgb8[o + 1] = (uint8_t)(rgb >> 8); ka.out_rgb8[o + 2] = (uint8_t)(rgb >> 16);
+      }
     }
     if (lane == 0 && ka.tile_depth) ka.tile_depth[(xy >> 16) * ka.tiles_x + (xy & 0xFFFFu)] = lds_load(&hdr[k].max_depth);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -616,6 +636,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     const uint32_t s_left = sc.spp - s_begin;
     const uint32_t s_count = s_left < ka.chunk_spp ? s_left : ka.chunk_spp;
     it_k = k; it_bx = bx; it_by = by; it_sbeg = s_begin; it_next = 0;
+    if constexpr (ACCUM) it_sbeg += ka.sample_base;  // (a pass: samples sample_base + [0, sc.spp) of every pixel)
     it_total = npx * s_count;  // pool item w = (pixel slot w % npx, sample s_begin + w / npx)
     py_slot = py; ok_slot = lane < npx && px < sc.width && lr < ka.local_rows;
     RT_PROF_COUNT(cnt_items);
@@ -1057,6 +1078,42 @@ __global__ __launch_bounds__(1024) void rt_order_tiles(const uint32_t* __restric
   for (uint32_t j = threadIdx.x; j < n_tiles; j += blockDim.x) {
     const uint32_t i = n_tiles - 1u - j;
     tile_order[atomicAdd(&start[w][key_of(i, tile_depth[i])], 1u)] = i;
+  }
+}
+
+// --------------------------------------------------------------------------- progressive rendering: resolve
+// accumulator (n_px pixels x 3 u64, rt_hip_accumulate) holding n samples per pixel -> linear f32 and / or RGB8 through the
+// rt_core.h functions the megakernel's tile flush calls, in the same order (fixed_to_mean, rt_nanf, f32_to_u8 of the sqrt).  One thread per 4 pixels: their 12 bytes of RGB8 leave
+// as three dword stores when the buffer is 4-byte aligned (the packed rows of a frame are one contiguous run), else as bytes.
+__global__ __launch_bounds__(256) void rt_resolve(const unsigned long long* __restrict__ accum, uint32_t n, uint64_t n_px,
+                                                  uint8_t* __restrict__ out_rgb8, float* __restrict__ out_linear) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, p0 = g * 4u;
+  if (p0 >= n_px) return;
+  const uint32_t np = n_px - p0 < 4u ? (uint32_t)(n_px - p0) : 4u;
+  uint32_t w[3] = {0u, 0u, 0u};  // the group's 12 RGB8 bytes, little-endian
+#pragma unroll
+  for (uint32_t i = 0; i < 4u; ++i) {
+    if (i >= np) break;
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; ++c) {
+      const uint64_t e = (p0 + i) * 3u + c;
+      const unsigned long long v = accum[e];
+      float lin = fixed_to_mean(v & ~ACCUM_NAN_BIT, n);  // (flush_tile's arithmetic, term for term)
+      if (v & ACCUM_NAN_BIT) lin = rt_nanf();
+      if (out_linear) out_linear[e] = lin;
+      const uint32_t b = i * 3u + c;
+      w[b >> 2] |= (uint32_t)f32_to_u8(__builtin_sqrtf(lin)) << (8u * (b & 3u));
+    }
+  }
+  if (!out_rgb8) return;
+  uint8_t* dst = out_rgb8 + p0 * 3u;
+  if (np == 4u && (reinterpret_cast<uintptr_t>(out_rgb8) & 3u) == 0u) {
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+    d[0] = w[0]; d[1] = w[1]; d[2] = w[2];
+  } else {
+#pragma unroll
+    for (uint32_t b = 0; b < 12u; ++b)
+      if (b < np * 3u) dst[b] = (uint8_t)(w[b >> 2] >> (8u * (b & 3u)));
   }
 }
 

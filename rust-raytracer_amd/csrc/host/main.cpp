@@ -16,6 +16,12 @@
 // over the G devices and frames are pipelined two deep (RT_ANIM=sharded, default), or the frames are distributed over the
 // devices, each rendering whole frames (RT_ANIM=frames); RT_STATS=1 prints frames per second and the per-frame kernel / frame / PNG
 // times to stderr (one JSON line).
+//
+// Progressive (`raytracer <config_file> <output_file> --passes K`): the scene's samples per pixel in K contiguous ranges, as even
+// as they come, each added to the scene's accumulator on the GPU (rt_hip_refine_to_host) and the image so far rewritten to
+// <output_file> after every pass (a temporary file in the same directory, then rename: a viewer never sees half a file).  Stderr
+// gets `pass i/K: S samples, kernel X ms`; stdout the same two lines as a one-shot run, `Frame time` over all the passes; the
+// last PNG is the one-shot run's, byte for byte.  One GPU: RT_GPUS > 1 is refused.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -202,6 +208,34 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
   return status;
 }
 
+// --passes K: one resident scene, K refinements of its accumulator, the PNG rewritten after each
+int progressive(RtSceneFile* sf, const char* filename, uint32_t passes) {
+  const RtScene* sc = rt_scene_get(sf);
+  RtHipScene* hs = nullptr;
+  int rc = rt_hip_scene_create(sc, 0, &hs);
+  std::printf("\nRendering %s\n", filename);  // main.rs:18
+  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
+  std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);
+  const std::string tmp = std::string(filename) + ".part";  // (same directory: rename() replaces the file in one step)
+  const uint32_t spp = sc->samples_per_pixel;
+  double frame_ms = 0.0;
+  int status = 0;
+  for (uint32_t i = 0; i < passes && status == 0; ++i) {
+    const uint32_t count = spp / passes + (i < spp % passes ? 1u : 0u);  // (the first spp % K passes take one sample more)
+    RtStats st{};
+    rc = rt_hip_refine_to_host(hs, count, pixels.data(), &st);
+    if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; break; }
+    frame_ms += st.frame_ms;
+    std::fprintf(stderr, "pass %u/%u: %u samples, kernel %.3f ms\n", i + 1, passes, count, st.kernel_ms);
+    rc = rt_png_write_rgb8(tmp.c_str(), pixels.data(), sc->width, sc->height);  // raytracer.rs:265
+    if (rc == RT_OK && std::rename(tmp.c_str(), filename) != 0) rc = RT_ERR_PNG;
+    if (rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error()); std::remove(tmp.c_str()); status = 101; }
+    if (i + 1 == passes && status == 0) std::printf("Frame time: %lldms\n", (long long)frame_ms);  // raytracer.rs:263, all the passes
+  }
+  rt_hip_scene_destroy(hs);
+  return status;
+}
+
 // RT_ANIM=frames: the frames DISTRIBUTED over the devices — device g renders whole frames g, g + G, ... on its own resident
 // scene and host thread (README.md:43-57 renders an animation one process per frame; this is that, with the scene loaded
 // once per device).  No gather, no shard penalty, no per-frame synchronisation between devices; every frame is the bytes the
@@ -287,17 +321,20 @@ double g_hip_init_ms = 0.0;
 int run(int argc, char** argv) {
   const auto t_main = std::chrono::steady_clock::now();
   int frames = 0;
+  long passes = 0;
   double orbit = 0.0;
   bool orbit_given = false, bad_args = argc < 3;
   for (int i = 3; i < argc && !bad_args; ++i) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit = std::atof(argv[++i]); orbit_given = true; }
-    else bad_args = true;
+    else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
+      char* end = nullptr;
+      passes = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != '\0' || passes < 1) bad_args = true;
+    } else bad_args = true;
   }
-  if (bad_args || (argc > 3 && frames <= 0)) {  // main.rs:9-12: usage line, normal return
-    std::printf("Usage: %s <config_file> <output_file>\n", argv[0]);
-    return 0;
-  }
+  auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
+  if (bad_args || (passes > 0 && (frames != 0 || orbit_given)) || (argc > 3 && passes == 0 && frames <= 0)) return usage();  // main.rs:9-12: usage line, normal return
   // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
   // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X
   // (tools/microbench/setup_costs.hip) — to move 80 KB of tables in and 2.9 MB of pixels out once.  With HSA_ENABLE_SDMA=0 the
@@ -327,6 +364,20 @@ int run(int argc, char** argv) {
   }
   RtScene* sc = rt_scene_get_mut(sf);
   if (const char* seed = std::getenv("RT_SEED")) sc->seed = std::strtoull(seed, nullptr, 0);
+  if (passes > 0) {
+    int status = 0;
+    const char* e = std::getenv("RT_GPUS");
+    if ((unsigned long)passes > sc->samples_per_pixel) status = usage();
+    else if (sc->n_gpus > 1 || (e && std::strtol(e, nullptr, 10) > 1)) {
+      std::fprintf(stderr, "--passes renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no progressive form)\n");
+      status = 101;
+    } else {
+      if (g_hip_init.joinable()) g_hip_init.join();
+      status = progressive(sf, argv[2], (uint32_t)passes);
+    }
+    rt_scene_free(sf);
+    return status;
+  }
   if (frames > 0) {
     if (g_hip_init.joinable()) g_hip_init.join();
     const int status = animate(sf, argv[2], frames, orbit_given ? orbit : 360.0 / frames);

@@ -53,6 +53,9 @@ def _bind(path, probes):
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_hip_set_camera.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4
     L.rt_hip_render_to_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.RtStats)]
+    L.rt_hip_accumulate.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.rt_hip_resolve.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_hip_refine_to_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_abi_sizeof.argtypes = [C.c_char_p]
     L.rt_abi_sizeof.restype = C.c_size_t
     L.rt_abi_version.restype = C.c_uint32
@@ -161,6 +164,26 @@ class HipScene:
         out = np.zeros((self.height, self.width, 3), np.uint8)
         st = abi.RtStats()
         _check(self._L.rt_hip_render_to_host(self._h, out.ctypes.data, C.byref(st)), self._L)
+        return out, st.as_dict()
+
+    def accumulate(self, d_accum, sample_begin, sample_count, tiles=None, stream=0):
+        """enqueue samples [sample_begin, sample_begin + sample_count) of every pixel of `tiles`, their exact fixed-point sums
+        ADDED to d_accum (a zeroed device buffer of rows x width x 3 uint64, 8-byte aligned; include/rt_abi.h); wait() reports it"""
+        _check(self._L.rt_hip_accumulate(self._h, C.byref(tiles) if tiles is not None else None, int(sample_begin), int(sample_count),
+                                         C.c_void_p(d_accum or None), C.c_void_p(stream or None)), self._L)
+
+    def resolve(self, d_accum, n_samples, d_rgb8, d_linear=0, tiles=None, stream=0):
+        """enqueue the resolve of d_accum holding n_samples samples per pixel into d_rgb8 / d_linear (either may be 0)"""
+        _check(self._L.rt_hip_resolve(self._h, C.byref(tiles) if tiles is not None else None, C.c_void_p(d_accum or None), int(n_samples),
+                                      C.c_void_p(d_rgb8 or None), C.c_void_p(d_linear or None), C.c_void_p(stream or None)), self._L)
+
+    def refine_to_host(self, sample_count):
+        """the next sample_count samples into the scene's own accumulator; the frame resolved over all it holds as a numpy
+        [h,w,3] array (blocking) + the pass's stats.  query("accum_samples") says how many samples per pixel it holds."""
+        import numpy as np
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        st = abi.RtStats()
+        _check(self._L.rt_hip_refine_to_host(self._h, int(sample_count), out.ctypes.data, C.byref(st)), self._L)
         return out, st.as_dict()
 
     def wait(self):
