@@ -28,6 +28,8 @@ def lib(abi):
                                        C.POINTER(abi.RtStats), C.c_int]
         L.rt_oracle_render_window.argtypes = [C.POINTER(abi.RtScene), C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.POINTER(abi.RtStats), C.c_int]
+        L.rt_oracle_accumulate.argtypes = [C.POINTER(abi.RtScene), C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.POINTER(abi.RtStats), C.c_int]
         L.rt_oracle_philox4x32_10.argtypes = [C.POINTER(C.c_uint32)] * 3
         L.rt_oracle_philox4x32_10.restype = None
         L.rt_oracle_sphere_hit.argtypes = [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
@@ -95,3 +97,20 @@ def render(abi, scene_ptr, tiles=None, n_threads=0, want_linear=True, x_range=No
     if rc != 0:
         raise RuntimeError(f"rt_oracle_render failed: {rc}")
     return rgb, lin, st.as_dict()
+
+
+def accumulate(abi, scene_ptr, begin, count, accum=None, tiles=None, x_range=None, n_threads=0):
+    """samples [begin, begin + count) of every pixel ADDED into accum by include/rt_abi.h's accumulator rule (rows x width x 3
+    uint64, packed like the RGB8 frame; None: a zeroed one) -> (accum, stats dict).  x_range = (x0, x1): only those pixels."""
+    sc = scene_ptr.contents
+    rows = abi.tiles_local_rows(sc.height, tiles)
+    if accum is None:
+        accum = np.zeros((rows, sc.width, 3), np.uint64)
+    assert accum.dtype == np.uint64 and accum.shape == (rows, sc.width, 3) and accum.flags.c_contiguous
+    st = abi.RtStats()
+    x0, x1 = x_range if x_range is not None else (0, sc.width)
+    rc = lib(abi).rt_oracle_accumulate(scene_ptr, C.byref(tiles) if tiles is not None else None, x0, x1, int(begin), int(count),
+                                       accum.ctypes.data, C.byref(st), n_threads)
+    if rc != 0:
+        raise RuntimeError(f"rt_oracle_accumulate failed: {rc}")
+    return accum, st.as_dict()

@@ -484,20 +484,26 @@ void rt_oracle_ray_color(const RtScene* scene, const double o[3], const double d
   out[0] = col.r; out[1] = col.g; out[2] = col.b;
 }
 
+/* raytracer.rs:197-202: sample s of pixel (x, y) — the camera jitter, get_ray and ray_color — with the RNG addressed by c->sample = s */
+static Rgb trace_sample(Ctx* c, uint32_t x, uint32_t y, uint32_t s) {
+  const RtScene* sc = c->scene;
+  const uint32_t w = sc->width, h = sc->height;
+  c->pixel = y * w + x;
+  c->sample = s;
+  uint32_t jw[4]; rng_words(c, NODE_CAMERA, 0, jw);
+  double u = ((double)x + u01_53(jw[0], jw[1])) / ((double)w - 1.0);                 /* :199 */
+  double v = ((double)h - ((double)y + u01_53(jw[2], jw[3]))) / ((double)h - 1.0);   /* :200 */
+  Ray r = camera_get_ray(sc, u, v);
+  return ray_color(c, r, sc->max_depth, sc->max_depth, 0, 0);
+}
+
 /* raytracer.rs:191-218 for pixels [x0, x1) of scanline y; out_row/out_lin are that row's 3*w bytes / floats */
 static void render_line(Ctx* c, uint32_t y, uint32_t x0, uint32_t x1, uint8_t* out_row, float* out_lin) {
   const RtScene* sc = c->scene;
-  const uint32_t w = sc->width, h = sc->height;
   for (uint32_t x = x0; x < x1; ++x) {
     float pixel_colors[3] = {0.0f, 0.0f, 0.0f};
-    c->pixel = y * w + x;
     for (uint32_t s = 0; s < sc->samples_per_pixel; ++s) {
-      c->sample = s;
-      uint32_t jw[4]; rng_words(c, NODE_CAMERA, 0, jw);
-      double u = ((double)x + u01_53(jw[0], jw[1])) / ((double)w - 1.0);                 /* :199 */
-      double v = ((double)h - ((double)y + u01_53(jw[2], jw[3]))) / ((double)h - 1.0);   /* :200 */
-      Ray r = camera_get_ray(sc, u, v);
-      Rgb col = ray_color(c, r, sc->max_depth, sc->max_depth, 0, 0);
+      Rgb col = trace_sample(c, x, y, s);
       pixel_colors[0] += col.r; pixel_colors[1] += col.g; pixel_colors[2] += col.b;
     }
     float scale = 1.0f / (float)sc->samples_per_pixel;
@@ -507,6 +513,31 @@ static void render_line(Ctx* c, uint32_t y, uint32_t x0, uint32_t x1, uint8_t* o
       if (out_row) out_row[3 * x + k] = rt_oracle_f32_to_u8(sqrtf(lin));                 /* :207-216 */
     }
   }
+}
+
+/* One sample into an accumulator word, by the rule of include/rt_abi.h (restated from its text, not from the kernel's code):
+ * a NaN channel adds 0 and sets bit 63; any other value is clamped to [0, 1] and floor(v * 2^40 + 0.5) is added to bits 0-62.
+ * Exact in f64: v is an f32 in [0, 1], 24 significant bits, so v * 2^40 is exact, below 2^41, and v * 2^40 + 0.5 needs at most
+ * 42 significant bits (its lowest at 2^-1): no rounding anywhere, and floor of it is the round-half-up integer. */
+#define ACCUM_FLAG (1ull << 63)
+static inline uint64_t accum_add(uint64_t word, float v) {
+  if (v != v) return word | ACCUM_FLAG;
+  double x = (double)v;
+  if (x < 0.0) x = 0.0;
+  if (x > 1.0) x = 1.0;
+  const uint64_t q = (uint64_t)floor(x * 1099511627776.0 + 0.5);
+  return (word & ACCUM_FLAG) | ((word & ~ACCUM_FLAG) + q);
+}
+
+/* samples [s0, s0 + n) of pixels [x0, x1) of scanline y added into that row's 3*w accumulator words */
+static void accumulate_line(Ctx* c, uint32_t y, uint32_t x0, uint32_t x1, uint32_t s0, uint32_t n, uint64_t* acc_row) {
+  for (uint32_t x = x0; x < x1; ++x)
+    for (uint32_t s = s0; s < s0 + n; ++s) {
+      Rgb col = trace_sample(c, x, y, s);
+      acc_row[3 * x + 0] = accum_add(acc_row[3 * x + 0], col.r);
+      acc_row[3 * x + 1] = accum_add(acc_row[3 * x + 1], col.g);
+      acc_row[3 * x + 2] = accum_add(acc_row[3 * x + 2], col.b);
+    }
 }
 
 int rt_oracle_threads(void) {
@@ -527,7 +558,7 @@ static double now_ms(void) {
  * asked for (the full-size parity tests compare single 4K rows at spp 1024).  Same pixels, same bits. */
 #define RT_ORACLE_XBLOCK 32u
 static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8, float* linear,
-                       RtStats* stats, int n_threads) {
+                       uint64_t* accum, uint32_t sample_begin, uint32_t sample_count, RtStats* stats, int n_threads) {
   if (!scene || scene->abi_version != RT_ABI_VERSION) return RT_ERR_INVALID;
   if (scene->width == 0 || scene->height == 0 || (scene->n_spheres && !scene->spheres)) return RT_ERR_INVALID;
   if (x1 > scene->width) x1 = scene->width;
@@ -553,14 +584,15 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
     c.scene = scene; c.lights = lights; c.n_lights = n_lights;
     uint32_t y = rt_tiles_global_row(tiles, lr);
     const uint32_t xa = x0 + xb * RT_ORACLE_XBLOCK, xe = xa + RT_ORACLE_XBLOCK < x1 ? xa + RT_ORACLE_XBLOCK : x1;
-    render_line(&c, y, xa, xe, rgb8 ? rgb8 + lr * row_elems : NULL, linear ? linear + lr * row_elems : NULL);
+    if (accum) accumulate_line(&c, y, xa, xe, sample_begin, sample_count, accum + lr * row_elems);
+    else render_line(&c, y, xa, xe, rgb8 ? rgb8 + lr * row_elems : NULL, linear ? linear + lr * row_elems : NULL);
     segments += c.segments; tex_oob += c.tex_oob; discarded += c.segments_discarded;
   }
   double t1 = now_ms();
   free(lights);
   if (stats) {
     memset(stats, 0, sizeof *stats);
-    stats->samples = (uint64_t)rows * (x1 - x0) * scene->samples_per_pixel;
+    stats->samples = (uint64_t)rows * (x1 - x0) * (accum ? sample_count : scene->samples_per_pixel);
     stats->segments = segments;
     stats->sphere_tests = segments * scene->n_spheres;
     stats->exact_tests = segments * scene->n_spheres;
@@ -575,10 +607,16 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
 }
 int rt_oracle_render(const RtScene* scene, const RtRowTiles* tiles, uint8_t* rgb8, float* linear,
                      RtStats* stats, int n_threads) {
-  return render_rows(scene, tiles, 0, scene ? scene->width : 0, rgb8, linear, stats, n_threads);
+  return render_rows(scene, tiles, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, stats, n_threads);
 }
 /* pixels [x0, x1) of the selected rows only; the buffers still hold whole rows (other pixels untouched) */
 int rt_oracle_render_window(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8,
                             float* linear, RtStats* stats, int n_threads) {
-  return render_rows(scene, tiles, x0, x1, rgb8, linear, stats, n_threads);
+  return render_rows(scene, tiles, x0, x1, rgb8, linear, NULL, 0, 0, stats, n_threads);
+}
+/* samples [sample_begin, sample_begin + sample_count) of pixels [x0, x1) of the selected rows ADDED into accum */
+int rt_oracle_accumulate(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
+                         uint32_t sample_count, uint64_t* accum, RtStats* stats, int n_threads) {
+  if (!accum || (uint64_t)sample_begin + sample_count > 0xFFFFFFFFull) return RT_ERR_INVALID;
+  return render_rows(scene, tiles, x0, x1, NULL, NULL, accum, sample_begin, sample_count, stats, n_threads);
 }

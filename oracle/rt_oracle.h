@@ -40,6 +40,12 @@ int rt_oracle_render(const RtScene* scene, const RtRowTiles* tiles, uint8_t* rgb
 /* the same for pixels [x0, x1) of those rows only (buffers still hold whole rows; other pixels are left untouched) */
 int rt_oracle_render_window(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8,
                             float* linear, RtStats* stats, int n_threads);
+/* Progressive rendering restated from include/rt_abi.h: samples [sample_begin, sample_begin + sample_count) of pixels [x0, x1) of
+ * the selected rows (render_line's camera jitter, get_ray and ray_color with the RNG at sample index s), each ADDED to `accum`
+ * (rt_tiles_local_rows()*width*3 u64, packed like rgb8) by the ABI's rule: a NaN channel sets bit 63, any other value is
+ * clamped to [0, 1] and floor(v * 2^40 + 0.5) is added.  Other words are left untouched.  stats: as rt_oracle_render's. */
+int rt_oracle_accumulate(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
+                         uint32_t sample_count, uint64_t* accum, RtStats* stats, int n_threads);
 int rt_oracle_threads(void);
 
 /* ---- hooks for the reference's known-answer tests ---- */

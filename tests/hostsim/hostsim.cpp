@@ -259,6 +259,19 @@ extern "C" void hostsim_sample_to_fixed(const float* v, uint64_t* out, uint64_t 
   for (int64_t i = 0; i < (int64_t)n; ++i) out[i] = sample_to_fixed(v[i]);
 }
 
+// rt_resolve (rt_kernel.hip) on the CPU: an accumulator of n_px pixels x 3 words holding n samples per pixel -> linear f32 and
+// RGB8 (either may be NULL) through rt_core.h's fixed_to_mean, rt_nanf and f32_to_u8 of the sqrt, in the tile flush's order
+extern "C" void hostsim_resolve(const uint64_t* accum, uint32_t n, uint64_t n_px, uint8_t* rgb8, float* lin) {
+#pragma omp parallel for
+  for (int64_t e = 0; e < (int64_t)(n_px * 3u); ++e) {
+    const unsigned long long v = accum[e];
+    float l = fixed_to_mean(v & ~ACCUM_NAN_BIT, n);
+    if (v & ACCUM_NAN_BIT) l = rt_nanf();
+    if (lin) lin[e] = l;
+    if (rgb8) rgb8[e] = f32_to_u8(sqrtf(l));
+  }
+}
+
 // rt_core.h rt_div255f over an array (property test against the IEEE quotient x / 255.0f)
 extern "C" void hostsim_div255(const float* x, float* out, uint64_t n) {
 #pragma omp parallel for
