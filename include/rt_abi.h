@@ -303,6 +303,46 @@ int rt_hip_resolve(RtHipScene*, const RtRowTiles* tiles, const void* d_accum, ui
  * allocated at first use and starts over after rt_hip_set_camera, rt_hip_set_option "max_depth" / "seed" / "accum_reset";
  * rt_hip_scene_query "accum_samples" says how many samples per pixel it holds.  stats: the pass's kernel. */
 int rt_hip_refine_to_host(RtHipScene*, uint32_t sample_count, uint8_t* out_rgb8, RtStats* stats);
+/* Adaptive sampling: per-tile sample counts, samples spent where the image is still noisy.  The TILES are the
+ * accumulating kernels' own pixel tiles for the scene's options and `tiles`: rt_hip_tile_grid writes {tile width, tile height,
+ * tiles_x, tiles_y}; tile id = ty * tiles_x + tx over the packed local rows (edge tiles are cut by the frame).  A tile holding
+ * n_t samples [0, n_t) resolves, pixel for pixel, to the frame rt_hip_render makes at samples_per_pixel = n_t, bit for bit.
+ *
+ * rt_hip_accumulate_tiles: rt_hip_accumulate for just the n_list tiles of d_tile_list (device u32 ids, 4-byte aligned), whose words
+ * alone change.  Ids must be distinct (two entries of one tile race in the flush); ids at or above the tile count are skipped.
+ * n_list 0, a NULL list or n_list above the tile count: RT_ERR_INVALID, and no work is enqueued.  Leaves the scene's learned queue
+ * order alone.  rt_hip_wait reports it; its `samples` counts n_list whole tiles.
+ *
+ * rt_hip_tile_error: the noise estimate of the listed tiles into d_tile_err[id] (f64, one per tile of the grid; only listed ids in
+ * the grid are written).  d_now holds samples [0, n_now), d_prev the first n_prev of them (0 < n_prev < n_now, else RT_ERR_INVALID),
+ * so A = prev and B = now - prev are disjoint halves.  Per pixel inside the frame none of whose six words has bit 63 set, in IEEE
+ * f64, in exactly this order: a_c = P_c / (n_prev * 2^40), b_c = (Q_c - P_c) / ((n_now - n_prev) * 2^40),
+ * d = (|a_0 - b_0| + |a_1 - b_1|) + |a_2 - b_2|, s = ((a_0 + b_0) + (a_1 + b_1)) + (a_2 + b_2), e = d / (1e-4 + sqrt(0.5 * s));
+ * the tile's error is the max of e, 0.0 if no pixel counts.  Guidance, not contract: for a grey pixel e is about 1.15 x the sum
+ * over channels of the two halves' gap in the PNG's sqrt space (full scale 1.0), so an error of 0.0136 is about one 8-bit level
+ * per channel.  Asynchronous, not reported by rt_hip_wait.
+ *
+ * rt_hip_resolve_tiles: rt_hip_resolve with each pixel divided by its tile's count d_tile_spp[id] (device u32, tiles_x*tiles_y
+ * entries, each 1 .. 2^23 - 1; other counts give unspecified pixels).
+ *
+ * rt_hip_render_adaptive_to_host: one whole adaptive frame, blocking.  N = samples_per_pixel, M = min(min_spp, N).  Round 0
+ * renders [0, M/2) and [M/2, M) into every tile with an estimate between them; after the round that brought the tiles to n, a tile
+ * goes on iff n < N and its error >= threshold, and the next round adds min(n, N - n) samples to every tile that goes on.
+ * threshold 0: every tile reaches N (the one-shot frame); M < 2: the one-shot frame, every count N.  Deterministic.  RGB8 to
+ * out_rgb8 (width*height*3), counts to out_tile_spp (tiles_y*tiles_x, may be NULL).  A NaN, negative or infinite threshold, or
+ * min_spp 0: RT_ERR_INVALID; N above 2^23 - 1: RT_ERR_UNSUPPORTED.  Its own accumulators (2 x width*height*24 bytes) and per-tile
+ * arrays are allocated at first use and freed with the scene; the progressive accumulator is untouched.  stats: samples = the sum
+ * of pixels x n_t, counters and kernel_ms summed over the rounds' megakernel launches, frame_ms = the whole call.
+ * rt_hip_scene_query "adaptive_rounds" and "adaptive_round_tiles_<i>" / "adaptive_round_spp_<i>" / "adaptive_round_kernel_us_<i>"
+ * describe the last such frame's rounds (-1 past the last). */
+int rt_hip_tile_grid(const RtHipScene*, const RtRowTiles* tiles, uint32_t out[4]);
+int rt_hip_accumulate_tiles(RtHipScene*, const RtRowTiles* tiles, const uint32_t* d_tile_list, uint32_t n_list, uint32_t sample_begin,
+                            uint32_t sample_count, void* d_accum, void* stream);
+int rt_hip_tile_error(RtHipScene*, const RtRowTiles* tiles, const uint32_t* d_tile_list, uint32_t n_list, const void* d_now, uint32_t n_now,
+                      const void* d_prev, uint32_t n_prev, double* d_tile_err, void* stream);
+int rt_hip_resolve_tiles(RtHipScene*, const RtRowTiles* tiles, const void* d_accum, const uint32_t* d_tile_spp, void* d_rgb8, void* d_linear,
+                         void* stream);
+int rt_hip_render_adaptive_to_host(RtHipScene*, double threshold, uint32_t min_spp, uint8_t* out_rgb8, uint32_t* out_tile_spp, RtStats* stats);
 /* A frame over the GPUs of one node, scene resident (the parallel loop of raytracer.rs:254-262 spread over devices;
  * animation: README.md:43-57).  n_gpus = 0 takes scene->n_gpus, then RT_GPUS, then 1.  Each rank renders
  * interleaved 2-scanline tiles (RtRowTiles{2, r, G}) on its own host thread and stream; ONE gather per frame

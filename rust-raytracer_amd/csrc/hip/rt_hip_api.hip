@@ -4,8 +4,11 @@
 // path in this library: without a gfx950 device every call fails with RT_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <mutex>
 #include <cstring>
 #include <string>
@@ -150,6 +153,12 @@ struct RtHipScene {
   uint32_t accum_samples = 0;
   bool accum_zero = true;
   void reset_accum() { accum_samples = 0; accum_zero = true; }
+  // adaptive frames, host form (rt_hip_render_adaptive_to_host): its own now / prev accumulators and per-tile list, errors and
+  // counts (allocated at first use), and what each round of the last frame did: {tiles, samples per pixel after it, kernel ms}
+  unsigned long long* d_ad_now = nullptr; unsigned long long* d_ad_prev = nullptr; size_t ad_bytes = 0;
+  uint32_t* d_ad_list = nullptr; double* d_ad_err = nullptr; uint32_t* d_ad_spp = nullptr; size_t ad_tiles = 0;
+  struct AdRound { uint32_t tiles, spp; double kernel_ms; };
+  std::vector<AdRound> ad_rounds;
   Slot& last_slot() { return slot[(n_launches + 1) & 1]; }  // the slot of the most recent launch
 };
 constexpr uint32_t RT_SLOT_COUNTERS = 32;  // segments, exact tests, tex_oob, grid steps, 4 x wave trip counts, 8 x section cycles, profile clocks, (the tile-queue cursors,) [28] repeated segments
@@ -215,7 +224,8 @@ extern "C" void rt_hip_scene_destroy(RtHipScene* s) {
     for (void* p : {s->d_geom, s->d_mat, s->d_lights, s->d_tex, s->d_sky, s->d_tex4, s->d_sky4, s->d_matc, s->d_cell_word, s->d_cell_items, s->d_large,
                     s->d_all, s->d_large_geom})
       if (p) (void)hipFree(p);
-  for (void* p : {(void*)s->d_counters, s->d_frame, (void*)s->d_tile_depth, (void*)s->d_tile_order, s->d_light_overflow, (void*)s->d_accum})
+  for (void* p : {(void*)s->d_counters, s->d_frame, (void*)s->d_tile_depth, (void*)s->d_tile_order, s->d_light_overflow, (void*)s->d_accum,
+                  (void*)s->d_ad_now, (void*)s->d_ad_prev, (void*)s->d_ad_list, (void*)s->d_ad_err, (void*)s->d_ad_spp})
     if (p) (void)hipFree(p);
   for (auto& sl : s->slot) {
     for (hipEvent_t e : {sl.ev_start, sl.ev_stop, sl.ev_copied}) if (e) (void)hipEventDestroy(e);
@@ -538,11 +548,48 @@ int warm_up(RtHipScene* s) {
 }  // namespace
 
 namespace {
+// The pixel tiles of a launch over local_rows packed rows: the unit of the megakernel's queue, of list launches, of the adaptive
+// frame's sample counts (rt_hip_tile_grid) and of rt_tile_error.  Tile id = ty * tiles_x + tx.
+struct TileGeom { uint32_t tile_log2 = 0, tile_wl = 0, tile_hl = 0, tiles_x = 0, tiles_y = 0; };
+int tile_geometry(const RtHipScene* s, uint32_t local_rows, TileGeom* out) {
+  // Pixel tile: the unit of the global queue, owned by ONE workgroup.  8x8 when the frame has
+  // >= ~100 tiles per workgroup; small frames (and the 1/8 shards of the multi-GPU run) use 4x4,
+  // 2x2 or 1x1 tiles, so that the heaviest tile (glass: 10x the mean) is a small part of a
+  // workgroup's share and the long-path regions spread over many workgroups.
+  const uint64_t want_tiles = (uint64_t)s->num_cus * 100u;
+  // tile geometry: 4^tl pixels, as a square (default) or a run of one scanline
+  // (shape 0: 2^t x 2^t; 1: 4^t x 1; 2 and 3: the square widened / flattened once or twice, 16x4 and 32x2 at t = 3)
+  // (default shape: squares — but the 2x2 tiles of a small frame / a multi-GPU shard as 4x1 strips: 12 contiguous bytes
+  //  leave in one packed store instead of two rows of byte stores; same time, WRITE_SIZE 2.71 -> 2.17 MB on an 1/8 shard
+  //  of the headline frame, profiles/r03_run10_shape_traffic_sweep.log)
+  // (shape 2 at t = 1 is the 2x2 square — the A/B arm of the 4x1 default, which no other value selects)
+  auto widen = [&](uint32_t t) { const uint32_t k = s->tile_shape == 0 ? (t == 1u ? 1u : 0u) : (s->tile_shape == 1 ? t : (s->tile_shape == 2 && t == 1u ? 0u : (uint32_t)s->tile_shape - 1u)); return k < t ? k : t; };
+  auto tiles_xy = [&](uint32_t t, uint32_t& tx, uint32_t& ty) {
+    const uint32_t wl = t + widen(t), hl = t - widen(t);
+    tx = (s->host.width + (1u << wl) - 1) >> wl; ty = (local_rows + (1u << hl) - 1) >> hl;
+  };
+  uint32_t tl = s->tile_log2 < 0 ? 3u : (uint32_t)s->tile_log2, tx = 0, ty = 0;
+  if (s->tile_log2 < 0) {
+    for (;;) { tiles_xy(tl, tx, ty); if (tl == 0 || (uint64_t)tx * ty >= want_tiles) break; tl--; }
+  }
+  // a slot header packs (tile column | tile row << 16), and the queue cursor is 32 bits
+  auto too_many = [&](uint32_t t) { tiles_xy(t, tx, ty); return tx > 65535u || ty > 65535u || (uint64_t)tx * ty >= (1ull << 31); };
+  while (tl < 3 && too_many(tl)) tl++;
+  if (too_many(tl)) return fail(RT_ERR_UNSUPPORTED, "frame too large for the tile queue (more than 65535 tiles on an axis or 2^31 tiles)");
+  out->tile_log2 = tl; out->tile_wl = tl + widen(tl); out->tile_hl = tl - widen(tl);
+  out->tiles_x = tx; out->tiles_y = ty;
+  return RT_OK;
+}
+}  // namespace
+
+namespace {
 // One launch of the megakernel over the given row tiles: samples [sample_base, sample_base + spp) of every pixel.  accum == nullptr:
 // the one-shot frame (rt_hip_render: sample_base 0, the scene's samples per pixel, pixels into d_rgb8 / d_linear); else the
-// accumulating kernels add the pass's sums to accum (rt_hip_accumulate).  The caller has checked its own arguments.
+// accumulating kernels add the pass's sums to accum (rt_hip_accumulate).  list != nullptr (accumulating only): just the n_list
+// tiles it names, in its order (rt_hip_accumulate_tiles); such a launch neither reads nor changes the scene's learned queue order,
+// and `samples` counts n_list whole tiles.  The caller has checked its own arguments.
 int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_linear, unsigned long long* accum, uint32_t sample_base,
-                 uint32_t spp, void* stream_) {
+                 uint32_t spp, void* stream_, const uint32_t* list = nullptr, uint32_t n_list = 0) {
   const uint32_t local_rows = rt_tiles_local_rows(s->host.height, tiles);
   hipStream_t stream = (hipStream_t)stream_;
   const bool has_lights = s->has_lights || s->force_lit != 0;
@@ -592,36 +639,17 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   const bool tiled = tiles && tiles->tile_rows && tiles->tile_stride;
   ka.tile_rows = tiled ? tiles->tile_rows : 0; ka.first_tile = tiled ? tiles->first_tile : 0;
   ka.tile_stride = tiled ? tiles->tile_stride : 0;
-  // Pixel tile: the unit of the global queue, owned by ONE workgroup.  8x8 when the frame has
-  // >= ~100 tiles per workgroup; small frames (and the 1/8 shards of the multi-GPU run) use 4x4,
-  // 2x2 or 1x1 tiles, so that the heaviest tile (glass: 10x the mean) is a small part of a
-  // workgroup's share and the long-path regions spread over many workgroups.
-  const uint64_t want_tiles = (uint64_t)s->num_cus * 100u;
-  // tile geometry: 4^tl pixels, as a square (default) or a run of one scanline
-  // (shape 0: 2^t x 2^t; 1: 4^t x 1; 2 and 3: the square widened / flattened once or twice, 16x4 and 32x2 at t = 3)
-  // (default shape: squares — but the 2x2 tiles of a small frame / a multi-GPU shard as 4x1 strips: 12 contiguous bytes
-  //  leave in one packed store instead of two rows of byte stores; same time, WRITE_SIZE 2.71 -> 2.17 MB on an 1/8 shard
-  //  of the headline frame, profiles/r03_run10_shape_traffic_sweep.log)
-  // (shape 2 at t = 1 is the 2x2 square — the A/B arm of the 4x1 default, which no other value selects)
-  auto widen = [&](uint32_t t) { const uint32_t k = s->tile_shape == 0 ? (t == 1u ? 1u : 0u) : (s->tile_shape == 1 ? t : (s->tile_shape == 2 && t == 1u ? 0u : (uint32_t)s->tile_shape - 1u)); return k < t ? k : t; };
-  auto tiles_xy = [&](uint32_t t, uint32_t& tx, uint32_t& ty) {
-    const uint32_t wl = t + widen(t), hl = t - widen(t);
-    tx = (s->host.width + (1u << wl) - 1) >> wl; ty = (local_rows + (1u << hl) - 1) >> hl;
-  };
-  uint32_t tl = (uint32_t)s->tile_log2, tx = 0, ty = 0;
-  if (s->tile_log2 < 0) {
-    tl = 3;
-    for (;;) { tiles_xy(tl, tx, ty); if (tl == 0 || (uint64_t)tx * ty >= want_tiles) break; tl--; }
-  }
-  // a slot header packs (tile column | tile row << 16), and the queue cursor is 32 bits
-  auto too_many = [&](uint32_t t) { tiles_xy(t, tx, ty); return tx > 65535u || ty > 65535u || (uint64_t)tx * ty >= (1ull << 31); };
-  while (tl < 3 && too_many(tl)) tl++;
-  if (too_many(tl)) return fail(RT_ERR_UNSUPPORTED, "frame too large for the tile queue (more than 65535 tiles on an axis or 2^31 tiles)");
+  TileGeom tg;
+  { const int rc_geom = tile_geometry(s, local_rows, &tg); if (rc_geom != RT_OK) return rc_geom; }
+  const uint32_t tl = tg.tile_log2;
   ka.tile_log2 = tl;
-  ka.tile_wl = tl + widen(tl); ka.tile_hl = tl - widen(tl);
+  ka.tile_wl = tg.tile_wl; ka.tile_hl = tg.tile_hl;
   ka.t_slots = rtk::tile_slots(tl);
-  ka.tiles_x = tx; s->last_tiles_x = tx;
-  ka.n_tiles = tx * ty;
+  ka.tiles_x = tg.tiles_x; s->last_tiles_x = tg.tiles_x;
+  ka.n_tiles = tg.tiles_x * tg.tiles_y;
+  // a list launch (rt_hip_accumulate_tiles): its queue is the list, mapped to tiles through tile_order
+  ka.n_queue = list ? n_list : ka.n_tiles;
+  if (list) sl.samples = ((uint64_t)n_list << (2u * tl)) * spp;
   // A tile's samples are handed out to the waves of its workgroup in chunks: an item's latency
   // is what the last wave of a frame waits for, but below ~128 samples per item the acquire /
   // finish overhead shows (measured, profiles/r01_run4_tiles.log): 8x8 -> 8 samples per pixel,
@@ -632,7 +660,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   if (chunk_spp == 0) {
     static const uint32_t by_tile[4] = {128u, 32u, 16u, 8u};
     const uint64_t target_items = (uint64_t)s->num_cus * rtk::WAVES * 60u;
-    const uint64_t ideal = ((uint64_t)ka.n_tiles * spp + target_items / 2) / target_items;  // samples per pixel and item
+    const uint64_t ideal = ((uint64_t)ka.n_queue * spp + target_items / 2) / target_items;  // samples per pixel and item (of the tiles queued)
     uint32_t c = 1;
     while ((uint64_t)c * 3u < ideal * 2u) c <<= 1;  // nearest power of two (geometric)
     // (1x1 and 4-pixel tiles never go below their base of 128 samples per item: the 1/8 shard of the headline frame runs 1.678 ms
@@ -644,7 +672,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   if (chunk_spp > spp || spp == 0) chunk_spp = spp ? spp : 1;
   ka.chunk_spp = chunk_spp;
   ka.n_chunks = spp ? (spp + chunk_spp - 1) / chunk_spp : 1;
-  const uint32_t n_items = ka.n_tiles * ka.n_chunks;
+  const uint32_t n_items = ka.n_queue * ka.n_chunks;
   // Tiles a workgroup takes from the frame's queue per atomic (rt_kernel.hip: wg_stash), at most, and the taper towards
   // single tiles at the end of the frame: remaining tiles / (workgroups x 16).  Measured (profiles/r03_run26_batch_sweep.log):
   // what counts is that ONE wave of a workgroup asks the queue at a time (cover frame at spp 8 / 32 / 128: 1.49 -> 1.15,
@@ -686,7 +714,8 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
     // on for frames of at least 2^19 pixels (the headline frame: 0.96 M; its 1/2 ... 1/8 shards and the 800x600 test scene are
     // below and lose 6 - 15 % to the coarser balance, profiles/r03_run8_shard_affinity_sweep.log) with at least 8 runs
     const bool big = (uint64_t)local_rows * s->host.width >= (1ull << 19);
-    if ((s->tile_affinity == 1 && big && n_groups >= 8u) || (s->tile_affinity == 2 && n_groups >= 8u)) {
+    // (list launches: off — their queue is the caller's list, not the frame's runs; DESIGN.md §11 has the A/B)
+    if (!list && ((s->tile_affinity == 1 && big && n_groups >= 8u) || (s->tile_affinity == 2 && n_groups >= 8u))) {
       ka.aff_group_log2 = gl;
       for (uint32_t g = 0; g < 8u && g < n_groups; ++g) {  // groups g, g + 8, ...: all full but possibly the frame's last
         const uint32_t mine = (n_groups - 1u - g) / 8u + 1u;
@@ -697,7 +726,10 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
       for (int x = 1; x < 8; ++x) ka.xcd_off[x] = ka.xcd_off[x - 1] + ka.xcd_cnt[x - 1];
     }
   }
-  if (s->order_mode >= 2) {
+  if (list) {  // the list is the queue, in the caller's order; no depths are measured
+    ka.order_mode = 1u;
+    ka.tile_order = list;
+  } else if (s->order_mode >= 2) {
     RtHipScene::OrderKey key;
     key.n_tiles = ka.n_tiles; key.tile_log2 = tl; key.tile_shape = (uint32_t)s->tile_shape; key.aff_group_log2 = ka.aff_group_log2;
     key.tile_rows = ka.tile_rows; key.first_tile = ka.first_tile; key.tile_stride = ka.tile_stride; key.local_rows = local_rows;
@@ -785,7 +817,82 @@ extern "C" int rt_hip_resolve(RtHipScene* s, const RtRowTiles* tiles, const void
   const uint64_t blocks = ((n_px + 3u) / 4u + 255u) / 256u;
   if (blocks > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "frame too large to resolve");
   hipLaunchKernelGGL(rtk::rt_resolve, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_accum, n_samples, n_px,
-                     (uint8_t*)d_rgb8, (float*)d_linear);
+                     (uint8_t*)d_rgb8, (float*)d_linear, (const uint32_t*)nullptr, 0u, 0u, 0u, 0u);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// Adaptive sampling: per-tile sample counts over the accumulating kernels' own pixel tiles.
+namespace {
+// the tiles of `tiles`' packed rows; n_list must name 1 .. tile count tiles
+int check_list(const RtHipScene* s, const RtRowTiles* tiles, const uint32_t* d_list, uint32_t n_list, TileGeom* tg) {
+  if (!d_list || n_list == 0) return fail(RT_ERR_INVALID, "the tile list must name at least one tile");
+  if (reinterpret_cast<uintptr_t>(d_list) & 3u) return fail(RT_ERR_INVALID, "the tile list must be 4-byte aligned");
+  const int rc = tile_geometry(s, rt_tiles_local_rows(s->host.height, tiles), tg);
+  if (rc != RT_OK) return rc;
+  if ((uint64_t)n_list > (uint64_t)tg->tiles_x * tg->tiles_y) return fail(RT_ERR_INVALID, "the tile list is longer than the frame has tiles");
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_hip_tile_grid(const RtHipScene* s, const RtRowTiles* tiles, uint32_t out[4]) {
+  if (!s || !out) return fail(RT_ERR_INVALID, "null argument");
+  TileGeom tg;
+  const int rc = tile_geometry(s, rt_tiles_local_rows(s->host.height, tiles), &tg);
+  if (rc != RT_OK) return rc;
+  out[0] = 1u << tg.tile_wl; out[1] = 1u << tg.tile_hl; out[2] = tg.tiles_x; out[3] = tg.tiles_y;
+  return RT_OK;
+}
+
+extern "C" int rt_hip_accumulate_tiles(RtHipScene* s, const RtRowTiles* tiles, const uint32_t* d_tile_list, uint32_t n_list, uint32_t sample_begin,
+                                       uint32_t sample_count, void* d_accum, void* stream) {
+  int rc = check_accum(s, tiles, d_accum);
+  if (rc != RT_OK) return rc;
+  TileGeom tg;
+  if ((rc = check_list(s, tiles, d_tile_list, n_list, &tg)) != RT_OK) return rc;
+  if (!d_accum) return fail(RT_ERR_INVALID, "null accumulator");
+  if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
+  if ((uint64_t)sample_begin + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  return launch_frame(s, tiles, nullptr, nullptr, (unsigned long long*)d_accum, sample_begin, sample_count, stream, d_tile_list, n_list);
+}
+
+extern "C" int rt_hip_tile_error(RtHipScene* s, const RtRowTiles* tiles, const uint32_t* d_tile_list, uint32_t n_list, const void* d_now, uint32_t n_now,
+                                 const void* d_prev, uint32_t n_prev, double* d_tile_err, void* stream) {
+  if (!s || !d_now || !d_prev || !d_tile_err) return fail(RT_ERR_INVALID, "null argument");
+  TileGeom tg;
+  int rc = check_list(s, tiles, d_tile_list, n_list, &tg);
+  if (rc != RT_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(d_now) | reinterpret_cast<uintptr_t>(d_prev) | reinterpret_cast<uintptr_t>(d_tile_err)) & 7u)
+    return fail(RT_ERR_INVALID, "accumulators and the error array must be 8-byte aligned");
+  if (n_prev == 0 || n_now <= n_prev) return fail(RT_ERR_INVALID, "the counts must satisfy 0 < n_prev < n_now");
+  if (n_now > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const uint64_t threads = (uint64_t)n_list << (2u * tg.tile_log2), blocks = (threads + 255u) / 256u;
+  hipLaunchKernelGGL(rtk::rt_tile_error, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_now, n_now,
+                     (const unsigned long long*)d_prev, n_prev, d_tile_list, n_list, tg.tile_log2, tg.tile_wl, tg.tile_hl, tg.tiles_x,
+                     tg.tiles_x * tg.tiles_y, s->host.width, rt_tiles_local_rows(s->host.height, tiles), d_tile_err);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+extern "C" int rt_hip_resolve_tiles(RtHipScene* s, const RtRowTiles* tiles, const void* d_accum, const uint32_t* d_tile_spp, void* d_rgb8, void* d_linear,
+                                    void* stream) {
+  int rc = check_accum(s, tiles, d_accum);
+  if (rc != RT_OK) return rc;
+  const uint32_t rows = rt_tiles_local_rows(s->host.height, tiles);
+  if (rows == 0) return RT_OK;
+  if (!d_tile_spp) return fail(RT_ERR_INVALID, "null tile counts");
+  if (reinterpret_cast<uintptr_t>(d_tile_spp) & 3u) return fail(RT_ERR_INVALID, "the tile counts must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  TileGeom tg;
+  if ((rc = tile_geometry(s, rows, &tg)) != RT_OK) return rc;
+  const uint64_t n_px = (uint64_t)rows * s->host.width;
+  if (!d_rgb8 && !d_linear) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const uint64_t blocks = ((n_px + 3u) / 4u + 255u) / 256u;
+  if (blocks > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "frame too large to resolve");
+  hipLaunchKernelGGL(rtk::rt_resolve, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_accum, 1u, n_px,
+                     (uint8_t*)d_rgb8, (float*)d_linear, d_tile_spp, s->host.width, tg.tiles_x, tg.tile_wl, tg.tile_hl);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -876,7 +983,17 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;  // samples per pixel in the scene's accumulator (rt_hip_refine_to_host)
+  if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
+  // the last rt_hip_render_adaptive_to_host: its rounds, and round i's tiles, samples per pixel after it, kernel time in microseconds
+  if (!std::strcmp(key, "adaptive_rounds")) return (int64_t)s->ad_rounds.size();
+  for (const char* f : {"adaptive_round_tiles_", "adaptive_round_spp_", "adaptive_round_kernel_us_"}) {
+    const size_t l = std::strlen(f);
+    if (std::strncmp(key, f, l) != 0 || key[l] < '0' || key[l] > '9') continue;
+    const unsigned long i = std::strtoul(key + l, nullptr, 10);
+    if (i >= s->ad_rounds.size()) return -1;
+    const RtHipScene::AdRound& r = s->ad_rounds[i];
+    return f[15] == 't' ? (int64_t)r.tiles : (f[15] == 's' ? (int64_t)r.spp : (int64_t)std::llround(r.kernel_ms * 1000.0));
+  }  // samples per pixel in the scene's accumulator (rt_hip_refine_to_host)
   if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->grid.n_cells * (s->grid.wide ? 16u : 8u) + (size_t)s->grid.n_items * (s->grid.wide ? 4u : 2u));
   return -1;
 }
@@ -961,6 +1078,121 @@ extern "C" int rt_hip_refine_to_host(RtHipScene* s, uint32_t sample_count, uint8
   if (stats) {
     *stats = st;
     stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return RT_OK;
+}
+
+// Adaptive sampling, host form, blocking, on the NULL stream like rt_hip_render_to_host.  M = min(min_spp, N):
+// round 0 renders [0, M/2) and [M/2, M) into every tile with a snapshot between them; after a round that brought its tiles to n,
+// a tile goes on iff n < N and its error >= threshold, and the next round adds min(n, N - n) samples to every tile that goes on.
+// Every pixel is the one-shot frame at its tile's count.  M < 2: the one-shot frame.
+extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, uint32_t min_spp, uint8_t* out_rgb8, uint32_t* out_tile_spp,
+                                              RtStats* stats) {
+  if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
+  if (!(threshold >= 0.0) || std::isinf(threshold)) return fail(RT_ERR_INVALID, "the threshold must be finite and at least 0");
+  if (min_spp == 0) return fail(RT_ERR_INVALID, "min_spp must be at least 1");
+  const uint32_t N = s->host.samples_per_pixel;
+  if (N > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an adaptive frame holds at most 2^23 - 1 samples per pixel");
+  auto t0 = std::chrono::steady_clock::now();
+  RT_HIP_TRY(hipSetDevice(s->device));
+  TileGeom tg;
+  int rc = tile_geometry(s, s->host.height, &tg);
+  if (rc != RT_OK) return rc;
+  const uint32_t nt = tg.tiles_x * tg.tiles_y, M = min_spp < N ? min_spp : N;
+  s->ad_rounds.clear();
+  if (M < 2) {  // (no estimate can be made: every tile at N)
+    RtStats st;
+    if ((rc = rt_hip_render_to_host(s, out_rgb8, &st)) != RT_OK) return rc;
+    s->ad_rounds.push_back({nt, N, st.kernel_ms});
+    if (out_tile_spp) std::fill(out_tile_spp, out_tile_spp + nt, N);
+    if (stats) { *stats = st; stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    return RT_OK;
+  }
+  const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 24;
+  if (bytes > s->ad_bytes) {
+    RT_HIP_TRY(hipDeviceSynchronize());
+    for (unsigned long long** p : {&s->d_ad_now, &s->d_ad_prev}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    s->ad_bytes = 0;
+    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_now, bytes));
+    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_prev, bytes));
+    s->ad_bytes = bytes;
+  }
+  if (nt > s->ad_tiles) {
+    RT_HIP_TRY(hipDeviceSynchronize());
+    for (void* p : {(void*)s->d_ad_list, (void*)s->d_ad_err, (void*)s->d_ad_spp}) if (p) (void)hipFree(p);
+    s->d_ad_list = nullptr; s->d_ad_err = nullptr; s->d_ad_spp = nullptr; s->ad_tiles = 0;
+    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_list, (size_t)nt * 4));
+    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_err, (size_t)nt * 8));
+    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_spp, (size_t)nt * 4));
+    s->ad_tiles = nt;
+  }
+  if (px * 3 > s->frame_bytes) {
+    if (s->d_frame) { (void)hipFree(s->d_frame); s->d_frame = nullptr; s->frame_bytes = 0; }
+    RT_HIP_TRY(hipMalloc(&s->d_frame, px * 3));
+    s->frame_bytes = px * 3;
+  }
+  RtStats total;
+  std::memset(&total, 0, sizeof total);
+  total.n_gpus_used = 1;
+  double round_ms = 0.0;
+  auto collect = [&]() -> int {  // the launch just enqueued: wait for it, add its figures to the frame's
+    RtStats st;
+    const int rc = rt_hip_wait(s, &st);
+    if (rc != RT_OK) return rc;
+    total.segments += st.segments; total.sphere_tests += st.sphere_tests; total.exact_tests += st.exact_tests;
+    total.tex_oob += st.tex_oob; total.grid_steps += st.grid_steps;
+    for (int k = 0; k < 4; ++k) total.wave_iters[k] += st.wave_iters[k];
+    for (int k = 0; k < 12; ++k) total.prof_cycles[k] += st.prof_cycles[k];
+    const uint64_t rep = (uint64_t)total.segments_repeated + st.segments_repeated;
+    total.segments_repeated = rep > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)rep;
+    total.kernel_ms += st.kernel_ms; round_ms += st.kernel_ms;
+    return RT_OK;
+  };
+  std::vector<uint32_t> n_t(nt, M), list(nt);
+  std::vector<double> err(nt, 0.0);
+  for (uint32_t t = 0; t < nt; ++t) list[t] = nt - 1u - t;  // (bottom of the image first, the kernel's own default order)
+  // round 0: every tile, two halves, the estimate between them
+  const uint32_t h = M / 2u;
+  RT_HIP_TRY(hipMemsetAsync(s->d_ad_now, 0, bytes, nullptr));
+  if ((rc = rt_hip_accumulate(s, nullptr, 0u, h, s->d_ad_now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpyAsync(s->d_ad_prev, s->d_ad_now, bytes, hipMemcpyDeviceToDevice, nullptr));
+  if ((rc = rt_hip_accumulate(s, nullptr, h, M - h, s->d_ad_now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(s->d_ad_list, list.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  uint32_t n = M, n_prev = h;
+  s->ad_rounds.push_back({nt, n, round_ms});
+  for (;;) {
+    if (n >= N) break;
+    if ((rc = rt_hip_tile_error(s, nullptr, s->d_ad_list, (uint32_t)list.size(), s->d_ad_now, n, s->d_ad_prev, n_prev, s->d_ad_err, nullptr)) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(err.data(), s->d_ad_err, (size_t)nt * 8, hipMemcpyDeviceToHost));
+    size_t k = 0;
+    for (uint32_t t : list) if (err[t] >= threshold) list[k++] = t;
+    list.resize(k);
+    if (list.empty()) break;
+    const uint32_t add = n < N - n ? n : N - n;
+    round_ms = 0.0;
+    RT_HIP_TRY(hipMemcpyAsync(s->d_ad_prev, s->d_ad_now, bytes, hipMemcpyDeviceToDevice, nullptr));
+    RT_HIP_TRY(hipMemcpy(s->d_ad_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = rt_hip_accumulate_tiles(s, nullptr, s->d_ad_list, (uint32_t)list.size(), n, add, s->d_ad_now, nullptr)) != RT_OK || (rc = collect()) != RT_OK)
+      return rc;
+    n_prev = n; n += add;
+    for (uint32_t t : list) n_t[t] = n;
+    s->ad_rounds.push_back({(uint32_t)list.size(), n, round_ms});
+  }
+  RT_HIP_TRY(hipMemcpy(s->d_ad_spp, n_t.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  if ((rc = rt_hip_resolve_tiles(s, nullptr, s->d_ad_now, s->d_ad_spp, s->d_frame, nullptr, nullptr)) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(out_rgb8, s->d_frame, px * 3, hipMemcpyDeviceToHost));
+  if (out_tile_spp) std::copy(n_t.begin(), n_t.end(), out_tile_spp);
+  if (stats) {
+    uint64_t samples = 0;
+    const uint32_t tw = 1u << tg.tile_wl, th = 1u << tg.tile_hl;
+    for (uint32_t t = 0; t < nt; ++t) {
+      const uint32_t by = t / tg.tiles_x, bx = t - by * tg.tiles_x;
+      const uint64_t w = std::min<uint64_t>(tw, s->host.width - bx * tw), hh = std::min<uint64_t>(th, s->host.height - by * th);
+      samples += w * hh * n_t[t];
+    }
+    total.samples = samples;
+    total.frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *stats = total;
   }
   return RT_OK;
 }

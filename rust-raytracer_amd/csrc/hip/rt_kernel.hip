@@ -62,6 +62,9 @@ struct KArgs {
   // packed like out_rgb8; bit 63 = a NaN sample) instead of writing pixels, and trace samples sample_base + [0, sc.spp).
   unsigned long long* accum;
   uint32_t sample_base;
+  // ACCUM kernels only: the queue's length.  n_tiles for a whole-frame pass; for a list launch (rt_hip_accumulate_tiles) the
+  // list's length, tile_order = the list: position g is tile tile_order[g], and ids at or above n_tiles are skipped.
+  uint32_t n_queue;
 };
 // tiles of XCD x in image order: the j-th one (aff_group_log2 = gl)
 __host__ __device__ inline uint32_t xcd_tile(uint32_t x, uint32_t j, uint32_t gl) { return ((((j >> gl) << 3) + x) << gl) + (j & ((1u << gl) - 1u)); }
@@ -537,20 +540,21 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
       // the next tile: from the workgroup's stash; whoever finds it empty first fetches the next batch from the queue
       uint32_t tile = 0;
       if (lane == 0) {
-        uint32_t g = 0xFFFFFFFFu;  // position in queue order; n_tiles: the frame has none left; ~0: a batch is on its way
+        uint32_t g = 0xFFFFFFFFu;  // position in queue order; nq: the frame has none left; ~0: a batch is on its way
+        const uint32_t nq = ACCUM ? ka.n_queue : ka.n_tiles;  // (the queue's length: a list launch's list, else the frame's tiles)
         unsigned long long old = atomicAdd(wg_stash, 1ull);
         const uint32_t s_next = (uint32_t)old, s_end = (uint32_t)(old >> 32);
         if (s_next < s_end) g = s_next;
         else if (s_next == s_end) {
           const uint32_t B = lds_load(wg_batch);
           uint32_t end = 0, rem = 0, share = gridDim.x * ka.batch_share;
-          g = ka.n_tiles;
+          g = nq;
           if (ka.aff_group_log2 == 0xFFFFFFFFu) {
             const uint32_t j = atomicAdd(ka.queue, B);
-            if (j < ka.n_tiles) { g = j; end = j + B < ka.n_tiles ? j + B : ka.n_tiles; rem = ka.n_tiles - end; }
+            if (j < nq) { g = j; end = j + B < nq ? j + B : nq; rem = nq - end; }
           } else {  // this XCD's queue first, then the others'
             uint32_t dry = lds_load(&wg_flags[3]);  // queues this workgroup has seen empty
-            for (uint32_t q = 0; q < 8u && g == ka.n_tiles; ++q) {
+            for (uint32_t q = 0; q < 8u && g == nq; ++q) {
               const uint32_t x = (my_xcd + q) & 7u;
               if ((dry >> x) & 1u) continue;
               const uint32_t cnt = ka.xcd_cnt[x];
@@ -562,7 +566,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
             share = (gridDim.x + 7u) / 8u * ka.batch_share;
             __hip_atomic_fetch_or(&wg_flags[3], dry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           }
-          if (g < ka.n_tiles) {
+          if (g < nq) {
             // the next batch: 1 / batch_share (a sixteenth) of a workgroup's fair share of what the queue still holds —
             // single tiles at the end of the frame, where a stashed tile is work no other workgroup can take
             const uint32_t nb = rem / share;
@@ -571,7 +575,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
           }
         }
         tile = g;
-        if (g < ka.n_tiles) {  // queue position -> tile
+        if (g < nq) {  // queue position -> tile
           if (ka.aff_group_log2 == 0xFFFFFFFFu) {
             if (ka.order_mode != 0u) tile = ka.tile_order ? ka.tile_order[g] : ka.n_tiles - 1u - g;
           } else if (ka.tile_order) tile = ka.tile_order[g];
@@ -581,12 +585,21 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
             const uint32_t j = g - ka.xcd_off[x];
             tile = xcd_tile(x, ka.order_mode != 0u ? ka.xcd_cnt[x] - 1u - j : j, ka.aff_group_log2);
           }
+          if constexpr (ACCUM) if (tile >= ka.n_tiles) tile = 0xFFFFFFFDu;  // a listed id outside the frame: skipped
+        } else if constexpr (ACCUM) {
+          if (g != 0xFFFFFFFFu) tile = 0xFFFFFFFEu;  // (the list is done: above every tile id)
         }
       }
       tile = bcast(tile);
       if (tile == 0xFFFFFFFFu) {  // another wave is fetching a batch: ask again in the next iteration
         if (lane == 0) lds_store(&hdr[k].state, (uint32_t)SLOT_FREE);
         return 0;
+      }
+      if constexpr (ACCUM) {
+        if (tile == 0xFFFFFFFDu) {  // free the slot and take the next queue position
+          if (lane == 0) lds_store(&hdr[k].state, (uint32_t)SLOT_FREE);
+          continue;
+        }
       }
       if (tile >= ka.n_tiles) {  // the frame's queue is empty
         if (lane == 0) { lds_store(&wg_flags[0], 1u); lds_store(&hdr[k].state, (uint32_t)SLOT_FREE); }
@@ -1085,8 +1098,12 @@ __global__ __launch_bounds__(1024) void rt_order_tiles(const uint32_t* __restric
 // accumulator (n_px pixels x 3 u64, rt_hip_accumulate) holding n samples per pixel -> linear f32 and / or RGB8 through the
 // rt_core.h functions the megakernel's tile flush calls, in the same order (fixed_to_mean, rt_nanf, f32_to_u8 of the sqrt).  One thread per 4 pixels: their 12 bytes of RGB8 leave
 // as three dword stores when the buffer is 4-byte aligned (the packed rows of a frame are one contiguous run), else as bytes.
+// tile_spp (adaptive frames, rt_hip_resolve_tiles): a pixel's count is its tile's, tile_spp[(row >> tile_hl) * tiles_x + (col >> tile_wl)]
+// of a frame `width` pixels wide; null: every pixel holds n.
 __global__ __launch_bounds__(256) void rt_resolve(const unsigned long long* __restrict__ accum, uint32_t n, uint64_t n_px,
-                                                  uint8_t* __restrict__ out_rgb8, float* __restrict__ out_linear) {
+                                                  uint8_t* __restrict__ out_rgb8, float* __restrict__ out_linear,
+                                                  const uint32_t* __restrict__ tile_spp, uint32_t width, uint32_t tiles_x, uint32_t tile_wl,
+                                                  uint32_t tile_hl) {
   const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, p0 = g * 4u;
   if (p0 >= n_px) return;
   const uint32_t np = n_px - p0 < 4u ? (uint32_t)(n_px - p0) : 4u;
@@ -1094,11 +1111,16 @@ __global__ __launch_bounds__(256) void rt_resolve(const unsigned long long* __re
 #pragma unroll
   for (uint32_t i = 0; i < 4u; ++i) {
     if (i >= np) break;
+    uint32_t n_i = n;
+    if (tile_spp) {
+      const uint64_t p = p0 + i, row = p / width;
+      n_i = tile_spp[(uint32_t)(row >> tile_hl) * tiles_x + ((uint32_t)(p - row * width) >> tile_wl)];
+    }
 #pragma unroll
     for (uint32_t c = 0; c < 3u; ++c) {
       const uint64_t e = (p0 + i) * 3u + c;
       const unsigned long long v = accum[e];
-      float lin = fixed_to_mean(v & ~ACCUM_NAN_BIT, n);  // (flush_tile's arithmetic, term for term)
+      float lin = fixed_to_mean(v & ~ACCUM_NAN_BIT, n_i);  // (flush_tile's arithmetic, term for term)
       if (v & ACCUM_NAN_BIT) lin = rt_nanf();
       if (out_linear) out_linear[e] = lin;
       const uint32_t b = i * 3u + c;
@@ -1115,6 +1137,48 @@ __global__ __launch_bounds__(256) void rt_resolve(const unsigned long long* __re
     for (uint32_t b = 0; b < 12u; ++b)
       if (b < np * 3u) dst[b] = (uint8_t)(w[b >> 2] >> (8u * (b & 3u)));
   }
+}
+
+// --------------------------------------------------------------------------- adaptive sampling: tile error
+// The noise estimate of DESIGN.md §11 for the tiles of a list: `now` holds samples [0, n_now) of every pixel, `prev` the first n_prev of
+// them (0 < n_prev < n_now), so A = prev and B = now - prev are two disjoint halves.  Per pixel inside the frame, unless one of its six
+// words carries the NaN flag: a_c = P_c / (n_prev 2^40), b_c = (Q_c - P_c) / ((n_now - n_prev) 2^40),
+// e = ((|a0-b0| + |a1-b1|) + |a2-b2|) / (1e-4 + sqrt(0.5 ((a0+b0) + (a1+b1)) + (a2+b2))), all IEEE f64 in exactly this order (the build
+// has -ffp-contract=off; rt_sqrt and `/` are correctly rounded, tests/test_gpu_parity.py).  err[tile] = the max over the tile's
+// pixels, 0.0 if none counts.  A group of 4^tile_log2 lanes per list entry (a wave for 8x8 tiles, 4 ... 64 tiles per wave for smaller
+// ones), one pixel per lane, max by lane shuffles inside the group.  Ids at or above n_tiles are skipped.
+__global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* __restrict__ now, uint32_t n_now, const unsigned long long* __restrict__ prev,
+                                                     uint32_t n_prev, const uint32_t* __restrict__ list, uint32_t n_list, uint32_t tile_log2,
+                                                     uint32_t tile_wl, uint32_t tile_hl, uint32_t tiles_x, uint32_t n_tiles, uint32_t width,
+                                                     uint32_t local_rows, double* __restrict__ err) {
+  const uint32_t npx = 1u << (2u * tile_log2), j = threadIdx.x & (npx - 1u);
+  const uint64_t entry = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> (2u * tile_log2);
+  const uint32_t tile = entry < n_list ? list[entry] : 0xFFFFFFFFu;
+  double e = 0.0;
+  if (tile < n_tiles) {
+    const uint32_t by = tile / tiles_x, bx = tile - by * tiles_x;
+    const uint32_t px = (bx << tile_wl) + (j & ((1u << tile_wl) - 1u)), lr = (by << tile_hl) + (j >> tile_wl);
+    if (px < width && lr < local_rows) {
+      const size_t o = ((size_t)lr * width + px) * 3u;
+      unsigned long long P[3], Q[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { P[c] = prev[o + c]; Q[c] = now[o + c]; }
+      if (!((P[0] | P[1] | P[2] | Q[0] | Q[1] | Q[2]) & ACCUM_NAN_BIT)) {
+        const double sa = (double)n_prev * 0x1p40, sb = (double)(n_now - n_prev) * 0x1p40;
+        double a[3], b[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { a[c] = (double)P[c] / sa; b[c] = (double)(Q[c] - P[c]) / sb; }
+        const double d = (fabs(a[0] - b[0]) + fabs(a[1] - b[1])) + fabs(a[2] - b[2]);
+        const double s = ((a[0] + b[0]) + (a[1] + b[1])) + (a[2] + b[2]);
+        e = d / (1.0e-4 + rt_sqrt(0.5 * s));
+      }
+    }
+  }
+  for (uint32_t off = npx >> 1; off != 0u; off >>= 1) {  // (every lane of the wave takes part: groups are aligned runs of lanes)
+    const double o = __shfl_xor(e, (int)off, 64);
+    e = o > e ? o : e;
+  }
+  if (j == 0u && tile < n_tiles) err[tile] = e;
 }
 
 #ifdef RT_TEST_PROBES

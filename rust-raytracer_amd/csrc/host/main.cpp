@@ -22,6 +22,12 @@
 // <output_file> after every pass (a temporary file in the same directory, then rename: a viewer never sees half a file).  Stderr
 // gets `pass i/K: S samples, kernel X ms`; stdout the same two lines as a one-shot run, `Frame time` over all the passes; the
 // last PNG is the one-shot run's, byte for byte.  One GPU: RT_GPUS > 1 is refused.
+//
+// Adaptive (`raytracer <config_file> <output_file> --adaptive E [--min-spp M]`, M = 16 by default): one adaptive frame
+// (rt_hip_render_adaptive_to_host) — every pixel tile gets samples until its noise estimate falls below E or it
+// holds the scene's samples per pixel, and each tile is the one-shot frame at its own count, byte for byte.  Stdout as a one-shot
+// run; stderr gets `round i: T tiles at n samples, kernel X ms` per round and what fraction of width x height x spp was traced.
+// One GPU: RT_GPUS > 1 is refused.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -236,6 +242,38 @@ int progressive(RtSceneFile* sf, const char* filename, uint32_t passes) {
   return status;
 }
 
+// --adaptive E [--min-spp M]: one adaptive frame of a resident scene
+int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t min_spp) {
+  const RtScene* sc = rt_scene_get(sf);
+  RtHipScene* hs = nullptr;
+  int rc = rt_hip_scene_create(sc, 0, &hs);
+  std::printf("\nRendering %s\n", filename);  // main.rs:18
+  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
+  std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);
+  RtStats st{};
+  rc = rt_hip_render_adaptive_to_host(hs, threshold, min_spp, pixels.data(), nullptr, &st);
+  int status = 0;
+  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; }
+  if (status == 0) {
+    std::printf("Frame time: %lldms\n", (long long)st.frame_ms);  // raytracer.rs:263
+    const int64_t rounds = rt_hip_scene_query(hs, "adaptive_rounds");
+    char key[64];
+    for (int64_t i = 0; i < rounds; ++i) {
+      int64_t v[3];
+      const char* f[3] = {"adaptive_round_tiles_", "adaptive_round_spp_", "adaptive_round_kernel_us_"};
+      for (int k = 0; k < 3; ++k) { std::snprintf(key, sizeof key, "%s%lld", f[k], (long long)i); v[k] = rt_hip_scene_query(hs, key); }
+      std::fprintf(stderr, "round %lld: %lld tiles at %lld samples, kernel %.3f ms\n", (long long)i, (long long)v[0], (long long)v[1], v[2] / 1000.0);
+    }
+    const double full = (double)sc->width * sc->height * sc->samples_per_pixel;
+    std::fprintf(stderr, "adaptive: %llu samples traced, %.4f of %ux%ux%u, kernel %.3f ms, frame %.3f ms\n", (unsigned long long)st.samples,
+                 full > 0 ? st.samples / full : 0.0, sc->width, sc->height, sc->samples_per_pixel, st.kernel_ms, st.frame_ms);
+    rc = rt_png_write_rgb8(filename, pixels.data(), sc->width, sc->height);  // raytracer.rs:265
+    if (rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error()); status = 101; }
+  }
+  rt_hip_scene_destroy(hs);
+  return status;
+}
+
 // RT_ANIM=frames: the frames DISTRIBUTED over the devices — device g renders whole frames g, g + G, ... on its own resident
 // scene and host thread (README.md:43-57 renders an animation one process per frame; this is that, with the scene loaded
 // once per device).  No gather, no shard penalty, no per-frame synchronisation between devices; every frame is the bytes the
@@ -321,9 +359,9 @@ double g_hip_init_ms = 0.0;
 int run(int argc, char** argv) {
   const auto t_main = std::chrono::steady_clock::now();
   int frames = 0;
-  long passes = 0;
-  double orbit = 0.0;
-  bool orbit_given = false, bad_args = argc < 3;
+  long passes = 0, min_spp = 16;
+  double orbit = 0.0, threshold = 0.0;
+  bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false;
   for (int i = 3; i < argc && !bad_args; ++i) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit = std::atof(argv[++i]); orbit_given = true; }
@@ -331,10 +369,22 @@ int run(int argc, char** argv) {
       char* end = nullptr;
       passes = std::strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end != '\0' || passes < 1) bad_args = true;
+    } else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) {
+      char* end = nullptr;
+      threshold = std::strtod(argv[++i], &end);
+      adapt = true;
+      if (end == argv[i] || *end != '\0' || !(threshold >= 0.0) || std::isinf(threshold)) bad_args = true;
+    } else if (!std::strcmp(argv[i], "--min-spp") && i + 1 < argc) {
+      char* end = nullptr;
+      min_spp = std::strtol(argv[++i], &end, 10);
+      min_spp_given = true;
+      if (end == argv[i] || *end != '\0' || min_spp < 1 || min_spp > 0xFFFFFFFFl) bad_args = true;
     } else bad_args = true;
   }
   auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
-  if (bad_args || (passes > 0 && (frames != 0 || orbit_given)) || (argc > 3 && passes == 0 && frames <= 0)) return usage();  // main.rs:9-12: usage line, normal return
+  if (bad_args || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
+      (argc > 3 && passes == 0 && !adapt && frames <= 0))
+    return usage();  // main.rs:9-12: usage line, normal return
   // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
   // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X
   // (tools/microbench/setup_costs.hip) — to move 80 KB of tables in and 2.9 MB of pixels out once.  With HSA_ENABLE_SDMA=0 the
@@ -374,6 +424,19 @@ int run(int argc, char** argv) {
     } else {
       if (g_hip_init.joinable()) g_hip_init.join();
       status = progressive(sf, argv[2], (uint32_t)passes);
+    }
+    rt_scene_free(sf);
+    return status;
+  }
+  if (adapt) {
+    int status = 0;
+    const char* e = std::getenv("RT_GPUS");
+    if (sc->n_gpus > 1 || (e && std::strtol(e, nullptr, 10) > 1)) {
+      std::fprintf(stderr, "--adaptive renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no adaptive form)\n");
+      status = 101;
+    } else {
+      if (g_hip_init.joinable()) g_hip_init.join();
+      status = adaptive(sf, argv[2], threshold, (uint32_t)min_spp);
     }
     rt_scene_free(sf);
     return status;

@@ -56,6 +56,13 @@ def _bind(path, probes):
     L.rt_hip_accumulate.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.rt_hip_resolve.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rt_hip_refine_to_host.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(abi.RtStats)]
+    L.rt_hip_tile_grid.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.POINTER(C.c_uint32)]
+    L.rt_hip_accumulate_tiles.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p]
+    L.rt_hip_tile_error.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                    C.c_uint32, C.c_void_p, C.c_void_p]
+    L.rt_hip_resolve_tiles.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_hip_render_adaptive_to_host.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_abi_sizeof.argtypes = [C.c_char_p]
     L.rt_abi_sizeof.restype = C.c_size_t
     L.rt_abi_version.restype = C.c_uint32
@@ -185,6 +192,45 @@ class HipScene:
         st = abi.RtStats()
         _check(self._L.rt_hip_refine_to_host(self._h, int(sample_count), out.ctypes.data, C.byref(st)), self._L)
         return out, st.as_dict()
+
+    def tile_grid(self, tiles=None):
+        """the pixel tiles of adaptive sampling for `tiles`' rows: (tile width, tile height, tiles_x, tiles_y); id = ty * tiles_x + tx"""
+        out = (C.c_uint32 * 4)()
+        _check(self._L.rt_hip_tile_grid(self._h, C.byref(tiles) if tiles is not None else None, out), self._L)
+        return tuple(int(v) for v in out)
+
+    def accumulate_tiles(self, d_list, n_list, d_accum, sample_begin, sample_count, tiles=None, stream=0):
+        """accumulate() for just the n_list distinct tile ids of d_list (device uint32; ids past the grid are skipped)"""
+        _check(self._L.rt_hip_accumulate_tiles(self._h, C.byref(tiles) if tiles is not None else None, C.c_void_p(d_list or None), int(n_list),
+                                               int(sample_begin), int(sample_count), C.c_void_p(d_accum or None), C.c_void_p(stream or None)), self._L)
+
+    def tile_error(self, d_list, n_list, d_now, n_now, d_prev, n_prev, d_tile_err, tiles=None, stream=0):
+        """enqueue the noise estimate of the listed tiles (d_now: samples [0, n_now), d_prev: [0, n_prev)) into d_tile_err[id] (float64)"""
+        _check(self._L.rt_hip_tile_error(self._h, C.byref(tiles) if tiles is not None else None, C.c_void_p(d_list or None), int(n_list),
+                                         C.c_void_p(d_now or None), int(n_now), C.c_void_p(d_prev or None), int(n_prev),
+                                         C.c_void_p(d_tile_err or None), C.c_void_p(stream or None)), self._L)
+
+    def resolve_tiles(self, d_accum, d_tile_spp, d_rgb8, d_linear=0, tiles=None, stream=0):
+        """enqueue resolve() with each pixel over its tile's count d_tile_spp[id] (device uint32, tiles_y x tiles_x)"""
+        _check(self._L.rt_hip_resolve_tiles(self._h, C.byref(tiles) if tiles is not None else None, C.c_void_p(d_accum or None),
+                                            C.c_void_p(d_tile_spp or None), C.c_void_p(d_rgb8 or None), C.c_void_p(d_linear or None),
+                                            C.c_void_p(stream or None)), self._L)
+
+    def render_adaptive(self, threshold, min_spp=16):
+        """one adaptive frame (blocking): rgb8 numpy [h,w,3], the per-tile counts [tiles_y, tiles_x] and the frame's stats"""
+        import numpy as np
+        _, _, tx, ty = self.tile_grid()
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        spp = np.zeros((ty, tx), np.uint32)
+        st = abi.RtStats()
+        _check(self._L.rt_hip_render_adaptive_to_host(self._h, float(threshold), int(min_spp), out.ctypes.data, spp.ctypes.data, C.byref(st)),
+               self._L)
+        return out, spp, st.as_dict()
+
+    def adaptive_rounds(self):
+        """the rounds of the last render_adaptive: [(tiles, samples per pixel after the round, kernel ms)]"""
+        return [(self.query(f"adaptive_round_tiles_{i}"), self.query(f"adaptive_round_spp_{i}"), self.query(f"adaptive_round_kernel_us_{i}") / 1000.0)
+                for i in range(max(self.query("adaptive_rounds"), 0))]
 
     def wait(self):
         st = abi.RtStats()
