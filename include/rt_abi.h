@@ -343,6 +343,50 @@ int rt_hip_tile_error(RtHipScene*, const RtRowTiles* tiles, const uint32_t* d_ti
 int rt_hip_resolve_tiles(RtHipScene*, const RtRowTiles* tiles, const void* d_accum, const uint32_t* d_tile_spp, void* d_rgb8, void* d_linear,
                          void* stream);
 int rt_hip_render_adaptive_to_host(RtHipScene*, double threshold, uint32_t min_spp, uint8_t* out_rgb8, uint32_t* out_tile_spp, RtStats* stats);
+/* Denoising: feature buffers of the first hit, and an edge-avoiding a-trous filter guided by them.  Whole frames
+ * only: `tiles` must be NULL (RT_ERR_UNSUPPORTED otherwise), frames of at most 1 048 560 rows.
+ *
+ * AOV RECORD: per pixel 8 f32 (32 B), rows x width packed row-major like a whole-frame d_linear, 16-byte aligned:
+ *   {albedo.r, albedo.g, albedo.b, inv_depth, normal.x, normal.y, normal.z, coverage}
+ * the means over samples [0, n) of what the camera ray of sample s — the ray rt_hip_render traces first for that sample, same Philox
+ * address — meets first.  A hit: albedo = the material colour (Lambertian, Metal), (1, 1, 1) (Glass, and Light: it emits (1, 1, 1)),
+ * the texel (Texture); normal = the front-facing unit normal of the hit record; inv_depth = 1 / t; it counts towards coverage.  A
+ * miss: albedo = the sky colour of the ray; normal, inv_depth 0; coverage the fraction of the n rays that hit.  Each field is
+ * summed in f64 in sample order, divided by n, rounded once to f32.
+ *
+ * rt_hip_render_aovs: the record of every pixel into d_aov (width*height*32 bytes) on `stream`, asynchronous, not reported by
+ * rt_hip_wait.  Reads the scene's tables only: no tile queue, learned order, counters or accumulator changes, so every later frame
+ * is byte-identical.  n_samples 0 or a misaligned buffer: RT_ERR_INVALID; above 2^23 - 1: RT_ERR_UNSUPPORTED.
+ *
+ * rt_hip_denoise: L = iterations (0 .. 8) passes of the filter over d_linear (f32 x 3 per pixel, as rt_hip_resolve writes it) guided
+ * by d_aov, into d_out_linear (f32 x 3, 4-byte aligned) and / or d_out_rgb8 (3 bytes per pixel, any alignment, the bytes
+ * rt_hip_resolve would make of the filtered radiance); either may be NULL.  Iteration i, stride 2^i, B3-spline taps
+ * h = (1/16, 1/4, 3/8, 1/4, 1/16) per axis, in IEEE f32 in exactly this order:
+ *   k_c = 4^i / (sc * sc), k_n = 1 / (sn * sn), k_a = 1 / (sa * sa), k_z = 1 / (sz * sz), each min(k, FLT_MAX);
+ *   a pixel with a NaN channel is copied; otherwise for each tap q = p + 2^i (dx, dy) inside the frame, dy outer, dx inner, -2 .. 2:
+ *     dc2 = (dr dr + dg dg) + db db over this iteration's input colour, dn2, da2 alike over normal and albedo, dz2 = dz dz
+ *     (differences q - p), x = ((dc2 k_c + dn2 k_n) + da2 k_a) + dz2 k_z,
+ *     W = 1 / (1 + x (1 + x (1/2 + x (f32(1/6) + x / 24)))), w = (h(dx) h(dy)) W;
+ *     a tap with w > 0 adds w c to the colour sum and w to the weight sum (f32, tap order); a NaN neighbour or x = inf adds nothing;
+ *   out = sum / weight sum per channel.  L = 0: the output linear bits are the input's.
+ * The scene owns the filter's ping-pong scratch (width*height*32 bytes, allocated at first use, freed with the scene); no caller
+ * buffer is written but the outputs, which must not overlap the inputs (RT_ERR_INVALID).  Asynchronous on `stream`.  More than 8
+ * iterations: RT_ERR_UNSUPPORTED; a sigma that is not finite and > 0, a NULL or misaligned input: RT_ERR_INVALID; nothing is enqueued.
+ *
+ * rt_hip_refine_to_host_denoised: rt_hip_refine_to_host — the same pass into the scene's own accumulator, the same reset rules —
+ * with the resolved frame denoised (`iterations` passes, the default sigmas below) before it leaves as RGB8.  The AOVs are computed
+ * once per accumulator start, over the first min(RT_DENOISE_AOV_SAMPLES, samples_per_pixel) samples.  Any split of [0, N) into passes
+ * gives the same final bytes, since the accumulator does. */
+#define RT_DENOISE_AOV_SAMPLES 8u
+#define RT_DENOISE_ITERATIONS 2u          /* the CLI's --denoise; the defaults below: the best of a sweep at 16 spp */
+#define RT_DENOISE_SIGMA_COLOR 0.25f
+#define RT_DENOISE_SIGMA_NORMAL 0.1f
+#define RT_DENOISE_SIGMA_ALBEDO 0.1f
+#define RT_DENOISE_SIGMA_INV_DEPTH 0.01f
+int rt_hip_render_aovs(RtHipScene*, const RtRowTiles* tiles, uint32_t n_samples, void* d_aov, void* stream);
+int rt_hip_denoise(RtHipScene*, const RtRowTiles* tiles, const void* d_linear, const void* d_aov, uint32_t iterations, float sigma_color,
+                   float sigma_normal, float sigma_albedo, float sigma_inv_depth, void* d_out_linear, void* d_out_rgb8, void* stream);
+int rt_hip_refine_to_host_denoised(RtHipScene*, uint32_t sample_count, uint32_t iterations, uint8_t* out_rgb8, RtStats* stats);
 /* A frame over the GPUs of one node, scene resident (the parallel loop of raytracer.rs:254-262 spread over devices;
  * animation: README.md:43-57).  n_gpus = 0 takes scene->n_gpus, then RT_GPUS, then 1.  Each rank renders
  * interleaved 2-scanline tiles (RtRowTiles{2, r, G}) on its own host thread and stream; ONE gather per frame

@@ -1731,4 +1731,118 @@ RT_HD uint8_t f32_to_u8(float x) {
 constexpr unsigned long long ACCUM_NAN_BIT = 1ull << 63;
 constexpr uint32_t ACCUM_MAX_SAMPLES = (1u << 23) - 1u;
 
+// linear radiance -> one RGB8 byte: the sqrt gamma and the palette conversion (raytracer.rs:207-213).  rt_resolve and rt_denoise
+// both write their bytes through this one function.
+RT_HD uint8_t linear_to_u8(float lin) { return f32_to_u8(__builtin_sqrtf(lin)); }
+
+// ------------------------------------------------------------------ denoising
+// Feature buffers (rt_hip_render_aovs): per pixel 8 f32 {albedo rgb, inv_depth, normal xyz, coverage}, the means over samples
+// [0, n) of what the CAMERA ray of each sample meets first — the ray the megakernel traces for that sample (the same Philox
+// address, lane_begin_sample_w).  Summed in f64 in sample order, divided by n, rounded once to f32.
+constexpr uint32_t AOV_FLOATS = 8u;
+template <class Tables>
+RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py, uint32_t n, float out[8]) {
+  double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  Lane<false> L;
+  L.ra.pixel = py * sc.width + px; L.ra.k0 = sc.seed_lo; L.ra.k1 = sc.seed_hi;
+  for (uint32_t s = 0; s < n; ++s) {
+    L.s = s;
+    lane_begin_sample(sc, L, px, py);
+    double closest = T_MAX;
+    int best = -1;
+    uint32_t n_exact = 0, n_steps = 0, tex_oob = 0;
+    hit_world_grid(sc, tb, L.o, L.d, closest, best, n_exact, n_steps);
+    float a[3];
+    if (best < 0) {  // raytracer.rs:133-163: the sky the ray sees
+      const Rgb c = sky_color(sc, L.d, tex_oob);
+      a[0] = c.r; a[1] = c.g; a[2] = c.b;
+    } else {
+      const SphereGeom g = tb.geom((uint32_t)best);
+      const MatCore m = tb.mat((uint32_t)best);
+      const Surface h = surface_at(L.o, L.d, closest, g, m.inv_r);
+      a[0] = m.albedo[0]; a[1] = m.albedo[1]; a[2] = m.albedo[2];
+      if (m.kind == RT_MAT_GLASS || m.kind == RT_MAT_LIGHT) a[0] = a[1] = a[2] = 1.0f;  // (Glass: white; Light emits (1, 1, 1), materials.rs:65-69)
+      else if (m.kind == RT_MAT_TEXTURE) {
+        const UV uv = sphere_uv_for_texel(h.point, g, sc.mat, (uint32_t)best);
+        const Rgb c = texture_albedo(sc, sc.mat[best], uv.u, uv.v, tex_oob);
+        a[0] = c.r; a[1] = c.g; a[2] = c.b;
+      } else if (m.kind != RT_MAT_LAMBERTIAN && m.kind != RT_MAT_METAL) a[0] = a[1] = a[2] = 0.0f;
+      acc[3] += 1.0 / closest;
+      acc[4] += h.normal.x; acc[5] += h.normal.y; acc[6] += h.normal.z;
+      acc[7] += 1.0;
+    }
+    acc[0] += (double)a[0]; acc[1] += (double)a[1]; acc[2] += (double)a[2];
+  }
+  for (int i = 0; i < 8; ++i) out[i] = (float)(acc[i] / (double)n);
+}
+
+// Edge-avoiding a-trous filter (Dammertz et al. 2010, rational weight).  Iteration i of L (L <= DENOISE_MAX_ITERATIONS): a 5x5
+// stencil of stride 2^i, B3-spline taps h = (1/16, 1/4, 3/8, 1/4, 1/16) per axis.  Every operation below is one IEEE f32 operation
+// (the build has -ffp-contract=off), in the order written; tests/denoise_ref.py restates it in numpy bit for bit.
+constexpr uint32_t DENOISE_MAX_ITERATIONS = 8u;
+struct DenoiseK { float kc, kn, ka, kz; };  // the weights of the four squared differences in iteration i
+// k = 4^i / (sigma_color * sigma_color) for colour, 1 / (sigma * sigma) for the guides, each clamped to FLT_MAX so that a tiny sigma
+// makes x = 0 * k = 0 at the centre, never 0 * inf = NaN
+RT_HD float denoise_k(float num, float sigma) {
+  const float s2 = sigma * sigma, k = num / s2;
+  return k > 3.4028234663852886e38f ? 3.4028234663852886e38f : k;
+}
+RT_HD DenoiseK denoise_consts(uint32_t iteration, float sigma_color, float sigma_normal, float sigma_albedo, float sigma_inv_depth) {
+  DenoiseK k;
+  k.kc = denoise_k((float)(1u << (2u * iteration)), sigma_color);
+  k.kn = denoise_k(1.0f, sigma_normal);
+  k.ka = denoise_k(1.0f, sigma_albedo);
+  k.kz = denoise_k(1.0f, sigma_inv_depth);
+  return k;
+}
+// W(x) = 1 / (1 + x (1 + x (1/2 + x (1/6 + x / 24)))): a rational stand-in for exp(-x); W(inf) = 0, W(NaN) = NaN
+RT_HD float denoise_w(float x) {
+  constexpr float SIXTH = (float)(1.0 / 6.0);
+  return 1.0f / (1.0f + x * (1.0f + x * (0.5f + x * (SIXTH + x / 24.0f))));
+}
+struct DnColour { float r, g, b; };
+struct DnGuide { float a[3], iz, n[3], cov; };
+// One output pixel (x, y) of one iteration.  `src` answers colour(i) (this iteration's input) and guide(i) (the AOV record) for the
+// row-major pixel index i of a width x height frame.  A pixel with a NaN channel is copied (the NaN-pixel rule); step 0 copies
+// every pixel (L = 0).  Otherwise, for the taps q = p + step (dx, dy) inside the frame, dy outer and dx inner, -2 .. 2:
+//   dc2 = (dr dr + dg dg) + db db, dn2 and da2 alike, dz2 = dz dz (differences neighbour - centre),
+//   x = ((dc2 kc + dn2 kn) + da2 ka) + dz2 kz,  w = (h(dx) h(dy)) W(x);
+// a tap with w > 0 adds w c to sum_c and w to sum_w (f32, in tap order; w = 0 or NaN: a NaN neighbour, x = inf, contributes
+// nothing), and the pixel is sum_c / sum_w.  The centre tap has x = 0, w = 9/64, whenever its guides are finite.
+template <class Src>
+RT_HD DnColour denoise_pixel(const Src& src, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t step, const DenoiseK& k) {
+  const size_t p = (size_t)y * width + x;
+  const DnColour c0 = src.colour(p);
+  if (step == 0u || c0.r != c0.r || c0.g != c0.g || c0.b != c0.b) return c0;
+  const DnGuide g0 = src.guide(p);
+  const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f;
+  for (int j = 0; j < 5; ++j) {
+    const uint32_t qy = y + (uint32_t)(j - 2) * step;  // (above the frame: wraps past height)
+    if (qy >= height) continue;
+    for (int i = 0; i < 5; ++i) {
+      const uint32_t qx = x + (uint32_t)(i - 2) * step;
+      if (qx >= width) continue;
+      const size_t q = (size_t)qy * width + qx;
+      const DnColour c = src.colour(q);
+      const DnGuide g = src.guide(q);
+      const float dr = c.r - c0.r, dg = c.g - c0.g, db = c.b - c0.b;
+      const float dc2 = (dr * dr + dg * dg) + db * db;
+      const float n0 = g.n[0] - g0.n[0], n1 = g.n[1] - g0.n[1], n2 = g.n[2] - g0.n[2];
+      const float dn2 = (n0 * n0 + n1 * n1) + n2 * n2;
+      const float a0 = g.a[0] - g0.a[0], a1 = g.a[1] - g0.a[1], a2 = g.a[2] - g0.a[2];
+      const float da2 = (a0 * a0 + a1 * a1) + a2 * a2;
+      const float dz = g.iz - g0.iz;
+      const float xw = ((dc2 * k.kc + dn2 * k.kn) + da2 * k.ka) + (dz * dz) * k.kz;
+      const float w = (h[i] * h[j]) * denoise_w(xw);
+      if (!(w > 0.0f)) continue;
+      sr = sr + w * c.r; sg = sg + w * c.g; sb = sb + w * c.b;
+      sw = sw + w;
+    }
+  }
+  DnColour o;
+  o.r = sr / sw; o.g = sg / sw; o.b = sb / sw;
+  return o;
+}
+
 }  // namespace rtc

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "rt_kernel.hip"
@@ -152,7 +153,13 @@ struct RtHipScene {
   unsigned long long* d_accum = nullptr; size_t accum_bytes = 0;
   uint32_t accum_samples = 0;
   bool accum_zero = true;
-  void reset_accum() { accum_samples = 0; accum_zero = true; }
+  void reset_accum() { accum_samples = 0; accum_zero = true; aov_ready = false; }
+  // denoising (rt_hip_denoise): the filter's float4 ping-pong (2 x width x height x 16 B), and for
+  // rt_hip_refine_to_host_denoised the resolved linear frame (x 12 B) and the AOV record of the accumulator's start (x 32 B); all
+  // allocated at first use.  aov_ready: d_dn_aov holds the AOVs of the current accumulator (reset_accum clears it)
+  void* d_dn_ping = nullptr; size_t dn_ping_bytes = 0;
+  void* d_dn_lin = nullptr; void* d_dn_aov = nullptr; size_t dn_host_px = 0;
+  bool aov_ready = false;
   // adaptive frames, host form (rt_hip_render_adaptive_to_host): its own now / prev accumulators and per-tile list, errors and
   // counts (allocated at first use), and what each round of the last frame did: {tiles, samples per pixel after it, kernel ms}
   unsigned long long* d_ad_now = nullptr; unsigned long long* d_ad_prev = nullptr; size_t ad_bytes = 0;
@@ -225,7 +232,8 @@ extern "C" void rt_hip_scene_destroy(RtHipScene* s) {
                     s->d_all, s->d_large_geom})
       if (p) (void)hipFree(p);
   for (void* p : {(void*)s->d_counters, s->d_frame, (void*)s->d_tile_depth, (void*)s->d_tile_order, s->d_light_overflow, (void*)s->d_accum,
-                  (void*)s->d_ad_now, (void*)s->d_ad_prev, (void*)s->d_ad_list, (void*)s->d_ad_err, (void*)s->d_ad_spp})
+                  (void*)s->d_ad_now, (void*)s->d_ad_prev, (void*)s->d_ad_list, (void*)s->d_ad_err, (void*)s->d_ad_spp,
+                  s->d_dn_ping, s->d_dn_lin, s->d_dn_aov})
     if (p) (void)hipFree(p);
   for (auto& sl : s->slot) {
     for (hipEvent_t e : {sl.ev_start, sl.ev_stop, sl.ev_copied}) if (e) (void)hipEventDestroy(e);
@@ -1046,9 +1054,17 @@ extern "C" int rt_hip_render_to_host(RtHipScene* s, uint8_t* out_rgb8, RtStats* 
   return RT_OK;
 }
 
+namespace {
+int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32_t iterations, const float sigma[4], void* d_out_linear,
+                  void* d_out_rgb8, hipStream_t stream);
+int ensure_denoise_host(RtHipScene* s);
+// the host form's AOV sample count: min(RT_DENOISE_AOV_SAMPLES, samples per pixel), at least 1
+uint32_t aov_default_samples(uint32_t spp) { return spp < 1u ? 1u : (spp < RT_DENOISE_AOV_SAMPLES ? spp : RT_DENOISE_AOV_SAMPLES); }
 // Progressive rendering into the scene's own accumulator, blocking: the next sample_count samples of every pixel, then the whole
 // accumulator resolved to RGB8 in out_rgb8.  Passes and the resolve run on the NULL stream, like rt_hip_render_to_host.
-extern "C" int rt_hip_refine_to_host(RtHipScene* s, uint32_t sample_count, uint8_t* out_rgb8, RtStats* stats) {
+// iterations >= 0 (rt_hip_refine_to_host_denoised): the resolve goes to linear f32 and is denoised over the AOVs of the
+// accumulator's start, aov_default_samples(spp) samples of them, computed once per start.
+int refine_to_host(RtHipScene* s, uint32_t sample_count, int iterations, uint8_t* out_rgb8, RtStats* stats) {
   if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
   if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
   if ((uint64_t)s->accum_samples + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
@@ -1066,10 +1082,21 @@ extern "C" int rt_hip_refine_to_host(RtHipScene* s, uint32_t sample_count, uint8
     RT_HIP_TRY(hipMalloc(&s->d_frame, bytes));
     s->frame_bytes = bytes;
   }
+  if (iterations >= 0) { const int rc = ensure_denoise_host(s); if (rc != RT_OK) return rc; }
   if (s->accum_zero && px) { RT_HIP_TRY(hipMemsetAsync(s->d_accum, 0, px * 24, nullptr)); s->accum_zero = false; }
   const uint32_t n = s->accum_samples + sample_count;
   int rc = rt_hip_accumulate(s, nullptr, s->accum_samples, sample_count, s->d_accum, nullptr);
-  if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->d_accum, n, s->d_frame, nullptr, nullptr);
+  if (iterations < 0) {
+    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->d_accum, n, s->d_frame, nullptr, nullptr);
+  } else {
+    if (rc == RT_OK && !s->aov_ready) {
+      rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(s->host.samples_per_pixel), s->d_dn_aov, nullptr);
+      if (rc == RT_OK) s->aov_ready = true;
+    }
+    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->d_accum, n, nullptr, s->d_dn_lin, nullptr);
+    const float sigma[4] = {RT_DENOISE_SIGMA_COLOR, RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_ALBEDO, RT_DENOISE_SIGMA_INV_DEPTH};
+    if (rc == RT_OK) rc = denoise_frame(s, s->d_dn_lin, s->d_dn_aov, (uint32_t)iterations, sigma, nullptr, s->d_frame, nullptr);
+  }
   RtStats st;
   if (rc == RT_OK) rc = rt_hip_wait(s, &st);
   if (rc != RT_OK) { s->reset_accum(); return rc; }  // (a pass that did not complete leaves the accumulator unknown: start over)
@@ -1080,6 +1107,122 @@ extern "C" int rt_hip_refine_to_host(RtHipScene* s, uint32_t sample_count, uint8
     stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_hip_refine_to_host(RtHipScene* s, uint32_t sample_count, uint8_t* out_rgb8, RtStats* stats) {
+  return refine_to_host(s, sample_count, -1, out_rgb8, stats);
+}
+
+// ---------------------------------------------------------------------------------------------------- denoising
+namespace {
+int check_whole_frame(const RtHipScene* s, const RtRowTiles* tiles) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (tiles) return fail(RT_ERR_UNSUPPORTED, "denoising works on whole frames only: tiles must be NULL");
+  if (s->host.height > 65535u * 16u) return fail(RT_ERR_UNSUPPORTED, "frames taller than 1 048 560 rows");
+  return RT_OK;
+}
+int check_sigmas(const float sigma[4]) {
+  for (int i = 0; i < 4; ++i)
+    if (!(sigma[i] > 0.0f) || !(sigma[i] <= 3.4028234663852886e38f)) return fail(RT_ERR_INVALID, "every sigma must be finite and greater than 0");
+  return RT_OK;
+}
+dim3 px_grid(const RtHipScene* s) { return dim3((s->host.width + 15u) / 16u, (s->host.height + 15u) / 16u); }
+// the L iterations: input -> ping -> pong -> ... -> outputs; arguments checked by the caller
+int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32_t iterations, const float sigma[4], void* d_out_linear,
+                  void* d_out_rgb8, hipStream_t stream) {
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px == 0 || (!d_out_linear && !d_out_rgb8)) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  if (iterations >= 2 && 2 * px * 16 > s->dn_ping_bytes) {
+    if (s->d_dn_ping) { RT_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->d_dn_ping); s->d_dn_ping = nullptr; s->dn_ping_bytes = 0; }
+    RT_HIP_TRY(hipMalloc(&s->d_dn_ping, 2 * px * 16));
+    s->dn_ping_bytes = 2 * px * 16;
+  }
+  float4* const buf[2] = {(float4*)s->d_dn_ping, (float4*)s->d_dn_ping + px};
+  const float4* aov = (const float4*)d_aov;
+  const uint32_t W = s->host.width, H = s->host.height;
+  const dim3 grid = px_grid(s), block(16, 16);
+  if (iterations == 0) {
+    hipLaunchKernelGGL((rtk::rt_denoise<false, true>), grid, block, 0, stream, (const float*)d_linear, aov, W, H, 0u, rtc::DenoiseK{},
+                       (float4*)nullptr, (float*)d_out_linear, (uint8_t*)d_out_rgb8);
+    RT_HIP_TRY(hipGetLastError());
+    return RT_OK;
+  }
+  for (uint32_t i = 0; i < iterations; ++i) {
+    const rtc::DenoiseK k = rtc::denoise_consts(i, sigma[0], sigma[1], sigma[2], sigma[3]);
+    const bool first = i == 0, last = i + 1 == iterations;
+    const float* in = first ? (const float*)d_linear : (const float*)buf[(i - 1) & 1];
+    float4* out4 = last ? nullptr : buf[i & 1];
+    float* ol = last ? (float*)d_out_linear : nullptr;
+    uint8_t* ob = last ? (uint8_t*)d_out_rgb8 : nullptr;
+    if (first && last) hipLaunchKernelGGL((rtk::rt_denoise<false, true>), grid, block, 0, stream, in, aov, W, H, 1u << i, k, out4, ol, ob);
+    else if (first) hipLaunchKernelGGL((rtk::rt_denoise<false, false>), grid, block, 0, stream, in, aov, W, H, 1u << i, k, out4, ol, ob);
+    else if (last) hipLaunchKernelGGL((rtk::rt_denoise<true, true>), grid, block, 0, stream, in, aov, W, H, 1u << i, k, out4, ol, ob);
+    else hipLaunchKernelGGL((rtk::rt_denoise<true, false>), grid, block, 0, stream, in, aov, W, H, 1u << i, k, out4, ol, ob);
+    RT_HIP_TRY(hipGetLastError());
+  }
+  return RT_OK;
+}
+// the host form's own linear frame and AOV record
+int ensure_denoise_host(RtHipScene* s) {
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px <= s->dn_host_px) return RT_OK;
+  if (s->d_dn_lin || s->d_dn_aov) {
+    RT_HIP_TRY(hipDeviceSynchronize());
+    if (s->d_dn_lin) (void)hipFree(s->d_dn_lin);
+    if (s->d_dn_aov) (void)hipFree(s->d_dn_aov);
+    s->d_dn_lin = s->d_dn_aov = nullptr; s->dn_host_px = 0;
+  }
+  RT_HIP_TRY(hipMalloc(&s->d_dn_lin, px * 12));
+  RT_HIP_TRY(hipMalloc(&s->d_dn_aov, px * 32));
+  s->dn_host_px = px;
+  s->aov_ready = false;
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32_t n_samples, void* d_aov, void* stream) {
+  const int rc = check_whole_frame(s, tiles);
+  if (rc != RT_OK) return rc;
+  if (n_samples == 0) return fail(RT_ERR_INVALID, "n_samples must be at least 1");
+  if (n_samples > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "at most 2^23 - 1 samples per pixel");
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px == 0) return RT_OK;
+  if (!d_aov) return fail(RT_ERR_INVALID, "null AOV buffer");
+  if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_aov, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+extern "C" int rt_hip_denoise(RtHipScene* s, const RtRowTiles* tiles, const void* d_linear, const void* d_aov, uint32_t iterations, float sigma_color,
+                              float sigma_normal, float sigma_albedo, float sigma_inv_depth, void* d_out_linear, void* d_out_rgb8, void* stream) {
+  int rc = check_whole_frame(s, tiles);
+  if (rc != RT_OK) return rc;
+  if (iterations > rtc::DENOISE_MAX_ITERATIONS) return fail(RT_ERR_UNSUPPORTED, "at most 8 iterations");
+  const float sigma[4] = {sigma_color, sigma_normal, sigma_albedo, sigma_inv_depth};
+  if ((rc = check_sigmas(sigma)) != RT_OK) return rc;
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px == 0) return RT_OK;
+  if (!d_linear || !d_aov) return fail(RT_ERR_INVALID, "null input buffer");
+  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_out_linear) & 3u) return fail(RT_ERR_INVALID, "d_out_linear must be 4-byte aligned");
+  // (an output over an input would be read by neighbouring threads while it is written)
+  const uintptr_t lin0 = (uintptr_t)d_linear, lin1 = lin0 + px * 12, aov0 = (uintptr_t)d_aov, aov1 = aov0 + px * 32;
+  for (const std::pair<uintptr_t, size_t> o : {std::make_pair((uintptr_t)d_out_linear, px * 12), std::make_pair((uintptr_t)d_out_rgb8, px * 3)})
+    if (o.first && ((o.first < lin1 && lin0 < o.first + o.second) || (o.first < aov1 && aov0 < o.first + o.second)))
+      return fail(RT_ERR_INVALID, "the outputs must not overlap the inputs");
+  return denoise_frame(s, d_linear, d_aov, iterations, sigma, d_out_linear, d_out_rgb8, (hipStream_t)stream);
+}
+
+extern "C" int rt_hip_refine_to_host_denoised(RtHipScene* s, uint32_t sample_count, uint32_t iterations, uint8_t* out_rgb8, RtStats* stats) {
+  if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
+  if (iterations > rtc::DENOISE_MAX_ITERATIONS) return fail(RT_ERR_UNSUPPORTED, "at most 8 iterations");
+  if (s->host.height > 65535u * 16u) return fail(RT_ERR_UNSUPPORTED, "frames taller than 1 048 560 rows");
+  return refine_to_host(s, sample_count, (int)iterations, out_rgb8, stats);
 }
 
 // Adaptive sampling, host form, blocking, on the NULL stream like rt_hip_render_to_host.  M = min(min_spp, N):

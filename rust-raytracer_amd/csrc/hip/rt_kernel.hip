@@ -1124,7 +1124,7 @@ __global__ __launch_bounds__(256) void rt_resolve(const unsigned long long* __re
       if (v & ACCUM_NAN_BIT) lin = rt_nanf();
       if (out_linear) out_linear[e] = lin;
       const uint32_t b = i * 3u + c;
-      w[b >> 2] |= (uint32_t)f32_to_u8(__builtin_sqrtf(lin)) << (8u * (b & 3u));
+      w[b >> 2] |= (uint32_t)linear_to_u8(lin) << (8u * (b & 3u));
     }
   }
   if (!out_rgb8) return;
@@ -1180,6 +1180,62 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
   }
   if (j == 0u && tile < n_tiles) err[tile] = e;
 }
+
+// --------------------------------------------------------------------------- denoising
+// Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
+// 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
+__global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x >= sc.width || y >= sc.height) return;
+  const GlobalTables tb{sc.geom, sc.matc};
+  float r[8];
+  aov_pixel(sc, tb, x, y, n, r);
+  const size_t p = (size_t)y * sc.width + x;
+  out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
+  out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
+}
+
+// One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
+// ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two
+// 16-byte loads per tap.  FINAL: the pixel goes to out_linear (f32 x 3) and / or out_rgb8 (3 bytes, any alignment), each if not
+// null; else to out4 (w = 0).
+struct DnSrc {
+  const float* in;
+  const float4* aov;
+  bool in4;
+  __device__ __forceinline__ DnColour colour(size_t i) const {
+    DnColour c;
+    if (in4) { const float4 v = reinterpret_cast<const float4*>(in)[i]; c.r = v.x; c.g = v.y; c.b = v.z; }
+    else { c.r = in[3 * i]; c.g = in[3 * i + 1]; c.b = in[3 * i + 2]; }
+    return c;
+  }
+  __device__ __forceinline__ DnGuide guide(size_t i) const {
+    const float4 u = aov[2 * i], v = aov[2 * i + 1];
+    DnGuide g;
+    g.a[0] = u.x; g.a[1] = u.y; g.a[2] = u.z; g.iz = u.w; g.n[0] = v.x; g.n[1] = v.y; g.n[2] = v.z; g.cov = v.w;
+    return g;
+  }
+};
+template <bool IN4, bool FINAL>
+__global__ __launch_bounds__(256) void rt_denoise(const float* __restrict__ in, const float4* __restrict__ aov, uint32_t width, uint32_t height,
+                                                  uint32_t step, DenoiseK k, float4* __restrict__ out4, float* __restrict__ out_linear,
+                                                  uint8_t* __restrict__ out_rgb8) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x >= width || y >= height) return;
+  const DnSrc src{in, aov, IN4};
+  const DnColour o = denoise_pixel(src, width, height, x, y, step, k);
+  const size_t p = (size_t)y * width + x;
+  if constexpr (FINAL) {
+    if (out_linear) { out_linear[3 * p] = o.r; out_linear[3 * p + 1] = o.g; out_linear[3 * p + 2] = o.b; }
+    if (out_rgb8) { out_rgb8[3 * p] = linear_to_u8(o.r); out_rgb8[3 * p + 1] = linear_to_u8(o.g); out_rgb8[3 * p + 2] = linear_to_u8(o.b); }
+  } else {
+    out4[p] = make_float4(o.r, o.g, o.b, 0.0f);
+  }
+}
+template __global__ void rt_denoise<false, false>(const float*, const float4*, uint32_t, uint32_t, uint32_t, DenoiseK, float4*, float*, uint8_t*);
+template __global__ void rt_denoise<false, true>(const float*, const float4*, uint32_t, uint32_t, uint32_t, DenoiseK, float4*, float*, uint8_t*);
+template __global__ void rt_denoise<true, false>(const float*, const float4*, uint32_t, uint32_t, uint32_t, DenoiseK, float4*, float*, uint8_t*);
+template __global__ void rt_denoise<true, true>(const float*, const float4*, uint32_t, uint32_t, uint32_t, DenoiseK, float4*, float*, uint8_t*);
 
 #ifdef RT_TEST_PROBES
 // --------------------------------------------------------------------------- device self-test

@@ -28,6 +28,11 @@
 // holds the scene's samples per pixel, and each tile is the one-shot frame at its own count, byte for byte.  Stdout as a one-shot
 // run; stderr gets `round i: T tiles at n samples, kernel X ms` per round and what fraction of width x height x spp was traced.
 // One GPU: RT_GPUS > 1 is refused.
+//
+// Denoised (`--denoise`, alone or with `--passes K`): every PNG the run writes is the resolved frame passed through the
+// feature-guided a-trous filter (rt_hip_refine_to_host_denoised, RT_DENOISE_ITERATIONS iterations, the default sigmas; DESIGN.md
+// §12).  The last PNG of `--passes K --denoise` is the `--denoise` run's, byte for byte.  Stdout as a one-shot run.  With --frames,
+// --orbit or --adaptive: the usage line.  One GPU: RT_GPUS > 1 is refused.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -215,7 +220,8 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
 }
 
 // --passes K: one resident scene, K refinements of its accumulator, the PNG rewritten after each
-int progressive(RtSceneFile* sf, const char* filename, uint32_t passes) {
+// (denoise: each pass's frame denoised; report_passes false: the one-shot `--denoise` run, no pass lines)
+int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool denoise = false, bool report_passes = true) {
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
   int rc = rt_hip_scene_create(sc, 0, &hs);
@@ -229,10 +235,10 @@ int progressive(RtSceneFile* sf, const char* filename, uint32_t passes) {
   for (uint32_t i = 0; i < passes && status == 0; ++i) {
     const uint32_t count = spp / passes + (i < spp % passes ? 1u : 0u);  // (the first spp % K passes take one sample more)
     RtStats st{};
-    rc = rt_hip_refine_to_host(hs, count, pixels.data(), &st);
+    rc = denoise ? rt_hip_refine_to_host_denoised(hs, count, RT_DENOISE_ITERATIONS, pixels.data(), &st) : rt_hip_refine_to_host(hs, count, pixels.data(), &st);
     if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; break; }
     frame_ms += st.frame_ms;
-    std::fprintf(stderr, "pass %u/%u: %u samples, kernel %.3f ms\n", i + 1, passes, count, st.kernel_ms);
+    if (report_passes) std::fprintf(stderr, "pass %u/%u: %u samples, kernel %.3f ms\n", i + 1, passes, count, st.kernel_ms);
     rc = rt_png_write_rgb8(tmp.c_str(), pixels.data(), sc->width, sc->height);  // raytracer.rs:265
     if (rc == RT_OK && std::rename(tmp.c_str(), filename) != 0) rc = RT_ERR_PNG;
     if (rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error()); std::remove(tmp.c_str()); status = 101; }
@@ -361,9 +367,10 @@ int run(int argc, char** argv) {
   int frames = 0;
   long passes = 0, min_spp = 16;
   double orbit = 0.0, threshold = 0.0;
-  bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false;
+  bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false, denoise = false;
   for (int i = 3; i < argc && !bad_args; ++i) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
     else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit = std::atof(argv[++i]); orbit_given = true; }
     else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
       char* end = nullptr;
@@ -383,7 +390,7 @@ int run(int argc, char** argv) {
   }
   auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
   if (bad_args || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
-      (argc > 3 && passes == 0 && !adapt && frames <= 0))
+      (denoise && (adapt || frames != 0 || orbit_given)) || (argc > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
     return usage();  // main.rs:9-12: usage line, normal return
   // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
   // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X
@@ -414,16 +421,17 @@ int run(int argc, char** argv) {
   }
   RtScene* sc = rt_scene_get_mut(sf);
   if (const char* seed = std::getenv("RT_SEED")) sc->seed = std::strtoull(seed, nullptr, 0);
-  if (passes > 0) {
+  if (passes > 0 || denoise) {
     int status = 0;
     const char* e = std::getenv("RT_GPUS");
     if ((unsigned long)passes > sc->samples_per_pixel) status = usage();
     else if (sc->n_gpus > 1 || (e && std::strtol(e, nullptr, 10) > 1)) {
-      std::fprintf(stderr, "--passes renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no progressive form)\n");
+      if (denoise) std::fprintf(stderr, "--denoise renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no denoised form)\n");
+      else std::fprintf(stderr, "--passes renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no progressive form)\n");
       status = 101;
     } else {
       if (g_hip_init.joinable()) g_hip_init.join();
-      status = progressive(sf, argv[2], (uint32_t)passes);
+      status = passes > 0 ? progressive(sf, argv[2], (uint32_t)passes, denoise) : progressive(sf, argv[2], 1u, true, false);
     }
     rt_scene_free(sf);
     return status;

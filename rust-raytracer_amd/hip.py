@@ -63,6 +63,10 @@ def _bind(path, probes):
                                     C.c_uint32, C.c_void_p, C.c_void_p]
     L.rt_hip_resolve_tiles.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rt_hip_render_adaptive_to_host.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.RtStats)]
+    L.rt_hip_render_aovs.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_void_p, C.c_void_p]
+    L.rt_hip_denoise.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                 C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rt_hip_refine_to_host_denoised.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_abi_sizeof.argtypes = [C.c_char_p]
     L.rt_abi_sizeof.restype = C.c_size_t
     L.rt_abi_version.restype = C.c_uint32
@@ -191,6 +195,33 @@ class HipScene:
         out = np.zeros((self.height, self.width, 3), np.uint8)
         st = abi.RtStats()
         _check(self._L.rt_hip_refine_to_host(self._h, int(sample_count), out.ctypes.data, C.byref(st)), self._L)
+        return out, st.as_dict()
+
+    # include/rt_abi.h RT_DENOISE_*: the defaults of the host form and the CLI's --denoise
+    DENOISE_ITERATIONS = 2
+    DENOISE_SIGMAS = (0.25, 0.1, 0.1, 0.01)   # colour, normal, albedo, inv_depth
+    DENOISE_AOV_SAMPLES = 8
+
+    def render_aovs(self, n_samples, d_aov, tiles=None, stream=0):
+        """enqueue the feature buffers of samples [0, n_samples): per pixel 8 float32 {albedo rgb, inv_depth, normal xyz, coverage}
+        into d_aov (height x width x 8 float32, 16-byte aligned); whole frames only (tiles must be None)"""
+        _check(self._L.rt_hip_render_aovs(self._h, C.byref(tiles) if tiles is not None else None, int(n_samples), C.c_void_p(d_aov or None),
+                                          C.c_void_p(stream or None)), self._L)
+
+    def denoise(self, d_linear, d_aov, iterations=DENOISE_ITERATIONS, d_out_linear=0, d_out_rgb8=0, sigmas=DENOISE_SIGMAS, tiles=None, stream=0):
+        """enqueue `iterations` passes of the a-trous filter over d_linear (height x width x 3 float32) guided by d_aov, into
+        d_out_linear and / or d_out_rgb8 (either may be 0); sigmas = (colour, normal, albedo, inv_depth)"""
+        sc, sn, sa, sz = (float(x) for x in sigmas)
+        _check(self._L.rt_hip_denoise(self._h, C.byref(tiles) if tiles is not None else None, C.c_void_p(d_linear or None), C.c_void_p(d_aov or None),
+                                      int(iterations), sc, sn, sa, sz, C.c_void_p(d_out_linear or None), C.c_void_p(d_out_rgb8 or None),
+                                      C.c_void_p(stream or None)), self._L)
+
+    def refine_to_host_denoised(self, sample_count, iterations=DENOISE_ITERATIONS):
+        """refine_to_host() with the frame denoised (default sigmas) before it leaves: numpy [h,w,3] uint8 + the pass's stats"""
+        import numpy as np
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        st = abi.RtStats()
+        _check(self._L.rt_hip_refine_to_host_denoised(self._h, int(sample_count), int(iterations), out.ctypes.data, C.byref(st)), self._L)
         return out, st.as_dict()
 
     def tile_grid(self, tiles=None):
