@@ -278,14 +278,23 @@ RT_HD float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
 struct U4 {
   uint32_t x, y, z, w;
 };
+// a ^ b ^ c: one v_bitop3_b32 (LUT 0x96) on gfx950 where the compiler emits two v_xor_b32 for the plain form (ROCm 7.2).
+// In a Philox round c is the round key, wave-uniform through rng(): the one SGPR operand the instruction may take.
+RT_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
 RT_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int round = 0; round < 10; ++round) {
     uint64_t p0 = (uint64_t)0xD2511F53u * c0;  // (the compiler emits one v_mad_u64_u32 per product on gfx950)
     uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
     uint32_t n1 = (uint32_t)p1;
-    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
     uint32_t n3 = (uint32_t)p0;
     c0 = n0; c1 = n1; c2 = n2; c3 = n3;
     k0 += 0x9E3779B9u;

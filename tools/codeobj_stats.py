@@ -53,7 +53,9 @@ def main():
             ins = re.findall(r"^\s+([vsd][a-z0-9_]+|scratch_\w+|global_\w+|flat_\w+|buffer_\w+)\b", b, flags=re.M)
             v = [i for i in ins if i.startswith("v_")]
             line += (f"  | static: {len(ins)} instr, {len(v)} VALU, v_mov {sum(i.startswith('v_mov') for i in v)} ({100.0 * sum(i.startswith('v_mov') for i in v) / max(1, len(v)):.1f} % of VALU), "
-                     f"v_cndmask {sum(i.startswith('v_cndmask') for i in v)}, scratch ld/st {sum(i.startswith('scratch_') for i in ins)}")
+                     f"v_cndmask {sum(i.startswith('v_cndmask') for i in v)}, scratch ld/st {sum(i.startswith('scratch_') for i in ins)}, "
+                     f"v_xor_b32 {sum(i.startswith('v_xor_b32') for i in v)}, v_bitop3_b32 {sum(i.startswith('v_bitop3_b32') for i in v)}, "
+                     f"v_mad_u64_u32 {sum(i.startswith('v_mad_u64_u32') for i in v)}")
         print(line)
 
 

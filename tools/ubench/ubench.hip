@@ -1,11 +1,12 @@
 // ubench.hip — instruction-throughput probes for gfx950 (design input for the megakernel; not product code).
 // Each probe runs REP x 16 independent instructions per wave; cycles from s_memtime.
-// Output: cycles per wave-instruction per SIMD at 1, 2 and 4 waves per SIMD.
+// Output: cycles per wave-instruction per SIMD at 1, 2 and 4 waves per SIMD.  `ubench NAME` runs only the probes whose name contains NAME.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
 #include <vector>
 #include <string>
+#include <cstring>
 #include <algorithm>
 
 #define REP 512
@@ -70,6 +71,13 @@ U32_PROBE(k_mul_lo_u32, B_MULLO)
 U32_PROBE(k_mul_hi_u32, B_MULHI)
 U32_PROBE(k_xor_b32, B_XOR)
 U32_PROBE(k_add3_u32, B_ADD3)
+// a Philox round's three-input XOR `hi ^ c ^ key`, key in an SGPR: one v_bitop3_b32 (LUT 0x96) against two dependent v_xor_b32
+// (the pair probe reports cycles per PAIR, so the two lines compare directly)
+#define B_BITOP3(i) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(u##i) : "v"(uc), "s"(us));
+#define B_XOR2(i) asm volatile("v_xor_b32 %0, %2, %0\n\tv_xor_b32 %0, %0, %1" : "+v"(u##i) : "v"(uc), "s"(us));
+#define U32S_PROBE(NAME, B) PROBE_ASM(NAME, R16(D_U32) uint32_t uc = (uint32_t)seed * 3u + 1u; uint32_t us = __builtin_amdgcn_readfirstlane((uint32_t)seed * 5u + 3u); uint32_t su = 0, R16(B), R16(S_U32) if (su == 12345u) out[0] = 1)
+U32S_PROBE(k_bitop3_b32_xor3, B_BITOP3)
+U32S_PROBE(k_xor_b32_pair, B_XOR2)
 #define D_U64(i) uint64_t w##i = (uint64_t)seed + i;
 #define S_U64(i) sw += w##i;
 #define B_MAD64(i) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(w##i) : "v"(uc), "v"(ud) : "vcc");
@@ -171,8 +179,11 @@ __global__ void k_global_gather(uint64_t* out, double seed, const uint4* __restr
   if ((threadIdx.x & 63) == 0) out[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = t1 - t0;
 }
 
+static const char* g_only = nullptr;  // argv[1]: run only the probes whose name contains it
+
 template <typename F>
 int run(const char* name, F launch, uint64_t* d_out, int insts_per_wave) {
+  if (g_only && !strstr(name, g_only)) return 0;
   for (int wps : {1, 2, 4}) {  // waves per SIMD: one block of 256*wps threads per CU
     int threads = 256 * wps, blocks = 256;
     if (threads > 1024) { threads = 1024; }
@@ -201,13 +212,15 @@ int run(const char* name, F launch, uint64_t* d_out, int insts_per_wave) {
   return 0;
 }
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1) g_only = argv[1];
   uint64_t* d_out; CHK(hipMalloc(&d_out, 1 << 20));
   const int N = REP * 16;
 #define RUN(K) run(#K, [&](int b, int t) { hipLaunchKernelGGL(K, dim3(b), dim3(t), 0, 0, d_out, 1.5); }, d_out, N)
   RUN(k_fma_f32); RUN(k_pk_fma_f32); RUN(k_fma_f64); RUN(k_add_f64); RUN(k_mul_f64);
   RUN(k_rcp_f64); RUN(k_rsq_f64); RUN(k_sqrt_f64); RUN(k_div_f64_ieee); RUN(k_sqrt_f64_ieee);
   RUN(k_mul_lo_u32); RUN(k_mul_hi_u32); RUN(k_mad_u64_u32); RUN(k_xor_b32); RUN(k_add3_u32);
+  RUN(k_bitop3_b32_xor3); RUN(k_xor_b32_pair);
   RUN(k_rcp_f32); RUN(k_rsq_f32); RUN(k_cvt_f64_u32);
   RUN(k_lds_gather<32>); RUN(k_lds_gather<16>); RUN(k_lds_gather<4>); RUN(k_lds_gather<2>);
   RUN(k_lds_gather_tp<32>); RUN(k_lds_gather_tp<16>); RUN(k_lds_gather_tp<8>); RUN(k_lds_gather_tp<4>); RUN(k_lds_gather_tp<2>);
