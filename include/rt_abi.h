@@ -272,7 +272,9 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * "grid_items" (u16 each), "grid_wide" (1: more than 65 535 spheres — 16-byte cells, u32 items), "grid_large" (spheres every ray tests), "table_bytes" (geometry + material cores + cell table +
  * item lists: what a workgroup stages into LDS once per launch), "texel_bytes" (textures + sky as 4-byte texels in HBM);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
- * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases).
+ * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
+ * "last_kernel" (the megakernel instantiation that ran: accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 |
+ * tables in LDS 1; -1 before the scene's first launch).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the

@@ -122,6 +122,7 @@ struct RtHipScene {
   void* d_light_overflow = nullptr; size_t light_overflow_bytes = 0;  // lit scenes: 560 B per lane of the largest launch so far (rt_core.h lane_light_begin)
   size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
   uint32_t last_pool_slots = 0, last_base_slots = 0; size_t last_lds_bytes = 0; bool last_lds_tables = false;  // of the last launch (rt_hip_scene_query)
+  int last_kernel = -1;    // megakernel instantiation of the last launch, encoded like cfg_key (rt_hip_scene_query "last_kernel"; -1: none yet)
   int chunk_spp = 0;       // 0 = automatic
   int tile_batch = 0;      // 0 = automatic; else tiles a workgroup takes from the queue per atomic, 1..64
   int tile_log2 = -1;      // -1 = automatic; else tiles of 4^k pixels, k = 0..3
@@ -456,6 +457,8 @@ int prepare_grid_t(RtHipScene* s, size_t lds_bytes, hipStream_t stream) {
 template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM>
 int launch_grid_t(RtHipScene* s, const rtk::KArgs& ka_in, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
   auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM>;
+  // (here, not in prepare_grid_t: warm_up prepares the scene's default configuration without launching it)
+  s->last_kernel = (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
   // persistent: exactly the resident set, never more workgroups than there are wave-sized items
   uint32_t wgs = (uint32_t)s->cfg_per_cu * (uint32_t)s->num_cus;
   const uint32_t need = (n_items + rtk::WAVES - 1) / rtk::WAVES;
@@ -991,6 +994,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
+  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
   // the last rt_hip_render_adaptive_to_host: its rounds, and round i's tiles, samples per pixel after it, kernel time in microseconds
   if (!std::strcmp(key, "adaptive_rounds")) return (int64_t)s->ad_rounds.size();

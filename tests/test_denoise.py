@@ -298,7 +298,10 @@ def test_aovs_match_the_mini_oracle(pkg, abi, oracle, torch_cuda, load_scene, mi
     gs = pkg.hip.HipScene(sc.ptr, 0)
     got = _aovs(torch_cuda, gs, n).cpu().numpy()
     gs.close()
-    want = _mini_aovs(oracle, abi, sc, n)
+    _check_aovs(got, _mini_aovs(oracle, abi, sc, n), name, n)
+
+
+def _check_aovs(got, want, name, n):
     bad = np.argwhere((_bits(got) != _bits(want)).any(-1))
     assert bad.size == 0, (name, n, len(bad), [(tuple(p), got[tuple(p)], want[tuple(p)]) for p in bad[:3]])
     cov = got[..., 7]
@@ -306,6 +309,32 @@ def test_aovs_match_the_mini_oracle(pkg, abi, oracle, torch_cuda, load_scene, mi
     if n == 1:   # (one ray: a unit normal where it hit, none where it missed)
         nrm = np.linalg.norm(got[..., 4:7].astype(np.float64), axis=-1)
         assert np.all(np.abs(nrm[cov == 1] - 1.0) < 1e-6) and not got[cov == 0][:, 3:7].any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,n", [("wide", 1), ("wide", 4), ("albedo_above_1", 1), ("albedo_above_1", 4)])
+def test_aovs_off_the_packed_simple_tables_match_the_mini_oracle(pkg, abi, oracle, host, torch_cuda, load_scene, mini_with_t, monkeypatch, case, n):
+    """the cover scene through the wide table format (librt_hip_probe.so with RT_GRID_WIDE=1), and with albedos above 1 (the
+    general colour map of the megakernel; the feature buffer carries the albedo as it is)"""
+    w, h = 20, 14
+    if case == "wide":
+        sc = load_scene("cover", w, h, 8)
+        monkeypatch.setenv("RT_GRID_WIDE", "1")
+        gs = pkg.hip.HipScene(sc.ptr, 0, library=pkg.hip.probe_lib())
+        assert gs.query("grid_wide") == 1
+    else:
+        with open(os.path.join(ROOT, "scenes", "cfg2_cover_1200x800_spp128.json")) as f:
+            cfg = json.load(f)
+        cfg.update(width=w, height=h, samples_per_pixel=8)
+        cfg["objects"][0]["material"] = {"Lambertian": {"albedo": [1.25, 0.6, 0.4]}}     # the ground
+        cfg["objects"][-2]["material"] = {"Lambertian": {"albedo": [0.4, 1.5, 0.1]}}     # the large Lambertian sphere
+        sc = host.Scene.loads(json.dumps(cfg))
+        gs = pkg.hip.HipScene(sc.ptr, 0)
+    got = _aovs(torch_cuda, gs, n).cpu().numpy()
+    gs.close()
+    _check_aovs(got, _mini_aovs(oracle, abi, sc, n), case, n)
+    if case != "wide":
+        assert (got[..., 0] > 1).any() and (got[..., 1] > 1).any(), "no albedo above 1 in view"
 
 
 def _gpu_denoise(torch, gs, lin, aov, L, sigmas=SIGMAS, rgb_offset=0, want_linear=True, want_rgb=True):
