@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Msamples/s of the ray_color hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,7 @@ Two hosts for N > 1, the line's config.parallelism says which ran:
   * `python bench.py --gpus N` (no torchrun): ONE process drives the PRODUCT path — the in-library group
     (rt_hip_group_*: host thread + stream per device, ncclCommInitAll, one ncclGather per frame, de-interleave
     kernel), K frames pipelined two deep (rt_hip_group_submit / _collect: frame i's gather under frame i+1's kernels), each
-    assembled in HBM of the first device; `value` from wall time.  Then blocking frames one at a time: `frame_latency_ms`,
+    assembled in HBM of the first device; `value` from wall time.  With --full, blocking frames one at a time: `frame_latency_ms`,
     its non-kernel part and the host-clock stage table (`frame_latency_stages_us`).  RT_GPUS_EMULATE=1 lets the ranks share
     devices (a 1-GPU box can run the whole path).
   * under torch.distributed.run (WORLD_SIZE set): one process per GPU, the same shards gathered by
@@ -26,7 +26,7 @@ Any failure prints ONE JSON line with an "error" key and exits non-zero — neve
 Process-per-GPU branch: in the timed region the tile buffers are double-buffered:
 frame i's gather runs (asynchronously, on the collective's stream) while frame i+1 is being
 rendered, and all K frames are assembled on rank 0 before the closing barrier — `value` is that
-pipelined throughput.  The latency of ONE frame with nothing overlapped (render, gather, row
+pipelined throughput.  With --full, the latency of ONE frame with nothing overlapped (render, gather, row
 permutation on rank 0) is measured separately after the timed region: `frame_latency_ms`, next
 to `n1_kernel_ms` (rank 0 rendering the whole frame alone) and their ratio.
 Rank 0 prints ONE JSON line.
@@ -36,6 +36,13 @@ after the timed region, the RGB8 frame of the last timed step (what a caller of 
 DIR/frame_rgb8.npy as float32 [H, W, 3] — at most 64 MB in all, beyond that a fixed sample (see _dump_outputs).  The scene
 and its Philox seed come from the scene file, so the same arguments give the same inputs in every run: two builds can be
 compared output for output.
+
+A plain run does only what `value` needs — set-up, warm-up, the K timed steps, --dump-outputs — and reports the figures of
+those steps (kernel time from their HIP events, path counters of the last launch, `roofline`).  --full adds everything that
+takes work of its own after the timed region: the blocking-frame latency, the N = 1 comparison and BASELINE configs[3] of
+N > 1 lines, and on N = 1 lines `frame_ms_to_host_buffer`, `first_frame_kernel_ms`, `cli`, `animation`, `mixed_radius_worlds`,
+`other_configs` and `cpu_baseline` with the parity check of this run's frame (--no-other-configs / --no-cpu-baseline leave
+groups of them out).
 
 Extra objects on that line (N = 1):
   roofline      the megakernel against the roof that binds it: vector-ALU issue (no dense contraction -> no MFMA;
@@ -48,9 +55,9 @@ Extra objects on that line (N = 1):
                 `algorithmic`: the reference's brute force (segments x n_spheres tests) over the same
                 time — a speed-up figure (the grid walk runs ~1 % of those tests), NOT a roofline fraction.
                 `traffic`: HBM bytes per launch from the PMC passes, and its ratio to the algorithmic bytes.
-  cpu_baseline  the CPU oracle (a literal restatement of the reference's rayon path) timed
-                on this box's host cores on a bounded sample of the same frame
-  other_configs the other BASELINE configs at full size on one GPU (2 frames each; median of 20 for frames under 50 ms): kernel_ms, Msamples/s
+  cpu_baseline  (--full) the CPU oracle (a literal restatement of the reference's rayon path) timed
+                on the host cores on a bounded sample of the same frame
+  other_configs (--full) the other BASELINE configs at full size on one GPU (2 frames each; median of 20 for frames under 50 ms): kernel_ms, Msamples/s
 """
 import argparse
 import glob
@@ -114,6 +121,8 @@ def _args():
                     help="cpu_baseline renders every k-th scanline (default: chosen for ~10 s of CPU wall time)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the frame of the last timed step to DIR/frame_rgb8.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the line can carry (see the module docstring)")
     return ap.parse_args()
 
 
@@ -282,30 +291,31 @@ def run_group(args):
     sync_all()
     elapsed = time.perf_counter() - t0
     dumped = _dump_outputs(args.dump_outputs, {"frame_rgb8": _group_frame_to_host(hip, grp, H, W)}) if args.dump_outputs else None
-    # ---- ONE frame at a time, nothing overlapped (the north star's case: G launches -> ONE gather -> de-interleave -> frame
-    # on the first device): latency, and where its non-kernel time goes (RtStats.group_us: host clock since submit)
-    lat, lkern, lgath, stages = [], [], [], []
-    for _ in range(max(5, min(args.steps, 20))):
-        st = grp.render()
-        lat.append(st["frame_ms"]); lkern.append(st["kernel_ms"]); lgath.append(st["gather_ms"]); stages.append(st["group_us"])
-    sync_all()
-    # the assembled frame against ONE launch of the whole frame on the first device (same process): must be byte-identical
-    frame, _ = grp.render_to_host()
+    if args.full:
+        # ---- ONE frame at a time, nothing overlapped (the north star's case: G launches -> ONE gather -> de-interleave -> frame
+        # on the first device): latency, and where its non-kernel time goes (RtStats.group_us: host clock since submit)
+        lat, lkern, lgath, stages = [], [], [], []
+        for _ in range(max(5, min(args.steps, 20))):
+            st = grp.render()
+            lat.append(st["frame_ms"]); lkern.append(st["kernel_ms"]); lgath.append(st["gather_ms"]); stages.append(st["group_us"])
+        sync_all()
+        # the assembled frame against ONE launch of the whole frame on the first device (same process): must be byte-identical
+        frame, _ = grp.render_to_host()
+        one = hip.HipScene(sc.ptr, devs[0])
+        if args.variant:
+            one.set_option("variant", args.variant)
+        ks = []
+        ref = None
+        for _ in range(4):
+            ref, st1 = one.render_to_host()
+            ks.append(st1["kernel_ms"])
+        one.close()
+        n1_kernel_ms = sorted(ks[1:])[1]
+        identical = bool(np.array_equal(frame, ref))
     info = grp.info()                  # (again: a gather that failed to enqueue mid-run has switched the transport)
     ranks = grp.ranks()                # where every rank runs + its kernel of the last frame
-    one = hip.HipScene(sc.ptr, devs[0])
-    if args.variant:
-        one.set_option("variant", args.variant)
-    ks = []
-    ref = None
-    for _ in range(4):
-        ref, st1 = one.render_to_host()
-        ks.append(st1["kernel_ms"])
-    one.close()
-    n1_kernel_ms = sorted(ks[1:])[1]
-    identical = bool(np.array_equal(frame, ref))
     grp.close()
-    if not identical:
+    if args.full and not identical:
         raise BenchError(f"the {args.gpus}-rank frame differs from the single launch in {int((frame != ref).sum())} bytes")
     samples = W * H * SPP
     med = lambda v: sorted(v)[len(v) // 2]    # noqa: E731
@@ -322,22 +332,14 @@ def run_group(args):
                                   f"(rt_hip_group_submit / _collect; frame_latency_ms = one blocking frame)"
                                   + (" — RANKS SHARE DEVICES (RT_GPUS_EMULATE=1: a functional check, not a scaling number)" if info["emulated"] else ""),
                    "inputs": "scene tables resident in HBM of every device before the timed region; each timed frame ends assembled in HBM of the first device"},
-        "value_note": "pipelined throughput (frame i's gather under frame i+1's kernels); frame_latency_ms is ONE blocking frame, speedup_vs_n1_latency the north star's figure",
+        "value_note": "pipelined throughput (frame i's gather under frame i+1's kernels)"
+                      + ("; frame_latency_ms is ONE blocking frame, speedup_vs_n1_latency the north star's figure" if args.full else ""),
         "kernel_ms": round(med(kern), 4),                 # slowest rank's shard, median over the timed (pipelined) frames
         "gather_ms": round(med(gath), 4),                 # device 0's clock: (rank 0's kernel start -> frame assembled) - slowest kernel
-        "frame_latency_ms": round(med(lat), 4),           # ONE blocking frame: submit -> assembled in HBM of the first device
-        "frame_latency_kernel_ms": round(med(lkern), 4),
-        "frame_latency_non_kernel_ms": round(med([a - b for a, b in zip(lat, lkern)]), 4),
-        "frame_latency_stages_us": {k: round(med([u[i] for u in stages]), 1) for i, k in enumerate(
-            ("last_rank_thread_running", "last_rank_enqueued", "submitter_knows", "gather_enqueued", "submit_returns", "assembled_seen", "frame_done", "stats_read"))},
-        "n1_kernel_ms": round(n1_kernel_ms, 4),           # the whole frame in one launch on the first device, same process
-        "speedup_vs_n1_latency": round(n1_kernel_ms / med(lat), 3),
-        "speedup_vs_n1_pipelined": round(n1_kernel_ms / ms_per_step, 3),
-        "frame_identical_to_n1": identical,
         "rccl_ranks": info["rccl_comms"], "transport": info["transport"], "transport_fallback": info["transport_fallback"],
         "transport_fallback_reason": info["fallback_reason"] or None, "rank_devices": info["rank_devices"],
         "distinct_devices": info["n_devices"], "visible_gpus": visible, "setup_ms": round(setup_s * 1e3, 1),
-        # one line explains its own efficiency: per rank, its kernel of the last blocking frame, when its host thread ran and had its
+        # one line explains its own efficiency: per rank, its kernel of the last frame, when its host thread ran and had its
         # launch enqueued (us since submit), where its device sits and whether it reaches the first device directly
         "per_rank": {"kernel_ms": [round(r["kernel_ms"], 4) for r in ranks], "t_wake_us": [round(r["t_wake_us"], 1) for r in ranks],
                      "t_enq_us": [round(r["t_enq_us"], 1) for r in ranks], "pci_bus_id": [r["pci_bus_id"] for r in ranks],
@@ -347,8 +349,21 @@ def run_group(args):
     }
     if dumped is not None:
         out["dumped_outputs"] = dumped
-    # the N > 1 line parses like the N = 1 line: the roofline of the dominant kernel per rank, and the CPU baseline (a pointer)
+    # the N > 1 line parses like the N = 1 line: the roofline of the dominant kernel per rank (and with --full the CPU baseline, a pointer)
     out["roofline"] = _group_roofline("cfg2", args.gpus, out["per_rank"]["kernel_ms"]) if headline else None
+    if not args.full:
+        return json.dumps(out)
+    out.update({
+        "frame_latency_ms": round(med(lat), 4),           # ONE blocking frame: submit -> assembled in HBM of the first device
+        "frame_latency_kernel_ms": round(med(lkern), 4),
+        "frame_latency_non_kernel_ms": round(med([a - b for a, b in zip(lat, lkern)]), 4),
+        "frame_latency_stages_us": {k: round(med([u[i] for u in stages]), 1) for i, k in enumerate(
+            ("last_rank_thread_running", "last_rank_enqueued", "submitter_knows", "gather_enqueued", "submit_returns", "assembled_seen", "frame_done", "stats_read"))},
+        "n1_kernel_ms": round(n1_kernel_ms, 4),           # the whole frame in one launch on the first device, same process
+        "speedup_vs_n1_latency": round(n1_kernel_ms / med(lat), 3),
+        "speedup_vs_n1_pipelined": round(n1_kernel_ms / ms_per_step, 3),
+        "frame_identical_to_n1": identical,
+    })
     out["cpu_baseline"] = _n1_cpu_baseline_pointer()
     if headline and not args.no_other_configs:
         try:   # (the extra must never cost the line)
@@ -573,7 +588,7 @@ def run_ranks(args):
 
     # ---- ONE frame, nothing overlapped (the north star's case: render -> one gather at frame end -> frame on rank 0)
     lat_ms = None
-    if collective:
+    if collective and args.full:
         lats = []
         for i in range(7):
             fence()
@@ -591,7 +606,7 @@ def run_ranks(args):
         gs.wait()
     # the whole frame on ONE GPU (rank 0), for the N = 1 reference inside the same line
     n1_kernel_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             full = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
             ks = []
@@ -603,7 +618,7 @@ def run_ranks(args):
 
     # ---- BASELINE configs[3] (the workload BASELINE.json names for the 8-GPU node) on the SAME ranks: 1 warm + 3 blocking frames
     c3 = None
-    if world > 1 and headline and not args.no_other_configs:
+    if world > 1 and headline and args.full and not args.no_other_configs:
         try:
             c3 = _configs3_on_ranks(torch, dist, pkg, rdist, rank, world, local_rank, dev, stream, data_group, transport)
         except BaseException as e:   # noqa: BLE001 — (every rank raises or none: the calls inside are collective)
@@ -708,8 +723,9 @@ def run_ranks(args):
                                "samples_share": [p["samples_share"] for p in per_rank], "pci_bus_id": [g["pci_bus_id"] for g in ranks_devices],
                                "numa_node": [g["numa_node"] for g in ranks_devices], "pinned_cpus": [g.get("pinned_cpus", 0) for g in ranks_devices],
                                "peer_to_root": [g["peer_to_root"] for g in ranks_devices]}
-            out["frame_latency_ms"] = round(lat_ms, 4)      # ONE frame: render (slowest rank) + gather + row permutation, no overlap
-            out["frame_latency_msamples_per_s"] = round(samples / lat_ms / 1e3, 1)
+            if args.full:
+                out["frame_latency_ms"] = round(lat_ms, 4)      # ONE frame: render (slowest rank) + gather + row permutation, no overlap
+                out["frame_latency_msamples_per_s"] = round(samples / lat_ms / 1e3, 1)
             if n1_kernel_ms is not None:
                 out["n1_kernel_ms"] = round(n1_kernel_ms, 4)                      # the whole frame on rank 0's GPU alone, same process
                 out["speedup_vs_n1_latency"] = round(n1_kernel_ms / lat_ms, 3)    # the north star's ">= 6x at 8 GPUs" figure
@@ -717,10 +733,14 @@ def run_ranks(args):
             if world > 1:   # the N > 1 line parses like the N = 1 line
                 if headline:
                     out["roofline"] = _group_roofline("cfg2", world, [p["kernel_ms"] for p in per_rank])
-                out["cpu_baseline"] = _n1_cpu_baseline_pointer()
+                if args.full:
+                    out["cpu_baseline"] = _n1_cpu_baseline_pointer()
                 if c3 is not None:
                     out["configs3_on_group"] = c3
         if world == 1:
+            out["value_note"] = "steady state: frame i uses the tile-queue order learned from frame i-1 of the same view"
+            out["git_head"] = _git_head()
+        if world == 1 and args.full:
             # the frame as a host caller sees it with the scene resident — kernel + the 2.88 MB
             # device-to-host copy of the RGB8 frame (pageable numpy buffer) — reported beside `value`, never as it
             gs.render_to_host()
@@ -742,10 +762,9 @@ def run_ranks(args):
                 k1.append(g1.wait()["kernel_ms"])
                 g1.close()
             out["first_frame_kernel_ms"] = round(min(k1[1:]), 4)
-            out["value_note"] = ("steady state: frame i uses the tile-queue order learned from frame i-1 of the same view; first_frame_kernel_ms = a scene's "
-                                 "FIRST frame (what a one-shot rt_render_rgb8 gets): bottom row first; the measured order knows which tiles hold this seed's rare 50-segment paths, which no seed predicts (DESIGN.md §4.1)")
-            out["git_head"] = _git_head()
-        if world == 1 and headline and not args.no_other_configs:
+            out["value_note"] += ("; first_frame_kernel_ms = a scene's FIRST frame (what a one-shot rt_render_rgb8 gets): bottom row first; "
+                                  "the measured order knows which tiles hold this seed's rare 50-segment paths, which no seed predicts (DESIGN.md §4.1)")
+        if world == 1 and headline and args.full and not args.no_other_configs:
             # (the extras must never cost the line: whatever goes wrong in one of them is reported in its place)
             def extra(fn, *a):
                 try:
@@ -760,7 +779,7 @@ def run_ranks(args):
             out["animation"] = extra(animation_runs, kernel_ms, out["first_frame_kernel_ms"])
             out["cli_note"] = ("median of 3 fresh processes each; the HIP runtime's start-up in a fresh process (hip_init_ms) varies 50 - 230 ms from run to run "
                                "on these boxes and is most of the spread of wall_ms (profiles/r05_run14_cli_wall.log: 150 - 160 ms wall is the typical figure)")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             oracle = graft.load_oracle()
             cores = oracle.lib(abi).rt_oracle_threads()
 

@@ -25,6 +25,21 @@ def test_bench_without_a_gpu_prints_a_json_error_line(gpus):
     assert d["value"] is None and d["n_gpus"] == gpus and "GPU" in d["error"] and d["metric"].startswith("Msamples/sec")
 
 
+def test_bench_full_without_a_gpu_prints_a_json_error_line():
+    """--full is part of the command line: without a GPU it ends like a plain run, in ONE JSON error line"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"],
+                       capture_output=True, text=True, cwd=ROOT, timeout=300, env=env)
+    assert r.returncode != 0
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-1000:]
+    d = json.loads(lines[0])
+    assert d["value"] is None and d["steps"] == 2 and "GPU" in d["error"]
+
+
 @pytest.mark.parametrize("steps,warmup", [(0, 1), (-3, 1), (2, -1)])
 def test_bench_rejects_step_counts_it_cannot_time(steps, warmup):
     """--steps K is the number of timed frames and ms_per_step divides by it: K < 1 (or a negative warm-up) is a JSON error line"""

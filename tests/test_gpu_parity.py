@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -1005,13 +1006,13 @@ def test_scene_is_not_reentrant_across_streams(pkg, load_scene, torch_cuda):
 
 @pytest.mark.parametrize("force_rccl", [False, True, "gloo", "inject"])
 def test_bench_line_contract(force_rccl):
-    """bench.py prints ONE JSON line with the driver's keys (+ roofline / cpu_baseline / other_configs objects) and
+    """`bench.py --full` prints ONE JSON line with the driver's keys (+ roofline / cpu_baseline / other_configs objects) and
     nothing else on stdout — also when an RCCL group is up (RT_BENCH_FORCE_COLLECTIVE: the N > 1 code path with one
     rank; RCCL's version banner must not reach stdout), where it also carries the one-frame latency, the rank /
     device census and the per-rank arrays — and when RCCL does NOT come up ("inject": its set-up raises; "gloo": forced):
     the run falls back to a host-staged gather over gloo, says so, and still delivers its line."""
     env = dict(os.environ, MASTER_PORT={False: "29561", True: "29562", "gloo": "29563", "inject": "29564"}[force_rccl])
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-row-stride", "200"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-row-stride", "200", "--full"]
     if force_rccl:
         env["RT_BENCH_FORCE_COLLECTIVE"] = "1"
         cmd.append("--no-other-configs")
@@ -1069,6 +1070,32 @@ def test_bench_line_contract(force_rccl):
             assert a["kernel_ms_moving_camera"]["median"] > 0 and a["png_ms"]["median"] > 0 and a["bound_by"] in ("kernel", "png")
             assert 0 < a["overlap_efficiency"] <= 1.05
         assert an[0]["moving_over_steady"] > 0.8 and len(an[0]["same_views"]["frames"]) == 5
+
+
+FULL_ONLY_KEYS = ("cpu_baseline", "parity_vs_oracle", "other_configs", "mixed_radius_worlds", "cli", "animation", "first_frame_kernel_ms",
+                  "frame_ms_to_host_buffer", "frame_latency_ms", "n1_kernel_ms", "frame_identical_to_n1", "configs3_on_group")
+
+
+def test_plain_bench_run_carries_only_the_timed_steps():
+    """A plain `bench.py` run (no --full) sets up, warms up, times its steps and prints the line: the headline keys and the
+    figures of the timed steps themselves, and none of what --full measures or checks after them."""
+    env = dict(os.environ, MASTER_PORT="29565")
+    env.pop("WORLD_SIZE", None)
+    steps, warmup = 3, 1
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, cwd=ROOT, timeout=600, env=env)
+    wall_s = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "kernel_ms", "roofline"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup and d["dtype"] == "f64" and "error" not in d
+    assert abs(d["value"] - 1200 * 800 * 128 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * d["value"]
+    assert [k for k in FULL_ONLY_KEYS if k in d] == []
+    print(f"plain bench run: {wall_s:.1f} s wall, {wall_s - (steps + warmup) * d['ms_per_step'] * 1e-3:.1f} s outside its steps")
 
 
 @pytest.mark.parametrize("kind", range(6))
@@ -1159,7 +1186,7 @@ def test_bench_process_per_gpu_with_two_ranks_on_this_gpu():
     env = dict(os.environ, RT_BENCH_ALLOW_SHARED_DEVICE="1", RT_BENCH_FORCE_TRANSPORT="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -1373,7 +1400,7 @@ def _run_bench(args, env_extra=None, timeout=600):
 def test_bench_multi_gpu_without_torchrun_runs_the_in_library_group():
     """`python bench.py --gpus N` (no torchrun) drives the PRODUCT's multi-GPU path — the in-library group —
     in one process and prints ONE JSON line; here with 4 ranks sharing the box's GPU (RT_GPUS_EMULATE=1)."""
-    r = _run_bench(["--gpus", "4", "--steps", "3", "--warmup", "1"], {"RT_GPUS_EMULATE": "1"})
+    r = _run_bench(["--gpus", "4", "--steps", "3", "--warmup", "1", "--full"], {"RT_GPUS_EMULATE": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
@@ -1417,9 +1444,9 @@ def _check_multi_gpu_line_extras(d, n):
 
 
 def test_bench_gpus_8_emulated_carries_configs3_on_the_group():
-    """`python bench.py --gpus 8` — the command of the driver's scaling run — with the 8 ranks on this box's GPU: value as
-    before, + BASELINE configs[3] on the 8-rank group, roofline and the cpu_baseline pointer."""
-    r = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1"], {"RT_GPUS_EMULATE": "1"}, timeout=900)
+    """`python bench.py --gpus 8 --full` — the command of the driver's scaling run, with everything else the line can carry — with
+    the 8 ranks sharing one GPU: value as before, + BASELINE configs[3] on the 8-rank group, roofline and the cpu_baseline pointer."""
+    r = _run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1", "--full"], {"RT_GPUS_EMULATE": "1"}, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.strip().splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]

@@ -22,10 +22,10 @@ REPO=$PWD
 if [[ " $* " == *" pmc "* ]]; then
   # HBM traffic: separate PMC passes, counters only (no trace domains), per the microarch guide
   for C in FETCH_SIZE WRITE_SIZE; do
-    ( cd /tmp && timeout 300 rocprofv3 --pmc $C --output-format csv -d "$REPO/$OUT/pmc_$C" -o bench -- python "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs ) > $OUT/pmc_$C.log 2>&1; stamp pmc_$C $?
+    ( cd /tmp && timeout 300 rocprofv3 --pmc $C --output-format csv -d "$REPO/$OUT/pmc_$C" -o bench -- python "$REPO/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs ) > $OUT/pmc_$C.log 2>&1; stamp pmc_$C $?
   done
-  ( cd /tmp && timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d "$REPO/$OUT/pmc_sq" -o bench -- python "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs ) > $OUT/pmc_sq.log 2>&1; stamp pmc_sq $?
-  ( cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_LDS SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d "$REPO/$OUT/pmc_sq2" -o bench -- python "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs ) > $OUT/pmc_sq2.log 2>&1; stamp pmc_sq2 $?
+  ( cd /tmp && timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d "$REPO/$OUT/pmc_sq" -o bench -- python "$REPO/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs ) > $OUT/pmc_sq.log 2>&1; stamp pmc_sq $?
+  ( cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_LDS SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d "$REPO/$OUT/pmc_sq2" -o bench -- python "$REPO/bench.py" --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs ) > $OUT/pmc_sq2.log 2>&1; stamp pmc_sq2 $?
   python tools/pmc_summary.py $OUT > $OUT/pmc_summary.json 2>$OUT/pmc_summary.err; stamp pmc_summary $?
   cat $OUT/pmc_summary.json
 fi
@@ -36,9 +36,9 @@ if [[ " $* " == *" pmcs "* ]]; then
 fi
 if [[ " $* " == *" group "* ]]; then
   # the product's multi-GPU path in ONE process (bench.py --gpus N without torchrun), ranks sharing this box's GPU
-  RT_GPUS_EMULATE=1 timeout 300 python bench.py --gpus 4 --steps 5 --warmup 2 > $OUT/bench_group4.log 2>$OUT/bench_group4.err; stamp bench_group4 $?
+  RT_GPUS_EMULATE=1 timeout 300 python bench.py --gpus 4 --steps 5 --warmup 2 --full > $OUT/bench_group4.log 2>$OUT/bench_group4.err; stamp bench_group4 $?
   tail -1 $OUT/bench_group4.log | cut -c1-1500
-  RT_GPUS_EMULATE=1 timeout 300 python bench.py --gpus 8 --steps 5 --warmup 2 > $OUT/bench_group8.log 2>$OUT/bench_group8.err; stamp bench_group8 $?
+  RT_GPUS_EMULATE=1 timeout 300 python bench.py --gpus 8 --steps 5 --warmup 2 --full > $OUT/bench_group8.log 2>$OUT/bench_group8.err; stamp bench_group8 $?
   tail -1 $OUT/bench_group8.log | cut -c1-1500
   timeout 120 python bench.py --gpus 8 --steps 2 --warmup 1 > $OUT/bench_group8_refused.log 2>/dev/null; stamp bench_group8_refused $?
   tail -1 $OUT/bench_group8_refused.log | cut -c1-400
@@ -89,10 +89,10 @@ if [[ " $* " == *" sweep "* ]]; then
   cat $OUT/sweep.log
 fi
 # the bench line last (its roofline reads the newest profiles/rNN_*pmc.json: copy gpurun_out/pmc_summary.json there after a pmc run)
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/$OUT/prof" -o bench -- python "$REPO/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs ) > $OUT/rocprof.log 2>&1
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$REPO/$OUT/prof" -o bench -- python "$REPO/bench.py" --steps 5 --warmup 1 --full --no-cpu-baseline --no-other-configs ) > $OUT/rocprof.log 2>&1
 stamp rocprof $?
 STATS=$(find $OUT/prof -name "*kernel_stats.csv" 2>/dev/null | head -1)
 if [ -n "$STATS" ]; then cp "$STATS" $OUT/kernel_stats.csv; head -6 "$STATS"; fi
-timeout 400 python bench.py --steps 10 --warmup 2 > $OUT/bench.log 2>&1; stamp bench $?
+timeout 400 python bench.py --steps 10 --warmup 2 --full > $OUT/bench.log 2>&1; stamp bench $?
 tail -1 $OUT/bench.log
 echo done | tee -a $OUT/summary.txt
