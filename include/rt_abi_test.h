@@ -43,6 +43,18 @@ int rt_hip_atan2_probe(const double* d_y, const double* d_x, double* d_out, uint
 int rt_hip_texel_probe(const double* d_points, const double centre_radius[4], double h_offset, uint64_t tex_w, uint64_t tex_h,
                        uint64_t* d_out, double* d_uv, uint32_t n, void* stream);
 int rt_hip_quot_probe(const double* d_x, const double* d_y, double* d_quot, double* d_rsqrt, double* d_div, uint32_t n, void* stream);
+/* The grid walk on the device (tests/test_walk_rays_gpu.py).  rt_hip_render_rays_probe: one whole frame through the scene's
+ * normal launch path (same instantiation, tiles and queue) in which every sample of pixel p starts from the camera ray
+ * d_rays[6p .. 6p+5] = {origin[3], direction[3]} instead of the jittered one; its bounces follow Philox as usual.  Sample 0's
+ * camera segment of pixel p writes the (t, sphere) hit_world returned to d_first_t[p] / d_first_sphere[p] (both or neither;
+ * -1: no hit).  Waits for the frame and fills stats; the scene's learned queue order is neither measured nor changed.
+ * rt_hip_walk_probe: rt_core.h hit_world_grid — the per-lane walk tests/hostsim runs — of n rays {origin[3], direction[3]}
+ * through the scene's tables, one per thread; d_t / d_best = its (t, sphere), t = f64::MAX and sphere = -1 without a hit;
+ * d_work (optional) = n x {exact sphere tests, grid steps} of each walk.
+ * All d_* are device pointers; rays of d_rays are pixel-major over the scene's width x height. */
+int rt_hip_render_rays_probe(RtHipScene*, const double* d_rays, double* d_first_t, int32_t* d_first_sphere, void* d_rgb8, void* d_linear,
+                             RtStats* stats);
+int rt_hip_walk_probe(RtHipScene*, const double* d_rays, double* d_t, int32_t* d_best, uint32_t* d_work, uint32_t n, void* stream);
 
 #ifdef __cplusplus
 }

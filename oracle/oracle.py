@@ -30,6 +30,7 @@ def lib(abi):
                                               C.POINTER(abi.RtStats), C.c_int]
         L.rt_oracle_accumulate.argtypes = [C.POINTER(abi.RtScene), C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.POINTER(abi.RtStats), C.c_int]
+        L.rt_oracle_render_rays.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.RtStats), C.c_int]
         L.rt_oracle_philox4x32_10.argtypes = [C.POINTER(C.c_uint32)] * 3
         L.rt_oracle_philox4x32_10.restype = None
         L.rt_oracle_sphere_hit.argtypes = [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
@@ -96,6 +97,21 @@ def render(abi, scene_ptr, tiles=None, n_threads=0, want_linear=True, x_range=No
                                           lin.ctypes.data if lin is not None else None, C.byref(st), n_threads)
     if rc != 0:
         raise RuntimeError(f"rt_oracle_render failed: {rc}")
+    return rgb, lin, st.as_dict()
+
+
+def render_rays(abi, scene_ptr, rays, n_threads=0):
+    """render() of the whole frame with the camera ray of every sample of pixel (y, x) taken from rays[y, x] = (origin, direction)
+    -> (rgb8 [h,w,3] u8, linear [h,w,3] f32, stats dict)"""
+    sc = scene_ptr.contents
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    assert rays.shape == (sc.height, sc.width, 6), rays.shape
+    rgb = np.zeros((sc.height, sc.width, 3), np.uint8)
+    lin = np.zeros((sc.height, sc.width, 3), np.float32)
+    st = abi.RtStats()
+    rc = lib(abi).rt_oracle_render_rays(scene_ptr, rays.ctypes.data, rgb.ctypes.data, lin.ctypes.data, C.byref(st), n_threads)
+    if rc != 0:
+        raise RuntimeError(f"rt_oracle_render_rays failed: {rc}")
     return rgb, lin, st.as_dict()
 
 

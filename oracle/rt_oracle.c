@@ -94,6 +94,8 @@ typedef struct {
    * throw away (raytracer.rs:124) — the GPU kernel skips exactly those segments */
   uint32_t discarding;
   uint64_t segments_discarded;
+  /* rt_oracle_render_rays: the camera ray of every sample of pixel p is rays[6p .. 6p+5] (origin, direction); NULL: get_ray's */
+  const double* rays;
 } Ctx;
 
 static void rng_words(const Ctx* c, uint32_t node, uint32_t slot, uint32_t w[4]) {
@@ -494,6 +496,10 @@ static Rgb trace_sample(Ctx* c, uint32_t x, uint32_t y, uint32_t s) {
   double u = ((double)x + u01_53(jw[0], jw[1])) / ((double)w - 1.0);                 /* :199 */
   double v = ((double)h - ((double)y + u01_53(jw[2], jw[3]))) / ((double)h - 1.0);   /* :200 */
   Ray r = camera_get_ray(sc, u, v);
+  if (c->rays) {
+    const double* q = c->rays + (size_t)c->pixel * 6;
+    r.origin = p3(q[0], q[1], q[2]); r.direction = p3(q[3], q[4], q[5]);
+  }
   return ray_color(c, r, sc->max_depth, sc->max_depth, 0, 0);
 }
 
@@ -558,7 +564,7 @@ static double now_ms(void) {
  * asked for (the full-size parity tests compare single 4K rows at spp 1024).  Same pixels, same bits. */
 #define RT_ORACLE_XBLOCK 32u
 static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8, float* linear,
-                       uint64_t* accum, uint32_t sample_begin, uint32_t sample_count, RtStats* stats, int n_threads) {
+                       uint64_t* accum, uint32_t sample_begin, uint32_t sample_count, const double* rays, RtStats* stats, int n_threads) {
   if (!scene || scene->abi_version != RT_ABI_VERSION) return RT_ERR_INVALID;
   if (scene->width == 0 || scene->height == 0 || (scene->n_spheres && !scene->spheres)) return RT_ERR_INVALID;
   if (x1 > scene->width) x1 = scene->width;
@@ -581,7 +587,7 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
   for (uint64_t task = 0; task < n_tasks; ++task) {
     const uint32_t lr = (uint32_t)(task / xblocks), xb = (uint32_t)(task % xblocks);
     Ctx c; memset(&c, 0, sizeof c);
-    c.scene = scene; c.lights = lights; c.n_lights = n_lights;
+    c.scene = scene; c.lights = lights; c.n_lights = n_lights; c.rays = rays;
     uint32_t y = rt_tiles_global_row(tiles, lr);
     const uint32_t xa = x0 + xb * RT_ORACLE_XBLOCK, xe = xa + RT_ORACLE_XBLOCK < x1 ? xa + RT_ORACLE_XBLOCK : x1;
     if (accum) accumulate_line(&c, y, xa, xe, sample_begin, sample_count, accum + lr * row_elems);
@@ -607,16 +613,21 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
 }
 int rt_oracle_render(const RtScene* scene, const RtRowTiles* tiles, uint8_t* rgb8, float* linear,
                      RtStats* stats, int n_threads) {
-  return render_rows(scene, tiles, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, stats, n_threads);
+  return render_rows(scene, tiles, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, NULL, stats, n_threads);
 }
 /* pixels [x0, x1) of the selected rows only; the buffers still hold whole rows (other pixels untouched) */
 int rt_oracle_render_window(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8,
                             float* linear, RtStats* stats, int n_threads) {
-  return render_rows(scene, tiles, x0, x1, rgb8, linear, NULL, 0, 0, stats, n_threads);
+  return render_rows(scene, tiles, x0, x1, rgb8, linear, NULL, 0, 0, NULL, stats, n_threads);
 }
 /* samples [sample_begin, sample_begin + sample_count) of pixels [x0, x1) of the selected rows ADDED into accum */
 int rt_oracle_accumulate(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
                          uint32_t sample_count, uint64_t* accum, RtStats* stats, int n_threads) {
   if (!accum || (uint64_t)sample_begin + sample_count > 0xFFFFFFFFull) return RT_ERR_INVALID;
-  return render_rows(scene, tiles, x0, x1, NULL, NULL, accum, sample_begin, sample_count, stats, n_threads);
+  return render_rows(scene, tiles, x0, x1, NULL, NULL, accum, sample_begin, sample_count, NULL, stats, n_threads);
+}
+/* rt_oracle_render with the camera ray of every sample of pixel p (= y * width + x) taken from rays[6p .. 6p+5] */
+int rt_oracle_render_rays(const RtScene* scene, const double* rays, uint8_t* rgb8, float* linear, RtStats* stats, int n_threads) {
+  if (!rays) return RT_ERR_INVALID;
+  return render_rows(scene, NULL, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, rays, stats, n_threads);
 }

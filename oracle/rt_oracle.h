@@ -46,6 +46,10 @@ int rt_oracle_render_window(const RtScene* scene, const RtRowTiles* tiles, uint3
  * clamped to [0, 1] and floor(v * 2^40 + 0.5) is added.  Other words are left untouched.  stats: as rt_oracle_render's. */
 int rt_oracle_accumulate(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
                          uint32_t sample_count, uint64_t* accum, RtStats* stats, int n_threads);
+/* rt_oracle_render (whole frame) with the camera ray of every sample of pixel p = y * width + x taken from rays[6p .. 6p+5] =
+ * {origin[3], direction[3]} instead of get_ray's; the jitter's RNG words, the rest of each path and the statistics are as
+ * rt_oracle_render's.  The device side is rt_hip_render_rays_probe (include/rt_abi_test.h). */
+int rt_oracle_render_rays(const RtScene* scene, const double* rays, uint8_t* rgb8, float* linear, RtStats* stats, int n_threads);
 int rt_oracle_threads(void);
 
 /* ---- hooks for the reference's known-answer tests ---- */

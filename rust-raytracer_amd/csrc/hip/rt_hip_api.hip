@@ -597,6 +597,11 @@ namespace {
 // One launch of the megakernel over the given row tiles: samples [sample_base, sample_base + spp) of every pixel.  accum == nullptr:
 // the one-shot frame (rt_hip_render: sample_base 0, the scene's samples per pixel, pixels into d_rgb8 / d_linear); else the
 // accumulating kernels add the pass's sums to accum (rt_hip_accumulate).  list != nullptr (accumulating only): just the n_list
+#ifdef RT_TEST_PROBES
+// the camera rays and first-hit record of the launch rt_hip_render_rays_probe is making (KArgs.probe_rays); null otherwise
+struct ProbeRays { const double* rays = nullptr; double* t = nullptr; int32_t* best = nullptr; };
+ProbeRays g_probe_rays;
+#endif
 // tiles it names, in its order (rt_hip_accumulate_tiles); such a launch neither reads nor changes the scene's learned queue order,
 // and `samples` counts n_list whole tiles.  The caller has checked its own arguments.
 int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_linear, unsigned long long* accum, uint32_t sample_base,
@@ -644,6 +649,9 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   }
   ka.out_rgb8 = (uint8_t*)d_rgb8; ka.out_linear = (float*)d_linear; ka.counters = s->d_counters;
   ka.accum = accum; ka.sample_base = sample_base;
+#ifdef RT_TEST_PROBES
+  ka.probe_rays = g_probe_rays.rays; ka.probe_t = g_probe_rays.t; ka.probe_best = g_probe_rays.best;
+#endif
   ka.sc.spp = spp;  // (the kernel's sample count: the pass's, for an accumulating launch)
   ka.queue = (uint32_t*)(s->d_counters + 24);
   ka.local_rows = local_rows;
@@ -763,6 +771,9 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
       s->order_ready = true; s->depth_fresh = false;
     }
     if (s->order_mode == 2 && s->order_age < 2) ka.tile_depth = s->d_tile_depth;  // (measured only while the order is still being built)
+#ifdef RT_TEST_PROBES
+    if (ka.probe_rays) ka.tile_depth = nullptr;  // (a probe frame's depths say nothing about the view: it measures none)
+#endif
     if (s->order_ready) ka.tile_order = s->d_tile_order;
   }
 
@@ -1400,6 +1411,28 @@ extern "C" int rt_hip_texel_probe(const double* d_points, const double centre_ra
   hipLaunchKernelGGL(rtk::rt_texel_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_points, centre_radius[0], centre_radius[1],
                      centre_radius[2], centre_radius[3], h_offset, (unsigned long long)tex_w, (unsigned long long)tex_h,
                      (unsigned long long*)d_out, d_uv, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// a frame of the scene's own launch path whose camera rays are the caller's (see rtk::KArgs.probe_rays); d_* are DEVICE pointers
+extern "C" int rt_hip_render_rays_probe(RtHipScene* s, const double* d_rays, double* d_first_t, int32_t* d_first_sphere, void* d_rgb8,
+                                        void* d_linear, RtStats* stats) {
+  if (!s || !d_rays || !d_rgb8) return fail(RT_ERR_INVALID, "null argument");
+  if (!d_first_t != !d_first_sphere) return fail(RT_ERR_INVALID, "the first-hit record needs both d_first_t and d_first_sphere");
+  if (s->host.samples_per_pixel > (1u << 22)) return fail(RT_ERR_UNSUPPORTED, "more than 2^22 samples per pixel");
+  g_probe_rays.rays = d_rays; g_probe_rays.t = d_first_t; g_probe_rays.best = d_first_sphere;
+  int rc = launch_frame(s, nullptr, d_rgb8, d_linear, nullptr, 0u, s->host.samples_per_pixel, nullptr);
+  g_probe_rays = ProbeRays();
+  if (rc == RT_OK) rc = rt_hip_wait(s, stats);
+  return rc;
+}
+
+// rt_core.h hit_world_grid of n rays on the device, one per thread, through the scene's tables (see rtk::rt_walk_probe)
+extern "C" int rt_hip_walk_probe(RtHipScene* s, const double* d_rays, double* d_t, int32_t* d_best, uint32_t* d_work, uint32_t n, void* stream) {
+  if (!s || !d_rays || !d_t || !d_best) return fail(RT_ERR_INVALID, "null argument");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_walk_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, d_rays, d_t, d_best, d_work, n);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }

@@ -65,6 +65,14 @@ struct KArgs {
   // ACCUM kernels only: the queue's length.  n_tiles for a whole-frame pass; for a list launch (rt_hip_accumulate_tiles) the
   // list's length, tile_order = the list: position g is tile tile_order[g], and ids at or above n_tiles are skipped.
   uint32_t n_queue;
+#ifdef RT_TEST_PROBES
+  // rt_hip_render_rays_probe (librt_hip_probe.so only): every sample of pixel p starts from the caller's camera ray
+  // probe_rays[6p .. 6p+5] (origin, direction) instead of the jittered one, and sample 0's camera segment records the
+  // (closest, best) that hit_world returned in probe_t[p] / probe_best[p].  Null: an ordinary frame.
+  const double* probe_rays;
+  double* probe_t;
+  int32_t* probe_best;
+#endif
 };
 // tiles of XCD x in image order: the j-th one (aff_group_log2 = gl)
 __host__ __device__ inline uint32_t xcd_tile(uint32_t x, uint32_t j, uint32_t gl) { return ((((j >> gl) << 3) + x) << gl) + (j & ((1u << gl) - 1u)); }
@@ -911,6 +919,12 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     double closest = t_max_fresh();
     int best = -1;
     if (wave_any(has_ray)) hit_world(closest, best);
+#ifdef RT_TEST_PROBES
+    {  // (node 0 outside a light ray: the camera segment; a repeated segment writes the same pair again)
+      const KArgs& kp = fresh_args();
+      if (kp.probe_t && has_ray && L.s == 0u && L.node == 0u && !(L.in_light & 1u)) { kp.probe_t[L.ra.pixel] = closest; kp.probe_best[L.ra.pixel] = best; }
+    }
+#endif
     RT_PROF(3);
     // (a) a ray that left the scene ends its sample here (raytracer.rs:133-163); light rays return to their parent in (d)
     bool miss = has_ray && best < 0;
@@ -982,6 +996,12 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     RT_PROF(4);
     // (e) the new samples start (raytracer.rs:199-201, camera.rs:79-84)
     if (fresh) { lane_begin_sample_w(fresh_args().sc, L, n_px, n_py, cam_w); has_ray = true; }
+#ifdef RT_TEST_PROBES
+    if (fresh && fresh_args().probe_rays) {  // (the jitter's Philox call above still happened: the RNG stream is the frame's)
+      const double* r = fresh_args().probe_rays + ((size_t)n_py * fresh_args().sc.width + n_px) * 6u;
+      L.o = v3(r[0], r[1], r[2]); L.d = v3(r[3], r[4], r[5]);
+    }
+#endif
     RT_PROF(0);
     if (!wave_any(has_ray)) {
       // nothing in flight.  Done when the frame has nothing left; otherwise (all tile slots are busy with other waves'
@@ -1273,6 +1293,23 @@ __global__ void rt_hit_probe(const double* rays, const double* spheres, double* 
   out_t[i] = hit ? closest : -1.0;
 }
 
+
+// hit_world_grid (rt_core.h) — the per-lane walk that tests/hostsim runs on the CPU and rt_aov runs here — of n rays, one per
+// thread, through the scene's own tables: out_t / out_best = its (closest, best) with closest-so-far = f64::MAX, out_work (optional)
+// = its exact tests and grid steps.  The device's arithmetic (v_rcp_f32, v_med3_f32, minNum / maxNum) without the megakernel's
+// lock-step wave form.
+__global__ void rt_walk_probe(const DevScene sc, const double* rays, double* out_t, int32_t* out_best, uint32_t* out_work, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+  const GlobalTables tb{sc.geom, sc.matc};
+  double closest = T_MAX;
+  int best = -1;
+  uint32_t n_exact = 0, n_steps = 0;
+  hit_world_grid(sc, tb, o, d, closest, best, n_exact, n_steps);
+  out_t[i] = closest; out_best[i] = best;
+  if (out_work) { out_work[2 * i] = n_exact; out_work[2 * i + 1] = n_steps; }
+}
 
 // The Texture hit's texel ON THE DEVICE, both ways (materials.rs:236-254 through sphere.rs:35-43): texel_fast — the
 // plain-f64 (u, v) through v_rsq_f64 / v_rcp_f64 + Newton steps that only the device build takes — beside the exact path

@@ -98,6 +98,8 @@ def _bind(path, probes):
         L.rt_hip_atan2_probe.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p]
         L.rt_hip_texel_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_hip_quot_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
+        L.rt_hip_render_rays_probe.argtypes = [C.c_void_p] * 6 + [C.POINTER(abi.RtStats)]
+        L.rt_hip_walk_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
     for name in (() if os.environ.get("RT_SKIP_LAYOUT_CHECK") else ("RtSphere", "RtTexture", "RtScene", "RtRowTiles", "RtStats", "RtGroupInfo", "RtGroupRank")):   # the binding's own layout check
         if L.rt_abi_sizeof(name.encode()) != C.sizeof(getattr(abi, name)):
             raise ImportError(f"{path}: sizeof({name}) = {L.rt_abi_sizeof(name.encode())} but abi.py has "
@@ -286,6 +288,20 @@ class HipScene:
         if n < 0:
             _check(n, self._L)
         return buf[32:32 + 4 * n].reshape(n, 4), buf[:32]
+
+    def render_rays_probe(self, d_rays, d_rgb8, d_linear=0, d_first_t=0, d_first_sphere=0):
+        """(probe library only) rt_hip_render_rays_probe: one frame whose camera rays are d_rays (h x w x 6 f64 on the device),
+        waited for -> stats dict"""
+        st = abi.RtStats()
+        _check(self._L.rt_hip_render_rays_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_first_t or None), C.c_void_p(d_first_sphere or None),
+                                                C.c_void_p(d_rgb8), C.c_void_p(d_linear or None), C.byref(st)), self._L)
+        return st.as_dict()
+
+    def walk_probe(self, d_rays, d_t, d_best, n, d_work=0, stream=0):
+        """(probe library only) rt_hip_walk_probe: hit_world_grid of n rays (device pointers; d_work: n x 2 u32 exact tests, grid
+        steps), enqueued on `stream`"""
+        _check(self._L.rt_hip_walk_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_t), C.c_void_p(d_best), C.c_void_p(d_work or None), n,
+                                         C.c_void_p(stream or None)), self._L)
 
     def close(self):
         if self._h:

@@ -187,6 +187,15 @@ extern "C" int hostsim_grid_info(const RtScene* scene, uint32_t out[6]) {
   return RT_OK;
 }
 
+// where the scene's grid lies (for tests): out = gmin[3], cell size[3] (= 1 / GridDesc.inv_cell); the planes of the cells'
+// faces along axis k are gmin[k] + i * size[k], i = 0 .. n[k]
+extern "C" int hostsim_grid_geom(const RtScene* scene, double out[6]) {
+  HostTables t;
+  if (!scene || !build_tables(*scene, t, true).empty()) return RT_ERR_INVALID;
+  for (int k = 0; k < 3; ++k) { out[k] = t.grid.gmin[k]; out[3 + k] = 1.0 / t.grid.inv_cell[k]; }
+  return RT_OK;
+}
+
 // 1: the scene's grid is in the wide table format (GridDesc.wide: 32-bit item lists), 0: packed, < 0: error
 extern "C" int hostsim_grid_wide(const RtScene* scene) {
   HostTables t;
@@ -223,6 +232,34 @@ extern "C" int hostsim_hit_world(const RtScene* scene, const double o[3], const 
     if (r >= 0.0) { c2 = r; b2 = (int)i; }
   }
   out[0] = b1; out[1] = b2; t_out[0] = c1; t_out[1] = c2;
+  return RT_OK;
+}
+
+// hostsim_hit_world for n rays {origin[3], direction[3]} of one scene (its tables built once): best / t = n x {grid, brute force},
+// work (optional) = n x {exact tests, grid steps} of the grid walk
+extern "C" int hostsim_hit_world_v(const RtScene* scene, const double* rays, uint64_t n, int* best, double* t, uint32_t* work) {
+  HostTables tt;
+  if (!scene || !build_tables(*scene, tt, true).empty()) return RT_ERR_INVALID;
+  DevScene ds;
+  fill_dev_scene(*scene, tt, ds);
+  ds.geom = tt.geom.data(); ds.matc = tt.matc.data(); ds.cell_word = tt.cell_word.data(); ds.cell_items = tt.grid.wide ? reinterpret_cast<const uint16_t*>(tt.cell_items32.data()) : tt.cell_items.data();
+  ds.large = tt.large.data(); ds.large_geom = tt.large_geom.data();
+  const GlobalTables tb{ds.geom, ds.matc};
+#pragma omp parallel for schedule(dynamic, 64)
+  for (uint64_t k = 0; k < n; ++k) {
+    const double* r = rays + 6 * k;
+    const V3 oo = v3(r[0], r[1], r[2]), dd = v3(r[3], r[4], r[5]);
+    const double a = length_squared(dd);
+    double c1 = T_MAX; int b1 = -1; uint32_t ne = 0, ns = 0;
+    hit_world_grid(ds, tb, oo, dd, c1, b1, ne, ns);
+    double c2 = T_MAX; int b2 = -1;
+    for (uint32_t i = 0; i < scene->n_spheres; ++i) {
+      const double q = exact_root(oo, dd, a, tt.geom[i], T_MIN, c2);
+      if (q >= 0.0) { c2 = q; b2 = (int)i; }
+    }
+    best[2 * k] = b1; best[2 * k + 1] = b2; t[2 * k] = c1; t[2 * k + 1] = c2;
+    if (work) { work[2 * k] = ne; work[2 * k + 1] = ns; }
+  }
   return RT_OK;
 }
 

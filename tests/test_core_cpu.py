@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from adversarial_rays import (CELL_EDGE, CELL_PLANE, FAMILIES, WORLDS, adversarial_ray, adversarial_world, grid_geometry, hit_world_v, random_scene,
+                              ray_table)
 from conftest import dvec
 from parity import assert_parity
 
@@ -290,21 +292,6 @@ def test_degenerate_scenes(hostsim, oracle, abi, host):
                 assert_parity(rgb, lin, o_rgb, o_lin, f"depth {depth} sky {sky} objs {len(objs)}")
 
 
-def _random_scene(abi, rng, n, spread, r_lo, r_hi, big=None):
-    spheres = (abi.RtSphere * (n + (1 if big else 0)))()
-    for i in range(n):
-        c = rng.uniform(-spread, spread, 3)
-        spheres[i].center[:] = list(c)
-        spheres[i].radius = float(rng.uniform(r_lo, r_hi)) * (-1.0 if i % 11 == 0 else 1.0)
-        spheres[i].kind = abi.RT_MAT_LAMBERTIAN
-    if big:
-        spheres[n].center[:] = [0.0, -big - spread, 0.0]
-        spheres[n].radius = big
-    sc = abi.RtScene(abi_version=abi.RT_ABI_VERSION, width=4, height=4, samples_per_pixel=1, max_depth=2,
-                     spheres=spheres, n_spheres=len(spheres))
-    return sc, spheres
-
-
 def test_grid_walk_adversarial_rays(hostsim, abi):
     """Random worlds (dense, sparse, flat, with a huge ground sphere, far from the origin) and
     rays chosen to stress the walk: origins on sphere surfaces, grazing tangents, axis-parallel
@@ -314,59 +301,41 @@ def test_grid_walk_adversarial_rays(hostsim, abi):
     out = (C.c_int * 2)()
     t_out = (C.c_double * 2)()
     n_rays = n_hits = 0
-    worlds = [dict(n=200, spread=5.0, r_lo=0.05, r_hi=0.6, big=None), dict(n=600, spread=20.0, r_lo=0.1, r_hi=0.3, big=1000.0),
-              dict(n=80, spread=1.0, r_lo=0.2, r_hi=0.5, big=None), dict(n=300, spread=8.0, r_lo=0.01, r_hi=2.5, big=None),
-              dict(n=900, spread=25.0, r_lo=0.2, r_hi=0.2, big=1000.0)]
-    for wi, wd in enumerate(worlds):
-        sc, spheres = _random_scene(abi, rng, **wd)
-        if wi == 1:  # flat world: every centre near y = 0
-            for i in range(wd["n"]):
-                spheres[i].center[1] = float(rng.uniform(0.0, 0.3))
-        if wi == 4:  # exactly one layer of equal spheres on the ground: the grid is a single cell high
-            for i in range(wd["n"]):
-                spheres[i].center[1] = 0.2
-                spheres[i].radius = 0.2
-        if wi == 3:  # far from the origin: large coordinates, small spheres
-            for i in range(wd["n"]):
-                for k in range(3):
-                    spheres[i].center[k] += 5000.0
+    for wi in range(len(WORLDS)):
+        sc, spheres, n = adversarial_world(abi, rng, wi)
         info = (C.c_uint32 * 6)()
         assert hostsim.hostsim_grid_info(C.byref(sc), info) == 0 and info[0] > 0, "world must be gridded"
-        n = wd["n"]
         for trial in range(1500):
-            i = int(rng.integers(n))
-            c = np.array(spheres[i].center[:]); r = abs(spheres[i].radius)
-            kind = trial % 7
-            nrm = rng.standard_normal(3); nrm /= np.linalg.norm(nrm)
-            if kind == 0:    # leaves a sphere surface in a random direction (a bounced ray)
-                o = c + nrm * r; d = rng.standard_normal(3)
-            elif kind == 1:  # grazes sphere i: offset from the centre ~ r (1 +- tiny)
-                tdir = np.cross(nrm, rng.standard_normal(3)); tdir /= np.linalg.norm(tdir)
-                p = c + nrm * r * (1.0 + rng.choice([-1, 1]) * 10.0 ** rng.uniform(-15, -2))
-                o = p - tdir * rng.uniform(0.5, 30.0); d = tdir * rng.uniform(0.1, 3.0)
-            elif kind == 2:  # axis-parallel through the sphere's bounding box
-                ax = int(rng.integers(3)); d = np.zeros(3); d[ax] = rng.choice([-1.0, 1.0]) * rng.uniform(0.2, 2.0)
-                o = c + rng.uniform(-1.2, 1.2, 3) * r; o[ax] -= np.sign(d[ax]) * rng.uniform(1.0, 40.0)
-            elif kind == 3:  # from far outside the grid towards a sphere
-                o = c + nrm * 10.0 ** rng.uniform(1, 4.5); d = (c + rng.uniform(-1, 1, 3) * r * 1.5) - o
-            elif kind == 4:  # one direction component denormal / zero, the others diagonal
-                d = rng.choice([-1.0, 1.0], 3); d[int(rng.integers(3))] = rng.choice([0.0, -0.0, 1e-310, -1e-300, 1e-40])
-                o = c - d * rng.uniform(0.5, 10.0) + rng.uniform(-1, 1, 3) * r
-            elif kind == 5:  # starts inside a sphere
-                o = c + nrm * r * rng.uniform(0.0, 0.999); d = rng.standard_normal(3) * 10.0 ** rng.uniform(-3, 3)
-            else:            # hits sphere i at (almost) its extreme point along an axis — for the outermost
-                             # spheres that is on the grid's outer face — coming in nearly parallel to that face
-                ax = int(rng.integers(3)); sgn = rng.choice([-1.0, 1.0])
-                e = np.zeros(3); e[ax] = sgn
-                p = c + e * r * (1.0 - 10.0 ** rng.uniform(-12, -2))
-                tdir = rng.standard_normal(3); tdir[ax] = 0.0; tdir /= np.linalg.norm(tdir)
-                d = tdir + e * 10.0 ** rng.uniform(-4, -1.5)
-                o = p - d * rng.uniform(0.5, 12.0)
+            kind = trial % FAMILIES
+            o, d = adversarial_ray(rng, spheres, n, kind)
             assert hostsim.hostsim_hit_world(C.byref(sc), dvec(*o), dvec(*d), out, t_out) == 0
             n_rays += 1
             n_hits += out[1] >= 0
             assert out[0] == out[1] and (out[0] < 0 or t_out[0] == t_out[1]), (wi, trial, kind, out[:], t_out[:])
     assert n_hits > 0.3 * n_rays
+
+
+def test_grid_walk_cell_plane_and_edge_rays(hostsim, abi):
+    """Rays lying in a plane between cells (the direction's component along that axis exactly +-0), along cell edges and from
+    cell corners one cell per axis at a time (every later crossing is a three-way tie of the DDA), in the worlds of
+    test_grid_walk_adversarial_rays: the host build of the walk must return exactly the brute-force (t, sphere)."""
+    rng = np.random.default_rng(78)
+    n_rays = n_hits = 0
+    for wi in range(len(WORLDS)):
+        sc, spheres, n = adversarial_world(abi, rng, wi)
+        gmin, size, ncell = grid_geometry(hostsim, C.byref(sc))
+        rays, fam = ray_table(rng, spheres, n, 1200, (CELL_PLANE, CELL_EDGE), (gmin, size, ncell))
+        o, d = rays[:, :3], rays[:, 3:]
+        on_plane = np.abs((o - gmin) / size - np.rint((o - gmin) / size)) < 1e-9
+        flat = on_plane & (d == 0.0)
+        assert flat[fam == CELL_PLANE].any(axis=1).all(), "a cell-plane ray that does not lie in a plane"
+        assert (on_plane[fam == CELL_EDGE].sum(axis=1) >= 2).all(), "a cell-edge ray that does not start on an edge"
+        bg, tg, bb, tb = hit_world_v(hostsim, C.byref(sc), rays)
+        bad = np.flatnonzero((bg != bb) | ((bb >= 0) & (tg != tb)))
+        assert bad.size == 0, (wi, bad[:5], rays[bad[:5]].tolist(), bg[bad[:5]], bb[bad[:5]])
+        n_rays += len(rays)
+        n_hits += int((bb >= 0).sum())
+    assert n_hits > 0.3 * n_rays, (n_hits, n_rays)
 
 
 def test_rays_from_far_away_walk_the_grid(hostsim, abi, monkeypatch):
@@ -376,7 +345,7 @@ def test_rays_from_far_away_walk_the_grid(hostsim, abi, monkeypatch):
     cells outside the grid and took the full scan over every sphere — correct, and 100 ms for ONE ray of a frame of a
     2 x 10^5-sphere world on the GPU.  At 2^-16 it walks — and finds what brute force finds."""
     rng = np.random.default_rng(17)
-    sc, spheres = _random_scene(abi, rng, n=900, spread=25.0, r_lo=0.2, r_hi=0.2, big=1000.0)
+    sc, spheres = random_scene(abi, rng, n=900, spread=25.0, r_lo=0.2, r_hi=0.2, big=1000.0)
     for i in range(900):
         spheres[i].center[1] = 0.2
         spheres[i].radius = 0.2
@@ -409,7 +378,7 @@ def test_any_order_hit_equals_object_order_scan(hostsim, abi):
     """coincident and duplicated spheres: ties in t must go to the lowest object index
     (raytracer.rs:52-57 keeps the first of equals), whatever order the cells list them in"""
     rng = np.random.default_rng(5)
-    sc, spheres = _random_scene(abi, rng, 120, 4.0, 0.2, 0.5)
+    sc, spheres = random_scene(abi, rng, 120, 4.0, 0.2, 0.5)
     for i in range(0, 120, 3):  # exact duplicates and same-centre shells
         spheres[i + 1].center[:] = spheres[i].center[:]
         spheres[i + 1].radius = spheres[i].radius
