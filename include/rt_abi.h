@@ -206,6 +206,14 @@ void rt_camera_derive(const double look_from[3], const double look_at[3], const 
                       double vfov_deg, double aspect, double out[13]);
 /* camera description of a loaded scene file (camera.rs:29-36): look_from[3], look_at[3], vup[3], vfov, aspect */
 void rt_scene_camera(const RtSceneFile*, double out[11]);
+/* Thin lens (an extension of the schema; the reference ignores both keys): the camera map's optional "aperture"
+ * (default 0: the pinhole) and "focus_dist" (default |look_from - look_at|).  out = aperture, focus_dist as resolved. */
+void rt_scene_lens(const RtSceneFile*, double out[2]);
+/* Camera::new with a thin lens of focus distance f, r = aperture / 2: out = origin[3], lower_left[3], horizontal[3], vertical[3]
+ * (on the focus plane), focal_length, u[3], v[3], r.  aperture 0: the pinhole — the first 13 values are rt_camera_derive's bits,
+ * whatever focus_dist.  What rt_hip_set_camera and rt_hip_set_lens take. */
+void rt_camera_derive_lens(const double look_from[3], const double look_at[3], const double vup[3], double vfov_deg, double aspect,
+                           double aperture, double focus_dist, double out[20]);
 /* raytracer.rs:220-229 find_lights: writes indices of Light spheres in object order */
 uint32_t rt_find_lights(const RtSphere* spheres, uint32_t n, uint32_t* out_idx, uint32_t cap);
 /* materials.rs:213-219 load_texture_image: Huffman JPEG (baseline, extended sequential, progressive; 8 bit, 1 or 3
@@ -274,7 +282,7 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
  * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
  * "last_kernel" (the megakernel instantiation that ran: accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 |
- * tables in LDS 1; -1 before the scene's first launch).
+ * tables in LDS 1; thin lens 32; -1 before the scene's first launch), "lens" (1: rt_hip_set_lens set a lens, 0: the pinhole).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
@@ -283,6 +291,13 @@ int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 int rt_hip_set_camera(RtHipScene*, const double origin[3], const double lower_left[3], const double horizontal[3],
                       const double vertical[3]);
 int rt_hip_render_to_host(RtHipScene*, uint8_t* out_rgb8, RtStats* stats);
+/* Thin-lens camera (RtScene has no lens, so a scene starts as the pinhole): every sample's camera ray leaves a
+ * point of the disc of radius lens_radius spanned by the unit vectors u and v, towards the point of the focus plane that
+ * rt_hip_set_camera's vectors name (rt_camera_derive_lens gives all of them).  lens_radius 0 selects the pinhole again; a
+ * negative or non-finite radius, or a null vector, is RT_ERR_INVALID and changes nothing.  A real change starts the scene's
+ * accumulator over, as rt_hip_set_camera does.  Every launch path follows it: rt_hip_render, rt_hip_accumulate(_tiles), the
+ * host forms, rt_hip_render_aovs. */
+int rt_hip_set_lens(RtHipScene*, const double u[3], const double v[3], double lens_radius);
 /* Progressive rendering: a frame's samples in passes, and the image resolved at any point.  Sample s of pixel p traces the same
  * path whatever the frame's sample count, and pixel sums are exact 2^-40 fixed point, so the passes of any split of [0, N) — any
  * sizes, any order — added up and resolved over N give the frame rt_hip_render makes at samples_per_pixel = N, bit for bit
@@ -453,6 +468,7 @@ void rt_hip_group_destroy(RtHipGroup*);
 uint32_t rt_hip_group_size(const RtHipGroup*);
 int rt_hip_group_set_camera(RtHipGroup*, const double origin[3], const double lower_left[3], const double horizontal[3],
                             const double vertical[3]);
+int rt_hip_group_set_lens(RtHipGroup*, const double u[3], const double v[3], double lens_radius);  /* rt_hip_set_lens on every rank */
 int rt_hip_group_set_option(RtHipGroup*, const char* key, int64_t value);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
@@ -462,7 +478,8 @@ uint32_t rt_hip_group_stacked_row(uint32_t y, uint32_t n_ranks, uint32_t pad_row
  * host RGB8 out.  Blocking.  Renders on scene->n_gpus devices (see RtScene.n_gpus / RT_GPUS): the scene
  * is replicated, device r renders scanline tiles r, r+G, ... (2 rows each) on its own host thread and
  * stream, the packed tiles meet on device 0 through ONE gather (RCCL send/recv over xGMI, or peer copies
- * with RT_GATHER=peer), are de-interleaved by a small kernel and leave in ONE device-to-host copy. */
+ * with RT_GATHER=peer), are de-interleaved by a small kernel and leave in ONE device-to-host copy.  The camera is RtScene's: a
+ * pinhole (a lens needs a group or scene and rt_hip_set_lens). */
 int rt_render_rgb8(const RtScene* scene, uint8_t* out_rgb8, RtStats* stats);
 const char* rt_strerror(int code);
 

@@ -51,11 +51,14 @@ def build_hip(force=False):
         built_from = None
     if os.path.exists(os.path.join(ROOT, ".git")) and built_from != kernel_src_hash():
         force = True
+    # (linked against librt_host.so: rt_abi.h is one seam, and a handle of librt_hip.so resolves its host calls — the scene file
+    #  and camera helpers — too)
+    link = ["-L" + HERE, "-Wl,--no-as-needed", "-lrt_host", "-Wl,-rpath,$ORIGIN"]
     jobs = []
     if force or _newer(out, deps):
-        jobs.append(["hipcc", *HIPFLAGS, "-shared", *src, "-o", out])
+        jobs.append(["hipcc", *HIPFLAGS, "-shared", *src, "-o", out, *link])
     if force or _newer(probe, deps):
-        jobs.append(["hipcc", *HIPFLAGS, "-DRT_TEST_PROBES", "-shared", *src, "-o", probe])
+        jobs.append(["hipcc", *HIPFLAGS, "-DRT_TEST_PROBES", "-shared", *src, "-o", probe, *link])
     procs = []
     for cmd in jobs:   # (side by side: each is ~20 s of one core)
         print("+", " ".join(cmd), file=sys.stderr, flush=True)

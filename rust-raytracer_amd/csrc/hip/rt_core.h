@@ -183,6 +183,9 @@ struct DevScene {
   const uint32_t* large;       // [n_large] sphere indices, object order
   const SphereGeom* large_geom;  // [n_large] their geometry, packed in the same order (streamed by scalar loads)
   const MatCore* matc;         // [n_spheres]
+  // thin lens (rt_hip_set_lens): the camera's unit vectors u and v and the lens radius aperture / 2; lens_r == 0 is the
+  // pinhole.  Read only by the LENS instantiations of the megakernel and by rt_aov_lens.
+  double lens_u[3], lens_v[3], lens_r;
 };
 
 // ------------------------------------------------------------------ f64 square root
@@ -311,6 +314,7 @@ RT_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint3
 //   node n, slot 1           : .w = the HIGH word of the light-sampling draw of a hit that is not Glass: the word attempt 0's
 //                              call leaves over, so a lit kernel decides `draw > threshold` without a second Philox stream —
 //                              the low word (slot 0) matters only when the high word alone leaves the comparison open (2^-32)
+//   node NODE_CAMERA, slot 1+a: attempt a of the thin lens's point in the unit disc (lens_disc): (.x, .y), then (.z, .w)
 constexpr uint32_t NODE_CAMERA = 0xFFFFFFFFu;
 RT_HD double u01_53(uint32_t lo, uint32_t hi) {  // rand 0.8 Standard f64: (u64 >> 11) * 2^-53
   // u >> 11 = h * 2^32 + l with h = hi >> 11 (21 bits), l = the 32 bits below: the value h * 2^-21 + l * 2^-53 is a 53-bit
@@ -350,6 +354,19 @@ RT_HD V3 random_in_unit_sphere(const RngAddr& a, uint32_t node) {
     U4 w = rng(a, node, 1u + attempt);
     V3 p = v3(range_m1_1(w.x), range_m1_1(w.y), range_m1_1(w.z));
     if (length_squared(p) < 1.0) return p;
+  }
+}
+
+// The point of a thin lens: rejection in the unit disc in random_in_unit_sphere's style.  Attempt a is
+// rng(a, NODE_CAMERA, 1 + a); its candidates are (.x, .y), then (.z, .w).  Slot 0 stays the jitter, so a lens sample still
+// depends on (pixel, sample) alone.
+RT_HD void lens_disc(const RngAddr& a, double& x, double& y) {
+  for (uint32_t attempt = 0;; ++attempt) {
+    const U4 w = rng(a, NODE_CAMERA, 1u + attempt);
+    x = range_m1_1(w.x); y = range_m1_1(w.y);
+    if (x * x + y * y < 1.0) return;
+    x = range_m1_1(w.z); y = range_m1_1(w.w);
+    if (x * x + y * y < 1.0) return;
   }
 }
 
@@ -1296,7 +1313,9 @@ struct Lane {
 
 // raytracer.rs:199-201 + camera.rs:79-84
 // (the four Philox words of the camera jitter — rng(L.ra, NODE_CAMERA, 0) with L.ra.sample = L.s — come from the caller)
-template <class LaneT>
+// LENS: the thin-lens camera of DESIGN.md §13 — the ray leaves a point of the lens disc (lens_disc, radius sc.lens_r, in the plane
+// of sc.lens_u / sc.lens_v) towards the same point of the focus plane (the host derived lower_left, horizontal, vertical there)
+template <bool LENS = false, class LaneT>
 RT_HD void lane_begin_sample_w(const DevScene& sc, LaneT& L, uint32_t px, uint32_t py, U4 w) {
   L.ra.sample = L.s;
   double un = (double)px + u01_53(w.x, w.y), vn = sc.height_d - ((double)py + u01_53(w.z, w.w));
@@ -1309,14 +1328,22 @@ RT_HD void lane_begin_sample_w(const DevScene& sc, LaneT& L, uint32_t px, uint32
   V3 ver = v3(sc.cam_v[0], sc.cam_v[1], sc.cam_v[2]);
   L.o = origin;
   L.d = sub(add(add(llc, muls(hor, u)), muls(ver, v)), origin);
+  if constexpr (LENS) {
+    double lx, ly;
+    lens_disc(L.ra, lx, ly);
+    const double rx = sc.lens_r * lx, ry = sc.lens_r * ly;
+    const V3 off = add(muls(v3(sc.lens_u[0], sc.lens_u[1], sc.lens_u[2]), rx), muls(v3(sc.lens_v[0], sc.lens_v[1], sc.lens_v[2]), ry));
+    L.o = add(origin, off);
+    L.d = sub(L.d, off);
+  }
   L.node = 0; L.k = 0; L.in_light = 0;
   fwd_init(L.fwd);
 }
 
-template <class LaneT>
+template <bool LENS = false, class LaneT>
 RT_HD void lane_begin_sample(const DevScene& sc, LaneT& L, uint32_t px, uint32_t py) {
   L.ra.sample = L.s;
-  lane_begin_sample_w(sc, L, px, py, rng(L.ra, NODE_CAMERA, 0));
+  lane_begin_sample_w<LENS>(sc, L, px, py, rng(L.ra, NODE_CAMERA, 0));
 }
 
 // ---- the colour map of LIT scenes whose albedos all lie in [0, 1] (Lane<true, true, *>) ------------------------------
@@ -1749,14 +1776,14 @@ RT_HD uint8_t linear_to_u8(float lin) { return f32_to_u8(__builtin_sqrtf(lin)); 
 // [0, n) of what the CAMERA ray of each sample meets first — the ray the megakernel traces for that sample (the same Philox
 // address, lane_begin_sample_w).  Summed in f64 in sample order, divided by n, rounded once to f32.
 constexpr uint32_t AOV_FLOATS = 8u;
-template <class Tables>
+template <bool LENS, class Tables>
 RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py, uint32_t n, float out[8]) {
   double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Lane<false> L;
   L.ra.pixel = py * sc.width + px; L.ra.k0 = sc.seed_lo; L.ra.k1 = sc.seed_hi;
   for (uint32_t s = 0; s < n; ++s) {
     L.s = s;
-    lane_begin_sample(sc, L, px, py);
+    lane_begin_sample<LENS>(sc, L, px, py);
     double closest = T_MAX;
     int best = -1;
     uint32_t n_exact = 0, n_steps = 0, tex_oob = 0;

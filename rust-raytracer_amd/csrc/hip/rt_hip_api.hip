@@ -431,10 +431,10 @@ namespace {
 // launch's start event is recorded — a first frame used to carry the 147 MB hipMalloc of a lit scene and the runtime's
 // first look at the kernel inside its kernel_ms (one-shot CLI frames: 8.4 ms for a 0.9 ms kernel, profiles/r05_run5_cli_stats_before_warmup.log)
 // — and once at scene creation for the scene's default configuration (warm_up).
-template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM>
+template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM, bool LENS>
 int prepare_grid_t(RtHipScene* s, size_t lds_bytes, hipStream_t stream) {
-  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM>;
-  const int key = (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
+  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>;
+  const int key = (LENS ? 32 : 0) | (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
   if (s->cfg_key != key || s->cfg_lds != lds_bytes) {
     if (lds_bytes > 48 * 1024) RT_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int per_cu_q = 0;
@@ -454,11 +454,11 @@ int prepare_grid_t(RtHipScene* s, size_t lds_bytes, hipStream_t stream) {
   }
   return RT_OK;
 }
-template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM>
+template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM, bool LENS>
 int launch_grid_t(RtHipScene* s, const rtk::KArgs& ka_in, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
-  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM>;
+  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>;
   // (here, not in prepare_grid_t: warm_up prepares the scene's default configuration without launching it)
-  s->last_kernel = (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
+  s->last_kernel = (LENS ? 32 : 0) | (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
   // persistent: exactly the resident set, never more workgroups than there are wave-sized items
   uint32_t wgs = (uint32_t)s->cfg_per_cu * (uint32_t)s->num_cus;
   const uint32_t need = (n_items + rtk::WAVES - 1) / rtk::WAVES;
@@ -469,11 +469,11 @@ int launch_grid_t(RtHipScene* s, const rtk::KArgs& ka_in, size_t lds_bytes, uint
   hipLaunchKernelGGL(kern, dim3(wgs), dim3(rtk::BLOCK), lds_bytes, stream, ka);
   return RT_OK;
 }
-// (lights, every albedo in [0, 1], tables in LDS, wide cell tables, accumulating) -> the instantiation's prepare / launch
-template <bool ACCUM>
+// (lights, every albedo in [0, 1], tables in LDS, wide cell tables, accumulating, thin lens) -> the instantiation's prepare / launch
+template <bool ACCUM, bool LENS>
 int dispatch_grid_t(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
   int rc;
-#define RT_GO(HL, SIMPLE, LDS, WIDE) rc = prepare_only ? prepare_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM>(s, lds_bytes, stream) : launch_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM>(s, *ka, lds_bytes, n_items, stream)
+#define RT_GO(HL, SIMPLE, LDS, WIDE) rc = prepare_only ? prepare_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>(s, lds_bytes, stream) : launch_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>(s, *ka, lds_bytes, n_items, stream)
   const bool simple = s->simple_colour;
   if (wide) {  // (the launch's grid has 32-bit item lists — more than 65 535 spheres; tables in L2: plan_lds never puts them in LDS)
     if (lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
@@ -489,8 +489,11 @@ int dispatch_grid_t(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, 
 }
 int dispatch_grid(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream,
                   bool accum = false) {
-  return accum ? dispatch_grid_t<true>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream)
-               : dispatch_grid_t<false>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream);
+  if (s->dev.lens_r != 0.0)
+    return accum ? dispatch_grid_t<true, true>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream)
+                 : dispatch_grid_t<false, true>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream);
+  return accum ? dispatch_grid_t<true, false>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream)
+               : dispatch_grid_t<false, false>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream);
 }
 
 // LDS budget of a launch: do the tables fit, how big are the light pools, how much dynamic LDS does a workgroup ask for.
@@ -1005,7 +1008,8 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
   // the last rt_hip_render_adaptive_to_host: its rounds, and round i's tiles, samples per pixel after it, kernel time in microseconds
   if (!std::strcmp(key, "adaptive_rounds")) return (int64_t)s->ad_rounds.size();
@@ -1044,6 +1048,20 @@ extern "C" int rt_hip_set_camera(RtHipScene* s, const double origin[3], const do
   static const bool keep_stale = std::getenv("RT_STALE_ORDER") != nullptr;
   if (!keep_stale) { s->order_ready = false; s->depth_fresh = false; }   // (stale arm: the previous view's depths are sorted into this frame's order)
   s->order_age = 0;
+  return RT_OK;
+}
+
+extern "C" int rt_hip_set_lens(RtHipScene* s, const double u[3], const double v[3], double lens_radius) {
+  if (!s || !u || !v) return fail(RT_ERR_INVALID, "null argument");
+  if (!(lens_radius >= 0.0 && lens_radius <= 1.7976931348623157e308)) return fail(RT_ERR_INVALID, "lens_radius must be finite and >= 0");
+  bool same = lens_radius == s->dev.lens_r;
+  if (lens_radius != 0.0)
+    for (int i = 0; i < 3; ++i) same = same && s->dev.lens_u[i] == u[i] && s->dev.lens_v[i] == v[i];
+  if (same) return RT_OK;  // (pinhole to pinhole, or the same lens: the accumulator and the queue order stay)
+  for (int i = 0; i < 3; ++i) { s->dev.lens_u[i] = u[i]; s->dev.lens_v[i] = v[i]; }
+  s->dev.lens_r = lens_radius;
+  s->reset_accum();
+  s->order_ready = false; s->depth_fresh = false; s->order_age = 0;  // (another view: it measures its own order, as after rt_hip_set_camera)
   return RT_OK;
 }
 
@@ -1207,7 +1225,8 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   if (!d_aov) return fail(RT_ERR_INVALID, "null AOV buffer");
   if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
   RT_HIP_TRY(hipSetDevice(s->device));
-  hipLaunchKernelGGL(rtk::rt_aov, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  if (s->dev.lens_r != 0.0) hipLaunchKernelGGL(rtk::rt_aov_lens, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  else hipLaunchKernelGGL(rtk::rt_aov, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }

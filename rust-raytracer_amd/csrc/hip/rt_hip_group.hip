@@ -543,6 +543,16 @@ extern "C" int rt_hip_group_set_camera(RtHipGroup* g, const double origin[3], co
   return RT_OK;
 }
 
+extern "C" int rt_hip_group_set_lens(RtHipGroup* g, const double u[3], const double v[3], double lens_radius) {
+  if (!g) return fail(RT_ERR_INVALID, "null argument");
+  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: a bad radius changes no rank)
+    int rc = rt_hip_set_lens(g->scene[r], u, v, lens_radius);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_set_lens(g->scene2[r], u, v, lens_radius);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
 namespace rtg { void prepare_staging(RtHipGroup* g, int n_frames); }
 extern "C" int rt_hip_group_set_option(RtHipGroup* g, const char* key, int64_t value) {
   if (!g || !key) return fail(RT_ERR_INVALID, "null argument");

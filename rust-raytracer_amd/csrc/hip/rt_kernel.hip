@@ -325,7 +325,9 @@ struct LdsTables {  // per-lane gathers from the workgroup's LDS copies
 // ACCUM: the accumulating form of progressive rendering (rt_hip_accumulate): a finished tile adds its exact sums to the caller's
 // accumulator (KArgs.accum) instead of writing pixels, and its samples are numbered from KArgs.sample_base.  Everything else —
 // the queue, the pools, the paths — is the one-shot kernel's, which is why a frame made of passes is the one-shot frame.
-template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false>
+// LENS: the thin-lens camera: each new sample's camera ray leaves a point of the lens (rt_core.h lane_begin_sample_w);
+// a compile-time arm, so the pinhole instantiations stay the code they were.
+template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false>
 __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs ka) {
   static_assert(!(LDS_TABLES && WIDE), "wide tables (more than 65 535 spheres) never fit LDS");
   const DevScene& sc = ka.sc;
@@ -995,7 +997,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     count_tiles(miss || finished, miss ? k_miss : my_k);
     RT_PROF(4);
     // (e) the new samples start (raytracer.rs:199-201, camera.rs:79-84)
-    if (fresh) { lane_begin_sample_w(fresh_args().sc, L, n_px, n_py, cam_w); has_ray = true; }
+    if (fresh) { lane_begin_sample_w<LENS>(fresh_args().sc, L, n_px, n_py, cam_w); has_ray = true; }
 #ifdef RT_TEST_PROBES
     if (fresh && fresh_args().probe_rays) {  // (the jitter's Philox call above still happened: the RNG stream is the frame's)
       const double* r = fresh_args().probe_rays + ((size_t)n_py * fresh_args().sc.width + n_px) * 6u;
@@ -1204,16 +1206,20 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
 // --------------------------------------------------------------------------- denoising
 // Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
 // 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
-__global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) {
+template <bool LENS>
+__device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float4* __restrict__ out) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x >= sc.width || y >= sc.height) return;
   const GlobalTables tb{sc.geom, sc.matc};
   float r[8];
-  aov_pixel(sc, tb, x, y, n, r);
+  aov_pixel<LENS>(sc, tb, x, y, n, r);
   const size_t p = (size_t)y * sc.width + x;
   out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
   out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
 }
+__global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false>(sc, n, out); }
+// (the thin-lens camera, DESIGN.md §13: the same first ray as the LENS megakernels)
+__global__ __launch_bounds__(256) void rt_aov_lens(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true>(sc, n, out); }
 
 // One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
 // ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two

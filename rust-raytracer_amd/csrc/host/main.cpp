@@ -33,6 +33,10 @@
 // feature-guided a-trous filter (rt_hip_refine_to_host_denoised, RT_DENOISE_ITERATIONS iterations, the default sigmas; DESIGN.md
 // §12).  The last PNG of `--passes K --denoise` is the `--denoise` run's, byte for byte.  Stdout as a one-shot run.  With --frames,
 // --orbit or --adaptive: the usage line.  One GPU: RT_GPUS > 1 is refused.
+//
+// Thin lens: a scene whose camera has a non-zero "aperture" renders through the lens in every mode above —
+// rt_camera_derive_lens gives the camera on the focus plane and the lens, set next to each other on the resident scene or group
+// (every --frames camera is re-derived so).  RtScene has no lens, so such a one-shot frame goes through a group, not rt_render_rgb8.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -47,8 +51,9 @@
 #include "../../../include/rt_abi.h"
 
 namespace {
-// camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77
-void orbit_camera(const double cam[11], double orbit_deg, int f, double out[13]) {
+// camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77 with the scene's
+// lens = {aperture, focus_dist} (rt_scene_lens; aperture 0: the pinhole, out[0..12] = rt_camera_derive's)
+void orbit_camera(const double cam[11], const double lens[2], double orbit_deg, int f, double out[20]) {
   const double *lf = cam, *la = cam + 3, *up = cam + 6;
   double k[3];
   const double kl = std::sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
@@ -59,7 +64,23 @@ void orbit_camera(const double cam[11], double orbit_deg, int f, double out[13])
   const double kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
   double from[3];
   for (int i = 0; i < 3; ++i) from[i] = la[i] + v[i] * c + kx[i] * s + k[i] * kv * (1.0 - c);
-  rt_camera_derive(from, la, up, cam[9], cam[10], out);
+  rt_camera_derive_lens(from, la, up, cam[9], cam[10], lens[0], lens[1], out);
+}
+// the scene file's camera with its thin lens, if it has one (aperture != 0): out as rt_camera_derive_lens
+bool lens_camera(const RtSceneFile* sf, double out[20]) {
+  double cam[11], lens[2];
+  rt_scene_camera(sf, cam);
+  rt_scene_lens(sf, lens);
+  if (lens[0] == 0.0) return false;
+  rt_camera_derive_lens(cam, cam + 3, cam + 6, cam[9], cam[10], lens[0], lens[1], out);
+  return true;
+}
+// a resident scene through that lens (nothing for a pinhole scene: it keeps RtScene's camera)
+int set_scene_lens(const RtSceneFile* sf, RtHipScene* hs) {
+  double c[20];
+  if (!lens_camera(sf, c)) return RT_OK;
+  const int rc = rt_hip_set_camera(hs, c, c + 3, c + 6, c + 9);
+  return rc != RT_OK ? rc : rt_hip_set_lens(hs, c + 13, c + 16, c[19]);
 }
 std::string frame_name(const char* prefix, int f) {
   char name[4096];
@@ -170,8 +191,9 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
   (void)rt_hip_group_set_option(hs, "prepare_host_output", 2);  // (pinned staging for the two frames in flight + the copy path, at set-up: not inside the first submit)
   const auto t_begin = std::chrono::steady_clock::now();
-  double cam[11];
+  double cam[11], lens[2];
   rt_scene_camera(sf, cam);
+  rt_scene_lens(sf, lens);
   const size_t bytes = (size_t)sc->width * sc->height * 3;
   const unsigned W = anim_writers();
   std::vector<std::vector<uint8_t>> store(2 + W, std::vector<uint8_t>(bytes));
@@ -197,13 +219,14 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
   };
   int submitted = 0, collected = 0;
   for (int f = 0; f < frames && status == 0 && !writers.failed(); ++f) {
-    double out[13];
+    double out[20];
     const auto t0 = std::chrono::steady_clock::now();
     uint8_t* buf = writers.take_buffer();
     const auto t1 = std::chrono::steady_clock::now();
-    orbit_camera(cam, orbit_deg, f, out);
+    orbit_camera(cam, lens, orbit_deg, f, out);
     rt_hip_group_set_camera(hs, out, out + 3, out + 6, out + 9);
-    rc = rt_hip_group_submit(hs, buf);
+    rc = lens[0] != 0.0 ? rt_hip_group_set_lens(hs, out + 13, out + 16, out[19]) : RT_OK;
+    if (rc == RT_OK) rc = rt_hip_group_submit(hs, buf);
     stats.host_us[0] += ms_between(t0, t1) * 1e3;
     stats.host_us[1] += ms_between(t1, std::chrono::steady_clock::now()) * 1e3;
     if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; break; }
@@ -225,6 +248,7 @@ int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool den
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
   int rc = rt_hip_scene_create(sc, 0, &hs);
+  if (rc == RT_OK) rc = set_scene_lens(sf, hs);
   std::printf("\nRendering %s\n", filename);  // main.rs:18
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
   std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);
@@ -253,6 +277,7 @@ int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t m
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
   int rc = rt_hip_scene_create(sc, 0, &hs);
+  if (rc == RT_OK) rc = set_scene_lens(sf, hs);
   std::printf("\nRendering %s\n", filename);  // main.rs:18
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
   std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);
@@ -293,8 +318,9 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
     std::fprintf(stderr, "render failed: RT_GPUS = %u but only %d device(s) visible\n", G, ndev);
     return 101;
   }
-  double cam[11];
+  double cam[11], lens[2];
   rt_scene_camera(sf, cam);
+  rt_scene_lens(sf, lens);
   const size_t bytes = (size_t)sc->width * sc->height * 3;
   const uint32_t w = sc->width, h = sc->height;
   std::mutex out_mu;
@@ -311,11 +337,12 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
       std::thread writer;
       int write_rc = RT_OK, i = 0;
       for (int f = (int)g; f < frames && write_rc == RT_OK; f += (int)G, ++i) {
-        double out[13];
-        orbit_camera(cam, orbit_deg, f, out);
+        double out[20];
+        orbit_camera(cam, lens, orbit_deg, f, out);
         rt_hip_set_camera(hs, out, out + 3, out + 6, out + 9);
+        rc = lens[0] != 0.0 ? rt_hip_set_lens(hs, out + 13, out + 16, out[19]) : RT_OK;
         RtStats st{};
-        rc = rt_hip_render_to_host(hs, buf[i & 1].data(), &st);
+        if (rc == RT_OK) rc = rt_hip_render_to_host(hs, buf[i & 1].data(), &st);
         const std::string fname = frame_name(prefix, f);
         {
           std::lock_guard<std::mutex> lk(out_mu);
@@ -340,6 +367,23 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
   stats.report("frames", frames, G, 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), 0.0);
   for (int s : status) if (s) return s;
   return 0;
+}
+
+// rt_render_rgb8 for a scene with a thin lens (RtScene carries none): the same one-frame group, with the lens camera c (rt_camera_derive_lens)
+int render_lens_rgb8(const RtScene* sc, const double c[20], uint8_t* out_rgb8, RtStats* stats) {
+  const auto t0 = std::chrono::steady_clock::now();
+  RtHipGroup* g = nullptr;
+  int rc = rt_hip_group_create(sc, 0, &g);
+  if (rc != RT_OK) return rc;
+  (void)rt_hip_group_set_option(g, "tile_order", 1);  // (one frame: no later frame could use a learned order — rt_render_rgb8's setting)
+  rc = rt_hip_group_set_camera(g, c, c + 3, c + 6, c + 9);
+  if (rc == RT_OK) rc = rt_hip_group_set_lens(g, c + 13, c + 16, c[19]);
+  if (rc == RT_OK) rc = rt_hip_group_set_option(g, "prepare_host_output", 1);
+  const double setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (rc == RT_OK) rc = rt_hip_group_render_to_host(g, out_rgb8, stats);
+  if (rc == RT_OK && stats) stats->setup_ms = setup_ms;
+  rt_hip_group_destroy(g);
+  return rc;
 }
 
 int animate(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg) {
@@ -463,7 +507,8 @@ int run(int argc, char** argv) {
   const auto t_hip = std::chrono::steady_clock::now();
   if (g_hip_init.joinable()) g_hip_init.join();  // (what of the runtime's start-up the load did not cover)
   const double hip_wait_ms = ms_since(t_hip), hip_init_ms = g_hip_init_ms;
-  rc = rt_render_rgb8(sc, pixels.data(), &st);
+  double cam_lens[20];
+  rc = lens_camera(sf, cam_lens) ? render_lens_rgb8(sc, cam_lens, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
   if (rc != RT_OK) {
     std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error());
     rt_scene_free(sf);

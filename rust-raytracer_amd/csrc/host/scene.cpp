@@ -133,6 +133,40 @@ extern "C" void rt_camera_derive(const double lf[3], const double la[3], const d
   out[12] = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
 }
 
+// camera.rs:45-77 with a thin lens: the viewport moves to the focus plane at distance f, r = aperture / 2.
+// aperture 0 is the pinhole: f = 1 gives rt_camera_derive's bits (x * 1.0 is x).
+extern "C" void rt_camera_derive_lens(const double lf[3], const double la[3], const double up[3], double vfov_deg, double aspect,
+                                      double aperture, double focus_dist, double out[20]) {
+  auto unit = [](const double v[3], double o[3]) {
+    double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    o[0] = v[0] / l; o[1] = v[1] / l; o[2] = v[2] / l;
+  };
+  auto cross = [](const double a[3], const double b[3], double o[3]) {
+    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+  };
+  const double f = aperture == 0.0 ? 1.0 : focus_dist;
+  const double theta = vfov_deg * (3.14159265358979323846264338327950288 / 180.0);
+  const double half_height = std::tan(theta / 2.0);
+  const double half_width = aspect * half_height;
+  const double hw = half_width * f, hh = half_height * f;
+  double d[3] = {lf[0] - la[0], lf[1] - la[1], lf[2] - la[2]};
+  double w[3], u[3], v[3], c[3];
+  unit(d, w);
+  cross(up, w, c);
+  unit(c, u);
+  cross(w, u, v);
+  for (int i = 0; i < 3; ++i) {
+    out[i] = lf[i];
+    out[3 + i] = ((lf[i] - u[i] * hw) - v[i] * hh) - w[i] * f;
+    out[6 + i] = (u[i] * 2.0) * hw;
+    out[9 + i] = (v[i] * 2.0) * hh;
+    out[13 + i] = u[i];
+    out[16 + i] = v[i];
+  }
+  out[12] = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  out[19] = aperture / 2.0;
+}
+
 // reference raytracer.rs:220-229
 extern "C" uint32_t rt_find_lights(const RtSphere* spheres, uint32_t n, uint32_t* out_idx, uint32_t cap) {
   uint32_t k = 0;
@@ -153,6 +187,9 @@ struct RtSceneFile {
   std::unique_ptr<uint8_t, void (*)(void*)> sky_pixels{nullptr, std::free};
   std::string sky_path;
   double look_from[3]{}, look_at[3]{}, vup[3]{}, vfov = 0, aspect = 0, focal_length = 0;
+  // the thin lens: the file's "aperture" / "focus_dist" if it had them (has_*: rt_scene_to_json writes only those)
+  double aperture = 0, focus_dist = 0;
+  bool has_aperture = false, has_focus_dist = false;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
   // concurrently, beside the parse), everything (read + parse + schema + waiting for the decodes)
   double read_ms = 0, json_ms = 0, jpeg_ms = 0, total_ms = 0;
@@ -285,8 +322,11 @@ void build_scene(const Value& root, RtSceneFile& sf) {
   }
 
   // camera.rs:29-42 CameraParams -> Camera::new
-  const Value* cam[5];
-  struct_fields(*cf[5], "CameraParams", {"look_from", "look_at", "vup", "vfov", "aspect"}, cam);
+  // (+ the optional thin-lens keys of a map; the sequence form stays the reference's five fields)
+  const Value* cam[7] = {};
+  if (cf[5]->kind == Value::Array) struct_fields(*cf[5], "CameraParams", {"look_from", "look_at", "vup", "vfov", "aspect"}, cam);
+  else struct_fields(*cf[5], "CameraParams", {"look_from", "look_at", "vup", "vfov", "aspect", "aperture", "focus_dist"}, cam,
+                     {false, false, false, false, false, true, true});
   as_point(*cam[0], "camera.look_from", sf.look_from);
   as_point(*cam[1], "camera.look_at", sf.look_at);
   as_point(*cam[2], "camera.vup", sf.vup);
@@ -297,6 +337,15 @@ void build_scene(const Value& root, RtSceneFile& sf) {
   std::memcpy(sc.cam_origin, c, 24); std::memcpy(sc.cam_lower_left, c + 3, 24);
   std::memcpy(sc.cam_horizontal, c + 6, 24); std::memcpy(sc.cam_vertical, c + 9, 24);
   sf.focal_length = c[12];
+  sf.has_aperture = cam[5] != nullptr; sf.has_focus_dist = cam[6] != nullptr;
+  if (sf.has_aperture) {
+    sf.aperture = as_f64(*cam[5], "camera.aperture");
+    if (!(sf.aperture >= 0.0)) bad("camera.aperture must be finite and >= 0, got " + cam[5]->text);
+  }
+  if (sf.has_focus_dist) {
+    sf.focus_dist = as_f64(*cam[6], "camera.focus_dist");
+    if (!(sf.focus_dist > 0.0)) bad("camera.focus_dist must be finite and > 0, got " + cam[6]->text);
+  }
 
   const Value& objs = *cf[6];
   if (objs.kind != Value::Array) bad("objects: expected an array");
@@ -406,7 +455,10 @@ std::string scene_json(const RtSceneFile& sf) {
   if (sc.sky_mode == RT_SKY_NONE) o += "null";
   else o += "{\"texture\":" + jstr(sc.sky_mode == RT_SKY_TEXTURE ? sf.sky_path : std::string()) + "}";
   o += ",\"camera\":{\"look_from\":" + point(sf.look_from) + ",\"look_at\":" + point(sf.look_at) +
-       ",\"vup\":" + point(sf.vup) + ",\"vfov\":" + f64s(sf.vfov) + ",\"aspect\":" + f64s(sf.aspect) + "},\"objects\":[";
+       ",\"vup\":" + point(sf.vup) + ",\"vfov\":" + f64s(sf.vfov) + ",\"aspect\":" + f64s(sf.aspect);
+  if (sf.has_aperture) o += ",\"aperture\":" + f64s(sf.aperture);
+  if (sf.has_focus_dist) o += ",\"focus_dist\":" + f64s(sf.focus_dist);
+  o += "},\"objects\":[";
   for (size_t i = 0; i < sf.spheres.size(); ++i) {
     const RtSphere& s = sf.spheres[i];
     if (i) o += ",";
@@ -482,6 +534,11 @@ extern "C" void rt_scene_camera(const RtSceneFile* sf, double out[11]) {
   if (!sf || !out) return;
   for (int i = 0; i < 3; ++i) { out[i] = sf->look_from[i]; out[3 + i] = sf->look_at[i]; out[6 + i] = sf->vup[i]; }
   out[9] = sf->vfov; out[10] = sf->aspect;
+}
+extern "C" void rt_scene_lens(const RtSceneFile* sf, double out[2]) {
+  if (!sf || !out) return;
+  out[0] = sf->aperture;
+  out[1] = sf->has_focus_dist ? sf->focus_dist : sf->focal_length;
 }
 extern "C" void rt_free(void* p) { std::free(p); }
 

@@ -52,6 +52,7 @@ def _bind(path, probes):
     L.rt_hip_scene_query.restype = C.c_int64
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_hip_set_camera.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4
+    L.rt_hip_set_lens.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]
     L.rt_hip_render_to_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_hip_accumulate.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.rt_hip_resolve.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -76,6 +77,7 @@ def _bind(path, probes):
     L.rt_hip_group_size.argtypes = [C.c_void_p]
     L.rt_hip_group_size.restype = C.c_uint32
     L.rt_hip_group_set_camera.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4
+    L.rt_hip_group_set_lens.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]
     L.rt_hip_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.rt_hip_group_render_to_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_hip_group_render.argtypes = [C.c_void_p, C.POINTER(abi.RtStats)]
@@ -170,6 +172,10 @@ class HipScene:
         """move the camera of the resident scene (the four vectors of camera.rs:52-63)"""
         v = [(C.c_double * 3)(*x) for x in (origin, lower_left, horizontal, vertical)]
         _check(self._L.rt_hip_set_camera(self._h, *v), self._L)
+
+    def set_lens(self, u, v, lens_radius):
+        """thin-lens camera: the unit vectors u, v of the lens plane and its radius; 0 = the pinhole"""
+        _check(self._L.rt_hip_set_lens(self._h, (C.c_double * 3)(*u), (C.c_double * 3)(*v), float(lens_radius)), self._L)
 
     def render_to_host(self):
         """whole frame into a numpy [h,w,3] array (blocking) + stats"""
@@ -333,6 +339,9 @@ class HipGroup:
     def set_camera(self, origin, lower_left, horizontal, vertical):
         v = [(C.c_double * 3)(*x) for x in (origin, lower_left, horizontal, vertical)]
         _check(self._L.rt_hip_group_set_camera(self._h, *v), self._L)
+
+    def set_lens(self, u, v, lens_radius):
+        _check(self._L.rt_hip_group_set_lens(self._h, (C.c_double * 3)(*u), (C.c_double * 3)(*v), float(lens_radius)), self._L)
 
     def render_to_host(self, out=None):
         import numpy as np

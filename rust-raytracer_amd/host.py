@@ -38,6 +38,10 @@ def lib():
         L.rt_host_last_error.restype = C.c_char_p
         L.rt_camera_derive.argtypes = [C.POINTER(C.c_double)] * 3 + [C.c_double, C.c_double, C.POINTER(C.c_double)]
         L.rt_camera_derive.restype = None
+        L.rt_camera_derive_lens.argtypes = [C.POINTER(C.c_double)] * 3 + [C.c_double] * 4 + [C.POINTER(C.c_double)]
+        L.rt_camera_derive_lens.restype = None
+        L.rt_scene_lens.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.rt_scene_lens.restype = None
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
         L.rt_jpeg_decode_file.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -113,6 +117,17 @@ def camera_derive(look_from, look_at, vup, vfov, aspect):
     lib().rt_camera_derive(arr(look_from), arr(look_at), arr(vup), vfov, aspect, out)
     o = list(out)
     return {"origin": o[0:3], "lower_left_corner": o[3:6], "horizontal": o[6:9], "vertical": o[9:12], "focal_length": o[12]}
+
+
+def camera_derive_lens(look_from, look_at, vup, vfov, aspect, aperture, focus_dist):
+    """Camera::new with a thin lens (DESIGN.md §13): camera_derive's five entries on the focus plane + the unit vectors u, v and
+    the lens radius aperture / 2 — what HipScene.set_camera and HipScene.set_lens take"""
+    arr = lambda v: (C.c_double * 3)(*v)
+    out = (C.c_double * 20)()
+    lib().rt_camera_derive_lens(arr(look_from), arr(look_at), arr(vup), vfov, aspect, aperture, focus_dist, out)
+    o = list(out)
+    return {"origin": o[0:3], "lower_left_corner": o[3:6], "horizontal": o[6:9], "vertical": o[9:12], "focal_length": o[12],
+            "u": o[13:16], "v": o[16:19], "lens_radius": o[19]}
 
 
 def jpeg_decode(path):
