@@ -5,11 +5,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
+#include <optional>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -54,7 +57,12 @@ struct Clock {   // mark("x") books the time since the previous mark under x
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   void mark(const char* name) {
     const auto n = std::chrono::steady_clock::now();
-    add(name, std::chrono::duration<double, std::milli>(n - t).count());
+    const double ms = std::chrono::duration<double, std::milli>(n - t).count();
+#ifdef RT_DEV_KNOBS  // (development: RT_GROUP_TRACE=1 prints every stage of every rank as it ends, to stderr)
+    static const bool trace = std::getenv("RT_GROUP_TRACE") != nullptr;
+    if (trace) std::fprintf(stderr, "[rt] %s %.3f ms\n", name, ms);
+#endif
+    add(name, ms);
     t = n;
   }
 };
@@ -74,34 +82,81 @@ extern "C" const char* rt_hip_setup_profile(void) {
 
 constexpr uint32_t RT_TIMELINE_WAVES = 8192;  // profile builds: {start, end} wall clock per wave behind the counters
 
+// One device allocation, owned: freed with its owner (on the current device: the owner sets it).  ensure() is the only place that
+// frees an existing buffer to allocate a larger one.
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  template <typename T = void> T* get() const { return static_cast<T*>(p); }
+  // At least `bytes`; *grew: it was (re)allocated, its contents are undefined.  Before an existing buffer is freed the work that may
+  // still read it has finished: the whole device's, or only `stream`'s where the caller knows that is the one stream using it.
+  // Runs only when a buffer grows — never per frame in steady state.
+  int ensure(size_t bytes, bool* grew = nullptr, std::optional<hipStream_t> stream = std::nullopt) {
+    if (grew) *grew = false;
+    if (bytes <= cap) return RT_OK;
+    if (p) {
+      RT_HIP_TRY(stream ? hipStreamSynchronize(*stream) : hipDeviceSynchronize());
+      (void)hipFree(p);
+      p = nullptr; cap = 0;
+    }
+    RT_HIP_TRY(hipMalloc(&p, bytes));
+    cap = bytes;
+    if (grew) *grew = true;
+    return RT_OK;
+  }
+};
+
 struct RtHipScene {
   int device = 0;
-  bool owns_tables = true;  // false: a VIEW of another scene (rt_hip_scene_clone_view): it shares that scene's tables, textures and host copies
-                            // and owns only what a launch writes — counters, stats slots, queue order, light overflow, framebuffer
+  // What rt_hip_scene_create builds, once: shared by the scene and its views (rt_hip_scene_clone_view), freed with the last of them.
+  struct Resident {
+    int device = 0;
+    DevBuf geom, mat, lights, tex, sky, tex4, sky4, matc, cell_word, cell_items, large, large_geom;
+    DevBuf all;              // 0..n-1: the `large` list of the brute-force arm (variant 1)
+    // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
+    // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
+    // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
+    // 10 - 25 ms later — the next kernel launch waits for that.  Found in round 6 as a one-shot frame of the test scene whose
+    // first launch started 20 ms late in two runs of three (profiles/r06_run5_first_launch_wait.log); with the buffers kept,
+    // 12 of 12 runs start in 0.07 ms.  They are freed with the scene, when nothing waits for the queues.
+    rtc::TexelVec keep_tex4, keep_sky4;
+    std::vector<uint8_t> keep_tex_rgb8, keep_sky_rgb8;
+    size_t texel_bytes = 0;
+    rtc::GridDesc grid{};    // the product grid (variant 0)
+    bool has_lights = false, simple_colour = false;
+    int num_cus = 0;
+    size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
+    ~Resident() { (void)hipSetDevice(device); }  // (the buffers are freed after this body)
+  };
+  std::shared_ptr<const Resident> res;
   RtScene host{};          // scalar fields only (pointers are not kept)
   rtc::DevScene dev{};     // device pointers filled in
-  bool has_lights = false, simple_colour = false;
-  void* d_geom = nullptr; void* d_mat = nullptr; void* d_lights = nullptr;
-  void* d_tex = nullptr; void* d_sky = nullptr; void* d_tex4 = nullptr; void* d_sky4 = nullptr;
-  // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
-  // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
-  // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
-  // 10 - 25 ms later — the next kernel launch waits for that.  Found in round 6 as a one-shot frame of the test scene whose
-  // first launch started 20 ms late in two runs of three (profiles/r06_run5_first_launch_wait.log); with the buffers kept,
-  // 12 of 12 runs start in 0.07 ms.  They are freed with the scene, when nothing waits for the queues.
-  rtc::TexelVec keep_tex4, keep_sky4;
-  std::vector<uint8_t> keep_tex_rgb8, keep_sky_rgb8;
-  size_t texel_bytes = 0;
-  void* d_matc = nullptr; void* d_cell_word = nullptr; void* d_cell_items = nullptr; void* d_large = nullptr;
-  void* d_all = nullptr;   // 0..n-1: the `large` list of the brute-force arm (variant 1)
-  void* d_large_geom = nullptr;
-  rtc::GridDesc grid{};    // the product grid (variant 0)
-  unsigned long long* d_counters = nullptr;  // 4 counters + the work-queue cursor
-  int num_cus = 0;
+  struct Options {         // what rt_hip_set_option sets (a view starts with its scene's)
+    int variant = 0;
+    int tile_log2 = -1;      // -1 = automatic; else tiles of 4^k pixels, k = 0..3
+    int tile_shape = 0;      // 0: 2^k x 2^k squares (default: 0.9 % faster); 1: runs of 4^k pixels of one scanline (contiguous
+                             // framebuffer bytes: HBM writes 10.9 -> 5.9 MiB per 1200x800 frame, profiles/r02_run8_*)
+    int tile_affinity = 1;   // "tile_affinity" option: runs of tiles belong to one XCD's queue (framebuffer lines complete in one L2)
+    int order_mode = 2;      // "tile_order" option: 0 top row first, 1 bottom row first, 2 deepest tiles of the previous frame first
+                             // (a frame without a previous one: bottom row first)
+    int force_lit = 0;       // "force_lit" option (diagnostics)
+    int light_pool_cap = 0;  // "light_pool" option: cap on the light-frame pool of lit scenes (0 = automatic; tests shrink it to force repeats and overflows)
+    int light_base_cap = 0;  // "light_base_pool" option: the same for the pool of colour-map bases
+    int light_nest_pool = 1; // "light_nest_pool" option: 0 = nested light activations always go through the HBM overflow (tests)
+    int chunk_spp = 0;       // 0 = automatic
+    int tile_batch = 0;      // 0 = automatic; else tiles a workgroup takes from the queue per atomic, 1..64
+  } opt;
+
+  // What a launch writes — each scene and view has its own.
+  DevBuf counters;          // 4 counters + the work-queue cursor
   int cfg_key = -1; size_t cfg_lds = 0; int cfg_per_cu = 0;  // cached launch configuration
-  void* d_frame = nullptr; size_t frame_bytes = 0;           // framebuffer of rt_hip_render_to_host
+  DevBuf frame;             // framebuffer of rt_hip_render_to_host
   // queue order feedback (rt_kernel.hip KArgs::tile_order): depths measured by the last frame of this tile geometry
-  uint32_t* d_tile_depth = nullptr; uint32_t* d_tile_order = nullptr; size_t order_cap = 0;
+  DevBuf tile_depth, tile_order;
   struct OrderKey {         // tile geometry (+ row tiles) an order belongs to: compared field by field
     uint32_t n_tiles = 0, tile_log2 = 0, tile_shape = 0, aff_group_log2 = 0, tile_rows = 0, first_tile = 0, tile_stride = 0, local_rows = 0;
     bool operator==(const OrderKey& o) const {
@@ -109,25 +164,12 @@ struct RtHipScene {
              tile_rows == o.tile_rows && first_tile == o.first_tile && tile_stride == o.tile_stride && local_rows == o.local_rows;
     }
   } order_key;              // n_tiles == 0: none yet
-  bool order_ready = false; // d_tile_order holds an order for order_key
-  bool depth_fresh = false; // d_tile_depth holds depths of THIS view (measured by its last frame) that d_tile_order does not reflect yet
+  bool order_ready = false; // tile_order holds an order for order_key
+  bool depth_fresh = false; // tile_depth holds depths of THIS view (measured by its last frame) that tile_order does not reflect yet
   int order_age = 0;        // frames since the order was last invalidated (geometry / camera / option change)
-  int tile_affinity = 1;    // "tile_affinity" option: runs of tiles belong to one XCD's queue (framebuffer lines complete in one L2)
-  int order_mode = 2;       // "tile_order" option: 0 top row first, 1 bottom row first, 2 deepest tiles of the previous frame first
-                            // (a frame without a previous one: bottom row first)
-  int force_lit = 0;       // "force_lit" option (diagnostics)
-  int light_pool_cap = 0;  // "light_pool" option: cap on the light-frame pool of lit scenes (0 = automatic; tests shrink it to force repeats and overflows)
-  int light_base_cap = 0;  // "light_base_pool" option: the same for the pool of colour-map bases
-  int light_nest_pool = 1; // "light_nest_pool" option: 0 = nested light activations always go through the HBM overflow (tests)
-  void* d_light_overflow = nullptr; size_t light_overflow_bytes = 0;  // lit scenes: 560 B per lane of the largest launch so far (rt_core.h lane_light_begin)
-  size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
+  DevBuf light_overflow;    // lit scenes: 560 B per lane of the largest launch so far (rt_core.h lane_light_begin)
   uint32_t last_pool_slots = 0, last_base_slots = 0; size_t last_lds_bytes = 0; bool last_lds_tables = false;  // of the last launch (rt_hip_scene_query)
-  int last_kernel = -1;    // megakernel instantiation of the last launch, encoded like cfg_key (rt_hip_scene_query "last_kernel"; -1: none yet)
-  int chunk_spp = 0;       // 0 = automatic
-  int tile_batch = 0;      // 0 = automatic; else tiles a workgroup takes from the queue per atomic, 1..64
-  int tile_log2 = -1;      // -1 = automatic; else tiles of 4^k pixels, k = 0..3
-  int tile_shape = 0;      // 0: 2^k x 2^k squares (default: 0.9 % faster); 1: runs of 4^k pixels of one scanline (contiguous
-                           // framebuffer bytes: HBM writes 10.9 -> 5.9 MiB per 1200x800 frame, profiles/r02_run8_*)
+  int last_kernel = -1;    // megakernel instantiation of the last launch, its Kernel::key (rt_hip_scene_query "last_kernel"; -1: none yet)
 
   // What rt_hip_wait reports about a launch lives in one of two SLOTS, used alternately: its event pair, the rows and waves
   // it covered, and a pinned host copy of its counters that an async copy fills right behind the kernel (stream-ordered:
@@ -148,23 +190,20 @@ struct RtHipScene {
   bool in_flight = false;  // a launch has been enqueued and rt_hip_wait has not returned for it yet
   uint64_t last_waves = 0;
   uint32_t last_tiles_x = 0;
-  int variant = 0;
   // progressive rendering, host form (rt_hip_refine_to_host): the scene's own accumulator (width x height x 3 u64, allocated at
   // first use) and the samples per pixel it holds; accum_zero: it must be cleared before the next pass adds to it
-  unsigned long long* d_accum = nullptr; size_t accum_bytes = 0;
+  DevBuf accum;
   uint32_t accum_samples = 0;
   bool accum_zero = true;
   void reset_accum() { accum_samples = 0; accum_zero = true; aov_ready = false; }
   // denoising (rt_hip_denoise): the filter's float4 ping-pong (2 x width x height x 16 B), and for
   // rt_hip_refine_to_host_denoised the resolved linear frame (x 12 B) and the AOV record of the accumulator's start (x 32 B); all
-  // allocated at first use.  aov_ready: d_dn_aov holds the AOVs of the current accumulator (reset_accum clears it)
-  void* d_dn_ping = nullptr; size_t dn_ping_bytes = 0;
-  void* d_dn_lin = nullptr; void* d_dn_aov = nullptr; size_t dn_host_px = 0;
+  // allocated at first use.  aov_ready: dn_aov holds the AOVs of the current accumulator (reset_accum clears it)
+  DevBuf dn_ping, dn_lin, dn_aov;
   bool aov_ready = false;
   // adaptive frames, host form (rt_hip_render_adaptive_to_host): its own now / prev accumulators and per-tile list, errors and
   // counts (allocated at first use), and what each round of the last frame did: {tiles, samples per pixel after it, kernel ms}
-  unsigned long long* d_ad_now = nullptr; unsigned long long* d_ad_prev = nullptr; size_t ad_bytes = 0;
-  uint32_t* d_ad_list = nullptr; double* d_ad_err = nullptr; uint32_t* d_ad_spp = nullptr; size_t ad_tiles = 0;
+  DevBuf ad_now, ad_prev, ad_list, ad_err, ad_spp;
   struct AdRound { uint32_t tiles, spp; double kernel_ms; };
   std::vector<AdRound> ad_rounds;
   Slot& last_slot() { return slot[(n_launches + 1) & 1]; }  // the slot of the most recent launch
@@ -216,10 +255,8 @@ extern "C" int rt_hip_device_warm(int device) {
   RT_HIP_TRY(hipMalloc(&p, 256));  // (the first allocation creates the device's context)
   hipLaunchKernelGGL(rtk::rt_warm_up, dim3(1), dim3(64), 0, nullptr);  // (the first launch loads this library's code object)
   RT_HIP_TRY(hipGetLastError());
-  if (!std::getenv("RT_NO_SCRATCH_WARMUP")) {
-    hipLaunchKernelGGL(rtk::rt_warm_up_scratch, dim3(1), dim3(64), 0, nullptr, (uint32_t*)nullptr, 1u);  // (... and gives the NULL stream's queue its scratch memory)
-    RT_HIP_TRY(hipGetLastError());
-  }
+  hipLaunchKernelGGL(rtk::rt_warm_up_scratch, dim3(1), dim3(64), 0, nullptr, (uint32_t*)nullptr, 1u);  // (... and gives the NULL stream's queue its scratch memory)
+  RT_HIP_TRY(hipGetLastError());
   RT_HIP_TRY(hipDeviceSynchronize());
   (void)hipFree(p);
   return RT_OK;
@@ -228,14 +265,6 @@ extern "C" int rt_hip_device_warm(int device) {
 extern "C" void rt_hip_scene_destroy(RtHipScene* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  if (s->owns_tables)
-    for (void* p : {s->d_geom, s->d_mat, s->d_lights, s->d_tex, s->d_sky, s->d_tex4, s->d_sky4, s->d_matc, s->d_cell_word, s->d_cell_items, s->d_large,
-                    s->d_all, s->d_large_geom})
-      if (p) (void)hipFree(p);
-  for (void* p : {(void*)s->d_counters, s->d_frame, (void*)s->d_tile_depth, (void*)s->d_tile_order, s->d_light_overflow, (void*)s->d_accum,
-                  (void*)s->d_ad_now, (void*)s->d_ad_prev, (void*)s->d_ad_list, (void*)s->d_ad_err, (void*)s->d_ad_spp,
-                  s->d_dn_ping, s->d_dn_lin, s->d_dn_aov})
-    if (p) (void)hipFree(p);
   for (auto& sl : s->slot) {
     for (hipEvent_t e : {sl.ev_start, sl.ev_stop, sl.ev_copied}) if (e) (void)hipEventDestroy(e);
     if (sl.h_counters) (void)hipHostFree(sl.h_counters);
@@ -245,10 +274,11 @@ extern "C" void rt_hip_scene_destroy(RtHipScene* s) {
 
 namespace {
 template <typename V>
-int upload(void** dst, const V& v) {
-  size_t bytes = v.size() * sizeof(typename V::value_type);
-  RT_HIP_TRY(hipMalloc(dst, bytes ? bytes : 16));
-  if (bytes) RT_HIP_TRY(hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice));
+int upload(DevBuf& dst, const V& v) {
+  const size_t bytes = v.size() * sizeof(typename V::value_type);
+  const int rc = dst.ensure(bytes ? bytes : 16);  // (an empty table is 16 bytes, never a null pointer)
+  if (rc != RT_OK) return rc;
+  if (bytes) RT_HIP_TRY(hipMemcpy(dst.p, v.data(), bytes, hipMemcpyHostToDevice));
   return RT_OK;
 }
 }  // namespace
@@ -256,8 +286,9 @@ int upload(void** dst, const V& v) {
 namespace {
 // what a LAUNCH of a scene writes: the counter block with the tile-queue cursors, the two stats slots (events + pinned words)
 int alloc_launch_state(RtHipScene* s) {
-  if (hipMalloc((void**)&s->d_counters, (32 + 4 * RT_TIMELINE_WAVES) * sizeof(unsigned long long)) != hipSuccess)
-    return fail(RT_ERR_HIP, "hipMalloc(counters) failed");
+  const size_t counter_bytes = (32 + 4 * RT_TIMELINE_WAVES) * sizeof(unsigned long long);
+  const int rc = s->counters.ensure(counter_bytes);
+  if (rc != RT_OK) return rc;
   for (auto& sl : s->slot) {
     if (hipEventCreate(&sl.ev_start) != hipSuccess || hipEventCreate(&sl.ev_stop) != hipSuccess ||
         hipEventCreateWithFlags(&sl.ev_copied, hipEventDisableTiming) != hipSuccess ||
@@ -265,7 +296,7 @@ int alloc_launch_state(RtHipScene* s) {
       return fail(RT_ERR_HIP, "hipEventCreate/hipHostMalloc failed");
     std::memset(sl.h_counters, 0, RT_SLOT_COUNTERS * sizeof(unsigned long long));
   }
-  if (hipMemset(s->d_counters, 0, (32 + 4 * RT_TIMELINE_WAVES) * sizeof(unsigned long long)) != hipSuccess)
+  if (hipMemset(s->counters.p, 0, counter_bytes) != hipSuccess)
     return fail(RT_ERR_HIP, "hipMemset failed");
   return RT_OK;
 }
@@ -273,23 +304,13 @@ int alloc_launch_state(RtHipScene* s) {
 
 // A second VIEW of a resident scene (internal; the group's overlapped frames): the same tables and textures in HBM, its own
 // launch state — so that a launch of the view and a launch of the scene may be in flight on two streams AT ONCE (a scene itself
-// is not re-entrant: one tile-queue cursor, one counter block).  The view must be destroyed before the scene it was cloned from.
+// is not re-entrant: one tile-queue cursor, one counter block).  The scene and its views may be destroyed in any order.
 int rt_hip_scene_clone_view(const RtHipScene* src, RtHipScene** out) {
   if (!src || !out) return fail(RT_ERR_INVALID, "null argument");
   *out = nullptr;
   RT_HIP_TRY(hipSetDevice(src->device));
   RtHipScene* s = new RtHipScene;
-  s->device = src->device; s->owns_tables = false;
-  s->host = src->host; s->dev = src->dev;
-  s->has_lights = src->has_lights; s->simple_colour = src->simple_colour;
-  s->d_geom = src->d_geom; s->d_mat = src->d_mat; s->d_lights = src->d_lights; s->d_tex = src->d_tex; s->d_sky = src->d_sky;
-  s->d_tex4 = src->d_tex4; s->d_sky4 = src->d_sky4; s->texel_bytes = src->texel_bytes; s->d_matc = src->d_matc;
-  s->d_cell_word = src->d_cell_word; s->d_cell_items = src->d_cell_items; s->d_large = src->d_large; s->d_all = src->d_all;
-  s->d_large_geom = src->d_large_geom; s->grid = src->grid; s->num_cus = src->num_cus; s->lds_cap = src->lds_cap;
-  s->tile_affinity = src->tile_affinity; s->order_mode = src->order_mode; s->force_lit = src->force_lit; s->light_pool_cap = src->light_pool_cap;
-  s->light_base_cap = src->light_base_cap; s->light_nest_pool = src->light_nest_pool; s->chunk_spp = src->chunk_spp; s->tile_batch = src->tile_batch;
-  s->tile_log2 = src->tile_log2; s->tile_shape = src->tile_shape; s->variant = src->variant;
-  s->dev.light_overflow = nullptr;   // (its own: two launches at once park their lanes' records apart)
+  s->device = src->device; s->res = src->res; s->host = src->host; s->dev = src->dev; s->opt = src->opt;
   int rc = alloc_launch_state(s);
   if (rc == RT_OK) rc = warm_up(s);  // (the launch configuration + the lit kernels' overflow slots, outside any frame)
   if (rc == RT_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(RT_ERR_HIP, "hipDeviceSynchronize failed");
@@ -304,9 +325,6 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
   int n = rt_hip_device_count();
   if (n <= 0) return fail(RT_ERR_NO_DEVICE, rt_strerror(RT_ERR_NO_DEVICE));
   if (device < 0 || device >= n) return fail(RT_ERR_INVALID, "device index out of range");
-  static const bool trace = std::getenv("RT_GROUP_TRACE") != nullptr;  // (development: where a scene's creation time goes)
-  const auto t_create = std::chrono::steady_clock::now();
-  auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count(); };
   if (!rtp::tl_in_group) rtp::reset();
   rtp::Clock pc;
   rtc::HostTables t;
@@ -315,70 +333,72 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
   pc.mark("scene.texels_rgbx");
-  const double t_tables = since();
   RT_HIP_TRY(hipSetDevice(device));
-  RtHipScene* s = new RtHipScene;
-  s->device = device;
-  s->host = *scene;
-  s->host.spheres = nullptr; s->host.textures = nullptr; s->host.sky_rgb8 = nullptr;
-  s->has_lights = !t.lights.empty();
-  s->simple_colour = t.simple_colour;
-  s->grid = t.grid;
-  rtc::fill_dev_scene(*scene, t, s->dev);
+  auto r = std::make_shared<RtHipScene::Resident>();
+  r->device = device;
+  r->has_lights = !t.lights.empty();
+  r->simple_colour = t.simple_colour;
+  r->grid = t.grid;
   {
     hipDeviceProp_t prop;
     RT_HIP_TRY(hipGetDeviceProperties(&prop, device));
-    s->num_cus = prop.multiProcessorCount;
+    r->num_cus = prop.multiProcessorCount;
     // 160 KB of LDS per CU on gfx950; the unlit layouts stay below LDS_TABLES_MAX_BYTES (156 KB) as before, the light pools may
     // take what the device says is left
     const size_t dev_lds = prop.sharedMemPerBlock > prop.maxSharedMemoryPerMultiProcessor ? prop.sharedMemPerBlock : prop.maxSharedMemoryPerMultiProcessor;
-    s->lds_cap = std::max<size_t>(rtk::LDS_TABLES_MAX_BYTES, std::min<size_t>(dev_lds, 160u * 1024u));
+    r->lds_cap = std::max<size_t>(rtk::LDS_TABLES_MAX_BYTES, std::min<size_t>(dev_lds, 160u * 1024u));
   }
   pc.mark("scene.device_properties");
   int rc;
-  auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
-  if ((rc = upload(&s->d_geom, t.geom)) != RT_OK) return bail(rc);
-  if ((rc = upload(&s->d_mat, t.mat)) != RT_OK) return bail(rc);
-  if ((rc = upload(&s->d_lights, t.lights)) != RT_OK) return bail(rc);
-  if ((rc = upload(&s->d_matc, t.matc)) != RT_OK) return bail(rc);
-  if ((rc = upload(&s->d_cell_word, t.cell_word)) != RT_OK) return bail(rc);
-  if ((rc = t.grid.wide ? upload(&s->d_cell_items, t.cell_items32) : upload(&s->d_cell_items, t.cell_items)) != RT_OK) return bail(rc);  // (wide tables: the 32-bit item lists)
-  if ((rc = upload(&s->d_large, t.large)) != RT_OK) return bail(rc);
-  if ((rc = upload(&s->d_large_geom, t.large_geom)) != RT_OK) return bail(rc);
+  if ((rc = upload(r->geom, t.geom)) != RT_OK) return rc;
+  if ((rc = upload(r->mat, t.mat)) != RT_OK) return rc;
+  if ((rc = upload(r->lights, t.lights)) != RT_OK) return rc;
+  if ((rc = upload(r->matc, t.matc)) != RT_OK) return rc;
+  if ((rc = upload(r->cell_word, t.cell_word)) != RT_OK) return rc;
+  if ((rc = t.grid.wide ? upload(r->cell_items, t.cell_items32) : upload(r->cell_items, t.cell_items)) != RT_OK) return rc;  // (wide tables: the 32-bit item lists)
+  if ((rc = upload(r->large, t.large)) != RT_OK) return rc;
+  if ((rc = upload(r->large_geom, t.large_geom)) != RT_OK) return rc;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
-    if ((rc = upload(&s->d_all, all)) != RT_OK) return bail(rc);
+    if ((rc = upload(r->all, all)) != RT_OK) return rc;
   }
   pc.mark("scene.upload_tables");
   // textures and sky: resident as 4-byte texels (rt_tables.h build_texels; one dword load per fetch); the caller's RGB8
   // bytes are uploaded too only if some record is outside that path's range (rt_core.h texels_fast)
-  s->texel_bytes = (t.tex4.size() + t.sky4.size()) * 4u;
-  if ((rc = upload(&s->d_tex4, t.tex4)) != RT_OK) return bail(rc);
-  if ((rc = upload(&s->d_sky4, t.sky4)) != RT_OK) return bail(rc);
+  r->texel_bytes = (t.tex4.size() + t.sky4.size()) * 4u;
+  if ((rc = upload(r->tex4, t.tex4)) != RT_OK) return rc;
+  if ((rc = upload(r->sky4, t.sky4)) != RT_OK) return rc;
   {
-    std::vector<uint8_t>& blob = s->keep_tex_rgb8;
+    std::vector<uint8_t>& blob = r->keep_tex_rgb8;
     blob.assign(t.need_rgb8 ? t.tex_bytes : 0, 0);
     if (t.need_rgb8)
       for (uint32_t i = 0; i < scene->n_textures; ++i)
         if (scene->textures[i].nbytes) std::memcpy(&blob[t.tex_off[i]], scene->textures[i].rgb8, scene->textures[i].nbytes);
-    if ((rc = upload(&s->d_tex, blob)) != RT_OK) return bail(rc);
+    if ((rc = upload(r->tex, blob)) != RT_OK) return rc;
   }
   {
-    std::vector<uint8_t>& sky = s->keep_sky_rgb8;
+    std::vector<uint8_t>& sky = r->keep_sky_rgb8;
     if (scene->sky_mode == RT_SKY_TEXTURE && !t.sky_fast) sky.assign(scene->sky_rgb8, scene->sky_rgb8 + scene->sky_w * scene->sky_h * 3);
-    if ((rc = upload(&s->d_sky, sky)) != RT_OK) return bail(rc);
+    if ((rc = upload(r->sky, sky)) != RT_OK) return rc;
   }
-  if (!std::getenv("RT_FREE_HOST_TEXELS")) { s->keep_tex4.swap(t.tex4); s->keep_sky4.swap(t.sky4); }  // (the variable: the round-5 behaviour, for the A/B)
+  r->keep_tex4.swap(t.tex4); r->keep_sky4.swap(t.sky4);
   pc.mark("scene.upload_texels");
+  RtHipScene* s = new RtHipScene;
+  s->device = device;
+  s->host = *scene;
+  s->host.spheres = nullptr; s->host.textures = nullptr; s->host.sky_rgb8 = nullptr;
+  rtc::fill_dev_scene(*scene, t, s->dev);
+  s->dev.geom = r->geom.get<const rtc::SphereGeom>(); s->dev.mat = r->mat.get<const rtc::SphereMat>();
+  s->dev.lights = r->lights.get<const uint32_t>();
+  s->dev.tex = r->tex.get<const uint8_t>(); s->dev.sky = r->sky.get<const uint8_t>();
+  s->dev.tex4 = r->tex4.get<const uint32_t>(); s->dev.sky4 = r->sky4.get<const uint32_t>();
+  s->dev.matc = r->matc.get<const rtc::MatCore>(); s->dev.cell_word = r->cell_word.get<const uint32_t>();
+  s->dev.cell_items = r->cell_items.get<const uint16_t>(); s->dev.large = r->large.get<const uint32_t>();
+  s->dev.large_geom = r->large_geom.get<const rtc::SphereGeom>();
+  s->res = std::move(r);
+  auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
-  s->dev.geom = (const rtc::SphereGeom*)s->d_geom; s->dev.mat = (const rtc::SphereMat*)s->d_mat;
-  s->dev.lights = (const uint32_t*)s->d_lights;
-  s->dev.tex = (const uint8_t*)s->d_tex; s->dev.sky = (const uint8_t*)s->d_sky;
-  s->dev.tex4 = (const uint32_t*)s->d_tex4; s->dev.sky4 = (const uint32_t*)s->d_sky4;
-  s->dev.matc = (const rtc::MatCore*)s->d_matc; s->dev.cell_word = (const uint32_t*)s->d_cell_word;
-  s->dev.cell_items = (const uint16_t*)s->d_cell_items; s->dev.large = (const uint32_t*)s->d_large;
-  s->dev.large_geom = (const rtc::SphereGeom*)s->d_large_geom;
   // Everything above went through the NULL stream — and hipMemset / hipMemcpy from pageable memory return before the device
   // has finished (they are asynchronous to the host: the fill / the DMA out of the staging buffer may still be queued).
   // The frames run on the CALLER's streams, and a non-blocking stream does not order itself behind the NULL stream: a first
@@ -388,13 +408,10 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
   // kernel attribute / occupancy / (lit scenes) overflow slots (a one-shot rt_render_rgb8 — the reference renders one frame per
   // process — reports this under setup_ms, outside its frame_ms window)
   pc.mark("scene.counters_events_pinned_words");
-  const double t_uploaded = since();
   if ((rc = warm_up(s)) != RT_OK) return bail(rc);
   pc.mark("scene.kernel_configuration");
-  const double t_warm = since();
   if (hipDeviceSynchronize() != hipSuccess) return bail(fail(RT_ERR_HIP, "hipDeviceSynchronize failed"));
   pc.mark("scene.device_idle");
-  if (trace) std::fprintf(stderr, "[rt scene] create: tables %.2f ms, uploads + events done %.2f, warm_up (module, configuration, overflow) %.2f, device idle %.2f\n", t_tables, t_uploaded, t_warm, since());
   *out = s;
   return RT_OK;
 }
@@ -402,17 +419,17 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
 extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) {
   if (!s || !key) return fail(RT_ERR_INVALID, "null argument");
   constexpr int64_t max_variant = 1;
-  if (!std::strcmp(key, "variant")) { if (value < 0 || value > max_variant) return fail(RT_ERR_INVALID, "variant must be 0 (grid walk) or 1 (brute force)"); s->variant = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "tile_log2")) { if (value < -1 || value > 3) return fail(RT_ERR_INVALID, "tile_log2 must be -1..3"); s->tile_log2 = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "tile_shape")) { if (value < 0 || value > 3) return fail(RT_ERR_INVALID, "tile_shape must be 0 (square), 1 (scanline runs), 2 (4:1) or 3 (16:1)"); s->tile_shape = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "tile_affinity")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_affinity must be 0 (off), 1 (large frames) or 2 (any frame of 8+ runs: tests)"); s->tile_affinity = (int)value; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; return RT_OK; }
-  if (!std::strcmp(key, "tile_order")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_order must be 0, 1 or 2"); s->order_mode = (int)value; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; return RT_OK; }
-  if (!std::strcmp(key, "light_pool")) { if (value < 0 || value > 1024 || (value != 0 && value < 32)) return fail(RT_ERR_INVALID, "light_pool must be 0 (automatic) or 32..1024"); s->light_pool_cap = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "light_base_pool")) { if (value < 0 || value > 1024 || (value != 0 && value < 32)) return fail(RT_ERR_INVALID, "light_base_pool must be 0 (automatic) or 32..1024"); s->light_base_cap = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "light_nest_pool")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "light_nest_pool must be 0 or 1"); s->light_nest_pool = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "force_lit")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "force_lit must be 0 or 1"); s->force_lit = (int)value; return RT_OK; }  // (diagnostics: an unlit scene through the lit kernels — what their code costs the ordinary lanes, profiles/r04_run5_lit_sections.log)
-  if (!std::strcmp(key, "tile_batch")) { if (value < 0 || value > 64) return fail(RT_ERR_INVALID, "tile_batch must be 0..64"); s->tile_batch = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "chunk_spp")) { if (value < 0) return fail(RT_ERR_INVALID, "chunk_spp must be >= 0"); s->chunk_spp = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "variant")) { if (value < 0 || value > max_variant) return fail(RT_ERR_INVALID, "variant must be 0 (grid walk) or 1 (brute force)"); s->opt.variant = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "tile_log2")) { if (value < -1 || value > 3) return fail(RT_ERR_INVALID, "tile_log2 must be -1..3"); s->opt.tile_log2 = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "tile_shape")) { if (value < 0 || value > 3) return fail(RT_ERR_INVALID, "tile_shape must be 0 (square), 1 (scanline runs), 2 (4:1) or 3 (16:1)"); s->opt.tile_shape = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "tile_affinity")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_affinity must be 0 (off), 1 (large frames) or 2 (any frame of 8+ runs: tests)"); s->opt.tile_affinity = (int)value; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; return RT_OK; }
+  if (!std::strcmp(key, "tile_order")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_order must be 0, 1 or 2"); s->opt.order_mode = (int)value; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; return RT_OK; }
+  if (!std::strcmp(key, "light_pool")) { if (value < 0 || value > 1024 || (value != 0 && value < 32)) return fail(RT_ERR_INVALID, "light_pool must be 0 (automatic) or 32..1024"); s->opt.light_pool_cap = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "light_base_pool")) { if (value < 0 || value > 1024 || (value != 0 && value < 32)) return fail(RT_ERR_INVALID, "light_base_pool must be 0 (automatic) or 32..1024"); s->opt.light_base_cap = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "light_nest_pool")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "light_nest_pool must be 0 or 1"); s->opt.light_nest_pool = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "force_lit")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "force_lit must be 0 or 1"); s->opt.force_lit = (int)value; return RT_OK; }  // (diagnostics: an unlit scene through the lit kernels — what their code costs the ordinary lanes, profiles/r04_run5_lit_sections.log)
+  if (!std::strcmp(key, "tile_batch")) { if (value < 0 || value > 64) return fail(RT_ERR_INVALID, "tile_batch must be 0..64"); s->opt.tile_batch = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "chunk_spp")) { if (value < 0) return fail(RT_ERR_INVALID, "chunk_spp must be >= 0"); s->opt.chunk_spp = (int)value; return RT_OK; }
   if (!std::strcmp(key, "samples_per_pixel") || !std::strcmp(key, "max_depth")) {
     if (value < 0 || value > (int64_t)0xFFFFFFFFll) return fail(RT_ERR_INVALID, std::string(key) + " must be in 0 .. 2^32-1");
     if (key[0] == 's') s->host.samples_per_pixel = s->dev.spp = (uint32_t)value;
@@ -426,74 +443,61 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
 
 namespace {
 
+// The megakernel instantiations and their keys: LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1 (lights, every albedo in
+// [0, 1], tables in LDS, wide cell tables, accumulating, thin lens).  Wide tables are never staged in LDS (plan_lds): those 16 keys
+// have no instantiation.
+using Megakernel = void (*)(rtk::KArgs);
+template <int K> Megakernel megakernel_of_key() {
+  if constexpr ((K & 9) == 9) return nullptr;
+  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, (K & 8) != 0, (K & 16) != 0, (K & 32) != 0>;
+}
+// J counts up over (LENS, ACCUM, WIDE, HL, LDS, SIMPLE); the compiler emits the kernels in the reverse of that order, the order they
+// have always had, which keeps the code object's layout (and tools/codeobj_stats.py's report) as it was
+template <int J> constexpr int key_at = (J & ~3) | ((J & 1) << 1) | ((J >> 1) & 1);
+template <int... J> std::array<Megakernel, 64> megakernels(std::integer_sequence<int, J...>) {
+  std::array<Megakernel, 64> t{};
+  ((t[key_at<J>] = megakernel_of_key<key_at<J>>()), ...);
+  return t;
+}
+struct Kernel { int key = -1; Megakernel fn = nullptr; };
+int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
+  static const std::array<Megakernel, 64> table = megakernels(std::make_integer_sequence<int, 64>());
+  if (wide && lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
+  out->key = (s->dev.lens_r != 0.0 ? 32 : 0) | (accum ? 16 : 0) | (wide ? 8 : 0) | (has_lights ? 4 : 0) | (s->res->simple_colour ? 2 : 0) | (lds_tables ? 1 : 0);
+  out->fn = table[out->key];
+  return RT_OK;
+}
+
 // Everything a launch needs that is NOT the launch: the kernel's dynamic-LDS attribute and its occupancy (worked out once per
 // configuration: two runtime calls a frame otherwise) and, lit kernels, the lanes' HBM overflow slots.  Runs BEFORE the
 // launch's start event is recorded — a first frame used to carry the 147 MB hipMalloc of a lit scene and the runtime's
 // first look at the kernel inside its kernel_ms (one-shot CLI frames: 8.4 ms for a 0.9 ms kernel, profiles/r05_run5_cli_stats_before_warmup.log)
 // — and once at scene creation for the scene's default configuration (warm_up).
-template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM, bool LENS>
-int prepare_grid_t(RtHipScene* s, size_t lds_bytes, hipStream_t stream) {
-  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>;
-  const int key = (LENS ? 32 : 0) | (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
-  if (s->cfg_key != key || s->cfg_lds != lds_bytes) {
-    if (lds_bytes > 48 * 1024) RT_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+int prepare(RtHipScene* s, const Kernel& k, size_t lds_bytes, hipStream_t stream) {
+  if (s->cfg_key != k.key || s->cfg_lds != lds_bytes) {
+    if (lds_bytes > 48 * 1024) RT_HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     int per_cu_q = 0;
-    RT_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_q, kern, rtk::BLOCK, lds_bytes));
+    RT_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_q, k.fn, rtk::BLOCK, lds_bytes));
     if (per_cu_q < 1) return fail(RT_ERR_HIP, "megakernel does not fit on a CU");
-    s->cfg_key = key; s->cfg_lds = lds_bytes; s->cfg_per_cu = per_cu_q;
+    s->cfg_key = k.key; s->cfg_lds = lds_bytes; s->cfg_per_cu = per_cu_q;
   }
-  if (HL) {  // the lanes' overflow slots for suspended light activations (rt_core.h lane_light_begin): for the resident set, kept
-    const size_t need_bytes = (size_t)s->cfg_per_cu * (size_t)s->num_cus * rtk::BLOCK * rtc::LIGHT_OVERFLOW_BYTES_PER_LANE;
-    if (need_bytes > s->light_overflow_bytes) {
-      // (an earlier launch of this scene may still be running on this stream with the old buffer: drain it first — once per
-      //  scene and configuration, never in a frame loop)
-      if (s->d_light_overflow) { RT_HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(s->d_light_overflow); s->d_light_overflow = nullptr; s->light_overflow_bytes = 0; }
-      RT_HIP_TRY(hipMalloc(&s->d_light_overflow, need_bytes));
-      s->light_overflow_bytes = need_bytes;
-    }
+  if (k.key & 4) {  // the lanes' overflow slots for suspended light activations (rt_core.h lane_light_begin): for the resident set, kept
+    // (an earlier launch of this scene may still be running on this stream with the old buffer: it drains that stream first — once
+    //  per scene and configuration, never in a frame loop)
+    const size_t need_bytes = (size_t)s->cfg_per_cu * (size_t)s->res->num_cus * rtk::BLOCK * rtc::LIGHT_OVERFLOW_BYTES_PER_LANE;
+    return s->light_overflow.ensure(need_bytes, nullptr, stream);
   }
   return RT_OK;
 }
-template <bool HL, bool SIMPLE, bool LDS, bool WIDE, bool ACCUM, bool LENS>
-int launch_grid_t(RtHipScene* s, const rtk::KArgs& ka_in, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
-  auto kern = rtk::rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>;
-  // (here, not in prepare_grid_t: warm_up prepares the scene's default configuration without launching it)
-  s->last_kernel = (LENS ? 32 : 0) | (ACCUM ? 16 : 0) | (WIDE ? 8 : 0) | (HL ? 4 : 0) | (SIMPLE ? 2 : 0) | (LDS ? 1 : 0);
+void launch(RtHipScene* s, const Kernel& k, rtk::KArgs ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
+  s->last_kernel = k.key;  // (here, not in prepare: warm_up prepares the scene's default configuration without launching it)
   // persistent: exactly the resident set, never more workgroups than there are wave-sized items
-  uint32_t wgs = (uint32_t)s->cfg_per_cu * (uint32_t)s->num_cus;
+  uint32_t wgs = (uint32_t)s->cfg_per_cu * (uint32_t)s->res->num_cus;
   const uint32_t need = (n_items + rtk::WAVES - 1) / rtk::WAVES;
   if (wgs > need) wgs = need;
   s->last_waves = (uint64_t)wgs * rtk::WAVES;
-  rtk::KArgs ka = ka_in;
-  if (HL) ka.sc.light_overflow = (unsigned char*)s->d_light_overflow;
-  hipLaunchKernelGGL(kern, dim3(wgs), dim3(rtk::BLOCK), lds_bytes, stream, ka);
-  return RT_OK;
-}
-// (lights, every albedo in [0, 1], tables in LDS, wide cell tables, accumulating, thin lens) -> the instantiation's prepare / launch
-template <bool ACCUM, bool LENS>
-int dispatch_grid_t(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream) {
-  int rc;
-#define RT_GO(HL, SIMPLE, LDS, WIDE) rc = prepare_only ? prepare_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>(s, lds_bytes, stream) : launch_grid_t<HL, SIMPLE, LDS, WIDE, ACCUM, LENS>(s, *ka, lds_bytes, n_items, stream)
-  const bool simple = s->simple_colour;
-  if (wide) {  // (the launch's grid has 32-bit item lists — more than 65 535 spheres; tables in L2: plan_lds never puts them in LDS)
-    if (lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
-    if (has_lights) { if (simple) RT_GO(true, true, false, true); else RT_GO(true, false, false, true); }
-    else { if (simple) RT_GO(false, true, false, true); else RT_GO(false, false, false, true); }
-  } else if (has_lights) {
-    if (lds_tables) { if (simple) RT_GO(true, true, true, false); else RT_GO(true, false, true, false); }
-    else { if (simple) RT_GO(true, true, false, false); else RT_GO(true, false, false, false); }
-  } else if (lds_tables) { if (simple) RT_GO(false, true, true, false); else RT_GO(false, false, true, false); }
-  else { if (simple) RT_GO(false, true, false, false); else RT_GO(false, false, false, false); }
-#undef RT_GO
-  return rc;
-}
-int dispatch_grid(RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool prepare_only, const rtk::KArgs* ka, size_t lds_bytes, uint32_t n_items, hipStream_t stream,
-                  bool accum = false) {
-  if (s->dev.lens_r != 0.0)
-    return accum ? dispatch_grid_t<true, true>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream)
-                 : dispatch_grid_t<false, true>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream);
-  return accum ? dispatch_grid_t<true, false>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream)
-               : dispatch_grid_t<false, false>(s, has_lights, lds_tables, wide, prepare_only, ka, lds_bytes, n_items, stream);
+  if (k.key & 4) ka.sc.light_overflow = s->light_overflow.get<unsigned char>();
+  hipLaunchKernelGGL(k.fn, dim3(wgs), dim3(rtk::BLOCK), lds_bytes, stream, ka);
 }
 
 // LDS budget of a launch: do the tables fit, how big are the light pools, how much dynamic LDS does a workgroup ask for.
@@ -508,7 +512,7 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
   // (forced pools of 64 / 32 frames on the lit cover scene: +1 % / +64 %, profiles/r03_run*_lit.log).  The pools get what is
   // left beside the tables, in the proportion of their demands, up to one record per lane; if that is less than 1.2 x the
   // demand the TABLES stay in L2 instead and the pools take their room.
-  const bool short_map = has_lights && s->simple_colour;
+  const bool short_map = has_lights && s->res->simple_colour;
   uint32_t pool_slots = 0, base_slots = 0;
   auto size_pools = [&](size_t avail, double* margin) {  // largest x with frames = x f 1024, bases = x b 1024 (multiples of 32, 32 .. 1024) inside `avail`
     const double n = (double)s->dev.n_lights, den = 2.9 + 0.2 * n * n;
@@ -524,9 +528,9 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
     if (bytes(hi) <= avail) lo = hi;
     else for (int it = 0; it < 40; ++it) { const double mid = 0.5 * (lo + hi); if (bytes(mid) <= avail) lo = mid; else hi = mid; }
     pool_slots = slots(lo, f); base_slots = slots(lo, b);
-    const bool forced_f = s->light_pool_cap > 0, forced_b = s->light_base_cap > 0;  // (tests: small pools on purpose)
-    if (forced_f && pool_slots > (uint32_t)s->light_pool_cap) pool_slots = (uint32_t)s->light_pool_cap & ~31u;
-    if (forced_b && base_slots > (uint32_t)s->light_base_cap) base_slots = (uint32_t)s->light_base_cap & ~31u;
+    const bool forced_f = s->opt.light_pool_cap > 0, forced_b = s->opt.light_base_cap > 0;  // (tests: small pools on purpose)
+    if (forced_f && pool_slots > (uint32_t)s->opt.light_pool_cap) pool_slots = (uint32_t)s->opt.light_pool_cap & ~31u;
+    if (forced_b && base_slots > (uint32_t)s->opt.light_base_cap) base_slots = (uint32_t)s->opt.light_base_cap & ~31u;
     if (margin) *margin = (forced_f || forced_b) ? 1e9 : std::min((double)pool_slots / (f * rtk::BLOCK), b > 0.0 ? (double)base_slots / (b * rtk::BLOCK) : 1e9);
     return bytes(0.0) <= avail;  // (the smallest pools fit)
   };
@@ -535,11 +539,11 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
   if (has_lights) {
     const size_t fixed = rtc::LIGHT_CENTRES_LDS_MAX * 24u;
     double margin = 0.0;
-    bool ok = lds_tables && no_pools.total + fixed < s->lds_cap && size_pools(s->lds_cap - no_pools.total - fixed, &margin) && margin >= 1.2;
+    bool ok = lds_tables && no_pools.total + fixed < s->res->lds_cap && size_pools(s->res->lds_cap - no_pools.total - fixed, &margin) && margin >= 1.2;
     if (!ok) {
       lds_tables = false;
       const size_t bare = rtk::lds_layout(0, 0, 0, false, false).total + fixed;
-      if (!size_pools(s->lds_cap - bare, nullptr)) return fail(RT_ERR_UNSUPPORTED, "no room for the light pools in LDS");
+      if (!size_pools(s->res->lds_cap - bare, nullptr)) return fail(RT_ERR_UNSUPPORTED, "no room for the light pools in LDS");
     }
   }
   out->lds_tables = lds_tables; out->pool_slots = pool_slots; out->base_slots = base_slots;
@@ -554,9 +558,11 @@ int warm_up(RtHipScene* s) {
   hipLaunchKernelGGL(rtk::rt_warm_up, dim3(1), dim3(64), 0, nullptr);
   RT_HIP_TRY(hipGetLastError());
   LdsPlan plan;
-  const int rc = plan_lds(s, s->dev.grid, s->has_lights, &plan);
+  int rc = plan_lds(s, s->dev.grid, s->res->has_lights, &plan);
   if (rc != RT_OK) return rc;
-  return dispatch_grid(s, s->has_lights, plan.lds_tables, s->dev.grid.wide != 0u, true, nullptr, plan.lds_bytes, 0, nullptr);
+  Kernel k;
+  if ((rc = select_kernel(s, s->res->has_lights, plan.lds_tables, s->dev.grid.wide != 0u, false, &k)) != RT_OK) return rc;
+  return prepare(s, k, plan.lds_bytes, nullptr);
 }
 
 }  // namespace
@@ -570,20 +576,21 @@ int tile_geometry(const RtHipScene* s, uint32_t local_rows, TileGeom* out) {
   // >= ~100 tiles per workgroup; small frames (and the 1/8 shards of the multi-GPU run) use 4x4,
   // 2x2 or 1x1 tiles, so that the heaviest tile (glass: 10x the mean) is a small part of a
   // workgroup's share and the long-path regions spread over many workgroups.
-  const uint64_t want_tiles = (uint64_t)s->num_cus * 100u;
+  const uint64_t want_tiles = (uint64_t)s->res->num_cus * 100u;
   // tile geometry: 4^tl pixels, as a square (default) or a run of one scanline
   // (shape 0: 2^t x 2^t; 1: 4^t x 1; 2 and 3: the square widened / flattened once or twice, 16x4 and 32x2 at t = 3)
   // (default shape: squares — but the 2x2 tiles of a small frame / a multi-GPU shard as 4x1 strips: 12 contiguous bytes
   //  leave in one packed store instead of two rows of byte stores; same time, WRITE_SIZE 2.71 -> 2.17 MB on an 1/8 shard
   //  of the headline frame, profiles/r03_run10_shape_traffic_sweep.log)
   // (shape 2 at t = 1 is the 2x2 square — the A/B arm of the 4x1 default, which no other value selects)
-  auto widen = [&](uint32_t t) { const uint32_t k = s->tile_shape == 0 ? (t == 1u ? 1u : 0u) : (s->tile_shape == 1 ? t : (s->tile_shape == 2 && t == 1u ? 0u : (uint32_t)s->tile_shape - 1u)); return k < t ? k : t; };
+  const int shape = s->opt.tile_shape;
+  auto widen = [&](uint32_t t) { const uint32_t k = shape == 0 ? (t == 1u ? 1u : 0u) : (shape == 1 ? t : (shape == 2 && t == 1u ? 0u : (uint32_t)shape - 1u)); return k < t ? k : t; };
   auto tiles_xy = [&](uint32_t t, uint32_t& tx, uint32_t& ty) {
     const uint32_t wl = t + widen(t), hl = t - widen(t);
     tx = (s->host.width + (1u << wl) - 1) >> wl; ty = (local_rows + (1u << hl) - 1) >> hl;
   };
-  uint32_t tl = s->tile_log2 < 0 ? 3u : (uint32_t)s->tile_log2, tx = 0, ty = 0;
-  if (s->tile_log2 < 0) {
+  uint32_t tl = s->opt.tile_log2 < 0 ? 3u : (uint32_t)s->opt.tile_log2, tx = 0, ty = 0;
+  if (s->opt.tile_log2 < 0) {
     for (;;) { tiles_xy(tl, tx, ty); if (tl == 0 || (uint64_t)tx * ty >= want_tiles) break; tl--; }
   }
   // a slot header packs (tile column | tile row << 16), and the queue cursor is 32 bits
@@ -611,7 +618,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
                  uint32_t spp, void* stream_, const uint32_t* list = nullptr, uint32_t n_list = 0) {
   const uint32_t local_rows = rt_tiles_local_rows(s->host.height, tiles);
   hipStream_t stream = (hipStream_t)stream_;
-  const bool has_lights = s->has_lights || s->force_lit != 0;
+  const bool has_lights = s->res->has_lights || s->opt.force_lit != 0;
   // one tile-queue cursor / counter block per scene: launches of a scene are ordered on ONE stream
   // (a caller that drained the first stream itself — hipStreamSynchronize, an event — need not call rt_hip_wait first:
   //  the scene asks its OWN event, recorded behind the last launch's counter copy — never the caller's stream handle,
@@ -630,11 +637,11 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   sl.samples = (uint64_t)local_rows * s->host.width * spp;
   s->last_stream = stream;
   sl.t_launch = std::chrono::steady_clock::now();
-  RT_HIP_TRY(hipMemsetAsync(s->d_counters, 0, 32 * sizeof(unsigned long long), stream));
+  RT_HIP_TRY(hipMemsetAsync(s->counters.p, 0, 32 * sizeof(unsigned long long), stream));
   // behind the kernel(s) of this launch: its counters into the slot's pinned words (what rt_hip_wait reads)
   auto finish_launch = [&](bool launched) -> int {
     sl.launched = launched; sl.waves = s->last_waves;
-    if (launched) RT_HIP_TRY(hipMemcpyAsync(sl.h_counters, s->d_counters, RT_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (launched) RT_HIP_TRY(hipMemcpyAsync(sl.h_counters, s->counters.p, RT_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     else std::memset(sl.h_counters, 0, RT_SLOT_COUNTERS * sizeof(unsigned long long));
     RT_HIP_TRY(hipEventRecord(sl.ev_copied, stream));
     s->in_flight = true;
@@ -644,19 +651,19 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
 
   rtk::KArgs ka;
   ka.sc = s->dev;
-  if (s->variant == 1) {  // brute-force arm: no grid, every sphere in the `large` list (object order)
+  if (s->opt.variant == 1) {  // brute-force arm: no grid, every sphere in the `large` list (object order)
     std::memset(&ka.sc.grid, 0, sizeof ka.sc.grid);
     ka.sc.grid.n_large = s->host.n_spheres;
-    ka.sc.large = (const uint32_t*)s->d_all;
-    ka.sc.large_geom = (const rtc::SphereGeom*)s->d_geom;
+    ka.sc.large = s->res->all.get<const uint32_t>();
+    ka.sc.large_geom = s->res->geom.get<const rtc::SphereGeom>();
   }
-  ka.out_rgb8 = (uint8_t*)d_rgb8; ka.out_linear = (float*)d_linear; ka.counters = s->d_counters;
+  ka.out_rgb8 = (uint8_t*)d_rgb8; ka.out_linear = (float*)d_linear; ka.counters = s->counters.get<unsigned long long>();
   ka.accum = accum; ka.sample_base = sample_base;
 #ifdef RT_TEST_PROBES
   ka.probe_rays = g_probe_rays.rays; ka.probe_t = g_probe_rays.t; ka.probe_best = g_probe_rays.best;
 #endif
   ka.sc.spp = spp;  // (the kernel's sample count: the pass's, for an accumulating launch)
-  ka.queue = (uint32_t*)(s->d_counters + 24);
+  ka.queue = (uint32_t*)(s->counters.get<unsigned long long>() + 24);
   ka.local_rows = local_rows;
   const bool tiled = tiles && tiles->tile_rows && tiles->tile_stride;
   ka.tile_rows = tiled ? tiles->tile_rows : 0; ka.first_tile = tiled ? tiles->first_tile : 0;
@@ -678,10 +685,10 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   // 4x4 -> 16, 2x2 -> 32, 1x1 -> 128 — give or take a factor of two so that a frame has about 60
   // items per wave (measured on the whole frame and its 1/2, 1/4, 1/8 shards, profiles/r01_run11_tiles.log:
   // both fewer, larger items and more, smaller ones lose up to 5 %).
-  uint32_t chunk_spp = (uint32_t)s->chunk_spp;
+  uint32_t chunk_spp = (uint32_t)s->opt.chunk_spp;
   if (chunk_spp == 0) {
     static const uint32_t by_tile[4] = {128u, 32u, 16u, 8u};
-    const uint64_t target_items = (uint64_t)s->num_cus * rtk::WAVES * 60u;
+    const uint64_t target_items = (uint64_t)s->res->num_cus * rtk::WAVES * 60u;
     const uint64_t ideal = ((uint64_t)ka.n_queue * spp + target_items / 2) / target_items;  // samples per pixel and item (of the tiles queued)
     uint32_t c = 1;
     while ((uint64_t)c * 3u < ideal * 2u) c <<= 1;  // nearest power of two (geometric)
@@ -701,7 +708,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   // 3.71 -> 3.35, 12.92 -> 12.80 ms with batches of one); batches of 4 add 5 % on frames of small tiles (test scene 1.09 ->
   // 1.03 ms).  Not more: a batch is a run of the queue's order, and that order puts the deepest tiles first — 8 or 16 of
   // them in one workgroup are the critical path of a short frame (1/8 shard: 1.76 -> 1.87 -> 2.45 ms).
-  ka.tile_batch = s->tile_batch > 0 ? (uint32_t)s->tile_batch : 4u;
+  ka.tile_batch = s->opt.tile_batch > 0 ? (uint32_t)s->opt.tile_batch : 4u;
   ka.batch_share = 16u;
 #ifdef RT_DEV_KNOBS
   if (const char* e = std::getenv("RT_BATCH_SHARE")) { const int v = std::atoi(e); if (v >= 1 && v <= 1024) ka.batch_share = (uint32_t)v; }
@@ -712,13 +719,13 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   const size_t lds_bytes = plan.lds_bytes;
   ka.sc.light_pool_slots = plan.pool_slots;
   ka.sc.light_base_slots = plan.base_slots;
-  ka.sc.light_nest_pool = (uint32_t)s->light_nest_pool;
-  ka.sc.light_overflow = nullptr;  // (launch_grid_t fills it in for the lit kernels)
+  ka.sc.light_nest_pool = (uint32_t)s->opt.light_nest_pool;
+  ka.sc.light_overflow = nullptr;  // (launch fills it in for the lit kernels)
   s->last_pool_slots = plan.pool_slots; s->last_base_slots = plan.base_slots; s->last_lds_tables = lds_tables; s->last_lds_bytes = lds_bytes;
 
   // queue order: bottom of the image first; from the second frame of a tile geometry on, the tiles whose samples ran
   // deepest in the previous frame first (their paths are what a frame ends on)
-  ka.order_mode = s->order_mode != 0 ? 1u : 0u;
+  ka.order_mode = s->opt.order_mode != 0 ? 1u : 0u;
   ka.tile_order = nullptr; ka.tile_depth = nullptr;
   // XCD affinity: runs of 1.5 KB of a scanline's tiles (512 pixels) per XCD, for large frames (smaller ones — the shards
   // of the headline frame — lose more to the coarser balance than the write traffic is worth: 2.10 instead of 1.89 ms,
@@ -737,7 +744,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
     // below and lose 6 - 15 % to the coarser balance, profiles/r03_run8_shard_affinity_sweep.log) with at least 8 runs
     const bool big = (uint64_t)local_rows * s->host.width >= (1ull << 19);
     // (list launches: off — their queue is the caller's list, not the frame's runs; DESIGN.md §11 has the A/B)
-    if (!list && ((s->tile_affinity == 1 && big && n_groups >= 8u) || (s->tile_affinity == 2 && n_groups >= 8u))) {
+    if (!list && ((s->opt.tile_affinity == 1 && big && n_groups >= 8u) || (s->opt.tile_affinity == 2 && n_groups >= 8u))) {
       ka.aff_group_log2 = gl;
       for (uint32_t g = 0; g < 8u && g < n_groups; ++g) {  // groups g, g + 8, ...: all full but possibly the frame's last
         const uint32_t mine = (n_groups - 1u - g) / 8u + 1u;
@@ -751,50 +758,41 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   if (list) {  // the list is the queue, in the caller's order; no depths are measured
     ka.order_mode = 1u;
     ka.tile_order = list;
-  } else if (s->order_mode >= 2) {
+  } else if (s->opt.order_mode >= 2) {
     RtHipScene::OrderKey key;
-    key.n_tiles = ka.n_tiles; key.tile_log2 = tl; key.tile_shape = (uint32_t)s->tile_shape; key.aff_group_log2 = ka.aff_group_log2;
+    key.n_tiles = ka.n_tiles; key.tile_log2 = tl; key.tile_shape = (uint32_t)s->opt.tile_shape; key.aff_group_log2 = ka.aff_group_log2;
     key.tile_rows = ka.tile_rows; key.first_tile = ka.first_tile; key.tile_stride = ka.tile_stride; key.local_rows = local_rows;
-    if (ka.n_tiles > s->order_cap) {
-      if (s->d_tile_depth) (void)hipFree(s->d_tile_depth);
-      if (s->d_tile_order) (void)hipFree(s->d_tile_order);
-      s->d_tile_depth = s->d_tile_order = nullptr; s->order_cap = 0;
-      RT_HIP_TRY(hipMalloc((void**)&s->d_tile_depth, (size_t)ka.n_tiles * 4));
-      RT_HIP_TRY(hipMalloc((void**)&s->d_tile_order, (size_t)ka.n_tiles * 4));
-      s->order_cap = ka.n_tiles;
-    }
+    int rc;
+    if ((rc = s->tile_depth.ensure((size_t)ka.n_tiles * 4)) != RT_OK || (rc = s->tile_order.ensure((size_t)ka.n_tiles * 4)) != RT_OK) return rc;
     if (!(key == s->order_key)) { s->order_key = key; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; }
     // The order of THIS frame from the depths the previous frame of the SAME view measured (sorted here, stream-ordered ahead of
     // the launch — until round 5 behind the frame that measured them, which an animation paid every frame for an order it never
     // used).  Which tiles breed deep paths is a property of scene and camera: rebuilt after each of a view's first two frames,
     // then kept; rt_hip_set_camera with a different camera starts over WITHOUT an order (below).
     if (s->depth_fresh) {
-      hipLaunchKernelGGL(rtk::rt_order_tiles, dim3(1), dim3(1024), 0, stream, (const uint32_t*)s->d_tile_depth, s->d_tile_order, ka.n_tiles, ka.aff_group_log2);
+      hipLaunchKernelGGL(rtk::rt_order_tiles, dim3(1), dim3(1024), 0, stream, s->tile_depth.get<const uint32_t>(), s->tile_order.get<uint32_t>(), ka.n_tiles, ka.aff_group_log2);
       RT_HIP_TRY(hipGetLastError());
       s->order_ready = true; s->depth_fresh = false;
     }
-    if (s->order_mode == 2 && s->order_age < 2) ka.tile_depth = s->d_tile_depth;  // (measured only while the order is still being built)
+    if (s->opt.order_mode == 2 && s->order_age < 2) ka.tile_depth = s->tile_depth.get<uint32_t>();  // (measured only while the order is still being built)
 #ifdef RT_TEST_PROBES
     if (ka.probe_rays) ka.tile_depth = nullptr;  // (a probe frame's depths say nothing about the view: it measures none)
 #endif
-    if (s->order_ready) ka.tile_order = s->d_tile_order;
+    if (s->order_ready) ka.tile_order = s->tile_order.get<uint32_t>();
   }
 
+  Kernel k;
   int rc;
-  auto launch = [&](const rtk::KArgs& ka, uint32_t n_items) -> int {
-    const int rc = dispatch_grid(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, false, &ka, lds_bytes, n_items, stream, accum != nullptr);
-    if (rc != RT_OK) return rc;
-    RT_HIP_TRY(hipGetLastError());
-    return RT_OK;
-  };
-  if ((rc = dispatch_grid(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, true, nullptr, lds_bytes, 0, stream, accum != nullptr)) != RT_OK) return rc;  // (host-side set-up: before the start event)
+  if ((rc = select_kernel(s, has_lights, lds_tables, ka.sc.grid.wide != 0u, accum != nullptr, &k)) != RT_OK) return rc;
+  if ((rc = prepare(s, k, lds_bytes, stream)) != RT_OK) return rc;  // (host-side set-up: before the start event)
   RT_HIP_TRY(hipEventRecord(sl.ev_start, stream));
   // A frame without a measured order (the first of a scene, a one-shot render) leaves the queue bottom row first and ends on
   // whatever deep path started last: 13.3 instead of 12.8 ms on the headline frame.  Two ways to SEED an order — a depth guess
   // from the spheres' projections, a one-sample probe launch — were built and measured in round 4, both slower than no seed
   // (profiles/r04_run3_first_frame_orders.log; the code: profiles/r05_order_seed_removed.patch): what the measured order
   // knows is WHICH tiles hold one of the rare 50-segment paths, which a replay of the same seeds predicts and nothing cheaper does.
-  if ((rc = launch(ka, n_items)) != RT_OK) return rc;
+  launch(s, k, ka, lds_bytes, n_items, stream);
+  RT_HIP_TRY(hipGetLastError());
   RT_HIP_TRY(hipEventRecord(sl.ev_stop, stream));
   if (ka.tile_depth) { s->order_age++; s->depth_fresh = true; }  // (the NEXT frame of this view sorts them into its order)
   return finish_launch(true);
@@ -931,7 +929,7 @@ extern "C" int rt_hip_debug_tile_depth(RtHipScene* s, uint32_t* out, uint32_t ca
   RT_HIP_TRY(hipSetDevice(s->device));
   if (s->n_launches) RT_HIP_TRY(hipStreamSynchronize(s->last_stream));
   const uint32_t n = s->order_key.n_tiles < cap ? s->order_key.n_tiles : cap;
-  if (n && s->d_tile_depth) RT_HIP_TRY(hipMemcpy(out, s->d_tile_depth, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (n && s->tile_depth.p) RT_HIP_TRY(hipMemcpy(out, s->tile_depth.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (tiles_x) *tiles_x = s->last_tiles_x;
   return (int)n;
 }
@@ -941,7 +939,7 @@ extern "C" int rt_hip_debug_timeline(RtHipScene* s, uint64_t* out, uint32_t max_
   RT_HIP_TRY(hipSetDevice(s->device));
   RT_HIP_TRY(hipStreamSynchronize(s->last_stream));
   const uint32_t n = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(s->last_waves, max_waves), RT_TIMELINE_WAVES);
-  RT_HIP_TRY(hipMemcpy(out, s->d_counters, (32 + (size_t)n * 4) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  RT_HIP_TRY(hipMemcpy(out, s->counters.p, (32 + (size_t)n * 4) * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return (int)n;
 }
 
@@ -999,11 +997,11 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!s || !key) return -1;
   if (!std::strcmp(key, "n_spheres")) return (int64_t)s->host.n_spheres;
   if (!std::strcmp(key, "n_lights")) return (int64_t)s->dev.n_lights;
-  if (!std::strcmp(key, "grid_cells")) return (int64_t)s->grid.n_cells;       // padded cell table (8 B each; wide tables: 16 B)
-  if (!std::strcmp(key, "grid_items")) return (int64_t)s->grid.n_items;       // u16 each (wide tables: u32)
-  if (!std::strcmp(key, "grid_wide")) return (int64_t)s->grid.wide;           // 1: 32-bit item lists (more than 65 535 spheres)
-  if (!std::strcmp(key, "grid_large")) return (int64_t)s->grid.n_large;
-  if (!std::strcmp(key, "texel_bytes")) return (int64_t)s->texel_bytes;       // 4-byte texels of textures + sky resident in HBM
+  if (!std::strcmp(key, "grid_cells")) return (int64_t)s->res->grid.n_cells;       // padded cell table (8 B each; wide tables: 16 B)
+  if (!std::strcmp(key, "grid_items")) return (int64_t)s->res->grid.n_items;       // u16 each (wide tables: u32)
+  if (!std::strcmp(key, "grid_wide")) return (int64_t)s->res->grid.wide;           // 1: 32-bit item lists (more than 65 535 spheres)
+  if (!std::strcmp(key, "grid_large")) return (int64_t)s->res->grid.n_large;
+  if (!std::strcmp(key, "texel_bytes")) return (int64_t)s->res->texel_bytes;       // 4-byte texels of textures + sky resident in HBM
   if (!std::strcmp(key, "light_pool_slots")) return (int64_t)s->last_pool_slots;  // of the last launch: records in the pools of light frames /
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
@@ -1021,7 +1019,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
     const RtHipScene::AdRound& r = s->ad_rounds[i];
     return f[15] == 't' ? (int64_t)r.tiles : (f[15] == 's' ? (int64_t)r.spp : (int64_t)std::llround(r.kernel_ms * 1000.0));
   }  // samples per pixel in the scene's accumulator (rt_hip_refine_to_host)
-  if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->grid.n_cells * (s->grid.wide ? 16u : 8u) + (size_t)s->grid.n_items * (s->grid.wide ? 4u : 2u));
+  if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->res->grid.n_cells * (s->res->grid.wide ? 16u : 8u) + (size_t)s->res->grid.n_items * (s->res->grid.wide ? 4u : 2u));
   return -1;
 }
 
@@ -1044,10 +1042,8 @@ extern "C" int rt_hip_set_camera(RtHipScene* s, const double origin[3], const do
   // in use ("the views of an animation are close") — measured in round 6 on the headline scene turning 3 degrees per frame:
   // the stale order costs 3 - 10 % against the view's own order and is WORSE than no order (+3 - 4 %): the tiles that hold a
   // view's rare 50-segment paths are 4x4 pixels, and a 3 degree turn moves the spheres by tens of pixels
-  // (bench.py `animation.same_views`, profiles/r06_run*_bench.json).  RT_STALE_ORDER=1: the round-5 behaviour, for the A/B.
-  static const bool keep_stale = std::getenv("RT_STALE_ORDER") != nullptr;
-  if (!keep_stale) { s->order_ready = false; s->depth_fresh = false; }   // (stale arm: the previous view's depths are sorted into this frame's order)
-  s->order_age = 0;
+  // (bench.py `animation.same_views`, profiles/r06_run*_bench.json; the old arm was removed after that A/B).
+  s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
   return RT_OK;
 }
 
@@ -1070,16 +1066,12 @@ extern "C" int rt_hip_render_to_host(RtHipScene* s, uint8_t* out_rgb8, RtStats* 
   auto t0 = std::chrono::steady_clock::now();
   RT_HIP_TRY(hipSetDevice(s->device));
   const size_t bytes = (size_t)s->host.width * s->host.height * 3;
-  if (bytes > s->frame_bytes) {
-    if (s->d_frame) { (void)hipFree(s->d_frame); s->d_frame = nullptr; s->frame_bytes = 0; }
-    RT_HIP_TRY(hipMalloc(&s->d_frame, bytes));
-    s->frame_bytes = bytes;
-  }
-  int rc = rt_hip_render(s, nullptr, s->d_frame, nullptr, nullptr);
+  int rc = s->frame.ensure(bytes);
+  if (rc == RT_OK) rc = rt_hip_render(s, nullptr, s->frame.p, nullptr, nullptr);
   RtStats st;
   if (rc == RT_OK) rc = rt_hip_wait(s, &st);
   if (rc != RT_OK) return rc;
-  RT_HIP_TRY(hipMemcpy(out_rgb8, s->d_frame, bytes, hipMemcpyDeviceToHost));
+  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, bytes, hipMemcpyDeviceToHost));
   if (stats) {
     *stats = st;
     stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1090,7 +1082,6 @@ extern "C" int rt_hip_render_to_host(RtHipScene* s, uint8_t* out_rgb8, RtStats* 
 namespace {
 int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32_t iterations, const float sigma[4], void* d_out_linear,
                   void* d_out_rgb8, hipStream_t stream);
-int ensure_denoise_host(RtHipScene* s);
 // the host form's AOV sample count: min(RT_DENOISE_AOV_SAMPLES, samples per pixel), at least 1
 uint32_t aov_default_samples(uint32_t spp) { return spp < 1u ? 1u : (spp < RT_DENOISE_AOV_SAMPLES ? spp : RT_DENOISE_AOV_SAMPLES); }
 // Progressive rendering into the scene's own accumulator, blocking: the next sample_count samples of every pixel, then the whole
@@ -1104,37 +1095,35 @@ int refine_to_host(RtHipScene* s, uint32_t sample_count, int iterations, uint8_t
   auto t0 = std::chrono::steady_clock::now();
   RT_HIP_TRY(hipSetDevice(s->device));
   const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 3;
-  if (px * 24 > s->accum_bytes) {
-    if (s->d_accum) { RT_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->d_accum); s->d_accum = nullptr; s->accum_bytes = 0; }
-    RT_HIP_TRY(hipMalloc((void**)&s->d_accum, px * 24));
-    s->accum_bytes = px * 24;
-    s->reset_accum();
+  bool grew = false;
+  int rc;
+  if ((rc = s->accum.ensure(px * 24, &grew)) != RT_OK) return rc;
+  if (grew) s->reset_accum();
+  if ((rc = s->frame.ensure(bytes)) != RT_OK) return rc;
+  if (iterations >= 0) {  // the host form's own linear frame and AOV record
+    if ((rc = s->dn_lin.ensure(px * 12)) != RT_OK || (rc = s->dn_aov.ensure(px * 32, &grew)) != RT_OK) return rc;
+    if (grew) s->aov_ready = false;
   }
-  if (bytes > s->frame_bytes) {
-    if (s->d_frame) { (void)hipFree(s->d_frame); s->d_frame = nullptr; s->frame_bytes = 0; }
-    RT_HIP_TRY(hipMalloc(&s->d_frame, bytes));
-    s->frame_bytes = bytes;
-  }
-  if (iterations >= 0) { const int rc = ensure_denoise_host(s); if (rc != RT_OK) return rc; }
-  if (s->accum_zero && px) { RT_HIP_TRY(hipMemsetAsync(s->d_accum, 0, px * 24, nullptr)); s->accum_zero = false; }
+  if (s->accum_zero && px) { RT_HIP_TRY(hipMemsetAsync(s->accum.p, 0, px * 24, nullptr)); s->accum_zero = false; }
   const uint32_t n = s->accum_samples + sample_count;
-  int rc = rt_hip_accumulate(s, nullptr, s->accum_samples, sample_count, s->d_accum, nullptr);
+  unsigned long long* accum = s->accum.get<unsigned long long>();
+  rc = rt_hip_accumulate(s, nullptr, s->accum_samples, sample_count, accum, nullptr);
   if (iterations < 0) {
-    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->d_accum, n, s->d_frame, nullptr, nullptr);
+    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, accum, n, s->frame.p, nullptr, nullptr);
   } else {
     if (rc == RT_OK && !s->aov_ready) {
-      rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(s->host.samples_per_pixel), s->d_dn_aov, nullptr);
+      rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(s->host.samples_per_pixel), s->dn_aov.p, nullptr);
       if (rc == RT_OK) s->aov_ready = true;
     }
-    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->d_accum, n, nullptr, s->d_dn_lin, nullptr);
+    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, accum, n, nullptr, s->dn_lin.p, nullptr);
     const float sigma[4] = {RT_DENOISE_SIGMA_COLOR, RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_ALBEDO, RT_DENOISE_SIGMA_INV_DEPTH};
-    if (rc == RT_OK) rc = denoise_frame(s, s->d_dn_lin, s->d_dn_aov, (uint32_t)iterations, sigma, nullptr, s->d_frame, nullptr);
+    if (rc == RT_OK) rc = denoise_frame(s, s->dn_lin.p, s->dn_aov.p, (uint32_t)iterations, sigma, nullptr, s->frame.p, nullptr);
   }
   RtStats st;
   if (rc == RT_OK) rc = rt_hip_wait(s, &st);
   if (rc != RT_OK) { s->reset_accum(); return rc; }  // (a pass that did not complete leaves the accumulator unknown: start over)
   s->accum_samples = n;
-  RT_HIP_TRY(hipMemcpy(out_rgb8, s->d_frame, bytes, hipMemcpyDeviceToHost));
+  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, bytes, hipMemcpyDeviceToHost));
   if (stats) {
     *stats = st;
     stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1167,12 +1156,8 @@ int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0 || (!d_out_linear && !d_out_rgb8)) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
-  if (iterations >= 2 && 2 * px * 16 > s->dn_ping_bytes) {
-    if (s->d_dn_ping) { RT_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->d_dn_ping); s->d_dn_ping = nullptr; s->dn_ping_bytes = 0; }
-    RT_HIP_TRY(hipMalloc(&s->d_dn_ping, 2 * px * 16));
-    s->dn_ping_bytes = 2 * px * 16;
-  }
-  float4* const buf[2] = {(float4*)s->d_dn_ping, (float4*)s->d_dn_ping + px};
+  if (iterations >= 2) { const int rc = s->dn_ping.ensure(2 * px * 16); if (rc != RT_OK) return rc; }
+  float4* const buf[2] = {s->dn_ping.get<float4>(), s->dn_ping.get<float4>() + px};
   const float4* aov = (const float4*)d_aov;
   const uint32_t W = s->host.width, H = s->host.height;
   const dim3 grid = px_grid(s), block(16, 16);
@@ -1195,22 +1180,6 @@ int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32
     else hipLaunchKernelGGL((rtk::rt_denoise<true, false>), grid, block, 0, stream, in, aov, W, H, 1u << i, k, out4, ol, ob);
     RT_HIP_TRY(hipGetLastError());
   }
-  return RT_OK;
-}
-// the host form's own linear frame and AOV record
-int ensure_denoise_host(RtHipScene* s) {
-  const size_t px = (size_t)s->host.width * s->host.height;
-  if (px <= s->dn_host_px) return RT_OK;
-  if (s->d_dn_lin || s->d_dn_aov) {
-    RT_HIP_TRY(hipDeviceSynchronize());
-    if (s->d_dn_lin) (void)hipFree(s->d_dn_lin);
-    if (s->d_dn_aov) (void)hipFree(s->d_dn_aov);
-    s->d_dn_lin = s->d_dn_aov = nullptr; s->dn_host_px = 0;
-  }
-  RT_HIP_TRY(hipMalloc(&s->d_dn_lin, px * 12));
-  RT_HIP_TRY(hipMalloc(&s->d_dn_aov, px * 32));
-  s->dn_host_px = px;
-  s->aov_ready = false;
   return RT_OK;
 }
 }  // namespace
@@ -1286,28 +1255,11 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
     return RT_OK;
   }
   const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 24;
-  if (bytes > s->ad_bytes) {
-    RT_HIP_TRY(hipDeviceSynchronize());
-    for (unsigned long long** p : {&s->d_ad_now, &s->d_ad_prev}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    s->ad_bytes = 0;
-    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_now, bytes));
-    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_prev, bytes));
-    s->ad_bytes = bytes;
-  }
-  if (nt > s->ad_tiles) {
-    RT_HIP_TRY(hipDeviceSynchronize());
-    for (void* p : {(void*)s->d_ad_list, (void*)s->d_ad_err, (void*)s->d_ad_spp}) if (p) (void)hipFree(p);
-    s->d_ad_list = nullptr; s->d_ad_err = nullptr; s->d_ad_spp = nullptr; s->ad_tiles = 0;
-    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_list, (size_t)nt * 4));
-    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_err, (size_t)nt * 8));
-    RT_HIP_TRY(hipMalloc((void**)&s->d_ad_spp, (size_t)nt * 4));
-    s->ad_tiles = nt;
-  }
-  if (px * 3 > s->frame_bytes) {
-    if (s->d_frame) { (void)hipFree(s->d_frame); s->d_frame = nullptr; s->frame_bytes = 0; }
-    RT_HIP_TRY(hipMalloc(&s->d_frame, px * 3));
-    s->frame_bytes = px * 3;
-  }
+  if ((rc = s->ad_now.ensure(bytes)) != RT_OK || (rc = s->ad_prev.ensure(bytes)) != RT_OK || (rc = s->ad_list.ensure((size_t)nt * 4)) != RT_OK ||
+      (rc = s->ad_err.ensure((size_t)nt * 8)) != RT_OK || (rc = s->ad_spp.ensure((size_t)nt * 4)) != RT_OK || (rc = s->frame.ensure(px * 3)) != RT_OK)
+    return rc;
+  unsigned long long* const now = s->ad_now.get<unsigned long long>(), * const prev = s->ad_prev.get<unsigned long long>();
+  uint32_t* const d_list = s->ad_list.get<uint32_t>();
   RtStats total;
   std::memset(&total, 0, sizeof total);
   total.n_gpus_used = 1;
@@ -1330,34 +1282,34 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
   for (uint32_t t = 0; t < nt; ++t) list[t] = nt - 1u - t;  // (bottom of the image first, the kernel's own default order)
   // round 0: every tile, two halves, the estimate between them
   const uint32_t h = M / 2u;
-  RT_HIP_TRY(hipMemsetAsync(s->d_ad_now, 0, bytes, nullptr));
-  if ((rc = rt_hip_accumulate(s, nullptr, 0u, h, s->d_ad_now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
-  RT_HIP_TRY(hipMemcpyAsync(s->d_ad_prev, s->d_ad_now, bytes, hipMemcpyDeviceToDevice, nullptr));
-  if ((rc = rt_hip_accumulate(s, nullptr, h, M - h, s->d_ad_now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
-  RT_HIP_TRY(hipMemcpy(s->d_ad_list, list.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  RT_HIP_TRY(hipMemsetAsync(now, 0, bytes, nullptr));
+  if ((rc = rt_hip_accumulate(s, nullptr, 0u, h, now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpyAsync(prev, now, bytes, hipMemcpyDeviceToDevice, nullptr));
+  if ((rc = rt_hip_accumulate(s, nullptr, h, M - h, now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(d_list, list.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
   uint32_t n = M, n_prev = h;
   s->ad_rounds.push_back({nt, n, round_ms});
   for (;;) {
     if (n >= N) break;
-    if ((rc = rt_hip_tile_error(s, nullptr, s->d_ad_list, (uint32_t)list.size(), s->d_ad_now, n, s->d_ad_prev, n_prev, s->d_ad_err, nullptr)) != RT_OK) return rc;
-    RT_HIP_TRY(hipMemcpy(err.data(), s->d_ad_err, (size_t)nt * 8, hipMemcpyDeviceToHost));
+    if ((rc = rt_hip_tile_error(s, nullptr, d_list, (uint32_t)list.size(), now, n, prev, n_prev, s->ad_err.get<double>(), nullptr)) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(err.data(), s->ad_err.get<double>(), (size_t)nt * 8, hipMemcpyDeviceToHost));
     size_t k = 0;
     for (uint32_t t : list) if (err[t] >= threshold) list[k++] = t;
     list.resize(k);
     if (list.empty()) break;
     const uint32_t add = n < N - n ? n : N - n;
     round_ms = 0.0;
-    RT_HIP_TRY(hipMemcpyAsync(s->d_ad_prev, s->d_ad_now, bytes, hipMemcpyDeviceToDevice, nullptr));
-    RT_HIP_TRY(hipMemcpy(s->d_ad_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
-    if ((rc = rt_hip_accumulate_tiles(s, nullptr, s->d_ad_list, (uint32_t)list.size(), n, add, s->d_ad_now, nullptr)) != RT_OK || (rc = collect()) != RT_OK)
+    RT_HIP_TRY(hipMemcpyAsync(prev, now, bytes, hipMemcpyDeviceToDevice, nullptr));
+    RT_HIP_TRY(hipMemcpy(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = rt_hip_accumulate_tiles(s, nullptr, d_list, (uint32_t)list.size(), n, add, now, nullptr)) != RT_OK || (rc = collect()) != RT_OK)
       return rc;
     n_prev = n; n += add;
     for (uint32_t t : list) n_t[t] = n;
     s->ad_rounds.push_back({(uint32_t)list.size(), n, round_ms});
   }
-  RT_HIP_TRY(hipMemcpy(s->d_ad_spp, n_t.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
-  if ((rc = rt_hip_resolve_tiles(s, nullptr, s->d_ad_now, s->d_ad_spp, s->d_frame, nullptr, nullptr)) != RT_OK) return rc;
-  RT_HIP_TRY(hipMemcpy(out_rgb8, s->d_frame, px * 3, hipMemcpyDeviceToHost));
+  RT_HIP_TRY(hipMemcpy(s->ad_spp.get<uint32_t>(), n_t.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  if ((rc = rt_hip_resolve_tiles(s, nullptr, now, s->ad_spp.get<uint32_t>(), s->frame.p, nullptr, nullptr)) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, px * 3, hipMemcpyDeviceToHost));
   if (out_tile_spp) std::copy(n_t.begin(), n_t.end(), out_tile_spp);
   if (stats) {
     uint64_t samples = 0;
@@ -1381,20 +1333,20 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
 int rt_hip_scene_warm(RtHipScene* s, hipStream_t stream) {
   if (!s || s->host.width == 0 || s->host.height == 0) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
-  void* row = nullptr;
-  RT_HIP_TRY(hipMalloc(&row, (size_t)s->host.width * 3 + 16));
-  const int saved_order = s->order_mode;
-  s->order_mode = 1;  // (nothing measured, nothing sorted)
+  DevBuf row;
+  int rc = row.ensure((size_t)s->host.width * 3 + 16);
+  if (rc != RT_OK) return rc;
+  const int saved_order = s->opt.order_mode;
+  s->opt.order_mode = 1;  // (nothing measured, nothing sorted)
   const RtRowTiles first_row{1u, 0u, s->host.height};
-  int rc = rt_hip_render(s, &first_row, row, nullptr, stream);
+  rc = rt_hip_render(s, &first_row, row.p, nullptr, stream);
   RtStats wst;
   if (rc == RT_OK) rc = rt_hip_wait(s, &wst);
   if (rc == RT_OK) rtp::add("rank0.warm_up_kernel_ms_by_events", wst.kernel_ms);
-  s->order_mode = saved_order;
+  s->opt.order_mode = saved_order;
   s->n_launches = 0; s->in_flight = false; s->last_stream = nullptr; s->last_waves = 0;
   s->order_key = RtHipScene::OrderKey(); s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
   for (auto& sl : s->slot) { sl.rows = 0; sl.samples = 0; sl.waves = 0; sl.launched = false; }
-  (void)hipFree(row);
   return rc;
 }
 

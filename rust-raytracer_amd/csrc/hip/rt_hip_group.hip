@@ -384,7 +384,7 @@ extern "C" void rt_hip_group_destroy(RtHipGroup* g) {
       if (r < f.ev_done.size() && f.ev_done[r]) (void)hipEventDestroy(f.ev_done[r]);
       if (r < f.ev_sent.size() && f.ev_sent[r]) (void)hipEventDestroy(f.ev_sent[r]);
     }
-    if (r < g->scene2.size() && g->scene2[r]) rt_hip_scene_destroy(g->scene2[r]);  // (the views first: they share their scene's tables)
+    if (r < g->scene2.size() && g->scene2[r]) rt_hip_scene_destroy(g->scene2[r]);
     if (g->scene[r]) rt_hip_scene_destroy(g->scene[r]);
     if (r < g->stream2.size() && g->stream2[r]) (void)hipStreamDestroy(g->stream2[r]);
     if (g->own_streams && r < g->stream.size() && g->stream[r]) (void)hipStreamDestroy(g->stream[r]);
@@ -423,12 +423,11 @@ int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, b
   const bool emulate = emu && emu[0] == '1';
   if (G > (uint32_t)ndev && !emulate)
     return fail(RT_ERR_INVALID, "n_gpus = " + std::to_string(G) + " but only " + std::to_string(ndev) + " device(s) visible");
-  const auto t_group = std::chrono::steady_clock::now();
   rtp::reset();
   rtp::Clock pc;
   RtHipGroup* g = new RtHipGroup;
   g->G = G; g->width = scene->width; g->height = scene->height;
-  g->own_streams = !(one_shot && G == 1 && !std::getenv("RT_ONE_SHOT_STREAMS"));
+  g->own_streams = !(one_shot && G == 1);
   g->row_bytes = (size_t)scene->width * 3;
   g->device.resize(G); g->scene.assign(G, nullptr); g->stream.assign(G, nullptr); g->xstream.assign(G, nullptr);
   g->tiles.resize(G); g->rc.assign(G, RT_OK); g->err.resize(G); g->t_wake_us.assign(G, 0.0); g->t_enq_us.assign(G, 0.0);
@@ -488,18 +487,14 @@ int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, b
         if (!ok) { g->rc[r] = RT_ERR_HIP; g->err[r] = "hipStreamCreate / hipEventCreate / hipMalloc(tiles) failed"; return; }
         rc_clock.mark("rank0.streams_events_tile_buffers");
         // the rank's kernel once through the rank's own render stream (one scanline): the first frame finds a warm queue
-        if (!std::getenv("RT_NO_KERNEL_WARMUP")) {
-          const auto tw = std::chrono::steady_clock::now();
-          g->rc[r] = rt_hip_scene_warm(g->scene[r], g->stream[r]);
-          if (std::getenv("RT_GROUP_TRACE")) std::fprintf(stderr, "[rt group] rank %u kernel warm-up %.2f ms\n", r, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count());
-          if (g->rc[r] != RT_OK) g->err[r] = rt_hip_last_error();
-        }
+        g->rc[r] = rt_hip_scene_warm(g->scene[r], g->stream[r]);
+        if (g->rc[r] != RT_OK) g->err[r] = rt_hip_last_error();
         rc_clock.mark("rank0.kernel_warm_up_one_scanline");
         if (!g->scene2.empty() && g->rc[r] == RT_OK) {  // the second view + its render stream (overlapped frames)
           g->rc[r] = rt_hip_scene_clone_view(g->scene[r], &g->scene2[r]);
           if (g->rc[r] == RT_OK && hipStreamCreateWithFlags(&g->stream2[r], hipStreamNonBlocking) != hipSuccess) { g->rc[r] = RT_ERR_HIP; g->err[r] = "hipStreamCreate (second render stream) failed"; }
           else if (g->rc[r] != RT_OK) g->err[r] = rt_hip_last_error();
-          if (g->rc[r] == RT_OK && !std::getenv("RT_NO_KERNEL_WARMUP")) { g->rc[r] = rt_hip_scene_warm(g->scene2[r], g->stream2[r]); if (g->rc[r] != RT_OK) g->err[r] = rt_hip_last_error(); }
+          if (g->rc[r] == RT_OK) { g->rc[r] = rt_hip_scene_warm(g->scene2[r], g->stream2[r]); if (g->rc[r] != RT_OK) g->err[r] = rt_hip_last_error(); }
           rc_clock.mark("rank0.second_view_and_stream");
         }
       });
@@ -527,7 +522,6 @@ int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, b
   pc.mark("group.transport");
   for (uint32_t r = 1; r < G; ++r) g->worker.emplace_back(rtg::worker_main, g, r);
   pc.mark("group.rank_threads");
-  if (std::getenv("RT_GROUP_TRACE")) std::fprintf(stderr, "[rt group] create: %.2f ms in all\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_group).count());
   *out = g;
   return RT_OK;
 }
@@ -651,7 +645,7 @@ void prepare_staging(RtHipGroup* g, int n_frames) {
   // ... and the copy path itself: the runtime sets its device-to-host machinery up with the first copy of a process (measured:
   // the first hipMemcpyAsync of a one-shot frame kept submit for ~8 ms — seven times the reference's test-scene kernel,
   // profiles/r05_run7_cli_warm_spin.log): one copy of the frame's size through the frame's own stream and buffers, here
-  if (g->frame[0].h_stage && g->frame[0].d_frame && !std::getenv("RT_NO_COPY_WARMUP")) {
+  if (g->frame[0].h_stage && g->frame[0].d_frame) {
     (void)hipMemcpyAsync(g->frame[0].h_stage, g->frame[0].d_frame, bytes, hipMemcpyDeviceToHost, g->xstream[0]);
     (void)hipStreamSynchronize(g->xstream[0]);
     (void)hipGetLastError();
@@ -752,16 +746,19 @@ int group_submit(RtHipGroup* g, uint8_t* out_rgb8) {
       // goes into a pinned staging buffer of the group and collect moves it on.  A destination that is pinned itself is written directly.
       const size_t bytes = (size_t)g->height * g->row_bytes;
       uint8_t* dst = f.out;
-      static const bool trace = std::getenv("RT_GROUP_TRACE") != nullptr;  // (development: where a submit's host time goes)
-      const double t_a = trace ? us_since(f.t0) : 0.0;
+#ifdef RT_DEV_KNOBS  // (development: RT_GROUP_TRACE=1, where a submit's host time goes — the copy is enqueued by RtStats.group_us[4])
+      static const bool trace = std::getenv("RT_GROUP_TRACE") != nullptr;
+      const double t_query = us_since(f.t0);
       const bool pinned_out = bytes != 0 && out_is_pinned(f.out);
-      const double t_b = trace ? us_since(f.t0) : 0.0;
+      if (trace) std::fprintf(stderr, "[rt group] submit: pointer query %.1f -> %.1f us (pinned %d)\n", t_query, us_since(f.t0), (int)pinned_out);
+#else
+      const bool pinned_out = bytes != 0 && out_is_pinned(f.out);
+#endif
       if (bytes != 0 && !pinned_out) {
         if (!f.h_stage && hipHostMalloc((void**)&f.h_stage, bytes, hipHostMallocDefault) != hipSuccess) { f.h_stage = nullptr; (void)hipGetLastError(); }
         if (f.h_stage) { dst = f.h_stage; f.staged = true; }  // (no pinned memory to be had: the old, blocking copy)
       }
       if (bytes != 0) RT_HIP_TRY(hipMemcpyAsync(dst, f.d_frame, bytes, hipMemcpyDeviceToHost, x0));
-      if (trace) std::fprintf(stderr, "[rt group] submit: before pointer query %.1f us, after %.1f, after hipMemcpyAsync %.1f (staged %d)\n", t_a, t_b, us_since(f.t0), (int)f.staged);
     }
     RT_HIP_TRY(hipEventRecord(f.ev_final, x0));
     return RT_OK;

@@ -46,6 +46,18 @@ def test_every_declared_symbol_is_exported_by_its_library(pkg):
     assert exported <= names, sorted(exported - names)
 
 
+PRODUCT_ENV = {"RT_GATHER", "RT_GATHER_SELFTEST", "RT_GPUS", "RT_GPUS_EMULATE", "RT_GROUP_OVERLAP", "RT_GROUP_PIN", "RT_RCCL_LIB",
+               "RT_RCCL_TIMEOUT_MS"}
+
+
+def test_product_library_reads_only_documented_environment_variables(pkg):
+    """The RT_* names among the NUL-terminated strings of librt_hip.so are exactly the variables INTEGRATION §3 documents:
+    development switches (RT_GROUP_TRACE, RT_BATCH_SHARE, ...) exist in -DRT_DEV_KNOBS builds only, test hooks in the probe build."""
+    data = open(pkg.hip.LIB_PATH, "rb").read()
+    names = {w.decode() for w in data.split(b"\0") if re.fullmatch(rb"RT_[A-Z0-9_]+", w)}
+    assert names == PRODUCT_ENV, sorted(names ^ PRODUCT_ENV)
+
+
 def _rust_structs(text):
     """{name: [(field, rust type)]} of the #[repr(C)] structs in INTEGRATION.md's Rust shim"""
     out = {}

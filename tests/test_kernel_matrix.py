@@ -1,7 +1,7 @@
 """Every instantiation of the megakernel against the CPU oracle.
 
 rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM> (rt_kernel.hip) runs as one of 24 instantiations, picked per launch by
-dispatch_grid_t (rt_hip_api.hip) from the scene (lights; every albedo in [0, 1]), where plan_lds puts the tables (LDS, L2, or
+select_kernel (rt_hip_api.hip) from the scene (lights; every albedo in [0, 1]), where plan_lds puts the tables (LDS, L2, or
 the wide format) and whether the launch is one-shot or accumulating.  rt_hip_scene_query("last_kernel") reports which one ran:
 ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1.
 
