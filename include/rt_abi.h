@@ -209,6 +209,11 @@ void rt_scene_camera(const RtSceneFile*, double out[11]);
 /* Thin lens (an extension of the schema; the reference ignores both keys): the camera map's optional "aperture"
  * (default 0: the pinhole) and "focus_dist" (default |look_from - look_at|).  out = aperture, focus_dist as resolved. */
 void rt_scene_lens(const RtSceneFile*, double out[2]);
+/* Motion blur (an extension of the schema; the reference ignores the key): a sphere map's optional "center1", its
+ * centre at shutter close ("center" is the centre at shutter open).  n_spheres x 3 values, center1 of each sphere (= its centre for a
+ * sphere without the key), or NULL when no sphere of the file has the key.  Owned by the scene file.  The loader rejects a
+ * duplicate center1, a non-finite center1 - center and center1 on a Light sphere. */
+const double* rt_scene_motion(const RtSceneFile*);
 /* Camera::new with a thin lens of focus distance f, r = aperture / 2: out = origin[3], lower_left[3], horizontal[3], vertical[3]
  * (on the focus plane), focal_length, u[3], v[3], r.  aperture 0: the pinhole — the first 13 values are rt_camera_derive's bits,
  * whatever focus_dist.  What rt_hip_set_camera and rt_hip_set_lens take. */
@@ -250,6 +255,12 @@ const char* rt_hip_setup_profile(void);
 /* Upload scene tables, textures and sky to HBM of `device`.  The caller may free the
  * RtScene and everything it points to as soon as this returns. */
 int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene** out);
+/* Motion blur: the scene whose sphere i moves linearly from its centre (shutter open) to center1[3i .. 3i+2] (shutter
+ * close).  Each sample of a pixel draws its shutter time tau from its own Philox address and traces its whole path at tau; a sphere is
+ * at c0 + dv * tau, dv = center1 - center (f64).  Motion is fixed at creation: the grid lists each moving sphere by its swept box.
+ * center1 NULL, or equal to every centre: the static scene of rt_hip_scene_create.  RT_ERR_INVALID for a non-finite center1 - center
+ * or a moving Light sphere.  rt_hip_scene_query "motion" = the number of moving spheres. */
+int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int device, RtHipScene** out);
 void rt_hip_scene_destroy(RtHipScene*);
 /* Launch the megakernel for the given row tiles on `stream` (a hipStream_t, NULL = default).
  *   d_rgb8    device buffer, rt_tiles_local_rows()*width*3 bytes, packed, top row first;
@@ -282,7 +293,8 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
  * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
  * "last_kernel" (the megakernel instantiation that ran: accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 |
- * tables in LDS 1; thin lens 32; -1 before the scene's first launch), "lens" (1: rt_hip_set_lens set a lens, 0: the pinhole).
+ * tables in LDS 1; thin lens 32; moving spheres 64; -1 before the scene's first launch), "lens" (1: rt_hip_set_lens set a lens, 0: the
+ * pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
@@ -445,6 +457,8 @@ typedef struct RtGroupRank {
  * later frame switches the same way and re-sends that frame's tiles.  Rank threads are pinned to the CPUs of their device's
  * NUMA node unless RT_GROUP_PIN=0. */
 int rt_hip_group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out);
+/* rt_hip_group_create whose every rank is rt_hip_scene_create_moving(scene, center1): motion blur */
+int rt_hip_group_create_moving(const RtScene* scene, const double* center1, uint32_t n_gpus, RtHipGroup** out);
 int rt_hip_group_info(const RtHipGroup*, RtGroupInfo* info);
 uint32_t rt_hip_group_ranks(const RtHipGroup*, RtGroupRank* out, uint32_t cap); /* fills min(cap, n_ranks) entries, returns n_ranks */
 const char* rt_hip_group_fallback_reason(const RtHipGroup*);                    /* "" unless RtGroupInfo.transport_fallback */
@@ -479,7 +493,8 @@ uint32_t rt_hip_group_stacked_row(uint32_t y, uint32_t n_ranks, uint32_t pad_row
  * is replicated, device r renders scanline tiles r, r+G, ... (2 rows each) on its own host thread and
  * stream, the packed tiles meet on device 0 through ONE gather (RCCL send/recv over xGMI, or peer copies
  * with RT_GATHER=peer), are de-interleaved by a small kernel and leave in ONE device-to-host copy.  The camera is RtScene's: a
- * pinhole (a lens needs a group or scene and rt_hip_set_lens). */
+ * pinhole (a lens needs a group or scene and rt_hip_set_lens), and every sphere is static (motion blur needs
+ * rt_hip_group_create_moving or rt_hip_scene_create_moving). */
 int rt_render_rgb8(const RtScene* scene, uint8_t* out_rgb8, RtStats* stats);
 const char* rt_strerror(int code);
 

@@ -40,7 +40,6 @@ def build_hip(force=False):
     -DRT_TEST_PROBES: + the device probes and debug calls of include/rt_abi_test.h, for tests/ and tools/diag.py only"""
     out = os.path.join(HERE, "librt_hip.so")
     probe = os.path.join(HERE, "librt_hip_probe.so")
-    src = _srcs("csrc/hip/rt_hip_api.hip")
     deps = _srcs(*HIP_DEPS) + [os.path.join(ROOT, "include/rt_abi.h"), os.path.join(ROOT, "include/rt_abi_test.h")]
     # (beside the file times: the source hash the libraries on disk were built from — a checkout or a clock that does not move
     #  forward leaves times that say nothing)
@@ -54,18 +53,30 @@ def build_hip(force=False):
     # (linked against librt_host.so: rt_abi.h is one seam, and a handle of librt_hip.so resolves its host calls — the scene file
     #  and camera helpers — too)
     link = ["-L" + HERE, "-Wl,--no-as-needed", "-lrt_host", "-Wl,-rpath,$ORIGIN"]
-    jobs = []
-    if force or _newer(out, deps):
-        jobs.append(["hipcc", *HIPFLAGS, "-shared", *src, "-o", out, *link])
-    if force or _newer(probe, deps):
-        jobs.append(["hipcc", *HIPFLAGS, "-DRT_TEST_PROBES", "-shared", *src, "-o", probe, *link])
-    procs = []
-    for cmd in jobs:   # (side by side: each is ~20 s of one core)
-        print("+", " ".join(cmd), file=sys.stderr, flush=True)
-        procs.append((cmd, subprocess.Popen(cmd, cwd=HERE)))
-    for cmd, pr in procs:
-        if pr.wait() != 0:
-            raise subprocess.CalledProcessError(pr.returncode, cmd)
+    # Two translation units per library, compiled side by side: rt_hip_api.hip (everything but the MOTION kernels) and
+    # rt_kernel_motion.hip (the 48 MOTION instantiations of the megakernel) — each ~1 minute of one core; one unit
+    # with all 96 instantiations was twice that.  Objects under build/ (git-ignored), then one link per library.
+    objdir = os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
+    units = [("csrc/hip/rt_hip_api.hip", ["-DRT_MOTION_TU_SPLIT"]), ("csrc/hip/rt_kernel_motion.hip", [])]
+    compiles, links = [], []
+    for lib, extra in ((out, []), (probe, ["-DRT_TEST_PROBES"])):
+        if not (force or _newer(lib, deps)):
+            continue
+        objs = []
+        for unit, defs in units:
+            obj = os.path.join(objdir, os.path.splitext(os.path.basename(unit))[0] + ("_probe" if extra else "") + ".o")
+            compiles.append(["hipcc", *HIPFLAGS, *extra, *defs, "-c", os.path.join(HERE, unit), "-o", obj])
+            objs.append(obj)
+        links.append(["hipcc", *HIPFLAGS, "-shared", *objs, "-o", lib, *link])
+    for batch in (compiles, links):
+        procs = []
+        for cmd in batch:   # (side by side)
+            print("+", " ".join(cmd), file=sys.stderr, flush=True)
+            procs.append((cmd, subprocess.Popen(cmd, cwd=HERE)))
+        for cmd, pr in procs:
+            if pr.wait() != 0:
+                raise subprocess.CalledProcessError(pr.returncode, cmd)
     return out
 
 
@@ -79,7 +90,7 @@ def build_cli(force=False):
     return out
 
 
-HIP_DEPS = ("csrc/hip/rt_hip_api.hip", "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h",
+HIP_DEPS = ("csrc/hip/rt_hip_api.hip", "csrc/hip/rt_kernel.hip", "csrc/hip/rt_kernel_motion.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h",
             "csrc/common/rt_atan2.h")
 
 

@@ -29,7 +29,7 @@
 #define RT_HD __host__ __device__ __forceinline__
 // cold paths (texture lookups): a real call, so that their constants (atan2's polynomial) are
 // not hoisted into registers that stay live across the whole path loop
-#define RT_HD_COLD __host__ __device__ __attribute__((noinline))
+#define RT_HD_COLD __host__ __device__ __attribute__((noinline)) inline  // (inline: one definition across the two translation units of the kernel set)
 #else
 #include <cmath>
 #define RT_HD inline
@@ -186,6 +186,9 @@ struct DevScene {
   // thin lens (rt_hip_set_lens): the camera's unit vectors u and v and the lens radius aperture / 2; lens_r == 0 is the
   // pinhole.  Read only by the LENS instantiations of the megakernel and by rt_aov_lens.
   double lens_u[3], lens_v[3], lens_r;
+  // motion blur (rt_hip_scene_create_moving): [n_spheres][4] {dv = center1 - center, 0} (a zero component stored as -0.0);
+  // null for a static scene.  Read only by the MOTION instantiations of the megakernel and by rt_aov_motion / rt_aov_lens_motion.
+  const double* motion;
 };
 
 // ------------------------------------------------------------------ f64 square root
@@ -315,7 +318,10 @@ RT_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint3
 //                              call leaves over, so a lit kernel decides `draw > threshold` without a second Philox stream —
 //                              the low word (slot 0) matters only when the high word alone leaves the comparison open (2^-32)
 //   node NODE_CAMERA, slot 1+a: attempt a of the thin lens's point in the unit disc (lens_disc): (.x, .y), then (.z, .w)
+//   node NODE_TIME, slot 0   : .x = the sample's shutter time tau = (.x >> 8) * 2^-24 (motion blur, sample_time)
+// (NODE_CAMERA and NODE_TIME are odd: never a child_node value, which are even)
 constexpr uint32_t NODE_CAMERA = 0xFFFFFFFFu;
+constexpr uint32_t NODE_TIME = 0xFFFFFFFDu;
 RT_HD double u01_53(uint32_t lo, uint32_t hi) {  // rand 0.8 Standard f64: (u64 >> 11) * 2^-53
   // u >> 11 = h * 2^32 + l with h = hi >> 11 (21 bits), l = the 32 bits below: the value h * 2^-21 + l * 2^-53 is a 53-bit
   // number < 1, so both products and their sum are exact — the same bits as converting the 64-bit integer and scaling it,
@@ -369,6 +375,11 @@ RT_HD void lens_disc(const RngAddr& a, double& x, double& y) {
     if (x * x + y * y < 1.0) return;
   }
 }
+
+// The shutter time of a sample (motion blur): tau in [0, 1) on a 2^-24 grid, exact in f32 (one VGPR) and in f64.  Every
+// segment of the sample — camera ray, bounces, nested light rays — is traced at this one tau, so a sample still depends on (pixel,
+// sample) alone.
+RT_HD float sample_time(const RngAddr& a) { return (float)(rng(a, NODE_TIME, 0u).x >> 8) * 5.9604644775390625e-08f; }
 
 // ------------------------------------------------------------------ conservative f32 cull
 // A sphere can only be hit (sphere.rs:51-53, discriminant >= 0) if the f32 quantity below is
@@ -892,6 +903,30 @@ struct GlobalTables {
   // two dependent global loads (a light ray starts in nearly every wave iteration of a lit scene)
   RT_HD V3 light_centre(const DevScene& sc, uint32_t j) const { const SphereGeom lg = g[sc.lights[j]]; return v3(lg.cx, lg.cy, lg.cz); }
 };
+
+// A sphere's geometry at shutter time tau: c_k = c0_k + dv_k * tau in f64, two roundings (the build has
+// -ffp-contract=off).  dv_k = -0.0 for a component that does not move, so c0_k + (-0.0) * tau gives c0_k's own bits back (+0 and -0
+// included): a static sphere of a motion scene is tested on exactly the bits it has in a static one.
+RT_HD SphereGeom geom_at(SphereGeom g, double dx, double dy, double dz, double tau) {
+  g.cx = g.cx + dx * tau; g.cy = g.cy + dy * tau; g.cz = g.cz + dz * tau;
+  return g;
+}
+// The one accessor of the MOTION code paths: a table type whose geom(i) is sphere i at the lane's tau (dv = DevScene::motion).
+// Materials and the light centres (lights never move) come from the wrapped tables unchanged.
+template <class Base>
+struct MotionTables {
+  Base b;
+  const double* dv;
+  double tau;
+  RT_HD SphereGeom geom(uint32_t i) const {
+    const double* m = dv + 4u * (size_t)i;
+    return geom_at(b.geom(i), m[0], m[1], m[2], tau);
+  }
+  RT_HD MatCore mat(uint32_t i) const { return b.mat(i); }
+  RT_HD V3 light_centre(const DevScene& sc, uint32_t j) const { return b.light_centre(sc, j); }
+};
+template <class Base>
+RT_HD MotionTables<Base> motion_tables(const Base& b, const double* dv, float tau) { return MotionTables<Base>{b, dv, (double)tau}; }
 
 // ------------------------------------------------------------------ scatter (materials.rs:44-54)
 enum { SCATTER_ABSORBED = 0, SCATTER_EMIT = 1, SCATTER_RAY = 2 };
@@ -1776,7 +1811,10 @@ RT_HD uint8_t linear_to_u8(float lin) { return f32_to_u8(__builtin_sqrtf(lin)); 
 // [0, n) of what the CAMERA ray of each sample meets first — the ray the megakernel traces for that sample (the same Philox
 // address, lane_begin_sample_w).  Summed in f64 in sample order, divided by n, rounded once to f32.
 constexpr uint32_t AOV_FLOATS = 8u;
-template <bool LENS, class Tables>
+// MOTION: the first hit at the sample's shutter time (sample_time), through the same MotionTables as the MOTION megakernels.
+template <class Tables>
+RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]);
+template <bool LENS, bool MOTION = false, class Tables>
 RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py, uint32_t n, float out[8]) {
   double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Lane<false> L;
@@ -1784,6 +1822,14 @@ RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t
   for (uint32_t s = 0; s < n; ++s) {
     L.s = s;
     lane_begin_sample<LENS>(sc, L, px, py);
+    if constexpr (MOTION) aov_sample(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
+    else aov_sample(sc, tb, L, acc);
+  }
+  for (int i = 0; i < 8; ++i) out[i] = (float)(acc[i] / (double)n);
+}
+template <class Tables>
+RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]) {
+  {
     double closest = T_MAX;
     int best = -1;
     uint32_t n_exact = 0, n_steps = 0, tex_oob = 0;
@@ -1809,7 +1855,6 @@ RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t
     }
     acc[0] += (double)a[0]; acc[1] += (double)a[1]; acc[2] += (double)a[2];
   }
-  for (int i = 0; i < 8; ++i) out[i] = (float)(acc[i] / (double)n);
 }
 
 // Edge-avoiding a-trous filter (Dammertz et al. 2010, rational weight).  Iteration i of L (L <= DENOISE_MAX_ITERATIONS): a 5x5

@@ -117,6 +117,8 @@ struct RtHipScene {
     int device = 0;
     DevBuf geom, mat, lights, tex, sky, tex4, sky4, matc, cell_word, cell_items, large, large_geom;
     DevBuf all;              // 0..n-1: the `large` list of the brute-force arm (variant 1)
+    DevBuf motion;           // motion blur: [n][4] dv per sphere (rt_tables.h HostTables::motion); unallocated when static
+    uint32_t n_moving = 0;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -320,6 +322,12 @@ int rt_hip_scene_clone_view(const RtHipScene* src, RtHipScene** out) {
 }
 
 extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene** out) {
+  return rt_hip_scene_create_moving(scene, nullptr, device, out);
+}
+
+// motion blur: the tables of a scene whose spheres move from center to center1 over the shutter.  Fixed at creation
+// (the grid lists each moving sphere by its swept box); a null center1, or one equal to every centre, is the static scene.
+extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int device, RtHipScene** out) {
   if (!scene || !out) return fail(RT_ERR_INVALID, "null argument");
   *out = nullptr;
   int n = rt_hip_device_count();
@@ -328,7 +336,7 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
   if (!rtp::tl_in_group) rtp::reset();
   rtp::Clock pc;
   rtc::HostTables t;
-  std::string why = rtc::build_tables(*scene, t);
+  std::string why = rtc::build_tables(*scene, t, false, center1);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
@@ -358,6 +366,8 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
   if ((rc = t.grid.wide ? upload(r->cell_items, t.cell_items32) : upload(r->cell_items, t.cell_items)) != RT_OK) return rc;  // (wide tables: the 32-bit item lists)
   if ((rc = upload(r->large, t.large)) != RT_OK) return rc;
   if ((rc = upload(r->large_geom, t.large_geom)) != RT_OK) return rc;
+  if (t.n_moving && (rc = upload(r->motion, t.motion)) != RT_OK) return rc;
+  r->n_moving = t.n_moving;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
@@ -396,6 +406,7 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
   s->dev.matc = r->matc.get<const rtc::MatCore>(); s->dev.cell_word = r->cell_word.get<const uint32_t>();
   s->dev.cell_items = r->cell_items.get<const uint16_t>(); s->dev.large = r->large.get<const uint32_t>();
   s->dev.large_geom = r->large_geom.get<const rtc::SphereGeom>();
+  s->dev.motion = r->n_moving ? r->motion.get<const double>() : nullptr;
   s->res = std::move(r);
   auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
@@ -441,29 +452,34 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
   return fail(RT_ERR_INVALID, std::string("unknown option ") + key);
 }
 
+#ifdef RT_MOTION_TU_SPLIT  // (the product build: rt_kernel_motion.hip compiles the MOTION half of the kernel set beside this file)
+#define RT_MOTION_EXTERN(HL, S, LDS, WIDE, A, LE) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, WIDE, A, LE, true>(rtk::KArgs);
+RT_MOTION_INSTANTIATIONS(RT_MOTION_EXTERN)
+#endif
+
 namespace {
 
-// The megakernel instantiations and their keys: LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1 (lights, every albedo in
-// [0, 1], tables in LDS, wide cell tables, accumulating, thin lens).  Wide tables are never staged in LDS (plan_lds): those 16 keys
-// have no instantiation.
+// The megakernel instantiations and their keys: MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1 (lights, every
+// albedo in [0, 1], tables in LDS, wide cell tables, accumulating, thin lens, moving spheres).  Wide tables are never staged in LDS
+// (plan_lds): those 32 keys have no instantiation.
 using Megakernel = void (*)(rtk::KArgs);
 template <int K> Megakernel megakernel_of_key() {
   if constexpr ((K & 9) == 9) return nullptr;
-  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, (K & 8) != 0, (K & 16) != 0, (K & 32) != 0>;
+  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, (K & 8) != 0, (K & 16) != 0, (K & 32) != 0, (K & 64) != 0>;
 }
-// J counts up over (LENS, ACCUM, WIDE, HL, LDS, SIMPLE); the compiler emits the kernels in the reverse of that order, the order they
-// have always had, which keeps the code object's layout (and tools/codeobj_stats.py's report) as it was
+// J counts up over (MOTION, LENS, ACCUM, WIDE, HL, LDS, SIMPLE); the compiler emits the kernels in the reverse of that order, the
+// order they have always had, which keeps the code object's layout (and tools/codeobj_stats.py's report) as it was
 template <int J> constexpr int key_at = (J & ~3) | ((J & 1) << 1) | ((J >> 1) & 1);
-template <int... J> std::array<Megakernel, 64> megakernels(std::integer_sequence<int, J...>) {
-  std::array<Megakernel, 64> t{};
+template <int... J> std::array<Megakernel, 128> megakernels(std::integer_sequence<int, J...>) {
+  std::array<Megakernel, 128> t{};
   ((t[key_at<J>] = megakernel_of_key<key_at<J>>()), ...);
   return t;
 }
 struct Kernel { int key = -1; Megakernel fn = nullptr; };
 int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
-  static const std::array<Megakernel, 64> table = megakernels(std::make_integer_sequence<int, 64>());
+  static const std::array<Megakernel, 128> table = megakernels(std::make_integer_sequence<int, 128>());
   if (wide && lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
-  out->key = (s->dev.lens_r != 0.0 ? 32 : 0) | (accum ? 16 : 0) | (wide ? 8 : 0) | (has_lights ? 4 : 0) | (s->res->simple_colour ? 2 : 0) | (lds_tables ? 1 : 0);
+  out->key = (s->dev.motion ? 64 : 0) | (s->dev.lens_r != 0.0 ? 32 : 0) | (accum ? 16 : 0) | (wide ? 8 : 0) | (has_lights ? 4 : 0) | (s->res->simple_colour ? 2 : 0) | (lds_tables ? 1 : 0);
   out->fn = table[out->key];
   return RT_OK;
 }
@@ -1006,7 +1022,8 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
   if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
   // the last rt_hip_render_adaptive_to_host: its rounds, and round i's tiles, samples per pixel after it, kernel time in microseconds
@@ -1194,7 +1211,9 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   if (!d_aov) return fail(RT_ERR_INVALID, "null AOV buffer");
   if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
   RT_HIP_TRY(hipSetDevice(s->device));
-  if (s->dev.lens_r != 0.0) hipLaunchKernelGGL(rtk::rt_aov_lens, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  const bool lens = s->dev.lens_r != 0.0;
+  if (s->dev.motion) hipLaunchKernelGGL(lens ? rtk::rt_aov_lens_motion : rtk::rt_aov_motion, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  else if (lens) hipLaunchKernelGGL(rtk::rt_aov_lens, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   else hipLaunchKernelGGL(rtk::rt_aov, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;

@@ -406,12 +406,16 @@ namespace rtg {
 // stream of its own is a hardware queue the runtime has to create (7.8 ms each on MI355X, serialised: tools/microbench/
 // setup_costs.hip, profiles/r06_run3_setup_costs.log) and buys a single blocking frame nothing: a one-rank one-shot group
 // renders, assembles and copies on the device's NULL stream, whose queue exists since the device was warmed.
-int group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot);
+int group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot, const double* center1 = nullptr);
 }
 extern "C" int rt_hip_group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out) {
   return rtg::group_create(scene, n_gpus, out, false);
 }
-int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot) {
+// motion blur: every rank's scene is rt_hip_scene_create_moving's (its overlap view shares the resident motion table)
+extern "C" int rt_hip_group_create_moving(const RtScene* scene, const double* center1, uint32_t n_gpus, RtHipGroup** out) {
+  return rtg::group_create(scene, n_gpus, out, false, center1);
+}
+int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot, const double* center1) {
   if (!scene || !out) return fail(RT_ERR_INVALID, "null argument");
   *out = nullptr;
   const int ndev = rt_hip_device_count();
@@ -469,12 +473,12 @@ int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, b
   {
     std::vector<std::thread> th;
     for (uint32_t r = 0; r < G; ++r)
-      th.emplace_back([g, scene, r]() {
+      th.emplace_back([g, scene, r, center1]() {
         rtp::tl_record = r == 0;
         rtp::tl_in_group = true;
         rtp::Clock rc_clock;
         rtg::pin_to_rank(g, r);  // (the replica's pinned counter words and staging copies are first touched on the device's node)
-        g->rc[r] = rt_hip_scene_create(scene, g->device[r], &g->scene[r]);
+        g->rc[r] = rt_hip_scene_create_moving(scene, center1, g->device[r], &g->scene[r]);
         if (g->rc[r] != RT_OK) { g->err[r] = rt_hip_last_error(); return; }
         rc_clock.t = std::chrono::steady_clock::now();   // (the scene's own stages are booked by rt_hip_scene_create)
         bool ok = !g->own_streams || (hipStreamCreateWithFlags(&g->stream[r], hipStreamNonBlocking) == hipSuccess &&

@@ -327,7 +327,10 @@ struct LdsTables {  // per-lane gathers from the workgroup's LDS copies
 // the queue, the pools, the paths — is the one-shot kernel's, which is why a frame made of passes is the one-shot frame.
 // LENS: the thin-lens camera: each new sample's camera ray leaves a point of the lens (rt_core.h lane_begin_sample_w);
 // a compile-time arm, so the pinhole instantiations stay the code they were.
-template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false>
+// MOTION: motion blur: each new sample draws its shutter time tau (rt_core.h sample_time), kept in one register for
+// the whole sample, and every read of a sphere's geometry — the `large` list, the full scan, the walk, the shading — is the sphere
+// at tau (rt_core.h geom_at / MotionTables, dv from HBM / L2).  A compile-time arm: the static instantiations stay the code they were.
+template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false, bool MOTION = false>
 __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs ka) {
   static_assert(!(LDS_TABLES && WIDE), "wide tables (more than 65 535 spheres) never fit LDS");
   const DevScene& sc = ka.sc;
@@ -419,6 +422,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     if (L.n_tex_oob != 0u) { __hip_atomic_fetch_add(&wg_counters[2], (unsigned long long)L.n_tex_oob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); L.n_tex_oob = 0u; }
   };
   uint32_t n_exact = 0, n_steps = 0;  // per-lane counters (one exec-masked add each)
+  float tau = 0.0f;  // MOTION: the shutter time of the lane's current sample (set where the sample starts; unused otherwise)
   // LIT kernels count segments per WAVE on the scalar unit (the lanes of the trace's lane mask: one s_bcnt1 per iteration)
   // and send out-of-range texel fetches — practically never — straight to the workgroup's counter: two registers every
   // lane carried across the walk loop, in the lit kernels exactly the pair that was spilled there (15 scratch round trips
@@ -771,7 +775,13 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
         const F64PtrK np = lg + (size_t)nx * 4u;
         SphereGeom gn; gn.cx = np[0]; gn.cy = np[1]; gn.cz = np[2]; gn.r = np[3];
         const uint32_t idxn = large_k[nx];
-        if (has_ray && rk.fast) exact_hit_any_order_t<true>(L.o, L.d, rk, g, idx, closest, best);
+        if constexpr (MOTION) {  // (the record and its dv are scalar; the centre at the lane's tau is per lane)
+          const F64PtrK mv = (F64PtrK)(uintptr_t)sc.motion + (size_t)idx * 4u;
+          const double mx = mv[0], my = mv[1], mz = mv[2];
+          if (has_ray && rk.fast) exact_hit_any_order_t<true>(L.o, L.d, rk, geom_at(g, mx, my, mz, (double)tau), idx, closest, best);
+        } else {
+          if (has_ray && rk.fast) exact_hit_any_order_t<true>(L.o, L.d, rk, g, idx, closest, best);
+        }
         g = gn; idx = idxn;
       }
     }
@@ -784,6 +794,11 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
       for (uint32_t idx = 0; idx < sc.n_spheres; ++idx) {
         const F64PtrK gp = geom_k + (size_t)idx * 4u;
         SphereGeom g; g.cx = gp[0]; g.cy = gp[1]; g.cz = gp[2]; g.r = gp[3];
+        if constexpr (MOTION) {
+          const F64PtrK mv = (F64PtrK)(uintptr_t)sc.motion + (size_t)idx * 4u;
+          const double mx = mv[0], my = mv[1], mz = mv[2];
+          if (mode == GRID_FALLBACK) g = geom_at(g, mx, my, mz, (double)tau);
+        }
         if (mode == GRID_FALLBACK) { const HitCB r = exact_hit_slow(L.o, L.d, rk.a, g, idx, closest, best); closest = r.closest; best = r.best; }
       }
       if (mode == GRID_FALLBACK) n_exact += sc.n_spheres;
@@ -897,7 +912,8 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
             it++;
             if (idx != last) {  // a sphere spanning consecutive cells is not re-tested
               last = idx; n_exact++;
-              exact_hit_any_order_t<true>(L.o, L.d, rk, tb.geom(idx), idx, closest, best);
+              if constexpr (MOTION) exact_hit_any_order_t<true>(L.o, L.d, rk, motion_tables(tb, sc.motion, tau).geom(idx), idx, closest, best);
+              else exact_hit_any_order_t<true>(L.o, L.d, rk, tb.geom(idx), idx, closest, best);
             }
           }
         }
@@ -974,9 +990,11 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     if (has_ray) {
 #ifdef RT_PROF_LIT
       rtc::ShadeProf shade_prof{prof_t, &prof_last, &cnt_w_step, &cnt_w_test};
-      status = lane_shade(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      if constexpr (MOTION) status = lane_shade(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      else status = lane_shade(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
 #else
-      status = lane_shade(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      if constexpr (MOTION) status = lane_shade(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      else status = lane_shade(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
 #endif
       if constexpr (HL) { if (status == LANE_REPEAT) L.n_tex_oob = 0u; }  // (the hit is shaded again next iteration: its out-of-range texel counts THEN, once — RtStats.tex_oob equals the oracle's)
       flush_oob();
@@ -997,7 +1015,10 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     count_tiles(miss || finished, miss ? k_miss : my_k);
     RT_PROF(4);
     // (e) the new samples start (raytracer.rs:199-201, camera.rs:79-84)
-    if (fresh) { lane_begin_sample_w<LENS>(fresh_args().sc, L, n_px, n_py, cam_w); has_ray = true; }
+    if (fresh) {
+      lane_begin_sample_w<LENS>(fresh_args().sc, L, n_px, n_py, cam_w); has_ray = true;
+      if constexpr (MOTION) tau = sample_time(L.ra);  // (kept across the sample's light activations: the lane holds the sample to its end)
+    }
 #ifdef RT_TEST_PROBES
     if (fresh && fresh_args().probe_rays) {  // (the jitter's Philox call above still happened: the RNG stream is the frame's)
       const double* r = fresh_args().probe_rays + ((size_t)n_py * fresh_args().sc.width + n_px) * 6u;
@@ -1061,6 +1082,16 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
   }
 }
 
+// The 48 MOTION instantiations (the static 48 with MOTION = true), as X(HL, SIMPLE, LDS_TABLES, WIDE, ACCUM, LENS): wide tables are never
+// staged in LDS.  The product build compiles them in a translation unit of their own, rt_kernel_motion.hip, beside rt_hip_api.hip
+// (build.py, -DRT_MOTION_TU_SPLIT): the two halves build in parallel instead of one twice as long.
+#define RT_MOTION_TABLES(X, HL, S, A, LE) X(HL, S, false, false, A, LE) X(HL, S, true, false, A, LE) X(HL, S, false, true, A, LE)
+#define RT_MOTION_MODES(X, HL, S) RT_MOTION_TABLES(X, HL, S, false, false) RT_MOTION_TABLES(X, HL, S, true, false) \
+                                  RT_MOTION_TABLES(X, HL, S, false, true) RT_MOTION_TABLES(X, HL, S, true, true)
+#define RT_MOTION_INSTANTIATIONS(X) RT_MOTION_MODES(X, false, false) RT_MOTION_MODES(X, false, true) RT_MOTION_MODES(X, true, false) \
+                                    RT_MOTION_MODES(X, true, true)
+
+#ifndef RT_KERNEL_MOTION_TU  // (rt_kernel_motion.hip takes the megakernel template alone; everything below is rt_hip_api.hip's)
 // Launched once when a scene is created: the runtime loads a module's code object onto the device with the first launch of ANY
 // of its kernels — milliseconds that would otherwise sit inside the first frame.
 __global__ void rt_warm_up() {}
@@ -1206,13 +1237,13 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
 // --------------------------------------------------------------------------- denoising
 // Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
 // 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
-template <bool LENS>
+template <bool LENS, bool MOTION = false>
 __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float4* __restrict__ out) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x >= sc.width || y >= sc.height) return;
   const GlobalTables tb{sc.geom, sc.matc};
   float r[8];
-  aov_pixel<LENS>(sc, tb, x, y, n, r);
+  aov_pixel<LENS, MOTION>(sc, tb, x, y, n, r);
   const size_t p = (size_t)y * sc.width + x;
   out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
   out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
@@ -1220,6 +1251,9 @@ __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float
 __global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false>(sc, n, out); }
 // (the thin-lens camera, DESIGN.md §13: the same first ray as the LENS megakernels)
 __global__ __launch_bounds__(256) void rt_aov_lens(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true>(sc, n, out); }
+// (motion blur, DESIGN.md §14: the first hit at each sample's shutter time, as the MOTION megakernels trace it)
+__global__ __launch_bounds__(256) void rt_aov_motion(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, true>(sc, n, out); }
+__global__ __launch_bounds__(256) void rt_aov_lens_motion(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, true>(sc, n, out); }
 
 // One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
 // ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two
@@ -1346,5 +1380,6 @@ __global__ void rt_quot_probe(const double* x, const double* y, double* out_quot
   if (out_div) out_div[i] = rt_div_inrange(x[i], y[i]);
 }
 #endif  // RT_TEST_PROBES
+#endif  // !RT_KERNEL_MOTION_TU
 
 }  // namespace rtk

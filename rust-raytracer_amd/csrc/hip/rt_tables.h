@@ -47,7 +47,24 @@ struct HostTables {
   std::vector<uint32_t> cell_items32;  // grid.wide: the item lists as 32-bit indices (cell_items is empty then)
   std::vector<uint32_t> large;
   std::vector<SphereGeom> large_geom;
+  // motion blur: [n][4] {dv = center1 - center, 0} with a zero component stored as -0.0; EMPTY for a static scene
+  // (no center1, or one equal to every centre).  n_moving: spheres with some dv component != 0.
+  std::vector<double> motion;
+  uint32_t n_moving = 0;
 };
+
+// The box a sphere's centre can occupy over the shutter, axis k: [c0 - |r|, c0 + |r|] for a static sphere (today's expressions), and
+// for a moving one the union of its boxes at c0 and c0 + dv, grown by a world-space slack that bounds the rounding of the kernel's
+// c0 + dv * tau (two f64 roundings, each <= 2^-53 of |c0| + |dv|) off the true segment: 4 * 2^-52 (|c0| + |dv|) + 1e-300.
+inline void sphere_box(const RtSphere& s, const HostTables& t, uint32_t i, int k, double& lo, double& hi) {
+  const double r = std::fabs(s.radius);
+  if (t.motion.empty() || t.motion[4 * (size_t)i + 3] == 0.0) { lo = s.center[k] - r; hi = s.center[k] + r; return; }
+  const double c0 = s.center[k], dv = t.motion[4 * (size_t)i + k], c1 = c0 + dv;
+  const double slack = 4.0 * 2.220446049250313e-16 * (std::fabs(c0) + std::fabs(dv)) + 1e-300;
+  lo = std::min(c0, c1) - r - slack;
+  hi = std::max(c0, c1) + r + slack;
+}
+inline bool sphere_moves(const HostTables& t, uint32_t i) { return !t.motion.empty() && t.motion[4 * (size_t)i + 3] != 0.0; }
 
 // Grid construction knobs (development tunables; the defaults are what ships).
 // Bytes the per-segment tables (geometry, material cores, cell entries, item lists) may take so
@@ -86,6 +103,9 @@ inline GridParams grid_params_from_env() {
 // `wide`: the table format (GridDesc.wide).  Returns false — with nothing usable in `t` — when the PACKED format cannot hold this
 // grid (more than 65 535 spheres: its item indices are u16, 0xFFFF = none; more than 4 095 items in a cell; 2^20 items or more):
 // the caller builds it again wide.
+// Motion (HostTables::motion not empty): every moving sphere is listed by its SWEPT box (sphere_box) grown by the same 2*pull margin,
+// with no per-cell distance test — so every cell holding a hit point at any tau is visited or within the margin of one that lists
+// it, as for a static sphere.  The `large` policy ranks a moving sphere by |r| + max_k |dv_k| / 2.
 inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp, bool wide) {
   const uint32_t n = sc.n_spheres;
   GridDesc& G = t.grid;
@@ -126,7 +146,11 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
     double r_rest = 0.0;  // the largest radius that is no candidate
     for (uint32_t i = 0; i < n; ++i) {
       if (is_large[i]) continue;
-      const double r = std::fabs(sc.spheres[i].radius);
+      double r = std::fabs(sc.spheres[i].radius);
+      if (sphere_moves(t, i)) {  // (the swept extent: half the longest axis of the sweep on top of the radius)
+        const double* m = &t.motion[4 * (size_t)i];
+        r = r + 0.5 * std::max(std::fabs(m[0]), std::max(std::fabs(m[1]), std::fabs(m[2])));
+      }
       if (r > gp.large_radius_ratio * r_med) big.push_back({r, i}); else r_rest = std::max(r_rest, r);
     }
     std::sort(big.begin(), big.end(), [](const std::pair<double, uint32_t>& a, const std::pair<double, uint32_t>& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); });
@@ -142,8 +166,10 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
     if (is_large[i]) continue;
     n_grid++;
     for (int k = 0; k < 3; ++k) {
-      lo[k] = std::min(lo[k], s.center[k] - std::fabs(s.radius));
-      hi[k] = std::max(hi[k], s.center[k] + std::fabs(s.radius));
+      double bl, bh;
+      sphere_box(s, t, i, k, bl, bh);
+      lo[k] = std::min(lo[k], bl);
+      hi[k] = std::max(hi[k], bh);
     }
   }
   if (n_grid < gp.min_spheres) { all_large(); return true; }
@@ -186,9 +212,10 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
     const RtSphere& s = sc.spheres[i];
     uint64_t cells = 1;
     for (int k = 0; k < 3; ++k) {
-      const double r = std::fabs(s.radius);
-      double a = std::floor((s.center[k] - r - G.gmin[k]) * G.inv_cell[k] - m);
-      double b = std::floor((s.center[k] + r - G.gmin[k]) * G.inv_cell[k] + m);
+      double bl, bh;
+      sphere_box(s, t, i, k, bl, bh);
+      double a = std::floor((bl - G.gmin[k]) * G.inv_cell[k] - m);
+      double b = std::floor((bh - G.gmin[k]) * G.inv_cell[k] + m);
       a = std::max(a, 0.0); b = std::min(b, (double)G.n[k] - 1.0);
       rng[i].a[k] = (int)a; rng[i].b[k] = (int)b;
       cells *= (uint64_t)(b >= a ? (int)b - (int)a + 1 : 0);
@@ -208,6 +235,8 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
     const double r = std::fabs(s.radius) * (1.0 + 1e-9);
     return d2 <= r * r;
   };
+  std::vector<uint8_t> moving(n, 0);
+  for (uint32_t i = 0; i < n; ++i) moving[i] = sphere_moves(t, i) ? 1 : 0;
   std::vector<uint32_t> count(n_inner, 0);
   auto padded = [&](uint32_t c) {
     const uint32_t ix = c % G.n[0], iy = (c / G.n[0]) % G.n[1], iz = c / (G.n[0] * G.n[1]);
@@ -243,7 +272,7 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
       for (int iz = rng[i].a[2]; iz <= rng[i].b[2]; ++iz)
         for (int iy = rng[i].a[1]; iy <= rng[i].b[1]; ++iy)
           for (int ix = rng[i].a[0]; ix <= rng[i].b[0]; ++ix) {
-            if (!overlaps(s, ix, iy, iz)) continue;
+            if (!moving[i] && !overlaps(s, ix, iy, iz)) continue;  // (a moving sphere: every cell of its swept box)
             const uint32_t c = (uint32_t)ix + G.n[0] * ((uint32_t)iy + G.n[1] * (uint32_t)iz);
             if (pass == 0) count[c]++;
             else if (wide) t.cell_items32[cursor[c]++] = i;
@@ -275,7 +304,9 @@ inline void build_grid(const RtScene& sc, HostTables& t, const GridParams& gp) {
 // returns "" or a description of why the scene is invalid (RT_ERR_INVALID)
 // want_cull: also the round-1 cull-pair table (HostTables::cull) — no kernel reads it any more; tests/hostsim's audit mode and
 // tools/analysis/walk_sim.cpp do (the product's rt_hip_scene_create leaves it out since round 6).
-inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull = false) {
+// center1 (motion blur): null, or [n_spheres][3] centres at shutter close (rt_scene_motion); a sphere whose center1
+// equals its centre (NaN components: both NaN) is static.  dv = center1 - center must be finite, and a Light sphere cannot move.
+inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull = false, const double* center1 = nullptr) {
   if (sc.abi_version != RT_ABI_VERSION) return "abi_version mismatch";
   if (sc.width == 0 || sc.height == 0) return "empty image";
   if (sc.n_spheres && !sc.spheres) return "null sphere table";
@@ -290,6 +321,27 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     t.tex_bytes += (sc.textures[i].nbytes + 15) & ~15ull;
   }
   const uint32_t n = sc.n_spheres;
+  t.motion.clear();
+  t.n_moving = 0;
+  if (center1 && sc.n_spheres) {
+    std::vector<double> mv(4 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+      const RtSphere& s = sc.spheres[i];
+      bool moves = false;
+      for (int k = 0; k < 3; ++k) {
+        const double c0 = s.center[k], c1 = center1[3 * (size_t)i + k];
+        const bool same = c1 == c0 || (c1 != c1 && c0 != c0);
+        const double dv = same ? -0.0 : c1 - c0;
+        if (!same && !(dv != 0.0 && std::isfinite(dv))) return "sphere " + std::to_string(i) + ": center1 - center is not finite";
+        mv[4 * (size_t)i + k] = dv;
+        moves = moves || !same;
+      }
+      mv[4 * (size_t)i + 3] = moves ? 1.0 : 0.0;  // (the pad word: 1 = this sphere moves; the kernel never reads it)
+      if (moves && s.kind == RT_MAT_LIGHT) return "sphere " + std::to_string(i) + ": a Light sphere cannot move";
+      if (moves) t.n_moving++;
+    }
+    if (t.n_moving) t.motion.swap(mv);
+  }
   t.geom.resize(n);
   t.mat.resize(n);
   t.matc.resize(n);

@@ -37,6 +37,9 @@
 // Thin lens: a scene whose camera has a non-zero "aperture" renders through the lens in every mode above —
 // rt_camera_derive_lens gives the camera on the focus plane and the lens, set next to each other on the resident scene or group
 // (every --frames camera is re-derived so).  RtScene has no lens, so such a one-shot frame goes through a group, not rt_render_rgb8.
+//
+// Motion blur: a scene whose spheres have "center1" (rt_scene_motion) is created with rt_hip_scene_create_moving /
+// rt_hip_group_create_moving in every mode above, with or without a lens; its one-shot frame goes through a one-frame group too.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -187,7 +190,7 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
   RtScene* sc = rt_scene_get_mut(sf);
   RtHipGroup* hs = nullptr;  // the scene resident on RT_GPUS devices (default 1)
   const auto t_create = std::chrono::steady_clock::now();
-  int rc = rt_hip_group_create(sc, 0, &hs);
+  int rc = rt_hip_group_create_moving(sc, rt_scene_motion(sf), 0, &hs);
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
   (void)rt_hip_group_set_option(hs, "prepare_host_output", 2);  // (pinned staging for the two frames in flight + the copy path, at set-up: not inside the first submit)
   const auto t_begin = std::chrono::steady_clock::now();
@@ -247,7 +250,7 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
 int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool denoise = false, bool report_passes = true) {
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
-  int rc = rt_hip_scene_create(sc, 0, &hs);
+  int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
   if (rc == RT_OK) rc = set_scene_lens(sf, hs);
   std::printf("\nRendering %s\n", filename);  // main.rs:18
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
@@ -276,7 +279,7 @@ int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool den
 int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t min_spp) {
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
-  int rc = rt_hip_scene_create(sc, 0, &hs);
+  int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
   if (rc == RT_OK) rc = set_scene_lens(sf, hs);
   std::printf("\nRendering %s\n", filename);  // main.rs:18
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
@@ -331,7 +334,7 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
   for (unsigned g = 0; g < G; ++g)
     th.emplace_back([&, g]() {
       RtHipScene* hs = nullptr;
-      int rc = rt_hip_scene_create(sc, (int)(g % (unsigned)ndev), &hs);
+      int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), (int)(g % (unsigned)ndev), &hs);
       if (rc != RT_OK) { std::lock_guard<std::mutex> lk(out_mu); std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status[g] = 101; return; }
       std::vector<uint8_t> buf[2] = {std::vector<uint8_t>(bytes), std::vector<uint8_t>(bytes)};
       std::thread writer;
@@ -369,15 +372,18 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
   return 0;
 }
 
-// rt_render_rgb8 for a scene with a thin lens (RtScene carries none): the same one-frame group, with the lens camera c (rt_camera_derive_lens)
-int render_lens_rgb8(const RtScene* sc, const double c[20], uint8_t* out_rgb8, RtStats* stats) {
+// rt_render_rgb8 for a scene with a thin lens or moving spheres (RtScene carries neither): the same one-frame group, with the lens
+// camera c (rt_camera_derive_lens; null: RtScene's pinhole) and the spheres' centres at shutter close center1 (null: static)
+int render_group_rgb8(const RtScene* sc, const double* c, const double* center1, uint8_t* out_rgb8, RtStats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
   RtHipGroup* g = nullptr;
-  int rc = rt_hip_group_create(sc, 0, &g);
+  int rc = rt_hip_group_create_moving(sc, center1, 0, &g);
   if (rc != RT_OK) return rc;
   (void)rt_hip_group_set_option(g, "tile_order", 1);  // (one frame: no later frame could use a learned order — rt_render_rgb8's setting)
-  rc = rt_hip_group_set_camera(g, c, c + 3, c + 6, c + 9);
-  if (rc == RT_OK) rc = rt_hip_group_set_lens(g, c + 13, c + 16, c[19]);
+  if (c) {
+    rc = rt_hip_group_set_camera(g, c, c + 3, c + 6, c + 9);
+    if (rc == RT_OK) rc = rt_hip_group_set_lens(g, c + 13, c + 16, c[19]);
+  }
   if (rc == RT_OK) rc = rt_hip_group_set_option(g, "prepare_host_output", 1);
   const double setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (rc == RT_OK) rc = rt_hip_group_render_to_host(g, out_rgb8, stats);
@@ -508,7 +514,9 @@ int run(int argc, char** argv) {
   if (g_hip_init.joinable()) g_hip_init.join();  // (what of the runtime's start-up the load did not cover)
   const double hip_wait_ms = ms_since(t_hip), hip_init_ms = g_hip_init_ms;
   double cam_lens[20];
-  rc = lens_camera(sf, cam_lens) ? render_lens_rgb8(sc, cam_lens, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
+  const bool lens = lens_camera(sf, cam_lens);
+  const double* center1 = rt_scene_motion(sf);
+  rc = lens || center1 ? render_group_rgb8(sc, lens ? cam_lens : nullptr, center1, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
   if (rc != RT_OK) {
     std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error());
     rt_scene_free(sf);

@@ -190,6 +190,11 @@ struct RtSceneFile {
   // the thin lens: the file's "aperture" / "focus_dist" if it had them (has_*: rt_scene_to_json writes only those)
   double aperture = 0, focus_dist = 0;
   bool has_aperture = false, has_focus_dist = false;
+  // motion blur: each sphere's "center1" (its centre at shutter close), = its centre for a sphere without the key;
+  // has_center1[i]: the file had the key (rt_scene_to_json writes only those); n_center1: how many had it (0: rt_scene_motion is NULL)
+  std::vector<double> center1;
+  std::vector<uint8_t> has_center1;
+  size_t n_center1 = 0;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
   // concurrently, beside the parse), everything (read + parse + schema + waiting for the decodes)
   double read_ms = 0, json_ms = 0, jpeg_ms = 0, total_ms = 0;
@@ -353,8 +358,17 @@ void build_scene(const Value& root, RtSceneFile& sf) {
   sf.spheres.reserve(objs.items.size());
   for (auto& o : objs.items) {
     RtSphere s{};
-    const Value* sp[3];
-    struct_fields(*o, "Sphere", {"center", "radius", "material"}, sp);
+    const Value* sp[4] = {};
+    // (+ the optional "center1" of a map; the sequence form stays the reference's three fields)
+    if (o->kind == Value::Array) struct_fields(*o, "Sphere", {"center", "radius", "material"}, sp);
+    else {
+      try {
+        struct_fields(*o, "Sphere", {"center", "radius", "material", "center1"}, sp, {false, false, false, true});
+      } catch (const SchemaError& e) {
+        if (e.msg.find("center1") != std::string::npos) bad("objects[" + std::to_string(sf.spheres.size()) + "]: " + e.msg);
+        throw;
+      }
+    }
     as_point(*sp[0], "Sphere.center", s.center);
     s.radius = as_f64(*sp[1], "Sphere.radius");
     const Value& m = *sp[2];
@@ -388,6 +402,17 @@ void build_scene(const Value& root, RtSceneFile& sf) {
     } else {
       bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`");
     }
+    double c1[3] = {s.center[0], s.center[1], s.center[2]};
+    if (sp[3]) {
+      const std::string which = "objects[" + std::to_string(sf.spheres.size()) + "]";
+      if (s.kind == RT_MAT_LIGHT) bad(which + ": a Light sphere cannot move (center1)");
+      as_point(*sp[3], "Sphere.center1", c1);
+      for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(c1[k] - s.center[k])) bad(which + ": center1 - center is not finite");
+      sf.n_center1++;
+    }
+    sf.center1.insert(sf.center1.end(), c1, c1 + 3);
+    sf.has_center1.push_back(sp[3] ? 1 : 0);
     sf.spheres.push_back(s);
   }
   sc.spheres = sf.spheres.data(); sc.n_spheres = uint32_t(sf.spheres.size());
@@ -462,7 +487,9 @@ std::string scene_json(const RtSceneFile& sf) {
   for (size_t i = 0; i < sf.spheres.size(); ++i) {
     const RtSphere& s = sf.spheres[i];
     if (i) o += ",";
-    o += "{\"center\":" + point(s.center) + ",\"radius\":" + f64s(s.radius) + ",\"material\":{";
+    o += "{\"center\":" + point(s.center);
+    if (sf.has_center1[i]) o += ",\"center1\":" + point(&sf.center1[3 * i]);
+    o += ",\"radius\":" + f64s(s.radius) + ",\"material\":{";
     switch (s.kind) {
       case RT_MAT_LAMBERTIAN: o += "\"Lambertian\":{\"albedo\":" + albedo(s.albedo) + "}"; break;
       case RT_MAT_METAL: o += "\"Metal\":{\"albedo\":" + albedo(s.albedo) + ",\"fuzz\":" + f64s(s.fuzz_or_ior) + "}"; break;
@@ -539,6 +566,9 @@ extern "C" void rt_scene_lens(const RtSceneFile* sf, double out[2]) {
   if (!sf || !out) return;
   out[0] = sf->aperture;
   out[1] = sf->has_focus_dist ? sf->focus_dist : sf->focal_length;
+}
+extern "C" const double* rt_scene_motion(const RtSceneFile* sf) {
+  return sf && sf->n_center1 != 0 ? sf->center1.data() : nullptr;
 }
 extern "C" void rt_free(void* p) { std::free(p); }
 

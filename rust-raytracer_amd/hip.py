@@ -43,6 +43,7 @@ def _bind(path, probes):
     L.rt_strerror.argtypes = [C.c_int]
     L.rt_strerror.restype = C.c_char_p
     L.rt_hip_scene_create.argtypes = [C.POINTER(abi.RtScene), C.c_int, C.POINTER(C.c_void_p)]
+    L.rt_hip_scene_create_moving.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_void_p)]
     L.rt_hip_scene_destroy.argtypes = [C.c_void_p]
     L.rt_hip_scene_destroy.restype = None
     L.rt_hip_render.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -72,6 +73,7 @@ def _bind(path, probes):
     L.rt_abi_sizeof.restype = C.c_size_t
     L.rt_abi_version.restype = C.c_uint32
     L.rt_hip_group_create.argtypes = [C.POINTER(abi.RtScene), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.rt_hip_group_create_moving.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rt_hip_group_destroy.argtypes = [C.c_void_p]
     L.rt_hip_group_destroy.restype = None
     L.rt_hip_group_size.argtypes = [C.c_void_p]
@@ -144,14 +146,29 @@ def device_count():
     return lib().rt_hip_device_count()
 
 
+def _center1_array(scene_ptr, center1):
+    """n_spheres x 3 centres at shutter close as the C array rt_hip_*_create_moving read"""
+    n = scene_ptr.contents.n_spheres
+    flat = [float(x) for c in center1 for x in c]
+    if len(flat) != 3 * n:
+        raise ValueError(f"center1 needs {n} x 3 values, got {len(flat)}")
+    return (C.c_double * max(1, 3 * n))(*flat)
+
+
 class HipScene:
     """Scene tables + textures resident in HBM of one GPU (rt_hip_scene_create).  `library`: probe_lib() for the tests and
     tools that use the debug calls; default: the product library."""
 
-    def __init__(self, scene_ptr, device=0, library=None):
+    def __init__(self, scene_ptr, device=0, library=None, center1=None):
+        """center1 (motion blur): None, or each sphere's centre at shutter close, n_spheres x 3 (host.Scene.center1()):
+        rt_hip_scene_create_moving"""
         self._L = library or lib()
         self._h = C.c_void_p()
-        _check(self._L.rt_hip_scene_create(scene_ptr, device, C.byref(self._h)), self._L)
+        if center1 is None:
+            _check(self._L.rt_hip_scene_create(scene_ptr, device, C.byref(self._h)), self._L)
+        else:
+            c1 = _center1_array(scene_ptr, center1)
+            _check(self._L.rt_hip_scene_create_moving(scene_ptr, c1, device, C.byref(self._h)), self._L)
         sc = scene_ptr.contents
         self.width, self.height = sc.width, sc.height
         self.device = device
@@ -325,10 +342,14 @@ class HipGroup:
     """The scene resident on n_gpus devices of this node, frames sharded by interleaved scanline tiles
     inside librt_hip.so (rt_hip_group_*): host threads + streams + ONE gather per frame, no torch."""
 
-    def __init__(self, scene_ptr, n_gpus=0, library=None):
+    def __init__(self, scene_ptr, n_gpus=0, library=None, center1=None):
         self._L = library or lib()     # (library: probe_lib() for the tests that inject transport faults)
         self._h = C.c_void_p()
-        _check(self._L.rt_hip_group_create(scene_ptr, n_gpus, C.byref(self._h)), self._L)
+        if center1 is None:
+            _check(self._L.rt_hip_group_create(scene_ptr, n_gpus, C.byref(self._h)), self._L)
+        else:  # (motion blur, DESIGN.md §14: rt_hip_group_create_moving)
+            c1 = _center1_array(scene_ptr, center1)
+            _check(self._L.rt_hip_group_create_moving(scene_ptr, c1, n_gpus, C.byref(self._h)), self._L)
         sc = scene_ptr.contents
         self.width, self.height = sc.width, sc.height
         self.size = self._L.rt_hip_group_size(self._h)

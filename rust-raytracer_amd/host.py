@@ -42,6 +42,8 @@ def lib():
         L.rt_camera_derive_lens.restype = None
         L.rt_scene_lens.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.rt_scene_lens.restype = None
+        L.rt_scene_motion.argtypes = [C.c_void_p]
+        L.rt_scene_motion.restype = C.POINTER(C.c_double)
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
         L.rt_jpeg_decode_file.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -92,6 +94,15 @@ class Scene:
         buf = C.create_string_buffer(need.value)
         _check(lib().rt_scene_to_json(self._h, buf, need.value, None))
         return buf.value.decode("utf-8")
+
+    def center1(self):
+        """motion blur: each sphere's centre at shutter close as a list of [x, y, z] (its centre for a sphere without
+        the key), or None when no sphere of the file has "center1" (rt_scene_motion)"""
+        p = lib().rt_scene_motion(self._h)
+        if not p:
+            return None
+        n = self.c.n_spheres
+        return [[p[3 * i], p[3 * i + 1], p[3 * i + 2]] for i in range(n)]
 
     def lights(self):
         sc = self.c
