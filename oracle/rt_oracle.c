@@ -83,6 +83,10 @@ void rt_oracle_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint3
  *                             (the word attempt 0 leaves over: one Philox call serves both draws of such a hit)
  * node = k for the k-th segment of the camera path, rt_child_node() for nested light rays. */
 #define NODE_CAMERA 0xFFFFFFFFu
+/* the extensions (include/rt_abi.h):
+ *   node 0xFFFFFFFF, slot 1+a : attempt a of the lens point: candidates (word 0, word 1) then (word 2, word 3)
+ *   node 0xFFFFFFFD, slot 0   : word 0 = the sample's shutter time, (word >> 8) * 2^-24 */
+#define NODE_TIME 0xFFFFFFFDu
 
 typedef struct {
   const RtScene* scene;
@@ -96,6 +100,12 @@ typedef struct {
   uint64_t segments_discarded;
   /* rt_oracle_render_rays: the camera ray of every sample of pixel p is rays[6p .. 6p+5] (origin, direction); NULL: get_ray's */
   const double* rays;
+  /* motion blur: dv[3i .. 3i+2] = center1 - center of sphere i (a zero component -0.0), NULL for a static scene;
+   * tau = the shutter time of the sample being traced, the same for every segment of it (nested light rays included) */
+  const double* dv;
+  double tau;
+  /* thin lens: rt_hip_set_lens's arguments; lens_r == 0 is the pinhole */
+  const double* lens_u; const double* lens_v; double lens_r;
 } Ctx;
 
 static void rng_words(const Ctx* c, uint32_t node, uint32_t slot, uint32_t w[4]) {
@@ -231,7 +241,12 @@ static int hit_world(Ctx* c, Ray r, double t_min, double t_max, HitRecord* best)
   for (uint32_t i = 0; i < sc->n_spheres; ++i) {
     const RtSphere* s = &sc->spheres[i];
     HitRecord h;
-    if (sphere_hit(p3(s->center[0], s->center[1], s->center[2]), s->radius, r, t_min, closest_so_far, &h)) {
+    P3 center = p3(s->center[0], s->center[1], s->center[2]);
+    if (c->dv) { /* the centre at the sample's shutter time, c0 + dv * tau, a product and a sum each rounded */
+      const double* dv = c->dv + 3 * (size_t)i;
+      center = p3_add(center, p3_muls(p3(dv[0], dv[1], dv[2]), c->tau));
+    }
+    if (sphere_hit(center, s->radius, r, t_min, closest_so_far, &h)) {
       closest_so_far = h.t;
       h.idx = i;
       *best = h;
@@ -486,8 +501,25 @@ void rt_oracle_ray_color(const RtScene* scene, const double o[3], const double d
   out[0] = col.r; out[1] = col.g; out[2] = col.b;
 }
 
-/* raytracer.rs:197-202: sample s of pixel (x, y) — the camera jitter, get_ray and ray_color — with the RNG addressed by c->sample = s */
-static Rgb trace_sample(Ctx* c, uint32_t x, uint32_t y, uint32_t s) {
+/* the lens point of the sample at (c->pixel, c->sample): attempts a = 0, 1, ... at node NODE_CAMERA, slot 1 + a; of each
+ * attempt the candidate (word 0, word 1), then (word 2, word 3); the first inside the open unit disc */
+static void lens_point(const Ctx* c, double* px, double* py) {
+  for (uint32_t attempt = 0;; ++attempt) {
+    uint32_t w[4]; rng_words(c, NODE_CAMERA, 1u + attempt, w);
+    for (int k = 0; k < 4; k += 2) {
+      double x = range_m1_1(w[k]), y = range_m1_1(w[k + 1]);
+      if (x * x + y * y < 1.0) { *px = x; *py = y; return; }
+    }
+  }
+}
+/* the shutter time of the sample at (c->pixel, c->sample), on the 2^-24 grid of [0, 1) */
+static double shutter_time(const Ctx* c) {
+  uint32_t w[4]; rng_words(c, NODE_TIME, 0, w);
+  return (double)(w[0] >> 8) * (1.0 / 16777216.0);
+}
+/* raytracer.rs:199-201 for sample s of pixel (x, y): the jitter and get_ray, through the thin lens if there is one (DESIGN.md §13:
+ * the scene's camera vectors then span the focus plane; the ray leaves origin + offset towards the same point of that plane) */
+static Ray camera_ray(Ctx* c, uint32_t x, uint32_t y, uint32_t s) {
   const RtScene* sc = c->scene;
   const uint32_t w = sc->width, h = sc->height;
   c->pixel = y * w + x;
@@ -496,6 +528,21 @@ static Rgb trace_sample(Ctx* c, uint32_t x, uint32_t y, uint32_t s) {
   double u = ((double)x + u01_53(jw[0], jw[1])) / ((double)w - 1.0);                 /* :199 */
   double v = ((double)h - ((double)y + u01_53(jw[2], jw[3]))) / ((double)h - 1.0);   /* :200 */
   Ray r = camera_get_ray(sc, u, v);
+  if (c->lens_r != 0.0) {
+    double px, py; lens_point(c, &px, &py);
+    P3 lu = p3(c->lens_u[0], c->lens_u[1], c->lens_u[2]), lv = p3(c->lens_v[0], c->lens_v[1], c->lens_v[2]);
+    P3 offset = p3_add(p3_muls(lu, c->lens_r * px), p3_muls(lv, c->lens_r * py));
+    r.origin = p3_add(r.origin, offset);
+    r.direction = p3_sub(r.direction, offset);
+  }
+  return r;
+}
+
+/* raytracer.rs:197-202: sample s of pixel (x, y) — the camera jitter, get_ray and ray_color — with the RNG addressed by c->sample = s */
+static Rgb trace_sample(Ctx* c, uint32_t x, uint32_t y, uint32_t s) {
+  const RtScene* sc = c->scene;
+  Ray r = camera_ray(c, x, y, s);
+  if (c->dv) c->tau = shutter_time(c);   /* one per sample: every segment below, nested light rays included, is traced at it */
   if (c->rays) {
     const double* q = c->rays + (size_t)c->pixel * 6;
     r.origin = p3(q[0], q[1], q[2]); r.direction = p3(q[3], q[4], q[5]);
@@ -563,10 +610,44 @@ static double now_ms(void) {
  * checker cuts a scanline into blocks of RT_ORACLE_XBLOCK pixels to keep every core busy when only a few rows are
  * asked for (the full-size parity tests compare single 4K rows at spp 1024).  Same pixels, same bits. */
 #define RT_ORACLE_XBLOCK 32u
+/* The extension as the tracer takes it: *dv = a malloc'd n x 3 table of center1 - center — one f64 subtraction per component, a
+ * component that does not move (center1 == center, or both NaN) stored as -0.0, so that c0 + dv * tau gives back c0's own bits — or NULL
+ * for a static scene (ext or center1 NULL, or center1 equal to every centre).  RT_ERR_INVALID, as rt_hip_scene_create_moving and
+ * rt_hip_set_lens refuse them: a difference that is not finite, a Light sphere that moves, a lens radius that is negative or not finite,
+ * a lens without its vectors. */
+static int ext_prepare(const RtScene* scene, const RtOracleExt* ext, double** dv_out) {
+  *dv_out = NULL;
+  if (!ext) return RT_OK;
+  if (!(ext->lens_r >= 0.0) || isinf(ext->lens_r) || (ext->lens_r != 0.0 && (!ext->lens_u || !ext->lens_v))) return RT_ERR_INVALID;
+  if (!ext->center1 || scene->n_spheres == 0) return RT_OK;
+  double* dv = (double*)malloc(sizeof(double) * 3 * (size_t)scene->n_spheres);
+  if (!dv) return RT_ERR_INVALID;
+  int any = 0;
+  for (uint32_t i = 0; i < scene->n_spheres; ++i) {
+    int moves = 0;
+    for (int k = 0; k < 3; ++k) {
+      const double c0 = scene->spheres[i].center[k], c1 = ext->center1[3 * (size_t)i + k];
+      const int same = c1 == c0 || (c1 != c1 && c0 != c0);
+      const double d = same ? -0.0 : c1 - c0;
+      if (!same && !isfinite(d)) { free(dv); return RT_ERR_INVALID; }
+      dv[3 * (size_t)i + k] = d;
+      moves |= !same;
+    }
+    if (moves && scene->spheres[i].kind == RT_MAT_LIGHT) { free(dv); return RT_ERR_INVALID; }
+    any |= moves;
+  }
+  if (!any) { free(dv); dv = NULL; }
+  *dv_out = dv;
+  return RT_OK;
+}
+
 static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8, float* linear,
-                       uint64_t* accum, uint32_t sample_begin, uint32_t sample_count, const double* rays, RtStats* stats, int n_threads) {
+                       uint64_t* accum, uint32_t sample_begin, uint32_t sample_count, const double* rays, const RtOracleExt* ext,
+                       RtStats* stats, int n_threads) {
   if (!scene || scene->abi_version != RT_ABI_VERSION) return RT_ERR_INVALID;
   if (scene->width == 0 || scene->height == 0 || (scene->n_spheres && !scene->spheres)) return RT_ERR_INVALID;
+  double* dv = NULL;
+  if (ext_prepare(scene, ext, &dv) != RT_OK) return RT_ERR_INVALID;
   if (x1 > scene->width) x1 = scene->width;
   if (x0 > x1) x0 = x1;
   uint32_t n_lights = rt_oracle_find_lights(scene->spheres, scene->n_spheres, NULL, 0);
@@ -588,6 +669,8 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
     const uint32_t lr = (uint32_t)(task / xblocks), xb = (uint32_t)(task % xblocks);
     Ctx c; memset(&c, 0, sizeof c);
     c.scene = scene; c.lights = lights; c.n_lights = n_lights; c.rays = rays;
+    c.dv = dv;
+    if (ext) { c.lens_u = ext->lens_u; c.lens_v = ext->lens_v; c.lens_r = ext->lens_r; }
     uint32_t y = rt_tiles_global_row(tiles, lr);
     const uint32_t xa = x0 + xb * RT_ORACLE_XBLOCK, xe = xa + RT_ORACLE_XBLOCK < x1 ? xa + RT_ORACLE_XBLOCK : x1;
     if (accum) accumulate_line(&c, y, xa, xe, sample_begin, sample_count, accum + lr * row_elems);
@@ -596,6 +679,7 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
   }
   double t1 = now_ms();
   free(lights);
+  free(dv);
   if (stats) {
     memset(stats, 0, sizeof *stats);
     stats->samples = (uint64_t)rows * (x1 - x0) * (accum ? sample_count : scene->samples_per_pixel);
@@ -613,21 +697,46 @@ static int render_rows(const RtScene* scene, const RtRowTiles* tiles, uint32_t x
 }
 int rt_oracle_render(const RtScene* scene, const RtRowTiles* tiles, uint8_t* rgb8, float* linear,
                      RtStats* stats, int n_threads) {
-  return render_rows(scene, tiles, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, NULL, stats, n_threads);
+  return render_rows(scene, tiles, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, NULL, NULL, stats, n_threads);
 }
 /* pixels [x0, x1) of the selected rows only; the buffers still hold whole rows (other pixels untouched) */
 int rt_oracle_render_window(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint8_t* rgb8,
                             float* linear, RtStats* stats, int n_threads) {
-  return render_rows(scene, tiles, x0, x1, rgb8, linear, NULL, 0, 0, NULL, stats, n_threads);
+  return render_rows(scene, tiles, x0, x1, rgb8, linear, NULL, 0, 0, NULL, NULL, stats, n_threads);
 }
 /* samples [sample_begin, sample_begin + sample_count) of pixels [x0, x1) of the selected rows ADDED into accum */
 int rt_oracle_accumulate(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
                          uint32_t sample_count, uint64_t* accum, RtStats* stats, int n_threads) {
   if (!accum || (uint64_t)sample_begin + sample_count > 0xFFFFFFFFull) return RT_ERR_INVALID;
-  return render_rows(scene, tiles, x0, x1, NULL, NULL, accum, sample_begin, sample_count, NULL, stats, n_threads);
+  return render_rows(scene, tiles, x0, x1, NULL, NULL, accum, sample_begin, sample_count, NULL, NULL, stats, n_threads);
 }
 /* rt_oracle_render with the camera ray of every sample of pixel p (= y * width + x) taken from rays[6p .. 6p+5] */
 int rt_oracle_render_rays(const RtScene* scene, const double* rays, uint8_t* rgb8, float* linear, RtStats* stats, int n_threads) {
   if (!rays) return RT_ERR_INVALID;
-  return render_rows(scene, NULL, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, rays, stats, n_threads);
+  return render_rows(scene, NULL, 0, scene ? scene->width : 0, rgb8, linear, NULL, 0, 0, rays, NULL, stats, n_threads);
+}
+
+/* ---- the lens and the shutter: the entry points above with an RtOracleExt ---- */
+int rt_oracle_render_window_ext(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, const RtOracleExt* ext,
+                                uint8_t* rgb8, float* linear, RtStats* stats, int n_threads) {
+  return render_rows(scene, tiles, x0, x1, rgb8, linear, NULL, 0, 0, NULL, ext, stats, n_threads);
+}
+int rt_oracle_accumulate_ext(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
+                             uint32_t sample_count, const RtOracleExt* ext, uint64_t* accum, RtStats* stats, int n_threads) {
+  if (!accum || (uint64_t)sample_begin + sample_count > 0xFFFFFFFFull) return RT_ERR_INVALID;
+  return render_rows(scene, tiles, x0, x1, NULL, NULL, accum, sample_begin, sample_count, NULL, ext, stats, n_threads);
+}
+int rt_oracle_camera_ray_ext(const RtScene* scene, const RtOracleExt* ext, uint32_t x, uint32_t y, uint32_t s, double out[7]) {
+  if (!scene || scene->width == 0 || scene->height == 0) return RT_ERR_INVALID;
+  double* dv = NULL;
+  if (ext_prepare(scene, ext, &dv) != RT_OK) return RT_ERR_INVALID;
+  free(dv);
+  Ctx c; memset(&c, 0, sizeof c);
+  c.scene = scene;
+  if (ext) { c.lens_u = ext->lens_u; c.lens_v = ext->lens_v; c.lens_r = ext->lens_r; }
+  Ray r = camera_ray(&c, x, y, s);
+  out[0] = r.origin.x; out[1] = r.origin.y; out[2] = r.origin.z;
+  out[3] = r.direction.x; out[4] = r.direction.y; out[5] = r.direction.z;
+  out[6] = shutter_time(&c);
+  return RT_OK;
 }

@@ -52,6 +52,36 @@ int rt_oracle_accumulate(const RtScene* scene, const RtRowTiles* tiles, uint32_t
 int rt_oracle_render_rays(const RtScene* scene, const double* rays, uint8_t* rgb8, float* linear, RtStats* stats, int n_threads);
 int rt_oracle_threads(void);
 
+/* ---- the extensions of the schema: thin lens and motion blur ----
+ * Restated from the contract (include/rt_abi.h), not from the kernel:
+ *   shutter time   tau = (philox(pixel, s, 0xFFFFFFFD, 0).x >> 8) * 2^-24, one per sample, used by every segment of the sample,
+ *                  nested light rays included;
+ *   moving sphere  dv = center1 - center (one f64 subtraction per component, a zero component stored as -0.0); its centre at tau is
+ *                  c0 + dv * tau (a product and a sum, each rounded); Sphere::hit, the normal (p - c) / r and the texture's (u, v) from
+ *                  p - c use that centre; light rays aim at the static light centres;
+ *   lens           the jitter stays at node 0xFFFFFFFF slot 0; the lens point comes from attempts a = 0, 1, ... of
+ *                  W = philox(pixel, s, 0xFFFFFFFF, 1 + a): candidates (range_m1_1(W.x), range_m1_1(W.y)) then (W.z, W.w), the first with
+ *                  px*px + py*py < 1; offset = u*(r*px) + v*(r*py); the ray starts at origin + offset with direction
+ *                  (((lower_left + horizontal*u_s) + vertical*v_s) - origin) - offset, the scene's camera vectors being
+ *                  rt_camera_derive_lens's (on the focus plane).
+ * Every member is optional.  ext NULL, center1 NULL or equal to every centre, and lens_r 0 give the plain entry points' results bit
+ * for bit, statistics included.  RT_ERR_INVALID (as rt_hip_scene_create_moving / rt_hip_set_lens refuse them): a center1 - center
+ * that is not finite, a Light sphere that moves, a lens_r that is negative or not finite, lens_r != 0 without lens_u and lens_v. */
+typedef struct RtOracleExt {
+  const double* center1; /* n_spheres x 3: the centres at shutter close; NULL = static */
+  const double* lens_u;  /* rt_hip_set_lens's arguments: the camera's unit vectors u and v ... */
+  const double* lens_v;
+  double lens_r;         /* ... and the lens radius aperture / 2; 0 = the pinhole */
+} RtOracleExt;
+/* rt_oracle_render_window / rt_oracle_accumulate through the extension */
+int rt_oracle_render_window_ext(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, const RtOracleExt* ext,
+                                uint8_t* rgb8, float* linear, RtStats* stats, int n_threads);
+int rt_oracle_accumulate_ext(const RtScene* scene, const RtRowTiles* tiles, uint32_t x0, uint32_t x1, uint32_t sample_begin,
+                             uint32_t sample_count, const RtOracleExt* ext, uint64_t* accum, RtStats* stats, int n_threads);
+/* hook: the camera ray and the shutter time of sample s of pixel (x, y): out = origin[3], direction[3], tau (tau is the contract's
+ * draw whether or not a sphere moves) */
+int rt_oracle_camera_ray_ext(const RtScene* scene, const RtOracleExt* ext, uint32_t x, uint32_t y, uint32_t s, double out[7]);
+
 /* ---- hooks for the reference's known-answer tests ---- */
 /* Philox4x32-10, Random123 layout */
 void rt_oracle_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
