@@ -54,7 +54,11 @@ enum {
   RT_MAT_METAL = 1,
   RT_MAT_GLASS = 2,
   RT_MAT_TEXTURE = 3,
-  RT_MAT_LIGHT = 4
+  RT_MAT_LIGHT = 4,
+  /* Participating medium (an extension of the schema; NOT a variant of the reference's enum, whose loader rejects it):
+   * a sphere of constant-density fog or smoke.  RtSphere.albedo is its albedo, RtSphere.fuzz_or_ior its density (finite, > 0); the radius
+   * must be finite and > 0. */
+  RT_MAT_MEDIUM = 5
 };
 
 /* config.rs:22-28, 49-64: sky null -> black; {"texture":""} -> gradient; path -> texture */
@@ -66,11 +70,11 @@ enum { RT_SKY_NONE = 0, RT_SKY_GRADIENT = 1, RT_SKY_TEXTURE = 2 };
 typedef struct RtSphere {
   double center[3];
   double radius;      /* may be negative: hollow glass, test_scene.json:137 */
-  double fuzz_or_ior; /* Metal.fuzz | Glass.index_of_refraction             */
+  double fuzz_or_ior; /* Metal.fuzz | Glass.index_of_refraction | Medium.density */
   double h_offset;    /* Texture.h_offset                                   */
   uint64_t tex_w;     /* Texture.width / height AS WRITTEN IN THE JSON      */
   uint64_t tex_h;     /*   (materials.rs:206-210), not the decoded size     */
-  float albedo[3];    /* Lambertian/Metal albedo; ignored for Texture       */
+  float albedo[3];    /* Lambertian/Metal/Medium albedo; ignored for Texture */
   uint32_t kind;      /* RT_MAT_*                                           */
   uint32_t tex_id;    /* index into RtScene.textures when kind==TEXTURE     */
   uint32_t reserved;
@@ -261,6 +265,22 @@ int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene** out);
  * center1 NULL, or equal to every centre: the static scene of rt_hip_scene_create.  RT_ERR_INVALID for a non-finite center1 - center
  * or a moving Light sphere.  rt_hip_scene_query "motion" = the number of moving spheres. */
 int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int device, RtHipScene** out);
+/* Participating media: a sphere of kind RT_MAT_MEDIUM scatters a ray at a random depth INSIDE the ball instead of on its
+ * surface.  The contract, IEEE f64 without contraction, for the segment with RNG node `node`, origin o, direction d and medium sphere i
+ * (centre at the sample's shutter time, like any sphere):
+ *   a, half_b, disc, sq as Sphere::hit forms them (sphere.rs:47-55); t1 = ((-half_b) - sq) / a, t2 = ((-half_b) + sq) / a;
+ *   disc < 0: no candidate.  t_in = t1 > 0.001 ? t1 : 0.001; !(t_in < t2): no candidate.
+ *   len = sqrt(a), inside = (t2 - t_in) * len.
+ *   W = philox(pixel, sample, node, 0x80000000 | i), u = u01_53(W.x, W.y): ONE draw per (node, sphere) — the candidate is the same
+ *   however often and in whatever order the sphere is tested, and overlapping media draw independently (their densities add).
+ *   E = rt_neg_log(1.0 - u) (csrc/common/rt_neg_log.h: its bits are part of the contract), dist = E / density;
+ *   !(dist <= inside): no candidate.  t = t_in + dist / len.
+ * The candidate enters the closest-hit rule like a surface root: t > 0.001, and t < closest, or t == closest and i < best.
+ * Scatter: direction = random_in_unit_sphere(node) (slots 1 + attempt, not normalised), or the incoming d if that is near_zero;
+ * attenuation = albedo; no normal.  For the light-sampling draw a medium counts as not Glass.  Denoising AOVs of a first hit in a medium:
+ * its albedo, normal (0, 0, 0), the usual 1 / t.
+ * rt_hip_scene_create* returns RT_ERR_INVALID for a medium whose radius or density is not finite and > 0, and RT_ERR_UNSUPPORTED for a
+ * medium in a scene of more than 65 535 spheres (wide tables have no MEDIUM kernels).  rt_hip_scene_query "media" = their number. */
 void rt_hip_scene_destroy(RtHipScene*);
 /* Launch the megakernel for the given row tiles on `stream` (a hipStream_t, NULL = default).
  *   d_rgb8    device buffer, rt_tiles_local_rows()*width*3 bytes, packed, top row first;
@@ -293,8 +313,9 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
  * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
  * "last_kernel" (the megakernel instantiation that ran: accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 |
- * tables in LDS 1; thin lens 32; moving spheres 64; -1 before the scene's first launch), "lens" (1: rt_hip_set_lens set a lens, 0: the
- * pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene).
+ * tables in LDS 1; thin lens 32; moving spheres 64; participating media 128; -1 before the scene's first launch), "lens" (1:
+ * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
+ * (spheres of kind RT_MAT_MEDIUM).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the

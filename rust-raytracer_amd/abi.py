@@ -5,7 +5,7 @@ RT_ABI_VERSION = 5
 RT_MAX_LIGHT_NEST = 8
 RT_OK, RT_ERR_INVALID, RT_ERR_NO_DEVICE, RT_ERR_HIP = 0, -1, -2, -3
 RT_ERR_IO, RT_ERR_PARSE, RT_ERR_TEXTURE, RT_ERR_PNG, RT_ERR_UNSUPPORTED = -4, -5, -6, -7, -8
-RT_MAT_LAMBERTIAN, RT_MAT_METAL, RT_MAT_GLASS, RT_MAT_TEXTURE, RT_MAT_LIGHT = range(5)
+RT_MAT_LAMBERTIAN, RT_MAT_METAL, RT_MAT_GLASS, RT_MAT_TEXTURE, RT_MAT_LIGHT, RT_MAT_MEDIUM = range(6)
 RT_SKY_NONE, RT_SKY_GRADIENT, RT_SKY_TEXTURE = range(3)
 
 

@@ -58,7 +58,9 @@ def build_hip(force=False):
     # with all 96 instantiations was twice that.  Objects under build/ (git-ignored), then one link per library.
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    units = [("csrc/hip/rt_hip_api.hip", ["-DRT_MOTION_TU_SPLIT"]), ("csrc/hip/rt_kernel_motion.hip", [])]
+    # (... and the 64 MEDIUM instantiations, DESIGN.md §15, in two more units of 32 each)
+    units = [("csrc/hip/rt_hip_api.hip", ["-DRT_MOTION_TU_SPLIT"]), ("csrc/hip/rt_kernel_motion.hip", []),
+             ("csrc/hip/rt_kernel_medium.hip", []), ("csrc/hip/rt_kernel_medium_motion.hip", [])]
     compiles, links = [], []
     for lib, extra in ((out, []), (probe, ["-DRT_TEST_PROBES"])):
         if not (force or _newer(lib, deps)):
@@ -91,7 +93,7 @@ def build_cli(force=False):
 
 
 HIP_DEPS = ("csrc/hip/rt_hip_api.hip", "csrc/hip/rt_kernel.hip", "csrc/hip/rt_kernel_motion.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h",
-            "csrc/common/rt_atan2.h")
+            "csrc/common/rt_atan2.h", "csrc/hip/rt_kernel_medium.hip", "csrc/hip/rt_kernel_medium_motion.hip", "csrc/common/rt_neg_log.h")
 
 
 def kernel_src_hash():

@@ -24,6 +24,10 @@
 #define RT_ATAN2_FN __host__ __device__ inline
 #endif
 #include "../common/rt_atan2.h"  // the one atan2 kernel and CPU checker share (sphere.rs:39)
+#if defined(__HIPCC__)
+#define RT_NEG_LOG_FN __host__ __device__ inline
+#endif
+#include "../common/rt_neg_log.h"  // the one -ln(x) of a medium's free-flight distance
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__ __forceinline__
@@ -189,6 +193,9 @@ struct DevScene {
   // motion blur (rt_hip_scene_create_moving): [n_spheres][4] {dv = center1 - center, 0} (a zero component stored as -0.0);
   // null for a static scene.  Read only by the MOTION instantiations of the megakernel and by rt_aov_motion / rt_aov_lens_motion.
   const double* motion;
+  // participating media: [n_spheres] the density of a Medium sphere, 0.0 for any other; null for a scene without one.
+  // Resident once and shared by views like `motion`.  Read only by the MEDIUM instantiations of the megakernel and the rt_aov*_medium kernels.
+  const double* medium;
 };
 
 // ------------------------------------------------------------------ f64 square root
@@ -572,6 +579,52 @@ RT_HD bool exact_hit_any_order(V3 o, V3 d, const RayK& rk, const SphereGeom& g, 
   return hit;
 }
 
+// ------------------------------------------------------------------ participating media
+// The candidate of medium sphere idx for the segment (ra, node, o, d) — the contract of include/rt_abi.h, IEEE f64, the operations
+// in the order written — and the closest-hit rule applied to it.  A function of (ray, sphere, draw) alone: the draw is addressed by
+// (node, sphere), so the candidate is the same however often and in whatever order the walk tests the sphere, and the order-free rule
+// above still reaches one answer.  COLD and by value (see exact_hit_slow): the Philox stream, the logarithm and the three divisions
+// stay out of the walk loop's register budget; only lanes whose sphere IS a medium call it.
+constexpr uint32_t MEDIUM_SLOT = 0x80000000u;  // slot of the free-flight draw of sphere i: MEDIUM_SLOT | i (attempt slots 1 + a never reach bit 31)
+RT_HD_COLD HitCB medium_hit(V3 o, V3 d, double a, SphereGeom g, double density, uint32_t idx, RngAddr ra, uint32_t node, double closest, int best) {
+  HitCB r; r.closest = closest; r.best = best;
+  const V3 oc = sub(o, v3(g.cx, g.cy, g.cz));
+  const double half_b = dot(oc, d);
+  const double c = length_squared(oc) - g.r * g.r;
+  const double disc = (half_b * half_b) - (a * c);
+  if (!(disc >= 0.0)) return r;
+  const double sq = rt_sqrt(disc);
+  const double t1 = ((-half_b) - sq) / a, t2 = ((-half_b) + sq) / a;
+  const double t_in = t1 > T_MIN ? t1 : T_MIN;
+  if (!(t_in < t2)) return r;
+  const double len = rt_sqrt(a);
+  const double inside = (t2 - t_in) * len;
+  const U4 w = rng(ra, node, MEDIUM_SLOT | idx);
+  const double u = u01_53(w.x, w.y);
+  const double dist = rt_neg_log(1.0 - u) / density;
+  if (!(dist <= inside)) return r;
+  const double t = t_in + dist / len;
+  const bool tie_ok = best >= 0 && idx < (uint32_t)best;
+  if (t > T_MIN && (t < closest || (tie_ok && t == closest))) { r.closest = t; r.best = (int)idx; }
+  return r;
+}
+// What hit_world needs to test media: the density table and the segment's RNG address.  Null = a scene without media.
+struct MediumCtx {
+  const double* density;
+  RngAddr ra;
+  uint32_t node;
+};
+template <class Tables>
+RT_HD void exact_or_medium_hit(const MediumCtx* mc, V3 o, V3 d, const RayK& rk, const Tables& tb, uint32_t idx, double& closest, int& best) {
+  const double den = mc->density[idx];
+  if (den != 0.0) {
+    const HitCB r = medium_hit(o, d, rk.a, tb.geom(idx), den, idx, mc->ra, mc->node, closest, best);
+    closest = r.closest; best = r.best;
+    return;
+  }
+  exact_hit_any_order(o, d, rk, tb.geom(idx), idx, closest, best);
+}
+
 // ------------------------------------------------------------------ grid walk (hit_world, raytracer.rs:44-59)
 // Incremental 3D-DDA over GridDesc in f32 cell units.  It only decides WHICH spheres get the
 // exact f64 test; it can visit too many cells but never too few (DESIGN.md "Grid walk").
@@ -692,22 +745,29 @@ RT_HD bool grid_done(const GridWalk& w, double closest) {
 
 // hit_world through the grid for ONE ray — the per-lane reference form of what the megakernel
 // does with 64 lanes in lock-step (rt_kernel.hip); tests/hostsim runs this one on the CPU.
-template <class Tables>
+// MEDIUM: `mc` says which spheres are media and carries the segment's RNG address; a compile-time arm.
+template <bool MEDIUM = false, class Tables>
 RT_HD void hit_world_grid(const DevScene& sc, const Tables& tb, V3 o, V3 d, double& closest, int& best,
-                          uint32_t& n_exact, uint32_t& n_steps) {
+                          uint32_t& n_exact, uint32_t& n_steps, const MediumCtx* mc = nullptr) {
+  (void)mc;
   const GridDesc& G = sc.grid;
   const RayK a = ray_consts(d);
   for (uint32_t i = 0; i < G.n_large; ++i) {
     const uint32_t idx = sc.large[i];
     n_exact++;
-    exact_hit_any_order(o, d, a, tb.geom(idx), idx, closest, best);
+    if constexpr (MEDIUM) exact_or_medium_hit(mc, o, d, a, tb, idx, closest, best);
+    else exact_hit_any_order(o, d, a, tb.geom(idx), idx, closest, best);
   }
   if (G.n[0] == 0u) return;
   GridWalk w;
   const int mode = grid_begin(G, o, d, w);
   if (mode == GRID_MISS) return;
   if (mode == GRID_FALLBACK) {
-    for (uint32_t idx = 0; idx < sc.n_spheres; ++idx) { n_exact++; exact_hit_any_order(o, d, a, tb.geom(idx), idx, closest, best); }
+    if constexpr (MEDIUM) {
+      for (uint32_t idx = 0; idx < sc.n_spheres; ++idx) { n_exact++; exact_or_medium_hit(mc, o, d, a, tb, idx, closest, best); }
+    } else {
+      for (uint32_t idx = 0; idx < sc.n_spheres; ++idx) { n_exact++; exact_hit_any_order(o, d, a, tb.geom(idx), idx, closest, best); }
+    }
     return;
   }
   uint32_t last = 0xFFFFFFFFu;
@@ -721,7 +781,8 @@ RT_HD void hit_world_grid(const DevScene& sc, const Tables& tb, V3 o, V3 d, doub
       if (idx == last) continue;  // the sphere tested last (large spheres span consecutive cells)
       last = idx;
       n_exact++;
-      exact_hit_any_order(o, d, a, tb.geom(idx), idx, closest, best);
+      if constexpr (MEDIUM) exact_or_medium_hit(mc, o, d, a, tb, idx, closest, best);
+      else exact_hit_any_order(o, d, a, tb.geom(idx), idx, closest, best);
     }
     if (best >= 0 && grid_done(w, closest)) return;
     n_steps++;
@@ -1076,14 +1137,24 @@ RT_HD bool material_draws_unit_sphere(uint32_t kind) {
 }
 // rnd_pre / glass_u_pre: the random_in_unit_sphere(ra, node) point and the Glass reflectance draw
 // (slot 0, .x.y) if the caller already drew them, or null
+// MEDIUM: a hit inside a participating medium scatters isotropically — the new direction is the unit-sphere point itself
+// (not normalised, as the reference's diffuse draws are), the incoming direction if that is near_zero; attenuation = albedo; no normal.
+// A compile-time arm: without it the function is the code it was.
+template <bool MEDIUM = false>
 RT_HD int scatter(const DevScene& sc, const RngAddr& ra, uint32_t node, V3 in_dir, const Surface& h,
                   const SphereGeom& g, const MatCore& m, uint32_t idx, V3& out_dir, float att[3], uint32_t& tex_oob,
                   const V3* rnd_pre = nullptr, const double* glass_u_pre = nullptr) {
   // Lambertian, Texture and Metal all draw random_in_unit_sphere (Metal even with fuzz = 0,
   // materials.rs:120); one shared rejection loop instead of one per material branch.
   V3 rnd = v3(0.0, 0.0, 0.0);
-  if (material_draws_unit_sphere(m.kind)) rnd = rnd_pre ? *rnd_pre : random_in_unit_sphere(ra, node);
+  if (material_draws_unit_sphere(m.kind) || (MEDIUM && m.kind == RT_MAT_MEDIUM)) rnd = rnd_pre ? *rnd_pre : random_in_unit_sphere(ra, node);
   att[0] = m.albedo[0]; att[1] = m.albedo[1]; att[2] = m.albedo[2];
+  if constexpr (MEDIUM) {
+    if (m.kind == RT_MAT_MEDIUM) {
+      out_dir = near_zero(rnd) ? in_dir : rnd;
+      return SCATTER_RAY;
+    }
+  }
   switch (m.kind) {
     case RT_MAT_LIGHT:  // :65-69
       att[0] = att[1] = att[2] = 1.0f;
@@ -1678,7 +1749,7 @@ struct ShadeProf { unsigned long long* t; unsigned long long* last; uint32_t* n_
 #define RT_SHADE_MARK(k) do { } while (0)
 #define RT_SHADE_COUNT(act_) do { } while (0)
 #endif
-template <class LaneT, class Tables>
+template <bool MEDIUM = false, class LaneT, class Tables>
 RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, double t, const V3* rnd_pre = nullptr,
                       const double* glass_u_pre = nullptr, const double* light_u_pre = nullptr, ShadeProf* sp = nullptr) {
   (void)sp;
@@ -1695,7 +1766,7 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
     Surface h = surface_at(L.o, L.d, t, g, m.inv_r);
     V3 out_dir = v3(0, 0, 0);
     float att[3];
-    int st = scatter(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
+    int st = scatter<MEDIUM>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
     if (st == SCATTER_ABSORBED) { lane_finish_sample(sc, L, rgb(0.f, 0.f, 0.f)); return LANE_FINISHED; }       // :127-131
     if (st == SCATTER_EMIT) { lane_finish_sample(sc, L, rgb(att[0], att[1], att[2])); return LANE_FINISHED; }  // :124
     return lane_continue_main(sc, L, h.point, out_dir, zero3, att) ? LANE_FINISHED : LANE_CONTINUE;
@@ -1717,7 +1788,7 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
       const MatCore m = tb.mat((uint32_t)idx);
       Surface h = surface_at(L.o, L.d, t, g, m.inv_r);
       point = h.point;
-      const int st = scatter(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
+      const int st = scatter<MEDIUM>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
       if (st != SCATTER_RAY) {  // :124 Light: its colour; :127-131 absorbed: black
         if (st == SCATTER_EMIT) col = rgb(att[0], att[1], att[2]);
         act = light_ray ? ACT_RETURN : ACT_FINISH;
@@ -1812,9 +1883,10 @@ RT_HD uint8_t linear_to_u8(float lin) { return f32_to_u8(__builtin_sqrtf(lin)); 
 // address, lane_begin_sample_w).  Summed in f64 in sample order, divided by n, rounded once to f32.
 constexpr uint32_t AOV_FLOATS = 8u;
 // MOTION: the first hit at the sample's shutter time (sample_time), through the same MotionTables as the MOTION megakernels.
-template <class Tables>
+// MEDIUM: a first hit inside a medium reports the medium's albedo, normal (0, 0, 0) and the usual 1 / t.
+template <bool MEDIUM = false, class Tables>
 RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]);
-template <bool LENS, bool MOTION = false, class Tables>
+template <bool LENS, bool MOTION = false, bool MEDIUM = false, class Tables>
 RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py, uint32_t n, float out[8]) {
   double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Lane<false> L;
@@ -1822,18 +1894,21 @@ RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t
   for (uint32_t s = 0; s < n; ++s) {
     L.s = s;
     lane_begin_sample<LENS>(sc, L, px, py);
-    if constexpr (MOTION) aov_sample(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
-    else aov_sample(sc, tb, L, acc);
+    if constexpr (MOTION) aov_sample<MEDIUM>(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
+    else aov_sample<MEDIUM>(sc, tb, L, acc);
   }
   for (int i = 0; i < 8; ++i) out[i] = (float)(acc[i] / (double)n);
 }
-template <class Tables>
+template <bool MEDIUM, class Tables>
 RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]) {
   {
     double closest = T_MAX;
     int best = -1;
     uint32_t n_exact = 0, n_steps = 0, tex_oob = 0;
-    hit_world_grid(sc, tb, L.o, L.d, closest, best, n_exact, n_steps);
+    if constexpr (MEDIUM) {
+      const MediumCtx mc{sc.medium, L.ra, L.node};  // (the camera segment: node 0)
+      hit_world_grid<true>(sc, tb, L.o, L.d, closest, best, n_exact, n_steps, &mc);
+    } else hit_world_grid(sc, tb, L.o, L.d, closest, best, n_exact, n_steps);
     float a[3];
     if (best < 0) {  // raytracer.rs:133-163: the sky the ray sees
       const Rgb c = sky_color(sc, L.d, tex_oob);
@@ -1848,9 +1923,9 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
         const UV uv = sphere_uv_for_texel(h.point, g, sc.mat, (uint32_t)best);
         const Rgb c = texture_albedo(sc, sc.mat[best], uv.u, uv.v, tex_oob);
         a[0] = c.r; a[1] = c.g; a[2] = c.b;
-      } else if (m.kind != RT_MAT_LAMBERTIAN && m.kind != RT_MAT_METAL) a[0] = a[1] = a[2] = 0.0f;
+      } else if (m.kind != RT_MAT_LAMBERTIAN && m.kind != RT_MAT_METAL && !(MEDIUM && m.kind == RT_MAT_MEDIUM)) a[0] = a[1] = a[2] = 0.0f;
       acc[3] += 1.0 / closest;
-      acc[4] += h.normal.x; acc[5] += h.normal.y; acc[6] += h.normal.z;
+      if (!(MEDIUM && m.kind == RT_MAT_MEDIUM)) { acc[4] += h.normal.x; acc[5] += h.normal.y; acc[6] += h.normal.z; }
       acc[7] += 1.0;
     }
     acc[0] += (double)a[0]; acc[1] += (double)a[1]; acc[2] += (double)a[2];

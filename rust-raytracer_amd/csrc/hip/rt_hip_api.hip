@@ -119,6 +119,8 @@ struct RtHipScene {
     DevBuf all;              // 0..n-1: the `large` list of the brute-force arm (variant 1)
     DevBuf motion;           // motion blur: [n][4] dv per sphere (rt_tables.h HostTables::motion); unallocated when static
     uint32_t n_moving = 0;
+    DevBuf medium;           // participating media: [n] density per sphere, 0 = no medium (HostTables::medium); unallocated without media
+    uint32_t n_media = 0;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -338,6 +340,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   rtc::HostTables t;
   std::string why = rtc::build_tables(*scene, t, false, center1);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
+  if (t.n_media && t.grid.wide) return fail(RT_ERR_UNSUPPORTED, "participating media in a scene with wide tables (more than 65 535 spheres)");
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
   pc.mark("scene.texels_rgbx");
@@ -368,6 +371,8 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   if ((rc = upload(r->large_geom, t.large_geom)) != RT_OK) return rc;
   if (t.n_moving && (rc = upload(r->motion, t.motion)) != RT_OK) return rc;
   r->n_moving = t.n_moving;
+  if (t.n_media && (rc = upload(r->medium, t.medium)) != RT_OK) return rc;
+  r->n_media = t.n_media;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
@@ -407,6 +412,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   s->dev.cell_items = r->cell_items.get<const uint16_t>(); s->dev.large = r->large.get<const uint32_t>();
   s->dev.large_geom = r->large_geom.get<const rtc::SphereGeom>();
   s->dev.motion = r->n_moving ? r->motion.get<const double>() : nullptr;
+  s->dev.medium = r->n_media ? r->medium.get<const double>() : nullptr;
   s->res = std::move(r);
   auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
@@ -455,10 +461,16 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
 #ifdef RT_MOTION_TU_SPLIT  // (the product build: rt_kernel_motion.hip compiles the MOTION half of the kernel set beside this file)
 #define RT_MOTION_EXTERN(HL, S, LDS, WIDE, A, LE) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, WIDE, A, LE, true>(rtk::KArgs);
 RT_MOTION_INSTANTIATIONS(RT_MOTION_EXTERN)
+// (... and rt_kernel_medium.hip / rt_kernel_medium_motion.hip the MEDIUM set)
+#define RT_MEDIUM_EXTERN(HL, S, LDS, A, LE, MO) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, false, A, LE, MO, true>(rtk::KArgs);
+RT_MEDIUM_INSTANTIATIONS(RT_MEDIUM_EXTERN, false)
+RT_MEDIUM_INSTANTIATIONS(RT_MEDIUM_EXTERN, true)
 #endif
 
 namespace {
 
+// The MEDIUM instantiations have the key of their static twin | 128 and a table of their own behind the first one:
+// the first 128 entries are made exactly as they were.
 // The megakernel instantiations and their keys: MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1 (lights, every
 // albedo in [0, 1], tables in LDS, wide cell tables, accumulating, thin lens, moving spheres).  Wide tables are never staged in LDS
 // (plan_lds): those 32 keys have no instantiation.
@@ -475,12 +487,27 @@ template <int... J> std::array<Megakernel, 128> megakernels(std::integer_sequenc
   ((t[key_at<J>] = megakernel_of_key<key_at<J>>()), ...);
   return t;
 }
+template <int K> Megakernel medium_megakernel_of_key() {  // K = the key without the MEDIUM bit; wide tables have no MEDIUM kernel
+  if constexpr ((K & 8) != 0) return nullptr;
+  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, false, (K & 16) != 0, (K & 32) != 0, (K & 64) != 0, true>;
+}
+template <int... K> std::array<Megakernel, 128> medium_megakernels(std::integer_sequence<int, K...>) {
+  std::array<Megakernel, 128> t{};
+  ((t[K] = medium_megakernel_of_key<K>()), ...);
+  return t;
+}
 struct Kernel { int key = -1; Megakernel fn = nullptr; };
 int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
   static const std::array<Megakernel, 128> table = megakernels(std::make_integer_sequence<int, 128>());
   if (wide && lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
   out->key = (s->dev.motion ? 64 : 0) | (s->dev.lens_r != 0.0 ? 32 : 0) | (accum ? 16 : 0) | (wide ? 8 : 0) | (has_lights ? 4 : 0) | (s->res->simple_colour ? 2 : 0) | (lds_tables ? 1 : 0);
   out->fn = table[out->key];
+  if (s->dev.medium) {
+    static const std::array<Megakernel, 128> medium_table = medium_megakernels(std::make_integer_sequence<int, 128>());
+    if (wide) return fail(RT_ERR_UNSUPPORTED, "participating media with wide tables");
+    out->fn = medium_table[out->key];
+    out->key |= 128;
+  }
   return RT_OK;
 }
 
@@ -1022,7 +1049,8 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
   if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
   if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
@@ -1212,7 +1240,11 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
   RT_HIP_TRY(hipSetDevice(s->device));
   const bool lens = s->dev.lens_r != 0.0;
-  if (s->dev.motion) hipLaunchKernelGGL(lens ? rtk::rt_aov_lens_motion : rtk::rt_aov_motion, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  if (s->dev.medium) {
+    auto k = s->dev.motion ? (lens ? rtk::rt_aov_lens_motion_medium : rtk::rt_aov_motion_medium) : (lens ? rtk::rt_aov_lens_medium : rtk::rt_aov_medium);
+    hipLaunchKernelGGL(k, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  }
+  else if (s->dev.motion) hipLaunchKernelGGL(lens ? rtk::rt_aov_lens_motion : rtk::rt_aov_motion, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   else if (lens) hipLaunchKernelGGL(rtk::rt_aov_lens, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   else hipLaunchKernelGGL(rtk::rt_aov, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   RT_HIP_TRY(hipGetLastError());

@@ -330,9 +330,14 @@ struct LdsTables {  // per-lane gathers from the workgroup's LDS copies
 // MOTION: motion blur: each new sample draws its shutter time tau (rt_core.h sample_time), kept in one register for
 // the whole sample, and every read of a sphere's geometry — the `large` list, the full scan, the walk, the shading — is the sphere
 // at tau (rt_core.h geom_at / MotionTables, dv from HBM / L2).  A compile-time arm: the static instantiations stay the code they were.
-template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false, bool MOTION = false>
+// MEDIUM: participating media: wherever a sphere gets its exact test — the `large` list, the full scan, the walk — the
+// sphere's density (DevScene::medium, HBM / L2) says whether it is a medium; if so the lane calls the cold rt_core.h medium_hit (one
+// Philox draw addressed by (node, sphere), rt_neg_log, the contract's divisions) instead of Sphere::hit.  The shading takes the
+// medium arm of scatter.  A compile-time arm: the other instantiations stay the code they were.
+template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false, bool MOTION = false, bool MEDIUM = false>
 __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs ka) {
   static_assert(!(LDS_TABLES && WIDE), "wide tables (more than 65 535 spheres) never fit LDS");
+  static_assert(!(MEDIUM && WIDE), "media with wide tables are refused at scene creation (RT_ERR_UNSUPPORTED)");
   const DevScene& sc = ka.sc;
   const GridDesc& G = sc.grid;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -775,7 +780,19 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
         const F64PtrK np = lg + (size_t)nx * 4u;
         SphereGeom gn; gn.cx = np[0]; gn.cy = np[1]; gn.cz = np[2]; gn.r = np[3];
         const uint32_t idxn = large_k[nx];
-        if constexpr (MOTION) {  // (the record and its dv are scalar; the centre at the lane's tau is per lane)
+        if constexpr (MEDIUM) {  // (the record, its dv and its density are scalar: a wave-uniform choice between the two tests)
+          SphereGeom gt = g;
+          if constexpr (MOTION) {
+            const F64PtrK mv = (F64PtrK)(uintptr_t)sc.motion + (size_t)idx * 4u;
+            const double mx = mv[0], my = mv[1], mz = mv[2];
+            gt = geom_at(g, mx, my, mz, (double)tau);
+          }
+          const double den = ((F64PtrK)(uintptr_t)sc.medium)[idx];
+          if (has_ray && rk.fast) {
+            if (den != 0.0) { const HitCB r = medium_hit(L.o, L.d, rk.a, gt, den, idx, L.ra, L.node, closest, best); closest = r.closest; best = r.best; }
+            else exact_hit_any_order_t<true>(L.o, L.d, rk, gt, idx, closest, best);
+          }
+        } else if constexpr (MOTION) {  // (the record and its dv are scalar; the centre at the lane's tau is per lane)
           const F64PtrK mv = (F64PtrK)(uintptr_t)sc.motion + (size_t)idx * 4u;
           const double mx = mv[0], my = mv[1], mz = mv[2];
           if (has_ray && rk.fast) exact_hit_any_order_t<true>(L.o, L.d, rk, geom_at(g, mx, my, mz, (double)tau), idx, closest, best);
@@ -799,7 +816,15 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
           const double mx = mv[0], my = mv[1], mz = mv[2];
           if (mode == GRID_FALLBACK) g = geom_at(g, mx, my, mz, (double)tau);
         }
-        if (mode == GRID_FALLBACK) { const HitCB r = exact_hit_slow(L.o, L.d, rk.a, g, idx, closest, best); closest = r.closest; best = r.best; }
+        if constexpr (MEDIUM) {
+          const double den = ((F64PtrK)(uintptr_t)sc.medium)[idx];
+          if (mode == GRID_FALLBACK) {
+            const HitCB r = den != 0.0 ? medium_hit(L.o, L.d, rk.a, g, den, idx, L.ra, L.node, closest, best) : exact_hit_slow(L.o, L.d, rk.a, g, idx, closest, best);
+            closest = r.closest; best = r.best;
+          }
+        } else {
+          if (mode == GRID_FALLBACK) { const HitCB r = exact_hit_slow(L.o, L.d, rk.a, g, idx, closest, best); closest = r.closest; best = r.best; }
+        }
       }
       if (mode == GRID_FALLBACK) n_exact += sc.n_spheres;
     }
@@ -912,8 +937,18 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
             it++;
             if (idx != last) {  // a sphere spanning consecutive cells is not re-tested
               last = idx; n_exact++;
-              if constexpr (MOTION) exact_hit_any_order_t<true>(L.o, L.d, rk, motion_tables(tb, sc.motion, tau).geom(idx), idx, closest, best);
-              else exact_hit_any_order_t<true>(L.o, L.d, rk, tb.geom(idx), idx, closest, best);
+              if constexpr (MEDIUM) {
+                SphereGeom gt;
+                if constexpr (MOTION) gt = motion_tables(tb, sc.motion, tau).geom(idx);
+                else gt = tb.geom(idx);
+                const double den = sc.medium[idx];
+                if (den != 0.0) { const HitCB r = medium_hit(L.o, L.d, rk.a, gt, den, idx, L.ra, L.node, closest, best); closest = r.closest; best = r.best; }
+                else exact_hit_any_order_t<true>(L.o, L.d, rk, gt, idx, closest, best);
+              } else if constexpr (MOTION) {
+                exact_hit_any_order_t<true>(L.o, L.d, rk, motion_tables(tb, sc.motion, tau).geom(idx), idx, closest, best);
+              } else {
+                exact_hit_any_order_t<true>(L.o, L.d, rk, tb.geom(idx), idx, closest, best);
+              }
             }
           }
         }
@@ -965,7 +1000,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     const uint32_t hit_kind = has_ray && best >= 0 ? tb.mat((uint32_t)best).kind : 0xFFFFFFFFu;
     double glass_u, light_u;
     U4 cam_w;
-    const V3 rnd = coop_random_in_unit_sphere(hit_kind != 0xFFFFFFFFu && material_draws_unit_sphere(hit_kind), hit_kind == RT_MAT_GLASS, fresh,
+    const V3 rnd = coop_random_in_unit_sphere(hit_kind != 0xFFFFFFFFu && (material_draws_unit_sphere(hit_kind) || (MEDIUM && hit_kind == RT_MAT_MEDIUM)), hit_kind == RT_MAT_GLASS, fresh,
                                               L.ra, L.node, lane, coop_xch, glass_u, light_u, cam_w);
 #ifdef RT_PROF_SPLIT  // (experiment builds: the random draws are booked under "item", lane_shade proper stays under "lane_shade")
     RT_PROF(5);
@@ -990,11 +1025,11 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     if (has_ray) {
 #ifdef RT_PROF_LIT
       rtc::ShadeProf shade_prof{prof_t, &prof_last, &cnt_w_step, &cnt_w_test};
-      if constexpr (MOTION) status = lane_shade(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
-      else status = lane_shade(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      if constexpr (MOTION) status = lane_shade<MEDIUM>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      else status = lane_shade<MEDIUM>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
 #else
-      if constexpr (MOTION) status = lane_shade(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
-      else status = lane_shade(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      if constexpr (MOTION) status = lane_shade<MEDIUM>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      else status = lane_shade<MEDIUM>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
 #endif
       if constexpr (HL) { if (status == LANE_REPEAT) L.n_tex_oob = 0u; }  // (the hit is shaded again next iteration: its out-of-range texel counts THEN, once — RtStats.tex_oob equals the oracle's)
       flush_oob();
@@ -1090,6 +1125,16 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
                                   RT_MOTION_TABLES(X, HL, S, false, true) RT_MOTION_TABLES(X, HL, S, true, true)
 #define RT_MOTION_INSTANTIATIONS(X) RT_MOTION_MODES(X, false, false) RT_MOTION_MODES(X, false, true) RT_MOTION_MODES(X, true, false) \
                                     RT_MOTION_MODES(X, true, true)
+
+// The 64 MEDIUM instantiations, as X(HL, SIMPLE, LDS_TABLES, ACCUM, LENS, MOTION): what a scene with a medium can select —
+// lit and unlit, both colour maps, LDS and L2 tables, accumulating, lens, motion; never wide tables.  Translation units of their own
+// (rt_kernel_medium.hip: the static half; rt_kernel_medium_motion.hip: the moving half), declared `extern template` in rt_hip_api.hip
+// under -DRT_MOTION_TU_SPLIT like the MOTION set.
+#define RT_MEDIUM_TABLES(X, HL, S, A, LE, MO) X(HL, S, false, A, LE, MO) X(HL, S, true, A, LE, MO)
+#define RT_MEDIUM_MODES(X, HL, S, MO) RT_MEDIUM_TABLES(X, HL, S, false, false, MO) RT_MEDIUM_TABLES(X, HL, S, true, false, MO) \
+                                      RT_MEDIUM_TABLES(X, HL, S, false, true, MO) RT_MEDIUM_TABLES(X, HL, S, true, true, MO)
+#define RT_MEDIUM_INSTANTIATIONS(X, MO) RT_MEDIUM_MODES(X, false, false, MO) RT_MEDIUM_MODES(X, false, true, MO) RT_MEDIUM_MODES(X, true, false, MO) \
+                                        RT_MEDIUM_MODES(X, true, true, MO)
 
 #ifndef RT_KERNEL_MOTION_TU  // (rt_kernel_motion.hip takes the megakernel template alone; everything below is rt_hip_api.hip's)
 // Launched once when a scene is created: the runtime loads a module's code object onto the device with the first launch of ANY
@@ -1237,13 +1282,13 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
 // --------------------------------------------------------------------------- denoising
 // Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
 // 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
-template <bool LENS, bool MOTION = false>
+template <bool LENS, bool MOTION = false, bool MEDIUM = false>
 __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float4* __restrict__ out) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x >= sc.width || y >= sc.height) return;
   const GlobalTables tb{sc.geom, sc.matc};
   float r[8];
-  aov_pixel<LENS, MOTION>(sc, tb, x, y, n, r);
+  aov_pixel<LENS, MOTION, MEDIUM>(sc, tb, x, y, n, r);
   const size_t p = (size_t)y * sc.width + x;
   out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
   out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
@@ -1254,6 +1299,11 @@ __global__ __launch_bounds__(256) void rt_aov_lens(const DevScene sc, uint32_t n
 // (motion blur, DESIGN.md §14: the first hit at each sample's shutter time, as the MOTION megakernels trace it)
 __global__ __launch_bounds__(256) void rt_aov_motion(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, true>(sc, n, out); }
 __global__ __launch_bounds__(256) void rt_aov_lens_motion(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, true>(sc, n, out); }
+// (participating media, DESIGN.md §15: the first hit may lie inside a medium, found as the MEDIUM megakernels find it)
+__global__ __launch_bounds__(256) void rt_aov_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, false, true>(sc, n, out); }
+__global__ __launch_bounds__(256) void rt_aov_lens_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, false, true>(sc, n, out); }
+__global__ __launch_bounds__(256) void rt_aov_motion_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, true, true>(sc, n, out); }
+__global__ __launch_bounds__(256) void rt_aov_lens_motion_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, true, true>(sc, n, out); }
 
 // One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
 // ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two

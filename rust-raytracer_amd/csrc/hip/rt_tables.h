@@ -51,6 +51,10 @@ struct HostTables {
   // (no center1, or one equal to every centre).  n_moving: spheres with some dv component != 0.
   std::vector<double> motion;
   uint32_t n_moving = 0;
+  // participating media: [n] the density of a sphere of kind RT_MAT_MEDIUM, 0.0 for every other sphere; EMPTY for a
+  // scene without a medium.  The record the MEDIUM kernels ask inside the exact test: "is sphere i a medium, and how dense?"
+  std::vector<double> medium;
+  uint32_t n_media = 0;
 };
 
 // The box a sphere's centre can occupy over the shutter, axis k: [c0 - |r|, c0 + |r|] for a static sphere (today's expressions), and
@@ -342,6 +346,8 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     }
     if (t.n_moving) t.motion.swap(mv);
   }
+  t.medium.clear();
+  t.n_media = 0;
   t.geom.resize(n);
   t.mat.resize(n);
   t.matc.resize(n);
@@ -358,7 +364,14 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
   t.need_rgb8 = false;
   for (uint32_t i = 0; i < n; ++i) {
     const RtSphere& s = sc.spheres[i];
-    if (s.kind > RT_MAT_LIGHT) return "bad material kind";
+    if (s.kind > RT_MAT_MEDIUM) return "bad material kind";
+    if (s.kind == RT_MAT_MEDIUM) {  // (the radius and the density of a medium: finite and > 0)
+      if (!(std::isfinite(s.radius) && s.radius > 0.0)) return "sphere " + std::to_string(i) + ": the radius of a Medium sphere must be finite and > 0";
+      if (!(std::isfinite(s.fuzz_or_ior) && s.fuzz_or_ior > 0.0)) return "sphere " + std::to_string(i) + ": Medium.density must be finite and > 0";
+      if (t.medium.empty()) t.medium.assign(n, 0.0);
+      t.medium[i] = s.fuzz_or_ior;
+      t.n_media++;
+    }
     t.geom[i] = SphereGeom{s.center[0], s.center[1], s.center[2], s.radius};
     SphereMat m;
     std::memset(&m, 0, sizeof m);
@@ -390,7 +403,7 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     }
     t.matc[i] = mc;
     if (s.kind == RT_MAT_LIGHT) t.lights.push_back(i);
-    if (s.kind == RT_MAT_LAMBERTIAN || s.kind == RT_MAT_METAL)
+    if (s.kind == RT_MAT_LAMBERTIAN || s.kind == RT_MAT_METAL || s.kind == RT_MAT_MEDIUM)
       for (int c = 0; c < 3; ++c)
         if (!(s.albedo[c] >= 0.0f && s.albedo[c] <= 1.0f)) t.simple_colour = false;
     if (want_cull) {

@@ -399,8 +399,20 @@ void build_scene(const Value& root, RtSceneFile& sf) {
     } else if (tag == "Light") {
       struct_fields(body, "Light", {}, f);   // materials.rs:56-57: `struct Light {}` — {} or []
       s.kind = RT_MAT_LIGHT;
+    } else if (tag == "Medium") {
+      // a participating medium: an extension — the reference's enum has no such variant and rejects the file
+      const std::string which = "objects[" + std::to_string(sf.spheres.size()) + "]";
+      try {
+        struct_fields(body, "Medium", {"albedo", "density"}, f);
+        s.kind = RT_MAT_MEDIUM; parse_albedo(*f[0], s.albedo);
+        s.fuzz_or_ior = as_f64(*f[1], "Medium.density");
+      } catch (const SchemaError& e) {
+        bad(which + ": " + e.msg);
+      }
+      if (!(std::isfinite(s.fuzz_or_ior) && s.fuzz_or_ior > 0.0)) bad(which + ": Medium.density must be finite and > 0, got " + f[1]->text);
+      if (!(std::isfinite(s.radius) && s.radius > 0.0)) bad(which + ": the radius of a Medium sphere must be finite and > 0, got " + sp[1]->text);
     } else {
-      bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`");
+      bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`, `Medium`");
     }
     double c1[3] = {s.center[0], s.center[1], s.center[2]};
     if (sp[3]) {
@@ -498,6 +510,7 @@ std::string scene_json(const RtSceneFile& sf) {
         o += "\"Texture\":{\"albedo\":" + albedo(s.albedo) + ",\"pixels\":\"/tmp/texture.jpg\",\"width\":" +
              std::to_string(s.tex_w) + ",\"height\":" + std::to_string(s.tex_h) + ",\"h_offset\":" + f64s(s.h_offset) + "}";
         break;
+      case RT_MAT_MEDIUM: o += "\"Medium\":{\"albedo\":" + albedo(s.albedo) + ",\"density\":" + f64s(s.fuzz_or_ior) + "}"; break;
       default: o += "\"Light\":{}"; break;
     }
     o += "}}";
