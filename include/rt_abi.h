@@ -58,7 +58,15 @@ enum {
   /* Participating medium (an extension of the schema; NOT a variant of the reference's enum, whose loader rejects it):
    * a sphere of constant-density fog or smoke.  RtSphere.albedo is its albedo, RtSphere.fuzz_or_ior its density (finite, > 0); the radius
    * must be finite and > 0. */
-  RT_MAT_MEDIUM = 5
+  RT_MAT_MEDIUM = 5,
+  /* Solid textures (extensions of the schema; the reference's loader rejects both).  Both scatter exactly like
+   * Lambertian; only the attenuation differs (the contract is below, at rt_hip_scene_create_moving).
+   * Checker: RtSphere.albedo is the `even` colour, h_offset the scale (cells per unit length; finite, > 0), and the `odd` colour
+   * travels as f32 bit patterns: tex_w = bits(r) | bits(g) << 32, tex_h = bits(b) (the high half of tex_h is ignored). */
+  RT_MAT_CHECKER = 6,
+  /* Noise: RtSphere.albedo is the colour, h_offset the scale (finite, > 0), tex_id the mode (0 noise, 1 turbulence, 2 marble),
+   * tex_w the octaves (1..16; mode 0 ignores their value), tex_h the seed (at most 2^32 - 1). */
+  RT_MAT_NOISE = 7
 };
 
 /* config.rs:22-28, 49-64: sky null -> black; {"texture":""} -> gradient; path -> texture */
@@ -71,12 +79,12 @@ typedef struct RtSphere {
   double center[3];
   double radius;      /* may be negative: hollow glass, test_scene.json:137 */
   double fuzz_or_ior; /* Metal.fuzz | Glass.index_of_refraction | Medium.density */
-  double h_offset;    /* Texture.h_offset                                   */
+  double h_offset;    /* Texture.h_offset | Checker.scale | Noise.scale      */
   uint64_t tex_w;     /* Texture.width / height AS WRITTEN IN THE JSON      */
   uint64_t tex_h;     /*   (materials.rs:206-210), not the decoded size     */
   float albedo[3];    /* Lambertian/Metal/Medium albedo; ignored for Texture */
   uint32_t kind;      /* RT_MAT_*                                           */
-  uint32_t tex_id;    /* index into RtScene.textures when kind==TEXTURE     */
+  uint32_t tex_id;    /* index into RtScene.textures when kind==TEXTURE; Noise: the mode */
   uint32_t reserved;
 } RtSphere;
 
@@ -281,6 +289,24 @@ int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int 
  * its albedo, normal (0, 0, 0), the usual 1 / t.
  * rt_hip_scene_create* returns RT_ERR_INVALID for a medium whose radius or density is not finite and > 0, and RT_ERR_UNSUPPORTED for a
  * medium in a scene of more than 65 535 spheres (wide tables have no MEDIUM kernels).  rt_hip_scene_query "media" = their number. */
+/* Solid textures: spheres of kind RT_MAT_CHECKER and RT_MAT_NOISE scatter as Lambertian does (the same
+ * random_in_unit_sphere draw, the same near_zero rule, "not Glass" for the light-sampling draw, negative radii allowed); their
+ * attenuation is a function of the hit point in the SPHERE'S frame.  The contract, IEEE f64 without contraction (the code, whose bits
+ * are the contract, is csrc/common/rt_solid.h; its header states every step):
+ *   q = hit point - the centre the accepted hit test used (for a moving sphere the centre at the sample's shutter time: the pattern
+ *   rides the ball); p = q * scale per component.
+ *   Checker: f_c = floor(p_c); any !(fabs(f_c) < 2^52): even; else ((int64)f_x + (int64)f_y + (int64)f_z) & 1: 0 even, 1 odd.
+ *   Noise: the lattice noise N(p) — 0.0 if any !(fabs(p_c) < 2^31); corner hash (i_x+dx)*0x9E3779B1 ^ (i_y+dy)*0x85EBCA77 ^
+ *   (i_z+dz)*0xC2B2AE3D ^ seed through the murmur3 finaliser (>>16, *0x85EBCA6B, >>13, *0xC2B2AE35, >>16), Perlin's 2002 gradient rule on
+ *   h & 15, smoothstep weights, blended dx innermost, then dy, then dz — and the factor f in [0, 1] of the sphere's mode:
+ *     noise: 0.5 * (1.0 + N(p)) clamped to [0, 1];  turbulence: T = fabs(sum over `octaves` passes of w * N(r), w halving, r doubling),
+ *     f = min(T, 1.0);  marble: x = 0.15915494309189535 * (p_z + 10.0 * T), s = x - floor(x), m = 1.0 - fabs(2.0 * s - 1.0),
+ *     f = m * m * (3.0 - 2.0 * m), 0.0 for a non-finite x.
+ *   attenuation_c = (float)(f * (double)albedo_c).
+ * Denoising AOVs of a first hit on a solid: the evaluated colour as albedo, the usual normal and 1 / t.
+ * rt_hip_scene_create* returns RT_ERR_INVALID for a scale that is not finite and > 0, octaves outside 1..16, a seed above 2^32 - 1 or a
+ * mode above 2, and RT_ERR_UNSUPPORTED for a solid in a scene of more than 65 535 spheres (wide tables have no SOLID kernels).
+ * rt_hip_scene_query "solids" = the number of Checker and Noise spheres.  A scene without one selects the kernels it always did. */
 void rt_hip_scene_destroy(RtHipScene*);
 /* Launch the megakernel for the given row tiles on `stream` (a hipStream_t, NULL = default).
  *   d_rgb8    device buffer, rt_tiles_local_rows()*width*3 bytes, packed, top row first;
@@ -313,9 +339,9 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
  * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
  * "last_kernel" (the megakernel instantiation that ran: accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 |
- * tables in LDS 1; thin lens 32; moving spheres 64; participating media 128; -1 before the scene's first launch), "lens" (1:
+ * tables in LDS 1; thin lens 32; moving spheres 64; participating media 128; solid textures 256; -1 before the scene's first launch), "lens" (1:
  * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
- * (spheres of kind RT_MAT_MEDIUM).
+ * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the

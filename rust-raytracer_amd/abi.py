@@ -5,7 +5,8 @@ RT_ABI_VERSION = 5
 RT_MAX_LIGHT_NEST = 8
 RT_OK, RT_ERR_INVALID, RT_ERR_NO_DEVICE, RT_ERR_HIP = 0, -1, -2, -3
 RT_ERR_IO, RT_ERR_PARSE, RT_ERR_TEXTURE, RT_ERR_PNG, RT_ERR_UNSUPPORTED = -4, -5, -6, -7, -8
-RT_MAT_LAMBERTIAN, RT_MAT_METAL, RT_MAT_GLASS, RT_MAT_TEXTURE, RT_MAT_LIGHT, RT_MAT_MEDIUM = range(6)
+RT_MAT_LAMBERTIAN, RT_MAT_METAL, RT_MAT_GLASS, RT_MAT_TEXTURE, RT_MAT_LIGHT, RT_MAT_MEDIUM, RT_MAT_CHECKER, RT_MAT_NOISE = range(8)
+RT_NOISE_MODES = ("noise", "turbulence", "marble")   # RtSphere.tex_id of a Noise sphere
 RT_SKY_NONE, RT_SKY_GRADIENT, RT_SKY_TEXTURE = range(3)
 
 
@@ -14,6 +15,19 @@ class RtSphere(C.Structure):
                 ("h_offset", C.c_double), ("tex_w", C.c_uint64), ("tex_h", C.c_uint64),
                 ("albedo", C.c_float * 3), ("kind", C.c_uint32), ("tex_id", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+def checker_odd_pack(rgb):
+    """the `odd` colour of a Checker sphere as (tex_w, tex_h): f32 bit patterns, tex_w = bits(r) | bits(g) << 32, tex_h = bits(b)"""
+    import struct
+    r, g, b = (struct.unpack("<I", struct.pack("<f", float(v)))[0] for v in rgb)
+    return r | (g << 32), b
+
+
+def checker_odd_unpack(tex_w, tex_h):
+    """(r, g, b) of checker_odd_pack's two words, as Python floats holding the f32 values"""
+    import struct
+    return tuple(struct.unpack("<f", struct.pack("<I", w & 0xFFFFFFFF))[0] for w in (tex_w, tex_w >> 32, tex_h))
 
 
 class RtTexture(C.Structure):

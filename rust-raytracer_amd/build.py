@@ -61,6 +61,8 @@ def build_hip(force=False):
     # (... and the 64 MEDIUM instantiations, DESIGN.md §15, in two more units of 32 each)
     units = [("csrc/hip/rt_hip_api.hip", ["-DRT_MOTION_TU_SPLIT"]), ("csrc/hip/rt_kernel_motion.hip", []),
              ("csrc/hip/rt_kernel_medium.hip", []), ("csrc/hip/rt_kernel_medium_motion.hip", [])]
+    # (... and the 128 SOLID instantiations, DESIGN.md §16, in four more units of 32 each)
+    units += [("csrc/hip/" + u, []) for u in SOLID_UNITS]
     compiles, links = [], []
     for lib, extra in ((out, []), (probe, ["-DRT_TEST_PROBES"])):
         if not (force or _newer(lib, deps)):
@@ -92,8 +94,10 @@ def build_cli(force=False):
     return out
 
 
+SOLID_UNITS = ("rt_kernel_solid.hip", "rt_kernel_solid_motion.hip", "rt_kernel_solid_medium.hip", "rt_kernel_solid_medium_motion.hip")
 HIP_DEPS = ("csrc/hip/rt_hip_api.hip", "csrc/hip/rt_kernel.hip", "csrc/hip/rt_kernel_motion.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h",
-            "csrc/common/rt_atan2.h", "csrc/hip/rt_kernel_medium.hip", "csrc/hip/rt_kernel_medium_motion.hip", "csrc/common/rt_neg_log.h")
+            "csrc/common/rt_atan2.h", "csrc/hip/rt_kernel_medium.hip", "csrc/hip/rt_kernel_medium_motion.hip", "csrc/common/rt_neg_log.h",
+            "csrc/common/rt_solid.h") + tuple("csrc/hip/" + u for u in SOLID_UNITS)
 
 
 def kernel_src_hash():

@@ -28,6 +28,10 @@
 #define RT_NEG_LOG_FN __host__ __device__ inline
 #endif
 #include "../common/rt_neg_log.h"  // the one -ln(x) of a medium's free-flight distance
+#if defined(__HIPCC__)
+#define RT_SOLID_FN __host__ __device__ inline
+#endif
+#include "../common/rt_solid.h"  // the one checker and lattice noise of the solid textures
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__ __forceinline__
@@ -60,6 +64,8 @@ struct SphereMat {  // 80 B: materials.rs:35-42 payloads
   uint32_t texel_last;    // tex_nbytes / 3 - 1: the texel an out-of-range index is clamped to
   uint32_t tex_fast;      // 1: take that path (the record's sizes are in texels_fast()'s range)
   uint32_t pad;
+  // Solid textures reuse the fields a non-Texture record leaves unused: h_offset = the scale; Checker: tex_w, tex_h =
+  // the odd colour's f32 bit patterns (solid_odd_colour); Noise: tex_w = octaves, tex_h = seed, pad = mode.
 };
 static_assert(sizeof(SphereMat) == 80, "SphereMat is 80 B");
 // When the 4-byte-texel path returns what materials.rs:236-254 returns.  With width, height <= 2^24 and |h_offset| <= 1024
@@ -1135,20 +1141,63 @@ RT_HD V3 unit_vector_fast(V3 a) {
 RT_HD bool material_draws_unit_sphere(uint32_t kind) {
   return kind == RT_MAT_LAMBERTIAN || kind == RT_MAT_TEXTURE || kind == RT_MAT_METAL;
 }
+// ------------------------------------------------------------------ solid textures
+// The SOLID arm of the kernels: Checker and Noise spheres scatter as Lambertian does; their attenuation is a function of the hit point
+// in the sphere's frame — the contract of include/rt_abi.h, whose arithmetic is csrc/common/rt_solid.h, bit for bit.
+RT_HD bool material_is_solid(uint32_t kind) { return kind == RT_MAT_CHECKER || kind == RT_MAT_NOISE; }
+template <bool SOLID>
+RT_HD bool material_draws_unit_sphere_t(uint32_t kind) {  // (without the arm: the function above, nothing else)
+  if constexpr (SOLID) return material_draws_unit_sphere(kind) || material_is_solid(kind);
+  else return material_draws_unit_sphere(kind);
+}
+struct SolidOdd { float c[3]; };
+RT_HD SolidOdd solid_odd_colour(uint64_t tex_w, uint64_t tex_h) {  // rt_abi.h: tex_w = bits(r) | bits(g) << 32, tex_h = bits(b)
+  const uint32_t b[3] = {(uint32_t)tex_w, (uint32_t)(tex_w >> 32), (uint32_t)tex_h};
+  SolidOdd o;
+  __builtin_memcpy(o.c, b, 12);
+  return o;
+}
+// The attenuation of a hit at `point` on the solid sphere whose record is `m`, `centre` being the centre the accepted hit test used
+// (the centre at the sample's shutter time for a moving sphere).  COLD and by value (see exact_hit_slow, medium_hit): up to 16 octaves
+// x 8 corners of integer hashing and f64 blending stay out of the path loop's register budget; only lanes that hit a solid call it.
+RT_HD_COLD Rgb solid_albedo(V3 point, V3 centre, SphereMat m) {
+  const V3 q = sub(point, centre);
+  const double px = q.x * m.h_offset, py = q.y * m.h_offset, pz = q.z * m.h_offset;
+  if (m.kind == RT_MAT_CHECKER) {
+    if (!rt_solid_checker_odd(px, py, pz)) return rgb(m.albedo[0], m.albedo[1], m.albedo[2]);
+    const SolidOdd o = solid_odd_colour(m.tex_w, m.tex_h);
+    return rgb(o.c[0], o.c[1], o.c[2]);
+  }
+  const double f = rt_solid_noise_factor(px, py, pz, m.pad, (uint32_t)m.tex_w, (uint32_t)m.tex_h);
+  return rgb((float)(f * (double)m.albedo[0]), (float)(f * (double)m.albedo[1]), (float)(f * (double)m.albedo[2]));
+}
 // rnd_pre / glass_u_pre: the random_in_unit_sphere(ra, node) point and the Glass reflectance draw
 // (slot 0, .x.y) if the caller already drew them, or null
 // MEDIUM: a hit inside a participating medium scatters isotropically — the new direction is the unit-sphere point itself
 // (not normalised, as the reference's diffuse draws are), the incoming direction if that is near_zero; attenuation = albedo; no normal.
 // A compile-time arm: without it the function is the code it was.
-template <bool MEDIUM = false>
+// SOLID: a hit on a Checker or Noise sphere scatters as Lambertian does, with the attenuation of solid_albedo.  Likewise
+// a compile-time arm.
+template <bool MEDIUM = false, bool SOLID = false>
 RT_HD int scatter(const DevScene& sc, const RngAddr& ra, uint32_t node, V3 in_dir, const Surface& h,
                   const SphereGeom& g, const MatCore& m, uint32_t idx, V3& out_dir, float att[3], uint32_t& tex_oob,
                   const V3* rnd_pre = nullptr, const double* glass_u_pre = nullptr) {
   // Lambertian, Texture and Metal all draw random_in_unit_sphere (Metal even with fuzz = 0,
   // materials.rs:120); one shared rejection loop instead of one per material branch.
   V3 rnd = v3(0.0, 0.0, 0.0);
-  if (material_draws_unit_sphere(m.kind) || (MEDIUM && m.kind == RT_MAT_MEDIUM)) rnd = rnd_pre ? *rnd_pre : random_in_unit_sphere(ra, node);
+  if (material_draws_unit_sphere_t<SOLID>(m.kind) || (MEDIUM && m.kind == RT_MAT_MEDIUM)) rnd = rnd_pre ? *rnd_pre : random_in_unit_sphere(ra, node);
   att[0] = m.albedo[0]; att[1] = m.albedo[1]; att[2] = m.albedo[2];
+  if constexpr (SOLID) {
+    if (material_is_solid(m.kind)) {  // materials.rs:84-95 with the solid's colour
+      V3 sd = add(h.normal, rnd);
+      if (near_zero(sd)) sd = h.normal;
+      V3 target = add(h.point, sd);
+      out_dir = sub(target, h.point);
+      const Rgb a = solid_albedo(h.point, v3(g.cx, g.cy, g.cz), sc.mat[idx]);
+      att[0] = a.r; att[1] = a.g; att[2] = a.b;
+      return SCATTER_RAY;
+    }
+  }
   if constexpr (MEDIUM) {
     if (m.kind == RT_MAT_MEDIUM) {
       out_dir = near_zero(rnd) ? in_dir : rnd;
@@ -1749,7 +1798,7 @@ struct ShadeProf { unsigned long long* t; unsigned long long* last; uint32_t* n_
 #define RT_SHADE_MARK(k) do { } while (0)
 #define RT_SHADE_COUNT(act_) do { } while (0)
 #endif
-template <bool MEDIUM = false, class LaneT, class Tables>
+template <bool MEDIUM = false, bool SOLID = false, class LaneT, class Tables>
 RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, double t, const V3* rnd_pre = nullptr,
                       const double* glass_u_pre = nullptr, const double* light_u_pre = nullptr, ShadeProf* sp = nullptr) {
   (void)sp;
@@ -1766,7 +1815,7 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
     Surface h = surface_at(L.o, L.d, t, g, m.inv_r);
     V3 out_dir = v3(0, 0, 0);
     float att[3];
-    int st = scatter<MEDIUM>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
+    int st = scatter<MEDIUM, SOLID>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
     if (st == SCATTER_ABSORBED) { lane_finish_sample(sc, L, rgb(0.f, 0.f, 0.f)); return LANE_FINISHED; }       // :127-131
     if (st == SCATTER_EMIT) { lane_finish_sample(sc, L, rgb(att[0], att[1], att[2])); return LANE_FINISHED; }  // :124
     return lane_continue_main(sc, L, h.point, out_dir, zero3, att) ? LANE_FINISHED : LANE_CONTINUE;
@@ -1788,7 +1837,7 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
       const MatCore m = tb.mat((uint32_t)idx);
       Surface h = surface_at(L.o, L.d, t, g, m.inv_r);
       point = h.point;
-      const int st = scatter<MEDIUM>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
+      const int st = scatter<MEDIUM, SOLID>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
       if (st != SCATTER_RAY) {  // :124 Light: its colour; :127-131 absorbed: black
         if (st == SCATTER_EMIT) col = rgb(att[0], att[1], att[2]);
         act = light_ray ? ACT_RETURN : ACT_FINISH;
@@ -1884,9 +1933,10 @@ RT_HD uint8_t linear_to_u8(float lin) { return f32_to_u8(__builtin_sqrtf(lin)); 
 constexpr uint32_t AOV_FLOATS = 8u;
 // MOTION: the first hit at the sample's shutter time (sample_time), through the same MotionTables as the MOTION megakernels.
 // MEDIUM: a first hit inside a medium reports the medium's albedo, normal (0, 0, 0) and the usual 1 / t.
-template <bool MEDIUM = false, class Tables>
+// SOLID: a first hit on a Checker or Noise sphere reports the colour solid_albedo evaluates there, as Texture its texel.
+template <bool MEDIUM = false, bool SOLID = false, class Tables>
 RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]);
-template <bool LENS, bool MOTION = false, bool MEDIUM = false, class Tables>
+template <bool LENS, bool MOTION = false, bool MEDIUM = false, bool SOLID = false, class Tables>
 RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py, uint32_t n, float out[8]) {
   double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Lane<false> L;
@@ -1894,12 +1944,12 @@ RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t
   for (uint32_t s = 0; s < n; ++s) {
     L.s = s;
     lane_begin_sample<LENS>(sc, L, px, py);
-    if constexpr (MOTION) aov_sample<MEDIUM>(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
-    else aov_sample<MEDIUM>(sc, tb, L, acc);
+    if constexpr (MOTION) aov_sample<MEDIUM, SOLID>(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
+    else aov_sample<MEDIUM, SOLID>(sc, tb, L, acc);
   }
   for (int i = 0; i < 8; ++i) out[i] = (float)(acc[i] / (double)n);
 }
-template <bool MEDIUM, class Tables>
+template <bool MEDIUM, bool SOLID, class Tables>
 RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]) {
   {
     double closest = T_MAX;
@@ -1922,6 +1972,9 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
       else if (m.kind == RT_MAT_TEXTURE) {
         const UV uv = sphere_uv_for_texel(h.point, g, sc.mat, (uint32_t)best);
         const Rgb c = texture_albedo(sc, sc.mat[best], uv.u, uv.v, tex_oob);
+        a[0] = c.r; a[1] = c.g; a[2] = c.b;
+      } else if (SOLID && material_is_solid(m.kind)) {
+        const Rgb c = solid_albedo(h.point, v3(g.cx, g.cy, g.cz), sc.mat[best]);
         a[0] = c.r; a[1] = c.g; a[2] = c.b;
       } else if (m.kind != RT_MAT_LAMBERTIAN && m.kind != RT_MAT_METAL && !(MEDIUM && m.kind == RT_MAT_MEDIUM)) a[0] = a[1] = a[2] = 0.0f;
       acc[3] += 1.0 / closest;

@@ -121,6 +121,7 @@ struct RtHipScene {
     uint32_t n_moving = 0;
     DevBuf medium;           // participating media: [n] density per sphere, 0 = no medium (HostTables::medium); unallocated without media
     uint32_t n_media = 0;
+    uint32_t n_solids = 0;   // solid textures: Checker and Noise spheres; their parameters are in the `mat` records
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -341,6 +342,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   std::string why = rtc::build_tables(*scene, t, false, center1);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
   if (t.n_media && t.grid.wide) return fail(RT_ERR_UNSUPPORTED, "participating media in a scene with wide tables (more than 65 535 spheres)");
+  if (t.n_solids && t.grid.wide) return fail(RT_ERR_UNSUPPORTED, "solid textures in a scene with wide tables (more than 65 535 spheres)");
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
   pc.mark("scene.texels_rgbx");
@@ -373,6 +375,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   r->n_moving = t.n_moving;
   if (t.n_media && (rc = upload(r->medium, t.medium)) != RT_OK) return rc;
   r->n_media = t.n_media;
+  r->n_solids = t.n_solids;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
@@ -465,6 +468,12 @@ RT_MOTION_INSTANTIATIONS(RT_MOTION_EXTERN)
 #define RT_MEDIUM_EXTERN(HL, S, LDS, A, LE, MO) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, false, A, LE, MO, true>(rtk::KArgs);
 RT_MEDIUM_INSTANTIATIONS(RT_MEDIUM_EXTERN, false)
 RT_MEDIUM_INSTANTIATIONS(RT_MEDIUM_EXTERN, true)
+// (... and the four rt_kernel_solid*.hip the SOLID set)
+#define RT_SOLID_EXTERN(HL, S, LDS, A, LE, MO, ME) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, false, A, LE, MO, ME, true>(rtk::KArgs);
+RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, false, false)
+RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, true, false)
+RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, false, true)
+RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, true, true)
 #endif
 
 namespace {
@@ -496,6 +505,17 @@ template <int... K> std::array<Megakernel, 128> medium_megakernels(std::integer_
   ((t[K] = medium_megakernel_of_key<K>()), ...);
   return t;
 }
+// The SOLID instantiations have the key of their twin | 256 and a table of their own behind the two above, indexed by
+// the key without the SOLID bit (MEDIUM 128 included); wide tables have no SOLID kernel.
+template <int K> Megakernel solid_megakernel_of_key() {
+  if constexpr ((K & 8) != 0) return nullptr;
+  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, false, (K & 16) != 0, (K & 32) != 0, (K & 64) != 0, (K & 128) != 0, true>;
+}
+template <int... K> std::array<Megakernel, 256> solid_megakernels(std::integer_sequence<int, K...>) {
+  std::array<Megakernel, 256> t{};
+  ((t[K] = solid_megakernel_of_key<K>()), ...);
+  return t;
+}
 struct Kernel { int key = -1; Megakernel fn = nullptr; };
 int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
   static const std::array<Megakernel, 128> table = megakernels(std::make_integer_sequence<int, 128>());
@@ -507,6 +527,12 @@ int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wi
     if (wide) return fail(RT_ERR_UNSUPPORTED, "participating media with wide tables");
     out->fn = medium_table[out->key];
     out->key |= 128;
+  }
+  if (s->res->n_solids) {
+    static const std::array<Megakernel, 256> solid_table = solid_megakernels(std::make_integer_sequence<int, 256>());
+    if (wide) return fail(RT_ERR_UNSUPPORTED, "solid textures with wide tables");
+    out->fn = solid_table[out->key];
+    out->key |= 256;
   }
   return RT_OK;
 }
@@ -1049,8 +1075,9 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
+  if (!std::strcmp(key, "solids")) return (int64_t)s->res->n_solids;       // spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE
   if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
   if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
@@ -1240,7 +1267,15 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
   RT_HIP_TRY(hipSetDevice(s->device));
   const bool lens = s->dev.lens_r != 0.0;
-  if (s->dev.medium) {
+  if (s->res->n_solids) {  // (LENS x MOTION x MEDIUM)
+    const int v = (lens ? 4 : 0) | (s->dev.motion ? 2 : 0) | (s->dev.medium ? 1 : 0);
+    void (*k)(const rtc::DevScene, uint32_t, float4*) =
+        v == 0 ? rtk::rt_aov_solid<false, false, false> : v == 1 ? rtk::rt_aov_solid<false, false, true> : v == 2 ? rtk::rt_aov_solid<false, true, false>
+        : v == 3 ? rtk::rt_aov_solid<false, true, true> : v == 4 ? rtk::rt_aov_solid<true, false, false> : v == 5 ? rtk::rt_aov_solid<true, false, true>
+        : v == 6 ? rtk::rt_aov_solid<true, true, false> : rtk::rt_aov_solid<true, true, true>;
+    hipLaunchKernelGGL(k, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  }
+  else if (s->dev.medium) {
     auto k = s->dev.motion ? (lens ? rtk::rt_aov_lens_motion_medium : rtk::rt_aov_motion_medium) : (lens ? rtk::rt_aov_lens_medium : rtk::rt_aov_medium);
     hipLaunchKernelGGL(k, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   }

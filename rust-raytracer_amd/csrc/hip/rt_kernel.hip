@@ -334,10 +334,15 @@ struct LdsTables {  // per-lane gathers from the workgroup's LDS copies
 // sphere's density (DevScene::medium, HBM / L2) says whether it is a medium; if so the lane calls the cold rt_core.h medium_hit (one
 // Philox draw addressed by (node, sphere), rt_neg_log, the contract's divisions) instead of Sphere::hit.  The shading takes the
 // medium arm of scatter.  A compile-time arm: the other instantiations stay the code they were.
-template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false, bool MOTION = false, bool MEDIUM = false>
+// SOLID: solid textures: a lane whose closest hit is a Checker or Noise sphere draws its unit-sphere point with the
+// diffuse lanes and takes the solid arm of scatter, which calls the cold rt_core.h solid_albedo (the hit point in the sphere's frame
+// through csrc/common/rt_solid.h).  The hit tests do not change.  A compile-time arm: the other instantiations stay the code they were.
+template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false, bool MOTION = false, bool MEDIUM = false,
+          bool SOLID = false>
 __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs ka) {
   static_assert(!(LDS_TABLES && WIDE), "wide tables (more than 65 535 spheres) never fit LDS");
   static_assert(!(MEDIUM && WIDE), "media with wide tables are refused at scene creation (RT_ERR_UNSUPPORTED)");
+  static_assert(!(SOLID && WIDE), "solid textures with wide tables are refused at scene creation (RT_ERR_UNSUPPORTED)");
   const DevScene& sc = ka.sc;
   const GridDesc& G = sc.grid;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1000,7 +1005,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     const uint32_t hit_kind = has_ray && best >= 0 ? tb.mat((uint32_t)best).kind : 0xFFFFFFFFu;
     double glass_u, light_u;
     U4 cam_w;
-    const V3 rnd = coop_random_in_unit_sphere(hit_kind != 0xFFFFFFFFu && (material_draws_unit_sphere(hit_kind) || (MEDIUM && hit_kind == RT_MAT_MEDIUM)), hit_kind == RT_MAT_GLASS, fresh,
+    const V3 rnd = coop_random_in_unit_sphere(hit_kind != 0xFFFFFFFFu && (material_draws_unit_sphere_t<SOLID>(hit_kind) || (MEDIUM && hit_kind == RT_MAT_MEDIUM)), hit_kind == RT_MAT_GLASS, fresh,
                                               L.ra, L.node, lane, coop_xch, glass_u, light_u, cam_w);
 #ifdef RT_PROF_SPLIT  // (experiment builds: the random draws are booked under "item", lane_shade proper stays under "lane_shade")
     RT_PROF(5);
@@ -1025,11 +1030,11 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     if (has_ray) {
 #ifdef RT_PROF_LIT
       rtc::ShadeProf shade_prof{prof_t, &prof_last, &cnt_w_step, &cnt_w_test};
-      if constexpr (MOTION) status = lane_shade<MEDIUM>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
-      else status = lane_shade<MEDIUM>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      if constexpr (MOTION) status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      else status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
 #else
-      if constexpr (MOTION) status = lane_shade<MEDIUM>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
-      else status = lane_shade<MEDIUM>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      if constexpr (MOTION) status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      else status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
 #endif
       if constexpr (HL) { if (status == LANE_REPEAT) L.n_tex_oob = 0u; }  // (the hit is shaded again next iteration: its out-of-range texel counts THEN, once — RtStats.tex_oob equals the oracle's)
       flush_oob();
@@ -1135,6 +1140,16 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
                                       RT_MEDIUM_TABLES(X, HL, S, false, true, MO) RT_MEDIUM_TABLES(X, HL, S, true, true, MO)
 #define RT_MEDIUM_INSTANTIATIONS(X, MO) RT_MEDIUM_MODES(X, false, false, MO) RT_MEDIUM_MODES(X, false, true, MO) RT_MEDIUM_MODES(X, true, false, MO) \
                                         RT_MEDIUM_MODES(X, true, true, MO)
+
+// The 128 SOLID instantiations, as X(HL, SIMPLE, LDS_TABLES, ACCUM, LENS, MOTION, MEDIUM): what a scene with a Checker or
+// Noise sphere can select — everything a MEDIUM scene can, with and without media; never wide tables.  Four translation units of 32 each
+// (rt_kernel_solid.hip, rt_kernel_solid_motion.hip, rt_kernel_solid_medium.hip, rt_kernel_solid_medium_motion.hip), declared
+// `extern template` in rt_hip_api.hip under -DRT_MOTION_TU_SPLIT like the MOTION and MEDIUM sets.
+#define RT_SOLID_TABLES(X, HL, S, A, LE, MO, ME) X(HL, S, false, A, LE, MO, ME) X(HL, S, true, A, LE, MO, ME)
+#define RT_SOLID_MODES(X, HL, S, MO, ME) RT_SOLID_TABLES(X, HL, S, false, false, MO, ME) RT_SOLID_TABLES(X, HL, S, true, false, MO, ME) \
+                                         RT_SOLID_TABLES(X, HL, S, false, true, MO, ME) RT_SOLID_TABLES(X, HL, S, true, true, MO, ME)
+#define RT_SOLID_INSTANTIATIONS(X, MO, ME) RT_SOLID_MODES(X, false, false, MO, ME) RT_SOLID_MODES(X, false, true, MO, ME) \
+                                           RT_SOLID_MODES(X, true, false, MO, ME) RT_SOLID_MODES(X, true, true, MO, ME)
 
 #ifndef RT_KERNEL_MOTION_TU  // (rt_kernel_motion.hip takes the megakernel template alone; everything below is rt_hip_api.hip's)
 // Launched once when a scene is created: the runtime loads a module's code object onto the device with the first launch of ANY
@@ -1282,13 +1297,13 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
 // --------------------------------------------------------------------------- denoising
 // Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
 // 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
-template <bool LENS, bool MOTION = false, bool MEDIUM = false>
+template <bool LENS, bool MOTION = false, bool MEDIUM = false, bool SOLID = false>
 __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float4* __restrict__ out) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x >= sc.width || y >= sc.height) return;
   const GlobalTables tb{sc.geom, sc.matc};
   float r[8];
-  aov_pixel<LENS, MOTION, MEDIUM>(sc, tb, x, y, n, r);
+  aov_pixel<LENS, MOTION, MEDIUM, SOLID>(sc, tb, x, y, n, r);
   const size_t p = (size_t)y * sc.width + x;
   out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
   out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
@@ -1304,6 +1319,9 @@ __global__ __launch_bounds__(256) void rt_aov_medium(const DevScene sc, uint32_t
 __global__ __launch_bounds__(256) void rt_aov_lens_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, false, true>(sc, n, out); }
 __global__ __launch_bounds__(256) void rt_aov_motion_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, true, true>(sc, n, out); }
 __global__ __launch_bounds__(256) void rt_aov_lens_motion_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, true, true>(sc, n, out); }
+// (solid textures, DESIGN.md §16: a first hit on a Checker or Noise sphere reports the colour evaluated there; LENS x MOTION x MEDIUM)
+template <bool LENS, bool MOTION, bool MEDIUM>
+__global__ __launch_bounds__(256) void rt_aov_solid(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<LENS, MOTION, MEDIUM, true>(sc, n, out); }
 
 // One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
 // ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two

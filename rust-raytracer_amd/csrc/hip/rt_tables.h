@@ -55,6 +55,8 @@ struct HostTables {
   // scene without a medium.  The record the MEDIUM kernels ask inside the exact test: "is sphere i a medium, and how dense?"
   std::vector<double> medium;
   uint32_t n_media = 0;
+  // solid textures: the number of Checker and Noise spheres; their parameters travel in the SphereMat records
+  uint32_t n_solids = 0;
 };
 
 // The box a sphere's centre can occupy over the shutter, axis k: [c0 - |r|, c0 + |r|] for a static sphere (today's expressions), and
@@ -348,6 +350,7 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
   }
   t.medium.clear();
   t.n_media = 0;
+  t.n_solids = 0;
   t.geom.resize(n);
   t.mat.resize(n);
   t.matc.resize(n);
@@ -364,7 +367,17 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
   t.need_rgb8 = false;
   for (uint32_t i = 0; i < n; ++i) {
     const RtSphere& s = sc.spheres[i];
-    if (s.kind > RT_MAT_MEDIUM) return "bad material kind";
+    if (s.kind > RT_MAT_NOISE) return "bad material kind";
+    if (s.kind == RT_MAT_CHECKER || s.kind == RT_MAT_NOISE) {  // (negative radii are allowed, as for Lambertian)
+      const std::string which = "sphere " + std::to_string(i) + (s.kind == RT_MAT_CHECKER ? ": Checker" : ": Noise");
+      if (!(std::isfinite(s.h_offset) && s.h_offset > 0.0)) return which + ".scale must be finite and > 0";
+      if (s.kind == RT_MAT_NOISE) {
+        if (s.tex_id > RT_SOLID_MODE_MARBLE) return which + ".mode must be 0 (noise), 1 (turbulence) or 2 (marble)";
+        if (s.tex_w < 1 || s.tex_w > RT_SOLID_MAX_OCTAVES) return which + ".octaves must be 1..16";
+        if (s.tex_h > 0xFFFFFFFFull) return which + ".seed must be at most 2^32 - 1";
+      }
+      t.n_solids++;
+    }
     if (s.kind == RT_MAT_MEDIUM) {  // (the radius and the density of a medium: finite and > 0)
       if (!(std::isfinite(s.radius) && s.radius > 0.0)) return "sphere " + std::to_string(i) + ": the radius of a Medium sphere must be finite and > 0";
       if (!(std::isfinite(s.fuzz_or_ior) && s.fuzz_or_ior > 0.0)) return "sphere " + std::to_string(i) + ": Medium.density must be finite and > 0";
@@ -378,6 +391,7 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     m.albedo[0] = s.albedo[0]; m.albedo[1] = s.albedo[1]; m.albedo[2] = s.albedo[2];
     m.kind = s.kind; m.fuzz_or_ior = s.fuzz_or_ior; m.h_offset = s.h_offset;
     m.tex_w = s.tex_w; m.tex_h = s.tex_h;
+    if (s.kind == RT_MAT_NOISE) m.pad = s.tex_id;  // (the mode; scale, octaves / odd colour and seed are h_offset, tex_w, tex_h above)
     if (s.kind == RT_MAT_TEXTURE) {
       if (s.tex_id >= sc.n_textures) return "texture id out of range";
       m.tex_off = t.tex_off[s.tex_id];
@@ -403,9 +417,14 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     }
     t.matc[i] = mc;
     if (s.kind == RT_MAT_LIGHT) t.lights.push_back(i);
-    if (s.kind == RT_MAT_LAMBERTIAN || s.kind == RT_MAT_METAL || s.kind == RT_MAT_MEDIUM)
+    if (s.kind == RT_MAT_LAMBERTIAN || s.kind == RT_MAT_METAL || s.kind == RT_MAT_MEDIUM || s.kind == RT_MAT_CHECKER || s.kind == RT_MAT_NOISE)
       for (int c = 0; c < 3; ++c)
         if (!(s.albedo[c] >= 0.0f && s.albedo[c] <= 1.0f)) t.simple_colour = false;
+    if (s.kind == RT_MAT_CHECKER) {  // (the odd colour counts too: an attenuation of a solid is a factor in [0, 1] times one of its colours)
+      const SolidOdd odd = solid_odd_colour(s.tex_w, s.tex_h);
+      for (int c = 0; c < 3; ++c)
+        if (!(odd.c[c] >= 0.0f && odd.c[c] <= 1.0f)) t.simple_colour = false;
+    }
     if (want_cull) {
       CullPair& cp = t.cull[i / 2];
       build_cull_entry(s, &cp.cx[i & 1], &cp.cy[i & 1], &cp.cz[i & 1], &cp.R[i & 1]);

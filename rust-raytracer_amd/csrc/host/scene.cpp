@@ -411,8 +411,46 @@ void build_scene(const Value& root, RtSceneFile& sf) {
       }
       if (!(std::isfinite(s.fuzz_or_ior) && s.fuzz_or_ior > 0.0)) bad(which + ": Medium.density must be finite and > 0, got " + f[1]->text);
       if (!(std::isfinite(s.radius) && s.radius > 0.0)) bad(which + ": the radius of a Medium sphere must be finite and > 0, got " + sp[1]->text);
+    } else if (tag == "Checker" || tag == "Noise") {
+      // solid textures: extensions — the reference's enum has no such variants and rejects the file
+      const std::string which = "objects[" + std::to_string(sf.spheres.size()) + "]";
+      try {
+        if (tag == "Checker") {
+          struct_fields(body, "Checker", {"even", "odd", "scale"}, f);
+          float odd[3];
+          s.kind = RT_MAT_CHECKER; parse_albedo(*f[0], s.albedo); parse_albedo(*f[1], odd);
+          uint32_t b[3];
+          std::memcpy(b, odd, 12);
+          s.tex_w = uint64_t(b[0]) | (uint64_t(b[1]) << 32); s.tex_h = b[2];   // (the odd colour as f32 bit patterns, rt_abi.h)
+          s.h_offset = as_f64(*f[2], "Checker.scale");
+        } else {
+          struct_fields(body, "Noise", {"albedo", "scale", "mode", "octaves", "seed"}, f, {false, false, true, true, true});
+          s.kind = RT_MAT_NOISE; parse_albedo(*f[0], s.albedo);
+          s.h_offset = as_f64(*f[1], "Noise.scale");
+          s.tex_id = 0; s.tex_w = 7; s.tex_h = 0;
+          if (f[2]) {
+            if (f[2]->kind != Value::String) bad("Noise.mode: expected a string");
+            const std::string& mode = f[2]->text;
+            if (mode == "noise") s.tex_id = 0;
+            else if (mode == "turbulence") s.tex_id = 1;
+            else if (mode == "marble") s.tex_id = 2;
+            else bad("Noise.mode: unknown mode `" + mode + "`, expected one of `noise`, `turbulence`, `marble`");
+          }
+          if (f[3]) {
+            s.tex_w = as_u64(*f[3], "Noise.octaves", ~0ull);
+            if (s.tex_w < 1 || s.tex_w > 16) bad("Noise.octaves must be 1..16, got " + f[3]->text);
+          }
+          if (f[4]) {
+            s.tex_h = as_u64(*f[4], "Noise.seed", ~0ull);
+            if (s.tex_h > 0xFFFFFFFFull) bad("Noise.seed must be at most 4294967295, got " + f[4]->text);
+          }
+        }
+      } catch (const SchemaError& e) {
+        bad(which + ": " + e.msg);
+      }
+      if (!(std::isfinite(s.h_offset) && s.h_offset > 0.0)) bad(which + ": " + tag + ".scale must be finite and > 0, got " + f[tag == "Checker" ? 2 : 1]->text);
     } else {
-      bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`, `Medium`");
+      bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`, `Medium`, `Checker`, `Noise`");
     }
     double c1[3] = {s.center[0], s.center[1], s.center[2]};
     if (sp[3]) {
@@ -511,6 +549,18 @@ std::string scene_json(const RtSceneFile& sf) {
              std::to_string(s.tex_w) + ",\"height\":" + std::to_string(s.tex_h) + ",\"h_offset\":" + f64s(s.h_offset) + "}";
         break;
       case RT_MAT_MEDIUM: o += "\"Medium\":{\"albedo\":" + albedo(s.albedo) + ",\"density\":" + f64s(s.fuzz_or_ior) + "}"; break;
+      case RT_MAT_CHECKER: {  // (the odd colour back out of its bit patterns)
+        const uint32_t b[3] = {uint32_t(s.tex_w), uint32_t(s.tex_w >> 32), uint32_t(s.tex_h)};
+        float odd[3];
+        std::memcpy(odd, b, 12);
+        o += "\"Checker\":{\"even\":" + albedo(s.albedo) + ",\"odd\":" + albedo(odd) + ",\"scale\":" + f64s(s.h_offset) + "}";
+        break;
+      }
+      case RT_MAT_NOISE:
+        o += "\"Noise\":{\"albedo\":" + albedo(s.albedo) + ",\"scale\":" + f64s(s.h_offset) + ",\"mode\":\"" +
+             (s.tex_id == 1 ? "turbulence" : (s.tex_id == 2 ? "marble" : "noise")) + "\",\"octaves\":" + std::to_string(s.tex_w) +
+             ",\"seed\":" + std::to_string(s.tex_h) + "}";
+        break;
       default: o += "\"Light\":{}"; break;
     }
     o += "}}";

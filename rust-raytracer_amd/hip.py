@@ -155,6 +155,10 @@ def _center1_array(scene_ptr, center1):
     return (C.c_double * max(1, 3 * n))(*flat)
 
 
+# bits of query("last_kernel") (include/rt_abi.h rt_hip_scene_query)
+KERNEL_LDS, KERNEL_SIMPLE, KERNEL_LIGHTS, KERNEL_WIDE, KERNEL_ACCUM, KERNEL_LENS, KERNEL_MOTION, KERNEL_MEDIUM, KERNEL_SOLID = (1 << b for b in range(9))
+
+
 class HipScene:
     """Scene tables + textures resident in HBM of one GPU (rt_hip_scene_create).  `library`: probe_lib() for the tests and
     tools that use the debug calls; default: the product library."""
@@ -177,7 +181,8 @@ class HipScene:
         _check(self._L.rt_hip_set_option(self._h, key.encode(), int(value)), self._L)
 
     def query(self, key):
-        """rt_hip_scene_query: what the resident scene was built into ("grid_cells", "table_bytes", ...); -1 = unknown key"""
+        """rt_hip_scene_query: what the resident scene was built into ("grid_cells", "table_bytes", "media", "solids", ...) and
+        "last_kernel", the instantiation that ran (KERNEL_* bits below); -1 = unknown key"""
         return int(self._L.rt_hip_scene_query(self._h, key.encode()))
 
     def render(self, d_rgb8, d_linear=0, tiles=None, stream=0):
