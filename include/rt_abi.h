@@ -269,7 +269,7 @@ const char* rt_hip_setup_profile(void);
 int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene** out);
 /* Motion blur: the scene whose sphere i moves linearly from its centre (shutter open) to center1[3i .. 3i+2] (shutter
  * close).  Each sample of a pixel draws its shutter time tau from its own Philox address and traces its whole path at tau; a sphere is
- * at c0 + dv * tau, dv = center1 - center (f64).  Motion is fixed at creation: the grid lists each moving sphere by its swept box.
+ * at c0 + dv * tau, dv = center1 - center (f64).  The grid lists each moving sphere by its swept box (rt_hip_scene_update_spheres moves the spheres later).
  * center1 NULL, or equal to every centre: the static scene of rt_hip_scene_create.  RT_ERR_INVALID for a non-finite center1 - center
  * or a moving Light sphere.  rt_hip_scene_query "motion" = the number of moving spheres. */
 int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int device, RtHipScene** out);
@@ -344,6 +344,20 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
+/* Diagnostics: a copy of one resident table, as the kernels read it.  name: "grid" (the GridDesc bytes), "cell_word", "cell_items",
+ * "large", "geom", "large_geom", "motion" (empty for a static scene).  A blocking device-to-host copy into out (cap bytes); *needed
+ * receives the table's size, and out may be NULL to ask for it.  An unknown name, or a buffer that is too small: RT_ERR_INVALID. */
+int rt_hip_scene_table(const RtHipScene*, const char* name, void* out, size_t cap, size_t* needed);
+/* Move the spheres of a resident scene.  center = n_spheres x 3 (shutter open), center1 = NULL or n_spheres x 3
+ * (shutter close), both host pointers.  Radii, materials, textures, sky, camera, lens and options keep their values.  Blocking, like
+ * rt_hip_scene_create; waits for the scene's own unfinished launch first.  The grid is rebuilt on the device, and on RT_OK every
+ * resident table (rt_hip_scene_table) is byte for byte what rt_hip_scene_create_moving builds for the same RtScene with these centres;
+ * the launch configuration and rt_hip_scene_query "table_bytes", "grid_*", "motion" follow.  The learned tile order, the progressive
+ * accumulator, the adaptive buffers and the cached denoise AOVs start over, as after rt_hip_set_camera.  Errors are creation's:
+ * RT_ERR_INVALID for a non-finite center1 - center or a moving Light, RT_ERR_UNSUPPORTED for a Medium or solid sphere whose new grid
+ * needs wide tables — and after any error the scene renders exactly as before the call.  Device buffers grow when the new grid needs
+ * it and are otherwise reused.  A scene whose tables a live view shares (a group's ranks) is RT_ERR_INVALID: rt_hip_group_update_spheres. */
+int rt_hip_scene_update_spheres(RtHipScene*, const double* center, const double* center1);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
  * camera of a resident scene — the four vectors of camera.rs:52-63 — without touching its tables,
  * and render whole frames of it into a host buffer (internal device framebuffer, blocking). */
@@ -531,6 +545,9 @@ int rt_hip_group_set_camera(RtHipGroup*, const double origin[3], const double lo
                             const double vertical[3]);
 int rt_hip_group_set_lens(RtHipGroup*, const double u[3], const double v[3], double lens_radius);  /* rt_hip_set_lens on every rank */
 int rt_hip_group_set_option(RtHipGroup*, const char* key, int64_t value);
+/* rt_hip_scene_update_spheres on every rank (each rank's tables are built once; its second view follows them).  RT_ERR_INVALID while a
+ * submitted frame is uncollected. */
+int rt_hip_group_update_spheres(RtHipGroup*, const double* center, const double* center1);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
  * tile height; *tile_rows_out receives that height (2) */

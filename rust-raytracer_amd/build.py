@@ -63,6 +63,8 @@ def build_hip(force=False):
              ("csrc/hip/rt_kernel_medium.hip", []), ("csrc/hip/rt_kernel_medium_motion.hip", [])]
     # (... and the 128 SOLID instantiations, DESIGN.md §16, in four more units of 32 each)
     units += [("csrc/hip/" + u, []) for u in SOLID_UNITS]
+    # (... and the device grid build of rt_hip_scene_update_spheres, DESIGN.md §17: a few small kernels)
+    units.append(("csrc/hip/rt_grid_build.hip", []))
     compiles, links = [], []
     for lib, extra in ((out, []), (probe, ["-DRT_TEST_PROBES"])):
         if not (force or _newer(lib, deps)):
@@ -88,7 +90,7 @@ def build_cli(force=False):
     """the `raytracer <config_file> <output_file>` binary (reference main.rs)"""
     out = os.path.join(HERE, "raytracer")
     src = _srcs("csrc/host/main.cpp")
-    deps = src + [os.path.join(HERE, "librt_host.so"), os.path.join(HERE, "librt_hip.so")]
+    deps = src + _srcs("csrc/host/anim_path.h") + [os.path.join(HERE, "librt_host.so"), os.path.join(HERE, "librt_hip.so")]
     if os.path.exists(src[0]) and (force or _newer(out, deps)):
         _run(["g++", *CXXFLAGS, *src, "-o", out, "-L" + HERE, "-lrt_host", "-lrt_hip", "-lpthread", "-Wl,-rpath,$ORIGIN"])
     return out
@@ -97,7 +99,7 @@ def build_cli(force=False):
 SOLID_UNITS = ("rt_kernel_solid.hip", "rt_kernel_solid_motion.hip", "rt_kernel_solid_medium.hip", "rt_kernel_solid_medium_motion.hip")
 HIP_DEPS = ("csrc/hip/rt_hip_api.hip", "csrc/hip/rt_kernel.hip", "csrc/hip/rt_kernel_motion.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h",
             "csrc/common/rt_atan2.h", "csrc/hip/rt_kernel_medium.hip", "csrc/hip/rt_kernel_medium_motion.hip", "csrc/common/rt_neg_log.h",
-            "csrc/common/rt_solid.h") + tuple("csrc/hip/" + u for u in SOLID_UNITS)
+            "csrc/common/rt_solid.h", "csrc/hip/rt_grid_build.h", "csrc/hip/rt_grid_build.hip") + tuple("csrc/hip/" + u for u in SOLID_UNITS)
 
 
 def kernel_src_hash():

@@ -92,6 +92,7 @@ struct DevBuf {
   DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { if (p) (void)hipFree(p); }
   template <typename T = void> T* get() const { return static_cast<T*>(p); }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
   // At least `bytes`; *grew: it was (re)allocated, its contents are undefined.  Before an existing buffer is freed the work that may
   // still read it has finished: the whole device's, or only `stream`'s where the caller knows that is the one stream using it.
   // Runs only when a buffer grows — never per frame in steady state.
@@ -132,12 +133,21 @@ struct RtHipScene {
     std::vector<uint8_t> keep_tex_rgb8, keep_sky_rgb8;
     size_t texel_bytes = 0;
     rtc::GridDesc grid{};    // the product grid (variant 0)
+    // rt_hip_scene_update_spheres: the scene's spheres at their current centres (the host plans the next grid from
+    // them) and a second copy the next centres are written into; the tables an update builds into, swapped with the ones above when
+    // it has succeeded (the old ones are the next update's spares: a steady animation allocates nothing); the device builder's
+    // scratch; and the host staging of its uploads, kept like the texels above (freeing memory HIP copied from stalls the queues).
+    std::vector<RtSphere> spheres, next_spheres;
+    struct Spare { DevBuf geom, cell_word, cell_items, large, large_geom, motion; } spare;
+    struct Scratch { DevBuf centre, plan_large, range, lflag, lpos, count, start, cursor, block_sum, counts, raw_items, raw_cell; } gb;
+    rtc::GridPlan plan;
+    std::vector<double> keep_motion;
     bool has_lights = false, simple_colour = false;
     int num_cus = 0;
     size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
     ~Resident() { (void)hipSetDevice(device); }  // (the buffers are freed after this body)
   };
-  std::shared_ptr<const Resident> res;
+  std::shared_ptr<Resident> res;
   RtScene host{};          // scalar fields only (pointers are not kept)
   rtc::DevScene dev{};     // device pointers filled in
   struct Options {         // what rt_hip_set_option sets (a view starts with its scene's)
@@ -352,6 +362,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   r->has_lights = !t.lights.empty();
   r->simple_colour = t.simple_colour;
   r->grid = t.grid;
+  r->spheres.assign(scene->spheres, scene->spheres + scene->n_spheres);
   {
     hipDeviceProp_t prop;
     RT_HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -621,17 +632,21 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
   return RT_OK;
 }
 
-int warm_up(RtHipScene* s) {
-  // (keeping every CU busy for 0.5 - 20 ms here does NOT make a first frame faster — it is not the clocks:
-  //  profiles/r05_run7_cli_warm_spin.log)
-  hipLaunchKernelGGL(rtk::rt_warm_up, dim3(1), dim3(64), 0, nullptr);
-  RT_HIP_TRY(hipGetLastError());
+// the launch configuration of the scene's tables and options: the LDS-or-L2 staging choice, the kernel, its attribute and occupancy
+int configure(RtHipScene* s) {
   LdsPlan plan;
   int rc = plan_lds(s, s->dev.grid, s->res->has_lights, &plan);
   if (rc != RT_OK) return rc;
   Kernel k;
   if ((rc = select_kernel(s, s->res->has_lights, plan.lds_tables, s->dev.grid.wide != 0u, false, &k)) != RT_OK) return rc;
   return prepare(s, k, plan.lds_bytes, nullptr);
+}
+int warm_up(RtHipScene* s) {
+  // (keeping every CU busy for 0.5 - 20 ms here does NOT make a first frame faster — it is not the clocks:
+  //  profiles/r05_run7_cli_warm_spin.log)
+  hipLaunchKernelGGL(rtk::rt_warm_up, dim3(1), dim3(64), 0, nullptr);
+  RT_HIP_TRY(hipGetLastError());
+  return configure(s);
 }
 
 }  // namespace
@@ -1434,6 +1449,158 @@ int rt_hip_scene_warm(RtHipScene* s, hipStream_t stream) {
   s->order_key = RtHipScene::OrderKey(); s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
   for (auto& sl : s->slot) { sl.rows = 0; sl.samples = 0; sl.waves = 0; sl.launched = false; }
   return rc;
+}
+
+
+// ------------------------------------------------------------------------------ moving the spheres of a resident scene
+namespace {
+// Point a scene (or a view) at its resident's current tables and start over what was derived from the old ones: the launch
+// configuration (as creation derives it), the learned tile order, the progressive accumulator with its cached AOVs, the adaptive rounds.
+int adopt_tables(RtHipScene* s) {
+  const RtHipScene::Resident& r = *s->res;
+  s->dev.grid = r.grid;
+  s->dev.geom = r.geom.get<const rtc::SphereGeom>();
+  s->dev.cell_word = r.cell_word.get<const uint32_t>();
+  s->dev.cell_items = r.cell_items.get<const uint16_t>();
+  s->dev.large = r.large.get<const uint32_t>();
+  s->dev.large_geom = r.large_geom.get<const rtc::SphereGeom>();
+  s->dev.motion = r.n_moving ? r.motion.get<const double>() : nullptr;
+  s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
+  s->reset_accum();
+  s->ad_rounds.clear();
+  return configure(s);
+}
+
+// views_follow: the caller (the group) re-points the views that share this scene's tables itself
+int scene_update(RtHipScene* s, const double* center, const double* center1, bool views_follow) {
+  if (!s || (!center && s->host.n_spheres)) return fail(RT_ERR_INVALID, "null argument");
+  if (!views_follow && s->res.use_count() > 1)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_update_spheres: the scene's tables are shared with a view (a group updates through rt_hip_group_update_spheres)");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  if (s->n_launches && s->in_flight) { RT_HIP_TRY(hipStreamSynchronize(s->last_stream)); s->in_flight = false; }
+  if (!rtp::tl_in_group) rtp::reset();
+  rtp::Clock pc;
+  RtHipScene::Resident& r = *s->res;
+  const uint32_t n = s->host.n_spheres;
+  // the host's part: the spheres at their new centres, the motion rows, the plan of the grid (rt_tables.h: creation's own code)
+  std::vector<RtSphere>& next = r.next_spheres;
+  if (next.size() != r.spheres.size()) next = r.spheres;
+  for (uint32_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) next[i].center[k] = center[3 * (size_t)i + k];
+  RtScene sc = s->host;
+  sc.spheres = next.data();
+  rtc::HostTables t;
+  const std::string why = rtc::build_motion(sc, center1, t);
+  if (!why.empty()) return fail(RT_ERR_INVALID, why);
+  const rtc::GridParams gp = rtc::grid_params_shipped();
+  const bool want_wide = gp.force_wide || n > 65535u;
+  rtgb::Job j;
+  rtc::GridPlan& plan = r.plan;
+  j.all_large = rtc::grid_plan(sc, t, gp, want_wide, j.G, plan) != rtc::GRID_PLAN_GRID;
+  if (j.all_large) std::memset(&j.G, 0, sizeof j.G);
+  pc.mark("update.host_plan");
+  const uint32_t inner = j.all_large ? 0u : rtgb::inner_cells(j.G);
+  auto room = [](DevBuf& b, size_t bytes) { return b.ensure(bytes ? bytes : 16); };
+  int rc;
+  RtHipScene::Resident::Scratch& gb = r.gb;
+  if ((rc = room(gb.centre, (size_t)n * 24)) != RT_OK || (rc = room(gb.plan_large, n)) != RT_OK || (rc = room(gb.range, (size_t)n * sizeof(rtc::GridRange))) != RT_OK ||
+      (rc = room(gb.lflag, (size_t)n * 4)) != RT_OK || (rc = room(gb.lpos, (size_t)n * 4)) != RT_OK || (rc = room(gb.count, (size_t)inner * 4)) != RT_OK ||
+      (rc = room(gb.start, (size_t)inner * 4)) != RT_OK || (rc = room(gb.cursor, (size_t)inner * 4)) != RT_OK ||
+      (rc = room(gb.block_sum, (rtgb::scan_blocks(std::max<size_t>(n, inner)) + 1) * 8)) != RT_OK || (rc = room(gb.counts, sizeof(rtgb::Counts))) != RT_OK ||
+      (rc = room(r.spare.geom, (size_t)n * sizeof(rtc::SphereGeom))) != RT_OK || (t.n_moving && (rc = room(r.spare.motion, (size_t)n * 32)) != RT_OK))
+    return rc;
+  if (n) RT_HIP_TRY(hipMemcpy(gb.centre.p, center, (size_t)n * 24, hipMemcpyHostToDevice));  // (the centres travel once)
+  if (!j.all_large) RT_HIP_TRY(hipMemcpy(gb.plan_large.p, plan.is_large.data(), n, hipMemcpyHostToDevice));
+  if (t.n_moving) {  // (uploaded from storage that lives as long as the scene)
+    r.keep_motion.assign(t.motion.begin(), t.motion.end());
+    RT_HIP_TRY(hipMemcpy(r.spare.motion.p, r.keep_motion.data(), (size_t)n * 32, hipMemcpyHostToDevice));
+  }
+  pc.mark("update.upload");
+  j.n = n;
+  for (int k = 0; k < 3; ++k) j.cell_w[k] = plan.cell_w[k];
+  j.m = plan.m; j.large_cell_limit = gp.large_cell_limit;
+  j.centre = gb.centre.get<const double>(); j.old_geom = r.geom.get<const rtc::SphereGeom>();
+  j.motion = t.n_moving ? r.spare.motion.get<const double>() : nullptr;
+  j.plan_large = gb.plan_large.get<const uint8_t>();
+  j.range = gb.range.get<rtc::GridRange>(); j.lflag = gb.lflag.get<uint32_t>(); j.lpos = gb.lpos.get<uint32_t>();
+  j.count = gb.count.get<uint32_t>(); j.start = gb.start.get<uint32_t>(); j.cursor = gb.cursor.get<uint32_t>();
+  j.block_sum = gb.block_sum.get<unsigned long long>(); j.counts = gb.counts.get<rtgb::Counts>();
+  j.geom = r.spare.geom.get<rtc::SphereGeom>();
+  rtgb::Counts cnt;
+  RT_HIP_TRY(rtgb::count(j, nullptr));
+  RT_HIP_TRY(hipMemcpy(&cnt, gb.counts.p, sizeof cnt, hipMemcpyDeviceToHost));  // the one readback: item total, fullest cell, `large` count
+  bool wide = want_wide;
+  if (!j.all_large && cnt.n_items >= 0xFFFFFFFEull) {  // (more items than a 32-bit list holds: no grid, as build_grid_as decides)
+    j.all_large = true;
+    std::memset(&j.G, 0, sizeof j.G);
+    RT_HIP_TRY(rtgb::count(j, nullptr));
+    RT_HIP_TRY(hipMemcpy(&cnt, gb.counts.p, sizeof cnt, hipMemcpyDeviceToHost));
+  }
+  // the packed format's limits, where build_grid falls back to the wide one
+  if (!j.all_large && !wide && (cnt.max_count > rtc::CELL_MAX_COUNT || cnt.n_items >= rtc::CELL_START_MASK)) wide = true;
+  pc.mark("update.count_kernels_and_readback");
+  j.G.n_items = (uint32_t)cnt.n_items; j.G.n_large = (uint32_t)cnt.n_large; j.G.wide = (!j.all_large && wide) ? 1u : 0u;
+  if (r.n_media && j.G.wide) return (fail(RT_ERR_UNSUPPORTED, "participating media in a scene with wide tables (more than 65 535 spheres)"));
+  if (r.n_solids && j.G.wide) return (fail(RT_ERR_UNSUPPORTED, "solid textures in a scene with wide tables (more than 65 535 spheres)"));
+  if ((rc = room(r.spare.cell_word, (size_t)j.G.n_cells * (j.G.wide ? 16u : 8u))) != RT_OK || (rc = room(r.spare.cell_items, (size_t)j.G.n_items * (j.G.wide ? 4u : 2u))) != RT_OK ||
+      (rc = room(gb.raw_items, (size_t)j.G.n_items * 4)) != RT_OK || (rc = room(gb.raw_cell, (size_t)j.G.n_items * 4)) != RT_OK ||
+      (rc = room(r.spare.large, (size_t)j.G.n_large * 4)) != RT_OK || (rc = room(r.spare.large_geom, (size_t)j.G.n_large * sizeof(rtc::SphereGeom))) != RT_OK)
+    return rc;
+  j.raw_items = gb.raw_items.get<uint32_t>(); j.raw_cell = gb.raw_cell.get<uint32_t>();
+  j.cell_word = r.spare.cell_word.get<uint32_t>(); j.cell_items = r.spare.cell_items.p;
+  j.large = r.spare.large.get<uint32_t>(); j.large_geom = r.spare.large_geom.get<rtc::SphereGeom>();
+  RT_HIP_TRY(rtgb::tables(j, cnt.n_items, cnt.n_large, j.G.wide != 0u, nullptr));
+  RT_HIP_TRY(hipDeviceSynchronize());
+  pc.mark("update.table_kernels");
+  // every table is built: swap them in (nothing above changed what the scene renders with)
+  r.geom.swap(r.spare.geom); r.cell_word.swap(r.spare.cell_word); r.cell_items.swap(r.spare.cell_items);
+  r.large.swap(r.spare.large); r.large_geom.swap(r.spare.large_geom);
+  if (t.n_moving) r.motion.swap(r.spare.motion);
+  r.n_moving = t.n_moving;
+  r.grid = j.G;
+  r.spheres.swap(r.next_spheres);
+  rc = adopt_tables(s);
+  pc.mark("update.configuration");
+  return rc;
+}
+}  // namespace
+
+// a view follows its scene's update (internal; rt_hip_group_update_spheres): the tables it shares have been rebuilt
+int rt_hip_scene_view_follow(RtHipScene* view) {
+  if (!view) return fail(RT_ERR_INVALID, "null argument");
+  RT_HIP_TRY(hipSetDevice(view->device));
+  if (view->n_launches && view->in_flight) { RT_HIP_TRY(hipStreamSynchronize(view->last_stream)); view->in_flight = false; }
+  return adopt_tables(view);
+}
+
+extern "C" int rt_hip_scene_update_spheres(RtHipScene* s, const double* center, const double* center1) {
+  return scene_update(s, center, center1, false);
+}
+
+// diagnostics: one resident table as the kernels read it
+extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* out, size_t cap, size_t* needed) {
+  if (!s || !name) return fail(RT_ERR_INVALID, "null argument");
+  const RtHipScene::Resident& r = *s->res;
+  const rtc::GridDesc& G = r.grid;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  bool host = false;
+  if (!std::strcmp(name, "grid")) { src = &G; bytes = sizeof G; host = true; }
+  else if (!std::strcmp(name, "cell_word")) { src = r.cell_word.p; bytes = (size_t)G.n_cells * (G.wide ? 16u : 8u); }
+  else if (!std::strcmp(name, "cell_items")) { src = r.cell_items.p; bytes = (size_t)G.n_items * (G.wide ? 4u : 2u); }
+  else if (!std::strcmp(name, "large")) { src = r.large.p; bytes = (size_t)G.n_large * 4; }
+  else if (!std::strcmp(name, "geom")) { src = r.geom.p; bytes = (size_t)s->host.n_spheres * sizeof(rtc::SphereGeom); }
+  else if (!std::strcmp(name, "large_geom")) { src = r.large_geom.p; bytes = (size_t)G.n_large * sizeof(rtc::SphereGeom); }
+  else if (!std::strcmp(name, "motion")) { src = r.motion.p; bytes = r.n_moving ? (size_t)s->host.n_spheres * 32 : 0; }
+  else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
+  if (needed) *needed = bytes;
+  if (!out) return RT_OK;
+  if (cap < bytes) return fail(RT_ERR_INVALID, "the buffer is smaller than the table");
+  if (!bytes) return RT_OK;
+  if (host) { std::memcpy(out, src, bytes); return RT_OK; }
+  RT_HIP_TRY(hipSetDevice(s->device));
+  RT_HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
 }
 
 #include "rt_hip_group.hip"  // rt_hip_group_* and rt_render_rgb8: the frame over 1..G devices

@@ -551,6 +551,19 @@ extern "C" int rt_hip_group_set_lens(RtHipGroup* g, const double u[3], const dou
   return RT_OK;
 }
 
+// move the spheres of every rank's scene (rt_hip_scene_update_spheres); each rank's tables are built once, its second view follows
+extern "C" int rt_hip_group_update_spheres(RtHipGroup* g, const double* center, const double* center1) {
+  if (!g) return fail(RT_ERR_INVALID, "null argument");
+  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_update_spheres: a submitted frame is uncollected");
+  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad centres change no rank)
+    int rc = scene_update(g->scene[r], center, center1, true);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r]);
+    if (rc != RT_OK) return rc;
+  }
+  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
+  return RT_OK;
+}
+
 namespace rtg { void prepare_staging(RtHipGroup* g, int n_frames); }
 extern "C" int rt_hip_group_set_option(RtHipGroup* g, const char* key, int64_t value) {
   if (!g || !key) return fail(RT_ERR_INVALID, "null argument");

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rt_core.h"
+#include "rt_grid_build.h"
 
 namespace rtc {
 
@@ -59,16 +60,11 @@ struct HostTables {
   uint32_t n_solids = 0;
 };
 
-// The box a sphere's centre can occupy over the shutter, axis k: [c0 - |r|, c0 + |r|] for a static sphere (today's expressions), and
-// for a moving one the union of its boxes at c0 and c0 + dv, grown by a world-space slack that bounds the rounding of the kernel's
-// c0 + dv * tau (two f64 roundings, each <= 2^-53 of |c0| + |dv|) off the true segment: 4 * 2^-52 (|c0| + |dv|) + 1e-300.
+// The box a sphere's centre can occupy over the shutter, axis k (rt_grid_build.h grid_sphere_box: the static box, or the swept one).
+inline bool sphere_moves(const HostTables& t, uint32_t i);
 inline void sphere_box(const RtSphere& s, const HostTables& t, uint32_t i, int k, double& lo, double& hi) {
-  const double r = std::fabs(s.radius);
-  if (t.motion.empty() || t.motion[4 * (size_t)i + 3] == 0.0) { lo = s.center[k] - r; hi = s.center[k] + r; return; }
-  const double c0 = s.center[k], dv = t.motion[4 * (size_t)i + k], c1 = c0 + dv;
-  const double slack = 4.0 * 2.220446049250313e-16 * (std::fabs(c0) + std::fabs(dv)) + 1e-300;
-  lo = std::min(c0, c1) - r - slack;
-  hi = std::max(c0, c1) + r + slack;
+  const bool moves = sphere_moves(t, i);
+  grid_sphere_box(s.center[k], s.radius, moves, moves ? t.motion[4 * (size_t)i + k] : 0.0, lo, hi);
 }
 inline bool sphere_moves(const HostTables& t, uint32_t i) { return !t.motion.empty() && t.motion[4 * (size_t)i + 3] != 0.0; }
 
@@ -103,37 +99,42 @@ inline GridParams grid_params_from_env() {
   return p;
 }
 
-// Uniform grid over the ordinary spheres; see GridDesc / 2*GridDesc.pull in rt_core.h for what the
-// walk relies on: sphere i is listed in every cell its bounding box, grown by 2*GridDesc.pull
-// cells, overlaps (cells farther from the centre than the radius are dropped again).
-// `wide`: the table format (GridDesc.wide).  Returns false — with nothing usable in `t` — when the PACKED format cannot hold this
-// grid (more than 65 535 spheres: its item indices are u16, 0xFFFF = none; more than 4 095 items in a cell; 2^20 items or more):
-// the caller builds it again wide.
-// Motion (HostTables::motion not empty): every moving sphere is listed by its SWEPT box (sphere_box) grown by the same 2*pull margin,
-// with no per-cell distance test — so every cell holding a hit point at any tau is visited or within the margin of one that lists
-// it, as for a static sphere (DESIGN.md §14).  The `large` policy ranks a moving sphere by |r| + max_k |dv_k| / 2.
-inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp, bool wide) {
+// what build_tables and rt_hip_scene_update_spheres build with
+inline GridParams grid_params_shipped() {
+  GridParams gp = grid_params_from_env();
+  // Finer cells mean fewer exact tests per ray but more steps (and more lock-step walk rounds per
+  // wave).  Measured once the tall spheres had left the grid (profiles/r01_run9_ab_cells.log: 484
+  // spheres in LDS, 10 001 spheres out of L2, 4K textured): 2 cells per gridded sphere is best or
+  // tied everywhere (2: 15.15 ms, 3: 15.25, 4: 15.9, 8: 16.6), so that is the automatic choice.
+  if (!(gp.cells_per_sphere > 0.0)) gp.cells_per_sphere = 2.0;
+  return gp;
+}
+
+// The scalar part of the grid build, O(n) on the host for the host builder below and for the device builder alike
+// (rt_hip_scene_update_spheres): which spheres are `large` before any cell is counted (non-finite ones, the biggest few by
+// radius), the bounds, the cell counts (std::cbrt stays the host's: the cell count depends on its bits) and the GridDesc but for
+// n_items, n_large and wide.
+enum GridPlanKind { GRID_PLAN_ALL_LARGE = 0, GRID_PLAN_GRID = 1, GRID_PLAN_NOT_PACKED = 2 };
+struct GridPlan {
+  std::vector<uint8_t> is_large;  // [n] 1: in `large` whatever its cells
+  double m = 0.0;                 // registration margin in cells (rt_core.h "Margins")
+  double cell_w[3] = {0, 0, 0};   // the cell widths, 1.0 / inv_cell
+};
+inline GridPlanKind grid_plan(const RtScene& sc, const HostTables& t, const GridParams& gp, bool wide, GridDesc& G, GridPlan& plan) {
   const uint32_t n = sc.n_spheres;
-  GridDesc& G = t.grid;
   std::memset(&G, 0, sizeof G);
-  t.cell_word.clear(); t.cell_items.clear(); t.cell_items32.clear(); t.large.clear();
-  auto all_large = [&]() {
-    std::memset(&G, 0, sizeof G);
-    t.cell_word.clear(); t.cell_items.clear(); t.cell_items32.clear(); t.large.resize(n);
-    for (uint32_t i = 0; i < n; ++i) t.large[i] = i;
-    G.n_large = n;
-  };
-  if (n < gp.min_spheres) { all_large(); return true; }
-  if (!wide && n > 65535u) return false;
-  if (n >= 0xFFFFFFFEu) { all_large(); return true; }
-  std::vector<uint8_t> is_large(n, 0);
+  if (n < gp.min_spheres) return GRID_PLAN_ALL_LARGE;
+  if (!wide && n > 65535u) return GRID_PLAN_NOT_PACKED;
+  if (n >= 0xFFFFFFFEu) return GRID_PLAN_ALL_LARGE;
+  std::vector<uint8_t>& is_large = plan.is_large;
+  is_large.assign(n, 0);
   std::vector<double> radii;
   for (uint32_t i = 0; i < n; ++i) {
     const RtSphere& s = sc.spheres[i];
     const bool finite = std::isfinite(s.center[0]) && std::isfinite(s.center[1]) && std::isfinite(s.center[2]) && std::isfinite(s.radius);
     if (!finite) is_large[i] = 1; else radii.push_back(std::fabs(s.radius));
   }
-  if (radii.size() < gp.min_spheres) { all_large(); return true; }
+  if (radii.size() < gp.min_spheres) return GRID_PLAN_ALL_LARGE;
   std::nth_element(radii.begin(), radii.begin() + radii.size() / 2, radii.end());
   const double r_med = radii[radii.size() / 2];
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -178,7 +179,7 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
       hi[k] = std::max(hi[k], bh);
     }
   }
-  if (n_grid < gp.min_spheres) { all_large(); return true; }
+  if (n_grid < gp.min_spheres) return GRID_PLAN_ALL_LARGE;
   double ext[3], vol = 1.0;
   for (int k = 0; k < 3; ++k) {
     const double pad = 1e-3 * (hi[k] - lo[k]) + 1e-9 * (std::fabs(lo[k]) + std::fabs(hi[k])) + 1e-12;
@@ -206,41 +207,51 @@ inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp
     G.nd[k] = (double)G.n[k];
   }
   G.pull = (float)(8.0 * grid_walk_eps(std::max(G.n[0], std::max(G.n[1], G.n[2]))));
-  const uint32_t n_inner = G.n[0] * G.n[1] * G.n[2];
   const uint32_t px = G.n[0] + 2, py = G.n[1] + 2, pz = G.n[2] + 2;  // padded with the EXIT border
   G.n_cells = px * py * pz;
-  // cell range of each gridded sphere (bounding box grown by the walk's margin)
-  struct Range { int a[3], b[3]; };
-  std::vector<Range> rng(n);
-  const double m = 2.0 * (double)G.pull;  // registration margin (rt_core.h "Margins")
+  plan.m = 2.0 * (double)G.pull;  // registration margin (rt_core.h "Margins")
+  for (int k = 0; k < 3; ++k) plan.cell_w[k] = 1.0 / G.inv_cell[k];
+  return GRID_PLAN_GRID;
+}
+
+// Uniform grid over the ordinary spheres; see GridDesc / 2*GridDesc.pull in rt_core.h for what the
+// walk relies on: sphere i is listed in every cell its bounding box, grown by 2*GridDesc.pull
+// cells, overlaps (cells farther from the centre than the radius are dropped again).
+// `wide`: the table format (GridDesc.wide).  Returns false — with nothing usable in `t` — when the PACKED format cannot hold this
+// grid (more than 65 535 spheres: its item indices are u16, 0xFFFF = none; more than 4 095 items in a cell; 2^20 items or more):
+// the caller builds it again wide.
+// Motion (HostTables::motion not empty): every moving sphere is listed by its SWEPT box (sphere_box) grown by the same 2*pull margin,
+// with no per-cell distance test — so every cell holding a hit point at any tau is visited or within the margin of one that lists
+// it, as for a static sphere (DESIGN.md §14).  The `large` policy ranks a moving sphere by |r| + max_k |dv_k| / 2.
+inline bool build_grid_as(const RtScene& sc, HostTables& t, const GridParams& gp, bool wide) {
+  const uint32_t n = sc.n_spheres;
+  GridDesc& G = t.grid;
+  t.cell_word.clear(); t.cell_items.clear(); t.cell_items32.clear(); t.large.clear();
+  auto all_large = [&]() {
+    std::memset(&G, 0, sizeof G);
+    t.cell_word.clear(); t.cell_items.clear(); t.cell_items32.clear(); t.large.resize(n);
+    for (uint32_t i = 0; i < n; ++i) t.large[i] = i;
+    G.n_large = n;
+  };
+  GridPlan plan;
+  const GridPlanKind kind = grid_plan(sc, t, gp, wide, G, plan);
+  if (kind == GRID_PLAN_ALL_LARGE) { all_large(); return true; }
+  if (kind == GRID_PLAN_NOT_PACKED) return false;
+  std::vector<uint8_t>& is_large = plan.is_large;
+  const uint32_t n_inner = G.n[0] * G.n[1] * G.n[2];
+  const uint32_t px = G.n[0] + 2, py = G.n[1] + 2, pz = G.n[2] + 2;  // padded with the EXIT border
+  (void)pz;
+  // cell range of each gridded sphere (bounding box grown by the walk's margin; rt_grid_build.h grid_cell_range)
+  std::vector<GridRange> rng(n);
+  const double m = plan.m;
   for (uint32_t i = 0; i < n; ++i) {
     if (is_large[i]) continue;
     const RtSphere& s = sc.spheres[i];
-    uint64_t cells = 1;
-    for (int k = 0; k < 3; ++k) {
-      double bl, bh;
-      sphere_box(s, t, i, k, bl, bh);
-      double a = std::floor((bl - G.gmin[k]) * G.inv_cell[k] - m);
-      double b = std::floor((bh - G.gmin[k]) * G.inv_cell[k] + m);
-      a = std::max(a, 0.0); b = std::min(b, (double)G.n[k] - 1.0);
-      rng[i].a[k] = (int)a; rng[i].b[k] = (int)b;
-      cells *= (uint64_t)(b >= a ? (int)b - (int)a + 1 : 0);
-    }
+    const uint64_t cells = grid_cell_range(G, m, s.center, s.radius, t.motion.empty() ? nullptr : &t.motion[4 * (size_t)i], rng[i]);
     if (cells > gp.large_cell_limit) is_large[i] = 1;
   }
-  // does the cell (grown by the margin) come within |r| of the centre?  (world units, f64)
-  auto overlaps = [&](const RtSphere& s, int ix, int iy, int iz) {
-    const int idx[3] = {ix, iy, iz};
-    double d2 = 0.0;
-    for (int k = 0; k < 3; ++k) {
-      const double w = 1.0 / G.inv_cell[k];
-      const double c0 = G.gmin[k] + ((double)idx[k] - m) * w, c1 = G.gmin[k] + ((double)idx[k] + 1.0 + m) * w;
-      const double d = s.center[k] < c0 ? c0 - s.center[k] : (s.center[k] > c1 ? s.center[k] - c1 : 0.0);
-      d2 += d * d;
-    }
-    const double r = std::fabs(s.radius) * (1.0 + 1e-9);
-    return d2 <= r * r;
-  };
+  // does the cell (grown by the margin) come within |r| of the centre?  (rt_grid_build.h grid_overlaps)
+  auto overlaps = [&](const RtSphere& s, int ix, int iy, int iz) { return grid_overlaps(G, plan.cell_w, m, s.center, s.radius, ix, iy, iz); };
   std::vector<uint8_t> moving(n, 0);
   for (uint32_t i = 0; i < n; ++i) moving[i] = sphere_moves(t, i) ? 1 : 0;
   std::vector<uint32_t> count(n_inner, 0);
@@ -307,25 +318,9 @@ inline void build_grid(const RtScene& sc, HostTables& t, const GridParams& gp) {
   if (!build_grid_as(sc, t, gp, wide)) build_grid_as(sc, t, gp, true);
 }
 
-// returns "" or a description of why the scene is invalid (RT_ERR_INVALID)
-// want_cull: also the round-1 cull-pair table (HostTables::cull) — no kernel reads it any more; tests/hostsim's audit mode and
-// tools/analysis/walk_sim.cpp do (the product's rt_hip_scene_create leaves it out since round 6).
-// center1 (motion blur, DESIGN.md §14): null, or [n_spheres][3] centres at shutter close (rt_scene_motion); a sphere whose center1
-// equals its centre (NaN components: both NaN) is static.  dv = center1 - center must be finite, and a Light sphere cannot move.
-inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull = false, const double* center1 = nullptr) {
-  if (sc.abi_version != RT_ABI_VERSION) return "abi_version mismatch";
-  if (sc.width == 0 || sc.height == 0) return "empty image";
-  if (sc.n_spheres && !sc.spheres) return "null sphere table";
-  if (sc.n_textures && !sc.textures) return "null texture table";
-  if (sc.sky_mode > RT_SKY_TEXTURE) return "bad sky_mode";
-  if (sc.sky_mode == RT_SKY_TEXTURE && (!sc.sky_rgb8 || sc.sky_w == 0 || sc.sky_h == 0)) return "sky texture missing";
-  t.tex_off.resize(sc.n_textures);
-  t.tex_bytes = 0;
-  for (uint32_t i = 0; i < sc.n_textures; ++i) {
-    if (sc.textures[i].nbytes && !sc.textures[i].rgb8) return "null texture pixels";
-    t.tex_off[i] = t.tex_bytes;
-    t.tex_bytes += (sc.textures[i].nbytes + 15) & ~15ull;
-  }
+// The motion table of a scene whose sphere i moves from its centre to center1[3i .. 3i+2] over the shutter (HostTables::motion, n_moving);
+// "" or why the motion is invalid.  Shared by build_tables and rt_hip_scene_update_spheres.
+inline std::string build_motion(const RtScene& sc, const double* center1, HostTables& t) {
   const uint32_t n = sc.n_spheres;
   t.motion.clear();
   t.n_moving = 0;
@@ -348,6 +343,30 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     }
     if (t.n_moving) t.motion.swap(mv);
   }
+  return "";
+}
+
+// returns "" or a description of why the scene is invalid (RT_ERR_INVALID)
+// want_cull: also the round-1 cull-pair table (HostTables::cull) — no kernel reads it any more; tests/hostsim's audit mode and
+// tools/analysis/walk_sim.cpp do (the product's rt_hip_scene_create leaves it out since round 6).
+// center1 (motion blur, DESIGN.md §14): null, or [n_spheres][3] centres at shutter close (rt_scene_motion); a sphere whose center1
+// equals its centre (NaN components: both NaN) is static.  dv = center1 - center must be finite, and a Light sphere cannot move.
+inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull = false, const double* center1 = nullptr) {
+  if (sc.abi_version != RT_ABI_VERSION) return "abi_version mismatch";
+  if (sc.width == 0 || sc.height == 0) return "empty image";
+  if (sc.n_spheres && !sc.spheres) return "null sphere table";
+  if (sc.n_textures && !sc.textures) return "null texture table";
+  if (sc.sky_mode > RT_SKY_TEXTURE) return "bad sky_mode";
+  if (sc.sky_mode == RT_SKY_TEXTURE && (!sc.sky_rgb8 || sc.sky_w == 0 || sc.sky_h == 0)) return "sky texture missing";
+  t.tex_off.resize(sc.n_textures);
+  t.tex_bytes = 0;
+  for (uint32_t i = 0; i < sc.n_textures; ++i) {
+    if (sc.textures[i].nbytes && !sc.textures[i].rgb8) return "null texture pixels";
+    t.tex_off[i] = t.tex_bytes;
+    t.tex_bytes += (sc.textures[i].nbytes + 15) & ~15ull;
+  }
+  const uint32_t n = sc.n_spheres;
+  { const std::string why = build_motion(sc, center1, t); if (!why.empty()) return why; }
   t.medium.clear();
   t.n_media = 0;
   t.n_solids = 0;
@@ -438,17 +457,8 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
     t.large_geom.resize(t.large.size());
     for (size_t i = 0; i < t.large.size(); ++i) t.large_geom[i] = t.geom[t.large[i]];
   };
-  GridParams gp = grid_params_from_env();
-  if (gp.cells_per_sphere > 0.0) { build_grid(sc, t, gp); pack_large(); }
-  else {
-    // Finer cells mean fewer exact tests per ray but more steps (and more lock-step walk rounds per
-    // wave).  Measured once the tall spheres had left the grid (profiles/r01_run9_ab_cells.log: 484
-    // spheres in LDS, 10 001 spheres out of L2, 4K textured): 2 cells per gridded sphere is best or
-    // tied everywhere (2: 15.15 ms, 3: 15.25, 4: 15.9, 8: 16.6), so that is the automatic choice.
-    gp.cells_per_sphere = 2.0;
-    build_grid(sc, t, gp);
-    pack_large();
-  }
+  build_grid(sc, t, grid_params_shipped());
+  pack_large();
   return "";
 }
 

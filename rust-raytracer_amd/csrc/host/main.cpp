@@ -40,6 +40,12 @@
 //
 // Motion blur: a scene whose spheres have "center1" (rt_scene_motion) is created with rt_hip_scene_create_moving /
 // rt_hip_group_create_moving in every mode above, with or without a lens; its one-shot frame goes through a one-frame group too.
+//
+// Moving spheres from frame to frame (`--frames N --shutter S`, 0 <= S <= 1): a sphere's "center" -> "center1" is its
+// path over the whole animation instead of over one exposure; frame f is exposed from center + dv f / N to center + dv (f + S) / N
+// (anim_path.h), S = 0 giving crisp spheres.  The resident scene's spheres are moved before every frame (rt_hip_group_update_spheres /
+// rt_hip_scene_update_spheres: the grid is rebuilt on the GPU).  A group refuses an update while a frame is in flight, so in this mode
+// frame f is collected before the spheres move for f + 1; its PNG is still written while f + 1 renders.  Only with --frames.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -52,6 +58,7 @@
 #include <vector>
 
 #include "../../../include/rt_abi.h"
+#include "anim_path.h"
 
 namespace {
 // camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77 with the scene's
@@ -186,7 +193,7 @@ unsigned anim_writers() {
 // Every frame SHARDED over the RT_GPUS devices (rt_hip_group_*), frames pipelined two deep: frame f+1 is submitted before
 // frame f is collected, so f's gather + de-interleave + device-to-host copy run under f+1's kernels, and f's PNG is encoded
 // on the writer threads meanwhile.  2 + W host buffers: two frames in flight + one per writer.
-int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg) {
+int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
   RtScene* sc = rt_scene_get_mut(sf);
   RtHipGroup* hs = nullptr;  // the scene resident on RT_GPUS devices (default 1)
   const auto t_create = std::chrono::steady_clock::now();
@@ -221,11 +228,21 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
     return !writers.failed();
   };
   int submitted = 0, collected = 0;
+  std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
+  if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
   for (int f = 0; f < frames && status == 0 && !writers.failed(); ++f) {
     double out[20];
     const auto t0 = std::chrono::steady_clock::now();
     uint8_t* buf = writers.take_buffer();
     const auto t1 = std::chrono::steady_clock::now();
+    if (shutter >= 0.0) {  // (no frame may be in flight while the spheres move: frame f - 1 is collected first, its PNG overlaps)
+      bool ok = true;
+      while (ok && collected < submitted) { ok = finish(collected); if (ok) collected++; }
+      if (!ok) { writers.give_buffer(buf); break; }
+      rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
+      rc = rt_hip_group_update_spheres(hs, c_f.data(), c1_f.data());
+      if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; writers.give_buffer(buf); break; }
+    }
     orbit_camera(cam, lens, orbit_deg, f, out);
     rt_hip_group_set_camera(hs, out, out + 3, out + 6, out + 9);
     rc = lens[0] != 0.0 ? rt_hip_group_set_lens(hs, out + 13, out + 16, out[19]) : RT_OK;
@@ -312,7 +329,7 @@ int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t m
 // scene and host thread (README.md:43-57 renders an animation one process per frame; this is that, with the scene loaded
 // once per device).  No gather, no shard penalty, no per-frame synchronisation between devices; every frame is the bytes the
 // sharded mode produces (Philox is addressed by pixel).  Per device the PNG of a frame is encoded while the next one renders.
-int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, unsigned G) {
+int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, unsigned G, double shutter) {
   RtScene* sc = rt_scene_get_mut(sf);
   const int ndev = rt_hip_device_count();
   const char* emu = std::getenv("RT_GPUS_EMULATE");
@@ -339,11 +356,17 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
       std::vector<uint8_t> buf[2] = {std::vector<uint8_t>(bytes), std::vector<uint8_t>(bytes)};
       std::thread writer;
       int write_rc = RT_OK, i = 0;
+      std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
+      if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
       for (int f = (int)g; f < frames && write_rc == RT_OK; f += (int)G, ++i) {
         double out[20];
         orbit_camera(cam, lens, orbit_deg, f, out);
         rt_hip_set_camera(hs, out, out + 3, out + 6, out + 9);
         rc = lens[0] != 0.0 ? rt_hip_set_lens(hs, out + 13, out + 16, out[19]) : RT_OK;
+        if (rc == RT_OK && shutter >= 0.0) {
+          rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
+          rc = rt_hip_scene_update_spheres(hs, c_f.data(), c1_f.data());
+        }
         RtStats st{};
         if (rc == RT_OK) rc = rt_hip_render_to_host(hs, buf[i & 1].data(), &st);
         const std::string fname = frame_name(prefix, f);
@@ -392,17 +415,18 @@ int render_group_rgb8(const RtScene* sc, const double* c, const double* center1,
   return rc;
 }
 
-int animate(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg) {
+// shutter < 0: no --shutter (every frame exposes the scene file's center -> center1)
+int animate(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
   const char* mode = std::getenv("RT_ANIM");
   if (mode && !std::strcmp(mode, "frames")) {
     const RtScene* sc = rt_scene_get(sf);
     unsigned G = sc->n_gpus;
     if (G == 0) { const char* e = std::getenv("RT_GPUS"); G = e ? (unsigned)std::strtoul(e, nullptr, 10) : 1u; }
     if (G < 1 || G > 1024) { std::fprintf(stderr, "render failed: RT_GPUS must be a positive device count\n"); return 101; }
-    return animate_frames(sf, prefix, frames, orbit_deg, G);
+    return animate_frames(sf, prefix, frames, orbit_deg, G, shutter);
   }
   if (mode && std::strcmp(mode, "sharded")) { std::fprintf(stderr, "RT_ANIM must be sharded (default) or frames\n"); return 101; }
-  return animate_sharded(sf, prefix, frames, orbit_deg);
+  return animate_sharded(sf, prefix, frames, orbit_deg, shutter);
 }
 }  // namespace
 
@@ -416,13 +440,17 @@ int run(int argc, char** argv) {
   const auto t_main = std::chrono::steady_clock::now();
   int frames = 0;
   long passes = 0, min_spp = 16;
-  double orbit = 0.0, threshold = 0.0;
+  double orbit = 0.0, threshold = 0.0, shutter = -1.0;
   bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false, denoise = false;
   for (int i = 3; i < argc && !bad_args; ++i) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
     else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit = std::atof(argv[++i]); orbit_given = true; }
-    else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
+    else if (!std::strcmp(argv[i], "--shutter") && i + 1 < argc) {
+      char* end = nullptr;
+      shutter = std::strtod(argv[++i], &end);
+      if (end == argv[i] || *end != '\0' || !(shutter >= 0.0 && shutter <= 1.0)) bad_args = true;
+    } else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
       char* end = nullptr;
       passes = std::strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end != '\0' || passes < 1) bad_args = true;
@@ -439,7 +467,7 @@ int run(int argc, char** argv) {
     } else bad_args = true;
   }
   auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
-  if (bad_args || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
+  if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || denoise)) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
       (denoise && (adapt || frames != 0 || orbit_given)) || (argc > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
     return usage();  // main.rs:9-12: usage line, normal return
   // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
@@ -501,7 +529,7 @@ int run(int argc, char** argv) {
   }
   if (frames > 0) {
     if (g_hip_init.joinable()) g_hip_init.join();
-    const int status = animate(sf, argv[2], frames, orbit_given ? orbit : 360.0 / frames);
+    const int status = animate(sf, argv[2], frames, orbit_given ? orbit : 360.0 / frames, shutter);
     rt_scene_free(sf);
     return status;
   }

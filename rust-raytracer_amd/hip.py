@@ -51,6 +51,9 @@ def _bind(path, probes):
     L.rt_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
     L.rt_hip_scene_query.argtypes = [C.c_void_p, C.c_char_p]
     L.rt_hip_scene_query.restype = C.c_int64
+    L.rt_hip_scene_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rt_hip_scene_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.rt_hip_group_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
     L.rt_hip_set_camera.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4
     L.rt_hip_set_lens.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]
@@ -155,6 +158,20 @@ def _center1_array(scene_ptr, center1):
     return (C.c_double * max(1, 3 * n))(*flat)
 
 
+def _centres(n, c, what):
+    """n x 3 centres (anything numpy can flatten) as a C array of doubles; None stays None"""
+    import numpy as np
+    if c is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(c, np.float64).reshape(-1))
+    if a.size != 3 * n:
+        raise ValueError(f"{what} needs {n} x 3 values, got {a.size}")
+    return (C.c_double * max(1, 3 * n)).from_buffer_copy(a.tobytes() if n else bytes(8))
+
+
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion")   # the names rt_hip_scene_table knows
+
+
 # bits of query("last_kernel") (include/rt_abi.h rt_hip_scene_query)
 KERNEL_LDS, KERNEL_SIMPLE, KERNEL_LIGHTS, KERNEL_WIDE, KERNEL_ACCUM, KERNEL_LENS, KERNEL_MOTION, KERNEL_MEDIUM, KERNEL_SOLID = (1 << b for b in range(9))
 
@@ -176,6 +193,21 @@ class HipScene:
         sc = scene_ptr.contents
         self.width, self.height = sc.width, sc.height
         self.device = device
+        self.n_spheres = sc.n_spheres
+
+    def update_spheres(self, center, center1=None):
+        """rt_hip_scene_update_spheres: move the spheres to `center` (n_spheres x 3, shutter open) and `center1` (None, or
+        n_spheres x 3 at shutter close); the grid is rebuilt on the device.  Blocking."""
+        _check(self._L.rt_hip_scene_update_spheres(self._h, _centres(self.n_spheres, center, "center"), _centres(self.n_spheres, center1, "center1")),
+               self._L)
+
+    def table(self, name):
+        """rt_hip_scene_table (diagnostics): the bytes of one resident table (TABLES) as the kernels read it"""
+        need = C.c_size_t(0)
+        _check(self._L.rt_hip_scene_table(self._h, name.encode(), None, 0, C.byref(need)), self._L)
+        buf = C.create_string_buffer(max(1, need.value))
+        _check(self._L.rt_hip_scene_table(self._h, name.encode(), buf, need.value, C.byref(need)), self._L)
+        return buf.raw[:need.value]
 
     def set_option(self, key, value):
         _check(self._L.rt_hip_set_option(self._h, key.encode(), int(value)), self._L)
@@ -358,6 +390,12 @@ class HipGroup:
         sc = scene_ptr.contents
         self.width, self.height = sc.width, sc.height
         self.size = self._L.rt_hip_group_size(self._h)
+        self.n_spheres = sc.n_spheres
+
+    def update_spheres(self, center, center1=None):
+        """rt_hip_group_update_spheres: HipScene.update_spheres on every rank; no submitted frame may be uncollected"""
+        _check(self._L.rt_hip_group_update_spheres(self._h, _centres(self.n_spheres, center, "center"), _centres(self.n_spheres, center1, "center1")),
+               self._L)
 
     def set_option(self, key, value):
         _check(self._L.rt_hip_group_set_option(self._h, key.encode(), int(value)), self._L)

@@ -3,7 +3,7 @@
 
     python tools/codeobj_stats.py [extra hipcc flags ...]  > profiles/rNN_codeobj.txt
 
-Compiles rt_hip_api.hip for gfx950 with the product's flags (+ extras) and -save-temps into a scratch directory
+Compiles rt_hip_api.hip and rt_grid_build.hip (the device grid build) for gfx950 with the product's flags (+ extras) and -save-temps into a scratch directory
 and prints one line per kernel: VGPRs, SGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, code size, and a static
 instruction census of the megakernel instantiations (v_mov share: the copies at control-flow joins).
 No GPU needed."""
@@ -14,7 +14,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "rust-raytracer_amd", "csrc", "hip", "rt_hip_api.hip")
+SRCS = [os.path.join(ROOT, "rust-raytracer_amd", "csrc", "hip", f) for f in ("rt_hip_api.hip", "rt_grid_build.hip")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRT_WAVES_PER_EU=4"]
 
 
@@ -26,16 +26,21 @@ def demangle_mk(name):
                 + (", accum=1" if accum else "") + (", lens=1" if lens else "") + (", motion=1" if motion else "") + (", medium=1" if medium else "")
                 + (", solid=1" if solid else "") + ">")
     out = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    return out.split("(")[0] if out else name
+    return out.replace("(anonymous namespace)::", "").split("(")[0] if out else name
 
 
 def main():
     extra = sys.argv[1:]
-    with tempfile.TemporaryDirectory() as td:
-        subprocess.run(["hipcc", *FLAGS, *extra, "-shared", SRC, "-o", os.path.join(td, "x.so"), "-save-temps"], check=True, cwd=td,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        asm = open(os.path.join(td, "rt_hip_api-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
     print("# hipcc " + " ".join(FLAGS + extra))
+    for src in SRCS:
+        with tempfile.TemporaryDirectory() as td:
+            subprocess.run(["hipcc", *FLAGS, *extra, "-shared", src, "-o", os.path.join(td, "x.so"), "-save-temps"], check=True, cwd=td,
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            asm = open(os.path.join(td, os.path.splitext(os.path.basename(src))[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
+        report(asm)
+
+
+def report(asm):
     # metadata block: one YAML record per kernel
     meta = {}
     for rec in re.split(r"\n  - \.", asm[asm.index("amdhsa.kernels:"):]):
@@ -50,6 +55,8 @@ def main():
         line = (f"{demangle_mk(name):70s} vgpr {int(f['vgpr_count']):3d}  sgpr {int(f['sgpr_count']):3d}  vgpr_spill {int(f['vgpr_spill_count']):3d}  "
                 f"sgpr_spill {int(f['sgpr_spill_count']):3d}  scratch {int(f['private_segment_fixed_size']):4d} B/lane")
         b = bodies.get(name)
+        if "rtgb" in name:   # (the grid build's kernels: their static LDS too)
+            line += f"  lds {int(f.get('group_segment_fixed_size', 0)):5d} B"
         if b and "megakernel" in name:
             ins = re.findall(r"^\s+([vsd][a-z0-9_]+|scratch_\w+|global_\w+|flat_\w+|buffer_\w+)\b", b, flags=re.M)
             v = [i for i in ins if i.startswith("v_")]
