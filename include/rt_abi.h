@@ -338,8 +338,9 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * item lists: what a workgroup stages into LDS once per launch), "texel_bytes" (textures + sky as 4-byte texels in HBM);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
  * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
- * "last_kernel" (the megakernel instantiation that ran: accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 |
- * tables in LDS 1; thin lens 32; moving spheres 64; participating media 128; solid textures 256; -1 before the scene's first launch), "lens" (1:
+ * "last_kernel" (the key of the megakernel instantiation that ran, nine bits: solid textures 256 | participating media 128 |
+ * moving spheres 64 | thin lens 32 | accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 | tables in LDS 1; wide tables
+ * never go with tables in LDS, media or solid textures; -1 before the scene's first launch), "lens" (1:
  * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
  * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE).
  * -1 for an unknown key. */

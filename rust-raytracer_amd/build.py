@@ -53,25 +53,17 @@ def build_hip(force=False):
     # (linked against librt_host.so: rt_abi.h is one seam, and a handle of librt_hip.so resolves its host calls — the scene file
     #  and camera helpers — too)
     link = ["-L" + HERE, "-Wl,--no-as-needed", "-lrt_host", "-Wl,-rpath,$ORIGIN"]
-    # Two translation units per library, compiled side by side: rt_hip_api.hip (everything but the MOTION kernels) and
-    # rt_kernel_motion.hip (the 48 MOTION instantiations of the megakernel) — each ~1 minute of one core; one unit
-    # with all 96 instantiations was twice that.  Objects under build/ (git-ignored), then one link per library.
+    # HIP_UNITS per library, compiled side by side, each about a minute of one core (one unit with the megakernel's 288 instantiations
+    # was many times that).  Objects under build/ (git-ignored), then one link per library.
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    # (... and the 64 MEDIUM instantiations, DESIGN.md §15, in two more units of 32 each)
-    units = [("csrc/hip/rt_hip_api.hip", ["-DRT_MOTION_TU_SPLIT"]), ("csrc/hip/rt_kernel_motion.hip", []),
-             ("csrc/hip/rt_kernel_medium.hip", []), ("csrc/hip/rt_kernel_medium_motion.hip", [])]
-    # (... and the 128 SOLID instantiations, DESIGN.md §16, in four more units of 32 each)
-    units += [("csrc/hip/" + u, []) for u in SOLID_UNITS]
-    # (... and the device grid build of rt_hip_scene_update_spheres, DESIGN.md §17: a few small kernels)
-    units.append(("csrc/hip/rt_grid_build.hip", []))
     compiles, links = [], []
     for lib, extra in ((out, []), (probe, ["-DRT_TEST_PROBES"])):
         if not (force or _newer(lib, deps)):
             continue
         objs = []
-        for unit, defs in units:
-            obj = os.path.join(objdir, os.path.splitext(os.path.basename(unit))[0] + ("_probe" if extra else "") + ".o")
+        for name, unit, defs in HIP_UNITS:
+            obj = os.path.join(objdir, name + ("_probe" if extra else "") + ".o")
             compiles.append(["hipcc", *HIPFLAGS, *extra, *defs, "-c", os.path.join(HERE, unit), "-o", obj])
             objs.append(obj)
         links.append(["hipcc", *HIPFLAGS, "-shared", *objs, "-o", lib, *link])
@@ -96,10 +88,16 @@ def build_cli(force=False):
     return out
 
 
-SOLID_UNITS = ("rt_kernel_solid.hip", "rt_kernel_solid_motion.hip", "rt_kernel_solid_medium.hip", "rt_kernel_solid_medium_motion.hip")
-HIP_DEPS = ("csrc/hip/rt_hip_api.hip", "csrc/hip/rt_kernel.hip", "csrc/hip/rt_kernel_motion.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h",
-            "csrc/common/rt_atan2.h", "csrc/hip/rt_kernel_medium.hip", "csrc/hip/rt_kernel_medium_motion.hip", "csrc/common/rt_neg_log.h",
-            "csrc/common/rt_solid.h", "csrc/hip/rt_grid_build.h", "csrc/hip/rt_grid_build.hip") + tuple("csrc/hip/" + u for u in SOLID_UNITS)
+# The translation units of librt_hip.so as (object name, source, defines): rt_hip_api.hip with kernel set 0 (the megakernel instantiations
+# with key >> 6 == 0, csrc/hip/rt_kernel.hip) and everything else; rt_kernel_set.hip once for each of the sets 1 - 7 (MOTION, DESIGN.md §14;
+# MEDIUM, §15; SOLID, §16); the device grid build of rt_hip_scene_update_spheres (§17: a few small kernels).
+HIP_UNITS = ([("rt_hip_api", "csrc/hip/rt_hip_api.hip", ["-DRT_KERNEL_SET_SPLIT"])]
+             + [("rt_kernel_set%d" % k, "csrc/hip/rt_kernel_set.hip", ["-DRT_KERNEL_SET=%d" % k]) for k in range(1, 8)]
+             + [("rt_grid_build", "csrc/hip/rt_grid_build.hip", [])])
+# what the units are compiled from: every unit, and the files they include
+HIP_DEPS = tuple(dict.fromkeys(u for _, u, _ in HIP_UNITS)) + (
+    "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h", "csrc/hip/rt_grid_build.h",
+    "csrc/common/rt_atan2.h", "csrc/common/rt_neg_log.h", "csrc/common/rt_solid.h")
 
 
 def kernel_src_hash():
@@ -109,7 +107,7 @@ def kernel_src_hash():
     h = hashlib.sha1()
     for f in _srcs(*HIP_DEPS) + [os.path.join(ROOT, "include/rt_abi.h")]:
         h.update(open(f, "rb").read())
-    h.update(" ".join(HIPFLAGS).encode())
+    h.update((" ".join(HIPFLAGS) + repr(HIP_UNITS)).encode())
     return h.hexdigest()[:12]
 
 

@@ -194,13 +194,13 @@ struct DevScene {
   const SphereGeom* large_geom;  // [n_large] their geometry, packed in the same order (streamed by scalar loads)
   const MatCore* matc;         // [n_spheres]
   // thin lens (rt_hip_set_lens): the camera's unit vectors u and v and the lens radius aperture / 2; lens_r == 0 is the
-  // pinhole.  Read only by the LENS instantiations of the megakernel and by rt_aov_lens.
+  // pinhole.  Read only by the LENS instantiations of the megakernel and of rt_aov.
   double lens_u[3], lens_v[3], lens_r;
   // motion blur (rt_hip_scene_create_moving): [n_spheres][4] {dv = center1 - center, 0} (a zero component stored as -0.0);
-  // null for a static scene.  Read only by the MOTION instantiations of the megakernel and by rt_aov_motion / rt_aov_lens_motion.
+  // null for a static scene.  Read only by the MOTION instantiations of the megakernel and of rt_aov.
   const double* motion;
   // participating media: [n_spheres] the density of a Medium sphere, 0.0 for any other; null for a scene without one.
-  // Resident once and shared by views like `motion`.  Read only by the MEDIUM instantiations of the megakernel and the rt_aov*_medium kernels.
+  // Resident once and shared by views like `motion`.  Read only by the MEDIUM instantiations of the megakernel and of rt_aov.
   const double* medium;
 };
 

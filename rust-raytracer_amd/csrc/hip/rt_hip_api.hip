@@ -37,6 +37,12 @@ int fail(int code, const std::string& m) { g_err = m; return code; }
       return fail(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                   \
   } while (0)
 
+// Wide tables have no kernel for media or solid textures (rtk::kernel_key_valid): such a scene is refused where its tables are made.
+int check_wide_tables(bool wide, bool media, bool solids) {
+  if (rtk::kernel_key_valid((wide ? rtk::KEY_WIDE : 0) | (media ? rtk::KEY_MEDIUM : 0) | (solids ? rtk::KEY_SOLID : 0))) return RT_OK;
+  return fail(RT_ERR_UNSUPPORTED, std::string(media ? "participating media" : "solid textures") + " in a scene with wide tables (more than 65 535 spheres)");
+}
+
 }  // namespace
 
 struct RtHipScene;
@@ -351,8 +357,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   rtc::HostTables t;
   std::string why = rtc::build_tables(*scene, t, false, center1);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
-  if (t.n_media && t.grid.wide) return fail(RT_ERR_UNSUPPORTED, "participating media in a scene with wide tables (more than 65 535 spheres)");
-  if (t.n_solids && t.grid.wide) return fail(RT_ERR_UNSUPPORTED, "solid textures in a scene with wide tables (more than 65 535 spheres)");
+  if (const int refused = check_wide_tables(t.grid.wide, t.n_media, t.n_solids)) return refused;
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
   pc.mark("scene.texels_rgbx");
@@ -472,79 +477,33 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
   return fail(RT_ERR_INVALID, std::string("unknown option ") + key);
 }
 
-#ifdef RT_MOTION_TU_SPLIT  // (the product build: rt_kernel_motion.hip compiles the MOTION half of the kernel set beside this file)
-#define RT_MOTION_EXTERN(HL, S, LDS, WIDE, A, LE) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, WIDE, A, LE, true>(rtk::KArgs);
-RT_MOTION_INSTANTIATIONS(RT_MOTION_EXTERN)
-// (... and rt_kernel_medium.hip / rt_kernel_medium_motion.hip the MEDIUM set)
-#define RT_MEDIUM_EXTERN(HL, S, LDS, A, LE, MO) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, false, A, LE, MO, true>(rtk::KArgs);
-RT_MEDIUM_INSTANTIATIONS(RT_MEDIUM_EXTERN, false)
-RT_MEDIUM_INSTANTIATIONS(RT_MEDIUM_EXTERN, true)
-// (... and the four rt_kernel_solid*.hip the SOLID set)
-#define RT_SOLID_EXTERN(HL, S, LDS, A, LE, MO, ME) extern template __global__ void rtk::rt_megakernel<HL, S, LDS, false, A, LE, MO, ME, true>(rtk::KArgs);
-RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, false, false)
-RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, true, false)
-RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, false, true)
-RT_SOLID_INSTANTIATIONS(RT_SOLID_EXTERN, true, true)
-#endif
-
 namespace {
 
-// The MEDIUM instantiations have the key of their static twin | 128 and a table of their own behind the first one:
-// the first 128 entries are made exactly as they were.
-// The megakernel instantiations and their keys: MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1 (lights, every
-// albedo in [0, 1], tables in LDS, wide cell tables, accumulating, thin lens, moving spheres).  Wide tables are never staged in LDS
-// (plan_lds): those 32 keys have no instantiation.
-using Megakernel = void (*)(rtk::KArgs);
-template <int K> Megakernel megakernel_of_key() {
-  if constexpr ((K & 9) == 9) return nullptr;
-  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, (K & 8) != 0, (K & 16) != 0, (K & 32) != 0, (K & 64) != 0>;
-}
-// J counts up over (MOTION, LENS, ACCUM, WIDE, HL, LDS, SIMPLE); the compiler emits the kernels in the reverse of that order, the
-// order they have always had, which keeps the code object's layout (and tools/codeobj_stats.py's report) as it was
-template <int J> constexpr int key_at = (J & ~3) | ((J & 1) << 1) | ((J >> 1) & 1);
-template <int... J> std::array<Megakernel, 128> megakernels(std::integer_sequence<int, J...>) {
-  std::array<Megakernel, 128> t{};
-  ((t[key_at<J>] = megakernel_of_key<key_at<J>>()), ...);
-  return t;
-}
-template <int K> Megakernel medium_megakernel_of_key() {  // K = the key without the MEDIUM bit; wide tables have no MEDIUM kernel
-  if constexpr ((K & 8) != 0) return nullptr;
-  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, false, (K & 16) != 0, (K & 32) != 0, (K & 64) != 0, true>;
-}
-template <int... K> std::array<Megakernel, 128> medium_megakernels(std::integer_sequence<int, K...>) {
-  std::array<Megakernel, 128> t{};
-  ((t[K] = medium_megakernel_of_key<K>()), ...);
-  return t;
-}
-// The SOLID instantiations have the key of their twin | 256 and a table of their own behind the two above, indexed by
-// the key without the SOLID bit (MEDIUM 128 included); wide tables have no SOLID kernel.
-template <int K> Megakernel solid_megakernel_of_key() {
-  if constexpr ((K & 8) != 0) return nullptr;
-  else return rtk::rt_megakernel<(K & 4) != 0, (K & 2) != 0, (K & 1) != 0, false, (K & 16) != 0, (K & 32) != 0, (K & 64) != 0, (K & 128) != 0, true>;
-}
-template <int... K> std::array<Megakernel, 256> solid_megakernels(std::integer_sequence<int, K...>) {
-  std::array<Megakernel, 256> t{};
-  ((t[K] = solid_megakernel_of_key<K>()), ...);
+// The megakernel instantiations by key (rt_kernel.hip): set 0, which this unit always compiles, and the slices of the sets 1 - 7 side by
+// side.  A null entry is a key that is not valid.
+using rtk::Megakernel;
+template <int... SET> std::array<Megakernel, rtk::KERNEL_KEYS> kernel_table(std::integer_sequence<int, SET...>) {
+  const rtk::KernelSetTable sets[] = {rtk::kernel_set_table<0>(std::make_integer_sequence<int, rtk::KERNEL_SET_KEYS>()), rtk::kernel_set<SET + 1>()...};
+  std::array<Megakernel, rtk::KERNEL_KEYS> t;
+  for (int key = 0; key < rtk::KERNEL_KEYS; ++key) {
+    t[key] = sets[key / rtk::KERNEL_SET_KEYS][key % rtk::KERNEL_SET_KEYS];
+    if ((t[key] != nullptr) != rtk::kernel_key_valid(key)) std::abort();  // (holds while megakernel_of_key decides by this predicate: the table cannot drift from it unnoticed)
+  }
   return t;
 }
 struct Kernel { int key = -1; Megakernel fn = nullptr; };
 int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
-  static const std::array<Megakernel, 128> table = megakernels(std::make_integer_sequence<int, 128>());
-  if (wide && lds_tables) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
-  out->key = (s->dev.motion ? 64 : 0) | (s->dev.lens_r != 0.0 ? 32 : 0) | (accum ? 16 : 0) | (wide ? 8 : 0) | (has_lights ? 4 : 0) | (s->res->simple_colour ? 2 : 0) | (lds_tables ? 1 : 0);
-  out->fn = table[out->key];
-  if (s->dev.medium) {
-    static const std::array<Megakernel, 128> medium_table = medium_megakernels(std::make_integer_sequence<int, 128>());
-    if (wide) return fail(RT_ERR_UNSUPPORTED, "participating media with wide tables");
-    out->fn = medium_table[out->key];
-    out->key |= 128;
+  static const std::array<Megakernel, rtk::KERNEL_KEYS> table = kernel_table(std::make_integer_sequence<int, rtk::KERNEL_SETS - 1>());
+  const int key = (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
+                  (s->dev.lens_r != 0.0 ? rtk::KEY_LENS : 0) | (accum ? rtk::KEY_ACCUM : 0) | (wide ? rtk::KEY_WIDE : 0) | (has_lights ? rtk::KEY_HL : 0) |
+                  (s->res->simple_colour ? rtk::KEY_SIMPLE : 0) | (lds_tables ? rtk::KEY_LDS : 0);
+  if (!rtk::kernel_key_valid(key)) {
+    if (key & rtk::KEY_LDS) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
+    if (key & rtk::KEY_MEDIUM) return fail(RT_ERR_UNSUPPORTED, "participating media with wide tables");
+    return fail(RT_ERR_UNSUPPORTED, "solid textures with wide tables");
   }
-  if (s->res->n_solids) {
-    static const std::array<Megakernel, 256> solid_table = solid_megakernels(std::make_integer_sequence<int, 256>());
-    if (wide) return fail(RT_ERR_UNSUPPORTED, "solid textures with wide tables");
-    out->fn = solid_table[out->key];
-    out->key |= 256;
-  }
+  out->key = key;
+  out->fn = table[key];
   return RT_OK;
 }
 
@@ -1269,6 +1228,11 @@ int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32
   }
   return RT_OK;
 }
+// The feature kernels by the four feature bits of the megakernel's key, (SOLID | MEDIUM | MOTION | LENS) / LENS
+using AovKernel = void (*)(const rtc::DevScene, uint32_t, float4*);
+template <int... F> std::array<AovKernel, 16> aov_kernels(std::integer_sequence<int, F...>) {
+  return {rtk::rt_aov<(F & 1) != 0, (F & 2) != 0, (F & 4) != 0, (F & 8) != 0>...};
+}
 }  // namespace
 
 extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32_t n_samples, void* d_aov, void* stream) {
@@ -1281,22 +1245,10 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   if (!d_aov) return fail(RT_ERR_INVALID, "null AOV buffer");
   if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
   RT_HIP_TRY(hipSetDevice(s->device));
-  const bool lens = s->dev.lens_r != 0.0;
-  if (s->res->n_solids) {  // (LENS x MOTION x MEDIUM)
-    const int v = (lens ? 4 : 0) | (s->dev.motion ? 2 : 0) | (s->dev.medium ? 1 : 0);
-    void (*k)(const rtc::DevScene, uint32_t, float4*) =
-        v == 0 ? rtk::rt_aov_solid<false, false, false> : v == 1 ? rtk::rt_aov_solid<false, false, true> : v == 2 ? rtk::rt_aov_solid<false, true, false>
-        : v == 3 ? rtk::rt_aov_solid<false, true, true> : v == 4 ? rtk::rt_aov_solid<true, false, false> : v == 5 ? rtk::rt_aov_solid<true, false, true>
-        : v == 6 ? rtk::rt_aov_solid<true, true, false> : rtk::rt_aov_solid<true, true, true>;
-    hipLaunchKernelGGL(k, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
-  }
-  else if (s->dev.medium) {
-    auto k = s->dev.motion ? (lens ? rtk::rt_aov_lens_motion_medium : rtk::rt_aov_motion_medium) : (lens ? rtk::rt_aov_lens_medium : rtk::rt_aov_medium);
-    hipLaunchKernelGGL(k, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
-  }
-  else if (s->dev.motion) hipLaunchKernelGGL(lens ? rtk::rt_aov_lens_motion : rtk::rt_aov_motion, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
-  else if (lens) hipLaunchKernelGGL(rtk::rt_aov_lens, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
-  else hipLaunchKernelGGL(rtk::rt_aov, px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  static const std::array<AovKernel, 16> table = aov_kernels(std::make_integer_sequence<int, 16>());
+  const int features = (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
+                       (s->dev.lens_r != 0.0 ? rtk::KEY_LENS : 0);
+  hipLaunchKernelGGL(table[features / rtk::KEY_LENS], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -1540,8 +1492,7 @@ int scene_update(RtHipScene* s, const double* center, const double* center1, boo
   if (!j.all_large && !wide && (cnt.max_count > rtc::CELL_MAX_COUNT || cnt.n_items >= rtc::CELL_START_MASK)) wide = true;
   pc.mark("update.count_kernels_and_readback");
   j.G.n_items = (uint32_t)cnt.n_items; j.G.n_large = (uint32_t)cnt.n_large; j.G.wide = (!j.all_large && wide) ? 1u : 0u;
-  if (r.n_media && j.G.wide) return (fail(RT_ERR_UNSUPPORTED, "participating media in a scene with wide tables (more than 65 535 spheres)"));
-  if (r.n_solids && j.G.wide) return (fail(RT_ERR_UNSUPPORTED, "solid textures in a scene with wide tables (more than 65 535 spheres)"));
+  if ((rc = check_wide_tables(j.G.wide, r.n_media, r.n_solids)) != RT_OK) return rc;
   if ((rc = room(r.spare.cell_word, (size_t)j.G.n_cells * (j.G.wide ? 16u : 8u))) != RT_OK || (rc = room(r.spare.cell_items, (size_t)j.G.n_items * (j.G.wide ? 4u : 2u))) != RT_OK ||
       (rc = room(gb.raw_items, (size_t)j.G.n_items * 4)) != RT_OK || (rc = room(gb.raw_cell, (size_t)j.G.n_items * 4)) != RT_OK ||
       (rc = room(r.spare.large, (size_t)j.G.n_large * 4)) != RT_OK || (rc = room(r.spare.large_geom, (size_t)j.G.n_large * sizeof(rtc::SphereGeom))) != RT_OK)

@@ -25,6 +25,9 @@
 //   * Philox4x32-10 per lane, addressed by (pixel, sample, node, slot).
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <utility>
+
 #include "rt_core.h"
 
 namespace rtk {
@@ -1122,36 +1125,36 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
   }
 }
 
-// The 48 MOTION instantiations (the static 48 with MOTION = true), as X(HL, SIMPLE, LDS_TABLES, WIDE, ACCUM, LENS): wide tables are never
-// staged in LDS.  The product build compiles them in a translation unit of their own, rt_kernel_motion.hip, beside rt_hip_api.hip
-// (build.py, -DRT_MOTION_TU_SPLIT): the two halves build in parallel instead of one twice as long.
-#define RT_MOTION_TABLES(X, HL, S, A, LE) X(HL, S, false, false, A, LE) X(HL, S, true, false, A, LE) X(HL, S, false, true, A, LE)
-#define RT_MOTION_MODES(X, HL, S) RT_MOTION_TABLES(X, HL, S, false, false) RT_MOTION_TABLES(X, HL, S, true, false) \
-                                  RT_MOTION_TABLES(X, HL, S, false, true) RT_MOTION_TABLES(X, HL, S, true, true)
-#define RT_MOTION_INSTANTIATIONS(X) RT_MOTION_MODES(X, false, false) RT_MOTION_MODES(X, false, true) RT_MOTION_MODES(X, true, false) \
-                                    RT_MOTION_MODES(X, true, true)
+// The key of an instantiation, one bit per template argument (rt_hip_scene_query "last_kernel", include/rt_abi.h), and its kernel set,
+// key >> 6 = (SOLID, MEDIUM, MOTION): the translation unit that compiles it (build.py; rt_kernel_set.hip).
+enum : int { KEY_LDS = 1, KEY_SIMPLE = 2, KEY_HL = 4, KEY_WIDE = 8, KEY_ACCUM = 16, KEY_LENS = 32, KEY_MOTION = 64, KEY_MEDIUM = 128, KEY_SOLID = 256,
+             KERNEL_KEYS = 512, KERNEL_SET_KEYS = 64, KERNEL_SETS = KERNEL_KEYS / KERNEL_SET_KEYS };
+// The keys that have an instantiation (the host's statement of rt_megakernel's static_asserts): 288 of the 512 — 48 in each of the
+// sets 0 and 1, 32 in each of the sets 2 - 7.
+constexpr bool kernel_key_valid(int key) {
+  return key >= 0 && key < KERNEL_KEYS && !((key & KEY_WIDE) && (key & (KEY_LDS | KEY_MEDIUM | KEY_SOLID)));
+}
+using Megakernel = void (*)(KArgs);
+template <int K> Megakernel megakernel_of_key() {  // null exactly where K is not valid
+  if constexpr (!kernel_key_valid(K)) return nullptr;
+  else return rt_megakernel<(K & KEY_HL) != 0, (K & KEY_SIMPLE) != 0, (K & KEY_LDS) != 0, (K & KEY_WIDE) != 0, (K & KEY_ACCUM) != 0, (K & KEY_LENS) != 0,
+                            (K & KEY_MOTION) != 0, (K & KEY_MEDIUM) != 0, (K & KEY_SOLID) != 0>;
+}
+// One set's slice of the key-indexed table: entry I belongs to key SET * 64 + I.  Instantiating it instantiates the set's kernels in this
+// translation unit.
+using KernelSetTable = std::array<Megakernel, KERNEL_SET_KEYS>;
+template <int SET, int... I> KernelSetTable kernel_set_table(std::integer_sequence<int, I...>) {
+  return KernelSetTable{megakernel_of_key<SET * KERNEL_SET_KEYS + I>()...};
+}
+// (internal, not part of the ABI.  The product build compiles the sets side by side, each ~1 minute of one core: set 0 with everything
+//  else in rt_hip_api.hip, built with -DRT_KERNEL_SET_SPLIT, which only declares this function; sets 1 - 7 in rt_kernel_set.hip, built once
+//  per set with -DRT_KERNEL_SET=<set>, which instantiates it for that set.  Without either flag rt_hip_api.hip compiles all eight.)
+template <int SET> __attribute__((visibility("hidden"))) KernelSetTable kernel_set();
+#ifndef RT_KERNEL_SET_SPLIT
+template <int SET> KernelSetTable kernel_set() { return kernel_set_table<SET>(std::make_integer_sequence<int, KERNEL_SET_KEYS>()); }
+#endif
 
-// The 64 MEDIUM instantiations, as X(HL, SIMPLE, LDS_TABLES, ACCUM, LENS, MOTION): what a scene with a medium can select —
-// lit and unlit, both colour maps, LDS and L2 tables, accumulating, lens, motion; never wide tables.  Translation units of their own
-// (rt_kernel_medium.hip: the static half; rt_kernel_medium_motion.hip: the moving half), declared `extern template` in rt_hip_api.hip
-// under -DRT_MOTION_TU_SPLIT like the MOTION set.
-#define RT_MEDIUM_TABLES(X, HL, S, A, LE, MO) X(HL, S, false, A, LE, MO) X(HL, S, true, A, LE, MO)
-#define RT_MEDIUM_MODES(X, HL, S, MO) RT_MEDIUM_TABLES(X, HL, S, false, false, MO) RT_MEDIUM_TABLES(X, HL, S, true, false, MO) \
-                                      RT_MEDIUM_TABLES(X, HL, S, false, true, MO) RT_MEDIUM_TABLES(X, HL, S, true, true, MO)
-#define RT_MEDIUM_INSTANTIATIONS(X, MO) RT_MEDIUM_MODES(X, false, false, MO) RT_MEDIUM_MODES(X, false, true, MO) RT_MEDIUM_MODES(X, true, false, MO) \
-                                        RT_MEDIUM_MODES(X, true, true, MO)
-
-// The 128 SOLID instantiations, as X(HL, SIMPLE, LDS_TABLES, ACCUM, LENS, MOTION, MEDIUM): what a scene with a Checker or
-// Noise sphere can select — everything a MEDIUM scene can, with and without media; never wide tables.  Four translation units of 32 each
-// (rt_kernel_solid.hip, rt_kernel_solid_motion.hip, rt_kernel_solid_medium.hip, rt_kernel_solid_medium_motion.hip), declared
-// `extern template` in rt_hip_api.hip under -DRT_MOTION_TU_SPLIT like the MOTION and MEDIUM sets.
-#define RT_SOLID_TABLES(X, HL, S, A, LE, MO, ME) X(HL, S, false, A, LE, MO, ME) X(HL, S, true, A, LE, MO, ME)
-#define RT_SOLID_MODES(X, HL, S, MO, ME) RT_SOLID_TABLES(X, HL, S, false, false, MO, ME) RT_SOLID_TABLES(X, HL, S, true, false, MO, ME) \
-                                         RT_SOLID_TABLES(X, HL, S, false, true, MO, ME) RT_SOLID_TABLES(X, HL, S, true, true, MO, ME)
-#define RT_SOLID_INSTANTIATIONS(X, MO, ME) RT_SOLID_MODES(X, false, false, MO, ME) RT_SOLID_MODES(X, false, true, MO, ME) \
-                                           RT_SOLID_MODES(X, true, false, MO, ME) RT_SOLID_MODES(X, true, true, MO, ME)
-
-#ifndef RT_KERNEL_MOTION_TU  // (rt_kernel_motion.hip takes the megakernel template alone; everything below is rt_hip_api.hip's)
+#ifndef RT_KERNEL_SET  // (rt_kernel_set.hip takes the megakernel template alone; everything below is rt_hip_api.hip's)
 // Launched once when a scene is created: the runtime loads a module's code object onto the device with the first launch of ANY
 // of its kernels — milliseconds that would otherwise sit inside the first frame.
 __global__ void rt_warm_up() {}
@@ -1297,7 +1300,7 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
 // --------------------------------------------------------------------------- denoising
 // Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
 // 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
-template <bool LENS, bool MOTION = false, bool MEDIUM = false, bool SOLID = false>
+template <bool LENS, bool MOTION, bool MEDIUM, bool SOLID>
 __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float4* __restrict__ out) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x >= sc.width || y >= sc.height) return;
@@ -1308,20 +1311,11 @@ __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float
   out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
   out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
 }
-__global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false>(sc, n, out); }
-// (the thin-lens camera, DESIGN.md §13: the same first ray as the LENS megakernels)
-__global__ __launch_bounds__(256) void rt_aov_lens(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true>(sc, n, out); }
-// (motion blur, DESIGN.md §14: the first hit at each sample's shutter time, as the MOTION megakernels trace it)
-__global__ __launch_bounds__(256) void rt_aov_motion(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, true>(sc, n, out); }
-__global__ __launch_bounds__(256) void rt_aov_lens_motion(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, true>(sc, n, out); }
-// (participating media, DESIGN.md §15: the first hit may lie inside a medium, found as the MEDIUM megakernels find it)
-__global__ __launch_bounds__(256) void rt_aov_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, false, true>(sc, n, out); }
-__global__ __launch_bounds__(256) void rt_aov_lens_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, false, true>(sc, n, out); }
-__global__ __launch_bounds__(256) void rt_aov_motion_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<false, true, true>(sc, n, out); }
-__global__ __launch_bounds__(256) void rt_aov_lens_motion_medium(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<true, true, true>(sc, n, out); }
-// (solid textures, DESIGN.md §16: a first hit on a Checker or Noise sphere reports the colour evaluated there; LENS x MOTION x MEDIUM)
-template <bool LENS, bool MOTION, bool MEDIUM>
-__global__ __launch_bounds__(256) void rt_aov_solid(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<LENS, MOTION, MEDIUM, true>(sc, n, out); }
+// LENS: the same first ray as the LENS megakernels.  MOTION (§14): the first hit at each sample's shutter time, as the
+// MOTION megakernels trace it.  MEDIUM (§15): the first hit may lie inside a medium, found as the MEDIUM megakernels find it.  SOLID (§16): a
+// first hit on a Checker or Noise sphere reports the colour evaluated there.
+template <bool LENS, bool MOTION, bool MEDIUM, bool SOLID>
+__global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<LENS, MOTION, MEDIUM, SOLID>(sc, n, out); }
 
 // One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
 // ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two
@@ -1448,6 +1442,6 @@ __global__ void rt_quot_probe(const double* x, const double* y, double* out_quot
   if (out_div) out_div[i] = rt_div_inrange(x[i], y[i]);
 }
 #endif  // RT_TEST_PROBES
-#endif  // !RT_KERNEL_MOTION_TU
+#endif  // !RT_KERNEL_SET
 
 }  // namespace rtk

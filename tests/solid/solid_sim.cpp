@@ -1,6 +1,6 @@
 // CPU build of the solid textures (tests/test_solid_cpu.py; tests only): csrc/common/rt_solid.h built for the host, point by point, and
 // the per-lane code of the SOLID kernels (rt_core.h scatter<MEDIUM, true> through lane_shade, aov_pixel's SOLID arm) one lane at a
-// time on tables rt_tables.h built — what the SOLID megakernels and rt_aov_solid kernels run, without a GPU.
+// time on tables rt_tables.h built — what the SOLID megakernels and the SOLID rt_aov kernels run, without a GPU.
 #include <cstdint>
 #include <cstring>
 

@@ -271,7 +271,7 @@ def test_first_hit_aovs_and_denoise(pkg, abi, oracle, host, torch_cuda, moving, 
     """the feature buffers of a medium scene are MediumMini's first hits (a medium: its albedo, normal 0, 1 / t); the denoiser runs"""
     torch = torch_cuda
     sc, c1, lens = _load(host, _cfg(_unlit_objs(moving), lens=LENS_KEYS if lens_on else None), 24, 16, 4, 8, seed=3)
-    assert (lens is not None) == lens_on     # (the four rt_aov*_medium kernels: pinhole / lens x static / moving)
+    assert (lens is not None) == lens_on     # (the four MEDIUM rt_aov kernels without SOLID: pinhole / lens x static / moving)
     gs = _hip_scene(pkg, sc, c1, lens)
     aov = torch.zeros((gs.height, gs.width, 8), dtype=torch.float32, device="cuda:0")
     gs.render_aovs(4, aov.data_ptr(), None, _stream(torch))

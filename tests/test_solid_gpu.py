@@ -262,6 +262,23 @@ def test_first_hit_aovs_and_denoise(pkg, abi, oracle, host, torch_cuda, moving, 
     gs.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("moving,lens_on", [(False, False), (True, False), (False, True), (True, True)])
+def test_first_hit_aovs_with_solids_and_a_medium(pkg, abi, oracle, host, torch_cuda, moving, lens_on):
+    """the four rt_aov<LENS, MOTION, true, true> kernels, which no other test launches: the feature buffers of a scene with solids and a
+    medium against the first hits of SolidMini — the restatement test_denoise.py compares with (mini_oracle.Mini), which by itself
+    knows neither kind of sphere, extended by MediumMini and SolidMini — under test_denoise.py's comparison: bit for bit"""
+    from test_denoise import _aovs, _check_aovs
+    sc, c1, lens = _load(host, _cfg(_unlit_objs(moving, medium=True), lens=LENS_KEYS if lens_on else None), 24, 16, 2, 8, seed=3)
+    gs = _hip_scene(pkg, sc, c1, lens)
+    assert gs.query("solids") > 0 and gs.query("media") > 0 and (gs.query("motion") > 0) == moving and gs.query("lens") == lens_on
+    got = _aovs(torch_cuda, gs, 2).cpu().numpy()
+    gs.close()
+    _check_aovs(got, _mini(oracle, abi, sc, c1, lens).aovs(2), "solids and a medium", 2)
+    # some pixels' first hits all lie inside the medium (fully covered, zero normal): the frame tells the MEDIUM kernels from the others
+    assert ((got[..., 7] == 1.0) & (np.abs(got[..., 4:7]).sum(-1) == 0.0)).any()
+
+
 WHITE = (C.c_uint8 * 3)(255, 255, 255)      # a 1 x 1 white sky texture: every miss returns 0.7 x (1, 1, 1), whatever its direction
 
 
