@@ -478,6 +478,69 @@ int rt_hip_render_aovs(RtHipScene*, const RtRowTiles* tiles, uint32_t n_samples,
 int rt_hip_denoise(RtHipScene*, const RtRowTiles* tiles, const void* d_linear, const void* d_aov, uint32_t iterations, float sigma_color,
                    float sigma_normal, float sigma_albedo, float sigma_inv_depth, void* d_out_linear, void* d_out_rgb8, void* stream);
 int rt_hip_refine_to_host_denoised(RtHipScene*, uint32_t sample_count, uint32_t iterations, uint8_t* out_rgb8, RtStats* stats);
+/* Temporal denoising for animations: each frame's colour is blended with the previous frame's accumulated colour,
+ * fetched where the pixel's first-hit surface was on screen one frame ago.  Whole frames only.
+ *
+ * HISTORY: per pixel 4 f32 (16 B) {r, g, b, n}, rows x width packed row-major, 16-byte aligned: the accumulated linear radiance and
+ * the number of frames in it (0: never reuse this pixel).  A CAMERA is 12 doubles: origin[3], lower_left[3], horizontal[3],
+ * vertical[3], the vectors of rt_hip_set_camera.
+ *
+ * rt_hip_reproject: one step.  d_linear (f32 x 3, as rt_hip_resolve writes it) and d_aov (the AOV record above) are this frame's,
+ * rendered with the scene's current camera; d_prev_history, d_prev_aov and prev_camera the previous frame's; d_out_history receives
+ * the new history.  Per pixel (x, y) of the w x h frame, with dot(p, q) = (p0 q0 + p1 q1) + p2 q2 and
+ * cross(p, q) = (p1 q2 - p2 q1, p2 q0 - p0 q2, p0 q1 - p1 q0), every operation one IEEE operation in exactly this order, no
+ * contraction (f64 up to the tap positions, f32 from the weights on):
+ *   c = the pixel's colour, g its record.  A NaN channel in c: out = c, n = 0, done.
+ *   Pixel centre (the camera ray of rt_hip_render with both jitters 0.5): u = (x + 0.5) / (w - 1), v = (h - (y + 0.5)) / (h - 1),
+ *     d = ((lower_left + horizontal u) + vertical v) - origin, per component.
+ *   Surface point: hit = g.coverage > 0 and g.inv_depth > 0.  A hit: t = (f64)coverage / (f64)inv_depth,
+ *     q = (origin + d t) - origin'.  Else (sky): q = d, a point at infinity.   (' marks the previous camera)
+ *   Into the previous camera: A = lower_left' - origin', n0 = cross(horizontal', vertical'), n1 = cross(vertical', A),
+ *     n2 = cross(A, horizontal'), det = dot(A, n0), a = dot(q, n0) / det, b = dot(q, n1) / det, e = dot(q, n2) / det.
+ *     No history unless a > 0 and a, b, e are finite.  fx = (b / a) (w - 1) - 0.5, fy = (h - (e / a) (h - 1)) - 0.5.
+ *     No history unless -1 <= fx < w and -1 <= fy < h (otherwise, or for a NaN, every tap lies outside the frame).
+ *   Taps: x0 = floor(fx), y0 = floor(fy), wx = (f32)(fx - x0), wy = (f32)(fy - y0); tap (i, j), j = 0, 1 outer, i = 0, 1 inner, is
+ *     pixel (x0 + i, y0 + j) with weight W = (i ? wx : 1 - wx) (j ? wy : 1 - wy).
+ *   ez = (f32)((f64)coverage / a) for a hit, 0 for sky: the inv_depth the previous frame recorded for this surface.
+ *   A tap counts iff it lies inside the frame; its history has n > 0 and no NaN in r, g, b; |normal' - normal|^2 <= tau_n and
+ *     |albedo' - albedo|^2 <= tau_a (each (d0 d0 + d1 d1) + d2 d2 of the f32 differences); and dz dz <= (tau_z ez) (tau_z ez) with
+ *     dz = inv_depth' - ez.  (A comparison with a NaN fails: the tap does not count.  Sky matches only sky.)
+ *   Over the taps that count, in tap order, from 0: s_c = s_c + W H'_c per channel, sw = sw + W, sn = sn + W H'_n.
+ *   History iff sw > 0: hist_c = s_c / sw, m = sn / sw + 1, n = m < n_max ? m : n_max, r = 1 / n,
+ *     alpha = alpha_min > r ? alpha_min : r, out_c = hist_c + alpha (c_c - hist_c).  No history: out = c, n = 1.
+ * Asynchronous on `stream`; reads the scene's size and camera only; writes no caller buffer but the output.  RT_ERR_INVALID, and
+ * nothing is enqueued, for: a NULL buffer or camera; d_linear not 4-byte aligned, another buffer not 16-byte aligned; an output that
+ * overlaps an input; a threshold that is not finite and >= 0; alpha_min outside [0, 1]; n_max not >= 1 (infinity is allowed).
+ *
+ * rt_hip_render_frame_temporal_to_host: frame `frame_index` of an animation on one resident scene, blocking.  In this order:
+ * samples [b, b + N) of every pixel, N = samples_per_pixel, b = (frame_index mod F) N, F = floor((2^23 - 1) / N) — consecutive frames
+ * trace different samples, frame 0 the one-shot frame's — into an accumulator of its own; the resolve to linear f32; the AOVs of
+ * the current view over samples [0, min(RT_DENOISE_AOV_SAMPLES, N)); rt_hip_reproject against the history, AOVs and camera the
+ * previous call left (none: every pixel starts at n = 1); rt_hip_denoise (`iterations` passes, the default sigmas) over the NEW
+ * history's r, g, b into RGB8.  What is kept for the next call is the colour BEFORE the spatial filter, so the filter's bias is never
+ * fed back.  The camera (rt_hip_set_camera, rt_hip_set_lens) and the spheres (rt_hip_scene_update_spheres) may change between calls;
+ * a moved sphere is handled by the tap test alone, there are no per-object motion vectors.  History, guides and accumulator
+ * (width*height*120 bytes: 24 + 2 x 16 + 2 x 32) belong to the scene: allocated at first use, freed with it; the progressive accumulator is untouched.
+ * Frame 0 of a scene without history is rt_hip_refine_to_host_denoised(N, iterations) of a fresh scene, byte for byte.
+ * More than 8 iterations or N above 2^23 - 1: RT_ERR_UNSUPPORTED.  stats: the frame's megakernel pass.
+ * rt_hip_temporal_configure: alpha_min, n_max and the thresholds the host form passes to rt_hip_reproject (checked as there; the
+ * history stays).  A scene starts with the RT_TEMPORAL_* values below: the best point of a 360-point sweep over a 3-degree-per-frame orbit of
+ * two scenes full of mirrors and glass, which is why alpha_min is so high (profiles/temporal_bench.json).
+ * rt_hip_temporal_reset: drop the history and free its buffers; the next frame starts over.
+ * rt_hip_temporal_history: the history the last frame left (width*height*4 f32) into a host buffer, blocking; RT_ERR_INVALID if
+ * the scene holds none. */
+#define RT_TEMPORAL_ALPHA_MIN 0.5f
+#define RT_TEMPORAL_N_MAX 8.0f
+#define RT_TEMPORAL_TAU_NORMAL 0.02f
+#define RT_TEMPORAL_TAU_ALBEDO 0.3f
+#define RT_TEMPORAL_TAU_INV_DEPTH 0.02f
+int rt_hip_reproject(RtHipScene*, const void* d_linear, const void* d_aov, const void* d_prev_history, const void* d_prev_aov,
+                     const double prev_camera[12], float alpha_min, float n_max, float tau_n, float tau_a, float tau_z, void* d_out_history,
+                     void* stream);
+int rt_hip_render_frame_temporal_to_host(RtHipScene*, uint32_t frame_index, uint32_t iterations, uint8_t* out_rgb8, RtStats* stats);
+int rt_hip_temporal_configure(RtHipScene*, float alpha_min, float n_max, float tau_n, float tau_a, float tau_z);
+int rt_hip_temporal_reset(RtHipScene*);
+int rt_hip_temporal_history(RtHipScene*, float* out_history);
 /* A frame over the GPUs of one node, scene resident (the parallel loop of raytracer.rs:254-262 spread over devices;
  * animation: README.md:43-57).  n_gpus = 0 takes scene->n_gpus, then RT_GPUS, then 1.  Each rank renders
  * interleaved 2-scanline tiles (RtRowTiles{2, r, G}) on its own host thread and stream; ONE gather per frame

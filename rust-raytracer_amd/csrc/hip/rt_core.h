@@ -2054,4 +2054,88 @@ RT_HD DnColour denoise_pixel(const Src& src, uint32_t width, uint32_t height, ui
   return o;
 }
 
+// ------------------------------------------------------------------ temporal reprojection
+// One pixel of rt_hip_reproject: this frame's colour blended with the previous frame's history, fetched where this pixel's first-hit
+// surface was on screen one frame ago.  The contract is stated step by step in include/rt_abi.h; every operation below is one IEEE
+// operation (f64 for the geometry, f32 for the blend; the build has -ffp-contract=off), in the order written, with floor as the only
+// library call; tests/temporal_ref.py restates it in numpy bit for bit.
+struct ReprojCam { double o[3], ll[3], h[3], v[3]; };  // origin, lower_left, horizontal, vertical (camera.rs:52-63)
+struct ReprojK { float alpha_min, n_max, tau_n, tau_a, tau_z; };
+struct RpHist { float r, g, b, n; };  // accumulated colour and the number of frames in it
+RT_HD double reproj_dot(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+RT_HD void reproj_cross(const double a[3], const double b[3], double out[3]) {
+  out[0] = a[1] * b[2] - a[2] * b[1]; out[1] = a[2] * b[0] - a[0] * b[2]; out[2] = a[0] * b[1] - a[1] * b[0];
+}
+RT_HD bool reproj_finite(double x) { return x >= -1.7976931348623157e308 && x <= 1.7976931348623157e308; }
+// `src` answers colour(i) and guide(i) of this frame, prev_hist(i) and prev_guide(i) of the previous one, for the row-major pixel
+// index i of a width x height frame.
+template <class Src>
+RT_HD RpHist reproject_pixel(const Src& src, const ReprojCam& cur, const ReprojCam& prev, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
+                             const ReprojK& k) {
+  const size_t p = (size_t)y * width + x;
+  const DnColour c = src.colour(p);
+  RpHist out;
+  out.r = c.r; out.g = c.g; out.b = c.b; out.n = 1.0f;
+  if (c.r != c.r || c.g != c.g || c.b != c.b) { out.n = 0.0f; return out; }  // (a NaN pixel is never reused)
+  const DnGuide g = src.guide(p);
+  // the pixel centre: lane_begin_sample_w with both jitters 0.5
+  const double wm1 = (double)(width - 1u), hm1 = (double)(height - 1u);
+  const double u = ((double)x + 0.5) / wm1, v = ((double)height - ((double)y + 0.5)) / hm1;
+  double d[3], q[3], A[3];
+  for (int i = 0; i < 3; ++i) d[i] = ((cur.ll[i] + cur.h[i] * u) + cur.v[i] * v) - cur.o[i];
+  const bool hit = g.cov > 0.0f && g.iz > 0.0f;
+  if (hit) {
+    const double t = (double)g.cov / (double)g.iz;
+    for (int i = 0; i < 3; ++i) q[i] = (cur.o[i] + d[i] * t) - prev.o[i];
+  } else {
+    for (int i = 0; i < 3; ++i) q[i] = d[i];  // (sky: a point at infinity)
+  }
+  // into the previous camera: q = a A + b hor' + c ver' (Cramer's rule)
+  for (int i = 0; i < 3; ++i) A[i] = prev.ll[i] - prev.o[i];
+  double n0[3], n1[3], n2[3];
+  reproj_cross(prev.h, prev.v, n0); reproj_cross(prev.v, A, n1); reproj_cross(A, prev.h, n2);
+  const double det = reproj_dot(A, n0);
+  const double a = reproj_dot(q, n0) / det, b = reproj_dot(q, n1) / det, cc = reproj_dot(q, n2) / det;
+  if (!(a > 0.0) || !reproj_finite(a) || !reproj_finite(b) || !reproj_finite(cc)) return out;
+  const double fx = (b / a) * wm1 - 0.5, fy = ((double)height - (cc / a) * hm1) - 0.5;
+  // (outside these bounds, or NaN: all four taps lie outside the frame)
+  if (!(fx >= -1.0 && fx < (double)width && fy >= -1.0 && fy < (double)height)) return out;
+  const double x0d = floor(fx), y0d = floor(fy);
+  const int x0 = (int)x0d, y0 = (int)y0d;
+  const float wx = (float)(fx - x0d), wy = (float)(fy - y0d);
+  const float ez = hit ? (float)((double)g.cov / a) : 0.0f;
+  const float lim = k.tau_z * ez, lim2 = lim * lim;
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sn = 0.0f;
+  for (int j = 0; j < 2; ++j) {
+    const int qy = y0 + j;
+    if (qy < 0 || qy >= (int)height) continue;
+    const float wj = j ? wy : 1.0f - wy;
+    for (int i = 0; i < 2; ++i) {
+      const int qx = x0 + i;
+      if (qx < 0 || qx >= (int)width) continue;
+      const size_t t = (size_t)qy * width + (size_t)qx;
+      const RpHist h = src.prev_hist(t);
+      if (!(h.n > 0.0f) || h.r != h.r || h.g != h.g || h.b != h.b) continue;
+      const DnGuide gp = src.prev_guide(t);
+      const float e0 = gp.n[0] - g.n[0], e1 = gp.n[1] - g.n[1], e2 = gp.n[2] - g.n[2];
+      if (!((e0 * e0 + e1 * e1) + e2 * e2 <= k.tau_n)) continue;
+      const float a0 = gp.a[0] - g.a[0], a1 = gp.a[1] - g.a[1], a2 = gp.a[2] - g.a[2];
+      if (!((a0 * a0 + a1 * a1) + a2 * a2 <= k.tau_a)) continue;
+      const float dz = gp.iz - ez;
+      if (!(dz * dz <= lim2)) continue;
+      const float w = (i ? wx : 1.0f - wx) * wj;
+      sr = sr + w * h.r; sg = sg + w * h.g; sb = sb + w * h.b;
+      sw = sw + w;
+      sn = sn + w * h.n;
+    }
+  }
+  if (!(sw > 0.0f)) return out;
+  const float n1f = sn / sw + 1.0f, n = n1f < k.n_max ? n1f : k.n_max;
+  const float inv = 1.0f / n, alpha = k.alpha_min > inv ? k.alpha_min : inv;
+  const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
+  out.r = hr + alpha * (c.r - hr); out.g = hg + alpha * (c.g - hg); out.b = hb + alpha * (c.b - hb);
+  out.n = n;
+  return out;
+}
+
 }  // namespace rtc

@@ -222,6 +222,14 @@ struct RtHipScene {
   // allocated at first use.  aov_ready: dn_aov holds the AOVs of the current accumulator (reset_accum clears it)
   DevBuf dn_ping, dn_lin, dn_aov;
   bool aov_ready = false;
+  // temporal denoising, host form (rt_hip_render_frame_temporal_to_host): the frame's own accumulator (x 24 B), and
+  // two histories (x 16 B) and guide records (x 32 B) used alternately — tp_cur names the pair the last frame wrote — with the
+  // camera of that frame; all allocated at first use, dropped by rt_hip_temporal_reset.  tp_valid: the pair holds a frame.
+  DevBuf tp_accum, tp_hist[2], tp_aov[2];
+  int tp_cur = 0;
+  bool tp_valid = false;
+  double tp_cam[12] = {};
+  float tp_k[5] = {RT_TEMPORAL_ALPHA_MIN, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH};
   // adaptive frames, host form (rt_hip_render_adaptive_to_host): its own now / prev accumulators and per-tile list, errors and
   // counts (allocated at first use), and what each round of the last frame did: {tiles, samples per pixel after it, kernel ms}
   DevBuf ad_now, ad_prev, ad_list, ad_err, ad_spp;
@@ -1127,7 +1135,7 @@ extern "C" int rt_hip_render_to_host(RtHipScene* s, uint8_t* out_rgb8, RtStats* 
 
 namespace {
 int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32_t iterations, const float sigma[4], void* d_out_linear,
-                  void* d_out_rgb8, hipStream_t stream);
+                  void* d_out_rgb8, hipStream_t stream, bool in4 = false);
 // the host form's AOV sample count: min(RT_DENOISE_AOV_SAMPLES, samples per pixel), at least 1
 uint32_t aov_default_samples(uint32_t spp) { return spp < 1u ? 1u : (spp < RT_DENOISE_AOV_SAMPLES ? spp : RT_DENOISE_AOV_SAMPLES); }
 // Progressive rendering into the scene's own accumulator, blocking: the next sample_count samples of every pixel, then the whole
@@ -1196,9 +1204,10 @@ int check_sigmas(const float sigma[4]) {
   return RT_OK;
 }
 dim3 px_grid(const RtHipScene* s) { return dim3((s->host.width + 15u) / 16u, (s->host.height + 15u) / 16u); }
-// the L iterations: input -> ping -> pong -> ... -> outputs; arguments checked by the caller
+// the L iterations: input -> ping -> pong -> ... -> outputs; arguments checked by the caller.  in4: the input is f32 x 4 per pixel (a
+// temporal history: its rgb is filtered, its fourth float ignored) and goes through the instantiations that read the ping-pong
 int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32_t iterations, const float sigma[4], void* d_out_linear,
-                  void* d_out_rgb8, hipStream_t stream) {
+                  void* d_out_rgb8, hipStream_t stream, bool in4) {
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0 || (!d_out_linear && !d_out_rgb8)) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
@@ -1208,15 +1217,17 @@ int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32
   const uint32_t W = s->host.width, H = s->host.height;
   const dim3 grid = px_grid(s), block(16, 16);
   if (iterations == 0) {
-    hipLaunchKernelGGL((rtk::rt_denoise<false, true>), grid, block, 0, stream, (const float*)d_linear, aov, W, H, 0u, rtc::DenoiseK{},
-                       (float4*)nullptr, (float*)d_out_linear, (uint8_t*)d_out_rgb8);
+    if (in4) hipLaunchKernelGGL((rtk::rt_denoise<true, true>), grid, block, 0, stream, (const float*)d_linear, aov, W, H, 0u, rtc::DenoiseK{},
+                                (float4*)nullptr, (float*)d_out_linear, (uint8_t*)d_out_rgb8);
+    else hipLaunchKernelGGL((rtk::rt_denoise<false, true>), grid, block, 0, stream, (const float*)d_linear, aov, W, H, 0u, rtc::DenoiseK{},
+                            (float4*)nullptr, (float*)d_out_linear, (uint8_t*)d_out_rgb8);
     RT_HIP_TRY(hipGetLastError());
     return RT_OK;
   }
   for (uint32_t i = 0; i < iterations; ++i) {
     const rtc::DenoiseK k = rtc::denoise_consts(i, sigma[0], sigma[1], sigma[2], sigma[3]);
-    const bool first = i == 0, last = i + 1 == iterations;
-    const float* in = first ? (const float*)d_linear : (const float*)buf[(i - 1) & 1];
+    const bool first = i == 0 && !in4, last = i + 1 == iterations;
+    const float* in = i == 0 ? (const float*)d_linear : (const float*)buf[(i - 1) & 1];
     float4* out4 = last ? nullptr : buf[i & 1];
     float* ol = last ? (float*)d_out_linear : nullptr;
     uint8_t* ob = last ? (uint8_t*)d_out_rgb8 : nullptr;
@@ -1279,6 +1290,141 @@ extern "C" int rt_hip_refine_to_host_denoised(RtHipScene* s, uint32_t sample_cou
   if (iterations > rtc::DENOISE_MAX_ITERATIONS) return fail(RT_ERR_UNSUPPORTED, "at most 8 iterations");
   if (s->host.height > 65535u * 16u) return fail(RT_ERR_UNSUPPORTED, "frames taller than 1 048 560 rows");
   return refine_to_host(s, sample_count, (int)iterations, out_rgb8, stats);
+}
+
+// ---------------------------------------------------------------------------------------------------- temporal denoising
+namespace {
+int check_reproject_params(float alpha_min, float n_max, float tau_n, float tau_a, float tau_z) {
+  for (float t : {tau_n, tau_a, tau_z})
+    if (!(t >= 0.0f) || !(t <= 3.4028234663852886e38f)) return fail(RT_ERR_INVALID, "every threshold must be finite and at least 0");
+  if (!(alpha_min >= 0.0f && alpha_min <= 1.0f)) return fail(RT_ERR_INVALID, "alpha_min must lie in [0, 1]");
+  if (!(n_max >= 1.0f)) return fail(RT_ERR_INVALID, "n_max must be at least 1");
+  return RT_OK;
+}
+rtc::ReprojCam reproj_cam(const double c[12]) {
+  rtc::ReprojCam r;
+  for (int i = 0; i < 3; ++i) { r.o[i] = c[i]; r.ll[i] = c[3 + i]; r.h[i] = c[6 + i]; r.v[i] = c[9 + i]; }
+  return r;
+}
+void scene_camera(const RtHipScene* s, double c[12]) {
+  for (int i = 0; i < 3; ++i) { c[i] = s->host.cam_origin[i]; c[3 + i] = s->host.cam_lower_left[i]; c[6 + i] = s->host.cam_horizontal[i]; c[9 + i] = s->host.cam_vertical[i]; }
+}
+// arguments checked by the caller
+int reproject_frame(RtHipScene* s, const void* d_linear, const void* d_aov, const void* d_prev_history, const void* d_prev_aov, const double prev_camera[12],
+                    const float k[5], void* d_out_history, hipStream_t stream) {
+  double cur[12];
+  scene_camera(s, cur);
+  const rtc::ReprojK rk{k[0], k[1], k[2], k[3], k[4]};
+  hipLaunchKernelGGL(rtk::rt_reproject, px_grid(s), dim3(16, 16), 0, stream, (const float*)d_linear, (const float4*)d_aov, (const float4*)d_prev_history,
+                     (const float4*)d_prev_aov, reproj_cam(cur), reproj_cam(prev_camera), s->host.width, s->host.height, rk, (float4*)d_out_history);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_hip_reproject(RtHipScene* s, const void* d_linear, const void* d_aov, const void* d_prev_history, const void* d_prev_aov,
+                                const double prev_camera[12], float alpha_min, float n_max, float tau_n, float tau_a, float tau_z, void* d_out_history,
+                                void* stream) {
+  int rc = check_whole_frame(s, nullptr);
+  if (rc != RT_OK) return rc;
+  if ((rc = check_reproject_params(alpha_min, n_max, tau_n, tau_a, tau_z)) != RT_OK) return rc;
+  if (!d_linear || !d_aov || !d_prev_history || !d_prev_aov || !prev_camera || !d_out_history) return fail(RT_ERR_INVALID, "null argument");
+  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  for (const void* q : {d_aov, d_prev_history, d_prev_aov, (const void*)d_out_history})
+    if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(RT_ERR_INVALID, "the guide and history buffers must be 16-byte aligned");
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px == 0) return RT_OK;
+  // (an output over an input would be read by other threads while it is written)
+  const uintptr_t o0 = (uintptr_t)d_out_history, o1 = o0 + px * 16;
+  for (const std::pair<uintptr_t, size_t> in : {std::make_pair((uintptr_t)d_linear, px * 12), std::make_pair((uintptr_t)d_aov, px * 32),
+                                                std::make_pair((uintptr_t)d_prev_history, px * 16), std::make_pair((uintptr_t)d_prev_aov, px * 32)})
+    if (in.first < o1 && o0 < in.first + in.second) return fail(RT_ERR_INVALID, "the output must not overlap the inputs");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const float k[5] = {alpha_min, n_max, tau_n, tau_a, tau_z};
+  return reproject_frame(s, d_linear, d_aov, d_prev_history, d_prev_aov, prev_camera, k, d_out_history, (hipStream_t)stream);
+}
+
+extern "C" int rt_hip_temporal_configure(RtHipScene* s, float alpha_min, float n_max, float tau_n, float tau_a, float tau_z) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  const int rc = check_reproject_params(alpha_min, n_max, tau_n, tau_a, tau_z);
+  if (rc != RT_OK) return rc;
+  const float k[5] = {alpha_min, n_max, tau_n, tau_a, tau_z};
+  std::memcpy(s->tp_k, k, sizeof k);
+  return RT_OK;
+}
+
+extern "C" int rt_hip_temporal_reset(RtHipScene* s) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  if (s->n_launches) RT_HIP_TRY(hipStreamSynchronize(s->last_stream));  // (the host form is blocking: nothing of it is in flight; a caller's own launch may be)
+  for (DevBuf* b : {&s->tp_accum, &s->tp_hist[0], &s->tp_hist[1], &s->tp_aov[0], &s->tp_aov[1]}) { DevBuf none; b->swap(none); }
+  s->tp_valid = false;
+  s->tp_cur = 0;
+  return RT_OK;
+}
+
+extern "C" int rt_hip_temporal_history(RtHipScene* s, float* out_history) {
+  if (!s || !out_history) return fail(RT_ERR_INVALID, "null argument");
+  if (!s->tp_valid) return fail(RT_ERR_INVALID, "the scene holds no temporal history");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px) RT_HIP_TRY(hipMemcpy(out_history, s->tp_hist[s->tp_cur].p, px * 16, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// One frame of an animation, blocking, on the NULL stream like rt_hip_render_to_host: samples [b, b + spp) into the frame's own
+// accumulator, resolved to linear f32, the AOVs of this view, one reprojection step against the history the previous call left, and
+// the spatial filter over the new history's rgb into RGB8.  The history keeps the colour BEFORE the filter.
+extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t frame_index, uint32_t iterations, uint8_t* out_rgb8, RtStats* stats) {
+  if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
+  if (iterations > rtc::DENOISE_MAX_ITERATIONS) return fail(RT_ERR_UNSUPPORTED, "at most 8 iterations");
+  int rc = check_whole_frame(s, nullptr);
+  if (rc != RT_OK) return rc;
+  const uint32_t spp = s->host.samples_per_pixel;
+  if (spp == 0) return fail(RT_ERR_INVALID, "samples_per_pixel must be at least 1");
+  if (spp > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  const uint32_t F = rtc::ACCUM_MAX_SAMPLES / spp, begin = (frame_index % F) * spp;  // (frames F apart share a sample range)
+  auto t0 = std::chrono::steady_clock::now();
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 3;
+  bool grew = false, any_grew = false;
+  if ((rc = s->tp_accum.ensure(px * 24)) != RT_OK || (rc = s->dn_lin.ensure(px * 12)) != RT_OK || (rc = s->frame.ensure(bytes)) != RT_OK) return rc;
+  for (int i = 0; i < 2; ++i) {
+    if ((rc = s->tp_hist[i].ensure(px * 16, &grew)) != RT_OK) return rc;
+    any_grew = any_grew || grew;
+    if ((rc = s->tp_aov[i].ensure(px * 32, &grew)) != RT_OK) return rc;
+    any_grew = any_grew || grew;
+  }
+  if (any_grew) s->tp_valid = false;
+  const int prev = s->tp_cur, cur = prev ^ 1;
+  double prev_cam[12];
+  if (s->tp_valid) std::memcpy(prev_cam, s->tp_cam, sizeof prev_cam);
+  else {  // no previous frame: a history of n = 0 everywhere, which no tap accepts
+    scene_camera(s, prev_cam);
+    if (px) {
+      RT_HIP_TRY(hipMemsetAsync(s->tp_hist[prev].p, 0, px * 16, nullptr));
+      RT_HIP_TRY(hipMemsetAsync(s->tp_aov[prev].p, 0, px * 32, nullptr));
+    }
+  }
+  if (px) RT_HIP_TRY(hipMemsetAsync(s->tp_accum.p, 0, px * 24, nullptr));
+  rc = rt_hip_accumulate(s, nullptr, begin, spp, s->tp_accum.p, nullptr);
+  if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->tp_accum.p, spp, nullptr, s->dn_lin.p, nullptr);
+  if (rc == RT_OK) rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(spp), s->tp_aov[cur].p, nullptr);
+  if (rc == RT_OK && px) rc = reproject_frame(s, s->dn_lin.p, s->tp_aov[cur].p, s->tp_hist[prev].p, s->tp_aov[prev].p, prev_cam, s->tp_k, s->tp_hist[cur].p, nullptr);
+  const float sigma[4] = {RT_DENOISE_SIGMA_COLOR, RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_ALBEDO, RT_DENOISE_SIGMA_INV_DEPTH};
+  if (rc == RT_OK) rc = denoise_frame(s, s->tp_hist[cur].p, s->tp_aov[cur].p, iterations, sigma, nullptr, s->frame.p, nullptr, true);
+  RtStats st;
+  if (rc == RT_OK) rc = rt_hip_wait(s, &st);
+  if (rc != RT_OK) { s->tp_valid = false; return rc; }  // (a frame that did not complete leaves the history unknown: start over)
+  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, bytes, hipMemcpyDeviceToHost));
+  s->tp_cur = cur;
+  s->tp_valid = true;
+  scene_camera(s, s->tp_cam);
+  if (stats) {
+    *stats = st;
+    stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return RT_OK;
 }
 
 // Adaptive sampling, host form, blocking, on the NULL stream like rt_hip_render_to_host.  M = min(min_spp, N):

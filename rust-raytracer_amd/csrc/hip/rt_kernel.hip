@@ -1359,6 +1359,36 @@ template __global__ void rt_denoise<false, true>(const float*, const float4*, ui
 template __global__ void rt_denoise<true, false>(const float*, const float4*, uint32_t, uint32_t, uint32_t, DenoiseK, float4*, float*, uint8_t*);
 template __global__ void rt_denoise<true, true>(const float*, const float4*, uint32_t, uint32_t, uint32_t, DenoiseK, float4*, float*, uint8_t*);
 
+// --------------------------------------------------------------------------- temporal reprojection
+// One step of the history (rt_core.h reproject_pixel): one thread per pixel, 16 x 16 blocks.  Per pixel: this frame's colour (three
+// f32 loads) and guide (two 16-byte loads), up to four taps of the previous frame's history (one 16-byte load each) and guide (two),
+// one 16-byte store.  Reads no scene table.
+struct RpSrc {
+  const float* lin;
+  const float4* aov;
+  const float4* prev_h;
+  const float4* prev_aov;
+  __device__ __forceinline__ DnColour colour(size_t i) const { DnColour c; c.r = lin[3 * i]; c.g = lin[3 * i + 1]; c.b = lin[3 * i + 2]; return c; }
+  static __device__ __forceinline__ DnGuide load_guide(const float4* a, size_t i) {
+    const float4 u = a[2 * i], v = a[2 * i + 1];
+    DnGuide g;
+    g.a[0] = u.x; g.a[1] = u.y; g.a[2] = u.z; g.iz = u.w; g.n[0] = v.x; g.n[1] = v.y; g.n[2] = v.z; g.cov = v.w;
+    return g;
+  }
+  __device__ __forceinline__ DnGuide guide(size_t i) const { return load_guide(aov, i); }
+  __device__ __forceinline__ DnGuide prev_guide(size_t i) const { return load_guide(prev_aov, i); }
+  __device__ __forceinline__ RpHist prev_hist(size_t i) const { const float4 v = prev_h[i]; RpHist h; h.r = v.x; h.g = v.y; h.b = v.z; h.n = v.w; return h; }
+};
+__global__ __launch_bounds__(256) void rt_reproject(const float* __restrict__ lin, const float4* __restrict__ aov, const float4* __restrict__ prev_h,
+                                                    const float4* __restrict__ prev_aov, ReprojCam cur, ReprojCam prev, uint32_t width, uint32_t height,
+                                                    ReprojK k, float4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x >= width || y >= height) return;
+  const RpSrc src{lin, aov, prev_h, prev_aov};
+  const RpHist o = reproject_pixel(src, cur, prev, width, height, x, y, k);
+  out[(size_t)y * width + x] = make_float4(o.r, o.g, o.b, o.n);
+}
+
 #ifdef RT_TEST_PROBES
 // --------------------------------------------------------------------------- device self-test
 // f64 sqrt / divide / f32 sqrt must be correctly rounded on the GPU for bit-parity with the CPU

@@ -31,8 +31,14 @@
 //
 // Denoised (`--denoise`, alone or with `--passes K`): every PNG the run writes is the resolved frame passed through the
 // feature-guided a-trous filter (rt_hip_refine_to_host_denoised, RT_DENOISE_ITERATIONS iterations, the default sigmas; DESIGN.md
-// §12).  The last PNG of `--passes K --denoise` is the `--denoise` run's, byte for byte.  Stdout as a one-shot run.  With --frames,
-// --orbit or --adaptive: the usage line.  One GPU: RT_GPUS > 1 is refused.
+// §12).  The last PNG of `--passes K --denoise` is the `--denoise` run's, byte for byte.  Stdout as a one-shot run.  With --adaptive,
+// or with only one of --frames and --orbit: the usage line.  One GPU: RT_GPUS > 1 is refused.
+//
+// Denoised animation (`--frames N --orbit DEG [--shutter S] --denoise`): the frames of the animation modes below, each
+// tracing a sample range of its own, blended with the previous frame's history where the first-hit surface was on screen one frame ago
+// and filtered spatially (rt_hip_render_frame_temporal_to_host, RT_DENOISE_ITERATIONS iterations) on one resident scene.  The turn per
+// frame must be named: --orbit is required (0 keeps the camera still).  Frame 0 is the `--denoise` one-shot frame, byte for byte.
+// PNGs are written on the writer threads.  One GPU: RT_GPUS > 1 is refused.
 //
 // Thin lens: a scene whose camera has a non-zero "aperture" renders through the lens in every mode above —
 // rt_camera_derive_lens gives the camera on the focus plane and the lens, set next to each other on the resident scene or group
@@ -292,6 +298,52 @@ int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool den
   return status;
 }
 
+// --frames N --orbit DEG [--shutter S] --denoise: the animation on one resident scene through the temporal host form, frame f's PNG
+// encoded on the writer threads while frame f + 1 renders (1 + W host buffers: the frame being rendered + one per writer)
+int animate_temporal(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
+  RtScene* sc = rt_scene_get_mut(sf);
+  RtHipScene* hs = nullptr;
+  const auto t_create = std::chrono::steady_clock::now();
+  int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
+  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
+  const auto t_begin = std::chrono::steady_clock::now();
+  double cam[11], lens[2];
+  rt_scene_camera(sf, cam);
+  rt_scene_lens(sf, lens);
+  const size_t bytes = (size_t)sc->width * sc->height * 3;
+  const unsigned W = anim_writers();
+  std::vector<std::vector<uint8_t>> store(1 + W, std::vector<uint8_t>(bytes));
+  AnimStats stats(frames);
+  PngWriters writers(W, prefix, sc->width, sc->height, &stats);
+  for (auto& b : store) writers.give_buffer(b.data());
+  std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
+  if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
+  int status = 0, done = 0;
+  for (int f = 0; f < frames && status == 0 && !writers.failed(); ++f) {
+    double out[20];
+    uint8_t* buf = writers.take_buffer();
+    orbit_camera(cam, lens, orbit_deg, f, out);
+    rc = rt_hip_set_camera(hs, out, out + 3, out + 6, out + 9);
+    if (rc == RT_OK && lens[0] != 0.0) rc = rt_hip_set_lens(hs, out + 13, out + 16, out[19]);
+    if (rc == RT_OK && shutter >= 0.0) {
+      rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
+      rc = rt_hip_scene_update_spheres(hs, c_f.data(), c1_f.data());
+    }
+    RtStats st{};
+    if (rc == RT_OK) rc = rt_hip_render_frame_temporal_to_host(hs, (uint32_t)f, RT_DENOISE_ITERATIONS, buf, &st);
+    if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; writers.give_buffer(buf); break; }
+    std::printf("\nRendering %s\nFrame time: %lldms\n", frame_name(prefix, f).c_str(), (long long)st.frame_ms);
+    stats.kernel_ms[f] = st.kernel_ms; stats.frame_ms[f] = st.frame_ms;
+    writers.push(f, buf);
+    done++;
+  }
+  writers.finish();
+  stats.report("temporal", done, 1, W, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), ms_between(t_create, t_begin));
+  rt_hip_scene_destroy(hs);
+  if (writers.write_rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", writers.write_err.c_str()); status = 101; }
+  return status;
+}
+
 // --adaptive E [--min-spp M]: one adaptive frame of a resident scene
 int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t min_spp) {
   const RtScene* sc = rt_scene_get(sf);
@@ -467,8 +519,9 @@ int run(int argc, char** argv) {
     } else bad_args = true;
   }
   auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
-  if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || denoise)) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
-      (denoise && (adapt || frames != 0 || orbit_given)) || (argc > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
+  const bool temporal = denoise && frames > 0 && orbit_given;  // (a denoised animation names its turn per frame)
+  if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || (denoise && !temporal))) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
+      (denoise && (adapt || ((frames != 0 || orbit_given) && !temporal))) || (argc > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
     return usage();  // main.rs:9-12: usage line, normal return
   // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
   // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X
@@ -509,7 +562,8 @@ int run(int argc, char** argv) {
       status = 101;
     } else {
       if (g_hip_init.joinable()) g_hip_init.join();
-      status = passes > 0 ? progressive(sf, argv[2], (uint32_t)passes, denoise) : progressive(sf, argv[2], 1u, true, false);
+      if (temporal) status = animate_temporal(sf, argv[2], frames, orbit, shutter);
+      else status = passes > 0 ? progressive(sf, argv[2], (uint32_t)passes, denoise) : progressive(sf, argv[2], 1u, true, false);
     }
     rt_scene_free(sf);
     return status;

@@ -72,6 +72,11 @@ def _bind(path, probes):
     L.rt_hip_denoise.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rt_hip_refine_to_host_denoised.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(abi.RtStats)]
+    L.rt_hip_reproject.argtypes = [C.c_void_p] * 5 + [C.POINTER(C.c_double)] + [C.c_float] * 5 + [C.c_void_p, C.c_void_p]
+    L.rt_hip_render_frame_temporal_to_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(abi.RtStats)]
+    L.rt_hip_temporal_configure.argtypes = [C.c_void_p] + [C.c_float] * 5
+    L.rt_hip_temporal_reset.argtypes = [C.c_void_p]
+    L.rt_hip_temporal_history.argtypes = [C.c_void_p, C.c_void_p]
     L.rt_abi_sizeof.argtypes = [C.c_char_p]
     L.rt_abi_sizeof.restype = C.c_size_t
     L.rt_abi_version.restype = C.c_uint32
@@ -285,6 +290,40 @@ class HipScene:
         st = abi.RtStats()
         _check(self._L.rt_hip_refine_to_host_denoised(self._h, int(sample_count), int(iterations), out.ctypes.data, C.byref(st)), self._L)
         return out, st.as_dict()
+
+    # include/rt_abi.h RT_TEMPORAL_*: alpha_min, n_max, tau_n, tau_a, tau_z a scene starts with (the best of a sweep)
+    TEMPORAL_PARAMS = (0.5, 8.0, 0.02, 0.3, 0.02)
+
+    def reproject(self, d_linear, d_aov, d_prev_history, d_prev_aov, prev_camera, d_out_history, params=TEMPORAL_PARAMS, stream=0):
+        """enqueue one temporal step: this frame's d_linear (h x w x 3 float32) and d_aov blended with the previous
+        frame's d_prev_history (h x w x 4 float32 {r, g, b, n}) found through d_prev_aov and prev_camera (12 doubles: origin, lower_left,
+        horizontal, vertical) into d_out_history; params = (alpha_min, n_max, tau_n, tau_a, tau_z)"""
+        cam = (C.c_double * 12)(*[float(x) for x in prev_camera]) if prev_camera is not None else None
+        _check(self._L.rt_hip_reproject(self._h, C.c_void_p(d_linear or None), C.c_void_p(d_aov or None), C.c_void_p(d_prev_history or None),
+                                        C.c_void_p(d_prev_aov or None), cam, *[float(x) for x in params], C.c_void_p(d_out_history or None),
+                                        C.c_void_p(stream or None)), self._L)
+
+    def render_frame_temporal_to_host(self, frame_index, iterations=DENOISE_ITERATIONS):
+        """frame `frame_index` of an animation: its own sample range, reprojected onto the history the previous call left, filtered:
+        numpy [h,w,3] uint8 + the pass's stats (blocking)"""
+        import numpy as np
+        out = np.zeros((self.height, self.width, 3), np.uint8)
+        st = abi.RtStats()
+        _check(self._L.rt_hip_render_frame_temporal_to_host(self._h, int(frame_index), int(iterations), out.ctypes.data, C.byref(st)), self._L)
+        return out, st.as_dict()
+
+    def temporal_configure(self, alpha_min, n_max, tau_n, tau_a, tau_z):
+        _check(self._L.rt_hip_temporal_configure(self._h, float(alpha_min), float(n_max), float(tau_n), float(tau_a), float(tau_z)), self._L)
+
+    def temporal_reset(self):
+        _check(self._L.rt_hip_temporal_reset(self._h), self._L)
+
+    def temporal_history(self):
+        """the history the last temporal frame left: numpy [h,w,4] float32 {r, g, b, n}"""
+        import numpy as np
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._L.rt_hip_temporal_history(self._h, out.ctypes.data), self._L)
+        return out
 
     def tile_grid(self, tiles=None):
         """the pixel tiles of adaptive sampling for `tiles`' rows: (tile width, tile height, tiles_x, tiles_y); id = ty * tiles_x + tx"""
