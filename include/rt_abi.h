@@ -541,6 +541,69 @@ int rt_hip_render_frame_temporal_to_host(RtHipScene*, uint32_t frame_index, uint
 int rt_hip_temporal_configure(RtHipScene*, float alpha_min, float n_max, float tau_n, float tau_a, float tau_z);
 int rt_hip_temporal_reset(RtHipScene*);
 int rt_hip_temporal_history(RtHipScene*, float* out_history);
+/* Temporal denoising with surface tracking: the step above told WHICH sphere a pixel shows, what it is made of and
+ * where that sphere stood one frame ago — so a moved sphere keeps the history of its own surface, and a mirror or a lens, whose
+ * picture first-hit reprojection cannot follow, is given a short history of its own.  Whole frames only.  Opt-in: nothing above changes.
+ *
+ * SURFACE RECORD: per pixel 16 B {u32 id, u32 kind, f64 t}, rows x width packed row-major, 16-byte aligned.  It describes ONE ray, the
+ * pixel-centre ray of the pinhole: u = (x + 0.5) / (w - 1), v = (h - (y + 0.5)) / (h - 1), d = ((lower_left + horizontal u) +
+ * vertical v) - origin per component, IEEE f64 with real divisions, from the camera origin even when a lens is set.  Its closest hit by
+ * the rule of hit_world (t > 0.001; of equal roots the sphere earlier in the scene wins): id = the sphere's index in the scene's
+ * order, kind = its RT_MAT_*, t = the accepted root.  A miss: id = kind = 0xFFFFFFFF, t = 0.0.  A scene with motion
+ * (rt_hip_scene_create_moving, rt_hip_scene_update_spheres) has every sphere at shutter time 0.5: centre_k + (center1_k - centre_k) * 0.5
+ * in f64.  A scene with media takes the medium candidate of DESIGN.md §15 with the RNG address (this pixel, sample 0, node 0); a first
+ * hit inside a medium reports the medium sphere's id and RT_MAT_MEDIUM.
+ *
+ * rt_hip_render_surface: the record of every pixel into d_surface (width*height*16 bytes) on `stream`, asynchronous, not reported by
+ * rt_hip_wait.  Reads the scene's tables and camera only: no tile queue, learned order, counters or accumulator changes, so every later
+ * frame is byte-identical.  Every scene rt_hip_render_aovs accepts.  A NULL or misaligned buffer: RT_ERR_INVALID; tiles:
+ * RT_ERR_UNSUPPORTED; nothing is enqueued.
+ *
+ * rt_hip_reproject_surface: one step.  As rt_hip_reproject, with this frame's and the previous frame's surface records
+ * (d_surface, d_prev_surface) and d_displacement: NULL (nothing moved), or a device table of n_spheres x 3 f64, sphere i's centre now
+ * minus its centre one frame ago, 8-byte aligned.  Per pixel (x, y), every operation one IEEE operation in exactly this order, no
+ * contraction (f64 for the geometry and the depth test, f32 from the weights on); dot and cross as above:
+ *   c = the pixel's colour, g its AOV record, s its surface record.  A NaN channel in c: out = c, n = 0, done.
+ *   Pixel centre: u, v and d as above.
+ *   Surface point: hit = s.id != 0xFFFFFFFF.  A hit: q = ((origin + d s.t) - D) - origin' per component, D = d_displacement[s.id];
+ *     with a NULL table (or s.id >= n_spheres) there is no subtraction, q = (origin + d s.t) - origin', the bits of D = 0.
+ *     Else (sky): q = d.
+ *   Into the previous camera: A, n0, n1, n2, det, a, b, e, the two "no history unless" rules, fx and fy exactly as in rt_hip_reproject.
+ *   Taps: x0, y0, wx, wy, the tap order and the weights W exactly as in rt_hip_reproject.
+ *   A tap counts iff it lies inside the frame; its history has n > 0 and no NaN in r, g, b; its previous surface record has
+ *     id' == s.id (sky matches only sky); |normal' - normal|^2 <= tau_n and |albedo' - albedo|^2 <= tau_a as in rt_hip_reproject;
+ *     and, for a hit, dt dt <= (tau_z a) (tau_z a) in f64 with dt = t' - a, t' the tap's previous t and tau_z widened to f64
+ *     (a is the previous camera's ray parameter of the surface point).  Sky has no depth test.  A comparison with a NaN fails.
+ *   Sums, hist_c, m, n and r = 1 / n as in rt_hip_reproject.  floor = alpha_specular if s.kind is RT_MAT_METAL or RT_MAT_GLASS, else
+ *     alpha_min; alpha = floor > r ? floor : r, out_c = hist_c + alpha (c_c - hist_c).  No history: out = c, n = 1.
+ *   (alpha_specular = 1: such a pixel keeps this frame's colour alone and goes on to the spatial filter.)
+ * Asynchronous on `stream`; writes no caller buffer but the output.  RT_ERR_INVALID, and nothing is enqueued, for: a NULL buffer or
+ * camera (d_displacement may be NULL); d_linear not 4-byte aligned, d_displacement not 8-byte, another buffer not 16-byte aligned; an
+ * output that overlaps an input, the two surface buffers and the displacement table included; a threshold that is not finite and
+ * >= 0; alpha_min or alpha_specular outside [0, 1]; n_max not >= 1.
+ *
+ * rt_hip_temporal_surface: switches rt_hip_render_frame_temporal_to_host between the path above (enable 0, how a scene starts: its
+ * bytes are unchanged) and surface tracking; a real change of mode drops the history as rt_hip_temporal_reset does.  alpha_specular
+ * (in [0, 1], else RT_ERR_INVALID) is kept either way; rt_hip_temporal_configure supplies the other five values in both modes
+ * (RT_TEMPORAL_SURFACE_* below are what the CLI's --temporal-surface configures: the best point of a sweep over alpha_min, alpha_specular and
+ * n_max on four animations, which left n_max and the thresholds at RT_TEMPORAL_*; profiles/temporal_surface_bench.json).  In surface mode a frame is, in this order: the
+ * accumulate, the resolve and the AOVs as above; rt_hip_render_surface; rt_hip_reproject_surface against the previous frame's history,
+ * AOVs, surface record and camera; rt_hip_denoise over the new history.  The displacement is the scene's own: per temporal frame it
+ * keeps each sphere's centre at shutter time 0.5 of the tables that frame rendered with, centre_k + (center1_k - centre_k) * 0.5 in f64,
+ * and uploads now - previous before the step (zeros for the first frame), so rt_hip_scene_update_spheres between calls is followed with no
+ * extra caller work.  Frame 0 of a scene without history stays rt_hip_refine_to_host_denoised, byte for byte.  The extra buffers
+ * (width*height*32 bytes + n_spheres*24) belong to the scene: allocated at first use in surface mode only, freed by
+ * rt_hip_temporal_reset and with the scene.  rt_hip_scene_query "temporal_surface": 0 / 1.
+ * Not handled: the group (multi-GPU) calls, row tiles, a thin lens (the centre ray is the pinhole's), what a mirror or a lens SHOWS
+ * (only its own surface is followed), moving Light spheres (no scene can hold one). */
+#define RT_TEMPORAL_SURFACE_ALPHA_MIN 0.5f
+#define RT_TEMPORAL_SURFACE_ALPHA_SPECULAR 1.0f
+int rt_hip_render_surface(RtHipScene*, const RtRowTiles* tiles, void* d_surface, void* stream);
+int rt_hip_reproject_surface(RtHipScene*, const void* d_linear, const void* d_aov, const void* d_surface, const void* d_prev_history,
+                             const void* d_prev_aov, const void* d_prev_surface, const double prev_camera[12], const double* d_displacement,
+                             float alpha_min, float alpha_specular, float n_max, float tau_n, float tau_a, float tau_z, void* d_out_history,
+                             void* stream);
+int rt_hip_temporal_surface(RtHipScene*, int enable, float alpha_specular);
 /* A frame over the GPUs of one node, scene resident (the parallel loop of raytracer.rs:254-262 spread over devices;
  * animation: README.md:43-57).  n_gpus = 0 takes scene->n_gpus, then RT_GPUS, then 1.  Each rank renders
  * interleaved 2-scanline tiles (RtRowTiles{2, r, G}) on its own host thread and stream; ONE gather per frame

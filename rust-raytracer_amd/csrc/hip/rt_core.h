@@ -2138,4 +2138,122 @@ RT_HD RpHist reproject_pixel(const Src& src, const ReprojCam& cur, const ReprojC
   return out;
 }
 
+// ------------------------------------------------------------------ temporal reprojection with surface tracking
+// SURFACE RECORD (rt_hip_render_surface): which sphere the pixel-centre pinhole ray — the ray reproject_pixel forms, plain IEEE
+// divisions, never the cam_fast reciprocals, the camera origin even under a lens — meets first, what it is made of and at which ray
+// parameter.  The closest hit of hit_world (t_min 0.001) through hit_world_grid; a miss is {SURFACE_NONE, SURFACE_NONE, 0.0}.
+// MOTION: every sphere at shutter time 0.5, through the MOTION kernels' tables.  MEDIUM: the medium candidate of §15 with the RNG address
+// (this pixel, sample 0, node 0).  No albedo is evaluated: LENS and SOLID do not matter here.
+constexpr uint32_t SURFACE_NONE = 0xFFFFFFFFu;
+constexpr float SURFACE_SHUTTER_TIME = 0.5f;
+struct SurfRec { uint32_t id, kind; double t; };  // 16 B
+template <bool MEDIUM = false, class Tables>
+RT_HD SurfRec surface_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, uint32_t pixel) {
+  double closest = T_MAX;
+  int best = -1;
+  uint32_t n_exact = 0, n_steps = 0;
+  if constexpr (MEDIUM) {
+    const MediumCtx mc{sc.medium, RngAddr{pixel, 0u, sc.seed_lo, sc.seed_hi}, 0u};
+    hit_world_grid<true>(sc, tb, o, d, closest, best, n_exact, n_steps, &mc);
+  } else hit_world_grid(sc, tb, o, d, closest, best, n_exact, n_steps);
+  SurfRec r;
+  r.id = SURFACE_NONE; r.kind = SURFACE_NONE; r.t = 0.0;
+  if (best >= 0) { r.id = (uint32_t)best; r.kind = tb.mat((uint32_t)best).kind; r.t = closest; }
+  return r;
+}
+template <bool MOTION = false, bool MEDIUM = false, class Tables>
+RT_HD SurfRec surface_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py) {
+  const double wm1 = (double)(sc.width - 1u), hm1 = (double)(sc.height - 1u);
+  const double u = ((double)px + 0.5) / wm1, v = ((double)sc.height - ((double)py + 0.5)) / hm1;
+  const V3 origin = v3(sc.cam_origin[0], sc.cam_origin[1], sc.cam_origin[2]);
+  const V3 llc = v3(sc.cam_ll[0], sc.cam_ll[1], sc.cam_ll[2]);
+  const V3 hor = v3(sc.cam_h[0], sc.cam_h[1], sc.cam_h[2]);
+  const V3 ver = v3(sc.cam_v[0], sc.cam_v[1], sc.cam_v[2]);
+  const V3 d = sub(add(add(llc, muls(hor, u)), muls(ver, v)), origin);
+  const uint32_t pixel = py * sc.width + px;
+  if constexpr (MOTION) return surface_ray<MEDIUM>(sc, motion_tables(tb, sc.motion, SURFACE_SHUTTER_TIME), origin, d, pixel);
+  else return surface_ray<MEDIUM>(sc, tb, origin, d, pixel);
+}
+
+// One pixel of rt_hip_reproject_surface: reproject_pixel with the surface point, the tap test and the floor on alpha taken from the
+// surface records (the contract, step by step, is in include/rt_abi.h; tests/temporal_surface_ref.py restates it in numpy bit for
+// bit).  Written beside reproject_pixel rather than shared with it, so that rt_reproject's code stays what it was.
+// `src` answers what reproject_pixel's does, and surf(i) / prev_surf(i), the two frames' surface records.  `disp`: null, or
+// [n_disp][3], each sphere's centre now minus its centre one frame ago (an id at or above n_disp has none: a record the scene did not write).
+struct ReprojSurfK { float alpha_min, alpha_specular, n_max, tau_n, tau_a, tau_z; };
+template <class Src>
+RT_HD RpHist reproject_surface_pixel(const Src& src, const ReprojCam& cur, const ReprojCam& prev, const double* disp, uint32_t n_disp, uint32_t width, uint32_t height,
+                                     uint32_t x, uint32_t y, const ReprojSurfK& k) {
+  const size_t p = (size_t)y * width + x;
+  const DnColour c = src.colour(p);
+  RpHist out;
+  out.r = c.r; out.g = c.g; out.b = c.b; out.n = 1.0f;
+  if (c.r != c.r || c.g != c.g || c.b != c.b) { out.n = 0.0f; return out; }  // (a NaN pixel is never reused)
+  const SurfRec s = src.surf(p);
+  const double wm1 = (double)(width - 1u), hm1 = (double)(height - 1u);
+  const double u = ((double)x + 0.5) / wm1, v = ((double)height - ((double)y + 0.5)) / hm1;
+  double d[3], q[3], A[3];
+  for (int i = 0; i < 3; ++i) d[i] = ((cur.ll[i] + cur.h[i] * u) + cur.v[i] * v) - cur.o[i];
+  const bool hit = s.id != SURFACE_NONE;
+  if (hit) {
+    if (disp && s.id < n_disp) {  // where this point of the sphere was one frame ago
+      const double* D = disp + 3u * (size_t)s.id;
+      for (int i = 0; i < 3; ++i) q[i] = ((cur.o[i] + d[i] * s.t) - D[i]) - prev.o[i];
+    } else {
+      for (int i = 0; i < 3; ++i) q[i] = (cur.o[i] + d[i] * s.t) - prev.o[i];
+    }
+  } else {
+    for (int i = 0; i < 3; ++i) q[i] = d[i];  // (sky: a point at infinity)
+  }
+  for (int i = 0; i < 3; ++i) A[i] = prev.ll[i] - prev.o[i];
+  double n0[3], n1[3], n2[3];
+  reproj_cross(prev.h, prev.v, n0); reproj_cross(prev.v, A, n1); reproj_cross(A, prev.h, n2);
+  const double det = reproj_dot(A, n0);
+  const double a = reproj_dot(q, n0) / det, b = reproj_dot(q, n1) / det, cc = reproj_dot(q, n2) / det;
+  if (!(a > 0.0) || !reproj_finite(a) || !reproj_finite(b) || !reproj_finite(cc)) return out;
+  const double fx = (b / a) * wm1 - 0.5, fy = ((double)height - (cc / a) * hm1) - 0.5;
+  if (!(fx >= -1.0 && fx < (double)width && fy >= -1.0 && fy < (double)height)) return out;
+  const double x0d = floor(fx), y0d = floor(fy);
+  const int x0 = (int)x0d, y0 = (int)y0d;
+  const float wx = (float)(fx - x0d), wy = (float)(fy - y0d);
+  const double lim = (double)k.tau_z * a, lim2 = lim * lim;  // (a: the previous camera's ray parameter of this surface point)
+  const DnGuide g = src.guide(p);
+  float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, sn = 0.0f;
+  for (int j = 0; j < 2; ++j) {
+    const int qy = y0 + j;
+    if (qy < 0 || qy >= (int)height) continue;
+    const float wj = j ? wy : 1.0f - wy;
+    for (int i = 0; i < 2; ++i) {
+      const int qx = x0 + i;
+      if (qx < 0 || qx >= (int)width) continue;
+      const size_t t = (size_t)qy * width + (size_t)qx;
+      const RpHist h = src.prev_hist(t);
+      if (!(h.n > 0.0f) || h.r != h.r || h.g != h.g || h.b != h.b) continue;
+      const SurfRec sp = src.prev_surf(t);
+      if (sp.id != s.id) continue;  // (another sphere, or sky against a surface)
+      const DnGuide gp = src.prev_guide(t);
+      const float e0 = gp.n[0] - g.n[0], e1 = gp.n[1] - g.n[1], e2 = gp.n[2] - g.n[2];
+      if (!((e0 * e0 + e1 * e1) + e2 * e2 <= k.tau_n)) continue;
+      const float a0 = gp.a[0] - g.a[0], a1 = gp.a[1] - g.a[1], a2 = gp.a[2] - g.a[2];
+      if (!((a0 * a0 + a1 * a1) + a2 * a2 <= k.tau_a)) continue;
+      if (hit) {
+        const double dt = sp.t - a;
+        if (!(dt * dt <= lim2)) continue;
+      }
+      const float w = (i ? wx : 1.0f - wx) * wj;
+      sr = sr + w * h.r; sg = sg + w * h.g; sb = sb + w * h.b;
+      sw = sw + w;
+      sn = sn + w * h.n;
+    }
+  }
+  if (!(sw > 0.0f)) return out;
+  const float n1f = sn / sw + 1.0f, n = n1f < k.n_max ? n1f : k.n_max;
+  const float floor_a = (s.kind == RT_MAT_METAL || s.kind == RT_MAT_GLASS) ? k.alpha_specular : k.alpha_min;
+  const float inv = 1.0f / n, alpha = floor_a > inv ? floor_a : inv;
+  const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
+  out.r = hr + alpha * (c.r - hr); out.g = hg + alpha * (c.g - hg); out.b = hb + alpha * (c.b - hb);
+  out.n = n;
+  return out;
+}
+
 }  // namespace rtc

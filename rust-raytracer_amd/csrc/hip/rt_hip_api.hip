@@ -148,6 +148,13 @@ struct RtHipScene {
     struct Scratch { DevBuf centre, plan_large, range, lflag, lpos, count, start, cursor, block_sum, counts, raw_items, raw_cell; } gb;
     rtc::GridPlan plan;
     std::vector<double> keep_motion;
+    // each sphere's centre at shutter time 0.5 of the tables above, c + (c1 - c) * 0.5 in f64 ([n][3]; rt_hip_temporal_surface's displacement)
+    std::vector<double> mid;
+    void set_mid(const std::vector<double>& motion) {
+      mid.resize(3 * spheres.size());
+      for (size_t i = 0; i < spheres.size(); ++i)
+        for (int k = 0; k < 3; ++k) mid[3 * i + k] = spheres[i].center[k] + (motion.empty() ? 0.0 : motion[4 * i + k]) * 0.5;
+    }
     bool has_lights = false, simple_colour = false;
     int num_cus = 0;
     size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
@@ -230,6 +237,13 @@ struct RtHipScene {
   bool tp_valid = false;
   double tp_cam[12] = {};
   float tp_k[5] = {RT_TEMPORAL_ALPHA_MIN, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH};
+  // ... with surface tracking (rt_hip_temporal_surface): two surface records (x 16 B) used alternately like the guides,
+  // the displacement table (n_spheres x 24 B) and its host staging (kept as long as the scene: HIP copied from it), and each sphere's
+  // centre at shutter time 0.5 of the tables the last temporal frame rendered with.  Allocated at first use in surface mode only.
+  bool tp_surface = false;
+  float tp_alpha_specular = RT_TEMPORAL_SURFACE_ALPHA_SPECULAR;
+  DevBuf tp_surf[2], tp_disp;
+  std::vector<double> tp_mid, tp_disp_host;
   // adaptive frames, host form (rt_hip_render_adaptive_to_host): its own now / prev accumulators and per-tile list, errors and
   // counts (allocated at first use), and what each round of the last frame did: {tiles, samples per pixel after it, kernel ms}
   DevBuf ad_now, ad_prev, ad_list, ad_err, ad_spp;
@@ -376,6 +390,7 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   r->simple_colour = t.simple_colour;
   r->grid = t.grid;
   r->spheres.assign(scene->spheres, scene->spheres + scene->n_spheres);
+  r->set_mid(t.motion);
   {
     hipDeviceProp_t prop;
     RT_HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -1063,6 +1078,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
   if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
+  if (!std::strcmp(key, "temporal_surface")) return s->tp_surface ? 1 : 0;
   // the last rt_hip_render_adaptive_to_host: its rounds, and round i's tiles, samples per pixel after it, kernel time in microseconds
   if (!std::strcmp(key, "adaptive_rounds")) return (int64_t)s->ad_rounds.size();
   for (const char* f : {"adaptive_round_tiles_", "adaptive_round_spp_", "adaptive_round_kernel_us_"}) {
@@ -1344,6 +1360,71 @@ extern "C" int rt_hip_reproject(RtHipScene* s, const void* d_linear, const void*
   return reproject_frame(s, d_linear, d_aov, d_prev_history, d_prev_aov, prev_camera, k, d_out_history, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------------------- surface tracking
+extern "C" int rt_hip_render_surface(RtHipScene* s, const RtRowTiles* tiles, void* d_surface, void* stream) {
+  const int rc = check_whole_frame(s, tiles);
+  if (rc != RT_OK) return rc;
+  if (!d_surface) return fail(RT_ERR_INVALID, "null surface buffer");
+  if (reinterpret_cast<uintptr_t>(d_surface) & 15u) return fail(RT_ERR_INVALID, "the surface buffer must be 16-byte aligned");
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px == 0) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  using SurfaceKernel = void (*)(const rtc::DevScene, uint4*);
+  static const SurfaceKernel table[4] = {rtk::rt_surface<false, false>, rtk::rt_surface<true, false>, rtk::rt_surface<false, true>, rtk::rt_surface<true, true>};
+  hipLaunchKernelGGL(table[(s->dev.motion ? 1 : 0) | (s->dev.medium ? 2 : 0)], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, (uint4*)d_surface);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+namespace {
+// arguments checked by the caller; k = alpha_min, n_max, tau_n, tau_a, tau_z
+int reproject_surface_frame(RtHipScene* s, const void* d_linear, const void* d_aov, const void* d_surface, const void* d_prev_history, const void* d_prev_aov,
+                            const void* d_prev_surface, const double prev_camera[12], const double* d_displacement, const float k[5], float alpha_specular,
+                            void* d_out_history, hipStream_t stream) {
+  double cur[12];
+  scene_camera(s, cur);
+  rtk::RpSurfArgs a;
+  a.lin = (const float*)d_linear; a.aov = (const float4*)d_aov; a.prev_h = (const float4*)d_prev_history; a.prev_aov = (const float4*)d_prev_aov;
+  a.surf = (const uint4*)d_surface; a.prev_surf = (const uint4*)d_prev_surface;
+  a.disp = d_displacement;
+  a.cur = reproj_cam(cur); a.prev = reproj_cam(prev_camera);
+  a.n_disp = s->host.n_spheres; a.width = s->host.width; a.height = s->host.height;
+  a.k = rtc::ReprojSurfK{k[0], alpha_specular, k[1], k[2], k[3], k[4]};
+  hipLaunchKernelGGL(rtk::rt_reproject_surface, px_grid(s), dim3(16, 16), 0, stream, a, (float4*)d_out_history);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_hip_reproject_surface(RtHipScene* s, const void* d_linear, const void* d_aov, const void* d_surface, const void* d_prev_history,
+                                        const void* d_prev_aov, const void* d_prev_surface, const double prev_camera[12], const double* d_displacement,
+                                        float alpha_min, float alpha_specular, float n_max, float tau_n, float tau_a, float tau_z, void* d_out_history,
+                                        void* stream) {
+  int rc = check_whole_frame(s, nullptr);
+  if (rc != RT_OK) return rc;
+  if ((rc = check_reproject_params(alpha_min, n_max, tau_n, tau_a, tau_z)) != RT_OK) return rc;
+  if (!(alpha_specular >= 0.0f && alpha_specular <= 1.0f)) return fail(RT_ERR_INVALID, "alpha_specular must lie in [0, 1]");
+  if (!d_linear || !d_aov || !d_surface || !d_prev_history || !d_prev_aov || !d_prev_surface || !prev_camera || !d_out_history)
+    return fail(RT_ERR_INVALID, "null argument");
+  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  for (const void* q : {d_aov, d_surface, d_prev_history, d_prev_aov, d_prev_surface, (const void*)d_out_history})
+    if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(RT_ERR_INVALID, "the guide, surface and history buffers must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_displacement) & 7u) return fail(RT_ERR_INVALID, "the displacement table must be 8-byte aligned");
+  const size_t px = (size_t)s->host.width * s->host.height;
+  if (px == 0) return RT_OK;
+  // (an output over an input would be read by other threads while it is written)
+  const uintptr_t o0 = (uintptr_t)d_out_history, o1 = o0 + px * 16;
+  for (const std::pair<uintptr_t, size_t> in : {std::make_pair((uintptr_t)d_linear, px * 12), std::make_pair((uintptr_t)d_aov, px * 32),
+                                                std::make_pair((uintptr_t)d_surface, px * 16), std::make_pair((uintptr_t)d_prev_history, px * 16),
+                                                std::make_pair((uintptr_t)d_prev_aov, px * 32), std::make_pair((uintptr_t)d_prev_surface, px * 16),
+                                                std::make_pair((uintptr_t)d_displacement, d_displacement ? (size_t)s->host.n_spheres * 24 : (size_t)0)})
+    if (in.first < o1 && o0 < in.first + in.second) return fail(RT_ERR_INVALID, "the output must not overlap the inputs");
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const float k[5] = {alpha_min, n_max, tau_n, tau_a, tau_z};
+  return reproject_surface_frame(s, d_linear, d_aov, d_surface, d_prev_history, d_prev_aov, d_prev_surface, prev_camera, d_displacement, k, alpha_specular,
+                                 d_out_history, (hipStream_t)stream);
+}
+
 extern "C" int rt_hip_temporal_configure(RtHipScene* s, float alpha_min, float n_max, float tau_n, float tau_a, float tau_z) {
   if (!s) return fail(RT_ERR_INVALID, "null argument");
   const int rc = check_reproject_params(alpha_min, n_max, tau_n, tau_a, tau_z);
@@ -1357,9 +1438,23 @@ extern "C" int rt_hip_temporal_reset(RtHipScene* s) {
   if (!s) return fail(RT_ERR_INVALID, "null argument");
   RT_HIP_TRY(hipSetDevice(s->device));
   if (s->n_launches) RT_HIP_TRY(hipStreamSynchronize(s->last_stream));  // (the host form is blocking: nothing of it is in flight; a caller's own launch may be)
-  for (DevBuf* b : {&s->tp_accum, &s->tp_hist[0], &s->tp_hist[1], &s->tp_aov[0], &s->tp_aov[1]}) { DevBuf none; b->swap(none); }
+  for (DevBuf* b : {&s->tp_accum, &s->tp_hist[0], &s->tp_hist[1], &s->tp_aov[0], &s->tp_aov[1], &s->tp_surf[0], &s->tp_surf[1], &s->tp_disp}) { DevBuf none; b->swap(none); }
   s->tp_valid = false;
   s->tp_cur = 0;
+  return RT_OK;
+}
+
+// Surface tracking on or off for the host form; a real change drops the history.
+extern "C" int rt_hip_temporal_surface(RtHipScene* s, int enable, float alpha_specular) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (!(alpha_specular >= 0.0f && alpha_specular <= 1.0f)) return fail(RT_ERR_INVALID, "alpha_specular must lie in [0, 1]");
+  const bool on = enable != 0;
+  if (on != s->tp_surface) {
+    const int rc = rt_hip_temporal_reset(s);
+    if (rc != RT_OK) return rc;
+    s->tp_surface = on;
+  }
+  s->tp_alpha_specular = alpha_specular;
   return RT_OK;
 }
 
@@ -1395,6 +1490,14 @@ extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t fram
     if ((rc = s->tp_aov[i].ensure(px * 32, &grew)) != RT_OK) return rc;
     any_grew = any_grew || grew;
   }
+  const uint32_t n_sph = s->host.n_spheres;
+  if (s->tp_surface) {
+    for (int i = 0; i < 2; ++i) {
+      if ((rc = s->tp_surf[i].ensure(px * 16, &grew)) != RT_OK) return rc;
+      any_grew = any_grew || grew;
+    }
+    if ((rc = s->tp_disp.ensure(n_sph ? (size_t)n_sph * 24 : 16)) != RT_OK) return rc;
+  }
   if (any_grew) s->tp_valid = false;
   const int prev = s->tp_cur, cur = prev ^ 1;
   double prev_cam[12];
@@ -1404,12 +1507,26 @@ extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t fram
     if (px) {
       RT_HIP_TRY(hipMemsetAsync(s->tp_hist[prev].p, 0, px * 16, nullptr));
       RT_HIP_TRY(hipMemsetAsync(s->tp_aov[prev].p, 0, px * 32, nullptr));
+      if (s->tp_surface) RT_HIP_TRY(hipMemsetAsync(s->tp_surf[prev].p, 0, px * 16, nullptr));
     }
+  }
+  if (s->tp_surface && n_sph) {  // each sphere's centre now minus its centre in the tables the previous temporal frame rendered with
+    const std::vector<double>& now = s->res->mid;
+    const bool have = s->tp_valid && s->tp_mid.size() == now.size();
+    s->tp_disp_host.resize(now.size());
+    for (size_t i = 0; i < now.size(); ++i) s->tp_disp_host[i] = have ? now[i] - s->tp_mid[i] : 0.0;
+    RT_HIP_TRY(hipMemcpy(s->tp_disp.p, s->tp_disp_host.data(), (size_t)n_sph * 24, hipMemcpyHostToDevice));
   }
   if (px) RT_HIP_TRY(hipMemsetAsync(s->tp_accum.p, 0, px * 24, nullptr));
   rc = rt_hip_accumulate(s, nullptr, begin, spp, s->tp_accum.p, nullptr);
   if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->tp_accum.p, spp, nullptr, s->dn_lin.p, nullptr);
   if (rc == RT_OK) rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(spp), s->tp_aov[cur].p, nullptr);
+  if (s->tp_surface) {
+    if (rc == RT_OK) rc = rt_hip_render_surface(s, nullptr, s->tp_surf[cur].p, nullptr);
+    if (rc == RT_OK && px)
+      rc = reproject_surface_frame(s, s->dn_lin.p, s->tp_aov[cur].p, s->tp_surf[cur].p, s->tp_hist[prev].p, s->tp_aov[prev].p, s->tp_surf[prev].p, prev_cam,
+                                   n_sph ? s->tp_disp.get<const double>() : nullptr, s->tp_k, s->tp_alpha_specular, s->tp_hist[cur].p, nullptr);
+  } else
   if (rc == RT_OK && px) rc = reproject_frame(s, s->dn_lin.p, s->tp_aov[cur].p, s->tp_hist[prev].p, s->tp_aov[prev].p, prev_cam, s->tp_k, s->tp_hist[cur].p, nullptr);
   const float sigma[4] = {RT_DENOISE_SIGMA_COLOR, RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_ALBEDO, RT_DENOISE_SIGMA_INV_DEPTH};
   if (rc == RT_OK) rc = denoise_frame(s, s->tp_hist[cur].p, s->tp_aov[cur].p, iterations, sigma, nullptr, s->frame.p, nullptr, true);
@@ -1420,6 +1537,7 @@ extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t fram
   s->tp_cur = cur;
   s->tp_valid = true;
   scene_camera(s, s->tp_cam);
+  if (s->tp_surface) s->tp_mid = s->res->mid;
   if (stats) {
     *stats = st;
     stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1656,6 +1774,7 @@ int scene_update(RtHipScene* s, const double* center, const double* center1, boo
   r.n_moving = t.n_moving;
   r.grid = j.G;
   r.spheres.swap(r.next_spheres);
+  r.set_mid(t.motion);
   rc = adopt_tables(s);
   pc.mark("update.configuration");
   return rc;

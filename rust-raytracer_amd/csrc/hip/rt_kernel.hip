@@ -1389,6 +1389,60 @@ __global__ __launch_bounds__(256) void rt_reproject(const float* __restrict__ li
   out[(size_t)y * width + x] = make_float4(o.r, o.g, o.b, o.n);
 }
 
+// --------------------------------------------------------------------------- temporal reprojection with surface tracking
+// The surface record of every pixel (rt_core.h surface_pixel): one thread per pixel, 16 x 16 blocks, one ray through the grid walk,
+// one 16-byte store {id, kind, t}.  Reads the scene's tables and camera only.  MOTION / MEDIUM as rt_aov's; no albedo is evaluated,
+// so there is no LENS or SOLID form.
+__device__ __forceinline__ uint4 surf_pack(const SurfRec& r) {
+  const unsigned long long tb = (unsigned long long)__double_as_longlong(r.t);
+  return make_uint4(r.id, r.kind, (uint32_t)tb, (uint32_t)(tb >> 32));
+}
+__device__ __forceinline__ SurfRec surf_unpack(const uint4 v) {
+  SurfRec r;
+  r.id = v.x; r.kind = v.y;
+  r.t = __longlong_as_double((long long)((unsigned long long)v.z | ((unsigned long long)v.w << 32)));
+  return r;
+}
+template <bool MOTION, bool MEDIUM>
+__global__ __launch_bounds__(256) void rt_surface(const DevScene sc, uint4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x >= sc.width || y >= sc.height) return;
+  const GlobalTables tb{sc.geom, sc.matc};
+  out[(size_t)y * sc.width + x] = surf_pack(surface_pixel<MOTION, MEDIUM>(sc, tb, x, y));
+}
+
+// One step of the history with surface tracking (rt_core.h reproject_surface_pixel): one thread per pixel, 16 x 16 blocks.  Per pixel:
+// this frame's colour (three f32 loads), surface record (one 16-byte load) and guide (two); per tap the previous history (one 16-byte
+// load), then its surface record (one) and only for a tap of the same sphere its guide (two); one 16-byte store.  A hit reads three
+// f64 of the displacement table.  Every load is a whole record: nothing is carried across taps, so the four taps reuse the registers.
+struct RpSurfSrc {
+  RpSrc base;
+  const uint4* surf_cur;
+  const uint4* surf_prev;
+  __device__ __forceinline__ DnColour colour(size_t i) const { return base.colour(i); }
+  __device__ __forceinline__ DnGuide guide(size_t i) const { return base.guide(i); }
+  __device__ __forceinline__ DnGuide prev_guide(size_t i) const { return base.prev_guide(i); }
+  __device__ __forceinline__ RpHist prev_hist(size_t i) const { return base.prev_hist(i); }
+  __device__ __forceinline__ SurfRec surf(size_t i) const { return surf_unpack(surf_cur[i]); }
+  __device__ __forceinline__ SurfRec prev_surf(size_t i) const { return surf_unpack(surf_prev[i]); }
+};
+struct RpSurfArgs {
+  const float* lin;
+  const float4 *aov, *prev_h, *prev_aov;
+  const uint4 *surf, *prev_surf;
+  const double* disp;
+  ReprojCam cur, prev;
+  uint32_t n_disp, width, height;
+  ReprojSurfK k;
+};
+__global__ __launch_bounds__(256) void rt_reproject_surface(const RpSurfArgs a, float4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x >= a.width || y >= a.height) return;
+  const RpSurfSrc src{RpSrc{a.lin, a.aov, a.prev_h, a.prev_aov}, a.surf, a.prev_surf};
+  const RpHist o = reproject_surface_pixel(src, a.cur, a.prev, a.disp, a.n_disp, a.width, a.height, x, y, a.k);
+  out[(size_t)y * a.width + x] = make_float4(o.r, o.g, o.b, o.n);
+}
+
 #ifdef RT_TEST_PROBES
 // --------------------------------------------------------------------------- device self-test
 // f64 sqrt / divide / f32 sqrt must be correctly rounded on the GPU for bit-parity with the CPU

@@ -39,6 +39,10 @@
 // and filtered spatially (rt_hip_render_frame_temporal_to_host, RT_DENOISE_ITERATIONS iterations) on one resident scene.  The turn per
 // frame must be named: --orbit is required (0 keeps the camera still).  Frame 0 is the `--denoise` one-shot frame, byte for byte.
 // PNGs are written on the writer threads.  One GPU: RT_GPUS > 1 is refused.
+// `--temporal-surface` (only in this mode) turns on surface tracking: moved spheres keep their history, Metal and Glass
+// pixels get the floor `--temporal-alpha-specular B` on alpha (default RT_TEMPORAL_SURFACE_ALPHA_SPECULAR; needs --temporal-surface).
+// `--temporal-alpha A` (only in this mode) sets alpha_min, the floor everywhere else (default RT_TEMPORAL_ALPHA_MIN, with
+// --temporal-surface RT_TEMPORAL_SURFACE_ALPHA_MIN).  A and B lie in [0, 1]; anything else: the usage line.
 //
 // Thin lens: a scene whose camera has a non-zero "aperture" renders through the lens in every mode above —
 // rt_camera_derive_lens gives the camera on the focus plane and the lens, set next to each other on the resident scene or group
@@ -300,11 +304,17 @@ int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool den
 
 // --frames N --orbit DEG [--shutter S] --denoise: the animation on one resident scene through the temporal host form, frame f's PNG
 // encoded on the writer threads while frame f + 1 renders (1 + W host buffers: the frame being rendered + one per writer)
-int animate_temporal(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
+// surface: --temporal-surface; alpha, alpha_specular: the two floors, < 0 = not given
+int animate_temporal(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter, bool surface, double alpha, double alpha_specular) {
   RtScene* sc = rt_scene_get_mut(sf);
   RtHipScene* hs = nullptr;
   const auto t_create = std::chrono::steady_clock::now();
   int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
+  if (rc == RT_OK && (surface || alpha >= 0.0)) {
+    const float a_min = alpha >= 0.0 ? (float)alpha : (surface ? RT_TEMPORAL_SURFACE_ALPHA_MIN : RT_TEMPORAL_ALPHA_MIN);
+    rc = rt_hip_temporal_configure(hs, a_min, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH);
+    if (rc == RT_OK && surface) rc = rt_hip_temporal_surface(hs, 1, alpha_specular >= 0.0 ? (float)alpha_specular : RT_TEMPORAL_SURFACE_ALPHA_SPECULAR);
+  }
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
   const auto t_begin = std::chrono::steady_clock::now();
   double cam[11], lens[2];
@@ -492,11 +502,18 @@ int run(int argc, char** argv) {
   const auto t_main = std::chrono::steady_clock::now();
   int frames = 0;
   long passes = 0, min_spp = 16;
-  double orbit = 0.0, threshold = 0.0, shutter = -1.0;
-  bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false, denoise = false;
+  double orbit = 0.0, threshold = 0.0, shutter = -1.0, t_alpha = -1.0, t_alpha_specular = -1.0;
+  bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false, denoise = false, t_surface = false;
   for (int i = 3; i < argc && !bad_args; ++i) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+    else if (!std::strcmp(argv[i], "--temporal-surface")) t_surface = true;
+    else if ((!std::strcmp(argv[i], "--temporal-alpha") || !std::strcmp(argv[i], "--temporal-alpha-specular")) && i + 1 < argc) {
+      double& dst = std::strcmp(argv[i], "--temporal-alpha") ? t_alpha_specular : t_alpha;
+      char* end = nullptr;
+      dst = std::strtod(argv[++i], &end);
+      if (end == argv[i] || *end != '\0' || !(dst >= 0.0 && dst <= 1.0)) bad_args = true;
+    }
     else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit = std::atof(argv[++i]); orbit_given = true; }
     else if (!std::strcmp(argv[i], "--shutter") && i + 1 < argc) {
       char* end = nullptr;
@@ -520,6 +537,8 @@ int run(int argc, char** argv) {
   }
   auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
   const bool temporal = denoise && frames > 0 && orbit_given;  // (a denoised animation names its turn per frame)
+  if (!temporal && (t_surface || t_alpha >= 0.0 || t_alpha_specular >= 0.0)) bad_args = true;  // (the three flags of the denoised animation alone)
+  if (t_alpha_specular >= 0.0 && !t_surface) bad_args = true;
   if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || (denoise && !temporal))) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
       (denoise && (adapt || ((frames != 0 || orbit_given) && !temporal))) || (argc > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
     return usage();  // main.rs:9-12: usage line, normal return
@@ -562,7 +581,7 @@ int run(int argc, char** argv) {
       status = 101;
     } else {
       if (g_hip_init.joinable()) g_hip_init.join();
-      if (temporal) status = animate_temporal(sf, argv[2], frames, orbit, shutter);
+      if (temporal) status = animate_temporal(sf, argv[2], frames, orbit, shutter, t_surface, t_alpha, t_alpha_specular);
       else status = passes > 0 ? progressive(sf, argv[2], (uint32_t)passes, denoise) : progressive(sf, argv[2], 1u, true, false);
     }
     rt_scene_free(sf);

@@ -77,6 +77,9 @@ def _bind(path, probes):
     L.rt_hip_temporal_configure.argtypes = [C.c_void_p] + [C.c_float] * 5
     L.rt_hip_temporal_reset.argtypes = [C.c_void_p]
     L.rt_hip_temporal_history.argtypes = [C.c_void_p, C.c_void_p]
+    L.rt_hip_render_surface.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p]
+    L.rt_hip_reproject_surface.argtypes = [C.c_void_p] * 7 + [C.POINTER(C.c_double), C.c_void_p] + [C.c_float] * 6 + [C.c_void_p, C.c_void_p]
+    L.rt_hip_temporal_surface.argtypes = [C.c_void_p, C.c_int, C.c_float]
     L.rt_abi_sizeof.argtypes = [C.c_char_p]
     L.rt_abi_sizeof.restype = C.c_size_t
     L.rt_abi_version.restype = C.c_uint32
@@ -324,6 +327,33 @@ class HipScene:
         out = np.zeros((self.height, self.width, 4), np.float32)
         _check(self._L.rt_hip_temporal_history(self._h, out.ctypes.data), self._L)
         return out
+
+    # include/rt_abi.h RT_TEMPORAL_SURFACE_*: alpha_min, alpha_specular the CLI's --temporal-surface configures (the best of a sweep)
+    TEMPORAL_SURFACE_PARAMS = (0.5, 1.0)
+
+    def render_surface(self, d_surface, tiles=None, stream=0):
+        """enqueue the surface record of every pixel: 16 bytes {uint32 id, uint32 kind, float64 t} of what the
+        pixel-centre pinhole ray meets first (id = kind = 0xFFFFFFFF, t = 0: the sky) into d_surface (height x width x 16 bytes,
+        16-byte aligned); whole frames only (tiles must be None)"""
+        _check(self._L.rt_hip_render_surface(self._h, C.byref(tiles) if tiles is not None else None, C.c_void_p(d_surface or None),
+                                             C.c_void_p(stream or None)), self._L)
+
+    def reproject_surface(self, d_linear, d_aov, d_surface, d_prev_history, d_prev_aov, d_prev_surface, prev_camera, d_out_history, d_displacement=0,
+                          params=TEMPORAL_PARAMS, alpha_specular=TEMPORAL_SURFACE_PARAMS[1], stream=0):
+        """enqueue one temporal step with surface tracking: reproject() with the two frames' surface records and d_displacement (0, or
+        n_spheres x 3 float64 on the device: each sphere's centre now minus its centre one frame ago); params = (alpha_min, n_max, tau_n,
+        tau_a, tau_z), alpha_specular = the floor on alpha of Metal and Glass pixels"""
+        cam = (C.c_double * 12)(*[float(x) for x in prev_camera]) if prev_camera is not None else None
+        a_min, n_max, tau_n, tau_a, tau_z = (float(x) for x in params)
+        _check(self._L.rt_hip_reproject_surface(self._h, C.c_void_p(d_linear or None), C.c_void_p(d_aov or None), C.c_void_p(d_surface or None),
+                                                C.c_void_p(d_prev_history or None), C.c_void_p(d_prev_aov or None), C.c_void_p(d_prev_surface or None),
+                                                cam, C.c_void_p(d_displacement or None), a_min, float(alpha_specular), n_max, tau_n, tau_a, tau_z,
+                                                C.c_void_p(d_out_history or None), C.c_void_p(stream or None)), self._L)
+
+    def temporal_surface(self, enable, alpha_specular=TEMPORAL_SURFACE_PARAMS[1]):
+        """render_frame_temporal_to_host() with (True) or without (False, how a scene starts) surface tracking; a change of mode drops
+        the history.  temporal_configure() supplies the other five values in both modes."""
+        _check(self._L.rt_hip_temporal_surface(self._h, 1 if enable else 0, float(alpha_specular)), self._L)
 
     def tile_grid(self, tiles=None):
         """the pixel tiles of adaptive sampling for `tiles`' rows: (tile width, tile height, tiles_x, tiles_y); id = ty * tiles_x + tx"""

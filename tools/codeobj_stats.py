@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Register / spill / scratch figures of every kernel in librt_hip.so, from the compiler's own metadata.
 
-    python tools/codeobj_stats.py [extra hipcc flags ...]  > profiles/rNN_codeobj.txt
+    python tools/codeobj_stats.py [--brief] [extra hipcc flags ...]  > profiles/rNN_codeobj.txt
 
 Compiles rt_hip_api.hip and rt_grid_build.hip (the device grid build) for gfx950 with the product's flags (+ extras) and -save-temps into a scratch directory
 and prints one line per kernel: VGPRs, SGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, code size, and a static
 instruction census of the megakernel instantiations (v_mov share: the copies at control-flow joins).
-No GPU needed."""
+--brief: the register, spill and scratch figures alone, for before / after pairs that are compared line by line.  No GPU needed."""
 import os
 import re
 import subprocess
@@ -30,17 +30,17 @@ def demangle_mk(name):
 
 
 def main():
-    extra = sys.argv[1:]
+    extra = [x for x in sys.argv[1:] if x != "--brief"]
     print("# hipcc " + " ".join(FLAGS + extra))
     for src in SRCS:
         with tempfile.TemporaryDirectory() as td:
             subprocess.run(["hipcc", *FLAGS, *extra, "-shared", src, "-o", os.path.join(td, "x.so"), "-save-temps"], check=True, cwd=td,
                            stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             asm = open(os.path.join(td, os.path.splitext(os.path.basename(src))[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
-        report(asm)
+        report(asm, "--brief" in sys.argv[1:])
 
 
-def report(asm):
+def report(asm, brief=False):
     # metadata block: one YAML record per kernel
     meta = {}
     for rec in re.split(r"\n  - \.", asm[asm.index("amdhsa.kernels:"):]):
@@ -54,6 +54,9 @@ def report(asm):
     for name, f in meta.items():
         line = (f"{demangle_mk(name):70s} vgpr {int(f['vgpr_count']):3d}  sgpr {int(f['sgpr_count']):3d}  vgpr_spill {int(f['vgpr_spill_count']):3d}  "
                 f"sgpr_spill {int(f['sgpr_spill_count']):3d}  scratch {int(f['private_segment_fixed_size']):4d} B/lane")
+        if brief:
+            print(re.sub(r"  +", "  ", line))
+            continue
         b = bodies.get(name)
         if "rtgb" in name:   # (the grid build's kernels: their static LDS too)
             line += f"  lds {int(f.get('group_segment_fixed_size', 0)):5d} B"
