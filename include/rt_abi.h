@@ -88,6 +88,25 @@ typedef struct RtSphere {
   uint32_t reserved;
 } RtSphere;
 
+/* A quad (an extension of the schema; the reference has no such object and its loader rejects the file): the flat
+ * parallelogram q + a u + b v, 0 <= a, b <= 1, two-sided.  The material fields mean what they mean in RtSphere; a quad may be
+ * Lambertian, Metal, Glass, Checker or Noise (the solid's pattern in the quad's frame: centre = q).  Texture, Light and Medium quads
+ * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads never move. */
+typedef struct RtQuad {
+  double q[3], u[3], v[3];
+  double fuzz_or_ior;
+  double h_offset;
+  uint64_t tex_w;
+  uint64_t tex_h;
+  float albedo[3];
+  uint32_t kind;
+  uint32_t tex_id;
+  uint32_t reserved;
+} RtQuad;
+/* The most quads a scene may hold; more is RT_ERR_UNSUPPORTED.  There is no spatial structure over the quads: EVERY ray segment tests
+ * EVERY quad, so the cost of a segment is linear in their number. */
+#define RT_MAX_QUADS 1024u
+
 /* decoded texture pixels, RGB8 (materials.rs:213-219) */
 typedef struct RtTexture {
   const uint8_t* rgb8;
@@ -226,6 +245,14 @@ void rt_scene_lens(const RtSceneFile*, double out[2]);
  * sphere without the key), or NULL when no sphere of the file has the key.  Owned by the scene file.  The loader rejects a
  * duplicate center1, a non-finite center1 - center and center1 on a Light sphere. */
 const double* rt_scene_motion(const RtSceneFile*);
+/* Quads and boxes (an extension of the schema; the reference's loader rejects both forms: missing `center`).  An element
+ * of "objects" with the keys "q", "u", "v", "material" (points {x, y, z}) instead of "center", "radius" is a quad;
+ * {"box": {"min": [x, y, z], "max": [x, y, z]}, "material": ...} is an axis-aligned box (min_c < max_c on every axis) that expands, in
+ * place in the quad order, to the six quads csrc/common/rt_quad.h lists, in that order, built with the operations listed there
+ * (rt_scene_to_json writes the six quads).  Spheres keep their relative order in RtScene.spheres, quads theirs here.  The quads of
+ * the file, *n of them, or NULL (and *n = 0) for a file without one.  Owned by the scene file.  The loader rejects, naming objects[i]
+ * by the file's own index: mixed keys, a duplicate key, "center1" on a quad, a degenerate quad, a material a quad cannot have. */
+const RtQuad* rt_scene_quads(const RtSceneFile*, uint32_t* n);
 /* Camera::new with a thin lens of focus distance f, r = aperture / 2: out = origin[3], lower_left[3], horizontal[3], vertical[3]
  * (on the focus plane), focal_length, u[3], v[3], r.  aperture 0: the pinhole — the first 13 values are rt_camera_derive's bits,
  * whatever focus_dist.  What rt_hip_set_camera and rt_hip_set_lens take. */
@@ -307,6 +334,26 @@ int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int 
  * rt_hip_scene_create* returns RT_ERR_INVALID for a scale that is not finite and > 0, octaves outside 1..16, a seed above 2^32 - 1 or a
  * mode above 2, and RT_ERR_UNSUPPORTED for a solid in a scene of more than 65 535 spheres (wide tables have no SOLID kernels).
  * rt_hip_scene_query "solids" = the number of Checker and Noise spheres.  A scene without one selects the kernels it always did. */
+/* Quads: the scene of rt_hip_scene_create_moving(scene, center1) plus n_quads flat parallelograms.  n_quads == 0 IS
+ * rt_hip_scene_create_moving: the same tables, the same kernels.  The contract, IEEE f64 without contraction (the code, whose bits are
+ * the contract, is csrc/common/rt_quad.h; its header states every step):
+ *   dot(p, q) = (p0 q0 + p1 q1) + p2 q2; cross as in rt_hip_reproject below.
+ *   once per quad, on the host: n = cross(u, v), nn = dot(n, n), len = sqrt(nn), N = n / len, D = dot(N, Q), w = n / nn.
+ *   per segment (o, d) with the closest hit so far `closest`: den = dot(N, d); fabs(den) < 1e-8 (or NaN): no hit;
+ *   t = (D - dot(N, o)) / den, accepted only if t > 0.001 and t < closest; P = o + d t, p = P - Q, alpha = dot(w, cross(p, v)),
+ *   beta = dot(w, cross(u, p)); accepted iff 0 <= alpha <= 1 and 0 <= beta <= 1.
+ *   record: point P, front_face = dot(d, N) < 0, normal = front_face ? N : -N, t.
+ * Order: quads are tested as if they followed every sphere in object order, quad k before quad k + 1, the comparison strict: on an
+ * equal t a sphere beats a quad and an earlier quad a later one (raytracer.rs:52-57 extended).  Ids: quad k is object n_spheres + k —
+ * in the surface record of rt_hip_render_surface too (rt_hip_reproject_surface takes such an id as "not displaced").
+ * Materials: Lambertian, Metal and Glass scatter unchanged (they see only point, normal, front_face and the incoming direction);
+ * Checker and Noise follow the solid contract with centre = Q.  A quad occludes light rays, media candidates and the first-hit rays of
+ * the AOVs like any surface; a first hit on a quad reports albedo by the material rule, the record's normal, 1 / t and its RT_MAT_*.
+ * RT_ERR_INVALID: a non-finite q, u or v; nn zero, subnormal or not finite; a Texture, Light or Medium quad; solid parameters the
+ * solid contract refuses.  RT_ERR_UNSUPPORTED: more than RT_MAX_QUADS quads; quads in a scene of more than 65 535 spheres (wide tables
+ * have no QUADS kernels).  rt_hip_scene_query "quads" = their number.  rt_hip_scene_update_spheres keeps them.  The QUADS kernels
+ * read the scene's tables from L2 and use the general colour map, whatever the scene's size and albedos. */
+int rt_hip_scene_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out);
 void rt_hip_scene_destroy(RtHipScene*);
 /* Launch the megakernel for the given row tiles on `stream` (a hipStream_t, NULL = default).
  *   d_rgb8    device buffer, rt_tiles_local_rows()*width*3 bytes, packed, top row first;
@@ -338,15 +385,17 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * item lists: what a workgroup stages into LDS once per launch), "texel_bytes" (textures + sky as 4-byte texels in HBM);
  * of the last launch: "lds_bytes" (dynamic LDS of a workgroup), "lds_tables" (1: the tables were staged in LDS),
  * "light_pool_slots" / "light_base_slots" (lit scenes: records in the workgroup's pools of light frames / colour-map bases),
- * "last_kernel" (the key of the megakernel instantiation that ran, nine bits: solid textures 256 | participating media 128 |
+ * "last_kernel" (the key of the megakernel instantiation that ran, ten bits: quads 512 | solid textures 256 | participating media 128 |
  * moving spheres 64 | thin lens 32 | accumulating 16 | wide tables 8 | lights 4 | every albedo in [0, 1] 2 | tables in LDS 1; wide tables
- * never go with tables in LDS, media or solid textures; -1 before the scene's first launch), "lens" (1:
+ * never go with tables in LDS, media, solid textures or quads, and quads never with tables in LDS or the short colour map (bits 1 and
+ * 2); -1 before the scene's first launch), "lens" (1:
  * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
- * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE).
+ * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres and quads of kind RT_MAT_CHECKER or RT_MAT_NOISE), "quads" (rt_hip_scene_create_quads).
  * -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Diagnostics: a copy of one resident table, as the kernels read it.  name: "grid" (the GridDesc bytes), "cell_word", "cell_items",
- * "large", "geom", "large_geom", "motion" (empty for a static scene).  A blocking device-to-host copy into out (cap bytes); *needed
+ * "large", "geom", "large_geom", "motion" (empty for a static scene), "quads" (RtQuadRec of csrc/common/rt_quad.h, 128 B each: q, u, v, N, w,
+ * D; empty for a scene without quads).  A blocking device-to-host copy into out (cap bytes); *needed
  * receives the table's size, and out may be NULL to ask for it.  An unknown name, or a buffer that is too small: RT_ERR_INVALID. */
 int rt_hip_scene_table(const RtHipScene*, const char* name, void* out, size_t cap, size_t* needed);
 /* Move the spheres of a resident scene.  center = n_spheres x 3 (shutter open), center1 = NULL or n_spheres x 3
@@ -647,6 +696,8 @@ typedef struct RtGroupRank {
 int rt_hip_group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out);
 /* rt_hip_group_create whose every rank is rt_hip_scene_create_moving(scene, center1): motion blur */
 int rt_hip_group_create_moving(const RtScene* scene, const double* center1, uint32_t n_gpus, RtHipGroup** out);
+/* rt_hip_group_create_moving whose every rank is rt_hip_scene_create_quads(scene, center1, quads, n_quads): quads */
+int rt_hip_group_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, uint32_t n_gpus, RtHipGroup** out);
 int rt_hip_group_info(const RtHipGroup*, RtGroupInfo* info);
 uint32_t rt_hip_group_ranks(const RtHipGroup*, RtGroupRank* out, uint32_t cap); /* fills min(cap, n_ranks) entries, returns n_ranks */
 const char* rt_hip_group_fallback_reason(const RtHipGroup*);                    /* "" unless RtGroupInfo.transport_fallback */
@@ -685,7 +736,8 @@ uint32_t rt_hip_group_stacked_row(uint32_t y, uint32_t n_ranks, uint32_t pad_row
  * stream, the packed tiles meet on device 0 through ONE gather (RCCL send/recv over xGMI, or peer copies
  * with RT_GATHER=peer), are de-interleaved by a small kernel and leave in ONE device-to-host copy.  The camera is RtScene's: a
  * pinhole (a lens needs a group or scene and rt_hip_set_lens), and every sphere is static (motion blur needs
- * rt_hip_group_create_moving or rt_hip_scene_create_moving). */
+ * rt_hip_group_create_moving or rt_hip_scene_create_moving).  It takes an RtScene, which holds no quads, so its frames are quad-free
+ * (quads need rt_hip_group_create_quads or rt_hip_scene_create_quads). */
 int rt_render_rgb8(const RtScene* scene, uint8_t* out_rgb8, RtStats* stats);
 const char* rt_strerror(int code);
 

@@ -17,6 +17,17 @@ class RtSphere(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class RtQuad(C.Structure):
+    """a flat parallelogram q + a u + b v; the material fields as RtSphere's"""
+    _fields_ = [("q", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3), ("fuzz_or_ior", C.c_double),
+                ("h_offset", C.c_double), ("tex_w", C.c_uint64), ("tex_h", C.c_uint64),
+                ("albedo", C.c_float * 3), ("kind", C.c_uint32), ("tex_id", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+RT_MAX_QUADS = 1024
+
+
 def checker_odd_pack(rgb):
     """the `odd` colour of a Checker sphere as (tex_w, tex_h): f32 bit patterns, tex_w = bits(r) | bits(g) << 32, tex_h = bits(b)"""
     import struct

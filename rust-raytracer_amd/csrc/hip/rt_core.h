@@ -32,6 +32,7 @@
 #define RT_SOLID_FN __host__ __device__ inline
 #endif
 #include "../common/rt_solid.h"  // the one checker and lattice noise of the solid textures
+#include "../common/rt_quad.h"   // the one quad test
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__ __forceinline__
@@ -202,6 +203,10 @@ struct DevScene {
   // participating media: [n_spheres] the density of a Medium sphere, 0.0 for any other; null for a scene without one.
   // Resident once and shared by views like `motion`.  Read only by the MEDIUM instantiations of the megakernel and of rt_aov.
   const double* medium;
+  // quads (rt_hip_scene_create_quads): [n_quads] records of csrc/common/rt_quad.h; null / 0 for a scene without one.  Quad k
+  // is object n_spheres + k: `mat` and `matc` hold n_spheres + n_quads records.  Read only by the QUADS instantiations.
+  const RtQuadRec* quads;
+  uint32_t n_quads, quads_pad;
 };
 
 // ------------------------------------------------------------------ f64 square root
@@ -1013,6 +1018,57 @@ RT_HD Surface surface_at(V3 o, V3 d, double t, const SphereGeom& g, double inv_r
   s.normal = s.front_face ? outward : neg(outward);              // :68
   return s;
 }
+// ------------------------------------------------------------------ quads
+// The QUADS arm of hit_world: every quad of the scene against the segment (o, d), AFTER every sphere has had its test, quad k before
+// quad k + 1, under the strict rule of rt_quad_hit — on an equal t a sphere beats a quad and an earlier quad a later one.  An accepted
+// quad k is object id_base + k.  COLD and by value (see exact_hit_slow, medium_hit): the division and the two cross products stay out of
+// the walk loop's register budget.  The table and the count are the same for every lane; the device form says so (readfirstlane), and
+// the records, indexed by the uniform counter through the constant address space, arrive as scalar-unit loads.
+RT_HD_COLD HitCB quads_hit(V3 o, V3 d, const RtQuadRec* quads, uint32_t n_quads, uint32_t id_base, double closest, int best) {
+  HitCB r; r.closest = closest; r.best = best;
+  const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const double __attribute__((address_space(4))) * QuadPtrK;
+  const unsigned long long addr = (unsigned long long)(uintptr_t)quads;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)addr), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(addr >> 32));
+  const QuadPtrK base = (QuadPtrK)(uintptr_t)(((unsigned long long)hi << 32) | lo);
+  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_quads);
+#else
+  const double* base = reinterpret_cast<const double*>(quads);
+  const uint32_t n = n_quads;
+#endif
+  static_assert(sizeof(RtQuadRec) == 128, "a quad record is 16 doubles");
+  for (uint32_t k = 0; k < n; ++k) {
+    RtQuadRec q;
+    for (int c = 0; c < 3; ++c) {
+      q.q[c] = base[16u * (size_t)k + c]; q.u[c] = base[16u * (size_t)k + 3 + c]; q.v[c] = base[16u * (size_t)k + 6 + c];
+      q.n[c] = base[16u * (size_t)k + 9 + c]; q.w[c] = base[16u * (size_t)k + 12 + c];
+    }
+    q.d = base[16u * (size_t)k + 15];
+    double t, P[3];
+    if (rt_quad_hit(q, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+  }
+  return r;
+}
+// What a hit on object idx records and the SphereGeom scatter sees: a sphere's (surface_at), or in the QUADS arm for idx >= n_spheres
+// quad idx - n_spheres: no division, the stored N; its "centre" — the frame of a solid's pattern — is Q.
+template <bool QUADS, class Tables>
+RT_HD Surface object_surface(const DevScene& sc, const Tables& tb, V3 o, V3 d, double t, uint32_t idx, double inv_r, SphereGeom& g) {
+  if constexpr (QUADS) {
+    if (idx >= sc.n_spheres) {
+      const RtQuadRec& q = sc.quads[idx - sc.n_spheres];
+      Surface s;
+      s.point = add(o, muls(d, t));                                // ray.rs:18-20: the P the test formed
+      const V3 N = v3(q.n[0], q.n[1], q.n[2]);
+      s.front_face = dot(d, N) < 0.0;
+      s.normal = s.front_face ? N : neg(N);
+      g.cx = q.q[0]; g.cy = q.q[1]; g.cz = q.q[2]; g.r = 0.0;
+      return s;
+    }
+  }
+  g = tb.geom(idx);
+  return surface_at(o, d, t, g, inv_r);
+}
 // sphere.rs:35-43, evaluated only when the closest hit is a Texture (a pure function of the
 // accepted hit, so skipping it for the other candidates changes nothing)
 struct UV {
@@ -1798,7 +1854,7 @@ struct ShadeProf { unsigned long long* t; unsigned long long* last; uint32_t* n_
 #define RT_SHADE_MARK(k) do { } while (0)
 #define RT_SHADE_COUNT(act_) do { } while (0)
 #endif
-template <bool MEDIUM = false, bool SOLID = false, class LaneT, class Tables>
+template <bool MEDIUM = false, bool SOLID = false, bool QUADS = false, class LaneT, class Tables>
 RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, double t, const V3* rnd_pre = nullptr,
                       const double* glass_u_pre = nullptr, const double* light_u_pre = nullptr, ShadeProf* sp = nullptr) {
   (void)sp;
@@ -1810,9 +1866,11 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
       lane_finish_sample(sc, L, sky_color(sc, L.d, L.n_tex_oob));
       return LANE_FINISHED;
     }
-    const SphereGeom g = tb.geom((uint32_t)idx);
-    const MatCore m = tb.mat((uint32_t)idx);
-    Surface h = surface_at(L.o, L.d, t, g, m.inv_r);
+    SphereGeom g;
+    MatCore m;
+    Surface h;
+    if constexpr (QUADS) { m = tb.mat((uint32_t)idx); h = object_surface<true>(sc, tb, L.o, L.d, t, (uint32_t)idx, m.inv_r, g); }
+    else { g = tb.geom((uint32_t)idx); m = tb.mat((uint32_t)idx); h = surface_at(L.o, L.d, t, g, m.inv_r); }
     V3 out_dir = v3(0, 0, 0);
     float att[3];
     int st = scatter<MEDIUM, SOLID>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
@@ -1833,9 +1891,11 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
       col = sky_color(sc, L.d, L.n_tex_oob);
       act = light_ray ? ACT_RETURN : ACT_FINISH;
     } else {
-      const SphereGeom g = tb.geom((uint32_t)idx);
-      const MatCore m = tb.mat((uint32_t)idx);
-      Surface h = surface_at(L.o, L.d, t, g, m.inv_r);
+      SphereGeom g;
+      MatCore m;
+      Surface h;
+      if constexpr (QUADS) { m = tb.mat((uint32_t)idx); h = object_surface<true>(sc, tb, L.o, L.d, t, (uint32_t)idx, m.inv_r, g); }
+      else { g = tb.geom((uint32_t)idx); m = tb.mat((uint32_t)idx); h = surface_at(L.o, L.d, t, g, m.inv_r); }
       point = h.point;
       const int st = scatter<MEDIUM, SOLID>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
       if (st != SCATTER_RAY) {  // :124 Light: its colour; :127-131 absorbed: black
@@ -1934,9 +1994,11 @@ constexpr uint32_t AOV_FLOATS = 8u;
 // MOTION: the first hit at the sample's shutter time (sample_time), through the same MotionTables as the MOTION megakernels.
 // MEDIUM: a first hit inside a medium reports the medium's albedo, normal (0, 0, 0) and the usual 1 / t.
 // SOLID: a first hit on a Checker or Noise sphere reports the colour solid_albedo evaluates there, as Texture its texel.
-template <bool MEDIUM = false, bool SOLID = false, class Tables>
+// QUADS: the quads are tested behind the spheres (quads_hit); a first hit on a quad reports albedo by the material rule, the
+// record's normal and 1 / t.
+template <bool MEDIUM = false, bool SOLID = false, bool QUADS = false, class Tables>
 RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]);
-template <bool LENS, bool MOTION = false, bool MEDIUM = false, bool SOLID = false, class Tables>
+template <bool LENS, bool MOTION = false, bool MEDIUM = false, bool SOLID = false, bool QUADS = false, class Tables>
 RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py, uint32_t n, float out[8]) {
   double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Lane<false> L;
@@ -1944,12 +2006,12 @@ RT_HD void aov_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t
   for (uint32_t s = 0; s < n; ++s) {
     L.s = s;
     lane_begin_sample<LENS>(sc, L, px, py);
-    if constexpr (MOTION) aov_sample<MEDIUM, SOLID>(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
-    else aov_sample<MEDIUM, SOLID>(sc, tb, L, acc);
+    if constexpr (MOTION) aov_sample<MEDIUM, SOLID, QUADS>(sc, motion_tables(tb, sc.motion, sample_time(L.ra)), L, acc);
+    else aov_sample<MEDIUM, SOLID, QUADS>(sc, tb, L, acc);
   }
   for (int i = 0; i < 8; ++i) out[i] = (float)(acc[i] / (double)n);
 }
-template <bool MEDIUM, bool SOLID, class Tables>
+template <bool MEDIUM, bool SOLID, bool QUADS, class Tables>
 RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L, double acc[8]) {
   {
     double closest = T_MAX;
@@ -1959,14 +2021,17 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
       const MediumCtx mc{sc.medium, L.ra, L.node};  // (the camera segment: node 0)
       hit_world_grid<true>(sc, tb, L.o, L.d, closest, best, n_exact, n_steps, &mc);
     } else hit_world_grid(sc, tb, L.o, L.d, closest, best, n_exact, n_steps);
+    if constexpr (QUADS) { const HitCB r = quads_hit(L.o, L.d, sc.quads, sc.n_quads, sc.n_spheres, closest, best); closest = r.closest; best = r.best; }
     float a[3];
     if (best < 0) {  // raytracer.rs:133-163: the sky the ray sees
       const Rgb c = sky_color(sc, L.d, tex_oob);
       a[0] = c.r; a[1] = c.g; a[2] = c.b;
     } else {
-      const SphereGeom g = tb.geom((uint32_t)best);
-      const MatCore m = tb.mat((uint32_t)best);
-      const Surface h = surface_at(L.o, L.d, closest, g, m.inv_r);
+      SphereGeom g;
+      MatCore m;
+      Surface h;
+      if constexpr (QUADS) { m = tb.mat((uint32_t)best); h = object_surface<true>(sc, tb, L.o, L.d, closest, (uint32_t)best, m.inv_r, g); }
+      else { g = tb.geom((uint32_t)best); m = tb.mat((uint32_t)best); h = surface_at(L.o, L.d, closest, g, m.inv_r); }
       a[0] = m.albedo[0]; a[1] = m.albedo[1]; a[2] = m.albedo[2];
       if (m.kind == RT_MAT_GLASS || m.kind == RT_MAT_LIGHT) a[0] = a[1] = a[2] = 1.0f;  // (Glass: white; Light emits (1, 1, 1), materials.rs:65-69)
       else if (m.kind == RT_MAT_TEXTURE) {
@@ -2147,7 +2212,8 @@ RT_HD RpHist reproject_pixel(const Src& src, const ReprojCam& cur, const ReprojC
 constexpr uint32_t SURFACE_NONE = 0xFFFFFFFFu;
 constexpr float SURFACE_SHUTTER_TIME = 0.5f;
 struct SurfRec { uint32_t id, kind; double t; };  // 16 B
-template <bool MEDIUM = false, class Tables>
+// QUADS: the quads behind the spheres; quad k is id n_spheres + k, its kind its RT_MAT_*.
+template <bool MEDIUM = false, bool QUADS = false, class Tables>
 RT_HD SurfRec surface_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, uint32_t pixel) {
   double closest = T_MAX;
   int best = -1;
@@ -2156,12 +2222,13 @@ RT_HD SurfRec surface_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, uint
     const MediumCtx mc{sc.medium, RngAddr{pixel, 0u, sc.seed_lo, sc.seed_hi}, 0u};
     hit_world_grid<true>(sc, tb, o, d, closest, best, n_exact, n_steps, &mc);
   } else hit_world_grid(sc, tb, o, d, closest, best, n_exact, n_steps);
+  if constexpr (QUADS) { const HitCB q = quads_hit(o, d, sc.quads, sc.n_quads, sc.n_spheres, closest, best); closest = q.closest; best = q.best; }
   SurfRec r;
   r.id = SURFACE_NONE; r.kind = SURFACE_NONE; r.t = 0.0;
   if (best >= 0) { r.id = (uint32_t)best; r.kind = tb.mat((uint32_t)best).kind; r.t = closest; }
   return r;
 }
-template <bool MOTION = false, bool MEDIUM = false, class Tables>
+template <bool MOTION = false, bool MEDIUM = false, bool QUADS = false, class Tables>
 RT_HD SurfRec surface_pixel(const DevScene& sc, const Tables& tb, uint32_t px, uint32_t py) {
   const double wm1 = (double)(sc.width - 1u), hm1 = (double)(sc.height - 1u);
   const double u = ((double)px + 0.5) / wm1, v = ((double)sc.height - ((double)py + 0.5)) / hm1;
@@ -2171,8 +2238,8 @@ RT_HD SurfRec surface_pixel(const DevScene& sc, const Tables& tb, uint32_t px, u
   const V3 ver = v3(sc.cam_v[0], sc.cam_v[1], sc.cam_v[2]);
   const V3 d = sub(add(add(llc, muls(hor, u)), muls(ver, v)), origin);
   const uint32_t pixel = py * sc.width + px;
-  if constexpr (MOTION) return surface_ray<MEDIUM>(sc, motion_tables(tb, sc.motion, SURFACE_SHUTTER_TIME), origin, d, pixel);
-  else return surface_ray<MEDIUM>(sc, tb, origin, d, pixel);
+  if constexpr (MOTION) return surface_ray<MEDIUM, QUADS>(sc, motion_tables(tb, sc.motion, SURFACE_SHUTTER_TIME), origin, d, pixel);
+  else return surface_ray<MEDIUM, QUADS>(sc, tb, origin, d, pixel);
 }
 
 // One pixel of rt_hip_reproject_surface: reproject_pixel with the surface point, the tap test and the floor on alpha taken from the

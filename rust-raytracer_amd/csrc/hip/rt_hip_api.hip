@@ -37,10 +37,10 @@ int fail(int code, const std::string& m) { g_err = m; return code; }
       return fail(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                   \
   } while (0)
 
-// Wide tables have no kernel for media or solid textures (rtk::kernel_key_valid): such a scene is refused where its tables are made.
-int check_wide_tables(bool wide, bool media, bool solids) {
-  if (rtk::kernel_key_valid((wide ? rtk::KEY_WIDE : 0) | (media ? rtk::KEY_MEDIUM : 0) | (solids ? rtk::KEY_SOLID : 0))) return RT_OK;
-  return fail(RT_ERR_UNSUPPORTED, std::string(media ? "participating media" : "solid textures") + " in a scene with wide tables (more than 65 535 spheres)");
+// Wide tables have no kernel for media, solid textures or quads (rtk::kernel_key_valid): such a scene is refused where its tables are made.
+int check_wide_tables(bool wide, bool media, bool solids, bool quads = false) {
+  if (rtk::kernel_key_valid((wide ? rtk::KEY_WIDE : 0) | (media ? rtk::KEY_MEDIUM : 0) | (solids ? rtk::KEY_SOLID : 0) | (quads ? rtk::KEY_QUADS : 0))) return RT_OK;
+  return fail(RT_ERR_UNSUPPORTED, std::string(media ? "participating media" : (solids ? "solid textures" : "quads")) + " in a scene with wide tables (more than 65 535 spheres)");
 }
 
 }  // namespace
@@ -128,7 +128,9 @@ struct RtHipScene {
     uint32_t n_moving = 0;
     DevBuf medium;           // participating media: [n] density per sphere, 0 = no medium (HostTables::medium); unallocated without media
     uint32_t n_media = 0;
-    uint32_t n_solids = 0;   // solid textures: Checker and Noise spheres; their parameters are in the `mat` records
+    uint32_t n_solids = 0;   // solid textures: Checker and Noise spheres (and quads); their parameters are in the `mat` records
+    DevBuf quads;            // quads: [n_quads] RtQuadRec; their materials are records n_spheres + k of `mat` and `matc`; unallocated without quads
+    uint32_t n_quads = 0;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -259,6 +261,7 @@ extern "C" uint32_t rt_abi_version(void) { return RT_ABI_VERSION; }
 extern "C" size_t rt_abi_sizeof(const char* name) {
   if (!name) return 0;
   if (!std::strcmp(name, "RtSphere")) return sizeof(RtSphere);
+  if (!std::strcmp(name, "RtQuad")) return sizeof(RtQuad);
   if (!std::strcmp(name, "RtTexture")) return sizeof(RtTexture);
   if (!std::strcmp(name, "RtScene")) return sizeof(RtScene);
   if (!std::strcmp(name, "RtRowTiles")) return sizeof(RtRowTiles);
@@ -369,17 +372,24 @@ extern "C" int rt_hip_scene_create(const RtScene* scene, int device, RtHipScene*
 // motion blur: the tables of a scene whose spheres move from center to center1 over the shutter.  Fixed at creation
 // (the grid lists each moving sphere by its swept box); a null center1, or one equal to every centre, is the static scene.
 extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int device, RtHipScene** out) {
-  if (!scene || !out) return fail(RT_ERR_INVALID, "null argument");
+  return rt_hip_scene_create_quads(scene, center1, nullptr, 0, device, out);
+}
+
+// quads: the scene above plus n_quads flat parallelograms, tested behind the spheres by the QUADS kernels; without a quad every
+// table and every kernel is what rt_hip_scene_create_moving always built and selected
+extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out) {
+  if (!scene || !out || (n_quads && !quads)) return fail(RT_ERR_INVALID, "null argument");
   *out = nullptr;
+  if (n_quads > RT_MAX_QUADS) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_QUADS (1024) quads: every segment tests every quad");
   int n = rt_hip_device_count();
   if (n <= 0) return fail(RT_ERR_NO_DEVICE, rt_strerror(RT_ERR_NO_DEVICE));
   if (device < 0 || device >= n) return fail(RT_ERR_INVALID, "device index out of range");
   if (!rtp::tl_in_group) rtp::reset();
   rtp::Clock pc;
   rtc::HostTables t;
-  std::string why = rtc::build_tables(*scene, t, false, center1);
+  std::string why = rtc::build_tables(*scene, t, false, center1, quads, n_quads);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
-  if (const int refused = check_wide_tables(t.grid.wide, t.n_media, t.n_solids)) return refused;
+  if (const int refused = check_wide_tables(t.grid.wide, t.n_media, t.n_solids, n_quads != 0)) return refused;
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
   pc.mark("scene.texels_rgbx");
@@ -415,6 +425,8 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   if (t.n_media && (rc = upload(r->medium, t.medium)) != RT_OK) return rc;
   r->n_media = t.n_media;
   r->n_solids = t.n_solids;
+  if (n_quads && (rc = upload(r->quads, t.quads)) != RT_OK) return rc;
+  r->n_quads = n_quads;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
@@ -455,6 +467,8 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
   s->dev.large_geom = r->large_geom.get<const rtc::SphereGeom>();
   s->dev.motion = r->n_moving ? r->motion.get<const double>() : nullptr;
   s->dev.medium = r->n_media ? r->medium.get<const double>() : nullptr;
+  s->dev.quads = r->n_quads ? r->quads.get<const RtQuadRec>() : nullptr;
+  s->dev.n_quads = r->n_quads;
   s->res = std::move(r);
   auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
@@ -517,13 +531,15 @@ template <int... SET> std::array<Megakernel, rtk::KERNEL_KEYS> kernel_table(std:
 struct Kernel { int key = -1; Megakernel fn = nullptr; };
 int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
   static const std::array<Megakernel, rtk::KERNEL_KEYS> table = kernel_table(std::make_integer_sequence<int, rtk::KERNEL_SETS - 1>());
-  const int key = (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
+  const int key = (s->res->n_quads ? rtk::KEY_QUADS : 0) | (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
                   (s->dev.lens_r != 0.0 ? rtk::KEY_LENS : 0) | (accum ? rtk::KEY_ACCUM : 0) | (wide ? rtk::KEY_WIDE : 0) | (has_lights ? rtk::KEY_HL : 0) |
                   (s->res->simple_colour ? rtk::KEY_SIMPLE : 0) | (lds_tables ? rtk::KEY_LDS : 0);
   if (!rtk::kernel_key_valid(key)) {
     if (key & rtk::KEY_LDS) return fail(RT_ERR_HIP, "wide cell tables cannot be staged in LDS");
+    if ((key & rtk::KEY_QUADS) && !(key & rtk::KEY_WIDE)) return fail(RT_ERR_HIP, "the QUADS kernels take their tables from L2 and the general colour map");
     if (key & rtk::KEY_MEDIUM) return fail(RT_ERR_UNSUPPORTED, "participating media with wide tables");
-    return fail(RT_ERR_UNSUPPORTED, "solid textures with wide tables");
+    if (key & rtk::KEY_SOLID) return fail(RT_ERR_UNSUPPORTED, "solid textures with wide tables");
+    return fail(RT_ERR_UNSUPPORTED, "quads with wide tables");
   }
   out->key = key;
   out->fn = table[key];
@@ -597,7 +613,7 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
     return bytes(0.0) <= avail;  // (the smallest pools fit)
   };
   const rtk::LdsLayout no_pools = rtk::lds_layout(s->host.n_spheres, G.n_cells, G.n_items, true, false);
-  bool lds_tables = !G.wide && no_pools.total <= rtk::LDS_TABLES_MAX_BYTES;
+  bool lds_tables = !G.wide && !s->res->n_quads && no_pools.total <= rtk::LDS_TABLES_MAX_BYTES;  // (the QUADS kernels exist with tables in L2 only)
   if (has_lights) {
     const size_t fixed = rtc::LIGHT_CENTRES_LDS_MAX * 24u;
     double margin = 0.0;
@@ -1072,7 +1088,8 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
+  if (!std::strcmp(key, "quads")) return (int64_t)s->res->n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
+  if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
   if (!std::strcmp(key, "solids")) return (int64_t)s->res->n_solids;       // spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE
   if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
@@ -1255,10 +1272,14 @@ int denoise_frame(RtHipScene* s, const void* d_linear, const void* d_aov, uint32
   }
   return RT_OK;
 }
-// The feature kernels by the four feature bits of the megakernel's key, (SOLID | MEDIUM | MOTION | LENS) / LENS
+// The feature kernels by the four feature bits of the megakernel's key, (SOLID | MEDIUM | MOTION | LENS) / LENS; the second table: the same
+// sixteen with the QUADS arm, for scenes that hold a quad
 using AovKernel = void (*)(const rtc::DevScene, uint32_t, float4*);
 template <int... F> std::array<AovKernel, 16> aov_kernels(std::integer_sequence<int, F...>) {
   return {rtk::rt_aov<(F & 1) != 0, (F & 2) != 0, (F & 4) != 0, (F & 8) != 0>...};
+}
+template <int... F> std::array<AovKernel, 16> aov_quads_kernels(std::integer_sequence<int, F...>) {
+  return {rtk::rt_aov_quads<(F & 1) != 0, (F & 2) != 0, (F & 4) != 0, (F & 8) != 0>...};
 }
 }  // namespace
 
@@ -1275,7 +1296,8 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   static const std::array<AovKernel, 16> table = aov_kernels(std::make_integer_sequence<int, 16>());
   const int features = (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
                        (s->dev.lens_r != 0.0 ? rtk::KEY_LENS : 0);
-  hipLaunchKernelGGL(table[features / rtk::KEY_LENS], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  static const std::array<AovKernel, 16> quads_table = aov_quads_kernels(std::make_integer_sequence<int, 16>());
+  hipLaunchKernelGGL((s->res->n_quads ? quads_table : table)[features / rtk::KEY_LENS], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -1370,8 +1392,9 @@ extern "C" int rt_hip_render_surface(RtHipScene* s, const RtRowTiles* tiles, voi
   if (px == 0) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
   using SurfaceKernel = void (*)(const rtc::DevScene, uint4*);
-  static const SurfaceKernel table[4] = {rtk::rt_surface<false, false>, rtk::rt_surface<true, false>, rtk::rt_surface<false, true>, rtk::rt_surface<true, true>};
-  hipLaunchKernelGGL(table[(s->dev.motion ? 1 : 0) | (s->dev.medium ? 2 : 0)], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, (uint4*)d_surface);
+  static const SurfaceKernel table[8] = {rtk::rt_surface<false, false>, rtk::rt_surface<true, false>, rtk::rt_surface<false, true>, rtk::rt_surface<true, true>,
+                                         rtk::rt_surface_quads<false, false>, rtk::rt_surface_quads<true, false>, rtk::rt_surface_quads<false, true>, rtk::rt_surface_quads<true, true>};
+  hipLaunchKernelGGL(table[(s->dev.motion ? 1 : 0) | (s->dev.medium ? 2 : 0) | (s->res->n_quads ? 4 : 0)], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, (uint4*)d_surface);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -1756,7 +1779,7 @@ int scene_update(RtHipScene* s, const double* center, const double* center1, boo
   if (!j.all_large && !wide && (cnt.max_count > rtc::CELL_MAX_COUNT || cnt.n_items >= rtc::CELL_START_MASK)) wide = true;
   pc.mark("update.count_kernels_and_readback");
   j.G.n_items = (uint32_t)cnt.n_items; j.G.n_large = (uint32_t)cnt.n_large; j.G.wide = (!j.all_large && wide) ? 1u : 0u;
-  if ((rc = check_wide_tables(j.G.wide, r.n_media, r.n_solids)) != RT_OK) return rc;
+  if ((rc = check_wide_tables(j.G.wide, r.n_media, r.n_solids, r.n_quads != 0)) != RT_OK) return rc;
   if ((rc = room(r.spare.cell_word, (size_t)j.G.n_cells * (j.G.wide ? 16u : 8u))) != RT_OK || (rc = room(r.spare.cell_items, (size_t)j.G.n_items * (j.G.wide ? 4u : 2u))) != RT_OK ||
       (rc = room(gb.raw_items, (size_t)j.G.n_items * 4)) != RT_OK || (rc = room(gb.raw_cell, (size_t)j.G.n_items * 4)) != RT_OK ||
       (rc = room(r.spare.large, (size_t)j.G.n_large * 4)) != RT_OK || (rc = room(r.spare.large_geom, (size_t)j.G.n_large * sizeof(rtc::SphereGeom))) != RT_OK)
@@ -1808,6 +1831,7 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "geom")) { src = r.geom.p; bytes = (size_t)s->host.n_spheres * sizeof(rtc::SphereGeom); }
   else if (!std::strcmp(name, "large_geom")) { src = r.large_geom.p; bytes = (size_t)G.n_large * sizeof(rtc::SphereGeom); }
   else if (!std::strcmp(name, "motion")) { src = r.motion.p; bytes = r.n_moving ? (size_t)s->host.n_spheres * 32 : 0; }
+  else if (!std::strcmp(name, "quads")) { src = r.quads.p; bytes = (size_t)r.n_quads * sizeof(RtQuadRec); }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
   if (needed) *needed = bytes;
   if (!out) return RT_OK;

@@ -340,12 +340,17 @@ struct LdsTables {  // per-lane gathers from the workgroup's LDS copies
 // SOLID: solid textures: a lane whose closest hit is a Checker or Noise sphere draws its unit-sphere point with the
 // diffuse lanes and takes the solid arm of scatter, which calls the cold rt_core.h solid_albedo (the hit point in the sphere's frame
 // through csrc/common/rt_solid.h).  The hit tests do not change.  A compile-time arm: the other instantiations stay the code they were.
+// QUADS: flat parallelograms: after the `large` list and the walk of a segment, every lane that holds a ray calls the cold
+// rt_core.h quads_hit — a loop over the scene's quad records (wave-uniform: scalar loads) under the strict closest-hit rule, so a quad is
+// tested as if it followed every sphere — and the shading takes the quad form of the surface record (rt_core.h object_surface).  These
+// kernels exist with the tables in L2 and the general colour map only.  A compile-time arm: the other instantiations stay the code they were.
 template <bool HL, bool SIMPLE, bool LDS_TABLES, bool WIDE = false, bool ACCUM = false, bool LENS = false, bool MOTION = false, bool MEDIUM = false,
-          bool SOLID = false>
+          bool SOLID = false, bool QUADS = false>
 __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs ka) {
   static_assert(!(LDS_TABLES && WIDE), "wide tables (more than 65 535 spheres) never fit LDS");
   static_assert(!(MEDIUM && WIDE), "media with wide tables are refused at scene creation (RT_ERR_UNSUPPORTED)");
   static_assert(!(SOLID && WIDE), "solid textures with wide tables are refused at scene creation (RT_ERR_UNSUPPORTED)");
+  static_assert(!(QUADS && (WIDE || LDS_TABLES || SIMPLE)), "the QUADS kernels: tables in L2, the general colour map, never wide (kernel_key_valid)");
   const DevScene& sc = ka.sc;
   const GridDesc& G = sc.grid;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -962,6 +967,9 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
         }
       }
     }
+    if constexpr (QUADS) {  // (4) the quads, behind every sphere: quad k is object n_spheres + k
+      if (has_ray) { const HitCB r = quads_hit(L.o, L.d, sc.quads, sc.n_quads, sc.n_spheres, closest, best); closest = r.closest; best = r.best; }
+    }
   };
 
   RT_PROF(5);
@@ -1033,11 +1041,11 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     if (has_ray) {
 #ifdef RT_PROF_LIT
       rtc::ShadeProf shade_prof{prof_t, &prof_last, &cnt_w_step, &cnt_w_test};
-      if constexpr (MOTION) status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
-      else status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      if constexpr (MOTION) status = lane_shade<MEDIUM, SOLID, QUADS>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
+      else status = lane_shade<MEDIUM, SOLID, QUADS>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr, &shade_prof);
 #else
-      if constexpr (MOTION) status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
-      else status = lane_shade<MEDIUM, SOLID>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      if constexpr (MOTION) status = lane_shade<MEDIUM, SOLID, QUADS>(fresh_args().sc, motion_tables(tb, fresh_args().sc.motion, tau), L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
+      else status = lane_shade<MEDIUM, SOLID, QUADS>(fresh_args().sc, tb, L, best, closest, &rnd, &glass_u, HL ? &light_u : nullptr);
 #endif
       if constexpr (HL) { if (status == LANE_REPEAT) L.n_tex_oob = 0u; }  // (the hit is shaded again next iteration: its out-of-range texel counts THEN, once — RtStats.tex_oob equals the oracle's)
       flush_oob();
@@ -1126,19 +1134,21 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
 }
 
 // The key of an instantiation, one bit per template argument (rt_hip_scene_query "last_kernel", include/rt_abi.h), and its kernel set,
-// key >> 6 = (SOLID, MEDIUM, MOTION): the translation unit that compiles it (build.py; rt_kernel_set.hip).
+// key >> 6 = (QUADS, SOLID, MEDIUM, MOTION): the translation unit that compiles it (build.py; rt_kernel_set.hip).
 enum : int { KEY_LDS = 1, KEY_SIMPLE = 2, KEY_HL = 4, KEY_WIDE = 8, KEY_ACCUM = 16, KEY_LENS = 32, KEY_MOTION = 64, KEY_MEDIUM = 128, KEY_SOLID = 256,
-             KERNEL_KEYS = 512, KERNEL_SET_KEYS = 64, KERNEL_SETS = KERNEL_KEYS / KERNEL_SET_KEYS };
-// The keys that have an instantiation (the host's statement of rt_megakernel's static_asserts): 288 of the 512 — 48 in each of the
-// sets 0 and 1, 32 in each of the sets 2 - 7.
+             KEY_QUADS = 512, KERNEL_KEYS = 1024, KERNEL_SET_KEYS = 64, KERNEL_SETS = KERNEL_KEYS / KERNEL_SET_KEYS };
+// The keys that have an instantiation (the host's statement of rt_megakernel's static_asserts): 352 of the 1024 — 48 in each of the
+// sets 0 and 1, 32 in each of the sets 2 - 7, and 8 in each of the sets 8 - 15: a QUADS kernel exists only with its tables
+// in L2 and the general colour map, never wide — lights x ACCUM x LENS x MOTION x MEDIUM x SOLID = 64, so that the matrix does not double.
 constexpr bool kernel_key_valid(int key) {
-  return key >= 0 && key < KERNEL_KEYS && !((key & KEY_WIDE) && (key & (KEY_LDS | KEY_MEDIUM | KEY_SOLID)));
+  return key >= 0 && key < KERNEL_KEYS && !((key & KEY_WIDE) && (key & (KEY_LDS | KEY_MEDIUM | KEY_SOLID | KEY_QUADS))) &&
+         !((key & KEY_QUADS) && (key & (KEY_LDS | KEY_SIMPLE)));
 }
 using Megakernel = void (*)(KArgs);
 template <int K> Megakernel megakernel_of_key() {  // null exactly where K is not valid
   if constexpr (!kernel_key_valid(K)) return nullptr;
   else return rt_megakernel<(K & KEY_HL) != 0, (K & KEY_SIMPLE) != 0, (K & KEY_LDS) != 0, (K & KEY_WIDE) != 0, (K & KEY_ACCUM) != 0, (K & KEY_LENS) != 0,
-                            (K & KEY_MOTION) != 0, (K & KEY_MEDIUM) != 0, (K & KEY_SOLID) != 0>;
+                            (K & KEY_MOTION) != 0, (K & KEY_MEDIUM) != 0, (K & KEY_SOLID) != 0, (K & KEY_QUADS) != 0>;
 }
 // One set's slice of the key-indexed table: entry I belongs to key SET * 64 + I.  Instantiating it instantiates the set's kernels in this
 // translation unit.
@@ -1147,8 +1157,8 @@ template <int SET, int... I> KernelSetTable kernel_set_table(std::integer_sequen
   return KernelSetTable{megakernel_of_key<SET * KERNEL_SET_KEYS + I>()...};
 }
 // (internal, not part of the ABI.  The product build compiles the sets side by side, each ~1 minute of one core: set 0 with everything
-//  else in rt_hip_api.hip, built with -DRT_KERNEL_SET_SPLIT, which only declares this function; sets 1 - 7 in rt_kernel_set.hip, built once
-//  per set with -DRT_KERNEL_SET=<set>, which instantiates it for that set.  Without either flag rt_hip_api.hip compiles all eight.)
+//  else in rt_hip_api.hip, built with -DRT_KERNEL_SET_SPLIT, which only declares this function; sets 1 - 15 in rt_kernel_set.hip, built once
+//  per set with -DRT_KERNEL_SET=<set>, which instantiates it for that set.  Without either flag rt_hip_api.hip compiles all sixteen.)
 template <int SET> __attribute__((visibility("hidden"))) KernelSetTable kernel_set();
 #ifndef RT_KERNEL_SET_SPLIT
 template <int SET> KernelSetTable kernel_set() { return kernel_set_table<SET>(std::make_integer_sequence<int, KERNEL_SET_KEYS>()); }
@@ -1300,13 +1310,13 @@ __global__ __launch_bounds__(256) void rt_tile_error(const unsigned long long* _
 // --------------------------------------------------------------------------- denoising
 // Feature buffers: one thread per pixel of a width x height frame, 16 x 16 blocks; the record (rt_core.h aov_pixel) leaves as two
 // 16-byte stores.  Reads the scene's tables only: no tile queue, counters, depths or accumulators.
-template <bool LENS, bool MOTION, bool MEDIUM, bool SOLID>
+template <bool LENS, bool MOTION, bool MEDIUM, bool SOLID, bool QUADS = false>
 __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float4* __restrict__ out) {
   const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
   if (x >= sc.width || y >= sc.height) return;
   const GlobalTables tb{sc.geom, sc.matc};
   float r[8];
-  aov_pixel<LENS, MOTION, MEDIUM, SOLID>(sc, tb, x, y, n, r);
+  aov_pixel<LENS, MOTION, MEDIUM, SOLID, QUADS>(sc, tb, x, y, n, r);
   const size_t p = (size_t)y * sc.width + x;
   out[2 * p] = make_float4(r[0], r[1], r[2], r[3]);
   out[2 * p + 1] = make_float4(r[4], r[5], r[6], r[7]);
@@ -1316,6 +1326,10 @@ __device__ __forceinline__ void aov_thread(const DevScene& sc, uint32_t n, float
 // first hit on a Checker or Noise sphere reports the colour evaluated there.
 template <bool LENS, bool MOTION, bool MEDIUM, bool SOLID>
 __global__ __launch_bounds__(256) void rt_aov(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<LENS, MOTION, MEDIUM, SOLID>(sc, n, out); }
+// ... and for a scene that holds quads: the same sixteen with the quads tested behind the spheres (kernels of their own name:
+// rt_aov's stay what they were)
+template <bool LENS, bool MOTION, bool MEDIUM, bool SOLID>
+__global__ __launch_bounds__(256) void rt_aov_quads(const DevScene sc, uint32_t n, float4* __restrict__ out) { aov_thread<LENS, MOTION, MEDIUM, SOLID, true>(sc, n, out); }
 
 // One a-trous iteration (rt_core.h denoise_pixel): one thread per pixel, 16 x 16 blocks.  IN4: the input colour is the float4
 // ping-pong of the previous iteration (one 16-byte load per tap), else the caller's packed linear f32 x 3.  The guide record is two
@@ -1409,6 +1423,14 @@ __global__ __launch_bounds__(256) void rt_surface(const DevScene sc, uint4* __re
   if (x >= sc.width || y >= sc.height) return;
   const GlobalTables tb{sc.geom, sc.matc};
   out[(size_t)y * sc.width + x] = surf_pack(surface_pixel<MOTION, MEDIUM>(sc, tb, x, y));
+}
+// ... for a scene that holds quads: quad k is id n_spheres + k
+template <bool MOTION, bool MEDIUM>
+__global__ __launch_bounds__(256) void rt_surface_quads(const DevScene sc, uint4* __restrict__ out) {
+  const uint32_t x = blockIdx.x * 16u + threadIdx.x, y = blockIdx.y * 16u + threadIdx.y;
+  if (x >= sc.width || y >= sc.height) return;
+  const GlobalTables tb{sc.geom, sc.matc};
+  out[(size_t)y * sc.width + x] = surf_pack(surface_pixel<MOTION, MEDIUM, true>(sc, tb, x, y));
 }
 
 // One step of the history with surface tracking (rt_core.h reproject_surface_pixel): one thread per pixel, 16 x 16 blocks.  Per pixel:

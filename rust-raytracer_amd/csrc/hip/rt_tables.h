@@ -58,6 +58,10 @@ struct HostTables {
   uint32_t n_media = 0;
   // solid textures: the number of Checker and Noise spheres; their parameters travel in the SphereMat records
   uint32_t n_solids = 0;
+  // quads: the resident records (csrc/common/rt_quad.h: the caller's q, u, v and the host's N, w, D); quad k's material
+  // records are mat[n_spheres + k] and matc[n_spheres + k] (inv_r 0), behind the spheres'.  EMPTY for a scene without a quad: every
+  // table is then what it was.  n_solids counts Checker and Noise quads too.
+  std::vector<RtQuadRec> quads;
 };
 
 // The box a sphere's centre can occupy over the shutter, axis k (rt_grid_build.h grid_sphere_box: the static box, or the swept one).
@@ -351,7 +355,12 @@ inline std::string build_motion(const RtScene& sc, const double* center1, HostTa
 // tools/analysis/walk_sim.cpp do (the product's rt_hip_scene_create leaves it out since round 6).
 // center1 (motion blur): null, or [n_spheres][3] centres at shutter close (rt_scene_motion); a sphere whose center1
 // equals its centre (NaN components: both NaN) is static.  dv = center1 - center must be finite, and a Light sphere cannot move.
-inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull = false, const double* center1 = nullptr) {
+// quads / n_quads: the scene's quads (rt_scene_quads); none builds the tables it always built.  Checked here: finite q, u, v; a
+// normal that is not degenerate; a material a quad can have; the solid parameters of a Checker or Noise quad.  (More than RT_MAX_QUADS and
+// quads with wide tables are RT_ERR_UNSUPPORTED: the caller's check.)
+inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables& t);
+inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull = false, const double* center1 = nullptr, const RtQuad* quads = nullptr,
+                                uint32_t n_quads = 0) {
   if (sc.abi_version != RT_ABI_VERSION) return "abi_version mismatch";
   if (sc.width == 0 || sc.height == 0) return "empty image";
   if (sc.n_spheres && !sc.spheres) return "null sphere table";
@@ -459,6 +468,54 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
   };
   build_grid(sc, t, grid_params_shipped());
   pack_large();
+  t.quads.clear();
+  if (n_quads) return build_quads(quads, n_quads, t);
+  return "";
+}
+inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables& t) {
+  if (!quads) return "null quad table";
+  t.quads.resize(n_quads);
+  for (uint32_t k = 0; k < n_quads; ++k) {
+    const RtQuad& q = quads[k];
+    const std::string which = "quad " + std::to_string(k);
+    const int bad = rt_quad_prepare(q.q, q.u, q.v, &t.quads[k]);
+    if (bad == 1) return which + ": q, u and v must be finite";
+    if (bad) return which + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)";
+    if (q.kind > RT_MAT_NOISE) return which + ": bad material kind";
+    if (q.kind == RT_MAT_TEXTURE) return which + ": a quad cannot be a Texture (it has no (u, v) map)";
+    if (q.kind == RT_MAT_LIGHT) return which + ": a quad cannot be a Light (the light loop aims at sphere centres)";
+    if (q.kind == RT_MAT_MEDIUM) return which + ": a quad cannot be a Medium (a medium needs a volume)";
+    if (q.kind == RT_MAT_CHECKER || q.kind == RT_MAT_NOISE) {  // (the checks of a solid sphere)
+      const std::string what = which + (q.kind == RT_MAT_CHECKER ? ": Checker" : ": Noise");
+      if (!(std::isfinite(q.h_offset) && q.h_offset > 0.0)) return what + ".scale must be finite and > 0";
+      if (q.kind == RT_MAT_NOISE) {
+        if (q.tex_id > RT_SOLID_MODE_MARBLE) return what + ".mode must be 0 (noise), 1 (turbulence) or 2 (marble)";
+        if (q.tex_w < 1 || q.tex_w > RT_SOLID_MAX_OCTAVES) return what + ".octaves must be 1..16";
+        if (q.tex_h > 0xFFFFFFFFull) return what + ".seed must be at most 2^32 - 1";
+      }
+      t.n_solids++;
+    }
+    SphereMat m;
+    std::memset(&m, 0, sizeof m);
+    m.albedo[0] = q.albedo[0]; m.albedo[1] = q.albedo[1]; m.albedo[2] = q.albedo[2];
+    m.kind = q.kind; m.fuzz_or_ior = q.fuzz_or_ior; m.h_offset = q.h_offset;
+    m.tex_w = q.tex_w; m.tex_h = q.tex_h;
+    if (q.kind == RT_MAT_NOISE) m.pad = q.tex_id;
+    t.mat.push_back(m);
+    MatCore mc;
+    mc.albedo[0] = m.albedo[0]; mc.albedo[1] = m.albedo[1]; mc.albedo[2] = m.albedo[2];
+    mc.kind = m.kind; mc.fuzz_or_ior = m.fuzz_or_ior;
+    mc.inv_r = 0.0;
+    mc.r0[0] = mc.r0[1] = 0.0;
+    if (q.kind == RT_MAT_GLASS) {  // (as for a Glass sphere above)
+      const double inv_ior = 1.0 / q.fuzz_or_ior;
+      matcore_set_inv_ior(mc, inv_ior);
+      mc.r0[0] = reflectance_r0(inv_ior);
+      mc.r0[1] = reflectance_r0(q.fuzz_or_ior);
+    }
+    t.matc.push_back(mc);
+  }
+  t.simple_colour = false;  // (the QUADS kernels exist with the general colour map only)
   return "";
 }
 

@@ -51,6 +51,10 @@
 // Motion blur: a scene whose spheres have "center1" (rt_scene_motion) is created with rt_hip_scene_create_moving /
 // rt_hip_group_create_moving in every mode above, with or without a lens; its one-shot frame goes through a one-frame group too.
 //
+// Quads and boxes: a scene file that holds a quad or a box (rt_scene_quads) is created with rt_hip_scene_create_quads /
+// rt_hip_group_create_quads in every mode above; its one-shot frame goes through a one-frame group too (RtScene carries no quads).  A
+// quad-free file takes the calls it always took.
+//
 // Moving spheres from frame to frame (`--frames N --shutter S`, 0 <= S <= 1): a sphere's "center" -> "center1" is its
 // path over the whole animation instead of over one exposure; frame f is exposed from center + dv f / N to center + dv (f + S) / N
 // (anim_path.h), S = 0 giving crisp spheres.  The resident scene's spheres are moved before every frame (rt_hip_group_update_spheres /
@@ -71,6 +75,19 @@
 #include "anim_path.h"
 
 namespace {
+// the resident scene / group of a scene file: with its quads if it has any, else the calls a quad-free file always took
+int create_scene(const RtSceneFile* sf, int device, RtHipScene** out) {
+  uint32_t n_quads = 0;
+  const RtQuad* quads = rt_scene_quads(sf, &n_quads);
+  if (n_quads) return rt_hip_scene_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, device, out);
+  return rt_hip_scene_create_moving(rt_scene_get(sf), rt_scene_motion(sf), device, out);
+}
+int create_group(const RtSceneFile* sf, RtHipGroup** out) {
+  uint32_t n_quads = 0;
+  const RtQuad* quads = rt_scene_quads(sf, &n_quads);
+  if (n_quads) return rt_hip_group_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, 0, out);
+  return rt_hip_group_create_moving(rt_scene_get(sf), rt_scene_motion(sf), 0, out);
+}
 // camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77 with the scene's
 // lens = {aperture, focus_dist} (rt_scene_lens; aperture 0: the pinhole, out[0..12] = rt_camera_derive's)
 void orbit_camera(const double cam[11], const double lens[2], double orbit_deg, int f, double out[20]) {
@@ -207,7 +224,7 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
   RtScene* sc = rt_scene_get_mut(sf);
   RtHipGroup* hs = nullptr;  // the scene resident on RT_GPUS devices (default 1)
   const auto t_create = std::chrono::steady_clock::now();
-  int rc = rt_hip_group_create_moving(sc, rt_scene_motion(sf), 0, &hs);
+  int rc = create_group(sf, &hs);
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
   (void)rt_hip_group_set_option(hs, "prepare_host_output", 2);  // (pinned staging for the two frames in flight + the copy path, at set-up: not inside the first submit)
   const auto t_begin = std::chrono::steady_clock::now();
@@ -277,7 +294,7 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
 int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool denoise = false, bool report_passes = true) {
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
-  int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
+  int rc = create_scene(sf, 0, &hs);
   if (rc == RT_OK) rc = set_scene_lens(sf, hs);
   std::printf("\nRendering %s\n", filename);  // main.rs:18
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
@@ -309,7 +326,7 @@ int animate_temporal(RtSceneFile* sf, const char* prefix, int frames, double orb
   RtScene* sc = rt_scene_get_mut(sf);
   RtHipScene* hs = nullptr;
   const auto t_create = std::chrono::steady_clock::now();
-  int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
+  int rc = create_scene(sf, 0, &hs);
   if (rc == RT_OK && (surface || alpha >= 0.0)) {
     const float a_min = alpha >= 0.0 ? (float)alpha : (surface ? RT_TEMPORAL_SURFACE_ALPHA_MIN : RT_TEMPORAL_ALPHA_MIN);
     rc = rt_hip_temporal_configure(hs, a_min, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH);
@@ -358,7 +375,7 @@ int animate_temporal(RtSceneFile* sf, const char* prefix, int frames, double orb
 int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t min_spp) {
   const RtScene* sc = rt_scene_get(sf);
   RtHipScene* hs = nullptr;
-  int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), 0, &hs);
+  int rc = create_scene(sf, 0, &hs);
   if (rc == RT_OK) rc = set_scene_lens(sf, hs);
   std::printf("\nRendering %s\n", filename);  // main.rs:18
   if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
@@ -413,7 +430,7 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
   for (unsigned g = 0; g < G; ++g)
     th.emplace_back([&, g]() {
       RtHipScene* hs = nullptr;
-      int rc = rt_hip_scene_create_moving(sc, rt_scene_motion(sf), (int)(g % (unsigned)ndev), &hs);
+      int rc = create_scene(sf, (int)(g % (unsigned)ndev), &hs);
       if (rc != RT_OK) { std::lock_guard<std::mutex> lk(out_mu); std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status[g] = 101; return; }
       std::vector<uint8_t> buf[2] = {std::vector<uint8_t>(bytes), std::vector<uint8_t>(bytes)};
       std::thread writer;
@@ -457,12 +474,12 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
   return 0;
 }
 
-// rt_render_rgb8 for a scene with a thin lens or moving spheres (RtScene carries neither): the same one-frame group, with the lens
-// camera c (rt_camera_derive_lens; null: RtScene's pinhole) and the spheres' centres at shutter close center1 (null: static)
-int render_group_rgb8(const RtScene* sc, const double* c, const double* center1, uint8_t* out_rgb8, RtStats* stats) {
+// rt_render_rgb8 for a scene with a thin lens, moving spheres or quads (RtScene carries none of them): the same one-frame group, with the
+// lens camera c (rt_camera_derive_lens; null: RtScene's pinhole), the spheres' centres at shutter close and the quads of the scene file
+int render_group_rgb8(const RtSceneFile* sf, const double* c, uint8_t* out_rgb8, RtStats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
   RtHipGroup* g = nullptr;
-  int rc = rt_hip_group_create_moving(sc, center1, 0, &g);
+  int rc = create_group(sf, &g);
   if (rc != RT_OK) return rc;
   (void)rt_hip_group_set_option(g, "tile_order", 1);  // (one frame: no later frame could use a learned order — rt_render_rgb8's setting)
   if (c) {
@@ -616,8 +633,9 @@ int run(int argc, char** argv) {
   const double hip_wait_ms = ms_since(t_hip), hip_init_ms = g_hip_init_ms;
   double cam_lens[20];
   const bool lens = lens_camera(sf, cam_lens);
-  const double* center1 = rt_scene_motion(sf);
-  rc = lens || center1 ? render_group_rgb8(sc, lens ? cam_lens : nullptr, center1, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
+  uint32_t n_quads = 0;
+  (void)rt_scene_quads(sf, &n_quads);
+  rc = lens || rt_scene_motion(sf) || n_quads ? render_group_rgb8(sf, lens ? cam_lens : nullptr, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
   if (rc != RT_OK) {
     std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error());
     rt_scene_free(sf);

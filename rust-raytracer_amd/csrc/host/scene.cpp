@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../../include/rt_abi.h"
+#include "../common/rt_quad.h"
 #include "json.hpp"
 
 extern "C" const char* rt_jpeg_last_error(void);
@@ -195,6 +196,10 @@ struct RtSceneFile {
   std::vector<double> center1;
   std::vector<uint8_t> has_center1;
   size_t n_center1 = 0;
+  // quads and boxes: the file's quads in file order (a box: its six quads in place), and for rt_scene_to_json the file's
+  // interleaving of the two kinds — is_quad[j]: the j-th object written is the next quad, else the next sphere
+  std::vector<RtQuad> quads;
+  std::vector<uint8_t> is_quad;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
   // concurrently, beside the parse), everything (read + parse + schema + waiting for the decodes)
   double read_ms = 0, json_ms = 0, jpeg_ms = 0, total_ms = 0;
@@ -356,22 +361,10 @@ void build_scene(const Value& root, RtSceneFile& sf) {
   if (objs.kind != Value::Array) bad("objects: expected an array");
   if (objs.items.size() > 0xFFFFFFFFull) throw UnsupportedError{"more than 2^32 - 1 objects"};
   sf.spheres.reserve(objs.items.size());
-  for (auto& o : objs.items) {
-    RtSphere s{};
-    const Value* sp[4] = {};
-    // (+ the optional "center1" of a map, DESIGN.md §14; the sequence form stays the reference's three fields)
-    if (o->kind == Value::Array) struct_fields(*o, "Sphere", {"center", "radius", "material"}, sp);
-    else {
-      try {
-        struct_fields(*o, "Sphere", {"center", "radius", "material", "center1"}, sp, {false, false, false, true});
-      } catch (const SchemaError& e) {
-        if (e.msg.find("center1") != std::string::npos) bad("objects[" + std::to_string(sf.spheres.size()) + "]: " + e.msg);
-        throw;
-      }
-    }
-    as_point(*sp[0], "Sphere.center", s.center);
-    s.radius = as_f64(*sp[1], "Sphere.radius");
-    const Value& m = *sp[2];
+  size_t obj_index = 0;  // the file's own index of the object being read (spheres and quads counted alike)
+  // the material of an object (materials.rs:35-42 and the extensions) into the material fields of `s`; radius_v: the sphere's radius as
+  // written (a Medium checks it), null for a quad
+  auto parse_material = [&](const Value& m, RtSphere& s, const Value* radius_v) {
     // externally tagged enum (materials.rs:35-42): a map with exactly one key (a second one — also the same one twice — is an error)
     if (m.kind != Value::Object || m.members.size() != 1) bad("material: expected a single-key enum object");
     const std::string& tag = m.members[0].first;
@@ -401,7 +394,7 @@ void build_scene(const Value& root, RtSceneFile& sf) {
       s.kind = RT_MAT_LIGHT;
     } else if (tag == "Medium") {
       // a participating medium: an extension — the reference's enum has no such variant and rejects the file
-      const std::string which = "objects[" + std::to_string(sf.spheres.size()) + "]";
+      const std::string which = "objects[" + std::to_string(obj_index) + "]";
       try {
         struct_fields(body, "Medium", {"albedo", "density"}, f);
         s.kind = RT_MAT_MEDIUM; parse_albedo(*f[0], s.albedo);
@@ -410,10 +403,10 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         bad(which + ": " + e.msg);
       }
       if (!(std::isfinite(s.fuzz_or_ior) && s.fuzz_or_ior > 0.0)) bad(which + ": Medium.density must be finite and > 0, got " + f[1]->text);
-      if (!(std::isfinite(s.radius) && s.radius > 0.0)) bad(which + ": the radius of a Medium sphere must be finite and > 0, got " + sp[1]->text);
+      if (radius_v && !(std::isfinite(s.radius) && s.radius > 0.0)) bad(which + ": the radius of a Medium sphere must be finite and > 0, got " + radius_v->text);
     } else if (tag == "Checker" || tag == "Noise") {
       // solid textures: extensions — the reference's enum has no such variants and rejects the file
-      const std::string which = "objects[" + std::to_string(sf.spheres.size()) + "]";
+      const std::string which = "objects[" + std::to_string(obj_index) + "]";
       try {
         if (tag == "Checker") {
           struct_fields(body, "Checker", {"even", "odd", "scale"}, f);
@@ -452,9 +445,84 @@ void build_scene(const Value& root, RtSceneFile& sf) {
     } else {
       bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`, `Medium`, `Checker`, `Noise`");
     }
+  };
+  // A quad or a box (extensions — the reference's loader rejects both forms: missing `center`): a map with the keys "q", "u",
+  // "v", "material", or "box" ({"min", "max"}), "material".  Every error names objects[i] by the file's own index.
+  auto parse_quad_or_box = [&](const Value& o) {
+    const std::string which = "objects[" + std::to_string(obj_index) + "]";
+    const bool is_box = o.find("box") != nullptr;
+    try {
+      for (const char* k : {"center", "radius"})
+        if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a sphere beside `" + (is_box ? "box" : "q`, `u`, `v") + "`");
+      if (is_box)
+        for (const char* k : {"q", "u", "v"})
+          if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a quad beside `box`");
+      if (o.find("center1")) bad("a quad cannot move (center1)");
+      const Value* f[4] = {};
+      double geo[6][9];
+      int n_new = 1;
+      if (is_box) {
+        struct_fields(o, "Box", {"box", "material"}, f);
+        const Value* b[2];
+        struct_fields(*f[0], "box", {"min", "max"}, b);
+        double mn[3], mx[3];
+        as_point(*b[0], "box.min", mn);
+        as_point(*b[1], "box.max", mx);
+        for (int k = 0; k < 3; ++k)
+          if (!(mn[k] < mx[k])) bad("box: min must be below max on every axis");
+        rt_box_quads(mn, mx, geo);
+        n_new = 6;
+      } else {
+        struct_fields(o, "Quad", {"q", "u", "v", "material"}, f);
+        as_point(*f[0], "Quad.q", geo[0]);
+        as_point(*f[1], "Quad.u", geo[0] + 3);
+        as_point(*f[2], "Quad.v", geo[0] + 6);
+      }
+      const Value& m = *f[is_box ? 1 : 3];
+      if (m.kind == Value::Object && m.members.size() == 1)
+        for (const char* k : {"Texture", "Light", "Medium"})
+          if (m.members[0].first == k) bad(std::string("a quad cannot be a ") + k + " (a quad may be Lambertian, Metal, Glass, Checker or Noise)");
+      RtSphere mat{};
+      parse_material(m, mat, nullptr);
+      for (int i = 0; i < n_new; ++i) {
+        RtQuad q{};
+        std::memcpy(q.q, geo[i], 24); std::memcpy(q.u, geo[i] + 3, 24); std::memcpy(q.v, geo[i] + 6, 24);
+        RtQuadRec rec;
+        if (rt_quad_prepare(q.q, q.u, q.v, &rec) != 0) bad("degenerate quad: |cross(u, v)|^2 is zero, subnormal or not finite");
+        q.fuzz_or_ior = mat.fuzz_or_ior; q.h_offset = mat.h_offset; q.tex_w = mat.tex_w; q.tex_h = mat.tex_h;
+        std::memcpy(q.albedo, mat.albedo, 12);
+        q.kind = mat.kind; q.tex_id = mat.tex_id;
+        sf.quads.push_back(q);
+        sf.is_quad.push_back(1);
+      }
+    } catch (const SchemaError& e) {
+      bad(e.msg.rfind(which, 0) == 0 ? e.msg : which + ": " + e.msg);
+    }
+  };
+  for (auto& o : objs.items) {
+    if (o->kind == Value::Object && (o->find("q") || o->find("u") || o->find("v") || o->find("box"))) {
+      parse_quad_or_box(*o);
+      ++obj_index;
+      continue;
+    }
+    RtSphere s{};
+    const Value* sp[4] = {};
+    // (+ the optional "center1" of a map, DESIGN.md §14; the sequence form stays the reference's three fields)
+    if (o->kind == Value::Array) struct_fields(*o, "Sphere", {"center", "radius", "material"}, sp);
+    else {
+      try {
+        struct_fields(*o, "Sphere", {"center", "radius", "material", "center1"}, sp, {false, false, false, true});
+      } catch (const SchemaError& e) {
+        if (e.msg.find("center1") != std::string::npos) bad("objects[" + std::to_string(obj_index) + "]: " + e.msg);
+        throw;
+      }
+    }
+    as_point(*sp[0], "Sphere.center", s.center);
+    s.radius = as_f64(*sp[1], "Sphere.radius");
+    parse_material(*sp[2], s, sp[1]);
     double c1[3] = {s.center[0], s.center[1], s.center[2]};
     if (sp[3]) {
-      const std::string which = "objects[" + std::to_string(sf.spheres.size()) + "]";
+      const std::string which = "objects[" + std::to_string(obj_index) + "]";
       if (s.kind == RT_MAT_LIGHT) bad(which + ": a Light sphere cannot move (center1)");
       as_point(*sp[3], "Sphere.center1", c1);
       for (int k = 0; k < 3; ++k)
@@ -464,7 +532,10 @@ void build_scene(const Value& root, RtSceneFile& sf) {
     sf.center1.insert(sf.center1.end(), c1, c1 + 3);
     sf.has_center1.push_back(sp[3] ? 1 : 0);
     sf.spheres.push_back(s);
+    sf.is_quad.push_back(0);
+    ++obj_index;
   }
+  if (sf.quads.size() > 0xFFFFFFFFull) throw UnsupportedError{"more than 2^32 - 1 quads"};
   sc.spheres = sf.spheres.data(); sc.n_spheres = uint32_t(sf.spheres.size());
   sc.textures = sf.textures.data(); sc.n_textures = uint32_t(sf.textures.size());
   sc.seed = 0;
@@ -534,12 +605,27 @@ std::string scene_json(const RtSceneFile& sf) {
   if (sf.has_aperture) o += ",\"aperture\":" + f64s(sf.aperture);
   if (sf.has_focus_dist) o += ",\"focus_dist\":" + f64s(sf.focus_dist);
   o += "},\"objects\":[";
-  for (size_t i = 0; i < sf.spheres.size(); ++i) {
-    const RtSphere& s = sf.spheres[i];
-    if (i) o += ",";
-    o += "{\"center\":" + point(s.center);
-    if (sf.has_center1[i]) o += ",\"center1\":" + point(&sf.center1[3 * i]);
-    o += ",\"radius\":" + f64s(s.radius) + ",\"material\":{";
+  // (the file's own interleaving of spheres and quads; a box was expanded to its six quads when it was read)
+  size_t i = 0, iq = 0;
+  for (size_t j = 0; j < sf.is_quad.size(); ++j) {
+    RtSphere qs{};  // (a quad's material fields, where the switch below reads a sphere's)
+    if (sf.is_quad[j]) {
+      const RtQuad& q = sf.quads[iq];
+      qs.fuzz_or_ior = q.fuzz_or_ior; qs.h_offset = q.h_offset; qs.tex_w = q.tex_w; qs.tex_h = q.tex_h;
+      std::memcpy(qs.albedo, q.albedo, 12);
+      qs.kind = q.kind; qs.tex_id = q.tex_id;
+    }
+    const RtSphere& s = sf.is_quad[j] ? qs : sf.spheres[i];
+    if (j) o += ",";
+    if (sf.is_quad[j]) {
+      const RtQuad& q = sf.quads[iq++];
+      o += "{\"q\":" + point(q.q) + ",\"u\":" + point(q.u) + ",\"v\":" + point(q.v) + ",\"material\":{";
+    } else {
+      o += "{\"center\":" + point(s.center);
+      if (sf.has_center1[i]) o += ",\"center1\":" + point(&sf.center1[3 * i]);
+      o += ",\"radius\":" + f64s(s.radius) + ",\"material\":{";
+      ++i;
+    }
     switch (s.kind) {
       case RT_MAT_LAMBERTIAN: o += "\"Lambertian\":{\"albedo\":" + albedo(s.albedo) + "}"; break;
       case RT_MAT_METAL: o += "\"Metal\":{\"albedo\":" + albedo(s.albedo) + ",\"fuzz\":" + f64s(s.fuzz_or_ior) + "}"; break;
@@ -632,6 +718,11 @@ extern "C" void rt_scene_lens(const RtSceneFile* sf, double out[2]) {
 }
 extern "C" const double* rt_scene_motion(const RtSceneFile* sf) {
   return sf && sf->n_center1 != 0 ? sf->center1.data() : nullptr;
+}
+extern "C" const RtQuad* rt_scene_quads(const RtSceneFile* sf, uint32_t* n) {
+  const bool any = sf && !sf->quads.empty();
+  if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
+  return any ? sf->quads.data() : nullptr;
 }
 extern "C" void rt_free(void* p) { std::free(p); }
 

@@ -44,6 +44,7 @@ def _bind(path, probes):
     L.rt_strerror.restype = C.c_char_p
     L.rt_hip_scene_create.argtypes = [C.POINTER(abi.RtScene), C.c_int, C.POINTER(C.c_void_p)]
     L.rt_hip_scene_create_moving.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_void_p)]
+    L.rt_hip_scene_create_quads.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.POINTER(abi.RtQuad), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
     L.rt_hip_scene_destroy.argtypes = [C.c_void_p]
     L.rt_hip_scene_destroy.restype = None
     L.rt_hip_render.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -85,6 +86,7 @@ def _bind(path, probes):
     L.rt_abi_version.restype = C.c_uint32
     L.rt_hip_group_create.argtypes = [C.POINTER(abi.RtScene), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rt_hip_group_create_moving.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.rt_hip_group_create_quads.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.POINTER(abi.RtQuad), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.rt_hip_group_destroy.argtypes = [C.c_void_p]
     L.rt_hip_group_destroy.restype = None
     L.rt_hip_group_size.argtypes = [C.c_void_p]
@@ -115,7 +117,7 @@ def _bind(path, probes):
         L.rt_hip_quot_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
         L.rt_hip_render_rays_probe.argtypes = [C.c_void_p] * 6 + [C.POINTER(abi.RtStats)]
         L.rt_hip_walk_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
-    for name in (() if os.environ.get("RT_SKIP_LAYOUT_CHECK") else ("RtSphere", "RtTexture", "RtScene", "RtRowTiles", "RtStats", "RtGroupInfo", "RtGroupRank")):   # the binding's own layout check
+    for name in (() if os.environ.get("RT_SKIP_LAYOUT_CHECK") else ("RtSphere", "RtQuad", "RtTexture", "RtScene", "RtRowTiles", "RtStats", "RtGroupInfo", "RtGroupRank")):   # the binding's own layout check
         if L.rt_abi_sizeof(name.encode()) != C.sizeof(getattr(abi, name)):
             raise ImportError(f"{path}: sizeof({name}) = {L.rt_abi_sizeof(name.encode())} but abi.py has "
                               f"{C.sizeof(getattr(abi, name))} — rebuild with __graft_entry__.build()")
@@ -177,23 +179,39 @@ def _centres(n, c, what):
     return (C.c_double * max(1, 3 * n)).from_buffer_copy(a.tobytes() if n else bytes(8))
 
 
-TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion")   # the names rt_hip_scene_table knows
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads")   # the names rt_hip_scene_table knows
+
+
+def _quads_array(quads):
+    """a sequence of abi.RtQuad (or a ctypes array of them) as (C array, count)"""
+    n = len(quads)
+    if isinstance(quads, C.Array) and quads._type_ is abi.RtQuad:
+        return quads, n
+    arr = (abi.RtQuad * max(1, n))()
+    for i, q in enumerate(quads):
+        arr[i] = q
+    return arr, n
 
 
 # bits of query("last_kernel") (include/rt_abi.h rt_hip_scene_query)
-KERNEL_LDS, KERNEL_SIMPLE, KERNEL_LIGHTS, KERNEL_WIDE, KERNEL_ACCUM, KERNEL_LENS, KERNEL_MOTION, KERNEL_MEDIUM, KERNEL_SOLID = (1 << b for b in range(9))
+KERNEL_LDS, KERNEL_SIMPLE, KERNEL_LIGHTS, KERNEL_WIDE, KERNEL_ACCUM, KERNEL_LENS, KERNEL_MOTION, KERNEL_MEDIUM, KERNEL_SOLID, KERNEL_QUADS = (1 << b for b in range(10))
 
 
 class HipScene:
     """Scene tables + textures resident in HBM of one GPU (rt_hip_scene_create).  `library`: probe_lib() for the tests and
     tools that use the debug calls; default: the product library."""
 
-    def __init__(self, scene_ptr, device=0, library=None, center1=None):
+    def __init__(self, scene_ptr, device=0, library=None, center1=None, quads=None):
         """center1 (motion blur): None, or each sphere's centre at shutter close, n_spheres x 3 (host.Scene.center1()):
-        rt_hip_scene_create_moving"""
+        rt_hip_scene_create_moving.  quads: None, or the scene's quads, abi.RtQuad records (host.Scene.quads()):
+        rt_hip_scene_create_quads"""
         self._L = library or lib()
         self._h = C.c_void_p()
-        if center1 is None:
+        if quads is not None:
+            qa, nq = _quads_array(quads)
+            c1 = _center1_array(scene_ptr, center1) if center1 is not None else None
+            _check(self._L.rt_hip_scene_create_quads(scene_ptr, c1, qa, nq, device, C.byref(self._h)), self._L)
+        elif center1 is None:
             _check(self._L.rt_hip_scene_create(scene_ptr, device, C.byref(self._h)), self._L)
         else:
             c1 = _center1_array(scene_ptr, center1)
@@ -448,10 +466,14 @@ class HipGroup:
     """The scene resident on n_gpus devices of this node, frames sharded by interleaved scanline tiles
     inside librt_hip.so (rt_hip_group_*): host threads + streams + ONE gather per frame, no torch."""
 
-    def __init__(self, scene_ptr, n_gpus=0, library=None, center1=None):
+    def __init__(self, scene_ptr, n_gpus=0, library=None, center1=None, quads=None):
         self._L = library or lib()     # (library: probe_lib() for the tests that inject transport faults)
         self._h = C.c_void_p()
-        if center1 is None:
+        if quads is not None:  # (quads, DESIGN.md §20: rt_hip_group_create_quads)
+            qa, nq = _quads_array(quads)
+            c1 = _center1_array(scene_ptr, center1) if center1 is not None else None
+            _check(self._L.rt_hip_group_create_quads(scene_ptr, c1, qa, nq, n_gpus, C.byref(self._h)), self._L)
+        elif center1 is None:
             _check(self._L.rt_hip_group_create(scene_ptr, n_gpus, C.byref(self._h)), self._L)
         else:  # (motion blur, DESIGN.md §14: rt_hip_group_create_moving)
             c1 = _center1_array(scene_ptr, center1)

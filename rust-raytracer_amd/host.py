@@ -44,6 +44,8 @@ def lib():
         L.rt_scene_lens.restype = None
         L.rt_scene_motion.argtypes = [C.c_void_p]
         L.rt_scene_motion.restype = C.POINTER(C.c_double)
+        L.rt_scene_quads.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.rt_scene_quads.restype = C.POINTER(abi.RtQuad)
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
         L.rt_jpeg_decode_file.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -103,6 +105,17 @@ class Scene:
             return None
         n = self.c.n_spheres
         return [[p[3 * i], p[3 * i + 1], p[3 * i + 2]] for i in range(n)]
+
+    def quads(self):
+        """quads and boxes: the file's quads as a ctypes array of abi.RtQuad (a copy), or None for a file without one
+        (rt_scene_quads)"""
+        n = C.c_uint32(0)
+        p = lib().rt_scene_quads(self._h, C.byref(n))
+        if not p or not n.value:
+            return None
+        out = (abi.RtQuad * n.value)()
+        C.memmove(out, p, C.sizeof(out))
+        return out
 
     def lights(self):
         sc = self.c

@@ -19,12 +19,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 
 
 def demangle_mk(name):
-    m = re.match(r"_ZN3rtk13rt_megakernelILb(\d)ELb(\d)ELb(\d)ELb(\d)(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?EEEvNS_5KArgsE", name)
+    m = re.match(r"_ZN3rtk13rt_megakernelILb(\d)ELb(\d)ELb(\d)ELb(\d)(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?(?:ELb(\d))?EEEvNS_5KArgsE", name)
     if m:
-        hl, simple, lds, wide, accum, lens, motion, medium, solid = (int(x or 0) for x in m.groups())
+        hl, simple, lds, wide, accum, lens, motion, medium, solid, quads = (int(x or 0) for x in m.groups())
         return (f"rt_megakernel<lights={hl}, simple_colour={simple}, lds_tables={lds}" + (", wide_tables=1" if wide else "")
                 + (", accum=1" if accum else "") + (", lens=1" if lens else "") + (", motion=1" if motion else "") + (", medium=1" if medium else "")
-                + (", solid=1" if solid else "") + ">")
+                + (", solid=1" if solid else "") + (", quads=1" if quads else "") + ">")
     out = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
     return out.replace("(anonymous namespace)::", "").split("(")[0] if out else name
 
