@@ -593,4 +593,19 @@ inline void fill_dev_scene(const RtScene& sc, const HostTables& t, DevScene& d) 
   d.grid = t.grid;
 }
 
+// Host only (the CPU builds of the per-lane code: tests/, tools/analysis/): point `d` at every table `t` owns.  Call it after
+// fill_dev_scene, which zeroes `d`.  motion, medium and quads stay null for a scene without them, as on the device; the RGB8 blobs
+// (tex, sky) are not a HostTables' to give.
+inline void bind_host_tables(const HostTables& t, DevScene& d) {
+  d.geom = t.geom.data(); d.mat = t.mat.data(); d.matc = t.matc.data(); d.lights = t.lights.data();
+  d.cell_word = t.cell_word.data();
+  d.cell_items = t.grid.wide ? reinterpret_cast<const uint16_t*>(t.cell_items32.data()) : t.cell_items.data();
+  d.large = t.large.data(); d.large_geom = t.large_geom.data();
+  d.tex4 = t.tex4.data(); d.sky4 = t.sky4.data();
+  d.motion = t.motion.empty() ? nullptr : t.motion.data();
+  d.medium = t.medium.empty() ? nullptr : t.medium.data();
+  d.quads = t.quads.empty() ? nullptr : t.quads.data();
+  d.n_quads = (uint32_t)t.quads.size();
+}
+
 }  // namespace rtc

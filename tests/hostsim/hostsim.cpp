@@ -141,13 +141,11 @@ extern "C" int hostsim_render(const RtScene* scene, const RtRowTiles* tiles, uin
   build_texels(*scene, t);  // (the 4-byte-texel path the device takes; the RGB8 blob serves the records outside its range)
   DevScene ds;
   fill_dev_scene(*scene, t, ds);
-  ds.tex4 = t.tex4.data(); ds.sky4 = t.sky4.data();
+  bind_host_tables(t, ds);
   std::vector<uint8_t> blob(t.tex_bytes ? t.tex_bytes : 1);
   for (uint32_t i = 0; i < scene->n_textures; ++i)
     if (scene->textures[i].nbytes) std::memcpy(&blob[t.tex_off[i]], scene->textures[i].rgb8, scene->textures[i].nbytes);
-  ds.geom = t.geom.data(); ds.mat = t.mat.data(); ds.lights = t.lights.data();
   ds.tex = blob.data(); ds.sky = scene->sky_rgb8;
-  ds.matc = t.matc.data(); ds.cell_word = t.cell_word.data(); ds.cell_items = t.grid.wide ? reinterpret_cast<const uint16_t*>(t.cell_items32.data()) : t.cell_items.data(); ds.large = t.large.data(); ds.large_geom = t.large_geom.data();
   // +32: the SHORT colour maps the product kernel takes when every albedo lies in [0, 1] (rt_core.h FwdT<true>; lit scenes:
   // q in registers + the memory-resident base of lane_compose) instead of the general clamped-affine map — bit-identical
   const bool short_map = (use_cull & 32) != 0 && t.simple_colour;
@@ -212,38 +210,14 @@ extern "C" int hostsim_grid_mode(const RtScene* scene, const double o[3], const 
   return grid_begin(t.grid, v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]), w);
 }
 
-// one ray against one scene through the grid and by brute force (adversarial tests):
-// out = {best_grid, best_brute}, t_out = {t_grid, t_brute}
-extern "C" int hostsim_hit_world(const RtScene* scene, const double o[3], const double d[3], int out[2], double t_out[2]) {
-  HostTables t;
-  if (!scene || !build_tables(*scene, t, true).empty()) return RT_ERR_INVALID;
-  DevScene ds;
-  fill_dev_scene(*scene, t, ds);
-  ds.geom = t.geom.data(); ds.matc = t.matc.data(); ds.cell_word = t.cell_word.data(); ds.cell_items = t.grid.wide ? reinterpret_cast<const uint16_t*>(t.cell_items32.data()) : t.cell_items.data();
-  ds.large = t.large.data(); ds.large_geom = t.large_geom.data();
-  const GlobalTables tb{ds.geom, ds.matc};
-  V3 oo = v3(o[0], o[1], o[2]), dd = v3(d[0], d[1], d[2]);
-  const double a = length_squared(dd);
-  double c1 = T_MAX; int b1 = -1; uint32_t ne = 0, ns = 0;
-  hit_world_grid(ds, tb, oo, dd, c1, b1, ne, ns);
-  double c2 = T_MAX; int b2 = -1;
-  for (uint32_t i = 0; i < scene->n_spheres; ++i) {
-    double r = exact_root(oo, dd, a, t.geom[i], T_MIN, c2);
-    if (r >= 0.0) { c2 = r; b2 = (int)i; }
-  }
-  out[0] = b1; out[1] = b2; t_out[0] = c1; t_out[1] = c2;
-  return RT_OK;
-}
-
-// hostsim_hit_world for n rays {origin[3], direction[3]} of one scene (its tables built once): best / t = n x {grid, brute force},
-// work (optional) = n x {exact tests, grid steps} of the grid walk
+// n rays {origin[3], direction[3]} against one scene (its tables built once) through the grid and by brute force (adversarial
+// tests): best / t = n x {grid, brute force}, work (optional) = n x {exact tests, grid steps} of the grid walk
 extern "C" int hostsim_hit_world_v(const RtScene* scene, const double* rays, uint64_t n, int* best, double* t, uint32_t* work) {
   HostTables tt;
   if (!scene || !build_tables(*scene, tt, true).empty()) return RT_ERR_INVALID;
   DevScene ds;
   fill_dev_scene(*scene, tt, ds);
-  ds.geom = tt.geom.data(); ds.matc = tt.matc.data(); ds.cell_word = tt.cell_word.data(); ds.cell_items = tt.grid.wide ? reinterpret_cast<const uint16_t*>(tt.cell_items32.data()) : tt.cell_items.data();
-  ds.large = tt.large.data(); ds.large_geom = tt.large_geom.data();
+  bind_host_tables(tt, ds);
   const GlobalTables tb{ds.geom, ds.matc};
 #pragma omp parallel for schedule(dynamic, 64)
   for (uint64_t k = 0; k < n; ++k) {
@@ -261,6 +235,12 @@ extern "C" int hostsim_hit_world_v(const RtScene* scene, const double* rays, uin
     if (work) { work[2 * k] = ne; work[2 * k + 1] = ns; }
   }
   return RT_OK;
+}
+
+// hostsim_hit_world_v for one ray: out = {best_grid, best_brute}, t_out = {t_grid, t_brute}
+extern "C" int hostsim_hit_world(const RtScene* scene, const double o[3], const double d[3], int out[2], double t_out[2]) {
+  const double ray[6] = {o[0], o[1], o[2], d[0], d[1], d[2]};
+  return hostsim_hit_world_v(scene, ray, 1, out, t_out, nullptr);
 }
 
 // rt_core.h div_by_recip over arrays (property test against the IEEE quotient)

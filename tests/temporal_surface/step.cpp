@@ -1,10 +1,10 @@
-// step.cpp — TEST TOOL, not part of the product.  The two per-pixel functions of temporal denoising with surface tracking
-// (rust-raytracer_amd/csrc/hip/rt_core.h surface_pixel and reproject_surface_pixel) built for the CPU with
-// -ffp-contract=off and driven over a whole frame one pixel at a time, surface_pixel on tables rt_tables.h built on the host.
-// tests/test_temporal_surface_cpu.py compares both with the numpy restatement (tests/temporal_surface_ref.py).
+// step.cpp — TEST TOOL, not part of the product.  The reprojection step of temporal denoising with surface tracking
+// (rust-raytracer_amd/csrc/hip/rt_core.h reproject_surface_pixel) built for the CPU with -ffp-contract=off and driven
+// over a whole frame one pixel at a time.  tests/test_temporal_surface_cpu.py compares it with the numpy restatement
+// (tests/temporal_surface_ref.py); the surface record itself (surface_pixel) comes from tests/lanesim/.
 #include <cstdint>
 
-#include "../../rust-raytracer_amd/csrc/hip/rt_tables.h"
+#include "../../rust-raytracer_amd/csrc/hip/rt_core.h"
 
 using namespace rtc;
 
@@ -51,29 +51,4 @@ extern "C" void surface_step_frame(const float* lin, const float* aov, const voi
       float* d = out_hist + 4 * ((size_t)y * width + x);
       d[0] = o.r; d[1] = o.g; d[2] = o.b; d[3] = o.n;
     }
-}
-
-// the surface record of every pixel of `sc` (center1: null, or the centres at shutter close) on host-built tables, through the grid
-// walk; returns 1 when build_tables refused the world
-extern "C" int surface_frame(const RtScene* sc, const double* center1, void* out) {
-  HostTables t;
-  if (!sc || !build_tables(*sc, t, false, center1).empty()) return 1;
-  DevScene ds;
-  fill_dev_scene(*sc, t, ds);
-  ds.geom = t.geom.data(); ds.matc = t.matc.data(); ds.mat = t.mat.data(); ds.lights = t.lights.data();
-  ds.cell_word = t.cell_word.data();
-  ds.cell_items = t.grid.wide ? reinterpret_cast<const uint16_t*>(t.cell_items32.data()) : t.cell_items.data();
-  ds.large = t.large.data(); ds.large_geom = t.large_geom.data();
-  ds.motion = t.motion.empty() ? nullptr : t.motion.data();
-  ds.medium = t.medium.empty() ? nullptr : t.medium.data();
-  const GlobalTables tb{ds.geom, ds.matc};
-  SurfRec* o = static_cast<SurfRec*>(out);
-  for (uint32_t y = 0; y < sc->height; ++y)
-    for (uint32_t x = 0; x < sc->width; ++x) {
-      SurfRec r;
-      if (ds.medium) r = ds.motion ? surface_pixel<true, true>(ds, tb, x, y) : surface_pixel<false, true>(ds, tb, x, y);
-      else r = ds.motion ? surface_pixel<true, false>(ds, tb, x, y) : surface_pixel<false, false>(ds, tb, x, y);
-      o[(size_t)y * sc->width + x] = r;
-    }
-  return 0;
 }

@@ -1,15 +1,15 @@
 """Participating media without a GPU: the schema, rt_neg_log built for the host, and rt_tables.h + hit_world_grid with
-media (tests/medium/medium_walk.cpp, a g++ build) against a brute force of the contract restated in tests/medium_mini.py."""
+media (tests/lanesim, a g++ build) against a brute force of the contract restated in tests/medium_mini.py."""
 import ctypes as C
 import json
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import adversarial_rays as AR
+import lane_sim
 import medium_mini as MM
 import mini_oracle as M
 
@@ -65,16 +65,8 @@ def test_old_scenes_load_and_serialize_as_before(host, abi):
 
 
 @pytest.fixture(scope="module")
-def medium_walk(abi, tmp_path_factory):
-    src = os.path.join(ROOT, "tests", "medium", "medium_walk.cpp")
-    so = str(tmp_path_factory.mktemp("medium_walk") / "libmedium_walk.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-DRT_TEST_PROBES", "-DRT_DEV_KNOBS", "-shared", src, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.medium_neg_log_v.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    L.medium_neg_log_v.restype = None
-    L.medium_tables.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.medium_hit_world_v.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
+def medium_walk(abi):
+    return lane_sim.load(abi)
 
 
 # rt_neg_log's error against the platform's log, measured on the argument set below: 1.000 ulp at worst.  The routine's
@@ -92,8 +84,7 @@ def test_neg_log_bits_accuracy_and_zero(medium_walk):
     x = 1.0 - k.astype(np.float64) * 2.0 ** -53      # (exact: k < 2^53, and 1 - k 2^-53 is a multiple of 2^-53 below 1)
     x = np.concatenate([x, [2.0 ** -53, 1.0 - 2.0 ** -53, 1.0, 0.5, 2.0 ** -0.5, np.nextafter(2.0 ** -0.5, 0.0)]])
     assert len(x) >= 1_000_000 and (x > 0.0).all()
-    out = np.zeros_like(x)
-    medium_walk.medium_neg_log_v(x.ctypes.data, len(x), out.ctypes.data)
+    out = medium_walk.medium_neg_log_v(x)
     worst = 0.0
     for xi, oi in zip(x.tolist(), out.tolist()):
         r = MM.neg_log(xi)
@@ -103,8 +94,7 @@ def test_neg_log_bits_accuracy_and_zero(medium_walk):
             worst = max(worst, abs(oi - ref) / math.ulp(ref))
     print(f"rt_neg_log: worst error against math.log {worst:.3f} ulp over {len(x)} arguments")
     assert worst <= NEG_LOG_MAX_ULP, worst
-    one = np.array([1.0]); res = np.zeros(1)
-    medium_walk.medium_neg_log_v(one.ctypes.data, 1, res.ctypes.data)
+    res = medium_walk.medium_neg_log_v(np.array([1.0]))
     assert res[0] == 0.0 and math.copysign(1.0, res[0]) == 1.0 and math.copysign(1.0, MM.neg_log(1.0)) == 1.0
 
 
@@ -174,10 +164,9 @@ def test_grid_walk_with_media_equals_brute_force(abi, medium_walk, monkeypatch, 
         for i in range(n):
             if i % 3 != 2:
                 c1[i] = c0[i] + rng.uniform(-0.7, 0.7, 3)
-    c1c = np.ascontiguousarray(c1)
-    c1p = c1c.ctypes.data if moving else None
-    info = np.zeros(8, np.uint32); listed = np.zeros(tot, np.uint32); is_large = np.zeros(tot, np.uint8)
-    assert medium_walk.medium_tables(C.byref(sc), c1p, info.ctypes.data, listed.ctypes.data, is_large.ctypes.data) == 0
+    c1c = np.ascontiguousarray(c1) if moving else None
+    rc, info, listed, is_large = medium_walk.medium_tables(sc, c1c)
+    assert rc == 0
     assert info[0] == len(media) and info[1] > 0, "the world must be gridded and know its media"
     assert bool(info[6]) == ("RT_GRID_WIDE" in env)
     # interior cells are kept: a big static medium in the grid is listed in about as many cells as its ball overlaps
@@ -202,9 +191,8 @@ def test_grid_walk_with_media_equals_brute_force(abi, medium_walk, monkeypatch, 
     rays = np.ascontiguousarray(np.concatenate([b[2] for b in blocks]))
     tau_v = np.concatenate([np.full(len(b[2]), b[0], np.float32) for b in blocks])
     nodes = np.ascontiguousarray(rng.choice(np.array([0, 1, 7, 0x80000002, 0xFFFFFFFE], np.uint32), len(rays)))
-    best = np.zeros(len(rays), np.int32); t = np.zeros(len(rays)); work = np.zeros((len(rays), 2), np.uint32)
-    assert medium_walk.medium_hit_world_v(C.byref(sc), c1p, rays.ctypes.data, tau_v.ctypes.data, nodes.ctypes.data, len(rays), best.ctypes.data,
-                                          t.ctypes.data, work.ctypes.data) == 0
+    rc, best, t, work = medium_walk.hit_world_v(sc, rays, c1c, tau=tau_v, node=nodes)
+    assert rc == 0
     k = 0
     n_medium_hits = 0
     for tau, ct, rr in blocks:
@@ -247,20 +235,19 @@ def test_tables_refuse_a_bad_medium(abi, medium_walk):
         spheres[5].radius = 0.5
         spheres[5].kind = abi.RT_MAT_MEDIUM
         spheres[5].fuzz_or_ior = 1.0
-        info = np.zeros(8, np.uint32); listed = np.zeros(40, np.uint32); lg = np.zeros(40, np.uint8)
-        assert medium_walk.medium_tables(C.byref(sc), None, info.ctypes.data, listed.ctypes.data, lg.ctypes.data) == 0 and info[0] == 1
+        rc, info, _, _ = medium_walk.medium_tables(sc)
+        assert rc == 0 and info[0] == 1
         setattr(spheres[5], field, v)
-        assert medium_walk.medium_tables(C.byref(sc), None, info.ctypes.data, listed.ctypes.data, lg.ctypes.data) == 1, (field, v)
+        assert medium_walk.medium_tables(sc)[0] == 1, (field, v)
     sc, spheres = AR.random_scene(abi, rng, 40, 3.0, 0.1, 0.4)
     spheres[5].kind = 6
-    assert medium_walk.medium_tables(C.byref(sc), None, info.ctypes.data, listed.ctypes.data, lg.ctypes.data) == 1
+    assert medium_walk.medium_tables(sc)[0] == 1
 
 
 def test_every_cell_inside_a_gridded_medium_lists_it(abi, medium_walk, monkeypatch):
     """interior cells stay listed: for big media that stay in the grid, the cell of EVERY sampled point of the ball — its heart
     included, cells wholly inside the ball — lists the sphere (rt_tables.h drops only cells farther from the centre than the radius)"""
     L = medium_walk
-    L.medium_cell_lists.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_uint32]
     monkeypatch.setenv("RT_GRID_N", "24,24,24")      # (cells of ~0.55: a ball of radius 1.2 has cells wholly inside it)
     rng = np.random.default_rng(77)
     sc, spheres, n = AR.adversarial_world(abi, rng, 0)
@@ -269,8 +256,8 @@ def test_every_cell_inside_a_gridded_medium_lists_it(abi, medium_walk, monkeypat
         spheres[i].radius = 1.2
         spheres[i].kind = abi.RT_MAT_MEDIUM
         spheres[i].fuzz_or_ior = 0.2
-    info = np.zeros(8, np.uint32); listed = np.zeros(len(spheres), np.uint32); is_large = np.zeros(len(spheres), np.uint8)
-    assert L.medium_tables(C.byref(sc), None, info.ctypes.data, listed.ctypes.data, is_large.ctypes.data) == 0 and info[1] > 0
+    rc, info, listed, is_large = L.medium_tables(sc)
+    assert rc == 0 and info[1] > 0
     cell = 2.0 * (5.0 + 1.2) / info[1:4].astype(np.float64)
     assert (info[1:4] == 24).all() and (cell * math.sqrt(3.0) < 1.2).all(), cell   # (a cell's diagonal is shorter than the radius)
     checked = 0
@@ -280,7 +267,7 @@ def test_every_cell_inside_a_gridded_medium_lists_it(abi, medium_walk, monkeypat
         for _ in range(400):
             v = rng.standard_normal(3); v /= np.linalg.norm(v)
             p = np.ascontiguousarray(c + v * 1.2 * rng.uniform(0.0, 0.999) ** (1.0 / 3.0))
-            got = L.medium_cell_lists(C.byref(sc), p.ctypes.data, i)
+            got = L.medium_cell_lists(sc, p, i)
             assert got in (1, -1), (i, p, got)      # (-1: the point lies outside the grid's box)
             checked += got == 1
     assert checked > 1000
@@ -291,23 +278,20 @@ SIM_CASES = [("unlit", False, 8), ("unlit", False, 50), ("unlit", True, 8), ("li
 
 @pytest.mark.parametrize("world,moving,depth", SIM_CASES)
 def test_cpu_build_of_the_lane_code_equals_the_restatement(abi, oracle, host, medium_walk, world, moving, depth):
-    """rt_core.h's MEDIUM lane code built for the host (hit_world_grid<true>, lane_shade<true> / scatter<true>; tests/medium/) against
+    """rt_core.h's MEDIUM lane code built for the host (hit_world_grid<true>, lane_shade<true> / scatter<true>; tests/lanesim/) against
     MediumMini on the scenes of the GPU parity test: tests/parity.py's bar and the exact segment identity, without a GPU"""
     import test_medium_gpu as G
     from parity import assert_parity, pooled_atol
-    L = medium_walk
-    L.medium_sim_render.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     objs = G._unlit_objs(moving) if world == "unlit" else G._lit_objs(moving)
     spp = 2 if world == "unlit" else 4
     sc, c1, _ = G._load(host, G._cfg(objs, sky=world == "unlit"), 18, 12, spp, depth, seed=21 + depth)
-    c1a = np.ascontiguousarray(c1, np.float64) if c1 is not None else None
-    rgb = np.zeros((12, 18, 3), np.uint8); lin = np.zeros((12, 18, 3), np.float32); segs = C.c_uint64()
-    assert L.medium_sim_render(sc.ptr, c1a.ctypes.data if c1a is not None else None, rgb.ctypes.data, lin.ctypes.data, C.byref(segs)) == 0
+    rc, rgb, lin, segs = medium_walk.render(sc.ptr, c1)
+    assert rc == 0 and rgb.shape == (12, 18, 3)
     OL = oracle.lib(abi)
     m = MM.MediumMini(sc.c, lambda y, x: OL.rt_oracle_atan2(y, x), c1)
     m_rgb, m_lin, m_segs = m.render()
     assert_parity(rgb, lin, m_rgb, m_lin, f"{world} moving={moving}", atol=pooled_atol(spp))
-    assert segs.value == m_segs - m.discarded, (segs.value, m_segs, m.discarded)
+    assert segs == m_segs - m.discarded, (segs, m_segs, m.discarded)
     if world == "lit":
         assert m.discarded > 0
 

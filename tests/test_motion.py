@@ -5,7 +5,7 @@ The reference for motion frames is MotionMini here: tests/mini_oracle.py's ray_c
 restated — each sample's shutter time tau = (philox(pixel, s, NODE_TIME, 0).x >> 8) * 2^-24, every sphere at c0 + dv * tau (dv the
 host's f64 difference, a zero component -0.0) for hit_world and the texture's (u, v); light rays still aim at the static light
 centres.  Colour is compared at the project's parity bar (tests/parity.py); geometry and paths are exact, so unlit segment counts
-are equal.  The grid walk over swept boxes is checked on the CPU (tests/motion, a g++ build of rt_tables.h + rt_core.h
+are equal.  The grid walk over swept boxes is checked on the CPU (tests/lanesim, a g++ build of rt_tables.h + rt_core.h
 hit_world_grid) and on the device (rt_hip_render_rays_probe) against a numpy brute force at each ray's tau."""
 import ctypes as C
 import json
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import adversarial_rays as AR
+import lane_sim
 import mini_oracle as M
 from parity import assert_parity, pooled_atol
 
@@ -277,32 +278,16 @@ def test_schema_errors(host, abi, extra, material, center, msg):
 
 
 @pytest.fixture(scope="module")
-def motion_walk(abi, tmp_path_factory):
-    """tests/motion/motion_walk.cpp: rt_tables.h's motion tables and rt_core.h's hit_world_grid through MotionTables, g++ build"""
-    src = os.path.join(ROOT, "tests", "motion", "motion_walk.cpp")
-    so = str(tmp_path_factory.mktemp("motion_walk") / "libmotion_walk.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-DRT_TEST_PROBES", "-DRT_DEV_KNOBS", "-shared", src, "-o", so],
-                   check=True)
-    L = C.CDLL(so)
-    L.motion_table.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.motion_hit_world_v.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
-def _table(L, scene_ptr, center1):
-    n = scene_ptr.contents.n_spheres
-    out = np.zeros((max(n, 1), 4), np.float64)
-    info = np.zeros(8, np.uint32)
-    c1 = np.ascontiguousarray(center1, np.float64) if center1 is not None else None
-    rc = L.motion_table(scene_ptr, c1.ctypes.data if c1 is not None else None, out.ctypes.data, info.ctypes.data)
-    return rc, out[:n], info
+def motion_walk(abi):
+    """tests/lanesim: rt_tables.h's motion tables and rt_core.h's hit_world_grid through MotionTables, g++ build"""
+    return lane_sim.load(abi)
 
 
 def test_dv_table_is_the_contract_bit_for_bit(host, motion_walk):
     sc = host.Scene.load(MOTION_SCENE)
     c0 = np.array([list(sc.c.spheres[i].center) for i in range(sc.c.n_spheres)])
     c1 = np.array(sc.center1())
-    rc, tab, info = _table(motion_walk, sc.ptr, c1)
+    rc, tab, info = motion_walk.motion_table(sc.ptr, c1)
     assert rc == 0 and info[0] == 405
     want = _dv_array(c0, c1)
     assert np.array_equal(tab[:, :3].view(np.uint64), want.view(np.uint64))      # (-0.0 where nothing moves: the sign bit too)
@@ -314,17 +299,17 @@ def test_dv_table_is_the_contract_bit_for_bit(host, motion_walk):
             assert np.array_equal(np.float64(z) + np.float64(-0.0) * np.float64(tau), np.float64(z)) and \
                 np.signbit(np.float64(z) + np.float64(-0.0) * np.float64(tau)) == np.signbit(np.float64(z))
     # a center1 equal to every centre, or none: the static scene (no table), and the same grid as without motion
-    rc0, _, info0 = _table(motion_walk, sc.ptr, None)
-    rc1, _, info1 = _table(motion_walk, sc.ptr, c0)
+    rc0, _, info0 = motion_walk.motion_table(sc.ptr, None)
+    rc1, _, info1 = motion_walk.motion_table(sc.ptr, c0)
     assert rc0 == rc1 == 2 and np.array_equal(info0, info1)
     # refused: a moving Light sphere, a non-finite difference
     test = host.Scene.load(TEST)
     lights = test.lights()
     tc = np.array([list(test.c.spheres[i].center) for i in range(test.c.n_spheres)])
     bad = tc.copy(); bad[lights[0], 1] += 1.0
-    assert _table(motion_walk, test.ptr, bad)[0] == 1
+    assert motion_walk.motion_table(test.ptr, bad)[0] == 1
     bad = tc.copy(); bad[0, 0] = np.inf
-    assert _table(motion_walk, test.ptr, bad)[0] == 1
+    assert motion_walk.motion_table(test.ptr, bad)[0] == 1
 
 
 MOTION_WORLDS = {
@@ -379,11 +364,10 @@ def test_swept_grid_walk_equals_brute_force(abi, motion_walk, monkeypatch, name)
         rays, _ = AR.ray_table(rng, moved, n, 140, list(range(AR.FAMILIES)))
         all_rays.append(rays); all_tau.append(np.full(len(rays), tau, np.float32))
     rays, tau_v = np.concatenate(all_rays), np.concatenate(all_tau)
-    best = np.zeros(len(rays), np.int32); t = np.zeros(len(rays)); work = np.zeros((len(rays), 2), np.uint32)
     c1c = np.ascontiguousarray(c1)
-    assert motion_walk.motion_hit_world_v(C.byref(sc), c1c.ctypes.data, rays.ctypes.data, tau_v.ctypes.data, len(rays), best.ctypes.data,
-                                          t.ctypes.data, work.ctypes.data) == 0
-    rc, _, info = _table(motion_walk, C.pointer(sc), c1c)
+    rc, best, t, work = motion_walk.hit_world_v(sc, rays, c1c, tau=tau_v)
+    assert rc == 0
+    rc, _, info = motion_walk.motion_table(C.pointer(sc), c1c)
     assert rc == 0 and info[1] > 0, "the world must be gridded"
     k = 0
     for tau, rr in zip(taus, all_rays):

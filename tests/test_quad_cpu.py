@@ -1,15 +1,15 @@
 """Quads and boxes without a GPU: the schema, csrc/common/rt_quad.h built for the host against the restatement of
 tests/quad_mini.py bit for bit and against properties that need no restatement, the tables rt_tables.h builds, and a CPU build of the
-QUADS lane code (tests/quad/quad_sim.cpp, a g++ build) against QuadMini on the frames of the GPU parity test."""
+QUADS lane code (tests/lanesim, a g++ build) against QuadMini on the frames of the GPU parity test."""
 import ctypes as C
 import json
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import lane_sim
 import quad_mini as QM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -130,34 +130,8 @@ def test_old_scenes_have_no_quad(host):
 
 # ------------------------------------------------------------------ rt_quad.h built for the host
 @pytest.fixture(scope="module")
-def quad_sim(abi, tmp_path_factory):
-    src = os.path.join(ROOT, "tests", "quad", "quad_sim.cpp")
-    so = str(tmp_path_factory.mktemp("quad_sim") / "libquad_sim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-DRT_TEST_PROBES", "-DRT_DEV_KNOBS", "-shared", src, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.quad_prepare_v.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.quad_hit_v.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
-    L.quad_box.argtypes = [C.c_void_p] * 3
-    L.quad_tables.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]
-    L.quad_tables.restype = C.c_int64
-    L.quad_tables_error.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64]
-    L.quad_sim_hits.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    L.quad_sim_render.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.quad_sim_aovs.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.quad_sim_surface.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
-
-def _hits(L, quv, rays, closest):
-    """rt_quad_hit / rt_quad_normal of the host build: (status, hit, t, P, normal, front)"""
-    quv = np.ascontiguousarray(quv, np.float64).reshape(9)
-    rays = np.ascontiguousarray(rays, np.float64)
-    closest = np.ascontiguousarray(closest, np.float64)
-    n = len(rays)
-    hit, front = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    t, P, nrm = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3))
-    st = L.quad_hit_v(quv.ctypes.data, rays.ctypes.data, closest.ctypes.data, n, hit.ctypes.data, t.ctypes.data, P.ctypes.data, nrm.ctypes.data, front.ctypes.data)
-    return st, hit, t, P, nrm, front
+def quad_sim(abi):
+    return lane_sim.load(abi)
 
 
 def _bits(x):
@@ -166,7 +140,7 @@ def _bits(x):
 
 def _compare(L, quv, rays, closest, what):
     """the host build against quad_mini on every ray: accept decision, t, P, normal and front_face bit for bit; returns the hit count"""
-    st, hit, t, P, nrm, front = _hits(L, quv, rays, closest)
+    st, hit, t, P, nrm, front = L.quad_hit_v(quv, rays, closest)
     c = QM.QuadConsts(quv[0:3], quv[3:6], quv[6:9])
     assert (st == 0) == c.ok, (what, quv)
     if not c.ok:
@@ -287,8 +261,7 @@ def test_prepare_refuses_what_the_contract_refuses(quad_sim):
         [0, 0, 0, 1, 0, 0, 0, 1, 0], [np.nan, 0, 0, 1, 0, 0, 0, 1, 0], [0, 0, 0, np.inf, 0, 0, 0, 1, 0], [0, 0, 0, 1, 0, 0, 0, -np.inf, 0],
         [0, 0, 0, 1, 0, 0, 2, 0, 0], [0, 0, 0, 0, 0, 0, 0, 1, 0], [0, 0, 0, 1e-160, 0, 0, 0, 1e-160, 0], [0, 0, 0, 1e160, 0, 0, 0, 1e160, 0],
         [0, 0, 0, 1.5e-154, 0, 0, 0, 1.0, 0], [0, 0, 0, 1.4e-154, 0, 0, 0, 1.0, 0], [1e308, 0, 0, 1e100, 0, 0, 0, 1e50, 0]], np.float64)
-    rec, st = np.zeros((len(quv), 16)), np.zeros(len(quv), np.int32)
-    quad_sim.quad_prepare_v(quv.ctypes.data, len(quv), rec.ctypes.data, st.ctypes.data)
+    rec, st = quad_sim.quad_prepare_v(quv)
     assert st.tolist() == [0, 1, 1, 1, 2, 2, 2, 2, 0, 2, 0]      # (1.5e-154^2 = 2.25e-308 is normal, 1.4e-154^2 = 1.96e-308 is not)
     for row, s, r in zip(quv, st, rec):
         c = QM.QuadConsts(row[0:3], row[3:6], row[6:9])
@@ -296,9 +269,8 @@ def test_prepare_refuses_what_the_contract_refuses(quad_sim):
         if c.ok:
             assert _bits(r).tolist() == _bits(list(c.Q) + list(c.u) + list(c.v) + list(c.N) + list(c.w) + [c.D]).tolist()
     # the box's six quads, with the header's operations
-    out = np.zeros((6, 9))
     mn, mx = np.array([0.1, -0.7, 0.3]), np.array([0.4, 0.2, 1.1])
-    quad_sim.quad_box(mn.ctypes.data, mx.ctypes.data, out.ctypes.data)
+    out = quad_sim.quad_box(mn, mx)
     want = np.array([list(a) + list(b) + list(c) for a, b, c in QM.box_quads(mn, mx)])
     assert _bits(out).tolist() == _bits(want).tolist()
     # all six normals point out of the box
@@ -344,7 +316,7 @@ def test_aimed_rays_hit_iff_the_target_is_inside(quad_sim):
         nrm /= np.linalg.norm(nrm)
         dirs = rays[:, 3:] / np.linalg.norm(rays[:, 3:], axis=1)[:, None]
         keep = np.abs(dirs @ nrm) >= math.sin(0.1)
-        st, hit, t, P, _, front = _hits(quad_sim, quv, rays, np.full(n_r, 1.7976931348623157e308))
+        st, hit, t, P, _, front = quad_sim.quad_hit_v(quv, rays, np.full(n_r, 1.7976931348623157e308))
         assert st == 0
         inside = ((ab > margin) & (ab < 1.0 - margin)).all(axis=1)
         outside = ((ab < -margin) | (ab > 1.0 + margin)).any(axis=1)
@@ -364,8 +336,8 @@ def test_swapped_winding_gives_the_same_hit(quad_sim):
         for quv in _quads(rng, 40, kind):
             rays = _aimed(rng, quv, 500)
             closest = np.where(rng.random(500) < 0.5, 1.7976931348623157e308, rng.uniform(0.0, 8.0, 500))
-            a = _hits(quad_sim, quv, rays, closest)
-            b = _hits(quad_sim, np.concatenate([quv[0:3], quv[6:9], quv[3:6]]), rays, closest)
+            a = quad_sim.quad_hit_v(quv, rays, closest)
+            b = quad_sim.quad_hit_v(np.concatenate([quv[0:3], quv[6:9], quv[3:6]]), rays, closest)
             assert a[0] == b[0] == 0 and np.array_equal(a[1], b[1])
             for x, y in zip(a[2:5], b[2:5]):
                 assert np.array_equal(_bits(x), _bits(y)), kind
@@ -399,22 +371,7 @@ def _c_world(abi, n=30):
 
 
 def _tables(L, sc, quads):
-    arr = (type(quads[0]) * len(quads))(*quads) if quads else None
-    info = np.zeros(6, np.uint32)
-    size = L.quad_tables(C.byref(sc), None, arr, len(quads) if quads else 0, info.ctypes.data, None, 0)
-    if size < 0:
-        msg = C.create_string_buffer(256)
-        L.quad_tables_error(C.byref(sc), None, arr, len(quads), msg, 256)
-        return None, info, msg.value.decode()
-    buf = np.zeros(size, np.uint8)
-    assert L.quad_tables(C.byref(sc), None, arr, len(quads) if quads else 0, info.ctypes.data, buf.ctypes.data, size) == size
-    parts, at = [], 0
-    for _ in range(12):
-        n = int(buf[at:at + 8].view(np.uint64)[0])
-        parts.append(buf[at + 8:at + 8 + n].tobytes())
-        at += 8 + n
-    parts.append(buf[at:].tobytes())
-    return parts, info, ""
+    return L.tables(sc, quads=(type(quads[0]) * len(quads))(*quads) if quads else None)
 
 
 def test_tables_validate_quads_and_leave_the_spheres_tables_alone(abi, quad_sim):
@@ -425,11 +382,8 @@ def test_tables_validate_quads_and_leave_the_spheres_tables_alone(abi, quad_sim)
     assert info0[4] == 0 and info0[5] == 1 and free[11] == b""
     # (a non-null pointer with a count of 0 is no quad either)
     one = (abi.RtQuad * 1)(_c_quad(abi))
-    info = np.zeros(6, np.uint32)
-    size = quad_sim.quad_tables(C.byref(sc), None, one, 0, info.ctypes.data, None, 0)
-    buf = np.zeros(size, np.uint8)
-    quad_sim.quad_tables(C.byref(sc), None, one, 0, info.ctypes.data, buf.ctypes.data, size)
-    assert b"".join(len(p).to_bytes(8, "little") + p for p in free[:12]) + free[12] == buf.tobytes()
+    blob, info = quad_sim.tables_blob(sc, quads=one, n_quads=0)
+    assert b"".join(len(p).to_bytes(8, "little") + p for p in free[:12]) + free[12] == blob
     quads = [_c_quad(abi), _c_quad(abi, kind=abi.RT_MAT_METAL), _c_quad(abi, kind=abi.RT_MAT_GLASS), _c_quad(abi, kind=abi.RT_MAT_CHECKER),
              _c_quad(abi, kind=abi.RT_MAT_NOISE, tex_id=2)]
     with_q, info, _ = _tables(quad_sim, sc, quads)
@@ -471,8 +425,8 @@ def test_ids_and_ties(abi, oracle, quad_sim):
                      [1.5, 3.0, 0.0, 0.0, -1.0, 0.0],      # from above: the coincident quads before quad 0
                      [5.0, 9.0, 5.0, 0.0, -1.0, 0.0],      # sphere 0, off every quad
                      [9.0, 9.0, 9.0, 0.0, 1.0, 0.0]])      # nothing
-    best, t = np.zeros(len(rays), np.int32), np.zeros(len(rays))
-    assert quad_sim.quad_sim_hits(C.byref(sc), quads, 3, rays.ctypes.data, len(rays), best.ctypes.data, t.ctypes.data) == 0
+    rc, best, t, _ = quad_sim.hit_world_v(sc, rays, quads=quads, miss_t=0.0)
+    assert rc == 0
     assert best.tolist() == [2 + 0, 1, 2 + 1, 2 + 1, 0, -1] and t[:4].tolist() == [2.0, 0.5, 0.25, 3.0]
     m = QM.QuadMini(sc, lambda y, x: oracle.lib(abi).rt_oracle_atan2(y, x), quads=list(quads))
     m.pixel = m.sample = 0
@@ -481,7 +435,8 @@ def test_ids_and_ties(abi, oracle, quad_sim):
         assert (hit[0] if hit else -1) == b and (hit is None or m.last_t == tt)
     # without the sphere the quad is what the first two rays see
     sc.n_spheres = 1
-    assert quad_sim.quad_sim_hits(C.byref(sc), quads, 3, rays.ctypes.data, 2, best.ctypes.data, t.ctypes.data) == 0
+    rc, best, t, _ = quad_sim.hit_world_v(sc, rays[:2], quads=quads, miss_t=0.0)
+    assert rc == 0
     assert best[:2].tolist() == [1 + 0, 1 + 1] and t[:2].tolist() == [2.0, 0.5]
 
 
@@ -512,17 +467,17 @@ SIM_CASES = [("floor", 8), ("floor", 50), ("room", 8), ("moving", 8), ("medium",
 
 @pytest.mark.parametrize("case,depth", SIM_CASES)
 def test_cpu_build_of_the_lane_code_equals_the_restatement(abi, oracle, host, quad_sim, case, depth):
-    """rt_core.h's QUADS lane code built for the host (quads_hit behind hit_world_grid, lane_shade<MEDIUM, true, true>; tests/quad/) against
-    QuadMini on the pinhole frames of the GPU parity test (48 x 32 at spp 4): tests/parity.py's bar and the exact segment identity"""
+    """rt_core.h's QUADS lane code built for the host (quads_hit behind hit_world_grid, lane_shade<MEDIUM, true, true>: the SOLID arm whatever
+    the scene holds, see tests/lanesim/lane_sim.h) against QuadMini on the pinhole frames of the GPU parity test (48 x 32 at spp 4):
+    tests/parity.py's bar and the exact segment identity"""
     import test_quad_gpu as G
     from parity import assert_parity, pooled_atol
     sc, c1, lens, quads = G.parity_world(host, case, depth)
-    c1a = np.ascontiguousarray(c1, np.float64) if c1 is not None else None
-    rgb = np.zeros((G.H, G.W, 3), np.uint8); lin = np.zeros((G.H, G.W, 3), np.float32); segs = C.c_uint64()
-    assert quad_sim.quad_sim_render(sc.ptr, c1a.ctypes.data if c1a is not None else None, quads, len(quads), rgb.ctypes.data, lin.ctypes.data, C.byref(segs)) == 0
+    rc, rgb, lin, segs = quad_sim.render(sc.ptr, c1, quads, features_or=quad_sim.F_SOLID)
+    assert rc == 0 and rgb.shape == (G.H, G.W, 3)
     m_rgb, m_lin, m_segs, m_disc = G.mini_frame(oracle, abi, host, case, depth)
     assert_parity(rgb, lin, m_rgb, m_lin, case, atol=pooled_atol(G.SPP))
-    assert segs.value == m_segs - m_disc, (segs.value, m_segs, m_disc)
+    assert segs == m_segs - m_disc, (segs, m_segs, m_disc)
     assert len(np.unique(rgb.reshape(-1, 3), axis=0)) > 100
 
 
@@ -530,15 +485,14 @@ def test_cpu_build_of_the_lane_code_equals_the_restatement(abi, oracle, host, qu
 def test_cpu_build_of_the_aovs_and_the_surface_record_equal_the_restatement(abi, oracle, host, quad_sim, case):
     import test_quad_gpu as G
     sc, c1, lens, quads = G.parity_world(host, case, 8)
-    c1a = np.ascontiguousarray(c1, np.float64) if c1 is not None else None
-    c1p = c1a.ctypes.data if c1a is not None else None
-    got = np.zeros((G.H, G.W, 8), np.float32)
-    assert quad_sim.quad_sim_aovs(sc.ptr, c1p, quads, len(quads), 2, got.ctypes.data) == 0
+    rc, got = quad_sim.aovs(sc.ptr, 2, c1, quads, features_or=quad_sim.F_SOLID)
+    assert rc == 0 and got.shape == (G.H, G.W, 8)
     m = G._mini(oracle, abi, sc, c1, None, quads)
     want = m.aovs(2)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), float(np.abs(got - want).max())
-    ids, kinds, ts = np.zeros((G.H, G.W), np.uint32), np.zeros((G.H, G.W), np.uint32), np.zeros((G.H, G.W))
-    assert quad_sim.quad_sim_surface(sc.ptr, c1p, quads, len(quads), ids.ctypes.data, kinds.ctypes.data, ts.ctypes.data) == 0
+    rc, rec = quad_sim.surface(sc.ptr, c1, quads)
+    assert rc == 0 and rec.shape == (G.H, G.W)
+    ids, kinds, ts = rec["id"], rec["kind"], rec["t"]
     w_ids, w_kinds, w_ts = m.surface()
     assert np.array_equal(ids, w_ids) and np.array_equal(kinds, w_kinds) and np.array_equal(_bits(ts), _bits(w_ts))
     n = sc.c.n_spheres

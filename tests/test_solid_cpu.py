@@ -1,15 +1,14 @@
 """Solid textures without a GPU: the schema, csrc/common/rt_solid.h built for the host against the restatement of
 tests/solid_mini.py bit for bit and against properties that need no restatement, and a CPU build of the SOLID lane code
-(tests/solid/solid_sim.cpp, a g++ build) against SolidMini on the frames of the GPU parity test."""
-import ctypes as C
+(tests/lanesim, a g++ build) against SolidMini on the frames of the GPU parity test."""
 import json
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import lane_sim
 import solid_mini as SM
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,40 +102,8 @@ def test_the_example_scene_is_generated(host, abi):
 
 # ------------------------------------------------------------------ rt_solid.h built for the host
 @pytest.fixture(scope="module")
-def solid_sim(abi, tmp_path_factory):
-    src = os.path.join(ROOT, "tests", "solid", "solid_sim.cpp")
-    so = str(tmp_path_factory.mktemp("solid_sim") / "libsolid_sim.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-DRT_TEST_PROBES", "-DRT_DEV_KNOBS", "-shared", src, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.solid_checker_v.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    L.solid_noise_v.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
-    L.solid_factor_v.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.solid_albedo_v.argtypes = [C.POINTER(abi.RtScene), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
-    L.solid_tables.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p]
-    L.solid_sim_render.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.solid_sim_aovs.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_uint32, C.c_void_p]
-    return L
-
-
-def _noise(L, p, seed):
-    p = np.ascontiguousarray(p, np.float64)
-    out = np.zeros(len(p))
-    L.solid_noise_v(p.ctypes.data, len(p), seed, out.ctypes.data)
-    return out
-
-
-def _factor(L, p, mode, octaves, seed):
-    p = np.ascontiguousarray(p, np.float64)
-    out = np.zeros(len(p))
-    L.solid_factor_v(p.ctypes.data, len(p), mode, octaves, seed, out.ctypes.data)
-    return out
-
-
-def _checker(L, p):
-    p = np.ascontiguousarray(p, np.float64)
-    out = np.zeros(len(p), np.int32)
-    L.solid_checker_v(p.ctypes.data, len(p), out.ctypes.data)
-    return out
+def solid_sim(abi):
+    return lane_sim.load(abi)
 
 
 def _points(rng, n):
@@ -171,7 +138,7 @@ def test_host_build_equals_the_restatement_bit_for_bit(solid_sim, mode, octaves)
     third = n // 3
     for j, seed in enumerate((0, 0xFFFFFFFF, 0x9E3779B9)):
         q = p[j * third:(j + 1) * third]
-        got = _factor(solid_sim, q, mode, octaves, seed)
+        got = solid_sim.solid_factor_v(q, mode, octaves, seed)
         for pt, g in zip(q.tolist(), got.tolist()):
             w = SM.factor(tuple(pt), mode, octaves, seed)
             assert w == g and math.copysign(1.0, w) == math.copysign(1.0, g), (pt, mode, octaves, seed, w, g)
@@ -182,11 +149,11 @@ def test_noise_and_checker_equal_the_restatement_bit_for_bit(solid_sim):
     rng = np.random.default_rng(1616)
     p = _points(rng, 100_000)
     for seed in (0, 0xFFFFFFFF):
-        got = _noise(solid_sim, p[:50_000] if seed else p[50_000:], seed)
+        got = solid_sim.solid_noise_v(p[:50_000] if seed else p[50_000:], seed)
         for pt, g in zip((p[:50_000] if seed else p[50_000:]).tolist(), got.tolist()):
             w = SM.noise(tuple(pt), seed)
             assert w == g and math.copysign(1.0, w) == math.copysign(1.0, g), (pt, seed, w, g)
-    got = _checker(solid_sim, p)
+    got = solid_sim.solid_checker_v(p)
     want = np.array([SM.checker_parity(tuple(pt)) for pt in p.tolist()], np.int32)
     assert np.array_equal(got, want), np.nonzero(got != want)[0][:5]
     assert 0.3 < got.mean() < 0.6
@@ -198,13 +165,13 @@ def test_noise_properties_without_the_restatement(solid_sim):
     lat = np.concatenate([rng.integers(-1000, 1000, (20_000, 3)), rng.integers(-2 ** 31 + 1, 2 ** 31 - 1, (20_000, 3)),
                           [[-2 ** 31 + 1, 2 ** 31 - 1, 0], [2 ** 31 - 1] * 3]]).astype(np.float64)
     for seed in (0, 77, 0xFFFFFFFF):
-        assert not _noise(solid_sim, lat, seed).any()
+        assert not solid_sim.solid_noise_v(lat, seed).any()
     # outside (-2^31, 2^31), NaN and inf: 0
     out = np.array([[2.0 ** 31, 0.5, 0.5], [0.5, -2.0 ** 31, 0.5], [0.5, 0.5, np.nan], [np.inf, 0.5, 0.5], [0.5, -np.inf, 0.5]])
-    assert not _noise(solid_sim, out, 5).any()
+    assert not solid_sim.solid_noise_v(out, 5).any()
     # |N| <= 1.5 (the bound rt_solid.h proves), and the values do spread
     p = rng.uniform(-300.0, 300.0, (200_000, 3))
-    v = _noise(solid_sim, p, 12345)
+    v = solid_sim.solid_noise_v(p, 12345)
     assert np.abs(v).max() <= 1.5 and v.max() > 0.7 and v.min() < -0.7 and abs(v.mean()) < 0.01
     # continuous across cell faces: 10^4 pairs straddling a face by 1e-13 of a cell
     base = rng.uniform(-50.0, 50.0, (10_000, 3))
@@ -215,32 +182,32 @@ def test_noise_properties_without_the_restatement(solid_sim):
     hi[np.arange(10_000), axis] = face + 1e-13
     assert (np.floor(lo) != np.floor(hi)).any(axis=1).all()
     for seed in (0, 0xFFFFFFFF):
-        assert np.abs(_noise(solid_sim, lo, seed) - _noise(solid_sim, hi, seed)).max() <= 1e-12
+        assert np.abs(solid_sim.solid_noise_v(lo, seed) - solid_sim.solid_noise_v(hi, seed)).max() <= 1e-12
     # the seed matters
-    assert (_noise(solid_sim, p[:1000], 1) != _noise(solid_sim, p[:1000], 2)).mean() > 0.9
+    assert (solid_sim.solid_noise_v(p[:1000], 1) != solid_sim.solid_noise_v(p[:1000], 2)).mean() > 0.9
 
 
 def test_checker_parity_flips_across_each_plane_family(solid_sim):
     rng = np.random.default_rng(1618)
     base = np.floor(rng.uniform(-200.0, 200.0, (3000, 3))) + rng.uniform(0.1, 0.9, (3000, 3))
-    a = _checker(solid_sim, base)
+    a = solid_sim.solid_checker_v(base)
     for c in range(3):
         step = base.copy()
         step[:, c] += 1.0
-        assert (_checker(solid_sim, step) == 1 - a).all(), c
+        assert (solid_sim.solid_checker_v(step) == 1 - a).all(), c
         step[:, c] += 1.0
-        assert (_checker(solid_sim, step) == a).all(), c
+        assert (solid_sim.solid_checker_v(step) == a).all(), c
     # just either side of a plane, negative coordinates included
     for c in range(3):
         lo, hi = base.copy(), base.copy()
         lo[:, c] = np.nextafter(np.floor(base[:, c]), -np.inf)
         hi[:, c] = np.floor(base[:, c])
-        assert (_checker(solid_sim, lo) != _checker(solid_sim, hi)).all(), c
+        assert (solid_sim.solid_checker_v(lo) != solid_sim.solid_checker_v(hi)).all(), c
     # the 2^52 bound: at and beyond it (and for NaN / inf) the colour is `even`; just below it the parity still counts
     big = np.array([[2.0 ** 52, 0.5, 0.5], [0.5, -2.0 ** 52, 1.5], [1.5, 0.5, 2.0 ** 60], [np.nan, 1.5, 0.5], [0.5, np.inf, 0.5], [0.5, 1.5, -np.inf]])
-    assert not _checker(solid_sim, big).any()
+    assert not solid_sim.solid_checker_v(big).any()
     below = np.array([[2.0 ** 52 - 1.0, 0.5, 0.5], [2.0 ** 52 - 2.0, 0.5, 0.5], [-(2.0 ** 52 - 1.0), 0.5, 0.5], [2.0 ** 52 - 0.5, 0.5, 0.5]])
-    assert _checker(solid_sim, below).tolist() == [1, 0, 1, 1]
+    assert solid_sim.solid_checker_v(below).tolist() == [1, 0, 1, 1]
 
 
 def test_solid_albedo_reads_the_record_in_the_spheres_frame(abi, host, solid_sim):
@@ -254,8 +221,8 @@ def test_solid_albedo_reads_the_record_in_the_spheres_frame(abi, host, solid_sim
         s.center[:] = [13.25, -7.5, 101.125]
         d = rng.standard_normal((2000, 3))
         pts = np.ascontiguousarray(np.array(s.center[:]) + 2.0 * d / np.linalg.norm(d, axis=1)[:, None])
-        col = np.zeros((2000, 3), np.float32)
-        assert solid_sim.solid_albedo_v(sc.ptr, 1, pts.ctypes.data, 2000, col.ctypes.data) == 0
+        rc, col = solid_sim.solid_albedo_v(sc.ptr, 1, pts)
+        assert rc == 0
         want = np.array([SM.solid_colour(s, tuple(s.center), tuple(p)) for p in pts.tolist()], np.float32)
         assert np.array_equal(col.view(np.uint32), want.view(np.uint32)), mat
         assert len(np.unique(col, axis=0)) > (1 if "Checker" in mat else 100)
@@ -274,8 +241,8 @@ def test_tables_count_solids_and_refuse_bad_records(abi, solid_sim):
         for k, v in kw.items():
             setattr(s, k, v)
         sc = abi.RtScene(abi_version=abi.RT_ABI_VERSION, width=4, height=4, samples_per_pixel=1, max_depth=2, sky_mode=1, spheres=spheres, n_spheres=2)
-        info = np.zeros(4, np.uint32)
-        return solid_sim.solid_tables(C.byref(sc), None, info.ctypes.data), info
+        parts, info, _ = solid_sim.tables(sc)      # info = {n_solids, ...}
+        return int(parts is None), info
     for kind in (abi.RT_MAT_CHECKER, abi.RT_MAT_NOISE):
         rc, info = world(kind)
         assert rc == 0 and info[0] == 1
@@ -298,17 +265,16 @@ SIM_CASES = [("unlit", "plain", 8), ("unlit", "plain", 50), ("unlit", "moving", 
 
 @pytest.mark.parametrize("world,variant,depth", SIM_CASES)
 def test_cpu_build_of_the_lane_code_equals_the_restatement(abi, oracle, host, solid_sim, world, variant, depth):
-    """rt_core.h's SOLID lane code built for the host (lane_shade<MEDIUM, true> / scatter's solid arm; tests/solid/) against SolidMini on
+    """rt_core.h's SOLID lane code built for the host (lane_shade<MEDIUM, true> / scatter's solid arm; tests/lanesim/) against SolidMini on
     the pinhole frames of the GPU parity test (24 x 16 at spp 4): tests/parity.py's bar and the exact segment identity"""
     import test_solid_gpu as G
     from parity import assert_parity, pooled_atol
     sc, c1, lens, spp, _ = G.parity_world(host, world, variant, depth)
-    c1a = np.ascontiguousarray(c1, np.float64) if c1 is not None else None
-    rgb = np.zeros((16, 24, 3), np.uint8); lin = np.zeros((16, 24, 3), np.float32); segs = C.c_uint64()
-    assert solid_sim.solid_sim_render(sc.ptr, c1a.ctypes.data if c1a is not None else None, rgb.ctypes.data, lin.ctypes.data, C.byref(segs)) == 0
+    rc, rgb, lin, segs = solid_sim.render(sc.ptr, c1)
+    assert rc == 0 and rgb.shape == (16, 24, 3)
     m_rgb, m_lin, m_segs, m_disc = G.mini_frame(oracle, abi, host, world, variant, depth)
     assert_parity(rgb, lin, m_rgb, m_lin, f"{world} {variant}", atol=pooled_atol(spp))
-    assert segs.value == m_segs - m_disc, (segs.value, m_segs, m_disc)
+    assert segs == m_segs - m_disc, (segs, m_segs, m_disc)
     # the frame does show its solids: not the frame of the same world with the solids' flat `albedo` colours
     assert len(np.unique(rgb.reshape(-1, 3), axis=0)) > (100 if world == "unlit" else 20)
 
@@ -317,9 +283,8 @@ def test_cpu_build_of_the_lane_code_equals_the_restatement(abi, oracle, host, so
 def test_cpu_build_of_the_aov_albedo_equals_the_restatement(abi, oracle, host, solid_sim, moving):
     import test_solid_gpu as G
     sc, c1, _ = G._load(host, G._cfg(G._unlit_objs(moving)), 24, 16, 4, 8, seed=3)
-    c1a = np.ascontiguousarray(c1, np.float64) if c1 is not None else None
-    got = np.zeros((16, 24, 8), np.float32)
-    assert solid_sim.solid_sim_aovs(sc.ptr, c1a.ctypes.data if c1a is not None else None, 4, got.ctypes.data) == 0
+    rc, got = solid_sim.aovs(sc.ptr, 4, c1)
+    assert rc == 0 and got.shape == (16, 24, 8)
     want = G._mini(oracle, abi, sc, c1).aovs(4)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), float(np.abs(got - want).max())
     assert (got[12:, :, 0] > 0.85).any() and (got[12:, :, 0] < 0.25).any(), "both colours of the ground show as albedo"

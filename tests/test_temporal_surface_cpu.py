@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import lane_sim
 import temporal_cases as TC
 import temporal_surface_cases as SC
 import temporal_surface_ref as R
@@ -26,14 +27,14 @@ def _bits(a):
 
 @pytest.fixture(scope="module")
 def step(tmp_path_factory, abi):
-    """CPU build of tests/temporal_surface/step.cpp, -ffp-contract=off"""
+    """CPU builds, -ffp-contract=off: reproject_surface_pixel in tests/temporal_surface/step.cpp, surface_pixel in tests/lanesim"""
     so = str(tmp_path_factory.mktemp("temporal_surface") / "libsurface_step.so")
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unknown-pragmas", "-shared",
                     os.path.join(ROOT, "tests", "temporal_surface", "step.cpp"), "-o", so], check=True)
     L = C.CDLL(so)
     L.surface_step_frame.argtypes = [C.c_void_p] * 9 + [C.c_uint32] * 3 + [C.c_void_p, C.c_void_p]
     L.surface_step_frame.restype = None
-    L.surface_frame.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.c_void_p]
+    sim = lane_sim.load(abi)
 
     class Step:
         @staticmethod
@@ -52,9 +53,8 @@ def step(tmp_path_factory, abi):
 
         @staticmethod
         def surface(sc, center1=None):
-            out = np.zeros((sc.c.height, sc.c.width), R.SURF)
-            c1 = None if center1 is None else np.ascontiguousarray(center1, np.float64)
-            assert L.surface_frame(sc.ptr, None if c1 is None else c1.ctypes.data, out.ctypes.data) == 0
+            rc, out = sim.surface(sc.ptr, center1)
+            assert rc == 0 and out.dtype == R.SURF
             return out
     return Step
 

@@ -42,7 +42,7 @@ int main(int argc, char** argv) {
   RtScene sc; memset(&sc, 0, sizeof sc); sc.abi_version = RT_ABI_VERSION; sc.width = sc.height = 16; sc.samples_per_pixel = 1; sc.max_depth = 5; sc.n_spheres = (uint32_t)n; sc.spheres = all.data();
   HostTables t; build_tables(sc, t); DevScene ds; fill_dev_scene(sc, t, ds);
   if (t.grid.wide) { fprintf(stderr, "wide grid: not handled here\n"); return 2; }
-  ds.geom = t.geom.data(); ds.matc = t.matc.data(); ds.cell_word = t.cell_word.data(); ds.cell_items = t.cell_items.data(); ds.large = t.large.data(); ds.large_geom = t.large_geom.data();
+  bind_host_tables(t, ds);
   printf("grid %ux%ux%u items %u large %u | ", t.grid.n[0], t.grid.n[1], t.grid.n[2], t.grid.n_items, t.grid.n_large);
   // the BVH holds every sphere but the ground (r >= 100: tested by every ray, like the grid's `large` list does)
   SP = all.data(); std::vector<uint32_t> always;

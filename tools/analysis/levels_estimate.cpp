@@ -13,8 +13,7 @@ struct Level { std::vector<RtSphere> sp; std::vector<uint32_t> map; HostTables t
 static void finish(Level& L){
   memset(&L.sc,0,sizeof L.sc); L.sc.abi_version=RT_ABI_VERSION; L.sc.width=L.sc.height=16; L.sc.samples_per_pixel=1; L.sc.max_depth=5; L.sc.n_spheres=(uint32_t)L.sp.size(); L.sc.spheres=L.sp.data();
 }
-static void bind(Level& L){ fill_dev_scene(L.sc,L.t,L.ds); L.ds.geom=L.t.geom.data(); L.ds.matc=L.t.matc.data(); L.ds.cell_word=L.t.cell_word.data();
-  L.ds.cell_items=L.t.grid.wide?reinterpret_cast<const uint16_t*>(L.t.cell_items32.data()):L.t.cell_items.data(); L.ds.large=L.t.large.data(); L.ds.large_geom=L.t.large_geom.data(); }
+static void bind(Level& L){ fill_dev_scene(L.sc,L.t,L.ds); bind_host_tables(L.t,L.ds); }
 int main(int argc,char**argv){
   FILE*f=fopen(argv[1],"rb"); std::vector<double> raw; double b[4]; while(fread(b,8,4,f)==4){raw.insert(raw.end(),b,b+4);} fclose(f);
   const size_t n=raw.size()/4; double ratio=argc>2?atof(argv[2]):4.0; double cps=argc>3?atof(argv[3]):2.0;
