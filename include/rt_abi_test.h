@@ -2,8 +2,8 @@
  * rt_abi_test.h — device probes and diagnostics of the MI355X path tracer: TEST INFRASTRUCTURE, not part of the seam.
  *
  * These entry points exist in librt_hip_probe.so only (the same sources as librt_hip.so compiled with -DRT_TEST_PROBES;
- * rust-raytracer_amd/build.py) — the product library exports none of them.  tests/test_gpu_parity.py and tools/diag.py
- * bind them; a host that replaces raytracer.rs:260-262 needs include/rt_abi.h alone.
+ * rust-raytracer_amd/build.py) — the product library exports none of them.  tests/test_gpu_parity.py, tests/test_walk_rays_gpu.py,
+ * tests/test_quad_rays_gpu.py and tools/diag.py bind them; a host that replaces raytracer.rs:260-262 needs include/rt_abi.h alone.
  */
 #ifndef RT_ABI_TEST_H
 #define RT_ABI_TEST_H
@@ -55,6 +55,14 @@ int rt_hip_quot_probe(const double* d_x, const double* d_y, double* d_quot, doub
 int rt_hip_render_rays_probe(RtHipScene*, const double* d_rays, double* d_first_t, int32_t* d_first_sphere, void* d_rgb8, void* d_linear,
                              RtStats* stats);
 int rt_hip_walk_probe(RtHipScene*, const double* d_rays, double* d_t, int32_t* d_best, uint32_t* d_work, uint32_t n, void* stream);
+/* The quad code on the device (tests/test_quad_rays_gpu.py): rt_core.h quads_hit — the QUADS arm of hit_world — of n rays
+ * d_rays[6i .. 6i+5] = {origin[3], direction[3]}, one per thread, against the scene's quads first_quad .. first_quad + n_quads - 1 in that
+ * order, each ray with its own closest hit so far d_closest[i] and no earlier object; on a hit, object_surface<true> of the accepted id.
+ * d_best[i] = the id (n_spheres + k) or -1; on a hit d_t[i], d_point[3i..], d_normal[3i..] (the hit normal) and d_front[i] (front_face,
+ * 0 / 1) are written, on a miss they are left as they were.  A range outside the scene's quads is RT_ERR_INVALID.  Any double is a valid
+ * component of a ray or a closest: the quad test is arithmetic alone.  All d_* are device pointers. */
+int rt_hip_quad_probe(RtHipScene*, const double* d_rays, const double* d_closest, uint32_t n, uint32_t first_quad, uint32_t n_quads,
+                      int32_t* d_best, double* d_t, double* d_point, double* d_normal, int32_t* d_front, void* stream);
 
 #ifdef __cplusplus
 }

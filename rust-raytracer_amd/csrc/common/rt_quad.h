@@ -1,6 +1,6 @@
 // rt_quad.h — the flat parallelogram of DESIGN.md §20 ("Quadrilaterals" of The Next Week), compiled by the host (rt_tables.h, scene.cpp),
-// the device (rt_core.h) and the CPU tests (tests/quad/quad_sim.cpp).  Its bits are the contract; tests/quad_mini.py restates it in plain
-// Python floats.
+// the device (rt_core.h) and the CPU tests (tests/lanesim/).  Its bits are the contract; tests/quad_mini.py restates it in plain Python
+// floats.
 //
 // A quad is Q, u, v (f64 x 3 each): the points Q + a u + b v with 0 <= a, b <= 1, two-sided.  Every operation below is ONE IEEE f64
 // operation in the order written, no contraction (every build has -ffp-contract=off):

@@ -1901,6 +1901,20 @@ extern "C" int rt_hip_walk_probe(RtHipScene* s, const double* d_rays, double* d_
   return RT_OK;
 }
 
+// rt_core.h quads_hit / object_surface<true> of n rays on the device, one per thread, against a range of the scene's quads (see
+// rtk::rt_quad_probe)
+extern "C" int rt_hip_quad_probe(RtHipScene* s, const double* d_rays, const double* d_closest, uint32_t n, uint32_t first_quad, uint32_t n_quads,
+                                 int32_t* d_best, double* d_t, double* d_point, double* d_normal, int32_t* d_front, void* stream) {
+  if (!s || !d_rays || !d_closest || !d_best || !d_t || !d_point || !d_normal || !d_front) return fail(RT_ERR_INVALID, "null argument");
+  if (first_quad > s->res->n_quads || n_quads > s->res->n_quads - first_quad) return fail(RT_ERR_INVALID, "the range lies outside the scene's quads");
+  if (!n) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_quad_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, d_rays, d_closest, n, first_quad, n_quads,
+                     d_best, d_t, d_point, d_normal, d_front);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
 extern "C" int rt_hip_quot_probe(const double* d_x, const double* d_y, double* d_quot, double* d_rsqrt, double* d_div, uint32_t n, void* stream) {
   if (!d_x || !d_y || !d_quot || !d_rsqrt) return fail(RT_ERR_INVALID, "null argument");
   hipLaunchKernelGGL(rtk::rt_quot_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_x, d_y, d_quot, d_rsqrt, d_div, n);

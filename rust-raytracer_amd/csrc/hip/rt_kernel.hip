@@ -1519,6 +1519,28 @@ __global__ void rt_walk_probe(const DevScene sc, const double* rays, double* out
   if (out_work) { out_work[2 * i] = n_exact; out_work[2 * i + 1] = n_steps; }
 }
 
+// quads_hit and object_surface<true> (rt_core.h) — the QUADS arm of hit_world and the surface record of a quad, whose bits are those of
+// csrc/common/rt_quad.h — of n rays, one per thread, against the scene's quads first_quad .. first_quad + n_quads - 1 in that order, with
+// each ray's own closest-so-far and no earlier hit: out_best = the accepted object id (n_spheres + k) or -1, and on a hit its t, point,
+// hit normal and front_face (untouched on a miss).  The device form of the scan — the cold call, the wave-uniform table pointer and count
+// (read under the partial exec mask of the last block), the records through the constant address space — without the megakernel around it.
+__global__ void rt_quad_probe(const DevScene sc, const double* rays, const double* closest, uint32_t n, uint32_t first_quad, uint32_t n_quads,
+                              int32_t* out_best, double* out_t, double* out_point, double* out_normal, int32_t* out_front) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+  const HitCB r = quads_hit(o, d, sc.quads + first_quad, n_quads, sc.n_spheres + first_quad, closest[i], -1);
+  out_best[i] = r.best;
+  if (r.best < 0) return;
+  const GlobalTables tb{sc.geom, sc.matc};
+  SphereGeom g;
+  const Surface s = object_surface<true>(sc, tb, o, d, r.closest, (uint32_t)r.best, 0.0, g);
+  out_t[i] = r.closest;
+  out_point[3 * i] = s.point.x; out_point[3 * i + 1] = s.point.y; out_point[3 * i + 2] = s.point.z;
+  out_normal[3 * i] = s.normal.x; out_normal[3 * i + 1] = s.normal.y; out_normal[3 * i + 2] = s.normal.z;
+  out_front[i] = s.front_face ? 1 : 0;
+}
+
 // The Texture hit's texel ON THE DEVICE, both ways (materials.rs:236-254 through sphere.rs:35-43): texel_fast — the
 // plain-f64 (u, v) through v_rsq_f64 / v_rcp_f64 + Newton steps that only the device build takes — beside the exact path
 // (three correctly rounded divisions + the shared double-double atan2).  out = n x {fast_ok, fast col, fast row, exact

@@ -117,6 +117,7 @@ def _bind(path, probes):
         L.rt_hip_quot_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
         L.rt_hip_render_rays_probe.argtypes = [C.c_void_p] * 6 + [C.POINTER(abi.RtStats)]
         L.rt_hip_walk_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
+        L.rt_hip_quad_probe.argtypes = [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p] * 6
     for name in (() if os.environ.get("RT_SKIP_LAYOUT_CHECK") else ("RtSphere", "RtQuad", "RtTexture", "RtScene", "RtRowTiles", "RtStats", "RtGroupInfo", "RtGroupRank")):   # the binding's own layout check
         if L.rt_abi_sizeof(name.encode()) != C.sizeof(getattr(abi, name)):
             raise ImportError(f"{path}: sizeof({name}) = {L.rt_abi_sizeof(name.encode())} but abi.py has "
@@ -449,6 +450,12 @@ class HipScene:
         steps), enqueued on `stream`"""
         _check(self._L.rt_hip_walk_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_t), C.c_void_p(d_best), C.c_void_p(d_work or None), n,
                                          C.c_void_p(stream or None)), self._L)
+
+    def quad_probe(self, d_rays, d_closest, n, first_quad, n_quads, d_best, d_t, d_point, d_normal, d_front, stream=0):
+        """(probe library only) rt_hip_quad_probe: quads_hit of n rays with their own closest-so-far against the scene's quads first_quad ..
+        first_quad + n_quads - 1, then object_surface of the accepted id (device pointers), enqueued on `stream`"""
+        _check(self._L.rt_hip_quad_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_closest), n, first_quad, n_quads, C.c_void_p(d_best), C.c_void_p(d_t),
+                                         C.c_void_p(d_point), C.c_void_p(d_normal), C.c_void_p(d_front), C.c_void_p(stream or None)), self._L)
 
     def close(self):
         if self._h:

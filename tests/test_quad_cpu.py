@@ -11,6 +11,7 @@ import pytest
 
 import lane_sim
 import quad_mini as QM
+from quad_rays import CLASSES, _aimed, _quads, class_tables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CORNELL_SCENE = os.path.join(ROOT, "scenes", "cornell_spheres_600x600_spp128.json")
@@ -159,97 +160,16 @@ def _compare(L, quv, rays, closest, what):
     return n_hit
 
 
-AXIS_QUV = np.array([-1.0, -2.0, 0.5, 4.0, 0.0, 0.0, 0.0, 2.0, 0.0])     # N = (0, 0, 1), D = 0.5 exactly: den = d_z, t = (0.5 - o_z) / d_z
-
-
-def _quads(rng, n, kind="generic"):
-    q = rng.uniform(-8.0, 8.0, (n, 3))
-    u = rng.standard_normal((n, 3)) * rng.uniform(0.5, 4.0, (n, 1))
-    v = rng.standard_normal((n, 3)) * rng.uniform(0.5, 4.0, (n, 1))
-    if kind == "skewed":      # nearly parallel edges: a sliver of a parallelogram
-        v = u * rng.uniform(0.3, 2.0, (n, 1)) + rng.standard_normal((n, 3)) * 10.0 ** rng.uniform(-6, -1, (n, 1))
-    if kind == "needle":      # one edge 10^3 .. 10^8 times the other
-        v = v * 10.0 ** rng.uniform(-8, -3, (n, 1))
-    return np.concatenate([q, u, v], axis=1)
-
-
-def _aimed(rng, quv, n, ab=None, dist=(0.5, 16.0)):
-    """n rays aimed at Q + a u + b v (a, b given or uniform in [-0.5, 1.5]) from random origins, d = (target - o) * a random scale"""
-    if ab is None:
-        ab = rng.uniform(-0.5, 1.5, (n, 2))
-    target = quv[0:3] + ab[:, :1] * quv[3:6] + ab[:, 1:] * quv[6:9]
-    dirs = rng.standard_normal((n, 3))
-    o = target - dirs / np.linalg.norm(dirs, axis=1)[:, None] * rng.uniform(*dist, (n, 1))
-    return np.concatenate([o, (target - o) * rng.uniform(0.25, 4.0, (n, 1))], axis=1)
-
-
-def _ulps(x, k):
-    """x moved by k units in the last place (k an integer array, either sign)"""
-    b = np.ascontiguousarray(x, np.float64).view(np.int64)
-    return (b + np.where(x >= 0, k, -k)).view(np.float64)
-
-
-CLASSES = ["generic", "den", "edges", "on_plane", "t_range", "magnitudes", "non_finite", "skewed", "needle"]
-
-
 @pytest.mark.filterwarnings("ignore::RuntimeWarning")     # (the classes make NaN, inf and overflow on purpose)
 @pytest.mark.parametrize("cls", CLASSES)
 def test_host_build_equals_the_restatement_bit_for_bit(quad_sim, cls):
-    """>= 10^5 rays per class (100 quads x 1 000 rays, or the axis-aligned quad whose den and t are exact functions of the ray) through
-    rt_quad_prepare / rt_quad_hit / rt_quad_normal against tests/quad_mini.py: accept decision, t, P, normal, front_face"""
-    rng = np.random.default_rng(2000 + CLASSES.index(cls))
-    n_q, n_r = 100, 1000
+    """>= 10^5 rays per class (tests/quad_rays.py: 100 quads x 1 000 rays, or the axis-aligned quad whose den and t are exact functions of
+    the ray) through rt_quad_prepare / rt_quad_hit / rt_quad_normal against tests/quad_mini.py: accept decision, t, P, normal, front_face"""
     total = hits = 0
-    if cls in ("generic", "skewed", "needle", "magnitudes", "non_finite", "edges", "on_plane"):
-        kind = cls if cls in ("skewed", "needle") else "generic"
-        for quv in _quads(rng, n_q, kind):
-            closest = np.where(rng.random(n_r) < 0.5, 1.7976931348623157e308, rng.uniform(0.0, 8.0, n_r))
-            if cls == "edges":       # through the four edges and corners: a, b within a few ulps of 0 and 1 (and exactly there)
-                ab = rng.uniform(-0.2, 1.2, (n_r, 2))
-                k = rng.integers(-4, 5, (n_r, 2))
-                edge = np.where(rng.random((n_r, 2)) < 0.5, _ulps(np.ones((n_r, 2)), k), k * 2.0 ** -54)
-                ab = np.where(rng.integers(0, 3, (n_r, 2)) > 0, edge, ab)
-                rays = _aimed(rng, quv, n_r, ab)
-            elif cls == "on_plane":  # origins on the plane (t = 0 up to rounding), any direction; some an exact vertex
-                ab = rng.uniform(-0.5, 1.5, (n_r, 2))
-                o = quv[0:3] + ab[:, :1] * quv[3:6] + ab[:, 1:] * quv[6:9]
-                o[:10] = quv[0:3]
-                rays = np.concatenate([o, rng.standard_normal((n_r, 3))], axis=1)
-            else:
-                rays = _aimed(rng, quv, n_r)
-            if cls == "magnitudes":  # huge and tiny |d| (t scales inversely), huge and tiny quads and distances
-                rays[:, 3:] *= 10.0 ** rng.uniform(-300, 300, (n_r, 1))
-                s = 10.0 ** rng.uniform(-100, 100)
-                quv, rays[:, :3] = quv * s, rays[:, :3] * s
-                rays[:, 3:] *= np.where(rng.random((n_r, 1)) < 0.5, s, 1.0)
-            if cls == "non_finite":
-                bad = np.array([np.nan, np.inf, -np.inf, 0.0, -0.0, 1e308, -1e308, 5e-324])
-                sel = rng.random((n_r, 6)) < 0.15
-                rays = np.where(sel, bad[rng.integers(0, len(bad), (n_r, 6))], rays)
-                closest = np.where(rng.random(n_r) < 0.2, bad[rng.integers(0, len(bad), n_r)], closest)
-            with np.errstate(all="ignore"):
-                hits += _compare(quad_sim, quv, rays, closest, cls)
-            total += n_r
-    else:
-        n = n_q * n_r
-        o = np.concatenate([rng.uniform(-3.0, 5.0, (n, 2)), rng.uniform(-4.0, 4.0, (n, 1))], axis=1)
-        d = rng.standard_normal((n, 3))
-        closest = np.full(n, 1.7976931348623157e308)
-        if cls == "den":         # den = d_z within a few ulps of +-1e-8 on both sides (and exactly there), and of 0
-            d[:, 2] = _ulps(np.where(rng.random(n) < 0.5, 1e-8, -1e-8), rng.integers(-6, 7, n))
-            d[: n // 20, 2] = rng.integers(-3, 4, n // 20) * 5e-324
-            o[:, 2] = 0.5 - d[:, 2] * rng.uniform(0.5, 2.0, n) * np.where(rng.random(n) < 0.9, 1.0, 1e8)   # t = 0.5 .. 2 (or 1e8: far off the quad)
-            d[:, :2] = (rng.uniform(-1.0, 3.0, (n, 2)) * [1.0, 0.5] + [0.0, -1.5] - o[:, :2]) / ((0.5 - o[:, 2]) / d[:, 2])[:, None]
-        else:                    # t within a few ulps of 0.001 and of closest, on both sides (and exactly there)
-            d[:, 2] = np.where(rng.random(n) < 0.5, 1.0, -2.0)
-            near_min = rng.random(n) < 0.5
-            t = np.where(near_min, _ulps(np.full(n, 0.001), rng.integers(-6, 7, n)), rng.uniform(0.01, 4.0, n))
-            o[:, 2] = 0.5 - t * d[:, 2]
-            t_real = (0.5 - o[:, 2]) / d[:, 2]
-            closest = np.where(near_min, closest, _ulps(t_real, rng.integers(-6, 7, n)))
-            d[:, :2] = (rng.uniform(-1.0, 3.0, (n, 2)) * [1.0, 0.5] + [0.0, -1.5] - o[:, :2]) / t_real[:, None]
-        hits = _compare(quad_sim, AXIS_QUV, np.concatenate([o, d], axis=1), closest, cls)
-        total = n
+    for quv, rays, closest in class_tables(cls):
+        with np.errstate(all="ignore"):
+            hits += _compare(quad_sim, quv, rays, closest, cls)
+        total += len(rays)
     assert total >= 100_000
     print(f"{cls}: {hits} of {total} rays hit")
     if cls not in ("magnitudes", "non_finite", "on_plane"):
