@@ -85,10 +85,7 @@ struct CullPair {  // 32 B
   float cx[2], cy[2], cz[2], R[2];
 };
 
-#ifndef RT_CULL_CHUNK
-#define RT_CULL_CHUNK 4
-#endif
-constexpr uint32_t CULL_CHUNK = RT_CULL_CHUNK;  // pairs per scan chunk; the table is padded to this
+constexpr uint32_t CULL_CHUNK = 4;  // pairs per scan chunk; the table is padded to this
 
 // Per-sphere fields every hit needs besides the geometry (48 B; the LDS copy of the material
 // table).  Texture parameters stay in the 80 B SphereMat and are fetched only when a Texture
@@ -215,10 +212,8 @@ struct DevScene {
 // selects).  Arguments in [2^-500, 2^500] need neither scaling nor fix-up: the same nine steps on the
 // unscaled value give the same bits (scaling by 2^256 only moves exponents), eight instructions shorter.
 // Everything else (0, denormals, huge, negative, NaN) takes the library's sqrt on a cold path.
-#ifndef RT_FAST_SQRT
-#define RT_FAST_SQRT 1  // (-0.3 % kernel time, profiles/r02_run1_ab.log, r02_run2_ab.log)
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && RT_FAST_SQRT
+// (-0.3 % kernel time against the library's sequence everywhere, profiles/r02_run1_ab.log, r02_run2_ab.log)
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ __attribute__((noinline)) inline double rt_sqrt_cold(double x) { return sqrt(x); }
 __device__ __forceinline__ double rt_sqrt(double x) {
   double g;
@@ -509,17 +504,14 @@ RT_HD RayK ray_consts(V3 d) {
   k.inv_a = rt_div_inrange(1.0, k.a);  // RN(1 / a) when `fast` (the only case it is used in)
   return k;
 }
-#ifndef RT_FLAT_HIT
-#define RT_FLAT_HIT 1  // (-1.5 % kernel time, profiles/r02_run9_ab.log)
-#endif
 template <bool FAST>
 RT_HD bool exact_hit_any_order_t(V3 o, V3 d, const RayK& rk, const SphereGeom& g, uint32_t idx, double& closest, int& best) {
   V3 oc = sub(o, v3(g.cx, g.cy, g.cz));
   double half_b = dot(oc, d);
   double c = length_squared(oc) - g.r * g.r;
-#if RT_FLAT_HIT
   // one divergent region instead of four nested ones: both roots are always formed and the winner is taken by selects
-  // (the nested form's merge points each copy closest / best; the far root costs 6 instructions more)
+  // (the nested form's merge points each copy closest / best; the far root costs 6 instructions more: -1.5 % kernel time,
+  //  profiles/r02_run9_ab.log)
   const double discriminant = (half_b * half_b) - (rk.a * c);
   bool hit = false;
   if (!(c > 0.0 && half_b > 0.0) && discriminant >= 0.0) {  // (exact shortcut, see exact_root)
@@ -536,24 +528,6 @@ RT_HD bool exact_hit_any_order_t(V3 o, V3 d, const RayK& rk, const SphereGeom& g
     best = hit ? (int)idx : best;
   }
   return hit;
-#else
-  if (c > 0.0 && half_b > 0.0) return false;  // exact shortcut, see exact_root
-  double discriminant = (half_b * half_b) - (rk.a * c);
-  if (discriminant >= 0.0) {
-    const bool tie_ok = best >= 0 && idx < (uint32_t)best;
-    double sqrtd = rt_sqrt(discriminant);
-    double num = (-half_b) - sqrtd;
-    double root = FAST ? div_by_recip(num, rk.a, rk.inv_a) : num / rk.a;
-    if (!(root > T_MIN && (root < closest || (tie_ok && root == closest)))) {
-      num = (-half_b) + sqrtd;
-      root = FAST ? div_by_recip(num, rk.a, rk.inv_a) : num / rk.a;
-      if (!(root > T_MIN && (root < closest || (tie_ok && root == closest)))) return false;
-    }
-    closest = root; best = (int)idx;
-    return true;
-  }
-  return false;
-#endif
 }
 // The part of the test above that decides "cannot be accepted" without a square root: the same operations in the same
 // order (sphere.rs:47-53), so `may_hit == false` exactly when exact_hit_any_order_t returns false at its first branch.

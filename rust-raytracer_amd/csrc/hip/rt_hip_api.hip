@@ -43,6 +43,24 @@ int check_wide_tables(bool wide, bool media, bool solids, bool quads = false) {
   return fail(RT_ERR_UNSUPPORTED, std::string(media ? "participating media" : (solids ? "solid textures" : "quads")) + " in a scene with wide tables (more than 65 535 spheres)");
 }
 
+// Argument checks the entry points share.  Each returns RT_OK or the refusal it has recorded (fail): `if (const int refused = ...) return refused;`
+// `p` is a multiple of `align` bytes, a power of two (null passes: what may be null is the caller's business)
+int check_aligned(const void* p, uintptr_t align, const char* message) {
+  return (reinterpret_cast<uintptr_t>(p) & (align - 1u)) ? fail(RT_ERR_INVALID, message) : RT_OK;
+}
+// samples [begin, begin + count) of a pixel fit the exact sums: 2^-40 fixed point in 64 bits (rt_core.h ACCUM_MAX_SAMPLES)
+int check_samples(uint64_t begin, uint64_t count, const char* holder = "an accumulator holds ") {
+  return begin + count > rtc::ACCUM_MAX_SAMPLES ? fail(RT_ERR_UNSUPPORTED, std::string(holder) + "at most 2^23 - 1 samples per pixel") : RT_OK;
+}
+// does the output range lie over one of the input ranges?  (it would be read by other threads while it is written; a null output: no)
+struct Range { const void* p; size_t bytes; };
+bool overlaps(Range out, std::initializer_list<Range> inputs) {
+  const uintptr_t o0 = (uintptr_t)out.p, o1 = o0 + out.bytes;
+  for (const Range& in : inputs)
+    if (o0 && (uintptr_t)in.p < o1 && o0 < (uintptr_t)in.p + in.bytes) return true;
+  return false;
+}
+
 }  // namespace
 
 struct RtHipScene;
@@ -96,6 +114,8 @@ struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept { swap(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }  // (what this one held is freed with `o`)
   ~DevBuf() { if (p) (void)hipFree(p); }
   template <typename T = void> T* get() const { return static_cast<T*>(p); }
   void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
@@ -185,18 +205,39 @@ struct RtHipScene {
   DevBuf counters;          // 4 counters + the work-queue cursor
   int cfg_key = -1; size_t cfg_lds = 0; int cfg_per_cu = 0;  // cached launch configuration
   DevBuf frame;             // framebuffer of rt_hip_render_to_host
+  // What the scene DERIVES from its tables, camera and options lives in four structs by owner (`order` here; `prog`, `tp` and `ad` below), each
+  // with the ONE member that drops it.  Who drops what: every entry is one call at the event's site, "-" means the event leaves it alone.
+  //
+  //   event                                                           order               prog       ad        tp
+  //   rt_hip_set_camera, the same four vectors                        -                   reset()    -         -
+  //   rt_hip_set_camera, another camera                               forget()            reset()    -         -
+  //   rt_hip_set_lens, the same lens                                  -                   -          -         -
+  //   rt_hip_set_lens, another lens                                   forget()            reset()    -         -
+  //   option tile_order, tile_affinity                                forget()            -          -         -
+  //   option seed, max_depth, accum_reset                             -                   reset()    -         -
+  //   option samples_per_pixel and every other option                 -                   -          -         -
+  //   rt_hip_scene_update_spheres, a view following (adopt_tables)    forget()            reset()    reset()   -
+  //   a launch whose OrderKey differs (launch_frame)                  forget(), new key   -          -         -
+  //   rt_hip_scene_warm (+ launch bookkeeping as after creation)      forget(), no key    -          -         -
+  //   rt_hip_temporal_surface (a real change), rt_hip_temporal_reset  -                   -          -         reset()
+  //   a host form that failed, or whose buffer grew: its own state    -                   reset()    -         valid = false
+  //
   // queue order feedback (rt_kernel.hip KArgs::tile_order): depths measured by the last frame of this tile geometry
-  DevBuf tile_depth, tile_order;
   struct OrderKey {         // tile geometry (+ row tiles) an order belongs to: compared field by field
     uint32_t n_tiles = 0, tile_log2 = 0, tile_shape = 0, aff_group_log2 = 0, tile_rows = 0, first_tile = 0, tile_stride = 0, local_rows = 0;
     bool operator==(const OrderKey& o) const {
       return n_tiles == o.n_tiles && tile_log2 == o.tile_log2 && tile_shape == o.tile_shape && aff_group_log2 == o.aff_group_log2 &&
              tile_rows == o.tile_rows && first_tile == o.first_tile && tile_stride == o.tile_stride && local_rows == o.local_rows;
     }
-  } order_key;              // n_tiles == 0: none yet
-  bool order_ready = false; // tile_order holds an order for order_key
-  bool depth_fresh = false; // tile_depth holds depths of THIS view (measured by its last frame) that tile_order does not reflect yet
-  int order_age = 0;        // frames since the order was last invalidated (geometry / camera / option change)
+  };
+  struct Order {
+    DevBuf tile_depth, tile_order;
+    OrderKey key;             // n_tiles == 0: none yet
+    bool ready = false;       // tile_order holds an order for key
+    bool fresh = false;       // tile_depth holds depths of THIS view (measured by its last frame) that tile_order does not reflect yet
+    int age = 0;              // frames since the order was last invalidated (geometry / camera / option change)
+    void forget() { ready = false; fresh = false; age = 0; }  // (the buffers stay: the next frames measure into them)
+  } order;
   DevBuf light_overflow;    // lit scenes: 560 B per lane of the largest launch so far (rt_core.h lane_light_begin)
   uint32_t last_pool_slots = 0, last_base_slots = 0; size_t last_lds_bytes = 0; bool last_lds_tables = false;  // of the last launch (rt_hip_scene_query)
   int last_kernel = -1;    // megakernel instantiation of the last launch, its Kernel::key (rt_hip_scene_query "last_kernel"; -1: none yet)
@@ -221,36 +262,51 @@ struct RtHipScene {
   uint64_t last_waves = 0;
   uint32_t last_tiles_x = 0;
   // progressive rendering, host form (rt_hip_refine_to_host): the scene's own accumulator (width x height x 3 u64, allocated at
-  // first use) and the samples per pixel it holds; accum_zero: it must be cleared before the next pass adds to it
-  DevBuf accum;
-  uint32_t accum_samples = 0;
-  bool accum_zero = true;
-  void reset_accum() { accum_samples = 0; accum_zero = true; aov_ready = false; }
-  // denoising (rt_hip_denoise): the filter's float4 ping-pong (2 x width x height x 16 B), and for
-  // rt_hip_refine_to_host_denoised the resolved linear frame (x 12 B) and the AOV record of the accumulator's start (x 32 B); all
-  // allocated at first use.  aov_ready: dn_aov holds the AOVs of the current accumulator (reset_accum clears it)
-  DevBuf dn_ping, dn_lin, dn_aov;
-  bool aov_ready = false;
+  // first use) and the samples per pixel it holds; zero: it must be cleared before the next pass adds to it.
+  // ... denoised (rt_hip_refine_to_host_denoised): the resolved linear frame (x 12 B; the temporal form resolves into it too)
+  // and the AOV record of the accumulator's start (x 32 B), allocated at first use.  aov_ready: dn_aov holds the AOVs of the current accumulator
+  struct Progressive {
+    DevBuf accum;
+    uint32_t samples = 0;
+    bool zero = true;
+    DevBuf dn_lin, dn_aov;
+    bool aov_ready = false;
+    void reset() { samples = 0; zero = true; aov_ready = false; }
+  } prog;
+  DevBuf dn_ping;           // denoising (rt_hip_denoise): the filter's float4 ping-pong (2 x width x height x 16 B), allocated at first use
   // temporal denoising, host form (rt_hip_render_frame_temporal_to_host): the frame's own accumulator (x 24 B), and
-  // two histories (x 16 B) and guide records (x 32 B) used alternately — tp_cur names the pair the last frame wrote — with the
-  // camera of that frame; all allocated at first use, dropped by rt_hip_temporal_reset.  tp_valid: the pair holds a frame.
-  DevBuf tp_accum, tp_hist[2], tp_aov[2];
-  int tp_cur = 0;
-  bool tp_valid = false;
-  double tp_cam[12] = {};
-  float tp_k[5] = {RT_TEMPORAL_ALPHA_MIN, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH};
+  // two histories (x 16 B) and guide records (x 32 B) used alternately — cur names the pair the last frame wrote — with the
+  // camera of that frame; all allocated at first use.  valid: the pair holds a frame.
   // ... with surface tracking (rt_hip_temporal_surface): two surface records (x 16 B) used alternately like the guides,
   // the displacement table (n_spheres x 24 B) and its host staging (kept as long as the scene: HIP copied from it), and each sphere's
   // centre at shutter time 0.5 of the tables the last temporal frame rendered with.  Allocated at first use in surface mode only.
-  bool tp_surface = false;
-  float tp_alpha_specular = RT_TEMPORAL_SURFACE_ALPHA_SPECULAR;
-  DevBuf tp_surf[2], tp_disp;
-  std::vector<double> tp_mid, tp_disp_host;
+  struct Temporal {
+    DevBuf accum, hist[2], aov[2];
+    int cur = 0;
+    bool valid = false;
+    double cam[12] = {};
+    float k[5] = {RT_TEMPORAL_ALPHA_MIN, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH};
+    bool surface = false;
+    float alpha_specular = RT_TEMPORAL_SURFACE_ALPHA_SPECULAR;
+    DevBuf surf[2], disp;
+    std::vector<double> mid, disp_host;
+    // the history and every buffer go (freed on the current device; the caller has drained the stream that used them); what
+    // rt_hip_temporal_configure and rt_hip_temporal_surface set stays, and so does the staging
+    void reset() {
+      Temporal none;
+      std::memcpy(none.k, k, sizeof k); none.surface = surface; none.alpha_specular = alpha_specular;
+      none.disp_host.swap(disp_host);
+      *this = std::move(none);
+    }
+  } tp;
   // adaptive frames, host form (rt_hip_render_adaptive_to_host): its own now / prev accumulators and per-tile list, errors and
   // counts (allocated at first use), and what each round of the last frame did: {tiles, samples per pixel after it, kernel ms}
-  DevBuf ad_now, ad_prev, ad_list, ad_err, ad_spp;
-  struct AdRound { uint32_t tiles, spp; double kernel_ms; };
-  std::vector<AdRound> ad_rounds;
+  struct Adaptive {
+    DevBuf now, prev, list, err, spp;
+    struct Round { uint32_t tiles, spp; double kernel_ms; };
+    std::vector<Round> rounds;
+    void reset() { rounds.clear(); }
+  } ad;
   Slot& last_slot() { return slot[(n_launches + 1) & 1]; }  // the slot of the most recent launch
 };
 constexpr uint32_t RT_SLOT_COUNTERS = 32;  // segments, exact tests, tex_oob, grid steps, 4 x wave trip counts, 8 x section cycles, profile clocks, (the tile-queue cursors,) [28] repeated segments
@@ -495,8 +551,8 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
   if (!std::strcmp(key, "variant")) { if (value < 0 || value > max_variant) return fail(RT_ERR_INVALID, "variant must be 0 (grid walk) or 1 (brute force)"); s->opt.variant = (int)value; return RT_OK; }
   if (!std::strcmp(key, "tile_log2")) { if (value < -1 || value > 3) return fail(RT_ERR_INVALID, "tile_log2 must be -1..3"); s->opt.tile_log2 = (int)value; return RT_OK; }
   if (!std::strcmp(key, "tile_shape")) { if (value < 0 || value > 3) return fail(RT_ERR_INVALID, "tile_shape must be 0 (square), 1 (scanline runs), 2 (4:1) or 3 (16:1)"); s->opt.tile_shape = (int)value; return RT_OK; }
-  if (!std::strcmp(key, "tile_affinity")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_affinity must be 0 (off), 1 (large frames) or 2 (any frame of 8+ runs: tests)"); s->opt.tile_affinity = (int)value; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; return RT_OK; }
-  if (!std::strcmp(key, "tile_order")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_order must be 0, 1 or 2"); s->opt.order_mode = (int)value; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; return RT_OK; }
+  if (!std::strcmp(key, "tile_affinity")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_affinity must be 0 (off), 1 (large frames) or 2 (any frame of 8+ runs: tests)"); s->opt.tile_affinity = (int)value; s->order.forget(); return RT_OK; }
+  if (!std::strcmp(key, "tile_order")) { if (value < 0 || value > 2) return fail(RT_ERR_INVALID, "tile_order must be 0, 1 or 2"); s->opt.order_mode = (int)value; s->order.forget(); return RT_OK; }
   if (!std::strcmp(key, "light_pool")) { if (value < 0 || value > 1024 || (value != 0 && value < 32)) return fail(RT_ERR_INVALID, "light_pool must be 0 (automatic) or 32..1024"); s->opt.light_pool_cap = (int)value; return RT_OK; }
   if (!std::strcmp(key, "light_base_pool")) { if (value < 0 || value > 1024 || (value != 0 && value < 32)) return fail(RT_ERR_INVALID, "light_base_pool must be 0 (automatic) or 32..1024"); s->opt.light_base_cap = (int)value; return RT_OK; }
   if (!std::strcmp(key, "light_nest_pool")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "light_nest_pool must be 0 or 1"); s->opt.light_nest_pool = (int)value; return RT_OK; }
@@ -506,11 +562,11 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
   if (!std::strcmp(key, "samples_per_pixel") || !std::strcmp(key, "max_depth")) {
     if (value < 0 || value > (int64_t)0xFFFFFFFFll) return fail(RT_ERR_INVALID, std::string(key) + " must be in 0 .. 2^32-1");
     if (key[0] == 's') s->host.samples_per_pixel = s->dev.spp = (uint32_t)value;
-    else { s->host.max_depth = s->dev.max_depth = (uint32_t)value; s->reset_accum(); }
+    else { s->host.max_depth = s->dev.max_depth = (uint32_t)value; s->prog.reset(); }
     return RT_OK;
   }
-  if (!std::strcmp(key, "seed")) { s->host.seed = (uint64_t)value; s->dev.seed_lo = (uint32_t)value; s->dev.seed_hi = (uint32_t)((uint64_t)value >> 32); s->reset_accum(); return RT_OK; }
-  if (!std::strcmp(key, "accum_reset")) { if (value != 1) return fail(RT_ERR_INVALID, "accum_reset takes the value 1"); s->reset_accum(); return RT_OK; }
+  if (!std::strcmp(key, "seed")) { s->host.seed = (uint64_t)value; s->dev.seed_lo = (uint32_t)value; s->dev.seed_hi = (uint32_t)((uint64_t)value >> 32); s->prog.reset(); return RT_OK; }
+  if (!std::strcmp(key, "accum_reset")) { if (value != 1) return fail(RT_ERR_INVALID, "accum_reset takes the value 1"); s->prog.reset(); return RT_OK; }
   return fail(RT_ERR_INVALID, std::string("unknown option ") + key);
 }
 
@@ -845,22 +901,22 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
     key.n_tiles = ka.n_tiles; key.tile_log2 = tl; key.tile_shape = (uint32_t)s->opt.tile_shape; key.aff_group_log2 = ka.aff_group_log2;
     key.tile_rows = ka.tile_rows; key.first_tile = ka.first_tile; key.tile_stride = ka.tile_stride; key.local_rows = local_rows;
     int rc;
-    if ((rc = s->tile_depth.ensure((size_t)ka.n_tiles * 4)) != RT_OK || (rc = s->tile_order.ensure((size_t)ka.n_tiles * 4)) != RT_OK) return rc;
-    if (!(key == s->order_key)) { s->order_key = key; s->order_ready = false; s->depth_fresh = false; s->order_age = 0; }
+    if ((rc = s->order.tile_depth.ensure((size_t)ka.n_tiles * 4)) != RT_OK || (rc = s->order.tile_order.ensure((size_t)ka.n_tiles * 4)) != RT_OK) return rc;
+    if (!(key == s->order.key)) { s->order.key = key; s->order.forget(); }
     // The order of THIS frame from the depths the previous frame of the SAME view measured (sorted here, stream-ordered ahead of
     // the launch — until round 5 behind the frame that measured them, which an animation paid every frame for an order it never
     // used).  Which tiles breed deep paths is a property of scene and camera: rebuilt after each of a view's first two frames,
     // then kept; rt_hip_set_camera with a different camera starts over WITHOUT an order (below).
-    if (s->depth_fresh) {
-      hipLaunchKernelGGL(rtk::rt_order_tiles, dim3(1), dim3(1024), 0, stream, s->tile_depth.get<const uint32_t>(), s->tile_order.get<uint32_t>(), ka.n_tiles, ka.aff_group_log2);
+    if (s->order.fresh) {
+      hipLaunchKernelGGL(rtk::rt_order_tiles, dim3(1), dim3(1024), 0, stream, s->order.tile_depth.get<const uint32_t>(), s->order.tile_order.get<uint32_t>(), ka.n_tiles, ka.aff_group_log2);
       RT_HIP_TRY(hipGetLastError());
-      s->order_ready = true; s->depth_fresh = false;
+      s->order.ready = true; s->order.fresh = false;
     }
-    if (s->opt.order_mode == 2 && s->order_age < 2) ka.tile_depth = s->tile_depth.get<uint32_t>();  // (measured only while the order is still being built)
+    if (s->opt.order_mode == 2 && s->order.age < 2) ka.tile_depth = s->order.tile_depth.get<uint32_t>();  // (measured only while the order is still being built)
 #ifdef RT_TEST_PROBES
     if (ka.probe_rays) ka.tile_depth = nullptr;  // (a probe frame's depths say nothing about the view: it measures none)
 #endif
-    if (s->order_ready) ka.tile_order = s->tile_order.get<uint32_t>();
+    if (s->order.ready) ka.tile_order = s->order.tile_order.get<uint32_t>();
   }
 
   Kernel k;
@@ -876,7 +932,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   launch(s, k, ka, lds_bytes, n_items, stream);
   RT_HIP_TRY(hipGetLastError());
   RT_HIP_TRY(hipEventRecord(sl.ev_stop, stream));
-  if (ka.tile_depth) { s->order_age++; s->depth_fresh = true; }  // (the NEXT frame of this view sorts them into its order)
+  if (ka.tile_depth) { s->order.age++; s->order.fresh = true; }  // (the NEXT frame of this view sorts them into its order)
   return finish_launch(true);
 }
 }  // namespace
@@ -897,7 +953,19 @@ int check_accum(const RtHipScene* s, const RtRowTiles* tiles, const void* d_accu
   if (!s) return fail(RT_ERR_INVALID, "null argument");
   if (rt_tiles_local_rows(s->host.height, tiles) == 0) return RT_OK;
   if (!d_accum) return fail(RT_ERR_INVALID, "null accumulator");
-  if (reinterpret_cast<uintptr_t>(d_accum) & 7u) return fail(RT_ERR_INVALID, "the accumulator must be 8-byte aligned");
+  return check_aligned(d_accum, 8, "the accumulator must be 8-byte aligned");
+}
+// rt_resolve over the n_px pixels of d_accum: every pixel over n_samples, or (d_tile_spp != nullptr) each over its tile's count d_tile_spp[id],
+// the tiles those of tg.  Arguments checked by the caller; nothing to write: nothing launched.
+int launch_resolve(RtHipScene* s, const void* d_accum, uint64_t n_px, uint32_t n_samples, const uint32_t* d_tile_spp, const TileGeom& tg, void* d_rgb8,
+                   void* d_linear, void* stream) {
+  if (!d_rgb8 && !d_linear) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  const uint64_t blocks = ((n_px + 3u) / 4u + 255u) / 256u;
+  if (blocks > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "frame too large to resolve");
+  hipLaunchKernelGGL(rtk::rt_resolve, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_accum, n_samples, n_px,
+                     (uint8_t*)d_rgb8, (float*)d_linear, d_tile_spp, d_tile_spp ? s->host.width : 0u, tg.tiles_x, tg.tile_wl, tg.tile_hl);
+  RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
 }  // namespace
@@ -906,7 +974,7 @@ extern "C" int rt_hip_accumulate(RtHipScene* s, const RtRowTiles* tiles, uint32_
   const int rc = check_accum(s, tiles, d_accum);
   if (rc != RT_OK) return rc;
   if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
-  if ((uint64_t)sample_begin + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  if (const int refused = check_samples(sample_begin, sample_count)) return refused;
   return launch_frame(s, tiles, nullptr, nullptr, (unsigned long long*)d_accum, sample_begin, sample_count, stream);
 }
 
@@ -914,17 +982,11 @@ extern "C" int rt_hip_resolve(RtHipScene* s, const RtRowTiles* tiles, const void
   int rc = check_accum(s, tiles, d_accum);
   if (rc != RT_OK) return rc;
   if (n_samples == 0) return fail(RT_ERR_INVALID, "n_samples must be at least 1");
-  if (n_samples > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
-  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  if ((rc = check_samples(0, n_samples)) != RT_OK) return rc;
+  if ((rc = check_aligned(d_linear, 4, "d_linear must be 4-byte aligned")) != RT_OK) return rc;
   const uint64_t n_px = (uint64_t)rt_tiles_local_rows(s->host.height, tiles) * s->host.width;
-  if (n_px == 0 || (!d_rgb8 && !d_linear)) return RT_OK;
-  RT_HIP_TRY(hipSetDevice(s->device));
-  const uint64_t blocks = ((n_px + 3u) / 4u + 255u) / 256u;
-  if (blocks > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "frame too large to resolve");
-  hipLaunchKernelGGL(rtk::rt_resolve, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_accum, n_samples, n_px,
-                     (uint8_t*)d_rgb8, (float*)d_linear, (const uint32_t*)nullptr, 0u, 0u, 0u, 0u);
-  RT_HIP_TRY(hipGetLastError());
-  return RT_OK;
+  if (n_px == 0) return RT_OK;
+  return launch_resolve(s, d_accum, n_px, n_samples, nullptr, TileGeom(), d_rgb8, d_linear, stream);
 }
 
 // Adaptive sampling: per-tile sample counts over the accumulating kernels' own pixel tiles.
@@ -932,7 +994,7 @@ namespace {
 // the tiles of `tiles`' packed rows; n_list must name 1 .. tile count tiles
 int check_list(const RtHipScene* s, const RtRowTiles* tiles, const uint32_t* d_list, uint32_t n_list, TileGeom* tg) {
   if (!d_list || n_list == 0) return fail(RT_ERR_INVALID, "the tile list must name at least one tile");
-  if (reinterpret_cast<uintptr_t>(d_list) & 3u) return fail(RT_ERR_INVALID, "the tile list must be 4-byte aligned");
+  if (const int refused = check_aligned(d_list, 4, "the tile list must be 4-byte aligned")) return refused;
   const int rc = tile_geometry(s, rt_tiles_local_rows(s->host.height, tiles), tg);
   if (rc != RT_OK) return rc;
   if ((uint64_t)n_list > (uint64_t)tg->tiles_x * tg->tiles_y) return fail(RT_ERR_INVALID, "the tile list is longer than the frame has tiles");
@@ -957,7 +1019,7 @@ extern "C" int rt_hip_accumulate_tiles(RtHipScene* s, const RtRowTiles* tiles, c
   if ((rc = check_list(s, tiles, d_tile_list, n_list, &tg)) != RT_OK) return rc;
   if (!d_accum) return fail(RT_ERR_INVALID, "null accumulator");
   if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
-  if ((uint64_t)sample_begin + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  if ((rc = check_samples(sample_begin, sample_count)) != RT_OK) return rc;
   return launch_frame(s, tiles, nullptr, nullptr, (unsigned long long*)d_accum, sample_begin, sample_count, stream, d_tile_list, n_list);
 }
 
@@ -967,10 +1029,10 @@ extern "C" int rt_hip_tile_error(RtHipScene* s, const RtRowTiles* tiles, const u
   TileGeom tg;
   int rc = check_list(s, tiles, d_tile_list, n_list, &tg);
   if (rc != RT_OK) return rc;
-  if ((reinterpret_cast<uintptr_t>(d_now) | reinterpret_cast<uintptr_t>(d_prev) | reinterpret_cast<uintptr_t>(d_tile_err)) & 7u)
-    return fail(RT_ERR_INVALID, "accumulators and the error array must be 8-byte aligned");
+  for (const void* q : {d_now, d_prev, (const void*)d_tile_err})
+    if ((rc = check_aligned(q, 8, "accumulators and the error array must be 8-byte aligned")) != RT_OK) return rc;
   if (n_prev == 0 || n_now <= n_prev) return fail(RT_ERR_INVALID, "the counts must satisfy 0 < n_prev < n_now");
-  if (n_now > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  if ((rc = check_samples(0, n_now)) != RT_OK) return rc;
   RT_HIP_TRY(hipSetDevice(s->device));
   const uint64_t threads = (uint64_t)n_list << (2u * tg.tile_log2), blocks = (threads + 255u) / 256u;
   hipLaunchKernelGGL(rtk::rt_tile_error, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_now, n_now,
@@ -987,19 +1049,11 @@ extern "C" int rt_hip_resolve_tiles(RtHipScene* s, const RtRowTiles* tiles, cons
   const uint32_t rows = rt_tiles_local_rows(s->host.height, tiles);
   if (rows == 0) return RT_OK;
   if (!d_tile_spp) return fail(RT_ERR_INVALID, "null tile counts");
-  if (reinterpret_cast<uintptr_t>(d_tile_spp) & 3u) return fail(RT_ERR_INVALID, "the tile counts must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  if ((rc = check_aligned(d_tile_spp, 4, "the tile counts must be 4-byte aligned")) != RT_OK) return rc;
+  if ((rc = check_aligned(d_linear, 4, "d_linear must be 4-byte aligned")) != RT_OK) return rc;
   TileGeom tg;
   if ((rc = tile_geometry(s, rows, &tg)) != RT_OK) return rc;
-  const uint64_t n_px = (uint64_t)rows * s->host.width;
-  if (!d_rgb8 && !d_linear) return RT_OK;
-  RT_HIP_TRY(hipSetDevice(s->device));
-  const uint64_t blocks = ((n_px + 3u) / 4u + 255u) / 256u;
-  if (blocks > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "frame too large to resolve");
-  hipLaunchKernelGGL(rtk::rt_resolve, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_accum, 1u, n_px,
-                     (uint8_t*)d_rgb8, (float*)d_linear, d_tile_spp, s->host.width, tg.tiles_x, tg.tile_wl, tg.tile_hl);
-  RT_HIP_TRY(hipGetLastError());
-  return RT_OK;
+  return launch_resolve(s, d_accum, (uint64_t)rows * s->host.width, 1u, d_tile_spp, tg, d_rgb8, d_linear, stream);
 }
 
 #ifdef RT_TEST_PROBES
@@ -1010,8 +1064,8 @@ extern "C" int rt_hip_debug_tile_depth(RtHipScene* s, uint32_t* out, uint32_t ca
   if (!s || !out) return fail(RT_ERR_INVALID, "null argument");
   RT_HIP_TRY(hipSetDevice(s->device));
   if (s->n_launches) RT_HIP_TRY(hipStreamSynchronize(s->last_stream));
-  const uint32_t n = s->order_key.n_tiles < cap ? s->order_key.n_tiles : cap;
-  if (n && s->tile_depth.p) RT_HIP_TRY(hipMemcpy(out, s->tile_depth.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  const uint32_t n = s->order.key.n_tiles < cap ? s->order.key.n_tiles : cap;
+  if (n && s->order.tile_depth.p) RT_HIP_TRY(hipMemcpy(out, s->order.tile_depth.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   if (tiles_x) *tiles_x = s->last_tiles_x;
   return (int)n;
 }
@@ -1094,16 +1148,16 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "solids")) return (int64_t)s->res->n_solids;       // spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE
   if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
   if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
-  if (!std::strcmp(key, "accum_samples")) return (int64_t)s->accum_samples;
-  if (!std::strcmp(key, "temporal_surface")) return s->tp_surface ? 1 : 0;
+  if (!std::strcmp(key, "accum_samples")) return (int64_t)s->prog.samples;
+  if (!std::strcmp(key, "temporal_surface")) return s->tp.surface ? 1 : 0;
   // the last rt_hip_render_adaptive_to_host: its rounds, and round i's tiles, samples per pixel after it, kernel time in microseconds
-  if (!std::strcmp(key, "adaptive_rounds")) return (int64_t)s->ad_rounds.size();
+  if (!std::strcmp(key, "adaptive_rounds")) return (int64_t)s->ad.rounds.size();
   for (const char* f : {"adaptive_round_tiles_", "adaptive_round_spp_", "adaptive_round_kernel_us_"}) {
     const size_t l = std::strlen(f);
     if (std::strncmp(key, f, l) != 0 || key[l] < '0' || key[l] > '9') continue;
     const unsigned long i = std::strtoul(key + l, nullptr, 10);
-    if (i >= s->ad_rounds.size()) return -1;
-    const RtHipScene::AdRound& r = s->ad_rounds[i];
+    if (i >= s->ad.rounds.size()) return -1;
+    const RtHipScene::Adaptive::Round& r = s->ad.rounds[i];
     return f[15] == 't' ? (int64_t)r.tiles : (f[15] == 's' ? (int64_t)r.spp : (int64_t)std::llround(r.kernel_ms * 1000.0));
   }  // samples per pixel in the scene's accumulator (rt_hip_refine_to_host)
   if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->res->grid.n_cells * (s->res->grid.wide ? 16u : 8u) + (size_t)s->res->grid.n_items * (s->res->grid.wide ? 4u : 2u));
@@ -1113,7 +1167,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
 extern "C" int rt_hip_set_camera(RtHipScene* s, const double origin[3], const double lower_left[3], const double horizontal[3],
                                  const double vertical[3]) {
   if (!s || !origin || !lower_left || !horizontal || !vertical) return fail(RT_ERR_INVALID, "null argument");
-  s->reset_accum();  // (whatever the camera: a progressive frame starts over)
+  s->prog.reset();  // (whatever the camera: a progressive frame starts over)
   bool same = true;
   for (int i = 0; i < 3; ++i)
     same = same && s->host.cam_origin[i] == origin[i] && s->host.cam_lower_left[i] == lower_left[i] && s->host.cam_horizontal[i] == horizontal[i] &&
@@ -1130,7 +1184,7 @@ extern "C" int rt_hip_set_camera(RtHipScene* s, const double origin[3], const do
   // the stale order costs 3 - 10 % against the view's own order and is WORSE than no order (+3 - 4 %): the tiles that hold a
   // view's rare 50-segment paths are 4x4 pixels, and a 3 degree turn moves the spheres by tens of pixels
   // (bench.py `animation.same_views`, profiles/r06_run*_bench.json; the old arm was removed after that A/B).
-  s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
+  s->order.forget();
   return RT_OK;
 }
 
@@ -1143,27 +1197,37 @@ extern "C" int rt_hip_set_lens(RtHipScene* s, const double u[3], const double v[
   if (same) return RT_OK;  // (pinhole to pinhole, or the same lens: the accumulator and the queue order stay)
   for (int i = 0; i < 3; ++i) { s->dev.lens_u[i] = u[i]; s->dev.lens_v[i] = v[i]; }
   s->dev.lens_r = lens_radius;
-  s->reset_accum();
-  s->order_ready = false; s->depth_fresh = false; s->order_age = 0;  // (another view: it measures its own order, as after rt_hip_set_camera)
+  s->prog.reset();
+  s->order.forget();  // (another view: it measures its own order, as after rt_hip_set_camera)
   return RT_OK;
 }
 
+namespace {
+// What the blocking host forms share.  They render into s->frame on the NULL stream: the clock and the device at the start; at the end the
+// wait for the form's launches, then the frame copied to the caller with the last launch's stats, frame_ms taken from the form's own start.
+struct HostForm {
+  RtHipScene* s;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  RtStats st{};   // of the form's last launch (wait)
+  int begin() { RT_HIP_TRY(hipSetDevice(s->device)); return RT_OK; }
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+  int wait(int rc) { return rc == RT_OK ? rt_hip_wait(s, &st) : rc; }  // rc: how enqueueing went; a form that failed drops its own state
+  int deliver(uint8_t* out_rgb8, RtStats* stats) {
+    RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, (size_t)s->host.width * s->host.height * 3, hipMemcpyDeviceToHost));
+    if (stats) { *stats = st; stats->frame_ms = ms(); }
+    return RT_OK;
+  }
+};
+}  // namespace
+
 extern "C" int rt_hip_render_to_host(RtHipScene* s, uint8_t* out_rgb8, RtStats* stats) {
   if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
-  auto t0 = std::chrono::steady_clock::now();
-  RT_HIP_TRY(hipSetDevice(s->device));
-  const size_t bytes = (size_t)s->host.width * s->host.height * 3;
-  int rc = s->frame.ensure(bytes);
+  HostForm f{s};
+  int rc = f.begin();
+  if (rc == RT_OK) rc = s->frame.ensure((size_t)s->host.width * s->host.height * 3);
   if (rc == RT_OK) rc = rt_hip_render(s, nullptr, s->frame.p, nullptr, nullptr);
-  RtStats st;
-  if (rc == RT_OK) rc = rt_hip_wait(s, &st);
-  if (rc != RT_OK) return rc;
-  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, bytes, hipMemcpyDeviceToHost));
-  if (stats) {
-    *stats = st;
-    stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return RT_OK;
+  if ((rc = f.wait(rc)) != RT_OK) return rc;
+  return f.deliver(out_rgb8, stats);
 }
 
 namespace {
@@ -1178,44 +1242,37 @@ uint32_t aov_default_samples(uint32_t spp) { return spp < 1u ? 1u : (spp < RT_DE
 int refine_to_host(RtHipScene* s, uint32_t sample_count, int iterations, uint8_t* out_rgb8, RtStats* stats) {
   if (!s || !out_rgb8) return fail(RT_ERR_INVALID, "null argument");
   if (sample_count == 0) return fail(RT_ERR_INVALID, "sample_count must be at least 1");
-  if ((uint64_t)s->accum_samples + sample_count > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
-  auto t0 = std::chrono::steady_clock::now();
-  RT_HIP_TRY(hipSetDevice(s->device));
+  if (const int refused = check_samples(s->prog.samples, sample_count)) return refused;
+  HostForm f{s};
+  int rc = f.begin();
+  if (rc != RT_OK) return rc;
   const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 3;
   bool grew = false;
-  int rc;
-  if ((rc = s->accum.ensure(px * 24, &grew)) != RT_OK) return rc;
-  if (grew) s->reset_accum();
+  if ((rc = s->prog.accum.ensure(px * 24, &grew)) != RT_OK) return rc;
+  if (grew) s->prog.reset();
   if ((rc = s->frame.ensure(bytes)) != RT_OK) return rc;
   if (iterations >= 0) {  // the host form's own linear frame and AOV record
-    if ((rc = s->dn_lin.ensure(px * 12)) != RT_OK || (rc = s->dn_aov.ensure(px * 32, &grew)) != RT_OK) return rc;
-    if (grew) s->aov_ready = false;
+    if ((rc = s->prog.dn_lin.ensure(px * 12)) != RT_OK || (rc = s->prog.dn_aov.ensure(px * 32, &grew)) != RT_OK) return rc;
+    if (grew) s->prog.aov_ready = false;
   }
-  if (s->accum_zero && px) { RT_HIP_TRY(hipMemsetAsync(s->accum.p, 0, px * 24, nullptr)); s->accum_zero = false; }
-  const uint32_t n = s->accum_samples + sample_count;
-  unsigned long long* accum = s->accum.get<unsigned long long>();
-  rc = rt_hip_accumulate(s, nullptr, s->accum_samples, sample_count, accum, nullptr);
+  if (s->prog.zero && px) { RT_HIP_TRY(hipMemsetAsync(s->prog.accum.p, 0, px * 24, nullptr)); s->prog.zero = false; }
+  const uint32_t n = s->prog.samples + sample_count;
+  unsigned long long* accum = s->prog.accum.get<unsigned long long>();
+  rc = rt_hip_accumulate(s, nullptr, s->prog.samples, sample_count, accum, nullptr);
   if (iterations < 0) {
     if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, accum, n, s->frame.p, nullptr, nullptr);
   } else {
-    if (rc == RT_OK && !s->aov_ready) {
-      rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(s->host.samples_per_pixel), s->dn_aov.p, nullptr);
-      if (rc == RT_OK) s->aov_ready = true;
+    if (rc == RT_OK && !s->prog.aov_ready) {
+      rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(s->host.samples_per_pixel), s->prog.dn_aov.p, nullptr);
+      if (rc == RT_OK) s->prog.aov_ready = true;
     }
-    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, accum, n, nullptr, s->dn_lin.p, nullptr);
+    if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, accum, n, nullptr, s->prog.dn_lin.p, nullptr);
     const float sigma[4] = {RT_DENOISE_SIGMA_COLOR, RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_ALBEDO, RT_DENOISE_SIGMA_INV_DEPTH};
-    if (rc == RT_OK) rc = denoise_frame(s, s->dn_lin.p, s->dn_aov.p, (uint32_t)iterations, sigma, nullptr, s->frame.p, nullptr);
+    if (rc == RT_OK) rc = denoise_frame(s, s->prog.dn_lin.p, s->prog.dn_aov.p, (uint32_t)iterations, sigma, nullptr, s->frame.p, nullptr);
   }
-  RtStats st;
-  if (rc == RT_OK) rc = rt_hip_wait(s, &st);
-  if (rc != RT_OK) { s->reset_accum(); return rc; }  // (a pass that did not complete leaves the accumulator unknown: start over)
-  s->accum_samples = n;
-  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, bytes, hipMemcpyDeviceToHost));
-  if (stats) {
-    *stats = st;
-    stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
-  return RT_OK;
+  if ((rc = f.wait(rc)) != RT_OK) { s->prog.reset(); return rc; }  // (a pass that did not complete leaves the accumulator unknown: start over)
+  s->prog.samples = n;
+  return f.deliver(out_rgb8, stats);
 }
 }  // namespace
 
@@ -1287,11 +1344,11 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   const int rc = check_whole_frame(s, tiles);
   if (rc != RT_OK) return rc;
   if (n_samples == 0) return fail(RT_ERR_INVALID, "n_samples must be at least 1");
-  if (n_samples > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "at most 2^23 - 1 samples per pixel");
+  if (const int refused = check_samples(0, n_samples, "")) return refused;
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0) return RT_OK;
   if (!d_aov) return fail(RT_ERR_INVALID, "null AOV buffer");
-  if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
+  if (const int refused = check_aligned(d_aov, 16, "the AOV buffer must be 16-byte aligned")) return refused;
   RT_HIP_TRY(hipSetDevice(s->device));
   static const std::array<AovKernel, 16> table = aov_kernels(std::make_integer_sequence<int, 16>());
   const int features = (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
@@ -1312,14 +1369,11 @@ extern "C" int rt_hip_denoise(RtHipScene* s, const RtRowTiles* tiles, const void
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0) return RT_OK;
   if (!d_linear || !d_aov) return fail(RT_ERR_INVALID, "null input buffer");
-  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_aov) & 15u) return fail(RT_ERR_INVALID, "the AOV buffer must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_out_linear) & 3u) return fail(RT_ERR_INVALID, "d_out_linear must be 4-byte aligned");
-  // (an output over an input would be read by neighbouring threads while it is written)
-  const uintptr_t lin0 = (uintptr_t)d_linear, lin1 = lin0 + px * 12, aov0 = (uintptr_t)d_aov, aov1 = aov0 + px * 32;
-  for (const std::pair<uintptr_t, size_t> o : {std::make_pair((uintptr_t)d_out_linear, px * 12), std::make_pair((uintptr_t)d_out_rgb8, px * 3)})
-    if (o.first && ((o.first < lin1 && lin0 < o.first + o.second) || (o.first < aov1 && aov0 < o.first + o.second)))
-      return fail(RT_ERR_INVALID, "the outputs must not overlap the inputs");
+  if ((rc = check_aligned(d_linear, 4, "d_linear must be 4-byte aligned")) != RT_OK) return rc;
+  if ((rc = check_aligned(d_aov, 16, "the AOV buffer must be 16-byte aligned")) != RT_OK) return rc;
+  if ((rc = check_aligned(d_out_linear, 4, "d_out_linear must be 4-byte aligned")) != RT_OK) return rc;
+  for (const Range out : {Range{d_out_linear, px * 12}, Range{d_out_rgb8, px * 3}})  // (neighbouring threads read the inputs while an output is written)
+    if (overlaps(out, {{d_linear, px * 12}, {d_aov, px * 32}})) return fail(RT_ERR_INVALID, "the outputs must not overlap the inputs");
   return denoise_frame(s, d_linear, d_aov, iterations, sigma, d_out_linear, d_out_rgb8, (hipStream_t)stream);
 }
 
@@ -1367,16 +1421,13 @@ extern "C" int rt_hip_reproject(RtHipScene* s, const void* d_linear, const void*
   if (rc != RT_OK) return rc;
   if ((rc = check_reproject_params(alpha_min, n_max, tau_n, tau_a, tau_z)) != RT_OK) return rc;
   if (!d_linear || !d_aov || !d_prev_history || !d_prev_aov || !prev_camera || !d_out_history) return fail(RT_ERR_INVALID, "null argument");
-  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  if ((rc = check_aligned(d_linear, 4, "d_linear must be 4-byte aligned")) != RT_OK) return rc;
   for (const void* q : {d_aov, d_prev_history, d_prev_aov, (const void*)d_out_history})
-    if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(RT_ERR_INVALID, "the guide and history buffers must be 16-byte aligned");
+    if ((rc = check_aligned(q, 16, "the guide and history buffers must be 16-byte aligned")) != RT_OK) return rc;
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0) return RT_OK;
-  // (an output over an input would be read by other threads while it is written)
-  const uintptr_t o0 = (uintptr_t)d_out_history, o1 = o0 + px * 16;
-  for (const std::pair<uintptr_t, size_t> in : {std::make_pair((uintptr_t)d_linear, px * 12), std::make_pair((uintptr_t)d_aov, px * 32),
-                                                std::make_pair((uintptr_t)d_prev_history, px * 16), std::make_pair((uintptr_t)d_prev_aov, px * 32)})
-    if (in.first < o1 && o0 < in.first + in.second) return fail(RT_ERR_INVALID, "the output must not overlap the inputs");
+  if (overlaps({d_out_history, px * 16}, {{d_linear, px * 12}, {d_aov, px * 32}, {d_prev_history, px * 16}, {d_prev_aov, px * 32}}))
+    return fail(RT_ERR_INVALID, "the output must not overlap the inputs");
   RT_HIP_TRY(hipSetDevice(s->device));
   const float k[5] = {alpha_min, n_max, tau_n, tau_a, tau_z};
   return reproject_frame(s, d_linear, d_aov, d_prev_history, d_prev_aov, prev_camera, k, d_out_history, (hipStream_t)stream);
@@ -1387,7 +1438,7 @@ extern "C" int rt_hip_render_surface(RtHipScene* s, const RtRowTiles* tiles, voi
   const int rc = check_whole_frame(s, tiles);
   if (rc != RT_OK) return rc;
   if (!d_surface) return fail(RT_ERR_INVALID, "null surface buffer");
-  if (reinterpret_cast<uintptr_t>(d_surface) & 15u) return fail(RT_ERR_INVALID, "the surface buffer must be 16-byte aligned");
+  if (const int refused = check_aligned(d_surface, 16, "the surface buffer must be 16-byte aligned")) return refused;
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
@@ -1429,19 +1480,15 @@ extern "C" int rt_hip_reproject_surface(RtHipScene* s, const void* d_linear, con
   if (!(alpha_specular >= 0.0f && alpha_specular <= 1.0f)) return fail(RT_ERR_INVALID, "alpha_specular must lie in [0, 1]");
   if (!d_linear || !d_aov || !d_surface || !d_prev_history || !d_prev_aov || !d_prev_surface || !prev_camera || !d_out_history)
     return fail(RT_ERR_INVALID, "null argument");
-  if (reinterpret_cast<uintptr_t>(d_linear) & 3u) return fail(RT_ERR_INVALID, "d_linear must be 4-byte aligned");
+  if ((rc = check_aligned(d_linear, 4, "d_linear must be 4-byte aligned")) != RT_OK) return rc;
   for (const void* q : {d_aov, d_surface, d_prev_history, d_prev_aov, d_prev_surface, (const void*)d_out_history})
-    if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(RT_ERR_INVALID, "the guide, surface and history buffers must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_displacement) & 7u) return fail(RT_ERR_INVALID, "the displacement table must be 8-byte aligned");
+    if ((rc = check_aligned(q, 16, "the guide, surface and history buffers must be 16-byte aligned")) != RT_OK) return rc;
+  if ((rc = check_aligned(d_displacement, 8, "the displacement table must be 8-byte aligned")) != RT_OK) return rc;
   const size_t px = (size_t)s->host.width * s->host.height;
   if (px == 0) return RT_OK;
-  // (an output over an input would be read by other threads while it is written)
-  const uintptr_t o0 = (uintptr_t)d_out_history, o1 = o0 + px * 16;
-  for (const std::pair<uintptr_t, size_t> in : {std::make_pair((uintptr_t)d_linear, px * 12), std::make_pair((uintptr_t)d_aov, px * 32),
-                                                std::make_pair((uintptr_t)d_surface, px * 16), std::make_pair((uintptr_t)d_prev_history, px * 16),
-                                                std::make_pair((uintptr_t)d_prev_aov, px * 32), std::make_pair((uintptr_t)d_prev_surface, px * 16),
-                                                std::make_pair((uintptr_t)d_displacement, d_displacement ? (size_t)s->host.n_spheres * 24 : (size_t)0)})
-    if (in.first < o1 && o0 < in.first + in.second) return fail(RT_ERR_INVALID, "the output must not overlap the inputs");
+  if (overlaps({d_out_history, px * 16}, {{d_linear, px * 12}, {d_aov, px * 32}, {d_surface, px * 16}, {d_prev_history, px * 16}, {d_prev_aov, px * 32},
+                                          {d_prev_surface, px * 16}, {d_displacement, d_displacement ? (size_t)s->host.n_spheres * 24 : (size_t)0}}))
+    return fail(RT_ERR_INVALID, "the output must not overlap the inputs");
   RT_HIP_TRY(hipSetDevice(s->device));
   const float k[5] = {alpha_min, n_max, tau_n, tau_a, tau_z};
   return reproject_surface_frame(s, d_linear, d_aov, d_surface, d_prev_history, d_prev_aov, d_prev_surface, prev_camera, d_displacement, k, alpha_specular,
@@ -1453,7 +1500,7 @@ extern "C" int rt_hip_temporal_configure(RtHipScene* s, float alpha_min, float n
   const int rc = check_reproject_params(alpha_min, n_max, tau_n, tau_a, tau_z);
   if (rc != RT_OK) return rc;
   const float k[5] = {alpha_min, n_max, tau_n, tau_a, tau_z};
-  std::memcpy(s->tp_k, k, sizeof k);
+  std::memcpy(s->tp.k, k, sizeof k);
   return RT_OK;
 }
 
@@ -1461,9 +1508,7 @@ extern "C" int rt_hip_temporal_reset(RtHipScene* s) {
   if (!s) return fail(RT_ERR_INVALID, "null argument");
   RT_HIP_TRY(hipSetDevice(s->device));
   if (s->n_launches) RT_HIP_TRY(hipStreamSynchronize(s->last_stream));  // (the host form is blocking: nothing of it is in flight; a caller's own launch may be)
-  for (DevBuf* b : {&s->tp_accum, &s->tp_hist[0], &s->tp_hist[1], &s->tp_aov[0], &s->tp_aov[1], &s->tp_surf[0], &s->tp_surf[1], &s->tp_disp}) { DevBuf none; b->swap(none); }
-  s->tp_valid = false;
-  s->tp_cur = 0;
+  s->tp.reset();
   return RT_OK;
 }
 
@@ -1472,21 +1517,21 @@ extern "C" int rt_hip_temporal_surface(RtHipScene* s, int enable, float alpha_sp
   if (!s) return fail(RT_ERR_INVALID, "null argument");
   if (!(alpha_specular >= 0.0f && alpha_specular <= 1.0f)) return fail(RT_ERR_INVALID, "alpha_specular must lie in [0, 1]");
   const bool on = enable != 0;
-  if (on != s->tp_surface) {
+  if (on != s->tp.surface) {
     const int rc = rt_hip_temporal_reset(s);
     if (rc != RT_OK) return rc;
-    s->tp_surface = on;
+    s->tp.surface = on;
   }
-  s->tp_alpha_specular = alpha_specular;
+  s->tp.alpha_specular = alpha_specular;
   return RT_OK;
 }
 
 extern "C" int rt_hip_temporal_history(RtHipScene* s, float* out_history) {
   if (!s || !out_history) return fail(RT_ERR_INVALID, "null argument");
-  if (!s->tp_valid) return fail(RT_ERR_INVALID, "the scene holds no temporal history");
+  if (!s->tp.valid) return fail(RT_ERR_INVALID, "the scene holds no temporal history");
   RT_HIP_TRY(hipSetDevice(s->device));
   const size_t px = (size_t)s->host.width * s->host.height;
-  if (px) RT_HIP_TRY(hipMemcpy(out_history, s->tp_hist[s->tp_cur].p, px * 16, hipMemcpyDeviceToHost));
+  if (px) RT_HIP_TRY(hipMemcpy(out_history, s->tp.hist[s->tp.cur].p, px * 16, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 
@@ -1500,71 +1545,65 @@ extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t fram
   if (rc != RT_OK) return rc;
   const uint32_t spp = s->host.samples_per_pixel;
   if (spp == 0) return fail(RT_ERR_INVALID, "samples_per_pixel must be at least 1");
-  if (spp > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an accumulator holds at most 2^23 - 1 samples per pixel");
+  if ((rc = check_samples(0, spp)) != RT_OK) return rc;
   const uint32_t F = rtc::ACCUM_MAX_SAMPLES / spp, begin = (frame_index % F) * spp;  // (frames F apart share a sample range)
-  auto t0 = std::chrono::steady_clock::now();
-  RT_HIP_TRY(hipSetDevice(s->device));
+  HostForm f{s};
+  if ((rc = f.begin()) != RT_OK) return rc;
   const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 3;
   bool grew = false, any_grew = false;
-  if ((rc = s->tp_accum.ensure(px * 24)) != RT_OK || (rc = s->dn_lin.ensure(px * 12)) != RT_OK || (rc = s->frame.ensure(bytes)) != RT_OK) return rc;
+  if ((rc = s->tp.accum.ensure(px * 24)) != RT_OK || (rc = s->prog.dn_lin.ensure(px * 12)) != RT_OK || (rc = s->frame.ensure(bytes)) != RT_OK) return rc;
   for (int i = 0; i < 2; ++i) {
-    if ((rc = s->tp_hist[i].ensure(px * 16, &grew)) != RT_OK) return rc;
+    if ((rc = s->tp.hist[i].ensure(px * 16, &grew)) != RT_OK) return rc;
     any_grew = any_grew || grew;
-    if ((rc = s->tp_aov[i].ensure(px * 32, &grew)) != RT_OK) return rc;
+    if ((rc = s->tp.aov[i].ensure(px * 32, &grew)) != RT_OK) return rc;
     any_grew = any_grew || grew;
   }
   const uint32_t n_sph = s->host.n_spheres;
-  if (s->tp_surface) {
+  if (s->tp.surface) {
     for (int i = 0; i < 2; ++i) {
-      if ((rc = s->tp_surf[i].ensure(px * 16, &grew)) != RT_OK) return rc;
+      if ((rc = s->tp.surf[i].ensure(px * 16, &grew)) != RT_OK) return rc;
       any_grew = any_grew || grew;
     }
-    if ((rc = s->tp_disp.ensure(n_sph ? (size_t)n_sph * 24 : 16)) != RT_OK) return rc;
+    if ((rc = s->tp.disp.ensure(n_sph ? (size_t)n_sph * 24 : 16)) != RT_OK) return rc;
   }
-  if (any_grew) s->tp_valid = false;
-  const int prev = s->tp_cur, cur = prev ^ 1;
+  if (any_grew) s->tp.valid = false;
+  const int prev = s->tp.cur, cur = prev ^ 1;
   double prev_cam[12];
-  if (s->tp_valid) std::memcpy(prev_cam, s->tp_cam, sizeof prev_cam);
+  if (s->tp.valid) std::memcpy(prev_cam, s->tp.cam, sizeof prev_cam);
   else {  // no previous frame: a history of n = 0 everywhere, which no tap accepts
     scene_camera(s, prev_cam);
     if (px) {
-      RT_HIP_TRY(hipMemsetAsync(s->tp_hist[prev].p, 0, px * 16, nullptr));
-      RT_HIP_TRY(hipMemsetAsync(s->tp_aov[prev].p, 0, px * 32, nullptr));
-      if (s->tp_surface) RT_HIP_TRY(hipMemsetAsync(s->tp_surf[prev].p, 0, px * 16, nullptr));
+      RT_HIP_TRY(hipMemsetAsync(s->tp.hist[prev].p, 0, px * 16, nullptr));
+      RT_HIP_TRY(hipMemsetAsync(s->tp.aov[prev].p, 0, px * 32, nullptr));
+      if (s->tp.surface) RT_HIP_TRY(hipMemsetAsync(s->tp.surf[prev].p, 0, px * 16, nullptr));
     }
   }
-  if (s->tp_surface && n_sph) {  // each sphere's centre now minus its centre in the tables the previous temporal frame rendered with
+  if (s->tp.surface && n_sph) {  // each sphere's centre now minus its centre in the tables the previous temporal frame rendered with
     const std::vector<double>& now = s->res->mid;
-    const bool have = s->tp_valid && s->tp_mid.size() == now.size();
-    s->tp_disp_host.resize(now.size());
-    for (size_t i = 0; i < now.size(); ++i) s->tp_disp_host[i] = have ? now[i] - s->tp_mid[i] : 0.0;
-    RT_HIP_TRY(hipMemcpy(s->tp_disp.p, s->tp_disp_host.data(), (size_t)n_sph * 24, hipMemcpyHostToDevice));
+    const bool have = s->tp.valid && s->tp.mid.size() == now.size();
+    s->tp.disp_host.resize(now.size());
+    for (size_t i = 0; i < now.size(); ++i) s->tp.disp_host[i] = have ? now[i] - s->tp.mid[i] : 0.0;
+    RT_HIP_TRY(hipMemcpy(s->tp.disp.p, s->tp.disp_host.data(), (size_t)n_sph * 24, hipMemcpyHostToDevice));
   }
-  if (px) RT_HIP_TRY(hipMemsetAsync(s->tp_accum.p, 0, px * 24, nullptr));
-  rc = rt_hip_accumulate(s, nullptr, begin, spp, s->tp_accum.p, nullptr);
-  if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->tp_accum.p, spp, nullptr, s->dn_lin.p, nullptr);
-  if (rc == RT_OK) rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(spp), s->tp_aov[cur].p, nullptr);
-  if (s->tp_surface) {
-    if (rc == RT_OK) rc = rt_hip_render_surface(s, nullptr, s->tp_surf[cur].p, nullptr);
+  if (px) RT_HIP_TRY(hipMemsetAsync(s->tp.accum.p, 0, px * 24, nullptr));
+  rc = rt_hip_accumulate(s, nullptr, begin, spp, s->tp.accum.p, nullptr);
+  if (rc == RT_OK) rc = rt_hip_resolve(s, nullptr, s->tp.accum.p, spp, nullptr, s->prog.dn_lin.p, nullptr);
+  if (rc == RT_OK) rc = rt_hip_render_aovs(s, nullptr, aov_default_samples(spp), s->tp.aov[cur].p, nullptr);
+  if (s->tp.surface) {
+    if (rc == RT_OK) rc = rt_hip_render_surface(s, nullptr, s->tp.surf[cur].p, nullptr);
     if (rc == RT_OK && px)
-      rc = reproject_surface_frame(s, s->dn_lin.p, s->tp_aov[cur].p, s->tp_surf[cur].p, s->tp_hist[prev].p, s->tp_aov[prev].p, s->tp_surf[prev].p, prev_cam,
-                                   n_sph ? s->tp_disp.get<const double>() : nullptr, s->tp_k, s->tp_alpha_specular, s->tp_hist[cur].p, nullptr);
+      rc = reproject_surface_frame(s, s->prog.dn_lin.p, s->tp.aov[cur].p, s->tp.surf[cur].p, s->tp.hist[prev].p, s->tp.aov[prev].p, s->tp.surf[prev].p, prev_cam,
+                                   n_sph ? s->tp.disp.get<const double>() : nullptr, s->tp.k, s->tp.alpha_specular, s->tp.hist[cur].p, nullptr);
   } else
-  if (rc == RT_OK && px) rc = reproject_frame(s, s->dn_lin.p, s->tp_aov[cur].p, s->tp_hist[prev].p, s->tp_aov[prev].p, prev_cam, s->tp_k, s->tp_hist[cur].p, nullptr);
+  if (rc == RT_OK && px) rc = reproject_frame(s, s->prog.dn_lin.p, s->tp.aov[cur].p, s->tp.hist[prev].p, s->tp.aov[prev].p, prev_cam, s->tp.k, s->tp.hist[cur].p, nullptr);
   const float sigma[4] = {RT_DENOISE_SIGMA_COLOR, RT_DENOISE_SIGMA_NORMAL, RT_DENOISE_SIGMA_ALBEDO, RT_DENOISE_SIGMA_INV_DEPTH};
-  if (rc == RT_OK) rc = denoise_frame(s, s->tp_hist[cur].p, s->tp_aov[cur].p, iterations, sigma, nullptr, s->frame.p, nullptr, true);
-  RtStats st;
-  if (rc == RT_OK) rc = rt_hip_wait(s, &st);
-  if (rc != RT_OK) { s->tp_valid = false; return rc; }  // (a frame that did not complete leaves the history unknown: start over)
-  RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, bytes, hipMemcpyDeviceToHost));
-  s->tp_cur = cur;
-  s->tp_valid = true;
-  scene_camera(s, s->tp_cam);
-  if (s->tp_surface) s->tp_mid = s->res->mid;
-  if (stats) {
-    *stats = st;
-    stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  }
+  if (rc == RT_OK) rc = denoise_frame(s, s->tp.hist[cur].p, s->tp.aov[cur].p, iterations, sigma, nullptr, s->frame.p, nullptr, true);
+  if ((rc = f.wait(rc)) != RT_OK) { s->tp.valid = false; return rc; }  // (a frame that did not complete leaves the history unknown: start over)
+  if ((rc = f.deliver(out_rgb8, stats)) != RT_OK) return rc;
+  s->tp.cur = cur;
+  s->tp.valid = true;
+  scene_camera(s, s->tp.cam);
+  if (s->tp.surface) s->tp.mid = s->res->mid;
   return RT_OK;
 }
 
@@ -1578,28 +1617,28 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
   if (!(threshold >= 0.0) || std::isinf(threshold)) return fail(RT_ERR_INVALID, "the threshold must be finite and at least 0");
   if (min_spp == 0) return fail(RT_ERR_INVALID, "min_spp must be at least 1");
   const uint32_t N = s->host.samples_per_pixel;
-  if (N > rtc::ACCUM_MAX_SAMPLES) return fail(RT_ERR_UNSUPPORTED, "an adaptive frame holds at most 2^23 - 1 samples per pixel");
-  auto t0 = std::chrono::steady_clock::now();
-  RT_HIP_TRY(hipSetDevice(s->device));
-  TileGeom tg;
-  int rc = tile_geometry(s, s->host.height, &tg);
+  if (const int refused = check_samples(0, N, "an adaptive frame holds ")) return refused;
+  HostForm f{s};  // (its clock and the device: the frame's stats are summed over the rounds below)
+  int rc = f.begin();
   if (rc != RT_OK) return rc;
+  TileGeom tg;
+  if ((rc = tile_geometry(s, s->host.height, &tg)) != RT_OK) return rc;
   const uint32_t nt = tg.tiles_x * tg.tiles_y, M = min_spp < N ? min_spp : N;
-  s->ad_rounds.clear();
+  s->ad.reset();
   if (M < 2) {  // (no estimate can be made: every tile at N)
     RtStats st;
     if ((rc = rt_hip_render_to_host(s, out_rgb8, &st)) != RT_OK) return rc;
-    s->ad_rounds.push_back({nt, N, st.kernel_ms});
+    s->ad.rounds.push_back({nt, N, st.kernel_ms});
     if (out_tile_spp) std::fill(out_tile_spp, out_tile_spp + nt, N);
-    if (stats) { *stats = st; stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    if (stats) { *stats = st; stats->frame_ms = f.ms(); }
     return RT_OK;
   }
   const size_t px = (size_t)s->host.width * s->host.height, bytes = px * 24;
-  if ((rc = s->ad_now.ensure(bytes)) != RT_OK || (rc = s->ad_prev.ensure(bytes)) != RT_OK || (rc = s->ad_list.ensure((size_t)nt * 4)) != RT_OK ||
-      (rc = s->ad_err.ensure((size_t)nt * 8)) != RT_OK || (rc = s->ad_spp.ensure((size_t)nt * 4)) != RT_OK || (rc = s->frame.ensure(px * 3)) != RT_OK)
+  if ((rc = s->ad.now.ensure(bytes)) != RT_OK || (rc = s->ad.prev.ensure(bytes)) != RT_OK || (rc = s->ad.list.ensure((size_t)nt * 4)) != RT_OK ||
+      (rc = s->ad.err.ensure((size_t)nt * 8)) != RT_OK || (rc = s->ad.spp.ensure((size_t)nt * 4)) != RT_OK || (rc = s->frame.ensure(px * 3)) != RT_OK)
     return rc;
-  unsigned long long* const now = s->ad_now.get<unsigned long long>(), * const prev = s->ad_prev.get<unsigned long long>();
-  uint32_t* const d_list = s->ad_list.get<uint32_t>();
+  unsigned long long* const now = s->ad.now.get<unsigned long long>(), * const prev = s->ad.prev.get<unsigned long long>();
+  uint32_t* const d_list = s->ad.list.get<uint32_t>();
   RtStats total;
   std::memset(&total, 0, sizeof total);
   total.n_gpus_used = 1;
@@ -1628,11 +1667,11 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
   if ((rc = rt_hip_accumulate(s, nullptr, h, M - h, now, nullptr)) != RT_OK || (rc = collect()) != RT_OK) return rc;
   RT_HIP_TRY(hipMemcpy(d_list, list.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
   uint32_t n = M, n_prev = h;
-  s->ad_rounds.push_back({nt, n, round_ms});
+  s->ad.rounds.push_back({nt, n, round_ms});
   for (;;) {
     if (n >= N) break;
-    if ((rc = rt_hip_tile_error(s, nullptr, d_list, (uint32_t)list.size(), now, n, prev, n_prev, s->ad_err.get<double>(), nullptr)) != RT_OK) return rc;
-    RT_HIP_TRY(hipMemcpy(err.data(), s->ad_err.get<double>(), (size_t)nt * 8, hipMemcpyDeviceToHost));
+    if ((rc = rt_hip_tile_error(s, nullptr, d_list, (uint32_t)list.size(), now, n, prev, n_prev, s->ad.err.get<double>(), nullptr)) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(err.data(), s->ad.err.get<double>(), (size_t)nt * 8, hipMemcpyDeviceToHost));
     size_t k = 0;
     for (uint32_t t : list) if (err[t] >= threshold) list[k++] = t;
     list.resize(k);
@@ -1645,10 +1684,10 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
       return rc;
     n_prev = n; n += add;
     for (uint32_t t : list) n_t[t] = n;
-    s->ad_rounds.push_back({(uint32_t)list.size(), n, round_ms});
+    s->ad.rounds.push_back({(uint32_t)list.size(), n, round_ms});
   }
-  RT_HIP_TRY(hipMemcpy(s->ad_spp.get<uint32_t>(), n_t.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
-  if ((rc = rt_hip_resolve_tiles(s, nullptr, now, s->ad_spp.get<uint32_t>(), s->frame.p, nullptr, nullptr)) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(s->ad.spp.get<uint32_t>(), n_t.data(), (size_t)nt * 4, hipMemcpyHostToDevice));
+  if ((rc = rt_hip_resolve_tiles(s, nullptr, now, s->ad.spp.get<uint32_t>(), s->frame.p, nullptr, nullptr)) != RT_OK) return rc;
   RT_HIP_TRY(hipMemcpy(out_rgb8, s->frame.p, px * 3, hipMemcpyDeviceToHost));
   if (out_tile_spp) std::copy(n_t.begin(), n_t.end(), out_tile_spp);
   if (stats) {
@@ -1660,7 +1699,7 @@ extern "C" int rt_hip_render_adaptive_to_host(RtHipScene* s, double threshold, u
       samples += w * hh * n_t[t];
     }
     total.samples = samples;
-    total.frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    total.frame_ms = f.ms();
     *stats = total;
   }
   return RT_OK;
@@ -1685,7 +1724,7 @@ int rt_hip_scene_warm(RtHipScene* s, hipStream_t stream) {
   if (rc == RT_OK) rtp::add("rank0.warm_up_kernel_ms_by_events", wst.kernel_ms);
   s->opt.order_mode = saved_order;
   s->n_launches = 0; s->in_flight = false; s->last_stream = nullptr; s->last_waves = 0;
-  s->order_key = RtHipScene::OrderKey(); s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
+  s->order.key = RtHipScene::OrderKey(); s->order.forget();
   for (auto& sl : s->slot) { sl.rows = 0; sl.samples = 0; sl.waves = 0; sl.launched = false; }
   return rc;
 }
@@ -1704,9 +1743,9 @@ int adopt_tables(RtHipScene* s) {
   s->dev.large = r.large.get<const uint32_t>();
   s->dev.large_geom = r.large_geom.get<const rtc::SphereGeom>();
   s->dev.motion = r.n_moving ? r.motion.get<const double>() : nullptr;
-  s->order_ready = false; s->depth_fresh = false; s->order_age = 0;
-  s->reset_accum();
-  s->ad_rounds.clear();
+  s->order.forget();
+  s->prog.reset();
+  s->ad.reset();
   return configure(s);
 }
 

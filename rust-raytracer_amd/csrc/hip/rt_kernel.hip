@@ -120,11 +120,7 @@ typedef const uint32_t __attribute__((address_space(4))) * U32PtrK;
 
 // ---- dynamic LDS layout: [flags][tile slots: headers, then pixel sums][coop exchange][geom][matc][cell entries][cell items]
 // one resident set of workgroups per CU must fit 160 KB of LDS
-#ifdef RT_LDS_TABLES_MAX
-constexpr uint32_t LDS_TABLES_MAX_BYTES = RT_LDS_TABLES_MAX;  // (occupancy experiments)
-#else
 constexpr uint32_t LDS_TABLES_MAX_BYTES = BLOCK >= 1024 ? 156u * 1024u : (BLOCK >= 512 ? 78u * 1024u : 52u * 1024u);
-#endif
 // Tile slots are shared by the workgroup.  A slot holds one open tile: header + the exact
 // fixed-point sums of its pixels.  It is freed when ALL samples of the tile have been added —
 // counted per tile, whichever waves traced them — so a long path only keeps its own tile's
@@ -204,12 +200,8 @@ __device__ __forceinline__ const KArgs& fresh_args() {
 // direct hand-out (r02_run12), single settle (r03_run14), carried walks (r02_run7), cull on landing (r04_run6, with the patch),
 // light migration (r04_run5, with the patch).
 
-#ifndef RT_DEEP_PATH
-#define RT_DEEP_PATH 2u  // camera paths at least this many segments long mark their tile (SlotHdr::max_depth); 2 / 3 / 4 / 6 / 8 / 16: 13.96 / 13.98 / 13.98 / 14.01 / 14.05 / 14.5 ms (profiles/r02_run10_ab.log)
-#endif
-#ifndef RT_COOP_LAYERS
-#define RT_COOP_LAYERS 4u  // attempts a failing lane gets per helper round, at most (64 / failing lanes, capped)
-#endif
+constexpr uint32_t DEEP_PATH = 2u;  // camera paths at least this many segments long mark their tile (SlotHdr::max_depth); 2 / 3 / 4 / 6 / 8 / 16: 13.96 / 13.98 / 13.98 / 14.01 / 14.05 / 14.5 ms (profiles/r02_run10_ab.log)
+constexpr uint32_t COOP_LAYERS = 4u;  // attempts a failing lane gets per helper round, at most (64 / failing lanes, capped)
 // Lanes whose hit is Glass need no point but one Philox call of their own (slot 0, the reflectance
 // draw of materials.rs:189): they make it in round 0, in the instruction stream the others use for
 // attempt 0, and get its first two words back in `glass_u`.
@@ -243,12 +235,8 @@ __device__ __forceinline__ V3 coop_random_in_unit_sphere(bool need, bool glass, 
     // Everything that depends on nf alone is wave-uniform and stays on the scalar unit: the compiler turned `64 / nf` and
     // `ceil(65536 / nf)` into ~20 VECTOR instructions of float-reciprocal division per helper round (there is no scalar
     // integer division), and the search for a failing lane's first accepted layer into ~20 more.
-#if RT_COOP_LAYERS == 4
-    const uint32_t layers = nf <= 16u ? 4u : (nf <= 21u ? 3u : (nf <= 32u ? 2u : 1u));  // min(4, 64 / nf)
-#else
-    uint32_t layers = 64u / nf;
-    if (layers > RT_COOP_LAYERS) layers = RT_COOP_LAYERS;
-#endif
+    static_assert(COOP_LAYERS == 4u, "the thresholds below and the pattern of helper bits are written out for four layers");
+    const uint32_t layers = nf <= 16u ? 4u : (nf <= 21u ? 3u : (nf <= 32u ? 2u : 1u));  // min(COOP_LAYERS, 64 / nf)
     const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(F >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)F, 0u));
     if (pending) xch[r] = make_uint4(ra.pixel, ra.sample, node, 0u);
     const uint32_t m = kCeil65536Over[nf];  // j = lane / nf for lane < 64 by multiplication (scalar load of a 65-entry table)
@@ -275,9 +263,6 @@ __device__ __forceinline__ V3 coop_random_in_unit_sphere(bool need, bool glass, 
       if (layers > 1u) pat |= p1;
       if (layers > 2u) pat |= p1 << (nf & 63u);
       if (layers > 3u) pat |= (p1 << (nf & 63u)) << (nf & 63u);
-#if RT_COOP_LAYERS > 4
-      for (uint32_t l = 4; l < layers; ++l) pat |= 1ull << (l * nf);
-#endif
     }
     const unsigned long long mine = pending ? ((A >> r) & pat) : 0ull;
     const bool found = mine != 0ull;
@@ -739,7 +724,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
       atomicAdd(&acc[0], sample_to_fixed(L.val[0]));
       atomicAdd(&acc[1], sample_to_fixed(L.val[1]));
       atomicAdd(&acc[2], sample_to_fixed(L.val[2]));
-      if (L.k >= RT_DEEP_PATH) atomicMax(&hdr[my_k].max_depth, L.k);  // (rare: tiles that breed deep paths go first next frame)
+      if (L.k >= DEEP_PATH) atomicMax(&hdr[my_k].max_depth, L.k);  // (rare: tiles that breed deep paths go first next frame)
       // NaN samples (frames one pixel wide or high; NaN scene data) added 0 above: flag the pixel instead.  Samples
       // are clamped to [0, 1], so the sum of the channels is NaN iff one of them is.  (A plain divergent branch right
       // here: a wave vote around it, or a cold call, cost 6-12 more spilled registers in the path loop.)
@@ -1018,9 +1003,6 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
     U4 cam_w;
     const V3 rnd = coop_random_in_unit_sphere(hit_kind != 0xFFFFFFFFu && (material_draws_unit_sphere_t<SOLID>(hit_kind) || (MEDIUM && hit_kind == RT_MAT_MEDIUM)), hit_kind == RT_MAT_GLASS, fresh,
                                               L.ra, L.node, lane, coop_xch, glass_u, light_u, cam_w);
-#ifdef RT_PROF_SPLIT  // (experiment builds: the random draws are booked under "item", lane_shade proper stays under "lane_shade")
-    RT_PROF(5);
-#endif
     if constexpr (HL) {
       // The light-sampling draw (raytracer.rs:100) of a hit that is not Glass: its HIGH word is the word attempt 0's Philox call
       // left over (slot 1, .w — rt_core.h, RNG addressing), so `draw > threshold` is decided here without a Philox stream of its
@@ -1033,9 +1015,6 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
         if (hit_kind != 0xFFFFFFFFu && (u_lo > thr) != (u_hi > thr)) light_u = u01_53(light_draw_low_word(L.ra, L.node), cam_w.w);
       }
     }
-#ifdef RT_PROF_SPLIT
-    RT_PROF(0);  // (the light draw alone: booked under "refill")
-#endif
     // (d) shade the hits
     int status = LANE_CONTINUE;
     if (has_ray) {
@@ -1473,7 +1452,7 @@ __global__ void rt_math_probe(const double* x, const double* y, double* out_sqrt
                               double* out_atan2, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  out_sqrt[i] = rt_sqrt(x[i]);  // the kernel's square root (RT_FAST_SQRT builds: the short sequence + its cold path)
+  out_sqrt[i] = rt_sqrt(x[i]);  // the kernel's square root (the short sequence + its cold path)
   out_div[i] = x[i] / y[i];
   out_sqrtf[i] = __builtin_sqrtf((float)x[i]);
   out_atan2[i] = rt_atan2(x[i] - 0.5, y[i] - 0.5);  // the shared routine (csrc/common/rt_atan2.h): must equal its CPU build bit for bit

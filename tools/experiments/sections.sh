@@ -1,6 +1,7 @@
 #!/bin/bash
-# RT_PROFILE section shares of a profile build (tools/ab_bench.py arm `prof`, or `prof_split`: the random draws booked apart from
-# lane_shade) on the headline frame, the cover frame at spp 32 through the unlit and the lit kernel, the lit cover frame and cfg1.
+# RT_PROFILE section shares of a profile build (tools/ab_bench.py arm `prof`) on the headline frame, the cover frame at spp 32 through
+# the unlit and the lit kernel, the lit cover frame and cfg1.  (The `prof_split` arm, which booked the random draws apart from
+# lane_shade, was removed with its compile-time switch: what it measured is profiles/r03_run6_lit_prof_split.log.)
 cd "${GRAFT_REPO_ROOT:-.}"
 LIB=${1:-build/ab/librt_hip_prof.so}
 {
