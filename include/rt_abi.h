@@ -91,7 +91,12 @@ typedef struct RtSphere {
 /* A quad (an extension of the schema; the reference has no such object and its loader rejects the file): the flat
  * parallelogram q + a u + b v, 0 <= a, b <= 1, two-sided.  The material fields mean what they mean in RtSphere; a quad may be
  * Lambertian, Metal, Glass, Checker or Noise (the solid's pattern in the quad's frame: centre = q).  Texture, Light and Medium quads
- * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads never move. */
+ * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads never move.
+ * Triangles: `reserved` carries the SHAPE of the flat primitive, RT_QUAD_SHAPE_PARALLELOGRAM (0, the quad above) or
+ * RT_QUAD_SHAPE_TRIANGLE (1): the points q + a u + b v with 0 <= a, 0 <= b, a + b <= 1, two-sided.  Everything else about the entry —
+ * its place in the order, its id, its materials, the refusals — is a quad's.  A value above 1 is RT_ERR_INVALID (`quad k: bad shape`). */
+#define RT_QUAD_SHAPE_PARALLELOGRAM 0u
+#define RT_QUAD_SHAPE_TRIANGLE 1u
 typedef struct RtQuad {
   double q[3], u[3], v[3];
   double fuzz_or_ior;
@@ -101,9 +106,9 @@ typedef struct RtQuad {
   float albedo[3];
   uint32_t kind;
   uint32_t tex_id;
-  uint32_t reserved;
+  uint32_t reserved;  /* the shape: RT_QUAD_SHAPE_* */
 } RtQuad;
-/* The most quads a scene may hold; more is RT_ERR_UNSUPPORTED.  There is no spatial structure over the quads: EVERY ray segment tests
+/* The most quads (of both shapes together) a scene may hold; more is RT_ERR_UNSUPPORTED.  There is no spatial structure over the quads: EVERY ray segment tests
  * EVERY quad, so the cost of a segment is linear in their number. */
 #define RT_MAX_QUADS 1024u
 
@@ -251,7 +256,15 @@ const double* rt_scene_motion(const RtSceneFile*);
  * place in the quad order, to the six quads csrc/common/rt_quad.h lists, in that order, built with the operations listed there
  * (rt_scene_to_json writes the six quads).  Spheres keep their relative order in RtScene.spheres, quads theirs here.  The quads of
  * the file, *n of them, or NULL (and *n = 0) for a file without one.  Owned by the scene file.  The loader rejects, naming objects[i]
- * by the file's own index: mixed keys, a duplicate key, "center1" on a quad, a degenerate quad, a material a quad cannot have. */
+ * by the file's own index: mixed keys, a duplicate key, "center1" on a quad, a degenerate quad, a material a quad cannot have.
+ * Triangles and meshes (extensions too).  {"q", "u", "v", "shape": "triangle" | "parallelogram", "material"} is the
+ * canonical form of a flat primitive ("shape" absent = parallelogram; rt_scene_to_json writes "shape" for a triangle, so a file
+ * without one serialises as it did).  {"triangle": [a, b, c], "material": M} is Q = a, u = b - a, v = c - a (one subtraction per
+ * component).  {"mesh": {"vertices": [[x, y, z], ...], "faces": [[i, j, k], ...]}, "material": M} expands in place, in face order, to
+ * its triangles (vertices[i], vertices[j], vertices[k]), as a box expands to its quads.  RtQuad.reserved = RT_QUAD_SHAPE_*.  Rejected,
+ * naming objects[i]: an unknown shape, a face without exactly three indices, an index out of range or not an integer, a non-finite
+ * vertex, a degenerate (collinear) triangle (naming its face), mixed or duplicate keys, "center1"; more than RT_MAX_QUADS entries in
+ * total is RT_ERR_UNSUPPORTED. */
 const RtQuad* rt_scene_quads(const RtSceneFile*, uint32_t* n);
 /* Camera::new with a thin lens of focus distance f, r = aperture / 2: out = origin[3], lower_left[3], horizontal[3], vertical[3]
  * (on the focus plane), focal_length, u[3], v[3], r.  aperture 0: the pinhole — the first 13 values are rt_camera_derive's bits,
@@ -343,6 +356,14 @@ int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int 
  *   t = (D - dot(N, o)) / den, accepted only if t > 0.001 and t < closest; P = o + d t, p = P - Q, alpha = dot(w, cross(p, v)),
  *   beta = dot(w, cross(u, p)); accepted iff 0 <= alpha <= 1 and 0 <= beta <= 1.
  *   record: point P, front_face = dot(d, N) < 0, normal = front_face ? N : -N, t.
+ * Triangles: an entry whose `reserved` is RT_QUAD_SHAPE_TRIANGLE.  Every entry has a limit lim, 2.0 for a parallelogram
+ * and 1.0 for a triangle, and a hit is accepted iff 0 <= alpha <= 1, 0 <= beta <= 1 AND alpha + beta <= lim (the sum: one IEEE f64
+ * addition).  With alpha, beta in [0, 1] the rounded sum never exceeds 2, so a parallelogram accepts what it accepted; for a triangle
+ * alpha <= 1 and beta <= 1 follow from the other three comparisons.  A NaN fails every comparison.  Everything else on this page holds
+ * for both shapes: order, ids and ties whatever the shapes; RT_MAX_QUADS counts both.  For Glass, front_face comes from N = cross(u, v)
+ * / |cross(u, v)|: a closed glass mesh needs outward (counter-clockwise) winding.  Not watertight: two triangles that share an edge
+ * each round their own alpha and beta.  A `reserved` above 1 is RT_ERR_INVALID (`quad k: bad shape`).  rt_hip_scene_query "triangles"
+ * = the number of triangle entries; rt_hip_scene_table "quad_lim" = the limits, n_quads x 8 bytes, or 0 bytes without a triangle.
  * Order: quads are tested as if they followed every sphere in object order, quad k before quad k + 1, the comparison strict: on an
  * equal t a sphere beats a quad and an earlier quad a later one (raytracer.rs:52-57 extended).  Ids: quad k is object n_spheres + k —
  * in the surface record of rt_hip_render_surface too (rt_hip_reproject_surface takes such an id as "not displaced").
@@ -390,12 +411,13 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * never go with tables in LDS, media, solid textures or quads, and quads never with tables in LDS or the short colour map (bits 1 and
  * 2); -1 before the scene's first launch), "lens" (1:
  * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
- * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres and quads of kind RT_MAT_CHECKER or RT_MAT_NOISE), "quads" (rt_hip_scene_create_quads).
- * -1 for an unknown key. */
+ * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres and quads of kind RT_MAT_CHECKER or RT_MAT_NOISE), "quads" (rt_hip_scene_create_quads; both shapes),
+ * "triangles" (the entries of shape RT_QUAD_SHAPE_TRIANGLE among them).  -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Diagnostics: a copy of one resident table, as the kernels read it.  name: "grid" (the GridDesc bytes), "cell_word", "cell_items",
  * "large", "geom", "large_geom", "motion" (empty for a static scene), "quads" (RtQuadRec of csrc/common/rt_quad.h, 128 B each: q, u, v, N, w,
- * D; empty for a scene without quads).  A blocking device-to-host copy into out (cap bytes); *needed
+ * D; empty for a scene without quads), "quad_lim" (f64 per entry: 2.0 parallelogram, 1.0 triangle; empty for a scene without a
+ * triangle).  A blocking device-to-host copy into out (cap bytes); *needed
  * receives the table's size, and out may be NULL to ask for it.  An unknown name, or a buffer that is too small: RT_ERR_INVALID. */
 int rt_hip_scene_table(const RtHipScene*, const char* name, void* out, size_t cap, size_t* needed);
 /* Move the spheres of a resident scene.  center = n_spheres x 3 (shutter open), center1 = NULL or n_spheres x 3

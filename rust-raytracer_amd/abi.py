@@ -26,6 +26,7 @@ class RtQuad(C.Structure):
 
 
 RT_MAX_QUADS = 1024
+RT_QUAD_SHAPE_PARALLELOGRAM, RT_QUAD_SHAPE_TRIANGLE = 0, 1   # RtQuad.reserved: the shape of a flat primitive
 
 
 def checker_odd_pack(rgb):

@@ -1,6 +1,6 @@
-// rt_quad.h — the flat parallelogram of DESIGN.md §20 ("Quadrilaterals" of The Next Week), compiled by the host (rt_tables.h, scene.cpp),
-// the device (rt_core.h) and the CPU tests (tests/lanesim/).  Its bits are the contract; tests/quad_mini.py restates it in plain Python
-// floats.
+// rt_quad.h — the flat parallelogram of DESIGN.md §20 ("Quadrilaterals" of The Next Week) and the triangle of §21, compiled by the host
+// (rt_tables.h, scene.cpp), the device (rt_core.h) and the CPU tests (tests/lanesim/, tests/trisim/).  Its bits are the contract;
+// tests/quad_mini.py and tests/tri_mini.py restate it in plain Python floats.
 //
 // A quad is Q, u, v (f64 x 3 each): the points Q + a u + b v with 0 <= a, b <= 1, two-sided.  Every operation below is ONE IEEE f64
 // operation in the order written, no contraction (every build has -ffp-contract=off):
@@ -16,6 +16,16 @@
 //     P = o + d t per component (ray.rs:18-20)    p = P - Q
 //     alpha = dot(w, cross(p, v))    beta = dot(w, cross(u, p))     accepted iff 0 <= alpha, alpha <= 1, 0 <= beta, beta <= 1
 // The record of an accepted hit: point P, front_face = dot(d, N) < 0, normal = front_face ? N : -N, and t.
+//
+// Triangles.  A flat primitive is Q, u, v plus a SHAPE: parallelogram (the quad above) or triangle, the points
+// Q + a u + b v with 0 <= a, 0 <= b, a + b <= 1, two-sided.  rt_quad_prepare, every step of the test up to and including alpha and
+// beta, the record and the 128-byte RtQuadRec are the quad's.  Each primitive has a limit `lim`: 2.0 for a parallelogram, 1.0 for a
+// triangle, and a hit is accepted (rt_flat_hit) iff
+//     0 <= alpha, alpha <= 1, 0 <= beta, beta <= 1 and alpha + beta <= lim          (the sum: ONE IEEE f64 addition, no contraction)
+// With alpha, beta in [0, 1] the rounded sum never exceeds 2, so lim = 2 accepts exactly what rt_quad_hit accepts; for a triangle
+// alpha <= 1 and beta <= 1 follow from the other three comparisons: one rule serves both shapes.  A NaN fails every comparison.
+// front_face comes from N = cross(u, v) / |cross(u, v)|: a closed Glass mesh needs outward (counter-clockwise) winding.  NOT
+// watertight: two triangles that share an edge each round their own alpha and beta; the test IS this arithmetic.
 //
 // An axis-aligned box (rt_box_quads) with corners min = (x0, y0, z0) and max = (x1, y1, z1), dx = x1 - x0, dy = y1 - y0, dz = z1 - z0
 // (one subtraction each; a negation is exact; every other component is +0.0), is these six quads in this order:
@@ -80,6 +90,25 @@ RT_QUAD_FN bool rt_quad_hit(const RtQuadRec& r, const double o[3], const double 
   rt_quad_cross(r.u, p, c);
   const double beta = rt_quad_dot(r.w, c);
   if (!(0.0 <= alpha && alpha <= 1.0 && 0.0 <= beta && beta <= 1.0)) return false;
+  *t_out = t;
+  return true;
+}
+
+// One segment against one flat primitive of limit `lim` (2.0: parallelogram, 1.0: triangle): rt_quad_hit's steps and bits, plus the
+// comparison of alpha + beta with lim.
+RT_QUAD_FN bool rt_flat_hit(const RtQuadRec& r, double lim, const double o[3], const double d[3], double closest, double* t_out, double P[3]) {
+  const double den = rt_quad_dot(r.n, d);
+  if (fabs(den) < 1e-8) return false;
+  const double t = (r.d - rt_quad_dot(r.n, o)) / den;
+  if (!(t > 0.001 && t < closest)) return false;
+  double p[3], c[3];
+  for (int k = 0; k < 3; ++k) { P[k] = o[k] + d[k] * t; p[k] = P[k] - r.q[k]; }
+  rt_quad_cross(p, r.v, c);
+  const double alpha = rt_quad_dot(r.w, c);
+  rt_quad_cross(r.u, p, c);
+  const double beta = rt_quad_dot(r.w, c);
+  if (!(0.0 <= alpha && alpha <= 1.0 && 0.0 <= beta && beta <= 1.0)) return false;
+  if (!(alpha + beta <= lim)) return false;
   *t_out = t;
   return true;
 }

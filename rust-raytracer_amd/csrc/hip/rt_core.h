@@ -156,6 +156,13 @@ RT_HD double grid_walk_eps(uint32_t n_max) {
   return n * (n + 1.0) * u + 6.0 * u * (n + 3.0);
 }
 
+// The flat primitives of a scene as the kernels take them: the records and, in a scene with a triangle, the limits.
+struct QuadView {
+  const RtQuadRec* rec;
+  const double* lim;
+  RT_HD const RtQuadRec& operator[](uint32_t k) const { return rec[k]; }
+};
+
 struct DevScene {
   uint32_t width, height, spp, max_depth;
   uint32_t sky_mode, n_spheres, n_lights;
@@ -202,8 +209,11 @@ struct DevScene {
   const double* medium;
   // quads (rt_hip_scene_create_quads): [n_quads] records of csrc/common/rt_quad.h; null / 0 for a scene without one.  Quad k
   // is object n_spheres + k: `mat` and `matc` hold n_spheres + n_quads records.  Read only by the QUADS instantiations.
-  const RtQuadRec* quads;
-  uint32_t n_quads, quads_pad;
+  // Triangles: `quads` is a view of two tables, the records and — only in a scene that holds a triangle — [n_quads] the
+  // limit of alpha + beta per entry (2.0 parallelogram, 1.0 triangle; null otherwise); n_tris counts the triangles.  Both tables reach
+  // the device by a host copy before any launch and are read through the scalar path: NO kernel may ever write them.
+  QuadView quads;
+  uint32_t n_quads, n_tris;
 };
 
 // ------------------------------------------------------------------ f64 square root
@@ -998,29 +1008,51 @@ RT_HD Surface surface_at(V3 o, V3 d, double t, const SphereGeom& g, double inv_r
 // quad k is object id_base + k.  COLD and by value (see exact_hit_slow, medium_hit): the division and the two cross products stay out of
 // the walk loop's register budget.  The table and the count are the same for every lane; the device form says so (readfirstlane), and
 // the records, indexed by the uniform counter through the constant address space, arrive as scalar-unit loads.
-RT_HD_COLD HitCB quads_hit(V3 o, V3 d, const RtQuadRec* quads, uint32_t n_quads, uint32_t id_base, double closest, int best) {
+// Triangles: `quads` is the view {records, limits}; a null limit table (no triangle in the scene) takes the loop of §20
+// unchanged, otherwise entry k's limit comes the same wave-uniform way and rt_flat_hit applies it.  A sub-range (rt_quad_probe) is a view
+// of its own: rec + first, lim ? lim + first : nullptr.
+RT_HD_COLD HitCB quads_hit(V3 o, V3 d, QuadView quads, uint32_t n_quads, uint32_t id_base, double closest, int best) {
   HitCB r; r.closest = closest; r.best = best;
   const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef const double __attribute__((address_space(4))) * QuadPtrK;
-  const unsigned long long addr = (unsigned long long)(uintptr_t)quads;
+  const unsigned long long addr = (unsigned long long)(uintptr_t)quads.rec;
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)addr), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(addr >> 32));
   const QuadPtrK base = (QuadPtrK)(uintptr_t)(((unsigned long long)hi << 32) | lo);
   const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_quads);
+  const unsigned long long laddr = (unsigned long long)(uintptr_t)quads.lim;
+  const uint32_t llo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)laddr), lhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(laddr >> 32));
+  const QuadPtrK lim = (QuadPtrK)(uintptr_t)(((unsigned long long)lhi << 32) | llo);
+  const bool tris = (((unsigned long long)lhi << 32) | llo) != 0ull;
 #else
-  const double* base = reinterpret_cast<const double*>(quads);
+  const double* base = reinterpret_cast<const double*>(quads.rec);
   const uint32_t n = n_quads;
+  const double* lim = quads.lim;
+  const bool tris = lim != nullptr;
 #endif
   static_assert(sizeof(RtQuadRec) == 128, "a quad record is 16 doubles");
-  for (uint32_t k = 0; k < n; ++k) {
-    RtQuadRec q;
+  auto load = [&](uint32_t k, RtQuadRec& q) {
     for (int c = 0; c < 3; ++c) {
       q.q[c] = base[16u * (size_t)k + c]; q.u[c] = base[16u * (size_t)k + 3 + c]; q.v[c] = base[16u * (size_t)k + 6 + c];
       q.n[c] = base[16u * (size_t)k + 9 + c]; q.w[c] = base[16u * (size_t)k + 12 + c];
     }
     q.d = base[16u * (size_t)k + 15];
+  };
+  if (!tris) {  // a scene without a triangle (wave-uniform): the loop of §20 as it was
+    for (uint32_t k = 0; k < n; ++k) {
+      RtQuadRec q;
+      load(k, q);
+      double t, P[3];
+      if (rt_quad_hit(q, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+    }
+    return r;
+  }
+  for (uint32_t k = 0; k < n; ++k) {  // §21: entry k's limit by one more scalar load
+    RtQuadRec q;
+    load(k, q);
+    const double lk = lim[k];
     double t, P[3];
-    if (rt_quad_hit(q, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+    if (rt_flat_hit(q, lk, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
   }
   return r;
 }

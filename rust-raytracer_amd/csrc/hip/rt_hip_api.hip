@@ -151,6 +151,8 @@ struct RtHipScene {
     uint32_t n_solids = 0;   // solid textures: Checker and Noise spheres (and quads); their parameters are in the `mat` records
     DevBuf quads;            // quads: [n_quads] RtQuadRec; their materials are records n_spheres + k of `mat` and `matc`; unallocated without quads
     uint32_t n_quads = 0;
+    DevBuf quad_lim;         // triangles: [n_quads] the limit of alpha + beta per entry; unallocated in a scene without a triangle
+    uint32_t n_tris = 0;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -483,6 +485,8 @@ extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* cen
   r->n_solids = t.n_solids;
   if (n_quads && (rc = upload(r->quads, t.quads)) != RT_OK) return rc;
   r->n_quads = n_quads;
+  if (!t.quad_lim.empty() && (rc = upload(r->quad_lim, t.quad_lim)) != RT_OK) return rc;
+  r->n_tris = t.n_tris;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
@@ -523,8 +527,9 @@ extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* cen
   s->dev.large_geom = r->large_geom.get<const rtc::SphereGeom>();
   s->dev.motion = r->n_moving ? r->motion.get<const double>() : nullptr;
   s->dev.medium = r->n_media ? r->medium.get<const double>() : nullptr;
-  s->dev.quads = r->n_quads ? r->quads.get<const RtQuadRec>() : nullptr;
-  s->dev.n_quads = r->n_quads;
+  s->dev.quads.rec = r->n_quads ? r->quads.get<const RtQuadRec>() : nullptr;
+  s->dev.quads.lim = r->n_tris ? r->quad_lim.get<const double>() : nullptr;
+  s->dev.n_quads = r->n_quads; s->dev.n_tris = r->n_tris;
   s->res = std::move(r);
   auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
@@ -1142,6 +1147,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
+  if (!std::strcmp(key, "triangles")) return (int64_t)s->res->n_tris;      // of "quads", the entries of shape triangle
   if (!std::strcmp(key, "quads")) return (int64_t)s->res->n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
   if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
@@ -1871,6 +1877,7 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "large_geom")) { src = r.large_geom.p; bytes = (size_t)G.n_large * sizeof(rtc::SphereGeom); }
   else if (!std::strcmp(name, "motion")) { src = r.motion.p; bytes = r.n_moving ? (size_t)s->host.n_spheres * 32 : 0; }
   else if (!std::strcmp(name, "quads")) { src = r.quads.p; bytes = (size_t)r.n_quads * sizeof(RtQuadRec); }
+  else if (!std::strcmp(name, "quad_lim")) { src = r.quad_lim.p; bytes = r.n_tris ? (size_t)r.n_quads * sizeof(double) : 0; }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
   if (needed) *needed = bytes;
   if (!out) return RT_OK;

@@ -1508,7 +1508,8 @@ __global__ void rt_quad_probe(const DevScene sc, const double* rays, const doubl
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
-  const HitCB r = quads_hit(o, d, sc.quads + first_quad, n_quads, sc.n_spheres + first_quad, closest[i], -1);
+  const QuadView range{sc.quads.rec + first_quad, sc.quads.lim ? sc.quads.lim + first_quad : nullptr};  // (§21: the limits follow the records)
+  const HitCB r = quads_hit(o, d, range, n_quads, sc.n_spheres + first_quad, closest[i], -1);
   out_best[i] = r.best;
   if (r.best < 0) return;
   const GlobalTables tb{sc.geom, sc.matc};

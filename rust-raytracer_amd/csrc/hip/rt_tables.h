@@ -62,6 +62,10 @@ struct HostTables {
   // records are mat[n_spheres + k] and matc[n_spheres + k] (inv_r 0), behind the spheres'.  EMPTY for a scene without a quad: every
   // table is then what it was.  n_solids counts Checker and Noise quads too.
   std::vector<RtQuadRec> quads;
+  // triangles: [n_quads] the limit of alpha + beta of entry k, 2.0 for a parallelogram and 1.0 for a triangle (RtQuad.reserved =
+  // RT_QUAD_SHAPE_*).  EMPTY unless some entry is a triangle: a scene of parallelograms builds what it built.  n_tris counts the triangles.
+  std::vector<double> quad_lim;
+  uint32_t n_tris = 0;
 };
 
 // The box a sphere's centre can occupy over the shutter, axis k (rt_grid_build.h grid_sphere_box: the static box, or the swept one).
@@ -468,7 +472,7 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
   };
   build_grid(sc, t, grid_params_shipped());
   pack_large();
-  t.quads.clear();
+  t.quads.clear(); t.quad_lim.clear(); t.n_tris = 0;
   if (n_quads) return build_quads(quads, n_quads, t);
   return "";
 }
@@ -481,6 +485,8 @@ inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables
     const int bad = rt_quad_prepare(q.q, q.u, q.v, &t.quads[k]);
     if (bad == 1) return which + ": q, u and v must be finite";
     if (bad) return which + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)";
+    if (q.reserved > RT_QUAD_SHAPE_TRIANGLE) return which + ": bad shape";
+    if (q.reserved == RT_QUAD_SHAPE_TRIANGLE) t.n_tris++;
     if (q.kind > RT_MAT_NOISE) return which + ": bad material kind";
     if (q.kind == RT_MAT_TEXTURE) return which + ": a quad cannot be a Texture (it has no (u, v) map)";
     if (q.kind == RT_MAT_LIGHT) return which + ": a quad cannot be a Light (the light loop aims at sphere centres)";
@@ -514,6 +520,10 @@ inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables
       mc.r0[1] = reflectance_r0(q.fuzz_or_ior);
     }
     t.matc.push_back(mc);
+  }
+  if (t.n_tris) {
+    t.quad_lim.resize(n_quads);
+    for (uint32_t k = 0; k < n_quads; ++k) t.quad_lim[k] = quads[k].reserved == RT_QUAD_SHAPE_TRIANGLE ? 1.0 : 2.0;
   }
   t.simple_colour = false;  // (the QUADS kernels exist with the general colour map only)
   return "";
@@ -604,8 +614,9 @@ inline void bind_host_tables(const HostTables& t, DevScene& d) {
   d.tex4 = t.tex4.data(); d.sky4 = t.sky4.data();
   d.motion = t.motion.empty() ? nullptr : t.motion.data();
   d.medium = t.medium.empty() ? nullptr : t.medium.data();
-  d.quads = t.quads.empty() ? nullptr : t.quads.data();
-  d.n_quads = (uint32_t)t.quads.size();
+  d.quads.rec = t.quads.empty() ? nullptr : t.quads.data();
+  d.quads.lim = t.quad_lim.empty() ? nullptr : t.quad_lim.data();
+  d.n_quads = (uint32_t)t.quads.size(); d.n_tris = t.n_tris;
 }
 
 }  // namespace rtc

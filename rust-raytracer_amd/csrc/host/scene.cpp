@@ -446,21 +446,28 @@ void build_scene(const Value& root, RtSceneFile& sf) {
       bad("unknown variant `" + tag + "`, expected one of `Lambertian`, `Metal`, `Glass`, `Texture`, `Light`, `Medium`, `Checker`, `Noise`");
     }
   };
-  // A quad or a box (extensions — the reference's loader rejects both forms: missing `center`): a map with the keys "q", "u",
-  // "v", "material", or "box" ({"min", "max"}), "material".  Every error names objects[i] by the file's own index.
-  auto parse_quad_or_box = [&](const Value& o) {
+  // A flat primitive (extensions — the reference's loader rejects every form: missing `center`): a map with the keys
+  // "q", "u", "v", "material" and the optional "shape" ("parallelogram" | "triangle"); or "box" ({"min", "max"}), "material"; or "triangle"
+  // ([a, b, c]: Q = a, u = b - a, v = c - a), "material"; or "mesh" ({"vertices", "faces"}: its triangles in face order), "material".
+  // Every error names objects[i] by the file's own index.
+  auto parse_flat = [&](const Value& o) {
     const std::string which = "objects[" + std::to_string(obj_index) + "]";
-    const bool is_box = o.find("box") != nullptr;
+    const bool is_box = o.find("box") != nullptr, is_tri = o.find("triangle") != nullptr, is_mesh = o.find("mesh") != nullptr;
+    const bool is_quad = o.find("q") || o.find("u") || o.find("v");
+    const char* form = is_box ? "box" : (is_mesh ? "mesh" : (is_tri ? "triangle" : "q`, `u`, `v"));
     try {
       for (const char* k : {"center", "radius"})
-        if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a sphere beside `" + (is_box ? "box" : "q`, `u`, `v") + "`");
-      if (is_box)
-        for (const char* k : {"q", "u", "v"})
-          if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a quad beside `box`");
-      if (o.find("center1")) bad("a quad cannot move (center1)");
-      const Value* f[4] = {};
-      double geo[6][9];
-      int n_new = 1;
+        if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a sphere beside `" + form + "`");
+      if (is_box || is_tri || is_mesh)
+        for (const char* k : {"q", "u", "v", "shape"})
+          if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a quad beside `" + form + "`");
+      if (int(is_box) + int(is_tri) + int(is_mesh) > 1) bad("mixed keys: only one of `box`, `triangle`, `mesh`");
+      if (o.find("center1")) bad(is_tri || is_mesh ? std::string("a ") + form + " cannot move (center1)" : std::string("a quad cannot move (center1)"));
+      const Value* f[5] = {};
+      struct Flat { double g[9]; uint32_t shape; };
+      std::vector<Flat> geo;
+      std::vector<std::string> label;   // what a degenerate entry is called
+      const Value* mat_v = nullptr;
       if (is_box) {
         struct_fields(o, "Box", {"box", "material"}, f);
         const Value* b[2];
@@ -470,28 +477,95 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         as_point(*b[1], "box.max", mx);
         for (int k = 0; k < 3; ++k)
           if (!(mn[k] < mx[k])) bad("box: min must be below max on every axis");
-        rt_box_quads(mn, mx, geo);
-        n_new = 6;
+        double six[6][9];
+        rt_box_quads(mn, mx, six);
+        for (int i = 0; i < 6; ++i) { Flat fl; std::memcpy(fl.g, six[i], sizeof fl.g); fl.shape = RT_QUAD_SHAPE_PARALLELOGRAM; geo.push_back(fl); label.push_back("quad"); }
+        mat_v = f[1];
+      } else if (is_tri || is_mesh) {
+        auto from_corners = [&](const double a[3], const double b[3], const double c[3], const std::string& name) {
+          Flat fl;
+          for (int k = 0; k < 3; ++k) { fl.g[k] = a[k]; fl.g[3 + k] = b[k] - a[k]; fl.g[6 + k] = c[k] - a[k]; }
+          fl.shape = RT_QUAD_SHAPE_TRIANGLE;
+          geo.push_back(fl); label.push_back(name);
+        };
+        if (is_tri) {
+          struct_fields(o, "Triangle", {"triangle", "material"}, f);
+          if (f[0]->kind != Value::Array || f[0]->items.size() != 3) bad("triangle: expected three vertices");
+          double c[3][3];
+          for (int i = 0; i < 3; ++i) as_point(*f[0]->items[i], "triangle vertex", c[i]);
+          from_corners(c[0], c[1], c[2], "triangle");
+        } else {
+          struct_fields(o, "Mesh", {"mesh", "material"}, f);
+          const Value* mv[2];
+          if (f[0]->kind != Value::Object) bad("mesh: expected a map with `vertices` and `faces`");
+          struct_fields(*f[0], "mesh", {"vertices", "faces"}, mv);
+          if (mv[0]->kind != Value::Array) bad("mesh.vertices: expected a sequence of points");
+          if (mv[1]->kind != Value::Array) bad("mesh.faces: expected a sequence of index triples");
+          std::vector<double> vert(3 * mv[0]->items.size());
+          for (size_t i = 0; i < mv[0]->items.size(); ++i) {
+            try {
+              as_point(*mv[0]->items[i], "a mesh vertex", &vert[3 * i]);
+            } catch (const SchemaError& e) {
+              bad("mesh vertex " + std::to_string(i) + ": " + e.msg);
+            }
+          }
+          for (size_t fi = 0; fi < mv[1]->items.size(); ++fi) {
+            const Value& face = *mv[1]->items[fi];
+            const std::string fname = "mesh face " + std::to_string(fi);
+            if (face.kind != Value::Array || face.items.size() != 3) bad(fname + ": a face has exactly three indices");
+            size_t ix[3];
+            for (int k = 0; k < 3; ++k) {
+              uint64_t v = 0;
+              try {
+                v = as_u64(*face.items[k], "a face index", ~0ull);
+              } catch (const SchemaError& e) {
+                bad(fname + ": " + e.msg);
+              }
+              if (v >= mv[0]->items.size()) bad(fname + ": index " + face.items[k]->text + " out of range (the mesh has " + std::to_string(mv[0]->items.size()) + " vertices)");
+              ix[k] = size_t(v);
+            }
+            from_corners(&vert[3 * ix[0]], &vert[3 * ix[1]], &vert[3 * ix[2]], fname);
+          }
+        }
+        mat_v = f[1];
       } else {
-        struct_fields(o, "Quad", {"q", "u", "v", "material"}, f);
-        as_point(*f[0], "Quad.q", geo[0]);
-        as_point(*f[1], "Quad.u", geo[0] + 3);
-        as_point(*f[2], "Quad.v", geo[0] + 6);
+        (void)is_quad;
+        struct_fields(o, "Quad", {"q", "u", "v", "material", "shape"}, f, {false, false, false, false, true});
+        Flat fl;
+        as_point(*f[0], "Quad.q", fl.g);
+        as_point(*f[1], "Quad.u", fl.g + 3);
+        as_point(*f[2], "Quad.v", fl.g + 6);
+        fl.shape = RT_QUAD_SHAPE_PARALLELOGRAM;
+        if (f[4]) {
+          if (f[4]->kind != Value::String) bad("shape: expected a string");
+          if (f[4]->text == "triangle") fl.shape = RT_QUAD_SHAPE_TRIANGLE;
+          else if (f[4]->text != "parallelogram") bad("unknown shape `" + f[4]->text + "`, expected one of `parallelogram`, `triangle`");
+        }
+        geo.push_back(fl); label.push_back(fl.shape == RT_QUAD_SHAPE_TRIANGLE ? "triangle" : "quad");
+        mat_v = f[3];
       }
-      const Value& m = *f[is_box ? 1 : 3];
+      const Value& m = *mat_v;
       if (m.kind == Value::Object && m.members.size() == 1)
         for (const char* k : {"Texture", "Light", "Medium"})
           if (m.members[0].first == k) bad(std::string("a quad cannot be a ") + k + " (a quad may be Lambertian, Metal, Glass, Checker or Noise)");
       RtSphere mat{};
       parse_material(m, mat, nullptr);
-      for (int i = 0; i < n_new; ++i) {
+      for (size_t i = 0; i < geo.size(); ++i) {
         RtQuad q{};
-        std::memcpy(q.q, geo[i], 24); std::memcpy(q.u, geo[i] + 3, 24); std::memcpy(q.v, geo[i] + 6, 24);
+        std::memcpy(q.q, geo[i].g, 24); std::memcpy(q.u, geo[i].g + 3, 24); std::memcpy(q.v, geo[i].g + 6, 24);
         RtQuadRec rec;
-        if (rt_quad_prepare(q.q, q.u, q.v, &rec) != 0) bad("degenerate quad: |cross(u, v)|^2 is zero, subnormal or not finite");
+        const int refused = rt_quad_prepare(q.q, q.u, q.v, &rec);
+        if (refused == 1 && geo[i].shape == RT_QUAD_SHAPE_TRIANGLE) bad(label[i] + ": an edge (b - a or c - a) is not finite");
+        if (refused != 0) {
+          if (label[i] == "quad") bad("degenerate quad: |cross(u, v)|^2 is zero, subnormal or not finite");
+          bad(label[i] + ": degenerate (collinear) triangle: |cross(u, v)|^2 is zero, subnormal or not finite");
+        }
         q.fuzz_or_ior = mat.fuzz_or_ior; q.h_offset = mat.h_offset; q.tex_w = mat.tex_w; q.tex_h = mat.tex_h;
         std::memcpy(q.albedo, mat.albedo, 12);
         q.kind = mat.kind; q.tex_id = mat.tex_id;
+        q.reserved = geo[i].shape;
+        if (sf.quads.size() >= RT_MAX_QUADS)
+          throw UnsupportedError{which + ": more than RT_MAX_QUADS (1024) quads and triangles in total: every segment tests every one"};
         sf.quads.push_back(q);
         sf.is_quad.push_back(1);
       }
@@ -500,8 +574,8 @@ void build_scene(const Value& root, RtSceneFile& sf) {
     }
   };
   for (auto& o : objs.items) {
-    if (o->kind == Value::Object && (o->find("q") || o->find("u") || o->find("v") || o->find("box"))) {
-      parse_quad_or_box(*o);
+    if (o->kind == Value::Object && (o->find("q") || o->find("u") || o->find("v") || o->find("box") || o->find("triangle") || o->find("mesh"))) {
+      parse_flat(*o);
       ++obj_index;
       continue;
     }
@@ -619,7 +693,8 @@ std::string scene_json(const RtSceneFile& sf) {
     if (j) o += ",";
     if (sf.is_quad[j]) {
       const RtQuad& q = sf.quads[iq++];
-      o += "{\"q\":" + point(q.q) + ",\"u\":" + point(q.u) + ",\"v\":" + point(q.v) + ",\"material\":{";
+      // (§21: a triangle carries its shape; a parallelogram is written as it always was, so a file without a triangle keeps its bytes)
+      o += "{\"q\":" + point(q.q) + ",\"u\":" + point(q.u) + ",\"v\":" + point(q.v) + (q.reserved == RT_QUAD_SHAPE_TRIANGLE ? ",\"shape\":\"triangle\"" : "") + ",\"material\":{";
     } else {
       o += "{\"center\":" + point(s.center);
       if (sf.has_center1[i]) o += ",\"center1\":" + point(&sf.center1[3 * i]);

@@ -180,7 +180,7 @@ def _centres(n, c, what):
     return (C.c_double * max(1, 3 * n)).from_buffer_copy(a.tobytes() if n else bytes(8))
 
 
-TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads")   # the names rt_hip_scene_table knows
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim")   # the names rt_hip_scene_table knows
 
 
 def _quads_array(quads):
@@ -204,7 +204,7 @@ class HipScene:
 
     def __init__(self, scene_ptr, device=0, library=None, center1=None, quads=None):
         """center1 (motion blur): None, or each sphere's centre at shutter close, n_spheres x 3 (host.Scene.center1()):
-        rt_hip_scene_create_moving.  quads: None, or the scene's quads, abi.RtQuad records (host.Scene.quads()):
+        rt_hip_scene_create_moving.  quads: None, or the scene's flat primitives, abi.RtQuad records whose `reserved` is abi.RT_QUAD_SHAPE_* (host.Scene.quads()):
         rt_hip_scene_create_quads"""
         self._L = library or lib()
         self._h = C.c_void_p()
