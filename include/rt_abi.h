@@ -111,6 +111,10 @@ typedef struct RtQuad {
 /* The most quads (of both shapes together) a scene may hold; more is RT_ERR_UNSUPPORTED.  There is no spatial structure over the quads: EVERY ray segment tests
  * EVERY quad, so the cost of a segment is linear in their number. */
 #define RT_MAX_QUADS 1024u
+/* The most flat primitives of a scene WITH the structure of DESIGN.md §22 (rt_hip_scene_create_flats_bvh; "flat_bvh": true in a scene file):
+ * 2^20.  Every place an object id n_spheres + k is kept holds it: `best` is an int32 and quads never go with wide tables, so an id stays below
+ * 65 535 + 2^20; the surface record's id is a u32 whose only reserved value is 0xFFFFFFFF; the AOVs and the colour map keep no id. */
+#define RT_MAX_FLATS_BVH 1048576u
 
 /* decoded texture pixels, RGB8 (materials.rs:213-219) */
 typedef struct RtTexture {
@@ -266,6 +270,11 @@ const double* rt_scene_motion(const RtSceneFile*);
  * vertex, a degenerate (collinear) triangle (naming its face), mixed or duplicate keys, "center1"; more than RT_MAX_QUADS entries in
  * total is RT_ERR_UNSUPPORTED. */
 const RtQuad* rt_scene_quads(const RtSceneFile*, uint32_t* n);
+/* The structure over the flat primitives (an extension too): a top-level "flat_bvh": true beside "camera" and "objects"
+ * asks for rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh and lifts the loader's cap from RT_MAX_QUADS to RT_MAX_FLATS_BVH
+ * (the entry that crosses it is still named by its objects[i]).  1 for such a file, 0 when the key is false or absent: today's behaviour.
+ * A value that is not a boolean is a load error.  rt_scene_to_json writes the key only when it is true. */
+int rt_scene_flat_bvh(const RtSceneFile*);
 /* Camera::new with a thin lens of focus distance f, r = aperture / 2: out = origin[3], lower_left[3], horizontal[3], vertical[3]
  * (on the focus plane), focal_length, u[3], v[3], r.  aperture 0: the pinhole — the first 13 values are rt_camera_derive's bits,
  * whatever focus_dist.  What rt_hip_set_camera and rt_hip_set_lens take. */
@@ -375,6 +384,20 @@ int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int 
  * have no QUADS kernels).  rt_hip_scene_query "quads" = their number.  rt_hip_scene_update_spheres keeps them.  The QUADS kernels
  * read the scene's tables from L2 and use the general colour map, whatever the scene's size and albedos. */
 int rt_hip_scene_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out);
+/* rt_hip_scene_create_quads with a structure over the flat primitives: a binary BVH, built on the host, that every QUADS
+ * kernel, the AOVs and the surface record walk instead of scanning the list.  THE FRAME IS THE FULL SCAN'S IN EVERY BIT.  Contract: for a
+ * segment (o, d) and the (closest_in, best_in) the spheres left, let A be the entries k that the test above accepts against closest_in;
+ * the scan returns the entry of A with the smallest (t_k, k) in lexicographic order, or its input unchanged when A is empty.  t_k does not
+ * depend on `closest`, so the structure returns exactly this in any visiting order: a sphere still beats a flat primitive on an equal t,
+ * an earlier entry a later one, a NaN fails every comparison.  The boxes are padded so that a node is skipped only when no entry below it
+ * can be accepted; entries and rays outside the preconditions of that padding (extreme skew, needles, coordinates beyond 2^40; a
+ * non-finite ray, |o_k| > 2^40, |d_k| > 2^100) are tested by every ray / take the full scan.
+ * Arguments and refusals are rt_hip_scene_create_quads's, but: the cap is RT_MAX_FLATS_BVH (RT_ERR_UNSUPPORTED beyond it); the count is
+ * checked before any record is read; n_quads = 0 is RT_ERR_INVALID.  Quads with wide tables stay RT_ERR_UNSUPPORTED.  "variant" 1 runs
+ * the full scan over such a scene, whatever its size.  rt_hip_scene_query "flat_bvh" = the node count (0: no structure);
+ * rt_hip_scene_table "flat_bvh" = the nodes (64 B each: f64 lo[3], hi[3]; u32 skip, first, count, pad) in depth-first order and
+ * "flat_bvh_order" = the u32 order table the leaves index (both 0 bytes without the structure).  rt_hip_scene_update_spheres keeps it. */
+int rt_hip_scene_create_flats_bvh(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out);
 void rt_hip_scene_destroy(RtHipScene*);
 /* Launch the megakernel for the given row tiles on `stream` (a hipStream_t, NULL = default).
  *   d_rgb8    device buffer, rt_tiles_local_rows()*width*3 bytes, packed, top row first;
@@ -412,12 +435,14 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * 2); -1 before the scene's first launch), "lens" (1:
  * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
  * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres and quads of kind RT_MAT_CHECKER or RT_MAT_NOISE), "quads" (rt_hip_scene_create_quads; both shapes),
- * "triangles" (the entries of shape RT_QUAD_SHAPE_TRIANGLE among them).  -1 for an unknown key. */
+ * "triangles" (the entries of shape RT_QUAD_SHAPE_TRIANGLE among them), "flat_bvh" (nodes of the structure over the flat primitives,
+ * rt_hip_scene_create_flats_bvh; 0: none).  -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Diagnostics: a copy of one resident table, as the kernels read it.  name: "grid" (the GridDesc bytes), "cell_word", "cell_items",
  * "large", "geom", "large_geom", "motion" (empty for a static scene), "quads" (RtQuadRec of csrc/common/rt_quad.h, 128 B each: q, u, v, N, w,
  * D; empty for a scene without quads), "quad_lim" (f64 per entry: 2.0 parallelogram, 1.0 triangle; empty for a scene without a
- * triangle).  A blocking device-to-host copy into out (cap bytes); *needed
+ * triangle), "flat_bvh" and "flat_bvh_order" (rt_hip_scene_create_flats_bvh: the nodes and the order table; empty without the
+ * structure).  A blocking device-to-host copy into out (cap bytes); *needed
  * receives the table's size, and out may be NULL to ask for it.  An unknown name, or a buffer that is too small: RT_ERR_INVALID. */
 int rt_hip_scene_table(const RtHipScene*, const char* name, void* out, size_t cap, size_t* needed);
 /* Move the spheres of a resident scene.  center = n_spheres x 3 (shutter open), center1 = NULL or n_spheres x 3
@@ -720,6 +745,8 @@ int rt_hip_group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out)
 int rt_hip_group_create_moving(const RtScene* scene, const double* center1, uint32_t n_gpus, RtHipGroup** out);
 /* rt_hip_group_create_moving whose every rank is rt_hip_scene_create_quads(scene, center1, quads, n_quads): quads */
 int rt_hip_group_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, uint32_t n_gpus, RtHipGroup** out);
+/* rt_hip_group_create_quads whose every rank is rt_hip_scene_create_flats_bvh(scene, center1, quads, n_quads), with its refusals */
+int rt_hip_group_create_flats_bvh(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, uint32_t n_gpus, RtHipGroup** out);
 int rt_hip_group_info(const RtHipGroup*, RtGroupInfo* info);
 uint32_t rt_hip_group_ranks(const RtHipGroup*, RtGroupRank* out, uint32_t cap); /* fills min(cap, n_ranks) entries, returns n_ranks */
 const char* rt_hip_group_fallback_reason(const RtHipGroup*);                    /* "" unless RtGroupInfo.transport_fallback */

@@ -27,6 +27,13 @@
 // front_face comes from N = cross(u, v) / |cross(u, v)|: a closed Glass mesh needs outward (counter-clockwise) winding.  NOT
 // watertight: two triangles that share an edge each round their own alpha and beta; the test IS this arithmetic.
 //
+// The list.  For a segment (o, d) and the (closest_in, best_in) the spheres left, let A be the entries k that
+// rt_flat_hit(rec_k, lim_k, o, d, closest_in, ...) accepts (lim_k = 2.0 in a scene without a triangle).  The full scan returns the entry of
+// A with the smallest (t_k, k) in lexicographic order, or its input unchanged when A is empty; t_k does not depend on `closest`, so neither
+// does the result depend on the visiting order.  Any structure over the entries (rt_core.h flats_hit_bvh) returns exactly this: a sphere
+// still beats a flat entry on an equal t, an earlier entry a later one, and a NaN fails every comparison (rt_flat_hit_tie below).
+// PRECONDITION: best_in is what the spheres left — a sphere's id or a miss, never a flat entry's.
+//
 // An axis-aligned box (rt_box_quads) with corners min = (x0, y0, z0) and max = (x1, y1, z1), dx = x1 - x0, dy = y1 - y0, dz = z1 - z0
 // (one subtraction each; a negation is exact; every other component is +0.0), is these six quads in this order:
 //     0 front  (z = z1): Q = (x0, y0, z1)  u = ( dx, 0, 0)  v = (0, dy,   0)
@@ -101,6 +108,28 @@ RT_QUAD_FN bool rt_flat_hit(const RtQuadRec& r, double lim, const double o[3], c
   if (fabs(den) < 1e-8) return false;
   const double t = (r.d - rt_quad_dot(r.n, o)) / den;
   if (!(t > 0.001 && t < closest)) return false;
+  double p[3], c[3];
+  for (int k = 0; k < 3; ++k) { P[k] = o[k] + d[k] * t; p[k] = P[k] - r.q[k]; }
+  rt_quad_cross(p, r.v, c);
+  const double alpha = rt_quad_dot(r.w, c);
+  rt_quad_cross(r.u, p, c);
+  const double beta = rt_quad_dot(r.w, c);
+  if (!(0.0 <= alpha && alpha <= 1.0 && 0.0 <= beta && beta <= 1.0)) return false;
+  if (!(alpha + beta <= lim)) return false;
+  *t_out = t;
+  return true;
+}
+
+// The order-free form of rt_flat_hit: its steps and bits, repeated, with the range test
+//     t > 0.001 and (t < closest or (tie_ok and t == closest)).
+// A traversal that meets the entries in any order sets tie_ok when the hit it holds is a flat entry of a LARGER index than this one: the
+// smaller index then takes an equal t, as it does in the scan.  With tie_ok false this is rt_flat_hit in decision and every output bit.
+RT_QUAD_FN bool rt_flat_hit_tie(const RtQuadRec& r, double lim, const double o[3], const double d[3], double closest, bool tie_ok, double* t_out,
+                                double P[3]) {
+  const double den = rt_quad_dot(r.n, d);
+  if (fabs(den) < 1e-8) return false;
+  const double t = (r.d - rt_quad_dot(r.n, o)) / den;
+  if (!(t > 0.001 && (t < closest || (tie_ok && t == closest)))) return false;
   double p[3], c[3];
   for (int k = 0; k < 3; ++k) { P[k] = o[k] + d[k] * t; p[k] = P[k] - r.q[k]; }
   rt_quad_cross(p, r.v, c);

@@ -157,11 +157,59 @@ RT_HD double grid_walk_eps(uint32_t n_max) {
 }
 
 // The flat primitives of a scene as the kernels take them: the records and, in a scene with a triangle, the limits.
+// The structure over them (rt_hip_scene_create_flats_bvh): a binary BVH in depth-first order, built on the host
+// (rt_tables.h build_flat_bvh).  Node i's box is [lo, hi], already padded per entry; `skip` is the node to go to when node i is rejected
+// (skip > i always: a walk needs one index and no stack); count == 0: an inner node, whose first child is node i + 1; count 1 .. 4: a leaf
+// of the entries order[first .. first + count - 1].  Entries outside the preconditions of the padding sit in leaves with an infinite box at
+// the front of the node order: every ray visits them.
+struct alignas(16) FlatNode {
+  double lo[3], hi[3];
+  uint32_t skip, first, count, pad;
+};
+static_assert(sizeof(FlatNode) == 64, "a BVH node is 64 bytes");
 struct QuadView {
   const RtQuadRec* rec;
   const double* lim;
   RT_HD const RtQuadRec& operator[](uint32_t k) const { return rec[k]; }
 };
+// The structure as the kernels reach it: a header resident IN FRONT OF THE RECORDS — the 128 bytes before DevScene::quads.rec[0], one
+// record's size — in a scene whose DevScene::n_tris carries FLAT_BVH_BIT (n_tris <= 2^20: the bit is free; no kernel reads the count).
+// So DevScene keeps its size and the kernel arguments their offsets — every kernel without the QUADS arm is the code object it was —
+// and flats_hit_bvh takes ONE pointer and scalars: o, d and a 16-byte QuadView fill the 16 argument registers of quads_hit's call
+// exactly, and any aggregate beyond them travels through scratch (measured: DESIGN.md §22).
+constexpr uint32_t FLAT_BVH_BIT = 0x80000000u;
+struct alignas(16) FlatBvhHeader {
+  const FlatNode* nodes;
+  const uint32_t* order;
+  const RtQuadRec* rec;
+  const double* lim;      // null in a scene without a triangle
+  uint32_t n_nodes, n_quads, id_base, pad0;
+  uint64_t pad[10];
+};
+static_assert(sizeof(FlatBvhHeader) == sizeof(RtQuadRec), "the header takes the slot of one record in front of the records");
+// The rays the structure takes (DESIGN.md §22 "Preconditions"): every component finite, |o_k| <= 2^40, |d_k| <= 2^100 (a zero, a
+// subnormal or a tiny d_k is fine: 1 / d_k = +-inf only ever says what is true of a ray that cannot leave its slab).
+// Every other ray (a NaN fails the comparisons) takes the full scan.  FLAT_RAY_SLACK: the ray's side of the padding, s = 2^-30 (|o_x| + |o_y|
+// + |o_z|), by which the slab test grows every box.
+constexpr double FLAT_RAY_O_MAX = 0x1p40;
+constexpr double FLAT_RAY_D_MAX = 0x1p100;
+constexpr double FLAT_RAY_SLACK = 0x1p-30;
+RT_HD bool flat_ray_ok(const double o[3], const double d[3]) {
+  bool ok = true;
+  for (int k = 0; k < 3; ++k) {
+    const double ad = fabs(d[k]);
+    ok = ok && fabs(o[k]) <= FLAT_RAY_O_MAX && ad <= FLAT_RAY_D_MAX;
+  }
+  return ok;
+}
+// (host builds of the tests only: what a walk did, tests/flatbvh/)
+#if defined(RT_FLAT_BVH_COUNT) && !defined(__HIPCC__)
+struct FlatBvhCount { uint64_t rays_bvh, rays_scan, box_tests, entry_tests, nan_axes; };
+inline FlatBvhCount g_flat_bvh_count;
+#define RT_FLAT_COUNT(f) (++g_flat_bvh_count.f)
+#else
+#define RT_FLAT_COUNT(f) ((void)0)
+#endif
 
 struct DevScene {
   uint32_t width, height, spp, max_depth;
@@ -213,6 +261,8 @@ struct DevScene {
   // limit of alpha + beta per entry (2.0 parallelogram, 1.0 triangle; null otherwise); n_tris counts the triangles.  Both tables reach
   // the device by a host copy before any launch and are read through the scalar path: NO kernel may ever write them.
   QuadView quads;
+  // n_tris | FLAT_BVH_BIT: the scene has the structure of DESIGN.md §22, its FlatBvhHeader in front of quads.rec[0] (flats_hit); the
+  // launch copy of "variant" 1 clears the bit.
   uint32_t n_quads, n_tris;
 };
 
@@ -1011,6 +1061,63 @@ RT_HD Surface surface_at(V3 o, V3 d, double t, const SphereGeom& g, double inv_r
 // Triangles: `quads` is the view {records, limits}; a null limit table (no triangle in the scene) takes the loop of §20
 // unchanged, otherwise entry k's limit comes the same wave-uniform way and rt_flat_hit applies it.  A sub-range (rt_quad_probe) is a view
 // of its own: rec + first, lim ? lim + first : nullptr.
+// The structure: the same answer as the scan below — the entry of the smallest (t, index) among those rt_flat_hit accepts
+// against the caller's closest — through the BVH of quads.nodes.  PER LANE: the lanes of a wave hold unrelated paths, so each walks its own
+// nodes with one index (FlatNode::skip: no stack), reading nodes, order, records and limits with ordinary vector loads.  A node is skipped
+// only when the slab test says CERTAINLY outside: every comparison is written so that a NaN (0 * inf of a ray that runs in a box face plane)
+// visits; the boxes carry the host's per-entry pad and the test adds the ray's slack s.  An entry is accepted by rt_flat_hit_tie, tie_ok
+// when the hit held is a flat entry of a larger index — never against a sphere (best < id_base) — so the visiting order cannot show.  The
+// loop is bounded by n_nodes whatever the tables hold.  A ray outside the preconditions (flat_ray_ok) takes the scan, here, per lane.
+// Cold, like quads_hit.  Called from flats_hit, never from quads_hit: the scan's call and body stay what they were.  Its arguments are
+// o, d and scalars: all in registers.
+RT_HD_COLD HitCB flats_hit_bvh(V3 o, V3 d, const FlatBvhHeader* header, double closest, int best) {
+  struct { const FlatNode* nodes; const uint32_t* order; uint32_t n_nodes; } bvh = {header->nodes, header->order, header->n_nodes};
+  const QuadView quads{header->rec, header->lim};
+  const uint32_t n_quads = header->n_quads, id_base = header->id_base;
+  HitCB r; r.closest = closest; r.best = best;
+  const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+  if (!flat_ray_ok(oo, dd)) {
+    RT_FLAT_COUNT(rays_scan);
+    for (uint32_t k = 0; k < n_quads; ++k) {
+      const RtQuadRec q = quads.rec[k];
+      const double lk = quads.lim ? quads.lim[k] : 2.0;
+      double t, P[3];
+      if (rt_flat_hit(q, lk, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+    }
+    return r;
+  }
+  RT_FLAT_COUNT(rays_bvh);
+  const double s = FLAT_RAY_SLACK * ((fabs(oo[0]) + fabs(oo[1])) + fabs(oo[2]));
+  const double inv[3] = {1.0 / dd[0], 1.0 / dd[1], 1.0 / dd[2]};
+  const uint32_t n_nodes = bvh.n_nodes;
+  uint32_t i = 0;
+  for (uint32_t step = 0; step < n_nodes && i < n_nodes; ++step) {
+    const FlatNode nd = bvh.nodes[i];
+    RT_FLAT_COUNT(box_tests);
+    double tn[3], tf[3];
+    for (int k = 0; k < 3; ++k) {
+      const double a = ((nd.lo[k] - s) - oo[k]) * inv[k], b = ((nd.hi[k] + s) - oo[k]) * inv[k];
+      if (a != a || b != b) RT_FLAT_COUNT(nan_axes);  // (0 * inf: the origin lies in a grown face plane and d_k is 0)
+      const bool rev = inv[k] < 0.0;  // (the sign of 1 / d_k: -0.0 gives -inf, and the pair is swapped as for any negative d_k)
+      tn[k] = rev ? b : a; tf[k] = rev ? a : b;
+    }
+    // certainly outside: some slab is left before another is entered, entered beyond the closest hit, or left before t = 0.001
+    const bool outside = tn[0] > tf[1] || tn[0] > tf[2] || tn[1] > tf[0] || tn[1] > tf[2] || tn[2] > tf[0] || tn[2] > tf[1] ||
+                         tn[0] > r.closest || tn[1] > r.closest || tn[2] > r.closest || tf[0] < 0.001 || tf[1] < 0.001 || tf[2] < 0.001;
+    if (outside) { i = nd.skip; continue; }
+    for (uint32_t j = 0; j < nd.count; ++j) {
+      const uint32_t k = bvh.order[nd.first + j];
+      const RtQuadRec q = quads.rec[k];
+      const double lk = quads.lim ? quads.lim[k] : 2.0;
+      const bool tie_ok = r.best >= (int)id_base && (uint32_t)r.best - id_base > k;
+      double t, P[3];
+      RT_FLAT_COUNT(entry_tests);
+      if (rt_flat_hit_tie(q, lk, oo, dd, r.closest, tie_ok, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+    }
+    i = nd.count ? nd.skip : i + 1u;
+  }
+  return r;
+}
 RT_HD_COLD HitCB quads_hit(V3 o, V3 d, QuadView quads, uint32_t n_quads, uint32_t id_base, double closest, int best) {
   HitCB r; r.closest = closest; r.best = best;
   const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
@@ -1055,6 +1162,12 @@ RT_HD_COLD HitCB quads_hit(V3 o, V3 d, QuadView quads, uint32_t n_quads, uint32_
     if (rt_flat_hit(q, lk, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
   }
   return r;
+}
+// What the QUADS arms call: the structure where the scene has one — sc is a kernel argument, so the test of the one bit
+// is wave-uniform — and otherwise quads_hit, whose call and body are what they were.
+RT_HD HitCB flats_hit(const DevScene& sc, V3 o, V3 d, double closest, int best) {
+  if (sc.n_tris & FLAT_BVH_BIT) return flats_hit_bvh(o, d, reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, closest, best);
+  return quads_hit(o, d, sc.quads, sc.n_quads, sc.n_spheres, closest, best);
 }
 // What a hit on object idx records and the SphereGeom scatter sees: a sphere's (surface_at), or in the QUADS arm for idx >= n_spheres
 // quad idx - n_spheres: no division, the stored N; its "centre" — the frame of a solid's pattern — is Q.
@@ -2027,7 +2140,7 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
       const MediumCtx mc{sc.medium, L.ra, L.node};  // (the camera segment: node 0)
       hit_world_grid<true>(sc, tb, L.o, L.d, closest, best, n_exact, n_steps, &mc);
     } else hit_world_grid(sc, tb, L.o, L.d, closest, best, n_exact, n_steps);
-    if constexpr (QUADS) { const HitCB r = quads_hit(L.o, L.d, sc.quads, sc.n_quads, sc.n_spheres, closest, best); closest = r.closest; best = r.best; }
+    if constexpr (QUADS) { const HitCB r = flats_hit(sc, L.o, L.d, closest, best); closest = r.closest; best = r.best; }
     float a[3];
     if (best < 0) {  // raytracer.rs:133-163: the sky the ray sees
       const Rgb c = sky_color(sc, L.d, tex_oob);
@@ -2228,7 +2341,7 @@ RT_HD SurfRec surface_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, uint
     const MediumCtx mc{sc.medium, RngAddr{pixel, 0u, sc.seed_lo, sc.seed_hi}, 0u};
     hit_world_grid<true>(sc, tb, o, d, closest, best, n_exact, n_steps, &mc);
   } else hit_world_grid(sc, tb, o, d, closest, best, n_exact, n_steps);
-  if constexpr (QUADS) { const HitCB q = quads_hit(o, d, sc.quads, sc.n_quads, sc.n_spheres, closest, best); closest = q.closest; best = q.best; }
+  if constexpr (QUADS) { const HitCB q = flats_hit(sc, o, d, closest, best); closest = q.closest; best = q.best; }
   SurfRec r;
   r.id = SURFACE_NONE; r.kind = SURFACE_NONE; r.t = 0.0;
   if (best >= 0) { r.id = (uint32_t)best; r.kind = tb.mat((uint32_t)best).kind; r.t = closest; }

@@ -153,6 +153,10 @@ struct RtHipScene {
     uint32_t n_quads = 0;
     DevBuf quad_lim;         // triangles: [n_quads] the limit of alpha + beta per entry; unallocated in a scene without a triangle
     uint32_t n_tris = 0;
+    // the structure over the flat primitives: [n_flat_nodes] FlatNode and [n_quads] the order table its leaves index;
+    // unallocated unless the scene came from rt_hip_scene_create_flats_bvh.  Written once, by the host copy below: flat primitives never move.
+    DevBuf flat_nodes, flat_order;
+    uint32_t n_flat_nodes = 0;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -435,10 +439,23 @@ extern "C" int rt_hip_scene_create_moving(const RtScene* scene, const double* ce
 
 // quads: the scene above plus n_quads flat parallelograms, tested behind the spheres by the QUADS kernels; without a quad every
 // table and every kernel is what rt_hip_scene_create_moving always built and selected
+namespace { int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out, bool flat_bvh); }
 extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out) {
+  return scene_create_flats(scene, center1, quads, n_quads, device, out, false);
+}
+// the structure: the scene above with a BVH over its flat primitives, which lifts their cap to RT_MAX_FLATS_BVH.  The count
+// is checked before any record is read, and there must be a flat primitive to build over.
+extern "C" int rt_hip_scene_create_flats_bvh(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out) {
+  if (out) *out = nullptr;
+  if (n_quads > RT_MAX_FLATS_BVH) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_FLATS_BVH (2^20) flat primitives");
+  if (n_quads == 0) return fail(RT_ERR_INVALID, "a flat BVH needs at least one flat primitive");
+  return scene_create_flats(scene, center1, quads, n_quads, device, out, true);
+}
+namespace {
+int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out, bool flat_bvh) {
   if (!scene || !out || (n_quads && !quads)) return fail(RT_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (n_quads > RT_MAX_QUADS) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_QUADS (1024) quads: every segment tests every quad");
+  if (!flat_bvh && n_quads > RT_MAX_QUADS) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_QUADS (1024) quads: every segment tests every quad");
   int n = rt_hip_device_count();
   if (n <= 0) return fail(RT_ERR_NO_DEVICE, rt_strerror(RT_ERR_NO_DEVICE));
   if (device < 0 || device >= n) return fail(RT_ERR_INVALID, "device index out of range");
@@ -448,6 +465,10 @@ extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* cen
   std::string why = rtc::build_tables(*scene, t, false, center1, quads, n_quads);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
   if (const int refused = check_wide_tables(t.grid.wide, t.n_media, t.n_solids, n_quads != 0)) return refused;
+  if (flat_bvh) {
+    why = rtc::build_flat_bvh(t);
+    if (!why.empty()) return fail(RT_ERR_INVALID, why);
+  }
   pc.mark("scene.tables_and_grid");
   rtc::build_texels(*scene, t);
   pc.mark("scene.texels_rgbx");
@@ -483,10 +504,21 @@ extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* cen
   if (t.n_media && (rc = upload(r->medium, t.medium)) != RT_OK) return rc;
   r->n_media = t.n_media;
   r->n_solids = t.n_solids;
-  if (n_quads && (rc = upload(r->quads, t.quads)) != RT_OK) return rc;
   r->n_quads = n_quads;
   if (!t.quad_lim.empty() && (rc = upload(r->quad_lim, t.quad_lim)) != RT_OK) return rc;
   r->n_tris = t.n_tris;
+  if (flat_bvh && ((rc = upload(r->flat_nodes, t.flat_nodes)) != RT_OK || (rc = upload(r->flat_order, t.flat_order)) != RT_OK)) return rc;
+  r->n_flat_nodes = (uint32_t)t.flat_nodes.size();
+  if (flat_bvh) {  // (§22: the records behind their header, one buffer; the header holds the device addresses of the four tables)
+    if ((rc = r->quads.ensure(t.flat_blob.size() * sizeof(RtQuadRec))) != RT_OK) return rc;
+    rtc::FlatBvhHeader h;
+    std::memset(&h, 0, sizeof h);
+    h.nodes = r->flat_nodes.get<const rtc::FlatNode>(); h.order = r->flat_order.get<const uint32_t>();
+    h.rec = r->quads.get<const RtQuadRec>() + 1; h.lim = t.n_tris ? r->quad_lim.get<const double>() : nullptr;
+    h.n_nodes = r->n_flat_nodes; h.n_quads = n_quads; h.id_base = scene->n_spheres;
+    std::memcpy(t.flat_blob.data(), &h, sizeof h);
+    RT_HIP_TRY(hipMemcpy(r->quads.p, t.flat_blob.data(), t.flat_blob.size() * sizeof(RtQuadRec), hipMemcpyHostToDevice));
+  } else if (n_quads && (rc = upload(r->quads, t.quads)) != RT_OK) return rc;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
@@ -530,6 +562,7 @@ extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* cen
   s->dev.quads.rec = r->n_quads ? r->quads.get<const RtQuadRec>() : nullptr;
   s->dev.quads.lim = r->n_tris ? r->quad_lim.get<const double>() : nullptr;
   s->dev.n_quads = r->n_quads; s->dev.n_tris = r->n_tris;
+  if (r->n_flat_nodes) { s->dev.quads.rec = r->quads.get<const RtQuadRec>() + 1; s->dev.n_tris |= rtc::FLAT_BVH_BIT; }  // (§22: the header lies in front)
   s->res = std::move(r);
   auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
@@ -549,6 +582,7 @@ extern "C" int rt_hip_scene_create_quads(const RtScene* scene, const double* cen
   *out = s;
   return RT_OK;
 }
+}  // namespace
 
 extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) {
   if (!s || !key) return fail(RT_ERR_INVALID, "null argument");
@@ -799,6 +833,7 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
     ka.sc.grid.n_large = s->host.n_spheres;
     ka.sc.large = s->res->all.get<const uint32_t>();
     ka.sc.large_geom = s->res->geom.get<const rtc::SphereGeom>();
+    ka.sc.n_tris &= ~rtc::FLAT_BVH_BIT;  // (§22: and every flat primitive in file order, the full scan)
   }
   ka.out_rgb8 = (uint8_t*)d_rgb8; ka.out_linear = (float*)d_linear; ka.counters = s->counters.get<unsigned long long>();
   ka.accum = accum; ka.sample_base = sample_base;
@@ -1148,6 +1183,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
   if (!std::strcmp(key, "triangles")) return (int64_t)s->res->n_tris;      // of "quads", the entries of shape triangle
+  if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->n_flat_nodes;  // nodes of the structure over the flat primitives; 0: none
   if (!std::strcmp(key, "quads")) return (int64_t)s->res->n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
   if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
@@ -1876,8 +1912,10 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "geom")) { src = r.geom.p; bytes = (size_t)s->host.n_spheres * sizeof(rtc::SphereGeom); }
   else if (!std::strcmp(name, "large_geom")) { src = r.large_geom.p; bytes = (size_t)G.n_large * sizeof(rtc::SphereGeom); }
   else if (!std::strcmp(name, "motion")) { src = r.motion.p; bytes = r.n_moving ? (size_t)s->host.n_spheres * 32 : 0; }
-  else if (!std::strcmp(name, "quads")) { src = r.quads.p; bytes = (size_t)r.n_quads * sizeof(RtQuadRec); }
+  else if (!std::strcmp(name, "quads")) { src = r.n_flat_nodes ? (const void*)(r.quads.get<const RtQuadRec>() + 1) : r.quads.p; bytes = (size_t)r.n_quads * sizeof(RtQuadRec); }
   else if (!std::strcmp(name, "quad_lim")) { src = r.quad_lim.p; bytes = r.n_tris ? (size_t)r.n_quads * sizeof(double) : 0; }
+  else if (!std::strcmp(name, "flat_bvh")) { src = r.flat_nodes.p; bytes = (size_t)r.n_flat_nodes * sizeof(rtc::FlatNode); }
+  else if (!std::strcmp(name, "flat_bvh_order")) { src = r.flat_order.p; bytes = r.n_flat_nodes ? (size_t)r.n_quads * sizeof(uint32_t) : 0; }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
   if (needed) *needed = bytes;
   if (!out) return RT_OK;

@@ -407,7 +407,7 @@ namespace rtg {
 // setup_costs.hip, profiles/r06_run3_setup_costs.log) and buys a single blocking frame nothing: a one-rank one-shot group
 // renders, assembles and copies on the device's NULL stream, whose queue exists since the device was warmed.
 int group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot, const double* center1 = nullptr, const RtQuad* quads = nullptr,
-                 uint32_t n_quads = 0);
+                 uint32_t n_quads = 0, bool flat_bvh = false);
 }
 extern "C" int rt_hip_group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out) {
   return rtg::group_create(scene, n_gpus, out, false);
@@ -420,7 +420,14 @@ extern "C" int rt_hip_group_create_moving(const RtScene* scene, const double* ce
 extern "C" int rt_hip_group_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, uint32_t n_gpus, RtHipGroup** out) {
   return rtg::group_create(scene, n_gpus, out, false, center1, quads, n_quads);
 }
-int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot, const double* center1, const RtQuad* quads, uint32_t n_quads) {
+// the structure: every rank's scene is rt_hip_scene_create_flats_bvh's, with its refusals
+extern "C" int rt_hip_group_create_flats_bvh(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, uint32_t n_gpus, RtHipGroup** out) {
+  if (out) *out = nullptr;
+  if (n_quads > RT_MAX_FLATS_BVH) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_FLATS_BVH (2^20) flat primitives");
+  if (n_quads == 0) return fail(RT_ERR_INVALID, "a flat BVH needs at least one flat primitive");
+  return rtg::group_create(scene, n_gpus, out, false, center1, quads, n_quads, true);
+}
+int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, bool one_shot, const double* center1, const RtQuad* quads, uint32_t n_quads, bool flat_bvh) {
   if (!scene || !out || (n_quads && !quads)) return fail(RT_ERR_INVALID, "null argument");
   *out = nullptr;
   const int ndev = rt_hip_device_count();
@@ -478,12 +485,13 @@ int rtg::group_create(const RtScene* scene, uint32_t n_gpus, RtHipGroup** out, b
   {
     std::vector<std::thread> th;
     for (uint32_t r = 0; r < G; ++r)
-      th.emplace_back([g, scene, r, center1, quads, n_quads]() {
+      th.emplace_back([g, scene, r, center1, quads, n_quads, flat_bvh]() {
         rtp::tl_record = r == 0;
         rtp::tl_in_group = true;
         rtp::Clock rc_clock;
         rtg::pin_to_rank(g, r);  // (the replica's pinned counter words and staging copies are first touched on the device's node)
-        g->rc[r] = rt_hip_scene_create_quads(scene, center1, quads, n_quads, g->device[r], &g->scene[r]);
+        g->rc[r] = flat_bvh ? rt_hip_scene_create_flats_bvh(scene, center1, quads, n_quads, g->device[r], &g->scene[r])
+                            : rt_hip_scene_create_quads(scene, center1, quads, n_quads, g->device[r], &g->scene[r]);
         if (g->rc[r] != RT_OK) { g->err[r] = rt_hip_last_error(); return; }
         rc_clock.t = std::chrono::steady_clock::now();   // (the scene's own stages are booked by rt_hip_scene_create)
         bool ok = !g->own_streams || (hipStreamCreateWithFlags(&g->stream[r], hipStreamNonBlocking) == hipSuccess &&

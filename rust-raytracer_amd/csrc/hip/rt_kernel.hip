@@ -953,7 +953,7 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
       }
     }
     if constexpr (QUADS) {  // (4) the quads, behind every sphere: quad k is object n_spheres + k
-      if (has_ray) { const HitCB r = quads_hit(L.o, L.d, sc.quads, sc.n_quads, sc.n_spheres, closest, best); closest = r.closest; best = r.best; }
+      if (has_ray) { const HitCB r = flats_hit(sc, L.o, L.d, closest, best); closest = r.closest; best = r.best; }
     }
   };
 
@@ -1509,7 +1509,9 @@ __global__ void rt_quad_probe(const DevScene sc, const double* rays, const doubl
   if (i >= n) return;
   const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
   const QuadView range{sc.quads.rec + first_quad, sc.quads.lim ? sc.quads.lim + first_quad : nullptr};  // (§21: the limits follow the records)
-  const HitCB r = quads_hit(o, d, range, n_quads, sc.n_spheres + first_quad, closest[i], -1);
+  // (§22: the full range of a scene with the structure goes through it, as the kernels' arms do; a proper sub-range is the scan)
+  const HitCB r = first_quad == 0u && n_quads == sc.n_quads ? flats_hit(sc, o, d, closest[i], -1)
+                                                            : quads_hit(o, d, range, n_quads, sc.n_spheres + first_quad, closest[i], -1);
   out_best[i] = r.best;
   if (r.best < 0) return;
   const GlobalTables tb{sc.geom, sc.matc};

@@ -66,6 +66,15 @@ struct HostTables {
   // RT_QUAD_SHAPE_*).  EMPTY unless some entry is a triangle: a scene of parallelograms builds what it built.  n_tris counts the triangles.
   std::vector<double> quad_lim;
   uint32_t n_tris = 0;
+  // the structure over the flat primitives (build_flat_bvh): the nodes in depth-first order and the order table the leaves
+  // index; flat_always: the entries outside the padding's preconditions, which sit in always-visited leaves at the front.  EMPTY unless
+  // build_flat_bvh ran (rt_hip_scene_create_flats_bvh): every other scene builds what it built.
+  std::vector<FlatNode> flat_nodes;
+  std::vector<uint32_t> flat_order;
+  uint32_t flat_always = 0;
+  // ... and, for the CPU builds of the lane code, the records again behind a FlatBvhHeader (rt_core.h): what DevScene::quads.rec points
+  // into when the structure is bound (bind_host_tables fills the header; the device's copy is laid out the same way)
+  std::vector<RtQuadRec> flat_blob;
 };
 
 // The box a sphere's centre can occupy over the shutter, axis k (rt_grid_build.h grid_sphere_box: the static box, or the swept one).
@@ -473,6 +482,7 @@ inline std::string build_tables(const RtScene& sc, HostTables& t, bool want_cull
   build_grid(sc, t, grid_params_shipped());
   pack_large();
   t.quads.clear(); t.quad_lim.clear(); t.n_tris = 0;
+  t.flat_nodes.clear(); t.flat_order.clear(); t.flat_always = 0; t.flat_blob.clear();
   if (n_quads) return build_quads(quads, n_quads, t);
   return "";
 }
@@ -527,6 +537,131 @@ inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables
   }
   t.simple_colour = false;  // (the QUADS kernels exist with the general colour map only)
   return "";
+}
+
+// ------------------------------------------------------------------ the structure over the flat primitives
+// The padded box of entry k, or false when the entry is outside the preconditions under which the pad is derived (§22): a corner
+// coordinate beyond 2^40 in magnitude, edges shorter than 2^-40, K = (|u| + |v|)^2 / |cross(u, v)| above 2^20 (extreme skew, a needle),
+// anything not finite.  The box is that of the corners Q, Q + u, Q + v (and Q + u + v for a parallelogram), grown on every axis by
+//     pad = 2^-20 (|u|_1 + |v|_1) + 2^-30 max |corner coordinate|:
+// orders of magnitude above the rounding terms it has to cover, and never zero — an axis-aligned wall has a box of thickness 2 pad.
+constexpr double FLAT_COORD_MAX = 0x1p40, FLAT_EDGE_MIN = 0x1p-40, FLAT_SKEW_MAX = 0x1p20;
+inline bool flat_entry_box(const RtQuadRec& r, double lim, double lo[3], double hi[3]) {
+  double l1 = 0.0, big = 0.0, edge = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    const double c[4] = {r.q[k], r.q[k] + r.u[k], r.q[k] + r.v[k], (r.q[k] + r.u[k]) + r.v[k]};
+    const int nc = lim < 2.0 ? 3 : 4;
+    lo[k] = hi[k] = c[0];
+    for (int j = 0; j < nc; ++j) {
+      if (!(std::fabs(c[j]) <= FLAT_COORD_MAX)) return false;
+      lo[k] = std::min(lo[k], c[j]); hi[k] = std::max(hi[k], c[j]);
+      big = std::max(big, std::fabs(c[j]));
+    }
+    l1 += std::fabs(r.u[k]) + std::fabs(r.v[k]);
+    edge = std::max(edge, std::max(std::fabs(r.u[k]), std::fabs(r.v[k])));
+  }
+  if (!(edge >= FLAT_EDGE_MIN)) return false;
+  double n[3];
+  rt_quad_cross(r.u, r.v, n);
+  const double len_n = std::sqrt(rt_quad_dot(n, n)), len_uv = std::sqrt(rt_quad_dot(r.u, r.u)) + std::sqrt(rt_quad_dot(r.v, r.v));
+  if (!(len_n > 0.0 && len_uv * len_uv <= FLAT_SKEW_MAX * len_n)) return false;
+  const double pad = 0x1p-20 * l1 + 0x1p-30 * big;
+  for (int k = 0; k < 3; ++k) {
+    lo[k] -= pad; hi[k] += pad;
+    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) return false;
+  }
+  return pad > 0.0;
+}
+
+// "" or what is wrong with the tables of a structure over n entries: skip > index and skip <= n_nodes for every node (a walk ends in at most
+// n_nodes steps), first + count <= n, count <= 4, the order table a permutation.  build_flat_bvh checks what it built with this.
+inline std::string check_flat_bvh(const std::vector<FlatNode>& nodes, const std::vector<uint32_t>& order, uint32_t n) {
+  const size_t nn = nodes.size();
+  if (order.size() != n) return "flat BVH: the order table does not have one entry per primitive";
+  for (size_t i = 0; i < nn; ++i) {
+    const FlatNode& nd = nodes[i];
+    if (!(nd.skip > i && nd.skip <= nn)) return "flat BVH: node " + std::to_string(i) + ": skip must be above the node's index and at most n_nodes";
+    if (nd.count > 4u || (uint64_t)nd.first + nd.count > n) return "flat BVH: node " + std::to_string(i) + ": a leaf outside the order table";
+  }
+  std::vector<uint8_t> seen(n, 0);
+  for (uint32_t k : order) {
+    if (k >= n || seen[k]) return "flat BVH: the order table is not a permutation";
+    seen[k] = 1;
+  }
+  return "";
+}
+
+// Build the structure over t.quads (after build_tables): deterministic, the same input gives the same bytes.  First the always-visited
+// leaves (infinite boxes) of the entries flat_entry_box refuses, in entry order, four to a leaf; then a binary tree over the others: a
+// range of at most 4 entries is a leaf (its entries in index order), a larger one is split at the median of the box centres along the
+// longest axis of their extent, ties by entry index (nth_element under a strict total order: the two halves are determined as sets).
+inline std::string build_flat_bvh(HostTables& t) {
+  const uint32_t n = (uint32_t)t.quads.size();
+  t.flat_nodes.clear(); t.flat_order.clear(); t.flat_always = 0; t.flat_blob.clear();
+  if (!n) return "flat BVH: no flat primitive";
+  struct Box { double lo[3], hi[3], c[3]; };
+  std::vector<Box> box(n);
+  std::vector<uint32_t> always, idx;
+  for (uint32_t k = 0; k < n; ++k) {
+    Box& b = box[k];
+    if (flat_entry_box(t.quads[k], t.quad_lim.empty() ? 2.0 : t.quad_lim[k], b.lo, b.hi)) {
+      for (int a = 0; a < 3; ++a) b.c[a] = 0.5 * b.lo[a] + 0.5 * b.hi[a];
+      idx.push_back(k);
+    } else always.push_back(k);
+  }
+  t.flat_always = (uint32_t)always.size();
+  t.flat_order.reserve(n);
+  for (size_t at = 0; at < always.size(); at += 4) {
+    FlatNode nd;
+    for (int a = 0; a < 3; ++a) { nd.lo[a] = -INFINITY; nd.hi[a] = INFINITY; }
+    nd.first = (uint32_t)t.flat_order.size();
+    nd.count = (uint32_t)std::min<size_t>(4, always.size() - at);
+    nd.skip = (uint32_t)t.flat_nodes.size() + 1u;
+    nd.pad = 0u;
+    for (uint32_t j = 0; j < nd.count; ++j) t.flat_order.push_back(always[at + j]);
+    t.flat_nodes.push_back(nd);
+  }
+  // depth first, the left child right behind its parent; the median split halves a range, so the recursion is log2(n) deep
+  struct Build {
+    HostTables& t; std::vector<Box>& box; std::vector<uint32_t>& idx;
+    void node(size_t a, size_t b) {
+      const size_t me = t.flat_nodes.size();
+      FlatNode nd;
+      for (int k = 0; k < 3; ++k) { nd.lo[k] = INFINITY; nd.hi[k] = -INFINITY; }
+      double clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+      for (size_t i = a; i < b; ++i) {
+        const Box& e = box[idx[i]];
+        for (int k = 0; k < 3; ++k) {
+          nd.lo[k] = std::min(nd.lo[k], e.lo[k]); nd.hi[k] = std::max(nd.hi[k], e.hi[k]);
+          clo[k] = std::min(clo[k], e.c[k]); chi[k] = std::max(chi[k], e.c[k]);
+        }
+      }
+      nd.pad = 0u;
+      if (b - a <= 4) {
+        std::sort(idx.begin() + a, idx.begin() + b);
+        nd.first = (uint32_t)t.flat_order.size(); nd.count = (uint32_t)(b - a); nd.skip = (uint32_t)me + 1u;
+        for (size_t i = a; i < b; ++i) t.flat_order.push_back(idx[i]);
+        t.flat_nodes.push_back(nd);
+        return;
+      }
+      int axis = 0;
+      for (int k = 1; k < 3; ++k) if (chi[k] - clo[k] > chi[axis] - clo[axis]) axis = k;
+      const size_t mid = a + (b - a) / 2;
+      std::nth_element(idx.begin() + a, idx.begin() + mid, idx.begin() + b, [&](uint32_t x, uint32_t y) {
+        const double cx = box[x].c[axis], cy = box[y].c[axis];
+        return cx < cy || (cx == cy && x < y);
+      });
+      nd.first = 0u; nd.count = 0u; nd.skip = 0u;
+      t.flat_nodes.push_back(nd);
+      node(a, mid);
+      node(mid, b);
+      t.flat_nodes[me].skip = (uint32_t)t.flat_nodes.size();
+    }
+  };
+  if (!idx.empty()) { Build bd{t, box, idx}; bd.node(0, idx.size()); }
+  t.flat_blob.assign(n + 1u, RtQuadRec{});
+  std::copy(t.quads.begin(), t.quads.end(), t.flat_blob.begin() + 1);
+  return check_flat_bvh(t.flat_nodes, t.flat_order, n);
 }
 
 // The textures and the sky as the device reads them: R | G << 8 | B << 16 per texel, textures back to back in table order
@@ -617,6 +752,15 @@ inline void bind_host_tables(const HostTables& t, DevScene& d) {
   d.quads.rec = t.quads.empty() ? nullptr : t.quads.data();
   d.quads.lim = t.quad_lim.empty() ? nullptr : t.quad_lim.data();
   d.n_quads = (uint32_t)t.quads.size(); d.n_tris = t.n_tris;
+  if (!t.flat_nodes.empty()) {  // (§22: the header in front of a copy of the records; id_base = the scene's sphere count, set by fill_dev_scene)
+    FlatBvhHeader h;
+    std::memset(&h, 0, sizeof h);
+    h.nodes = t.flat_nodes.data(); h.order = t.flat_order.data(); h.rec = t.flat_blob.data() + 1; h.lim = d.quads.lim;
+    h.n_nodes = (uint32_t)t.flat_nodes.size(); h.n_quads = d.n_quads; h.id_base = d.n_spheres;
+    std::memcpy(const_cast<RtQuadRec*>(t.flat_blob.data()), &h, sizeof h);
+    d.quads.rec = t.flat_blob.data() + 1;
+    d.n_tris |= FLAT_BVH_BIT;
+  }
 }
 
 }  // namespace rtc

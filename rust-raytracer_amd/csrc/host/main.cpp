@@ -55,6 +55,11 @@
 // rt_hip_group_create_quads in every mode above; its one-shot frame goes through a one-frame group too (RtScene carries no quads).  A
 // quad-free file takes the calls it always took.
 //
+// The structure over the flat primitives: a file with "flat_bvh": true (rt_scene_flat_bvh) is created with
+// rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh instead, in every mode above; `--flat-bvh` (with any of the modes, or alone)
+// does the same for any file that holds a flat primitive, for A/B runs; on a file without one it changes nothing (there is nothing to build
+// over), and given twice it is refused with the usage line.  The frame is the same in every bit.
+//
 // Moving spheres from frame to frame (`--frames N --shutter S`, 0 <= S <= 1): a sphere's "center" -> "center1" is its
 // path over the whole animation instead of over one exposure; frame f is exposed from center + dv f / N to center + dv (f + S) / N
 // (anim_path.h), S = 0 giving crisp spheres.  The resident scene's spheres are moved before every frame (rt_hip_group_update_spheres /
@@ -75,16 +80,19 @@
 #include "anim_path.h"
 
 namespace {
+bool g_flat_bvh = false;  // --flat-bvh
 // the resident scene / group of a scene file: with its quads if it has any, else the calls a quad-free file always took
 int create_scene(const RtSceneFile* sf, int device, RtHipScene** out) {
   uint32_t n_quads = 0;
   const RtQuad* quads = rt_scene_quads(sf, &n_quads);
+  if (n_quads && (g_flat_bvh || rt_scene_flat_bvh(sf))) return rt_hip_scene_create_flats_bvh(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, device, out);
   if (n_quads) return rt_hip_scene_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, device, out);
   return rt_hip_scene_create_moving(rt_scene_get(sf), rt_scene_motion(sf), device, out);
 }
 int create_group(const RtSceneFile* sf, RtHipGroup** out) {
   uint32_t n_quads = 0;
   const RtQuad* quads = rt_scene_quads(sf, &n_quads);
+  if (n_quads && (g_flat_bvh || rt_scene_flat_bvh(sf))) return rt_hip_group_create_flats_bvh(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, 0, out);
   if (n_quads) return rt_hip_group_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, 0, out);
   return rt_hip_group_create_moving(rt_scene_get(sf), rt_scene_motion(sf), 0, out);
 }
@@ -524,6 +532,7 @@ int run(int argc, char** argv) {
   for (int i = 3; i < argc && !bad_args; ++i) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+    else if (!std::strcmp(argv[i], "--flat-bvh")) { bad_args = g_flat_bvh; g_flat_bvh = true; }  // (given twice: the usage line)
     else if (!std::strcmp(argv[i], "--temporal-surface")) t_surface = true;
     else if ((!std::strcmp(argv[i], "--temporal-alpha") || !std::strcmp(argv[i], "--temporal-alpha-specular")) && i + 1 < argc) {
       double& dst = std::strcmp(argv[i], "--temporal-alpha") ? t_alpha_specular : t_alpha;
@@ -557,7 +566,7 @@ int run(int argc, char** argv) {
   if (!temporal && (t_surface || t_alpha >= 0.0 || t_alpha_specular >= 0.0)) bad_args = true;  // (the three flags of the denoised animation alone)
   if (t_alpha_specular >= 0.0 && !t_surface) bad_args = true;
   if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || (denoise && !temporal))) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
-      (denoise && (adapt || ((frames != 0 || orbit_given) && !temporal))) || (argc > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
+      (denoise && (adapt || ((frames != 0 || orbit_given) && !temporal))) || (argc - (g_flat_bvh ? 1 : 0) > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
     return usage();  // main.rs:9-12: usage line, normal return
   // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
   // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X

@@ -200,6 +200,8 @@ struct RtSceneFile {
   // interleaving of the two kinds — is_quad[j]: the j-th object written is the next quad, else the next sphere
   std::vector<RtQuad> quads;
   std::vector<uint8_t> is_quad;
+  // the structure over the flat primitives: the file's top-level "flat_bvh": true (rt_scene_flat_bvh; written back only when true)
+  bool flat_bvh = false;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
   // concurrently, beside the parse), everything (read + parse + schema + waiting for the decodes)
   double read_ms = 0, json_ms = 0, jpeg_ms = 0, total_ms = 0;
@@ -304,6 +306,12 @@ void build_scene(const Value& root, RtSceneFile& sf) {
     if (d > 0x7FFFFFFFull) throw UnsupportedError{"max_depth = " + cf[3]->text + " does not fit 31 bits"};
     sc.max_depth = uint32_t(d);
   }
+
+  if (const Value* fb = root.find("flat_bvh")) {  // (ours alone: the reference ignores an unknown key)
+    if (fb->kind != Value::Bool) bad("flat_bvh: expected a boolean");
+    sf.flat_bvh = fb->b;
+  }
+  const size_t max_flats = sf.flat_bvh ? RT_MAX_FLATS_BVH : RT_MAX_QUADS;
 
   std::map<std::string, uint32_t> cache;
   DecodeJobsGuard dj;
@@ -564,8 +572,10 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         std::memcpy(q.albedo, mat.albedo, 12);
         q.kind = mat.kind; q.tex_id = mat.tex_id;
         q.reserved = geo[i].shape;
-        if (sf.quads.size() >= RT_MAX_QUADS)
+        if (sf.quads.size() >= max_flats) {
+          if (sf.flat_bvh) throw UnsupportedError{which + ": more than RT_MAX_FLATS_BVH (2^20) quads and triangles in total"};
           throw UnsupportedError{which + ": more than RT_MAX_QUADS (1024) quads and triangles in total: every segment tests every one"};
+        }
         sf.quads.push_back(q);
         sf.is_quad.push_back(1);
       }
@@ -726,7 +736,7 @@ std::string scene_json(const RtSceneFile& sf) {
     }
     o += "}}";
   }
-  return o + "]}";
+  return o + (sf.flat_bvh ? "],\"flat_bvh\":true}" : "]}");
 }
 
 }  // namespace
@@ -799,6 +809,7 @@ extern "C" const RtQuad* rt_scene_quads(const RtSceneFile* sf, uint32_t* n) {
   if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
   return any ? sf->quads.data() : nullptr;
 }
+extern "C" int rt_scene_flat_bvh(const RtSceneFile* sf) { return sf && sf->flat_bvh ? 1 : 0; }
 extern "C" void rt_free(void* p) { std::free(p); }
 
 extern "C" int rt_scene_to_json(const RtSceneFile* sf, char* buf, size_t cap, size_t* needed) {

@@ -45,6 +45,7 @@ def _bind(path, probes):
     L.rt_hip_scene_create.argtypes = [C.POINTER(abi.RtScene), C.c_int, C.POINTER(C.c_void_p)]
     L.rt_hip_scene_create_moving.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_void_p)]
     L.rt_hip_scene_create_quads.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.POINTER(abi.RtQuad), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.rt_hip_scene_create_flats_bvh.argtypes = L.rt_hip_scene_create_quads.argtypes
     L.rt_hip_scene_destroy.argtypes = [C.c_void_p]
     L.rt_hip_scene_destroy.restype = None
     L.rt_hip_render.argtypes = [C.c_void_p, C.POINTER(abi.RtRowTiles), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -87,6 +88,7 @@ def _bind(path, probes):
     L.rt_hip_group_create.argtypes = [C.POINTER(abi.RtScene), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rt_hip_group_create_moving.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_void_p)]
     L.rt_hip_group_create_quads.argtypes = [C.POINTER(abi.RtScene), C.POINTER(C.c_double), C.POINTER(abi.RtQuad), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.rt_hip_group_create_flats_bvh.argtypes = L.rt_hip_group_create_quads.argtypes
     L.rt_hip_group_destroy.argtypes = [C.c_void_p]
     L.rt_hip_group_destroy.restype = None
     L.rt_hip_group_size.argtypes = [C.c_void_p]
@@ -180,7 +182,7 @@ def _centres(n, c, what):
     return (C.c_double * max(1, 3 * n)).from_buffer_copy(a.tobytes() if n else bytes(8))
 
 
-TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim")   # the names rt_hip_scene_table knows
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order")   # the names rt_hip_scene_table knows
 
 
 def _quads_array(quads):
@@ -202,16 +204,19 @@ class HipScene:
     """Scene tables + textures resident in HBM of one GPU (rt_hip_scene_create).  `library`: probe_lib() for the tests and
     tools that use the debug calls; default: the product library."""
 
-    def __init__(self, scene_ptr, device=0, library=None, center1=None, quads=None):
+    def __init__(self, scene_ptr, device=0, library=None, center1=None, quads=None, flat_bvh=False):
         """center1 (motion blur): None, or each sphere's centre at shutter close, n_spheres x 3 (host.Scene.center1()):
         rt_hip_scene_create_moving.  quads: None, or the scene's flat primitives, abi.RtQuad records whose `reserved` is abi.RT_QUAD_SHAPE_* (host.Scene.quads()):
-        rt_hip_scene_create_quads"""
+        rt_hip_scene_create_quads; flat_bvh: with the structure over them, rt_hip_scene_create_flats_bvh (it needs quads)"""
         self._L = library or lib()
         self._h = C.c_void_p()
+        if flat_bvh and quads is None:
+            raise ValueError("flat_bvh needs quads")
         if quads is not None:
             qa, nq = _quads_array(quads)
             c1 = _center1_array(scene_ptr, center1) if center1 is not None else None
-            _check(self._L.rt_hip_scene_create_quads(scene_ptr, c1, qa, nq, device, C.byref(self._h)), self._L)
+            create = self._L.rt_hip_scene_create_flats_bvh if flat_bvh else self._L.rt_hip_scene_create_quads
+            _check(create(scene_ptr, c1, qa, nq, device, C.byref(self._h)), self._L)
         elif center1 is None:
             _check(self._L.rt_hip_scene_create(scene_ptr, device, C.byref(self._h)), self._L)
         else:
@@ -473,13 +478,16 @@ class HipGroup:
     """The scene resident on n_gpus devices of this node, frames sharded by interleaved scanline tiles
     inside librt_hip.so (rt_hip_group_*): host threads + streams + ONE gather per frame, no torch."""
 
-    def __init__(self, scene_ptr, n_gpus=0, library=None, center1=None, quads=None):
+    def __init__(self, scene_ptr, n_gpus=0, library=None, center1=None, quads=None, flat_bvh=False):
         self._L = library or lib()     # (library: probe_lib() for the tests that inject transport faults)
         self._h = C.c_void_p()
-        if quads is not None:  # (quads, DESIGN.md §20: rt_hip_group_create_quads)
+        if flat_bvh and quads is None:
+            raise ValueError("flat_bvh needs quads")
+        if quads is not None:  # (quads, DESIGN.md §20: rt_hip_group_create_quads; flat_bvh, §22: rt_hip_group_create_flats_bvh)
             qa, nq = _quads_array(quads)
             c1 = _center1_array(scene_ptr, center1) if center1 is not None else None
-            _check(self._L.rt_hip_group_create_quads(scene_ptr, c1, qa, nq, n_gpus, C.byref(self._h)), self._L)
+            create = self._L.rt_hip_group_create_flats_bvh if flat_bvh else self._L.rt_hip_group_create_quads
+            _check(create(scene_ptr, c1, qa, nq, n_gpus, C.byref(self._h)), self._L)
         elif center1 is None:
             _check(self._L.rt_hip_group_create(scene_ptr, n_gpus, C.byref(self._h)), self._L)
         else:  # (motion blur, DESIGN.md §14: rt_hip_group_create_moving)

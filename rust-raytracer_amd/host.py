@@ -46,6 +46,7 @@ def lib():
         L.rt_scene_motion.restype = C.POINTER(C.c_double)
         L.rt_scene_quads.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.rt_scene_quads.restype = C.POINTER(abi.RtQuad)
+        L.rt_scene_flat_bvh.argtypes = [C.c_void_p]
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
         L.rt_jpeg_decode_file.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -116,6 +117,10 @@ class Scene:
         out = (abi.RtQuad * n.value)()
         C.memmove(out, p, C.sizeof(out))
         return out
+
+    def flat_bvh(self):
+        """the structure over the flat primitives: True for a file with "flat_bvh": true (rt_scene_flat_bvh)"""
+        return bool(lib().rt_scene_flat_bvh(self._h))
 
     def lights(self):
         sc = self.c
