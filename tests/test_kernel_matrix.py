@@ -1,9 +1,14 @@
-"""Every instantiation of the megakernel against the CPU oracle.
+"""The 24 base instantiations of the megakernel against the CPU oracle.
 
-rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM> (rt_kernel.hip) runs as one of 24 instantiations, picked per launch by
-select_kernel (rt_hip_api.hip) from the scene (lights; every albedo in [0, 1]), where plan_lds puts the tables (LDS, L2, or
-the wide format) and whether the launch is one-shot or accumulating.  rt_hip_scene_query("last_kernel") reports which one ran:
-ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1.
+rt_megakernel<HL, SIMPLE, LDS, WIDE, ACCUM, LENS, MOTION, MEDIUM, SOLID, QUADS> (rt_kernel.hip) has 352 instantiations
+(kernel_key_valid), one picked per launch from the scene (lights; every albedo in [0, 1]; a lens; moving spheres; media; solid
+textures; flat primitives), where plan_lds puts the tables (LDS, L2, or the wide format) and whether the launch is one-shot or
+accumulating.  rt_hip_scene_query("last_kernel") reports which one ran:
+QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1.
+
+This module pins the 24 with none of the five feature bits (ALL_KEYS) to the C oracle.  The others belong to the sweeps of
+test_lens.py (24), test_motion.py (48), test_medium_layers.py (64), test_solid_gpu.py (128) and test_quad_gpu.py (64), each
+compared with the plain-Python restatement; tests/test_feature_matrix.py accounts for all 352.
 
 One small scene per (HL, SIMPLE, table form) cell, through:
   - the one-shot frame against oracle.render (tests/parity.py's bar) and its path count;
@@ -13,7 +18,7 @@ One small scene per (HL, SIMPLE, table form) cell, through:
   - rt_hip_accumulate_tiles over a strided, reversed tile list with out-of-range ids: the listed tiles are the whole-frame
     words bit for bit, the others keep their guard words;
   - (a lit and a wide cell) the adaptive host form: each tile is the one-shot frame at the tile's count.
-The last test asserts that all 24 instantiations were launched, so a change that re-routes a cell cannot shrink the coverage
+The last test asserts that all 24 base instantiations were launched, so a change that re-routes a cell cannot shrink the coverage
 unnoticed."""
 import json
 import os

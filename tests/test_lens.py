@@ -16,6 +16,7 @@ import pytest
 
 import mini_oracle as M
 from parity import assert_parity, pooled_atol
+from test_kernel_matrix import ALL_KEYS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COVER = os.path.join(ROOT, "scenes", "cfg2_cover_1200x800_spp128.json")
@@ -24,6 +25,7 @@ TEX = os.path.join(ROOT, "scenes", "cfg3_cover_4k_textured.json")
 DOF = os.path.join(ROOT, "scenes", "cover_dof_1200x800_spp128.json")
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRT_WAVES_PER_EU=4"]  # build.py's
 LENS = 32   # rt_hip_scene_query("last_kernel") bit of the LENS instantiations
+SWEEP_KEYS = {LENS | k for k in ALL_KEYS}   # the 24 that test_every_lens_instantiation_is_launched pins
 
 
 def _cfg(path, **cam):
@@ -331,7 +333,7 @@ def test_lens_frames_against_the_restatement(pkg, abi, oracle, host, torch_cuda,
 def test_every_lens_instantiation_is_launched(pkg, abi, oracle, host, torch_cuda, monkeypatch):
     """each (lights, simple colour, table form) cell of tests/test_kernel_matrix.py through a lens, one-shot and accumulating:
     the 24 LENS instantiations, each frame at the parity bar against the restatement, the accumulated frame the one-shot's"""
-    from test_kernel_matrix import ACCUM, ALL_KEYS, CELLS, _cell_id, _cell_json, _key
+    from test_kernel_matrix import ACCUM, CELLS, _cell_id, _cell_json, _key
     torch = torch_cuda
     seen = {}
     for cell in CELLS:
@@ -361,7 +363,7 @@ def test_every_lens_instantiation_is_launched(pkg, abi, oracle, host, torch_cuda
         if not hl:
             assert one[2]["segments"] == m_segs == acc[2], (name, one[2]["segments"], m_segs, acc[2])
         gs.close()
-    assert set(seen) == {LENS | k for k in ALL_KEYS}, sorted(set(seen) ^ {LENS | k for k in ALL_KEYS})
+    assert set(seen) == SWEEP_KEYS, sorted(set(seen) ^ SWEEP_KEYS)
 
 
 @pytest.mark.gpu

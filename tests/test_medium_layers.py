@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from test_kernel_matrix import ALL_KEYS, CELLS, WIDE, _cell_id, _cell_json, _key
 from test_medium_gpu import ACCUM, LENS, MEDIUM, MOTION, _hip_scene, _load, _med, _one_shot, _same, _stream
 
 pytestmark = pytest.mark.gpu
@@ -35,60 +36,77 @@ def _fog_cfg(w, h, spp, lens=False, moving=False):
     return cfg
 
 
+# One scene per cell of the MEDIUM sweep, in the sweep's order: (lights, colour map, LDS / L2 tables) x pinhole / lens x static / moving.
+SWEEP_CELLS = [(hl, simple, form, with_lens, moving) for hl, simple, form in CELLS if form != "wide"     # (media with wide tables are refused,
+               for with_lens in (False, True) for moving in (False, True)]                                #  test_medium_gpu.py)
+SWEEP_KEYS = {MEDIUM | m | l | k for k in ALL_KEYS if not k & WIDE for m in (0, MOTION) for l in (0, LENS)}   # the 64 MEDIUM instantiations
+
+
+def sweep_name(cell):
+    return _cell_id(cell[:3]) + ("/lens" if cell[3] else "") + ("/moving" if cell[4] else "")
+
+
+def sweep_key(cell):
+    """last_kernel of a cell's one-shot frame"""
+    return MEDIUM | (MOTION if cell[4] else 0) | (LENS if cell[3] else 0) | _key(*cell[:3])
+
+
+def sweep_world(host, cell, width, height, pinhole=False):
+    """(host scene, center1, lens, number of media) of one cell at width x height, spp 2: the cell's world of test_kernel_matrix.py with
+    every third sphere a medium; moving: every second sphere moves over the shutter.  pinhole: the same world without the cell's lens."""
+    hl, simple, form, with_lens, moving = cell
+    cfg = json.loads(_cell_json(hl, simple, form, width=width, height=height, spp=2))
+    rng = np.random.default_rng(2 * SWEEP_CELLS.index(cell))
+    n_media = 0
+    for i, o in enumerate(cfg["objects"]):
+        if i == 0 or "Light" in o["material"]:
+            continue
+        if i % 3 == 1:
+            o["material"] = _med([0.8, 0.7, 0.6], round(float(rng.uniform(1.0, 10.0)), 3))
+            n_media += 1
+        if moving and i % 2 == 0:
+            cc, off = o["center"], rng.uniform(-0.3, 0.3, 3)
+            o["center1"] = {"x": cc["x"] + off[0], "y": cc["y"] + off[1], "z": cc["z"] + off[2]}
+    if with_lens and not pinhole:
+        cfg["camera"].update(aperture=0.5, focus_dist=7.0)
+    sc, c1, lens = _load(host, cfg, width, height, 2, cfg["max_depth"])
+    return sc, c1, lens, n_media
+
+
 def test_every_medium_instantiation_is_launched(pkg, abi, host, torch_cuda):
     """(lights, colour map, LDS / L2 tables) x pinhole / lens x static / moving x one-shot / accumulating: the 64 MEDIUM instantiations,
-    each selected by the scene that should reach it; the accumulated frame is the one-shot's, and the grid walk is the full scan's"""
-    from test_kernel_matrix import ALL_KEYS, CELLS, WIDE, _cell_id, _cell_json, _key
+    each selected by the scene that should reach it; the accumulated frame is the one-shot's, and the grid walk is the full scan's.
+    (tests/test_feature_matrix.py compares every one of these cells with the restatement.)"""
     torch = torch_cuda
     seen = {}
-    for cell in CELLS:
-        hl, simple, form = cell
-        if form == "wide":
-            continue     # (media with wide tables are refused, test_medium_gpu.py)
-        for with_lens in (False, True):
-            for moving in (False, True):
-                name = _cell_id(cell) + ("/lens" if with_lens else "") + ("/moving" if moving else "")
-                cfg = json.loads(_cell_json(hl, simple, form, width=9, height=6, spp=2))
-                rng = np.random.default_rng(len(seen))
-                n_media = 0
-                for i, o in enumerate(cfg["objects"]):
-                    if i == 0 or "Light" in o["material"]:
-                        continue
-                    if i % 3 == 1:
-                        o["material"] = _med([0.8, 0.7, 0.6], round(float(rng.uniform(1.0, 10.0)), 3))
-                        n_media += 1
-                    if moving and i % 2 == 0:
-                        cc, off = o["center"], rng.uniform(-0.3, 0.3, 3)
-                        o["center1"] = {"x": cc["x"] + off[0], "y": cc["y"] + off[1], "z": cc["z"] + off[2]}
-                if with_lens:
-                    cfg["camera"].update(aperture=0.5, focus_dist=7.0)
-                sc, c1, lens = _load(host, cfg, 9, 6, 2, cfg["max_depth"])
-                gs = _hip_scene(pkg, sc, c1, lens)
-                assert gs.query("media") == n_media > 0
-                want = MEDIUM | (MOTION if moving else 0) | (LENS if with_lens else 0) | _key(*cell)
-                one = _one_shot(torch, gs)
-                assert gs.query("last_kernel") == want, (name, gs.query("last_kernel"), want)
-                seen.setdefault(want, name)
-                acc = torch.zeros((gs.height, gs.width, 3), dtype=torch.int64, device="cuda:0")
-                segs = 0
-                for b, e in ((1, 2), (0, 1)):
-                    gs.accumulate(acc.data_ptr(), b, e - b, None, _stream(torch))
-                    segs += gs.wait()["segments"]
-                assert gs.query("last_kernel") == want | ACCUM, (name, gs.query("last_kernel"))
-                seen.setdefault(want | ACCUM, name)
-                rgb = torch.zeros((gs.height, gs.width, 3), dtype=torch.uint8, device="cuda:0")
-                lin = torch.zeros((gs.height, gs.width, 3), dtype=torch.float32, device="cuda:0")
-                gs.resolve(acc.data_ptr(), 2, rgb.data_ptr(), lin.data_ptr(), None, _stream(torch))
-                torch.cuda.current_stream().synchronize()
-                _same(one, (rgb.cpu().numpy(), lin.cpu().numpy()), f"{name}: accumulated vs one-shot")
-                assert segs == one[2]["segments"], name
-                gs.set_option("variant", 1)
-                full = _one_shot(torch, gs)
-                _same(one, full, f"{name}: grid walk vs full scan")
-                assert full[2]["segments"] == one[2]["segments"], name
-                gs.close()
-    base = {k for k in ALL_KEYS if not k & WIDE}
-    want = {MEDIUM | m | l | k for k in base for m in (0, MOTION) for l in (0, LENS)}
+    for cell in SWEEP_CELLS:
+        name = sweep_name(cell)
+        sc, c1, lens, n_media = sweep_world(host, cell, 9, 6)
+        gs = _hip_scene(pkg, sc, c1, lens)
+        assert gs.query("media") == n_media > 0
+        want = sweep_key(cell)
+        one = _one_shot(torch, gs)
+        assert gs.query("last_kernel") == want, (name, gs.query("last_kernel"), want)
+        seen.setdefault(want, name)
+        acc = torch.zeros((gs.height, gs.width, 3), dtype=torch.int64, device="cuda:0")
+        segs = 0
+        for b, e in ((1, 2), (0, 1)):
+            gs.accumulate(acc.data_ptr(), b, e - b, None, _stream(torch))
+            segs += gs.wait()["segments"]
+        assert gs.query("last_kernel") == want | ACCUM, (name, gs.query("last_kernel"))
+        seen.setdefault(want | ACCUM, name)
+        rgb = torch.zeros((gs.height, gs.width, 3), dtype=torch.uint8, device="cuda:0")
+        lin = torch.zeros((gs.height, gs.width, 3), dtype=torch.float32, device="cuda:0")
+        gs.resolve(acc.data_ptr(), 2, rgb.data_ptr(), lin.data_ptr(), None, _stream(torch))
+        torch.cuda.current_stream().synchronize()
+        _same(one, (rgb.cpu().numpy(), lin.cpu().numpy()), f"{name}: accumulated vs one-shot")
+        assert segs == one[2]["segments"], name
+        gs.set_option("variant", 1)
+        full = _one_shot(torch, gs)
+        _same(one, full, f"{name}: grid walk vs full scan")
+        assert full[2]["segments"] == one[2]["segments"], name
+        gs.close()
+    want = SWEEP_KEYS
     assert len(want) == 64 and set(seen) == want, sorted(set(seen) ^ want)
 
 

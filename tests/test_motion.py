@@ -20,6 +20,7 @@ import adversarial_rays as AR
 import lane_sim
 import mini_oracle as M
 from parity import assert_parity, pooled_atol
+from test_kernel_matrix import ALL_KEYS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COVER = os.path.join(ROOT, "scenes", "cfg2_cover_1200x800_spp128.json")
@@ -28,6 +29,7 @@ TEST = os.path.join(ROOT, "scenes", "cfg1_test_800x600_spp16.json")
 TEX = os.path.join(ROOT, "scenes", "cfg3_cover_4k_textured.json")
 MOTION = 64    # rt_hip_scene_query("last_kernel") bit of the MOTION instantiations
 LENS = 32
+SWEEP_KEYS = {MOTION | l | k for k in ALL_KEYS for l in (0, LENS)}   # the 48 that test_every_motion_instantiation_is_launched pins
 NODE_TIME = 0xFFFFFFFD
 TAU_LAST = 1.0 - 2.0 ** -24
 
@@ -524,7 +526,7 @@ def test_every_motion_instantiation_is_launched(pkg, abi, oracle, host, torch_cu
     """each (lights, simple colour, table form) cell of tests/test_kernel_matrix.py with moving spheres, pinhole and lens,
     one-shot and accumulating: the 48 MOTION instantiations, each frame at the parity bar against the restatement, the
     accumulated frame the one-shot's"""
-    from test_kernel_matrix import ACCUM, ALL_KEYS, CELLS, _cell_id, _cell_json, _key
+    from test_kernel_matrix import ACCUM, CELLS, _cell_id, _cell_json, _key
     torch = torch_cuda
     seen = {}
     for cell in CELLS:
@@ -562,8 +564,8 @@ def test_every_motion_instantiation_is_launched(pkg, abi, oracle, host, torch_cu
             if not hl:
                 assert one[2]["segments"] == m_segs == acc[2], (name, one[2]["segments"], m_segs, acc[2])
             gs.close()
-    want = {MOTION | k for k in ALL_KEYS} | {MOTION | LENS | k for k in ALL_KEYS}
-    assert set(seen) == want, sorted(set(seen) ^ want)
+    want = SWEEP_KEYS
+    assert len(want) == 48 and set(seen) == want, sorted(set(seen) ^ want)
 
 
 @pytest.mark.gpu

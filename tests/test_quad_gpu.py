@@ -165,7 +165,8 @@ def test_small_frames_against_the_restatement(pkg, abi, oracle, host, torch_cuda
 
 
 def _matrix_cfg(hl, medium, solid, moving):
-    """a 9 x 6 world for one cell of the QUADS matrix: a floor quad (a Checker in the SOLID cells), a small box, five spheres"""
+    """a small world for one cell of the QUADS matrix: a floor quad (a Checker in the SOLID cells), a small box, five spheres.  The lit
+    cells keep the sky: under a black one nine tenths of a 2-sample frame are zero, and zeros agree with any reference."""
     objs = [
         _quad((-5, -0.5, -5), (10, 0, 0), (0, 0, 10), _chk((0.9, 0.9, 0.9), (0.2, 0.2, 0.2), 1.5) if solid else _lam(0.6, 0.6, 0.6)),
         _obj((0, 0.5, 0), 1.0, _lam(0.8, 0.2, 0.2), (0.2, 0.6, 0.1) if moving else None),
@@ -177,52 +178,76 @@ def _matrix_cfg(hl, medium, solid, moving):
         objs.append(_obj((0, 3.5, 1), 0.8, {"Light": {}}))
     if medium:
         objs.append(_obj((-0.8, -0.2, 1.8), 0.6, _med((0.8, 0.7, 0.6), 2.5)))
-    return _cfg(objs, sky=not hl)
+    return _cfg(objs)
+
+
+# One scene per cell of the QUADS sweep, in the sweep's order: lights x pinhole / lens x static / moving x without / with media x
+# without / with solids.
+SWEEP_CELLS = [(hl, with_lens, moving, medium, solid) for hl in (False, True) for with_lens in (False, True) for moving in (False, True)
+               for medium in (False, True) for solid in (False, True)]
+SWEEP_KEYS = {QUADS | s | me | m | l | a | h for s in (0, SOLID) for me in (0, MEDIUM) for m in (0, MOTION) for l in (0, LENS)     # the 64 QUADS
+              for a in (0, ACCUM) for h in (0, HL)}                                                                               # instantiations
+
+
+def sweep_name(cell):
+    hl, with_lens, moving, medium, solid = cell
+    return f"hl={hl} lens={with_lens} moving={moving} medium={medium} solid={solid}"
+
+
+def sweep_key(cell):
+    """last_kernel of a cell's one-shot frame"""
+    hl, with_lens, moving, medium, solid = cell
+    return QUADS | (SOLID if solid else 0) | (MEDIUM if medium else 0) | (MOTION if moving else 0) | (LENS if with_lens else 0) | (HL if hl else 0)
+
+
+def sweep_world(host, cell, width, height, pinhole=False):
+    """(host scene, center1, lens, quads) of one cell at width x height, spp 2, depth 6: _matrix_cfg's world.  pinhole: the same world
+    without the cell's lens."""
+    hl, with_lens, moving, medium, solid = cell
+    cfg = _matrix_cfg(hl, medium, solid, moving)
+    if with_lens and not pinhole:
+        cfg["camera"].update(aperture=0.5, focus_dist=6.0)
+    sc, c1, lens = _load(host, cfg, width, height, 2, 6, seed=2 * SWEEP_CELLS.index(cell))
+    return sc, c1, lens, sc.quads()
 
 
 @pytest.mark.gpu
 def test_every_quads_instantiation_is_launched(pkg, abi, host, torch_cuda, load_scene):
     """lights x pinhole / lens x static / moving x with / without media x with / without solids x one-shot / accumulating: the 64 QUADS
     instantiations, each selected by the scene that should reach it and reporting its key; the accumulated frame is the one-shot's and the
-    grid walk is the full scan's.  A quad-free scene reports the key it always reported."""
+    grid walk is the full scan's.  A quad-free scene reports the key it always reported.  (tests/test_feature_matrix.py compares every
+    one of these cells with the restatement.)"""
     torch = torch_cuda
     seen = {}
-    for hl in (False, True):
-        for with_lens in (False, True):
-            for moving in (False, True):
-                for medium in (False, True):
-                    for solid in (False, True):
-                        name = f"hl={hl} lens={with_lens} moving={moving} medium={medium} solid={solid}"
-                        cfg = _matrix_cfg(hl, medium, solid, moving)
-                        if with_lens:
-                            cfg["camera"].update(aperture=0.5, focus_dist=6.0)
-                        sc, c1, lens = _load(host, cfg, 9, 6, 2, 6, seed=len(seen))
-                        gs = _hip_scene(pkg, sc, c1, lens, sc.quads())
-                        assert gs.query("quads") == 7 and (gs.query("solids") == 7) == solid and (gs.query("media") == 1) == medium, name
-                        want = QUADS | (SOLID if solid else 0) | (MEDIUM if medium else 0) | (MOTION if moving else 0) | (LENS if with_lens else 0) | (HL if hl else 0)
-                        one = _one_shot(torch, gs)
-                        assert gs.query("last_kernel") == want, (name, gs.query("last_kernel"), want)
-                        seen.setdefault(want, name)
-                        acc = torch.zeros((gs.height, gs.width, 3), dtype=torch.int64, device="cuda:0")
-                        segs = 0
-                        for b, e in ((1, 2), (0, 1)):
-                            gs.accumulate(acc.data_ptr(), b, e - b, None, _stream(torch))
-                            segs += gs.wait()["segments"]
-                        assert gs.query("last_kernel") == want | ACCUM, (name, gs.query("last_kernel"))
-                        seen.setdefault(want | ACCUM, name)
-                        rgb = torch.zeros((gs.height, gs.width, 3), dtype=torch.uint8, device="cuda:0")
-                        lin = torch.zeros((gs.height, gs.width, 3), dtype=torch.float32, device="cuda:0")
-                        gs.resolve(acc.data_ptr(), 2, rgb.data_ptr(), lin.data_ptr(), None, _stream(torch))
-                        torch.cuda.current_stream().synchronize()
-                        _same(one, (rgb.cpu().numpy(), lin.cpu().numpy()), f"{name}: accumulated vs one-shot")
-                        assert segs == one[2]["segments"], name
-                        gs.set_option("variant", 1)
-                        full = _one_shot(torch, gs)
-                        assert gs.query("last_kernel") == want, name
-                        _same(one, full, f"{name}: grid walk vs full scan")
-                        assert full[2]["segments"] == one[2]["segments"], name
-                        gs.close()
-    want = {QUADS | s | me | m | l | a | h for s in (0, SOLID) for me in (0, MEDIUM) for m in (0, MOTION) for l in (0, LENS) for a in (0, ACCUM) for h in (0, HL)}
+    for cell in SWEEP_CELLS:
+        name, medium, solid = sweep_name(cell), cell[3], cell[4]
+        sc, c1, lens, quads = sweep_world(host, cell, 9, 6)
+        gs = _hip_scene(pkg, sc, c1, lens, quads)
+        assert gs.query("quads") == 7 and (gs.query("solids") == 7) == solid and (gs.query("media") == 1) == medium, name
+        want = sweep_key(cell)
+        one = _one_shot(torch, gs)
+        assert gs.query("last_kernel") == want, (name, gs.query("last_kernel"), want)
+        seen.setdefault(want, name)
+        acc = torch.zeros((gs.height, gs.width, 3), dtype=torch.int64, device="cuda:0")
+        segs = 0
+        for b, e in ((1, 2), (0, 1)):
+            gs.accumulate(acc.data_ptr(), b, e - b, None, _stream(torch))
+            segs += gs.wait()["segments"]
+        assert gs.query("last_kernel") == want | ACCUM, (name, gs.query("last_kernel"))
+        seen.setdefault(want | ACCUM, name)
+        rgb = torch.zeros((gs.height, gs.width, 3), dtype=torch.uint8, device="cuda:0")
+        lin = torch.zeros((gs.height, gs.width, 3), dtype=torch.float32, device="cuda:0")
+        gs.resolve(acc.data_ptr(), 2, rgb.data_ptr(), lin.data_ptr(), None, _stream(torch))
+        torch.cuda.current_stream().synchronize()
+        _same(one, (rgb.cpu().numpy(), lin.cpu().numpy()), f"{name}: accumulated vs one-shot")
+        assert segs == one[2]["segments"], name
+        gs.set_option("variant", 1)
+        full = _one_shot(torch, gs)
+        assert gs.query("last_kernel") == want, name
+        _same(one, full, f"{name}: grid walk vs full scan")
+        assert full[2]["segments"] == one[2]["segments"], name
+        gs.close()
+    want = SWEEP_KEYS
     assert len(want) == 64 and set(seen) == want, sorted(set(seen) ^ want)
     # the headline-like quad-free scene: tables in LDS, the short colour map, nothing else — through either entry point
     sc = load_scene("cover", 48, 32, 2)

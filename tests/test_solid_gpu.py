@@ -13,6 +13,7 @@ import pytest
 import fuzz_worlds as FW
 import solid_mini as SM
 from parity import assert_parity, pooled_atol
+from test_kernel_matrix import ALL_KEYS, CELLS, WIDE, _cell_id, _cell_json, _key
 from test_medium_gpu import _cfg, _hip_scene, _lam, _load, _med, _obj, _one_shot, _same, _stream
 
 SOLID, MEDIUM, MOTION, LENS, ACCUM = 256, 128, 64, 32, 16
@@ -127,71 +128,89 @@ def test_small_frames_against_the_restatement(pkg, abi, oracle, host, torch_cuda
     gs.close()
 
 
+# One scene per cell of the SOLID sweep, in the sweep's order: (lights, colour map, LDS / L2 tables) x pinhole / lens x static / moving x
+# without / with media.
+SWEEP_CELLS = [(hl, simple, form, with_lens, moving, medium) for hl, simple, form in CELLS if form != "wide"   # (solids with wide tables are
+               for with_lens in (False, True) for moving in (False, True) for medium in (False, True)]         #  refused, below)
+SWEEP_KEYS = {SOLID | me | m | l | k for k in ALL_KEYS if not k & WIDE for me in (0, MEDIUM) for m in (0, MOTION) for l in (0, LENS)}   # the 128
+
+
+def sweep_name(cell):
+    return _cell_id(cell[:3]) + ("/lens" if cell[3] else "") + ("/moving" if cell[4] else "") + ("/medium" if cell[5] else "")
+
+
+def sweep_key(cell):
+    """last_kernel of a cell's one-shot frame"""
+    return SOLID | (MEDIUM if cell[5] else 0) | (MOTION if cell[4] else 0) | (LENS if cell[3] else 0) | _key(*cell[:3])
+
+
+def sweep_world(host, cell, width, height, pinhole=False):
+    """(host scene, center1, lens, number of solids, number of media) of one cell at width x height, spp 2: the cell's world of
+    test_kernel_matrix.py with a checkered ground and every third sphere a Noise; medium: another third are media; moving: every second
+    sphere moves over the shutter.  pinhole: the same world without the cell's lens."""
+    hl, simple, form, with_lens, moving, medium = cell
+    cfg = json.loads(_cell_json(hl, simple, form, width=width, height=height, spp=2))
+    rng = np.random.default_rng(2 * SWEEP_CELLS.index(cell))
+    n_solids = n_media = 0
+    for i, o in enumerate(cfg["objects"]):
+        if "Light" in o["material"]:
+            continue
+        if i == 0:   # the ground keeps its colour (the general colour map's albedo above 1 included) as a checker
+            a = next(iter(o["material"].values())).get("albedo", [0.5, 0.5, 0.5])
+            o["material"] = _chk(a, [0.1, 0.1, 0.1], 2.0)
+            n_solids += 1
+        elif i % 3 == 1:
+            o["material"] = _noi([0.8, 0.7, 0.6], 3.0, ("noise", "turbulence", "marble")[i % 9 // 3], 1 + i % 4, i)
+            n_solids += 1
+        elif medium and i % 3 == 2 and o["radius"] > 0:
+            o["material"] = _med([0.8, 0.7, 0.6], round(float(rng.uniform(1.0, 10.0)), 3))
+            n_media += 1
+        if moving and i % 2 == 1:
+            cc, off = o["center"], rng.uniform(-0.3, 0.3, 3)
+            o["center1"] = {"x": cc["x"] + off[0], "y": cc["y"] + off[1], "z": cc["z"] + off[2]}
+    if with_lens and not pinhole:
+        cfg["camera"].update(aperture=0.5, focus_dist=7.0)
+    sc, c1, lens = _load(host, cfg, width, height, 2, cfg["max_depth"])
+    return sc, c1, lens, n_solids, n_media
+
+
 @pytest.mark.gpu
 def test_every_solid_instantiation_is_launched(pkg, abi, host, torch_cuda):
     """(lights, colour map, LDS / L2 tables) x pinhole / lens x static / moving x with / without media x one-shot / accumulating: the 128
     SOLID instantiations, each selected by the scene that should reach it and reporting its key; the accumulated frame is the one-shot's,
-    and the grid walk is the full scan's ("variant" 1)"""
-    from test_kernel_matrix import ALL_KEYS, CELLS, WIDE, _cell_id, _cell_json, _key
+    and the grid walk is the full scan's ("variant" 1).  (tests/test_feature_matrix.py compares every one of these cells with the
+    restatement.)"""
     torch = torch_cuda
     seen = {}
-    for cell in CELLS:
-        hl, simple, form = cell
-        if form == "wide":
-            continue     # (solids with wide tables are refused, below)
-        for with_lens in (False, True):
-            for moving in (False, True):
-                for medium in (False, True):
-                    name = _cell_id(cell) + ("/lens" if with_lens else "") + ("/moving" if moving else "") + ("/medium" if medium else "")
-                    cfg = json.loads(_cell_json(hl, simple, form, width=9, height=6, spp=2))
-                    rng = np.random.default_rng(len(seen))
-                    n_solids = n_media = 0
-                    for i, o in enumerate(cfg["objects"]):
-                        if "Light" in o["material"]:
-                            continue
-                        if i == 0:   # the ground keeps its colour (the general colour map's albedo above 1 included) as a checker
-                            a = next(iter(o["material"].values())).get("albedo", [0.5, 0.5, 0.5])
-                            o["material"] = _chk(a, [0.1, 0.1, 0.1], 2.0)
-                            n_solids += 1
-                        elif i % 3 == 1:
-                            o["material"] = _noi([0.8, 0.7, 0.6], 3.0, ("noise", "turbulence", "marble")[i % 9 // 3], 1 + i % 4, i)
-                            n_solids += 1
-                        elif medium and i % 3 == 2 and o["radius"] > 0:
-                            o["material"] = _med([0.8, 0.7, 0.6], round(float(rng.uniform(1.0, 10.0)), 3))
-                            n_media += 1
-                        if moving and i % 2 == 1:
-                            cc, off = o["center"], rng.uniform(-0.3, 0.3, 3)
-                            o["center1"] = {"x": cc["x"] + off[0], "y": cc["y"] + off[1], "z": cc["z"] + off[2]}
-                    if with_lens:
-                        cfg["camera"].update(aperture=0.5, focus_dist=7.0)
-                    sc, c1, lens = _load(host, cfg, 9, 6, 2, cfg["max_depth"])
-                    gs = _hip_scene(pkg, sc, c1, lens)
-                    assert gs.query("solids") == n_solids > 1 and (gs.query("media") == n_media) and (n_media > 0) == medium, name
-                    want = SOLID | (MEDIUM if medium else 0) | (MOTION if moving else 0) | (LENS if with_lens else 0) | _key(*cell)
-                    one = _one_shot(torch, gs)
-                    assert gs.query("last_kernel") == want, (name, gs.query("last_kernel"), want)
-                    seen.setdefault(want, name)
-                    acc = torch.zeros((gs.height, gs.width, 3), dtype=torch.int64, device="cuda:0")
-                    segs = 0
-                    for b, e in ((1, 2), (0, 1)):
-                        gs.accumulate(acc.data_ptr(), b, e - b, None, _stream(torch))
-                        segs += gs.wait()["segments"]
-                    assert gs.query("last_kernel") == want | ACCUM, (name, gs.query("last_kernel"))
-                    seen.setdefault(want | ACCUM, name)
-                    rgb = torch.zeros((gs.height, gs.width, 3), dtype=torch.uint8, device="cuda:0")
-                    lin = torch.zeros((gs.height, gs.width, 3), dtype=torch.float32, device="cuda:0")
-                    gs.resolve(acc.data_ptr(), 2, rgb.data_ptr(), lin.data_ptr(), None, _stream(torch))
-                    torch.cuda.current_stream().synchronize()
-                    _same(one, (rgb.cpu().numpy(), lin.cpu().numpy()), f"{name}: accumulated vs one-shot")
-                    assert segs == one[2]["segments"], name
-                    gs.set_option("variant", 1)
-                    full = _one_shot(torch, gs)
-                    assert gs.query("last_kernel") == want, name
-                    _same(one, full, f"{name}: grid walk vs full scan")
-                    assert full[2]["segments"] == one[2]["segments"], name
-                    gs.close()
-    base = {k for k in ALL_KEYS if not k & WIDE}
-    want = {SOLID | me | m | l | k for k in base for me in (0, MEDIUM) for m in (0, MOTION) for l in (0, LENS)}
+    for cell in SWEEP_CELLS:
+        name, medium = sweep_name(cell), cell[5]
+        sc, c1, lens, n_solids, n_media = sweep_world(host, cell, 9, 6)
+        gs = _hip_scene(pkg, sc, c1, lens)
+        assert gs.query("solids") == n_solids > 1 and (gs.query("media") == n_media) and (n_media > 0) == medium, name
+        want = sweep_key(cell)
+        one = _one_shot(torch, gs)
+        assert gs.query("last_kernel") == want, (name, gs.query("last_kernel"), want)
+        seen.setdefault(want, name)
+        acc = torch.zeros((gs.height, gs.width, 3), dtype=torch.int64, device="cuda:0")
+        segs = 0
+        for b, e in ((1, 2), (0, 1)):
+            gs.accumulate(acc.data_ptr(), b, e - b, None, _stream(torch))
+            segs += gs.wait()["segments"]
+        assert gs.query("last_kernel") == want | ACCUM, (name, gs.query("last_kernel"))
+        seen.setdefault(want | ACCUM, name)
+        rgb = torch.zeros((gs.height, gs.width, 3), dtype=torch.uint8, device="cuda:0")
+        lin = torch.zeros((gs.height, gs.width, 3), dtype=torch.float32, device="cuda:0")
+        gs.resolve(acc.data_ptr(), 2, rgb.data_ptr(), lin.data_ptr(), None, _stream(torch))
+        torch.cuda.current_stream().synchronize()
+        _same(one, (rgb.cpu().numpy(), lin.cpu().numpy()), f"{name}: accumulated vs one-shot")
+        assert segs == one[2]["segments"], name
+        gs.set_option("variant", 1)
+        full = _one_shot(torch, gs)
+        assert gs.query("last_kernel") == want, name
+        _same(one, full, f"{name}: grid walk vs full scan")
+        assert full[2]["segments"] == one[2]["segments"], name
+        gs.close()
+    want = SWEEP_KEYS
     assert len(want) == 128 and set(seen) == want, sorted(set(seen) ^ want)
 
 
