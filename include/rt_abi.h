@@ -91,7 +91,7 @@ typedef struct RtSphere {
 /* A quad (an extension of the schema; the reference has no such object and its loader rejects the file): the flat
  * parallelogram q + a u + b v, 0 <= a, b <= 1, two-sided.  The material fields mean what they mean in RtSphere; a quad may be
  * Lambertian, Metal, Glass, Checker or Noise (the solid's pattern in the quad's frame: centre = q).  Texture, Light and Medium quads
- * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads never move.
+ * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads do not move within a frame (no center1); rt_hip_scene_update_flats moves them between frames.
  * Triangles: `reserved` carries the SHAPE of the flat primitive, RT_QUAD_SHAPE_PARALLELOGRAM (0, the quad above) or
  * RT_QUAD_SHAPE_TRIANGLE (1): the points q + a u + b v with 0 <= a, 0 <= b, a + b <= 1, two-sided.  Everything else about the entry —
  * its place in the order, its id, its materials, the refusals — is a quad's.  A value above 1 is RT_ERR_INVALID (`quad k: bad shape`). */
@@ -381,7 +381,7 @@ int rt_hip_scene_create_moving(const RtScene* scene, const double* center1, int 
  * the AOVs like any surface; a first hit on a quad reports albedo by the material rule, the record's normal, 1 / t and its RT_MAT_*.
  * RT_ERR_INVALID: a non-finite q, u or v; nn zero, subnormal or not finite; a Texture, Light or Medium quad; solid parameters the
  * solid contract refuses.  RT_ERR_UNSUPPORTED: more than RT_MAX_QUADS quads; quads in a scene of more than 65 535 spheres (wide tables
- * have no QUADS kernels).  rt_hip_scene_query "quads" = their number.  rt_hip_scene_update_spheres keeps them.  The QUADS kernels
+ * have no QUADS kernels).  rt_hip_scene_query "quads" = their number.  rt_hip_scene_update_spheres keeps them where they are; rt_hip_scene_update_flats moves them.  The QUADS kernels
  * read the scene's tables from L2 and use the general colour map, whatever the scene's size and albedos. */
 int rt_hip_scene_create_quads(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out);
 /* rt_hip_scene_create_quads with a structure over the flat primitives: a binary BVH, built on the host, that every QUADS
@@ -396,7 +396,8 @@ int rt_hip_scene_create_quads(const RtScene* scene, const double* center1, const
  * checked before any record is read; n_quads = 0 is RT_ERR_INVALID.  Quads with wide tables stay RT_ERR_UNSUPPORTED.  "variant" 1 runs
  * the full scan over such a scene, whatever its size.  rt_hip_scene_query "flat_bvh" = the node count (0: no structure);
  * rt_hip_scene_table "flat_bvh" = the nodes (64 B each: f64 lo[3], hi[3]; u32 skip, first, count, pad) in depth-first order and
- * "flat_bvh_order" = the u32 order table the leaves index (both 0 bytes without the structure).  rt_hip_scene_update_spheres keeps it. */
+ * "flat_bvh_order" = the u32 order table the leaves index (both 0 bytes without the structure).  rt_hip_scene_update_spheres keeps it;
+ * rt_hip_scene_update_flats refits it or builds it anew. */
 int rt_hip_scene_create_flats_bvh(const RtScene* scene, const double* center1, const RtQuad* quads, uint32_t n_quads, int device, RtHipScene** out);
 void rt_hip_scene_destroy(RtHipScene*);
 /* Launch the megakernel for the given row tiles on `stream` (a hipStream_t, NULL = default).
@@ -436,7 +437,8 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * rt_hip_set_lens set a lens, 0: the pinhole), "motion" (spheres that move, rt_hip_scene_create_moving; 0: a static scene), "media"
  * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres and quads of kind RT_MAT_CHECKER or RT_MAT_NOISE), "quads" (rt_hip_scene_create_quads; both shapes),
  * "triangles" (the entries of shape RT_QUAD_SHAPE_TRIANGLE among them), "flat_bvh" (nodes of the structure over the flat primitives,
- * rt_hip_scene_create_flats_bvh; 0: none).  -1 for an unknown key. */
+ * rt_hip_scene_create_flats_bvh; 0: none), "flat_refits" (rt_hip_scene_update_flats calls applied by refit since the structure was last built:
+ * 0 after creation and after a rebuild).  -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Diagnostics: a copy of one resident table, as the kernels read it.  name: "grid" (the GridDesc bytes), "cell_word", "cell_items",
  * "large", "geom", "large_geom", "motion" (empty for a static scene), "quads" (RtQuadRec of csrc/common/rt_quad.h, 128 B each: q, u, v, N, w,
@@ -455,6 +457,33 @@ int rt_hip_scene_table(const RtHipScene*, const char* name, void* out, size_t ca
  * needs wide tables — and after any error the scene renders exactly as before the call.  Device buffers grow when the new grid needs
  * it and are otherwise reused.  A scene whose tables a live view shares (a group's ranks) is RT_ERR_INVALID: rt_hip_group_update_spheres. */
 int rt_hip_scene_update_spheres(RtHipScene*, const double* center, const double* center1);
+/* Move the flat primitives of a resident scene.  quv = n_quads x 9 f64: q, u, v of every entry, in entry order; n_quads
+ * must be the scene's.  Shapes, materials, spheres, camera, lens and options keep their values.  Blocking, like
+ * rt_hip_scene_update_spheres; waits for the scene's own unfinished launch first.  Scenes of rt_hip_scene_create_quads (the full scan:
+ * only the records are made anew) and of rt_hip_scene_create_flats_bvh.  On RT_OK:
+ *   - rt_hip_scene_table "quads" is byte for byte what creation builds for these q, u, v (rt_quad_prepare's bits, computed on the device);
+ *   - every frame, AOV buffer and surface record is bit for bit that of a scene freshly created with the new geometry, for "variant" 0 and 1;
+ *   - "quad_lim" and the material records are untouched.
+ * A scene with the structure is REFIT by default: "flat_bvh_order" and every node's skip, first, count and pad stay, a leaf's box becomes
+ * the union of its entries' padded boxes and an inner node's the union of its children's (min and max are exact: the union over all
+ * entries below it), always-visited leaves keep their infinite boxes; refitting back to the geometry of the last build restores that
+ * build's node table byte for byte.  The frame of such a scene is the full scan's in every bit whatever the tree looks like, so a refit
+ * scene renders what a rebuilt one renders; what a refit costs is tree quality, never a bit.  The structure is REBUILT on the host — all
+ * four flat tables then byte for byte creation's — when flags holds RT_UPDATE_FLATS_REBUILD, or when the set of entries outside the
+ * padding's preconditions differs from the resident one (an entry became a needle, crossed 2^40, or stopped being one).
+ * rt_hip_scene_query "flat_refits" counts the updates applied by refit since the last build (0 after creation or a rebuild): a caller
+ * decides with it when to pay for a rebuild.  RT_UPDATE_FLATS_DEVICE: quv is device memory on the scene's device (8-byte aligned): an
+ * update by refit then crosses no PCIe but the status readback; a rebuild copies the geometry back to the host first.
+ * Every error is RT_ERR_INVALID, with creation's wording where creation has one: a null argument; an unknown flag; n_quads different
+ * from the scene's; a scene without flat primitives; a non-finite component ("quad k: ..."); a degenerate entry ("quad k: ..."; of all bad
+ * entries the lowest k is reported); a scene whose tables a live view shares (rt_hip_group_update_flats).  After any error the scene
+ * renders exactly as before the call and its tables are unchanged.  An update drops what rt_hip_scene_update_spheres drops (the learned
+ * tile order, the progressive accumulator with its cached AOVs, the adaptive rounds) and the temporal history (as rt_hip_temporal_reset:
+ * moved flat primitives are not followed through the temporal filter).  rt_hip_scene_update_spheres afterwards keeps the moved flat
+ * primitives, and a flat update keeps moved spheres.  Device buffers are allocated by the first update and reused from then on. */
+#define RT_UPDATE_FLATS_REBUILD 1u   /* build the structure anew on the host: tables byte for byte creation's */
+#define RT_UPDATE_FLATS_DEVICE  2u   /* quv is device memory on the scene's device */
+int rt_hip_scene_update_flats(RtHipScene*, const double* quv, uint32_t n_quads, uint32_t flags);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
  * camera of a resident scene — the four vectors of camera.rs:52-63 — without touching its tables,
  * and render whole frames of it into a host buffer (internal device framebuffer, blocking). */
@@ -775,6 +804,9 @@ int rt_hip_group_set_option(RtHipGroup*, const char* key, int64_t value);
 /* rt_hip_scene_update_spheres on every rank (each rank's tables are built once; its second view follows them).  RT_ERR_INVALID while a
  * submitted frame is uncollected. */
 int rt_hip_group_update_spheres(RtHipGroup*, const double* center, const double* center1);
+/* rt_hip_scene_update_flats on every rank (each rank's tables are updated once; its second view follows them).  RT_ERR_INVALID while a
+ * submitted frame is uncollected, and for RT_UPDATE_FLATS_DEVICE in a group whose ranks are on more than one device. */
+int rt_hip_group_update_flats(RtHipGroup*, const double* quv, uint32_t n_quads, uint32_t flags);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
  * tile height; *tile_rows_out receives that height (2) */

@@ -91,13 +91,14 @@ def build_cli(force=False):
 # The translation units of librt_hip.so as (object name, source, defines): rt_hip_api.hip with kernel set 0 (the megakernel instantiations
 # with key >> 6 == 0, csrc/hip/rt_kernel.hip) and everything else; rt_kernel_set.hip once for each of the sets 1 - 15 (MOTION, DESIGN.md §14;
 # MEDIUM, §15; SOLID, §16; QUADS, §20: the sets 8 - 15, eight kernels each); the device grid build of rt_hip_scene_update_spheres (§17: a few
-# small kernels).
+# small kernels); the records and the refit of rt_hip_scene_update_flats (§24: three small kernels).
 HIP_UNITS = ([("rt_hip_api", "csrc/hip/rt_hip_api.hip", ["-DRT_KERNEL_SET_SPLIT"])]
              + [("rt_kernel_set%d" % k, "csrc/hip/rt_kernel_set.hip", ["-DRT_KERNEL_SET=%d" % k]) for k in range(1, 16)]
-             + [("rt_grid_build", "csrc/hip/rt_grid_build.hip", [])])
+             + [("rt_grid_build", "csrc/hip/rt_grid_build.hip", []), ("rt_flat_build", "csrc/hip/rt_flat_build.hip", [])])
 # what the units are compiled from: every unit, and the files they include
 HIP_DEPS = tuple(dict.fromkeys(u for _, u, _ in HIP_UNITS)) + (
     "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h", "csrc/hip/rt_grid_build.h",
+    "csrc/hip/rt_flat_build.h",
     "csrc/common/rt_atan2.h", "csrc/common/rt_neg_log.h", "csrc/common/rt_solid.h", "csrc/common/rt_quad.h")
 
 

@@ -6,7 +6,7 @@
 // operation in the order written, no contraction (every build has -ffp-contract=off):
 //     dot(p, q)   = (p0 q0 + p1 q1) + p2 q2
 //     cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)          (rt_abi.h, rt_hip_reproject's)
-// Once per quad, on the host (rt_quad_prepare):
+// Once per quad (rt_quad_prepare: the host at creation, the device when the flat primitives of a resident scene move):
 //     n = cross(u, v)    nn = dot(n, n)    len = sqrt(nn)
 //     N = n / len per component    D = dot(N, Q)    w = n / nn per component
 // A quad whose q, u or v has a non-finite component, or whose nn is zero, subnormal or not finite, is refused.
@@ -69,9 +69,10 @@ RT_QUAD_FN void rt_quad_cross(const double a[3], const double b[3], double out[3
 }
 RT_QUAD_FN bool rt_quad_finite(double x) { return x >= -1.7976931348623157e308 && x <= 1.7976931348623157e308; }
 
-// The per-quad constants (host only: sqrt is the C library's, correctly rounded).  0: fine; 1: a non-finite component of q, u or v;
-// 2: degenerate (nn zero, subnormal or not finite).
-inline int rt_quad_prepare(const double q[3], const double u[3], const double v[3], RtQuadRec* out) {
+// The per-quad constants, on the host (creation) and on the device (rt_flat_build.hip: rt_hip_scene_update_flats): sqrt and /
+// are correctly rounded on both, so the record's bits are the same.  0: fine; 1: a non-finite component of q, u or v; 2: degenerate (nn
+// zero, subnormal or not finite).
+RT_QUAD_FN int rt_quad_prepare(const double q[3], const double u[3], const double v[3], RtQuadRec* out) {
   for (int k = 0; k < 3; ++k)
     if (!rt_quad_finite(q[k]) || !rt_quad_finite(u[k]) || !rt_quad_finite(v[k])) return 1;
   double n[3];

@@ -1,0 +1,129 @@
+// rt_flat_build.h — the per-entry expressions of the structure over the flat primitives, shared by the host builder
+// (rt_tables.h build_flat_bvh: what rt_hip_scene_create_flats_bvh runs) and the device code that moves the flat primitives of a resident
+// scene (rt_flat_build.hip: what rt_hip_scene_update_flats runs), the static topology the refit needs, and the device
+// code's entry points.  Both sides compile these f64 expressions without contraction (-ffp-contract=off); every operation in them is
+// correctly rounded or exact (+ - * / sqrt fabs compare), so they give the same bits on both.
+#pragma once
+#include <vector>
+
+#include "rt_core.h"
+
+namespace rtc {
+
+// The padded box of entry k, or false when the entry is outside the preconditions under which the pad is derived (§22): a corner
+// coordinate beyond 2^40 in magnitude, edges shorter than 2^-40, K = (|u| + |v|)^2 / |cross(u, v)| above 2^20 (extreme skew, a needle),
+// anything not finite.  The box is that of the corners Q, Q + u, Q + v (and Q + u + v for a parallelogram), grown on every axis by
+//     pad = 2^-20 (|u|_1 + |v|_1) + 2^-30 max |corner coordinate|:
+// orders of magnitude above the rounding terms it has to cover, and never zero — an axis-aligned wall has a box of thickness 2 pad.
+// (flat_min / flat_max are std::min / std::max as comparisons: the second operand only where it is strictly smaller / larger.)
+constexpr double FLAT_COORD_MAX = 0x1p40, FLAT_EDGE_MIN = 0x1p-40, FLAT_SKEW_MAX = 0x1p20;
+RT_HD double flat_min(double a, double b) { return b < a ? b : a; }
+RT_HD double flat_max(double a, double b) { return a < b ? b : a; }
+RT_HD bool flat_entry_box(const RtQuadRec& r, double lim, double lo[3], double hi[3]) {
+  double l1 = 0.0, big = 0.0, edge = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    const double c[4] = {r.q[k], r.q[k] + r.u[k], r.q[k] + r.v[k], (r.q[k] + r.u[k]) + r.v[k]};
+    const int nc = lim < 2.0 ? 3 : 4;
+    lo[k] = hi[k] = c[0];
+    for (int j = 0; j < nc; ++j) {
+      if (!(fabs(c[j]) <= FLAT_COORD_MAX)) return false;
+      lo[k] = flat_min(lo[k], c[j]); hi[k] = flat_max(hi[k], c[j]);
+      big = flat_max(big, fabs(c[j]));
+    }
+    l1 += fabs(r.u[k]) + fabs(r.v[k]);
+    edge = flat_max(edge, flat_max(fabs(r.u[k]), fabs(r.v[k])));
+  }
+  if (!(edge >= FLAT_EDGE_MIN)) return false;
+  double n[3];
+  rt_quad_cross(r.u, r.v, n);
+  const double len_n = sqrt(rt_quad_dot(n, n)), len_uv = sqrt(rt_quad_dot(r.u, r.u)) + sqrt(rt_quad_dot(r.v, r.v));
+  if (!(len_n > 0.0 && len_uv * len_uv <= FLAT_SKEW_MAX * len_n)) return false;
+  const double pad = 0x1p-20 * l1 + 0x1p-30 * big;
+  for (int k = 0; k < 3; ++k) {
+    lo[k] -= pad; hi[k] += pad;
+    if (!(rt_quad_finite(lo[k]) && rt_quad_finite(hi[k]))) return false;
+  }
+  return pad > 0.0;
+}
+
+// What a refit needs of a built structure and what follows from entry counts alone (build_flat_bvh splits at the median BY COUNT): which
+// entries have a box (1) and which sit in the always-visited run (0); the bounded leaves; the inner nodes grouped by height (a leaf has
+// height 0, an inner node one more than the taller of its children, node i + 1 and node nodes[i + 1].skip), the nodes of height h being
+// level_nodes[level_start[h - 1] .. level_start[h]).  Derived once per build, on the host: the node order is depth first, so a child's
+// index is above its parent's and one backward pass finds every height.
+struct FlatTopology {
+  std::vector<uint32_t> boxed;        // [n_quads]
+  std::vector<uint32_t> leaves;       // the bounded leaves' node indices
+  std::vector<uint32_t> level_nodes;  // the inner nodes, by height
+  std::vector<uint32_t> level_start;  // [heights + 1], level_start[0] = 0
+  uint32_t n_run = 0;                 // always-visited leaves: the first n_run nodes
+};
+inline void flat_topology(const std::vector<FlatNode>& nodes, const std::vector<uint32_t>& order, uint32_t n_always, FlatTopology& tp) {
+  const uint32_t nn = (uint32_t)nodes.size();
+  tp.boxed.assign(order.size(), 1u);
+  for (uint32_t k = 0; k < n_always; ++k) tp.boxed[order[k]] = 0u;
+  tp.n_run = (n_always + 3u) / 4u;
+  tp.leaves.clear(); tp.level_nodes.clear(); tp.level_start.assign(1, 0u);
+  std::vector<uint32_t> height(nn, 0u);
+  uint32_t top = 0;
+  for (uint32_t i = nn; i-- > tp.n_run;) {
+    if (nodes[i].count) continue;
+    const uint32_t l = i + 1u, r = nodes[l].skip;
+    height[i] = 1u + (height[l] > height[r] ? height[l] : height[r]);
+    top = height[i] > top ? height[i] : top;
+  }
+  std::vector<uint32_t> at(top + 1u, 0u);
+  for (uint32_t i = tp.n_run; i < nn; ++i) {
+    if (nodes[i].count) tp.leaves.push_back(i); else at[height[i]]++;
+  }
+  for (uint32_t h = 1; h <= top; ++h) tp.level_start.push_back(tp.level_start.back() + at[h]);
+  tp.level_nodes.resize(tp.level_start.back());
+  std::vector<uint32_t> cursor(tp.level_start.begin(), tp.level_start.end());
+  for (uint32_t i = tp.n_run; i < nn; ++i)
+    if (!nodes[i].count) tp.level_nodes[cursor[height[i] - 1u]++] = i;
+}
+
+}  // namespace rtc
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+// The device code: per entry, its record (rt_quad.h rt_quad_prepare) and its padded box; per node, the union of what lies below it.  Two
+// steps before ONE small readback (Status): prepare() and, for a scene with the structure, refit().  Every pointer is device memory; all
+// work is enqueued on `stream`; a function returns the first HIP launch error.  Nothing here writes a table a frame reads: the records and
+// the nodes go into spare buffers the caller swaps in after the readback said that all is well.
+namespace rtfb {
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+struct Status {              // what prepare() leaves in Job::status
+  uint32_t bad_finite;       // the lowest entry with a non-finite component, or NONE
+  uint32_t bad_degenerate;   // the lowest degenerate entry, or NONE
+  uint32_t mismatch;         // entries whose boxed / refused flag differs from the resident one: the structure must be built anew
+  uint32_t pad;
+};
+
+struct Job {
+  uint32_t n = 0;                           // entries
+  // inputs
+  const double* quv = nullptr;              // [n][9] the new q, u, v
+  const double* lim = nullptr;              // [n] or null: a scene of parallelograms
+  const uint32_t* boxed = nullptr;          // [n] the resident flags (FlatTopology::boxed); null: a scene without the structure
+  // outputs of prepare()
+  RtQuadRec* rec = nullptr;                 // [n] the spare records
+  double* box = nullptr;                    // [n][6] lo, hi of every boxed entry (scratch); null without the structure
+  Status* status = nullptr;
+  // refit(): the live tables give the topology, the spare node table takes every node
+  uint32_t n_nodes = 0, n_run = 0, n_leaves = 0;
+  const rtc::FlatNode* live_nodes = nullptr;
+  const uint32_t* order = nullptr;
+  const uint32_t* leaves = nullptr;         // [n_leaves]
+  const uint32_t* level_nodes = nullptr;    // as FlatTopology's, resident
+  const uint32_t* level_start = nullptr;    // HOST memory, [n_levels + 1]
+  uint32_t n_levels = 0;
+  rtc::FlatNode* nodes = nullptr;           // [n_nodes] the spare node table
+};
+
+hipError_t prepare(const Job& j, hipStream_t stream);
+hipError_t refit(const Job& j, hipStream_t stream);
+
+}  // namespace rtfb
+#endif

@@ -154,9 +154,24 @@ struct RtHipScene {
     DevBuf quad_lim;         // triangles: [n_quads] the limit of alpha + beta per entry; unallocated in a scene without a triangle
     uint32_t n_tris = 0;
     // the structure over the flat primitives: [n_flat_nodes] FlatNode and [n_quads] the order table its leaves index;
-    // unallocated unless the scene came from rt_hip_scene_create_flats_bvh.  Written once, by the host copy below: flat primitives never move.
+    // unallocated unless the scene came from rt_hip_scene_create_flats_bvh.  Written by the host copy below and by rt_hip_scene_update_flats.
     DevBuf flat_nodes, flat_order;
     uint32_t n_flat_nodes = 0;
+    // rt_hip_scene_update_flats: the buffers an update builds into, swapped with `quads`, `flat_nodes` and (a rebuild)
+    // `flat_order` when it has succeeded — the old ones are the next update's spares, a steady animation allocates nothing; the device
+    // code's scratch (the geometry as uploaded, a box per entry, the status block); what a refit needs of the structure as built
+    // (rt_flat_build.h FlatTopology: resident, and on the host, where its vectors are the staging of their uploads); the limits on the
+    // host (a rebuild runs build_flat_bvh); the host staging of a rebuild's uploads, kept like the texels below (freeing memory HIP
+    // copied from stalls the queues); and the updates applied by refit since the structure was last built.
+    struct FlatSpare { DevBuf quads, flat_nodes, flat_order; } fspare;
+    struct FlatScratch { DevBuf quv, box, status; } fb;
+    DevBuf flat_boxed, flat_leaves, flat_levels;
+    rtc::FlatTopology flat_topo;
+    std::vector<double> host_lim, keep_quv;
+    std::vector<rtc::FlatNode> keep_flat_nodes;
+    std::vector<uint32_t> keep_flat_order;
+    rtc::FlatBvhHeader keep_flat_header{};
+    uint32_t flat_refits = 0;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -223,6 +238,7 @@ struct RtHipScene {
   //   option seed, max_depth, accum_reset                             -                   reset()    -         -
   //   option samples_per_pixel and every other option                 -                   -          -         -
   //   rt_hip_scene_update_spheres, a view following (adopt_tables)    forget()            reset()    reset()   -
+  //   rt_hip_scene_update_flats, a view following (adopt_flats)       forget()            reset()    reset()   reset()
   //   a launch whose OrderKey differs (launch_frame)                  forget(), new key   -          -         -
   //   rt_hip_scene_warm (+ launch bookkeeping as after creation)      forget(), no key    -          -         -
   //   rt_hip_temporal_surface (a real change), rt_hip_temporal_reset  -                   -          -         reset()
@@ -389,6 +405,13 @@ int upload(DevBuf& dst, const V& v) {
   if (bytes) RT_HIP_TRY(hipMemcpy(dst.p, v.data(), bytes, hipMemcpyHostToDevice));
   return RT_OK;
 }
+// what a refit needs of the structure just built (creation and every rebuild): derived on the host from the static topology, uploaded once
+int upload_flat_topology(RtHipScene::Resident& r, const std::vector<rtc::FlatNode>& nodes, const std::vector<uint32_t>& order, uint32_t n_always) {
+  rtc::flat_topology(nodes, order, n_always, r.flat_topo);
+  int rc;
+  if ((rc = upload(r.flat_boxed, r.flat_topo.boxed)) != RT_OK || (rc = upload(r.flat_leaves, r.flat_topo.leaves)) != RT_OK) return rc;
+  return upload(r.flat_levels, r.flat_topo.level_nodes);
+}
 }  // namespace
 
 namespace {
@@ -509,6 +532,8 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   r->n_tris = t.n_tris;
   if (flat_bvh && ((rc = upload(r->flat_nodes, t.flat_nodes)) != RT_OK || (rc = upload(r->flat_order, t.flat_order)) != RT_OK)) return rc;
   r->n_flat_nodes = (uint32_t)t.flat_nodes.size();
+  r->host_lim = t.quad_lim;
+  if (flat_bvh && (rc = upload_flat_topology(*r, t.flat_nodes, t.flat_order, t.flat_always)) != RT_OK) return rc;
   if (flat_bvh) {  // (§22: the records behind their header, one buffer; the header holds the device addresses of the four tables)
     if ((rc = r->quads.ensure(t.flat_blob.size() * sizeof(RtQuadRec))) != RT_OK) return rc;
     rtc::FlatBvhHeader h;
@@ -1184,6 +1209,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
   if (!std::strcmp(key, "triangles")) return (int64_t)s->res->n_tris;      // of "quads", the entries of shape triangle
   if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->n_flat_nodes;  // nodes of the structure over the flat primitives; 0: none
+  if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat_refits;  // updates applied by refit since the structure was last built
   if (!std::strcmp(key, "quads")) return (int64_t)s->res->n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
   if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
@@ -1785,6 +1811,7 @@ int adopt_tables(RtHipScene* s) {
   s->dev.large = r.large.get<const uint32_t>();
   s->dev.large_geom = r.large_geom.get<const rtc::SphereGeom>();
   s->dev.motion = r.n_moving ? r.motion.get<const double>() : nullptr;
+  if (r.n_quads) s->dev.quads.rec = r.quads.get<const RtQuadRec>() + (r.n_flat_nodes ? 1 : 0);  // (rt_hip_scene_update_flats swaps the records; §22: the header lies in front)
   s->order.forget();
   s->prog.reset();
   s->ad.reset();
@@ -1895,6 +1922,134 @@ int rt_hip_scene_view_follow(RtHipScene* view) {
 
 extern "C" int rt_hip_scene_update_spheres(RtHipScene* s, const double* center, const double* center1) {
   return scene_update(s, center, center1, false);
+}
+
+// ------------------------------------------------------------------------------ moving the flat primitives of a resident scene
+namespace {
+// a scene (or a view) takes over the records and the structure its resident now holds: what adopt_tables starts over, and the temporal
+// history (rt_hip_reproject_surface takes a flat id as "not displaced": a moved flat primitive is not followed through the filter)
+int adopt_flats(RtHipScene* s) {
+  s->tp.reset();
+  return adopt_tables(s);
+}
+
+// views_follow: the caller (the group) re-points the views that share this scene's tables itself
+int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags, bool views_follow) {
+  if (!s || !quv) return fail(RT_ERR_INVALID, "null argument");
+  if (flags & ~(RT_UPDATE_FLATS_REBUILD | RT_UPDATE_FLATS_DEVICE)) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: unknown flag");
+  RtHipScene::Resident& r = *s->res;
+  if (!r.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene has no flat primitive");
+  if (n_quads != r.n_quads)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(r.n_quads) + " flat primitives");
+  if (!views_follow && s->res.use_count() > 1)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene's tables are shared with a view (a group updates through rt_hip_group_update_flats)");
+  const bool on_device = (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
+  if (on_device)
+    if (const int refused = check_aligned(quv, 8, "rt_hip_scene_update_flats: quv must be 8-byte aligned")) return refused;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  if (s->n_launches && s->in_flight) { RT_HIP_TRY(hipStreamSynchronize(s->last_stream)); s->in_flight = false; }
+  if (!rtp::tl_in_group) rtp::reset();
+  rtp::Clock pc;
+  const uint32_t n = n_quads;
+  const bool bvh = r.n_flat_nodes != 0u;
+  bool rebuild = bvh && (flags & RT_UPDATE_FLATS_REBUILD) != 0u;
+  auto room = [](DevBuf& b, size_t bytes) { return b.ensure(bytes ? bytes : 16); };
+  int rc;
+  if ((rc = room(r.fspare.quads, ((size_t)n + (bvh ? 1u : 0u)) * sizeof(RtQuadRec))) != RT_OK || (rc = room(r.fb.status, sizeof(rtfb::Status))) != RT_OK ||
+      (!on_device && (rc = room(r.fb.quv, (size_t)n * 72)) != RT_OK) ||
+      (bvh && ((rc = room(r.fb.box, (size_t)n * 48)) != RT_OK || (rc = room(r.fspare.flat_nodes, (size_t)r.n_flat_nodes * sizeof(rtc::FlatNode))) != RT_OK)))
+    return rc;
+  if (!on_device) RT_HIP_TRY(hipMemcpy(r.fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
+  pc.mark("update_flats.upload");
+  RtQuadRec* const spare_rec = r.fspare.quads.get<RtQuadRec>() + (bvh ? 1 : 0);
+  const double* const d_lim = r.n_tris ? r.quad_lim.get<const double>() : nullptr;
+  rtfb::Job j;
+  j.n = n;
+  j.quv = on_device ? quv : r.fb.quv.get<const double>();
+  j.lim = d_lim;
+  j.rec = spare_rec;
+  j.status = r.fb.status.get<rtfb::Status>();
+  if (bvh) {
+    const rtc::FlatTopology& tp = r.flat_topo;
+    j.boxed = r.flat_boxed.get<const uint32_t>(); j.box = r.fb.box.get<double>();
+    j.n_nodes = r.n_flat_nodes; j.n_run = tp.n_run; j.n_leaves = (uint32_t)tp.leaves.size();
+    j.live_nodes = r.flat_nodes.get<const rtc::FlatNode>(); j.order = r.flat_order.get<const uint32_t>();
+    j.leaves = r.flat_leaves.get<const uint32_t>(); j.level_nodes = r.flat_levels.get<const uint32_t>();
+    j.level_start = tp.level_start.data(); j.n_levels = (uint32_t)tp.level_start.size() - 1u;
+    j.nodes = r.fspare.flat_nodes.get<rtc::FlatNode>();
+  }
+  rtc::FlatBvhHeader& h = r.keep_flat_header;  // (the staging of its upload: it lives as long as the scene)
+  auto put_header = [&](const DevBuf& nodes, uint32_t n_nodes, const DevBuf& order) {
+    std::memset(&h, 0, sizeof h);
+    h.nodes = nodes.get<const rtc::FlatNode>(); h.order = order.get<const uint32_t>();
+    h.rec = spare_rec; h.lim = d_lim;
+    h.n_nodes = n_nodes; h.n_quads = n; h.id_base = s->host.n_spheres;
+    return hipMemcpy(r.fspare.quads.p, &h, sizeof h, hipMemcpyHostToDevice);
+  };
+  RT_HIP_TRY(rtfb::prepare(j, nullptr));
+  if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
+    RT_HIP_TRY(rtfb::refit(j, nullptr));
+    RT_HIP_TRY(put_header(r.fspare.flat_nodes, r.n_flat_nodes, r.flat_order));  // the spare's header: its own records, the nodes that go live with it
+  }
+  rtfb::Status st;
+  RT_HIP_TRY(hipMemcpy(&st, r.fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the first bad entry of each class, changed flags
+  pc.mark("update_flats.kernels_and_readback");
+  if (st.bad_finite != rtfb::NONE || st.bad_degenerate != rtfb::NONE) {  // (creation's loop stops at the first bad entry: the lowest index wins)
+    if (st.bad_finite < st.bad_degenerate) return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + ": q, u and v must be finite");
+    return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)");
+  }
+  if (bvh && st.mismatch) rebuild = true;  // an entry became a needle, crossed 2^40, or stopped being one: the order table is another
+  uint32_t n_nodes = r.n_flat_nodes;
+  uint32_t n_always = 0;
+  if (rebuild) {  // the host's build_flat_bvh over the host's records, as creation runs it; the records themselves stay the device's
+    const double* host_quv = quv;
+    if (on_device) {
+      r.keep_quv.resize(9 * (size_t)n);
+      RT_HIP_TRY(hipMemcpy(r.keep_quv.data(), quv, (size_t)n * 72, hipMemcpyDeviceToHost));
+      host_quv = r.keep_quv.data();
+    }
+    rtc::HostTables t;
+    t.quads.resize(n);
+    for (uint32_t k = 0; k < n; ++k)
+      if (rt_quad_prepare(host_quv + 9 * (size_t)k, host_quv + 9 * (size_t)k + 3, host_quv + 9 * (size_t)k + 6, &t.quads[k]))
+        return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": the host refuses an entry the device accepted");
+    t.quad_lim = r.host_lim;
+    const std::string why = rtc::build_flat_bvh(t);
+    if (!why.empty()) return fail(RT_ERR_INVALID, why);
+    r.keep_flat_nodes.assign(t.flat_nodes.begin(), t.flat_nodes.end());
+    r.keep_flat_order.assign(t.flat_order.begin(), t.flat_order.end());
+    n_nodes = (uint32_t)r.keep_flat_nodes.size();
+    n_always = t.flat_always;
+    pc.mark("update_flats.host_build");
+    if ((rc = room(r.fspare.flat_nodes, (size_t)n_nodes * sizeof(rtc::FlatNode))) != RT_OK || (rc = room(r.fspare.flat_order, (size_t)n * 4)) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(r.fspare.flat_nodes.p, r.keep_flat_nodes.data(), (size_t)n_nodes * sizeof(rtc::FlatNode), hipMemcpyHostToDevice));
+    RT_HIP_TRY(hipMemcpy(r.fspare.flat_order.p, r.keep_flat_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    RT_HIP_TRY(put_header(r.fspare.flat_nodes, n_nodes, r.fspare.flat_order));
+    if ((rc = upload_flat_topology(r, r.keep_flat_nodes, r.keep_flat_order, n_always)) != RT_OK) return rc;
+    pc.mark("update_flats.upload_structure");
+  }
+  RT_HIP_TRY(hipDeviceSynchronize());
+  // everything is built: swap it in (nothing above changed what the scene renders with)
+  r.quads.swap(r.fspare.quads);
+  if (bvh) r.flat_nodes.swap(r.fspare.flat_nodes);
+  if (rebuild) { r.flat_order.swap(r.fspare.flat_order); r.n_flat_nodes = n_nodes; }
+  r.flat_refits = (bvh && !rebuild) ? r.flat_refits + 1u : 0u;
+  rc = adopt_flats(s);
+  pc.mark("update_flats.configuration");
+  return rc;
+}
+}  // namespace
+
+// a view follows its scene's flat update (internal; rt_hip_group_update_flats)
+int rt_hip_scene_view_follow_flats(RtHipScene* view) {
+  if (!view) return fail(RT_ERR_INVALID, "null argument");
+  RT_HIP_TRY(hipSetDevice(view->device));
+  if (view->n_launches && view->in_flight) { RT_HIP_TRY(hipStreamSynchronize(view->last_stream)); view->in_flight = false; }
+  return adopt_flats(view);
+}
+
+extern "C" int rt_hip_scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags) {
+  return scene_update_flats(s, quv, n_quads, flags, false);
 }
 
 // diagnostics: one resident table as the kernels read it

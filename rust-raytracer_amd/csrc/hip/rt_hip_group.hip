@@ -577,6 +577,23 @@ extern "C" int rt_hip_group_update_spheres(RtHipGroup* g, const double* center, 
   return RT_OK;
 }
 
+// move the flat primitives of every rank's scene (rt_hip_scene_update_flats); each rank's resident tables are updated once, its second
+// view follows.  quv with RT_UPDATE_FLATS_DEVICE is memory of ONE device: a group of several devices takes host memory.
+extern "C" int rt_hip_group_update_flats(RtHipGroup* g, const double* quv, uint32_t n_quads, uint32_t flags) {
+  if (!g) return fail(RT_ERR_INVALID, "null argument");
+  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_update_flats: a submitted frame is uncollected");
+  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
+    for (uint32_t r = 1; r < g->G; ++r)
+      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_update_flats: device memory serves the ranks of one device only");
+  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad geometry changes no rank)
+    int rc = scene_update_flats(g->scene[r], quv, n_quads, flags, true);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow_flats(g->scene2[r]);
+    if (rc != RT_OK) return rc;
+  }
+  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
+  return RT_OK;
+}
+
 namespace rtg { void prepare_staging(RtHipGroup* g, int n_frames); }
 extern "C" int rt_hip_group_set_option(RtHipGroup* g, const char* key, int64_t value) {
   if (!g || !key) return fail(RT_ERR_INVALID, "null argument");

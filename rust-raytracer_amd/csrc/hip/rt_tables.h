@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rt_core.h"
+#include "rt_flat_build.h"
 #include "rt_grid_build.h"
 
 namespace rtc {
@@ -540,38 +541,8 @@ inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables
 }
 
 // ------------------------------------------------------------------ the structure over the flat primitives
-// The padded box of entry k, or false when the entry is outside the preconditions under which the pad is derived (§22): a corner
-// coordinate beyond 2^40 in magnitude, edges shorter than 2^-40, K = (|u| + |v|)^2 / |cross(u, v)| above 2^20 (extreme skew, a needle),
-// anything not finite.  The box is that of the corners Q, Q + u, Q + v (and Q + u + v for a parallelogram), grown on every axis by
-//     pad = 2^-20 (|u|_1 + |v|_1) + 2^-30 max |corner coordinate|:
-// orders of magnitude above the rounding terms it has to cover, and never zero — an axis-aligned wall has a box of thickness 2 pad.
-constexpr double FLAT_COORD_MAX = 0x1p40, FLAT_EDGE_MIN = 0x1p-40, FLAT_SKEW_MAX = 0x1p20;
-inline bool flat_entry_box(const RtQuadRec& r, double lim, double lo[3], double hi[3]) {
-  double l1 = 0.0, big = 0.0, edge = 0.0;
-  for (int k = 0; k < 3; ++k) {
-    const double c[4] = {r.q[k], r.q[k] + r.u[k], r.q[k] + r.v[k], (r.q[k] + r.u[k]) + r.v[k]};
-    const int nc = lim < 2.0 ? 3 : 4;
-    lo[k] = hi[k] = c[0];
-    for (int j = 0; j < nc; ++j) {
-      if (!(std::fabs(c[j]) <= FLAT_COORD_MAX)) return false;
-      lo[k] = std::min(lo[k], c[j]); hi[k] = std::max(hi[k], c[j]);
-      big = std::max(big, std::fabs(c[j]));
-    }
-    l1 += std::fabs(r.u[k]) + std::fabs(r.v[k]);
-    edge = std::max(edge, std::max(std::fabs(r.u[k]), std::fabs(r.v[k])));
-  }
-  if (!(edge >= FLAT_EDGE_MIN)) return false;
-  double n[3];
-  rt_quad_cross(r.u, r.v, n);
-  const double len_n = std::sqrt(rt_quad_dot(n, n)), len_uv = std::sqrt(rt_quad_dot(r.u, r.u)) + std::sqrt(rt_quad_dot(r.v, r.v));
-  if (!(len_n > 0.0 && len_uv * len_uv <= FLAT_SKEW_MAX * len_n)) return false;
-  const double pad = 0x1p-20 * l1 + 0x1p-30 * big;
-  for (int k = 0; k < 3; ++k) {
-    lo[k] -= pad; hi[k] += pad;
-    if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) return false;
-  }
-  return pad > 0.0;
-}
+// (the padded box of an entry, flat_entry_box, and its constants: rt_flat_build.h — the device code that moves the flat primitives of a
+//  resident scene computes the same boxes)
 
 // "" or what is wrong with the tables of a structure over n entries: skip > index and skip <= n_nodes for every node (a walk ends in at most
 // n_nodes steps), first + count <= n, count <= 4, the order table a permutation.  build_flat_bvh checks what it built with this.

@@ -60,6 +60,13 @@
 // does the same for any file that holds a flat primitive, for A/B runs; on a file without one it changes nothing (there is nothing to build
 // over), and given twice it is refused with the usage line.  The frame is the same in every bit.
 //
+// Moving flat primitives from frame to frame (`--frames N --flat-frames PREFIX`): frame f takes its flat primitives from the
+// scene file PREFIX%03d.json (only its quads, boxes, triangles and meshes are used; count, shapes and materials must be the base file's —
+// anything else, or an unreadable file, ends the run with a message that names the frame).  The resident scene's flat primitives are moved
+// before every frame (rt_hip_group_update_flats / rt_hip_scene_update_flats: the structure of --flat-bvh is refit on the GPU); as for
+// --shutter no frame is in flight meanwhile, and the next frame's file is read while the frame renders.  Combines with --orbit, --shutter,
+// --flat-bvh, RT_GPUS and RT_ANIM=frames; without --frames, or with --denoise, --passes or --adaptive: the usage line.
+//
 // Moving spheres from frame to frame (`--frames N --shutter S`, 0 <= S <= 1): a sphere's "center" -> "center1" is its
 // path over the whole animation instead of over one exposure; frame f is exposed from center + dv f / N to center + dv (f + S) / N
 // (anim_path.h), S = 0 giving crisp spheres.  The resident scene's spheres are moved before every frame (rt_hip_group_update_spheres /
@@ -96,6 +103,38 @@ int create_group(const RtSceneFile* sf, RtHipGroup** out) {
   if (n_quads) return rt_hip_group_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, 0, out);
   return rt_hip_group_create_moving(rt_scene_get(sf), rt_scene_motion(sf), 0, out);
 }
+// --flat-frames PREFIX: frame f takes its flat primitives from the scene file PREFIX%03d.json, read with the ordinary loader;
+// only its rt_scene_quads are used, and they must be the base file's in count, shapes and materials.  load() returns "" and the
+// frame's q, u, v (n x 9), or what is wrong, naming the frame.  (One file at a time: the loader's error text is per process.)
+struct FlatFrames {
+  std::string prefix;
+  std::vector<RtQuad> base;
+  std::vector<double> quv;  // of the frame loaded last by the sharded animation
+  std::mutex mu;
+  bool on() const { return !prefix.empty(); }
+  std::string load(int f, std::vector<double>& out) {
+    std::lock_guard<std::mutex> lk(mu);
+    char path[4096];
+    std::snprintf(path, sizeof path, "%s%03d.json", prefix.c_str(), f);
+    const std::string which = "frame " + std::to_string(f) + " (" + path + "): ";
+    RtSceneFile* ff = nullptr;
+    if (rt_scene_load_file(path, &ff) != RT_OK) return which + rt_host_last_error();
+    uint32_t n = 0;
+    const RtQuad* q = rt_scene_quads(ff, &n);
+    std::string why;
+    if (n != base.size()) why = which + std::to_string(n) + " flat primitives, the scene has " + std::to_string(base.size());
+    out.resize(9 * base.size());
+    for (uint32_t k = 0; why.empty() && k < n; ++k) {
+      if (q[k].reserved != base[k].reserved) why = which + "flat primitive " + std::to_string(k) + " has another shape than the scene's";
+      else if (std::memcmp(&q[k].fuzz_or_ior, &base[k].fuzz_or_ior, sizeof(RtQuad) - offsetof(RtQuad, fuzz_or_ior)))
+        why = which + "flat primitive " + std::to_string(k) + " has another material than the scene's";
+      std::memcpy(&out[9 * (size_t)k], q[k].q, 72);
+    }
+    rt_scene_free(ff);
+    return why;
+  }
+};
+FlatFrames g_flats;
 // camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77 with the scene's
 // lens = {aperture, focus_dist} (rt_scene_lens; aperture 0: the pinhole, out[0..12] = rt_camera_derive's)
 void orbit_camera(const double cam[11], const double lens[2], double orbit_deg, int f, double out[20]) {
@@ -264,18 +303,23 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
   };
   int submitted = 0, collected = 0;
   std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
+  std::string flats_why;          // --flat-frames: what was wrong with a frame's file
   if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
   for (int f = 0; f < frames && status == 0 && !writers.failed(); ++f) {
     double out[20];
     const auto t0 = std::chrono::steady_clock::now();
     uint8_t* buf = writers.take_buffer();
     const auto t1 = std::chrono::steady_clock::now();
-    if (shutter >= 0.0) {  // (no frame may be in flight while the spheres move: frame f - 1 is collected first, its PNG overlaps)
+    if (shutter >= 0.0 || g_flats.on()) {  // (no frame may be in flight while the spheres or the flat primitives move: frame f - 1 is collected first, its PNG overlaps)
       bool ok = true;
       while (ok && collected < submitted) { ok = finish(collected); if (ok) collected++; }
       if (!ok) { writers.give_buffer(buf); break; }
-      rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
-      rc = rt_hip_group_update_spheres(hs, c_f.data(), c1_f.data());
+      rc = RT_OK;
+      if (shutter >= 0.0) {
+        rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
+        rc = rt_hip_group_update_spheres(hs, c_f.data(), c1_f.data());
+      }
+      if (rc == RT_OK && g_flats.on()) rc = rt_hip_group_update_flats(hs, g_flats.quv.data(), (uint32_t)g_flats.base.size(), 0u);
       if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; writers.give_buffer(buf); break; }
     }
     orbit_camera(cam, lens, orbit_deg, f, out);
@@ -287,9 +331,14 @@ int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbi
     if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; break; }
     in_flight.push_back(buf);
     submitted++;
+    if (g_flats.on() && f + 1 < frames) {  // (the next frame's file is read and checked while this frame renders)
+      flats_why = g_flats.load(f + 1, g_flats.quv);
+      if (!flats_why.empty()) break;
+    }
     if (submitted - collected == 2) { if (!finish(collected)) break; collected++; }
   }
   while (status == 0 && !writers.failed() && collected < submitted) { if (!finish(collected)) break; collected++; }
+  if (!flats_why.empty()) { std::fprintf(stderr, "%s\n", flats_why.c_str()); status = 101; }
   writers.finish();
   stats.report("sharded", collected, rt_hip_group_size(hs), W, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), ms_between(t_create, t_begin));
   rt_hip_group_destroy(hs);
@@ -443,7 +492,7 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
       std::vector<uint8_t> buf[2] = {std::vector<uint8_t>(bytes), std::vector<uint8_t>(bytes)};
       std::thread writer;
       int write_rc = RT_OK, i = 0;
-      std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
+      std::vector<double> c_f, c1_f, quv_f;  // --shutter: the spheres of the frame; --flat-frames: its flat primitives
       if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
       for (int f = (int)g; f < frames && write_rc == RT_OK; f += (int)G, ++i) {
         double out[20];
@@ -453,6 +502,11 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
         if (rc == RT_OK && shutter >= 0.0) {
           rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
           rc = rt_hip_scene_update_spheres(hs, c_f.data(), c1_f.data());
+        }
+        if (rc == RT_OK && g_flats.on()) {
+          const std::string why = g_flats.load(f, quv_f);
+          if (!why.empty()) { std::lock_guard<std::mutex> lk(out_mu); std::fprintf(stderr, "%s\n", why.c_str()); status[g] = 101; break; }
+          rc = rt_hip_scene_update_flats(hs, quv_f.data(), (uint32_t)g_flats.base.size(), 0u);
         }
         RtStats st{};
         if (rc == RT_OK) rc = rt_hip_render_to_host(hs, buf[i & 1].data(), &st);
@@ -504,6 +558,14 @@ int render_group_rgb8(const RtSceneFile* sf, const double* c, uint8_t* out_rgb8,
 
 // shutter < 0: no --shutter (every frame exposes the scene file's center -> center1)
 int animate(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
+  if (g_flats.on()) {  // (frame 0's file is read and checked before anything is created on a device)
+    uint32_t n_quads = 0;
+    const RtQuad* quads = rt_scene_quads(sf, &n_quads);
+    if (!n_quads) { std::fprintf(stderr, "--flat-frames: the scene has no flat primitive\n"); return 101; }
+    g_flats.base.assign(quads, quads + n_quads);
+    const std::string why = g_flats.load(0, g_flats.quv);
+    if (!why.empty()) { std::fprintf(stderr, "%s\n", why.c_str()); return 101; }
+  }
   const char* mode = std::getenv("RT_ANIM");
   if (mode && !std::strcmp(mode, "frames")) {
     const RtScene* sc = rt_scene_get(sf);
@@ -533,6 +595,7 @@ int run(int argc, char** argv) {
     if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
     else if (!std::strcmp(argv[i], "--flat-bvh")) { bad_args = g_flat_bvh; g_flat_bvh = true; }  // (given twice: the usage line)
+    else if (!std::strcmp(argv[i], "--flat-frames") && i + 1 < argc) { bad_args = g_flats.on() || !argv[i + 1][0]; g_flats.prefix = argv[++i]; }
     else if (!std::strcmp(argv[i], "--temporal-surface")) t_surface = true;
     else if ((!std::strcmp(argv[i], "--temporal-alpha") || !std::strcmp(argv[i], "--temporal-alpha-specular")) && i + 1 < argc) {
       double& dst = std::strcmp(argv[i], "--temporal-alpha") ? t_alpha_specular : t_alpha;
@@ -565,6 +628,7 @@ int run(int argc, char** argv) {
   const bool temporal = denoise && frames > 0 && orbit_given;  // (a denoised animation names its turn per frame)
   if (!temporal && (t_surface || t_alpha >= 0.0 || t_alpha_specular >= 0.0)) bad_args = true;  // (the three flags of the denoised animation alone)
   if (t_alpha_specular >= 0.0 && !t_surface) bad_args = true;
+  if (g_flats.on() && (frames <= 0 || denoise || passes > 0 || adapt)) bad_args = true;  // (moved flat primitives are not followed by the temporal filter)
   if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || (denoise && !temporal))) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
       (denoise && (adapt || ((frames != 0 || orbit_given) && !temporal))) || (argc - (g_flat_bvh ? 1 : 0) > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
     return usage();  // main.rs:9-12: usage line, normal return

@@ -54,6 +54,8 @@ def _bind(path, probes):
     L.rt_hip_scene_query.argtypes = [C.c_void_p, C.c_char_p]
     L.rt_hip_scene_query.restype = C.c_int64
     L.rt_hip_scene_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.rt_hip_scene_update_flats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_group_update_flats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_scene_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rt_hip_group_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
@@ -182,6 +184,26 @@ def _centres(n, c, what):
     return (C.c_double * max(1, 3 * n)).from_buffer_copy(a.tobytes() if n else bytes(8))
 
 
+def _flat_geometry(quv, device, rebuild):
+    """the arguments of rt_hip_*_update_flats for quv, an [n, 9] float64 numpy array (or anything numpy makes one of) or a CUDA torch
+    tensor of that shape and dtype: (pointer, n, flags, what must stay alive over the call).  A contiguous tensor on `device` (an index;
+    None: never) is handed over as device memory; any other tensor travels through the host."""
+    import numpy as np
+    flags = abi.RT_UPDATE_FLATS_REBUILD if rebuild else 0
+    if hasattr(quv, "data_ptr") and hasattr(quv, "is_cuda"):   # a torch tensor
+        if quv.dim() != 2 or quv.shape[1] != 9 or str(quv.dtype) != "torch.float64":
+            raise ValueError(f"quv must be an [n, 9] float64 tensor, got {tuple(quv.shape)} {quv.dtype}")
+        if quv.is_cuda and quv.is_contiguous() and device is not None and quv.device.index == device:
+            import torch
+            torch.cuda.current_stream(quv.device).synchronize()   # (the library reads on its own stream: what wrote the tensor has finished)
+            return C.c_void_p(quv.data_ptr()), quv.shape[0], flags | abi.RT_UPDATE_FLATS_DEVICE, quv
+        quv = quv.detach().cpu().numpy()
+    a = np.ascontiguousarray(np.asarray(quv, np.float64))
+    if a.ndim != 2 or a.shape[1] != 9:
+        raise ValueError(f"quv must be n x 9 values, got shape {a.shape}")
+    return C.c_void_p(a.ctypes.data), a.shape[0], flags, a
+
+
 TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order")   # the names rt_hip_scene_table knows
 
 
@@ -232,6 +254,14 @@ class HipScene:
         n_spheres x 3 at shutter close); the grid is rebuilt on the device.  Blocking."""
         _check(self._L.rt_hip_scene_update_spheres(self._h, _centres(self.n_spheres, center, "center"), _centres(self.n_spheres, center1, "center1")),
                self._L)
+
+    def update_flats(self, quv, rebuild=False):
+        """rt_hip_scene_update_flats: move the flat primitives to quv — [n_quads, 9] float64 (q, u, v per entry), a numpy
+        array or a CUDA torch tensor; a contiguous tensor on the scene's device is read where it is (no PCIe).  The structure is refit on
+        the device; rebuild=True (or a change of the set of entries outside its preconditions) builds it anew on the host.  Blocking."""
+        p, n, flags, keep = _flat_geometry(quv, self.device, rebuild)
+        _check(self._L.rt_hip_scene_update_flats(self._h, p, n, flags), self._L)
+        del keep
 
     def table(self, name):
         """rt_hip_scene_table (diagnostics): the bytes of one resident table (TABLES) as the kernels read it"""
@@ -502,6 +532,13 @@ class HipGroup:
         """rt_hip_group_update_spheres: HipScene.update_spheres on every rank; no submitted frame may be uncollected"""
         _check(self._L.rt_hip_group_update_spheres(self._h, _centres(self.n_spheres, center, "center"), _centres(self.n_spheres, center1, "center1")),
                self._L)
+
+    def update_flats(self, quv, rebuild=False):
+        """rt_hip_group_update_flats: HipScene.update_flats on every rank (the geometry travels through host memory: the ranks may be on
+        several devices); no submitted frame may be uncollected"""
+        p, n, flags, keep = _flat_geometry(quv, None, rebuild)
+        _check(self._L.rt_hip_group_update_flats(self._h, p, n, flags), self._L)
+        del keep
 
     def set_option(self, key, value):
         _check(self._L.rt_hip_group_set_option(self._h, key.encode(), int(value)), self._L)
