@@ -90,6 +90,8 @@ struct Clock {   // mark("x") books the time since the previous mark under x
     t = n;
   }
 };
+// how a scene's creation or update starts: with a profile of its own, unless a group is being created
+Clock begin() { if (!tl_in_group) reset(); return Clock(); }
 }  // namespace rtp
 extern "C" const char* rt_hip_setup_profile(void) {
   std::lock_guard<std::mutex> lk(rtp::g_mu);
@@ -137,41 +139,84 @@ struct DevBuf {
   }
 };
 
+enum class Moved { spheres, flats };  // what an update replaced in a resident scene (adopt_tables)
+
 struct RtHipScene {
   int device = 0;
   // What rt_hip_scene_create builds, once: shared by the scene and its views (rt_hip_scene_clone_view), freed with the last of them.
+  // The tables an update replaces come in generations of one type: `live` is what the kernels read, `spare` what the next update builds
+  // into and swaps in when it has succeeded — the old tables are the update after's spares, a steady animation allocates nothing.
   struct Resident {
     int device = 0;
-    DevBuf geom, mat, lights, tex, sky, tex4, sky4, matc, cell_word, cell_items, large, large_geom;
-    DevBuf all;              // 0..n-1: the `large` list of the brute-force arm (variant 1)
-    DevBuf motion;           // motion blur: [n][4] dv per sphere (rt_tables.h HostTables::motion); unallocated when static
-    uint32_t n_moving = 0;
+    bool has_lights = false, simple_colour = false;
+    int num_cus = 0;
+    size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
+    // The spheres, and what rt_hip_scene_update_spheres moves them with.
+    struct Spheres {
+      struct Tables {          // the geometry and the product grid (variant 0) over it
+        DevBuf geom, cell_word, cell_items, large, large_geom;
+        rtc::GridDesc grid{};
+        // motion blur: [n][4] dv per sphere (rt_tables.h HostTables::motion).  It counts only while n_moving: static tables own whatever
+        // buffer the swap left them (none, or an older generation's rows), and every reader asks n_moving first (Resident::point, rt_hip_scene_table)
+        DevBuf motion;
+        uint32_t n_moving = 0;
+      } live, spare;
+      struct Scratch { DevBuf centre, plan_large, range, lflag, lpos, count, start, cursor, block_sum, counts, raw_items, raw_cell; } scratch;  // the device builder's
+      DevBuf all;              // 0..n-1: the `large` list of the brute-force arm (variant 1)
+      // on the host: the spheres at their current centres (the host plans the next grid from them) and a second copy the next centres are
+      // written into; the plan; the staging of the motion upload, kept like the texels below
+      std::vector<RtSphere> spheres, next_spheres;
+      rtc::GridPlan plan;
+      std::vector<double> keep_motion;
+      // each sphere's centre at shutter time 0.5 of the live tables, c + (c1 - c) * 0.5 in f64 ([n][3]; rt_hip_temporal_surface's displacement)
+      std::vector<double> mid;
+      void set_mid(const std::vector<double>& motion) {
+        mid.resize(3 * spheres.size());
+        for (size_t i = 0; i < spheres.size(); ++i)
+          for (int k = 0; k < 3; ++k) mid[3 * i + k] = spheres[i].center[k] + (motion.empty() ? 0.0 : motion[4 * i + k]) * 0.5;
+      }
+    } sph;
+    // The flat primitives (quads; triangles, §21), the structure over them (§22: only in a scene that came from
+    // rt_hip_scene_create_flats_bvh) and what rt_hip_scene_update_flats (§24) moves them with.
+    struct Flats {
+      struct Tables {
+        // [n_quads] RtQuadRec, their materials are records n_spheres + k of `mat` and `matc`; with the structure: one buffer, the FlatBvhHeader
+        // in front of the records (Flats::first_rec).  Unallocated without quads.
+        DevBuf rec;
+        DevBuf nodes, order;   // the structure: [n_nodes] FlatNode and [n_quads] the order table its leaves index
+      } live, spare;           // (a refit keeps the live order table: only a rebuild swaps it)
+      DevBuf lim;              // [n_quads] the limit of alpha + beta per entry; unallocated in a scene without a triangle
+      uint32_t n_quads = 0, n_tris = 0, n_nodes = 0;  // (n_nodes: of the live structure; 0: none, every segment scans the records)
+      // what a refit needs of the structure as built (rt_flat_build.h FlatTopology), on the device and on the host: topo's vectors are the staging of their uploads
+      DevBuf boxed, leaves, levels;
+      rtc::FlatTopology topo;
+      struct Scratch { DevBuf quv, box, status; } scratch;  // the device code's: the geometry as uploaded, a box per entry, the status block
+      // on the host: the limits (a rebuild runs build_flat_bvh) and the staging of a rebuild's uploads, kept like the texels below
+      std::vector<double> host_lim, keep_quv;
+      std::vector<rtc::FlatNode> keep_nodes;
+      std::vector<uint32_t> keep_order;
+      rtc::FlatBvhHeader keep_header{};
+      uint32_t refits = 0;     // the updates applied by refit since the structure was last built
+      // the first record of a generation as the kernels see it (DevScene::quads.rec): behind the header, where there is a structure
+      uint32_t header_recs() const { return n_nodes ? 1u : 0u; }  // the record slots the header takes
+      RtQuadRec* first_rec(const Tables& t) const { return t.rec.get<RtQuadRec>() + header_recs(); }
+      size_t rec_bytes() const { return ((size_t)n_quads + header_recs()) * sizeof(RtQuadRec); }  // of Tables::rec
+      const double* dev_lim() const { return n_tris ? lim.get<const double>() : nullptr; }
+      // the header in front of generation `t`'s records: they, `t`'s n_nodes nodes, the limits, and the order table that is live beside them
+      rtc::FlatBvhHeader header(const Tables& t, uint32_t t_n_nodes, const DevBuf& order, uint32_t id_base) const {
+        rtc::FlatBvhHeader h{};
+        h.nodes = t.nodes.get<const rtc::FlatNode>(); h.order = order.get<const uint32_t>();
+        h.rec = first_rec(t); h.lim = dev_lim();
+        h.n_nodes = t_n_nodes; h.n_quads = n_quads; h.id_base = id_base;
+        return h;
+      }
+    } flat;
+    // Materials, lights, media, textures and sky: uploaded at creation, never replaced.
+    DevBuf mat, matc, lights;
     DevBuf medium;           // participating media: [n] density per sphere, 0 = no medium (HostTables::medium); unallocated without media
     uint32_t n_media = 0;
     uint32_t n_solids = 0;   // solid textures: Checker and Noise spheres (and quads); their parameters are in the `mat` records
-    DevBuf quads;            // quads: [n_quads] RtQuadRec; their materials are records n_spheres + k of `mat` and `matc`; unallocated without quads
-    uint32_t n_quads = 0;
-    DevBuf quad_lim;         // triangles: [n_quads] the limit of alpha + beta per entry; unallocated in a scene without a triangle
-    uint32_t n_tris = 0;
-    // the structure over the flat primitives: [n_flat_nodes] FlatNode and [n_quads] the order table its leaves index;
-    // unallocated unless the scene came from rt_hip_scene_create_flats_bvh.  Written by the host copy below and by rt_hip_scene_update_flats.
-    DevBuf flat_nodes, flat_order;
-    uint32_t n_flat_nodes = 0;
-    // rt_hip_scene_update_flats: the buffers an update builds into, swapped with `quads`, `flat_nodes` and (a rebuild)
-    // `flat_order` when it has succeeded — the old ones are the next update's spares, a steady animation allocates nothing; the device
-    // code's scratch (the geometry as uploaded, a box per entry, the status block); what a refit needs of the structure as built
-    // (rt_flat_build.h FlatTopology: resident, and on the host, where its vectors are the staging of their uploads); the limits on the
-    // host (a rebuild runs build_flat_bvh); the host staging of a rebuild's uploads, kept like the texels below (freeing memory HIP
-    // copied from stalls the queues); and the updates applied by refit since the structure was last built.
-    struct FlatSpare { DevBuf quads, flat_nodes, flat_order; } fspare;
-    struct FlatScratch { DevBuf quv, box, status; } fb;
-    DevBuf flat_boxed, flat_leaves, flat_levels;
-    rtc::FlatTopology flat_topo;
-    std::vector<double> host_lim, keep_quv;
-    std::vector<rtc::FlatNode> keep_flat_nodes;
-    std::vector<uint32_t> keep_flat_order;
-    rtc::FlatBvhHeader keep_flat_header{};
-    uint32_t flat_refits = 0;
+    DevBuf tex, sky, tex4, sky4;
     // The host copies of the BIG uploads (texels: 29 MB for the reference's test scene) live as long as the scene.  hipMemcpy from
     // pageable memory pins the source pages for the device (a userptr mapping the runtime caches); giving such memory back to
     // the OS (free -> munmap) fires the driver's MMU notifier, which EVICTS the process's hardware queues and restores them
@@ -181,26 +226,22 @@ struct RtHipScene {
     rtc::TexelVec keep_tex4, keep_sky4;
     std::vector<uint8_t> keep_tex_rgb8, keep_sky_rgb8;
     size_t texel_bytes = 0;
-    rtc::GridDesc grid{};    // the product grid (variant 0)
-    // rt_hip_scene_update_spheres: the scene's spheres at their current centres (the host plans the next grid from
-    // them) and a second copy the next centres are written into; the tables an update builds into, swapped with the ones above when
-    // it has succeeded (the old ones are the next update's spares: a steady animation allocates nothing); the device builder's
-    // scratch; and the host staging of its uploads, kept like the texels above (freeing memory HIP copied from stalls the queues).
-    std::vector<RtSphere> spheres, next_spheres;
-    struct Spare { DevBuf geom, cell_word, cell_items, large, large_geom, motion; } spare;
-    struct Scratch { DevBuf centre, plan_large, range, lflag, lpos, count, start, cursor, block_sum, counts, raw_items, raw_cell; } gb;
-    rtc::GridPlan plan;
-    std::vector<double> keep_motion;
-    // each sphere's centre at shutter time 0.5 of the tables above, c + (c1 - c) * 0.5 in f64 ([n][3]; rt_hip_temporal_surface's displacement)
-    std::vector<double> mid;
-    void set_mid(const std::vector<double>& motion) {
-      mid.resize(3 * spheres.size());
-      for (size_t i = 0; i < spheres.size(); ++i)
-        for (int k = 0; k < 3; ++k) mid[3 * i + k] = spheres[i].center[k] + (motion.empty() ? 0.0 : motion[4 * i + k]) * 0.5;
+    // Point a scene's (or a view's) kernels at the live tables: every pointer and count of DevScene that follows from this struct.
+    void point(rtc::DevScene& d) const {
+      const Spheres::Tables& t = sph.live;
+      d.grid = t.grid;
+      d.geom = t.geom.get<const rtc::SphereGeom>(); d.cell_word = t.cell_word.get<const uint32_t>();
+      d.cell_items = t.cell_items.get<const uint16_t>(); d.large = t.large.get<const uint32_t>();
+      d.large_geom = t.large_geom.get<const rtc::SphereGeom>();
+      d.motion = t.n_moving ? t.motion.get<const double>() : nullptr;
+      d.quads.rec = flat.n_quads ? flat.first_rec(flat.live) : nullptr; d.quads.lim = flat.dev_lim();
+      d.n_quads = flat.n_quads;
+      d.n_tris = flat.n_tris | (flat.n_nodes ? rtc::FLAT_BVH_BIT : 0u);  // (§22: the bit says that the header lies in front of quads.rec[0])
+      d.mat = mat.get<const rtc::SphereMat>(); d.matc = matc.get<const rtc::MatCore>();
+      d.lights = lights.get<const uint32_t>(); d.medium = n_media ? medium.get<const double>() : nullptr;
+      d.tex = tex.get<const uint8_t>(); d.sky = sky.get<const uint8_t>();
+      d.tex4 = tex4.get<const uint32_t>(); d.sky4 = sky4.get<const uint32_t>();
     }
-    bool has_lights = false, simple_colour = false;
-    int num_cus = 0;
-    size_t lds_cap = 0;      // dynamic LDS a workgroup may ask for on this device
     ~Resident() { (void)hipSetDevice(device); }  // (the buffers are freed after this body)
   };
   std::shared_ptr<Resident> res;
@@ -238,7 +279,7 @@ struct RtHipScene {
   //   option seed, max_depth, accum_reset                             -                   reset()    -         -
   //   option samples_per_pixel and every other option                 -                   -          -         -
   //   rt_hip_scene_update_spheres, a view following (adopt_tables)    forget()            reset()    reset()   -
-  //   rt_hip_scene_update_flats, a view following (adopt_flats)       forget()            reset()    reset()   reset()
+  //   rt_hip_scene_update_flats, a view following (adopt_tables)      forget()            reset()    reset()   reset()
   //   a launch whose OrderKey differs (launch_frame)                  forget(), new key   -          -         -
   //   rt_hip_scene_warm (+ launch bookkeeping as after creation)      forget(), no key    -          -         -
   //   rt_hip_temporal_surface (a real change), rt_hip_temporal_reset  -                   -          -         reset()
@@ -397,20 +438,30 @@ extern "C" void rt_hip_scene_destroy(RtHipScene* s) {
 }
 
 namespace {
+int room(DevBuf& b, size_t bytes) { return b.ensure(bytes ? bytes : 16); }  // (an empty table is 16 bytes, never a null pointer)
 template <typename V>
 int upload(DevBuf& dst, const V& v) {
   const size_t bytes = v.size() * sizeof(typename V::value_type);
-  const int rc = dst.ensure(bytes ? bytes : 16);  // (an empty table is 16 bytes, never a null pointer)
+  const int rc = room(dst, bytes);
   if (rc != RT_OK) return rc;
   if (bytes) RT_HIP_TRY(hipMemcpy(dst.p, v.data(), bytes, hipMemcpyHostToDevice));
   return RT_OK;
 }
-// what a refit needs of the structure just built (creation and every rebuild): derived on the host from the static topology, uploaded once
-int upload_flat_topology(RtHipScene::Resident& r, const std::vector<rtc::FlatNode>& nodes, const std::vector<uint32_t>& order, uint32_t n_always) {
-  rtc::flat_topology(nodes, order, n_always, r.flat_topo);
+// the structure just built (creation and every rebuild) into generation `g`, and what a refit needs of it: derived on the host from the static
+// topology, uploaded once
+int upload_flat_structure(RtHipScene::Resident::Flats& f, RtHipScene::Resident::Flats::Tables& g, const std::vector<rtc::FlatNode>& nodes,
+                          const std::vector<uint32_t>& order, uint32_t n_always) {
   int rc;
-  if ((rc = upload(r.flat_boxed, r.flat_topo.boxed)) != RT_OK || (rc = upload(r.flat_leaves, r.flat_topo.leaves)) != RT_OK) return rc;
-  return upload(r.flat_levels, r.flat_topo.level_nodes);
+  if ((rc = upload(g.nodes, nodes)) != RT_OK || (rc = upload(g.order, order)) != RT_OK) return rc;
+  rtc::flat_topology(nodes, order, n_always, f.topo);
+  if ((rc = upload(f.boxed, f.topo.boxed)) != RT_OK || (rc = upload(f.leaves, f.topo.leaves)) != RT_OK) return rc;
+  return upload(f.levels, f.topo.level_nodes);
+}
+// before a scene or a view takes other tables: its device is current, and a launch in flight has finished (its stream is synchronised)
+int make_current_and_drain(RtHipScene* s) {
+  RT_HIP_TRY(hipSetDevice(s->device));
+  if (s->n_launches && s->in_flight) { RT_HIP_TRY(hipStreamSynchronize(s->last_stream)); s->in_flight = false; }
+  return RT_OK;
 }
 }  // namespace
 
@@ -482,8 +533,7 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   int n = rt_hip_device_count();
   if (n <= 0) return fail(RT_ERR_NO_DEVICE, rt_strerror(RT_ERR_NO_DEVICE));
   if (device < 0 || device >= n) return fail(RT_ERR_INVALID, "device index out of range");
-  if (!rtp::tl_in_group) rtp::reset();
-  rtp::Clock pc;
+  rtp::Clock pc = rtp::begin();
   rtc::HostTables t;
   std::string why = rtc::build_tables(*scene, t, false, center1, quads, n_quads);
   if (!why.empty()) return fail(RT_ERR_INVALID, why);
@@ -500,9 +550,11 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   r->device = device;
   r->has_lights = !t.lights.empty();
   r->simple_colour = t.simple_colour;
-  r->grid = t.grid;
-  r->spheres.assign(scene->spheres, scene->spheres + scene->n_spheres);
-  r->set_mid(t.motion);
+  RtHipScene::Resident::Spheres::Tables& live = r->sph.live;
+  RtHipScene::Resident::Flats& f = r->flat;
+  live.grid = t.grid;
+  r->sph.spheres.assign(scene->spheres, scene->spheres + scene->n_spheres);
+  r->sph.set_mid(t.motion);
   {
     hipDeviceProp_t prop;
     RT_HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -514,40 +566,34 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   }
   pc.mark("scene.device_properties");
   int rc;
-  if ((rc = upload(r->geom, t.geom)) != RT_OK) return rc;
+  if ((rc = upload(live.geom, t.geom)) != RT_OK) return rc;
   if ((rc = upload(r->mat, t.mat)) != RT_OK) return rc;
   if ((rc = upload(r->lights, t.lights)) != RT_OK) return rc;
   if ((rc = upload(r->matc, t.matc)) != RT_OK) return rc;
-  if ((rc = upload(r->cell_word, t.cell_word)) != RT_OK) return rc;
-  if ((rc = t.grid.wide ? upload(r->cell_items, t.cell_items32) : upload(r->cell_items, t.cell_items)) != RT_OK) return rc;  // (wide tables: the 32-bit item lists)
-  if ((rc = upload(r->large, t.large)) != RT_OK) return rc;
-  if ((rc = upload(r->large_geom, t.large_geom)) != RT_OK) return rc;
-  if (t.n_moving && (rc = upload(r->motion, t.motion)) != RT_OK) return rc;
-  r->n_moving = t.n_moving;
+  if ((rc = upload(live.cell_word, t.cell_word)) != RT_OK) return rc;
+  if ((rc = t.grid.wide ? upload(live.cell_items, t.cell_items32) : upload(live.cell_items, t.cell_items)) != RT_OK) return rc;  // (wide tables: the 32-bit item lists)
+  if ((rc = upload(live.large, t.large)) != RT_OK) return rc;
+  if ((rc = upload(live.large_geom, t.large_geom)) != RT_OK) return rc;
+  if (t.n_moving && (rc = upload(live.motion, t.motion)) != RT_OK) return rc;
+  live.n_moving = t.n_moving;
   if (t.n_media && (rc = upload(r->medium, t.medium)) != RT_OK) return rc;
   r->n_media = t.n_media;
   r->n_solids = t.n_solids;
-  r->n_quads = n_quads;
-  if (!t.quad_lim.empty() && (rc = upload(r->quad_lim, t.quad_lim)) != RT_OK) return rc;
-  r->n_tris = t.n_tris;
-  if (flat_bvh && ((rc = upload(r->flat_nodes, t.flat_nodes)) != RT_OK || (rc = upload(r->flat_order, t.flat_order)) != RT_OK)) return rc;
-  r->n_flat_nodes = (uint32_t)t.flat_nodes.size();
-  r->host_lim = t.quad_lim;
-  if (flat_bvh && (rc = upload_flat_topology(*r, t.flat_nodes, t.flat_order, t.flat_always)) != RT_OK) return rc;
+  f.n_quads = n_quads;
+  if (!t.quad_lim.empty() && (rc = upload(f.lim, t.quad_lim)) != RT_OK) return rc;
+  f.n_tris = t.n_tris;
+  f.n_nodes = (uint32_t)t.flat_nodes.size(); f.host_lim = t.quad_lim;
   if (flat_bvh) {  // (§22: the records behind their header, one buffer; the header holds the device addresses of the four tables)
-    if ((rc = r->quads.ensure(t.flat_blob.size() * sizeof(RtQuadRec))) != RT_OK) return rc;
-    rtc::FlatBvhHeader h;
-    std::memset(&h, 0, sizeof h);
-    h.nodes = r->flat_nodes.get<const rtc::FlatNode>(); h.order = r->flat_order.get<const uint32_t>();
-    h.rec = r->quads.get<const RtQuadRec>() + 1; h.lim = t.n_tris ? r->quad_lim.get<const double>() : nullptr;
-    h.n_nodes = r->n_flat_nodes; h.n_quads = n_quads; h.id_base = scene->n_spheres;
+    if ((rc = upload_flat_structure(f, f.live, t.flat_nodes, t.flat_order, t.flat_always)) != RT_OK) return rc;
+    if ((rc = f.live.rec.ensure(t.flat_blob.size() * sizeof(RtQuadRec))) != RT_OK) return rc;
+    const rtc::FlatBvhHeader h = f.header(f.live, f.n_nodes, f.live.order, scene->n_spheres);
     std::memcpy(t.flat_blob.data(), &h, sizeof h);
-    RT_HIP_TRY(hipMemcpy(r->quads.p, t.flat_blob.data(), t.flat_blob.size() * sizeof(RtQuadRec), hipMemcpyHostToDevice));
-  } else if (n_quads && (rc = upload(r->quads, t.quads)) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(f.live.rec.p, t.flat_blob.data(), t.flat_blob.size() * sizeof(RtQuadRec), hipMemcpyHostToDevice));
+  } else if (n_quads && (rc = upload(f.live.rec, t.quads)) != RT_OK) return rc;
   {
     std::vector<uint32_t> all(scene->n_spheres);
     for (uint32_t i = 0; i < scene->n_spheres; ++i) all[i] = i;
-    if ((rc = upload(r->all, all)) != RT_OK) return rc;
+    if ((rc = upload(r->sph.all, all)) != RT_OK) return rc;
   }
   pc.mark("scene.upload_tables");
   // textures and sky: resident as 4-byte texels (rt_tables.h build_texels; one dword load per fetch); the caller's RGB8
@@ -575,19 +621,7 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   s->host = *scene;
   s->host.spheres = nullptr; s->host.textures = nullptr; s->host.sky_rgb8 = nullptr;
   rtc::fill_dev_scene(*scene, t, s->dev);
-  s->dev.geom = r->geom.get<const rtc::SphereGeom>(); s->dev.mat = r->mat.get<const rtc::SphereMat>();
-  s->dev.lights = r->lights.get<const uint32_t>();
-  s->dev.tex = r->tex.get<const uint8_t>(); s->dev.sky = r->sky.get<const uint8_t>();
-  s->dev.tex4 = r->tex4.get<const uint32_t>(); s->dev.sky4 = r->sky4.get<const uint32_t>();
-  s->dev.matc = r->matc.get<const rtc::MatCore>(); s->dev.cell_word = r->cell_word.get<const uint32_t>();
-  s->dev.cell_items = r->cell_items.get<const uint16_t>(); s->dev.large = r->large.get<const uint32_t>();
-  s->dev.large_geom = r->large_geom.get<const rtc::SphereGeom>();
-  s->dev.motion = r->n_moving ? r->motion.get<const double>() : nullptr;
-  s->dev.medium = r->n_media ? r->medium.get<const double>() : nullptr;
-  s->dev.quads.rec = r->n_quads ? r->quads.get<const RtQuadRec>() : nullptr;
-  s->dev.quads.lim = r->n_tris ? r->quad_lim.get<const double>() : nullptr;
-  s->dev.n_quads = r->n_quads; s->dev.n_tris = r->n_tris;
-  if (r->n_flat_nodes) { s->dev.quads.rec = r->quads.get<const RtQuadRec>() + 1; s->dev.n_tris |= rtc::FLAT_BVH_BIT; }  // (§22: the header lies in front)
+  r->point(s->dev);
   s->res = std::move(r);
   auto bail = [&](int code) { rt_hip_scene_destroy(s); return code; };
   if ((rc = alloc_launch_state(s)) != RT_OK) return bail(rc);
@@ -651,7 +685,7 @@ template <int... SET> std::array<Megakernel, rtk::KERNEL_KEYS> kernel_table(std:
 struct Kernel { int key = -1; Megakernel fn = nullptr; };
 int select_kernel(const RtHipScene* s, bool has_lights, bool lds_tables, bool wide, bool accum, Kernel* out) {
   static const std::array<Megakernel, rtk::KERNEL_KEYS> table = kernel_table(std::make_integer_sequence<int, rtk::KERNEL_SETS - 1>());
-  const int key = (s->res->n_quads ? rtk::KEY_QUADS : 0) | (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
+  const int key = (s->res->flat.n_quads ? rtk::KEY_QUADS : 0) | (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
                   (s->dev.lens_r != 0.0 ? rtk::KEY_LENS : 0) | (accum ? rtk::KEY_ACCUM : 0) | (wide ? rtk::KEY_WIDE : 0) | (has_lights ? rtk::KEY_HL : 0) |
                   (s->res->simple_colour ? rtk::KEY_SIMPLE : 0) | (lds_tables ? rtk::KEY_LDS : 0);
   if (!rtk::kernel_key_valid(key)) {
@@ -733,7 +767,7 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
     return bytes(0.0) <= avail;  // (the smallest pools fit)
   };
   const rtk::LdsLayout no_pools = rtk::lds_layout(s->host.n_spheres, G.n_cells, G.n_items, true, false);
-  bool lds_tables = !G.wide && !s->res->n_quads && no_pools.total <= rtk::LDS_TABLES_MAX_BYTES;  // (the QUADS kernels exist with tables in L2 only)
+  bool lds_tables = !G.wide && !s->res->flat.n_quads && no_pools.total <= rtk::LDS_TABLES_MAX_BYTES;  // (the QUADS kernels exist with tables in L2 only)
   if (has_lights) {
     const size_t fixed = rtc::LIGHT_CENTRES_LDS_MAX * 24u;
     double margin = 0.0;
@@ -856,8 +890,8 @@ int launch_frame(RtHipScene* s, const RtRowTiles* tiles, void* d_rgb8, void* d_l
   if (s->opt.variant == 1) {  // brute-force arm: no grid, every sphere in the `large` list (object order)
     std::memset(&ka.sc.grid, 0, sizeof ka.sc.grid);
     ka.sc.grid.n_large = s->host.n_spheres;
-    ka.sc.large = s->res->all.get<const uint32_t>();
-    ka.sc.large_geom = s->res->geom.get<const rtc::SphereGeom>();
+    ka.sc.large = s->res->sph.all.get<const uint32_t>();
+    ka.sc.large_geom = s->res->sph.live.geom.get<const rtc::SphereGeom>();
     ka.sc.n_tris &= ~rtc::FLAT_BVH_BIT;  // (§22: and every flat primitive in file order, the full scan)
   }
   ka.out_rgb8 = (uint8_t*)d_rgb8; ka.out_linear = (float*)d_linear; ka.counters = s->counters.get<unsigned long long>();
@@ -1198,23 +1232,23 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!s || !key) return -1;
   if (!std::strcmp(key, "n_spheres")) return (int64_t)s->host.n_spheres;
   if (!std::strcmp(key, "n_lights")) return (int64_t)s->dev.n_lights;
-  if (!std::strcmp(key, "grid_cells")) return (int64_t)s->res->grid.n_cells;       // padded cell table (8 B each; wide tables: 16 B)
-  if (!std::strcmp(key, "grid_items")) return (int64_t)s->res->grid.n_items;       // u16 each (wide tables: u32)
-  if (!std::strcmp(key, "grid_wide")) return (int64_t)s->res->grid.wide;           // 1: 32-bit item lists (more than 65 535 spheres)
-  if (!std::strcmp(key, "grid_large")) return (int64_t)s->res->grid.n_large;
+  if (!std::strcmp(key, "grid_cells")) return (int64_t)s->res->sph.live.grid.n_cells;       // padded cell table (8 B each; wide tables: 16 B)
+  if (!std::strcmp(key, "grid_items")) return (int64_t)s->res->sph.live.grid.n_items;       // u16 each (wide tables: u32)
+  if (!std::strcmp(key, "grid_wide")) return (int64_t)s->res->sph.live.grid.wide;           // 1: 32-bit item lists (more than 65 535 spheres)
+  if (!std::strcmp(key, "grid_large")) return (int64_t)s->res->sph.live.grid.n_large;
   if (!std::strcmp(key, "texel_bytes")) return (int64_t)s->res->texel_bytes;       // 4-byte texels of textures + sky resident in HBM
   if (!std::strcmp(key, "light_pool_slots")) return (int64_t)s->last_pool_slots;  // of the last launch: records in the pools of light frames /
   if (!std::strcmp(key, "light_base_slots")) return (int64_t)s->last_base_slots;  // colour-map bases, the kernel's dynamic LDS, tables staged in LDS
   if (!std::strcmp(key, "lds_bytes")) return (int64_t)s->last_lds_bytes;
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
-  if (!std::strcmp(key, "triangles")) return (int64_t)s->res->n_tris;      // of "quads", the entries of shape triangle
-  if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->n_flat_nodes;  // nodes of the structure over the flat primitives; 0: none
-  if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat_refits;  // updates applied by refit since the structure was last built
-  if (!std::strcmp(key, "quads")) return (int64_t)s->res->n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
+  if (!std::strcmp(key, "triangles")) return (int64_t)s->res->flat.n_tris;      // of "quads", the entries of shape triangle
+  if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->flat.n_nodes;  // nodes of the structure over the flat primitives; 0: none
+  if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat.refits;  // updates applied by refit since the structure was last built
+  if (!std::strcmp(key, "quads")) return (int64_t)s->res->flat.n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
   if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
   if (!std::strcmp(key, "solids")) return (int64_t)s->res->n_solids;       // spheres of kind RT_MAT_CHECKER or RT_MAT_NOISE
-  if (!std::strcmp(key, "motion")) return (int64_t)s->res->n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
+  if (!std::strcmp(key, "motion")) return (int64_t)s->res->sph.live.n_moving;       // spheres that move over the shutter (rt_hip_scene_create_moving); 0: static
   if (!std::strcmp(key, "lens")) return s->dev.lens_r != 0.0 ? 1 : 0;    // 1: a thin lens is set (rt_hip_set_lens), 0: the pinhole
   if (!std::strcmp(key, "accum_samples")) return (int64_t)s->prog.samples;
   if (!std::strcmp(key, "temporal_surface")) return s->tp.surface ? 1 : 0;
@@ -1228,7 +1262,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
     const RtHipScene::Adaptive::Round& r = s->ad.rounds[i];
     return f[15] == 't' ? (int64_t)r.tiles : (f[15] == 's' ? (int64_t)r.spp : (int64_t)std::llround(r.kernel_ms * 1000.0));
   }  // samples per pixel in the scene's accumulator (rt_hip_refine_to_host)
-  if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->res->grid.n_cells * (s->res->grid.wide ? 16u : 8u) + (size_t)s->res->grid.n_items * (s->res->grid.wide ? 4u : 2u));
+  if (!std::strcmp(key, "table_bytes")) return (int64_t)((size_t)s->host.n_spheres * (sizeof(rtc::SphereGeom) + sizeof(rtc::MatCore)) + (size_t)s->res->sph.live.grid.n_cells * (s->res->sph.live.grid.wide ? 16u : 8u) + (size_t)s->res->sph.live.grid.n_items * (s->res->sph.live.grid.wide ? 4u : 2u));
   return -1;
 }
 
@@ -1422,7 +1456,7 @@ extern "C" int rt_hip_render_aovs(RtHipScene* s, const RtRowTiles* tiles, uint32
   const int features = (s->res->n_solids ? rtk::KEY_SOLID : 0) | (s->dev.medium ? rtk::KEY_MEDIUM : 0) | (s->dev.motion ? rtk::KEY_MOTION : 0) |
                        (s->dev.lens_r != 0.0 ? rtk::KEY_LENS : 0);
   static const std::array<AovKernel, 16> quads_table = aov_quads_kernels(std::make_integer_sequence<int, 16>());
-  hipLaunchKernelGGL((s->res->n_quads ? quads_table : table)[features / rtk::KEY_LENS], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
+  hipLaunchKernelGGL((s->res->flat.n_quads ? quads_table : table)[features / rtk::KEY_LENS], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, n_samples, (float4*)d_aov);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -1513,7 +1547,7 @@ extern "C" int rt_hip_render_surface(RtHipScene* s, const RtRowTiles* tiles, voi
   using SurfaceKernel = void (*)(const rtc::DevScene, uint4*);
   static const SurfaceKernel table[8] = {rtk::rt_surface<false, false>, rtk::rt_surface<true, false>, rtk::rt_surface<false, true>, rtk::rt_surface<true, true>,
                                          rtk::rt_surface_quads<false, false>, rtk::rt_surface_quads<true, false>, rtk::rt_surface_quads<false, true>, rtk::rt_surface_quads<true, true>};
-  hipLaunchKernelGGL(table[(s->dev.motion ? 1 : 0) | (s->dev.medium ? 2 : 0) | (s->res->n_quads ? 4 : 0)], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, (uint4*)d_surface);
+  hipLaunchKernelGGL(table[(s->dev.motion ? 1 : 0) | (s->dev.medium ? 2 : 0) | (s->res->flat.n_quads ? 4 : 0)], px_grid(s), dim3(16, 16), 0, (hipStream_t)stream, s->dev, (uint4*)d_surface);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
@@ -1647,7 +1681,7 @@ extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t fram
     }
   }
   if (s->tp.surface && n_sph) {  // each sphere's centre now minus its centre in the tables the previous temporal frame rendered with
-    const std::vector<double>& now = s->res->mid;
+    const std::vector<double>& now = s->res->sph.mid;
     const bool have = s->tp.valid && s->tp.mid.size() == now.size();
     s->tp.disp_host.resize(now.size());
     for (size_t i = 0; i < now.size(); ++i) s->tp.disp_host[i] = have ? now[i] - s->tp.mid[i] : 0.0;
@@ -1671,7 +1705,7 @@ extern "C" int rt_hip_render_frame_temporal_to_host(RtHipScene* s, uint32_t fram
   s->tp.cur = cur;
   s->tp.valid = true;
   scene_camera(s, s->tp.cam);
-  if (s->tp.surface) s->tp.mid = s->res->mid;
+  if (s->tp.surface) s->tp.mid = s->res->sph.mid;
   return RT_OK;
 }
 
@@ -1800,18 +1834,13 @@ int rt_hip_scene_warm(RtHipScene* s, hipStream_t stream) {
 
 // ------------------------------------------------------------------------------ moving the spheres of a resident scene
 namespace {
-// Point a scene (or a view) at its resident's current tables and start over what was derived from the old ones: the launch
-// configuration (as creation derives it), the learned tile order, the progressive accumulator with its cached AOVs, the adaptive rounds.
-int adopt_tables(RtHipScene* s) {
-  const RtHipScene::Resident& r = *s->res;
-  s->dev.grid = r.grid;
-  s->dev.geom = r.geom.get<const rtc::SphereGeom>();
-  s->dev.cell_word = r.cell_word.get<const uint32_t>();
-  s->dev.cell_items = r.cell_items.get<const uint16_t>();
-  s->dev.large = r.large.get<const uint32_t>();
-  s->dev.large_geom = r.large_geom.get<const rtc::SphereGeom>();
-  s->dev.motion = r.n_moving ? r.motion.get<const double>() : nullptr;
-  if (r.n_quads) s->dev.quads.rec = r.quads.get<const RtQuadRec>() + (r.n_flat_nodes ? 1 : 0);  // (rt_hip_scene_update_flats swaps the records; §22: the header lies in front)
+// Point a scene (or a view) at its resident's live tables and start over what was derived from the old ones: the launch
+// configuration (as creation derives it), the learned tile order, the progressive accumulator with its cached AOVs, the adaptive rounds;
+// and where the flat primitives moved, the temporal history (rt_hip_reproject_surface takes a flat id as "not displaced": a moved flat
+// primitive is not followed through the filter)
+int adopt_tables(RtHipScene* s, Moved what) {
+  if (what == Moved::flats) s->tp.reset();
+  s->res->point(s->dev);
   s->order.forget();
   s->prog.reset();
   s->ad.reset();
@@ -1823,11 +1852,10 @@ int scene_update(RtHipScene* s, const double* center, const double* center1, boo
   if (!s || (!center && s->host.n_spheres)) return fail(RT_ERR_INVALID, "null argument");
   if (!views_follow && s->res.use_count() > 1)
     return fail(RT_ERR_INVALID, "rt_hip_scene_update_spheres: the scene's tables are shared with a view (a group updates through rt_hip_group_update_spheres)");
-  RT_HIP_TRY(hipSetDevice(s->device));
-  if (s->n_launches && s->in_flight) { RT_HIP_TRY(hipStreamSynchronize(s->last_stream)); s->in_flight = false; }
-  if (!rtp::tl_in_group) rtp::reset();
-  rtp::Clock pc;
-  RtHipScene::Resident& r = *s->res;
+  int rc;
+  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  rtp::Clock pc = rtp::begin();
+  RtHipScene::Resident::Spheres& r = s->res->sph;
   const uint32_t n = s->host.n_spheres;
   // the host's part: the spheres at their new centres, the motion rows, the plan of the grid (rt_tables.h: creation's own code)
   std::vector<RtSphere>& next = r.next_spheres;
@@ -1847,32 +1875,31 @@ int scene_update(RtHipScene* s, const double* center, const double* center1, boo
   if (j.all_large) std::memset(&j.G, 0, sizeof j.G);
   pc.mark("update.host_plan");
   const uint32_t inner = j.all_large ? 0u : rtgb::inner_cells(j.G);
-  auto room = [](DevBuf& b, size_t bytes) { return b.ensure(bytes ? bytes : 16); };
-  int rc;
-  RtHipScene::Resident::Scratch& gb = r.gb;
+  RtHipScene::Resident::Spheres::Scratch& gb = r.scratch;
+  RtHipScene::Resident::Spheres::Tables& spare = r.spare;
   if ((rc = room(gb.centre, (size_t)n * 24)) != RT_OK || (rc = room(gb.plan_large, n)) != RT_OK || (rc = room(gb.range, (size_t)n * sizeof(rtc::GridRange))) != RT_OK ||
       (rc = room(gb.lflag, (size_t)n * 4)) != RT_OK || (rc = room(gb.lpos, (size_t)n * 4)) != RT_OK || (rc = room(gb.count, (size_t)inner * 4)) != RT_OK ||
       (rc = room(gb.start, (size_t)inner * 4)) != RT_OK || (rc = room(gb.cursor, (size_t)inner * 4)) != RT_OK ||
       (rc = room(gb.block_sum, (rtgb::scan_blocks(std::max<size_t>(n, inner)) + 1) * 8)) != RT_OK || (rc = room(gb.counts, sizeof(rtgb::Counts))) != RT_OK ||
-      (rc = room(r.spare.geom, (size_t)n * sizeof(rtc::SphereGeom))) != RT_OK || (t.n_moving && (rc = room(r.spare.motion, (size_t)n * 32)) != RT_OK))
+      (rc = room(spare.geom, (size_t)n * sizeof(rtc::SphereGeom))) != RT_OK || (t.n_moving && (rc = room(spare.motion, (size_t)n * 32)) != RT_OK))
     return rc;
   if (n) RT_HIP_TRY(hipMemcpy(gb.centre.p, center, (size_t)n * 24, hipMemcpyHostToDevice));  // (the centres travel once)
   if (!j.all_large) RT_HIP_TRY(hipMemcpy(gb.plan_large.p, plan.is_large.data(), n, hipMemcpyHostToDevice));
   if (t.n_moving) {  // (uploaded from storage that lives as long as the scene)
     r.keep_motion.assign(t.motion.begin(), t.motion.end());
-    RT_HIP_TRY(hipMemcpy(r.spare.motion.p, r.keep_motion.data(), (size_t)n * 32, hipMemcpyHostToDevice));
+    RT_HIP_TRY(hipMemcpy(spare.motion.p, r.keep_motion.data(), (size_t)n * 32, hipMemcpyHostToDevice));
   }
   pc.mark("update.upload");
   j.n = n;
   for (int k = 0; k < 3; ++k) j.cell_w[k] = plan.cell_w[k];
   j.m = plan.m; j.large_cell_limit = gp.large_cell_limit;
-  j.centre = gb.centre.get<const double>(); j.old_geom = r.geom.get<const rtc::SphereGeom>();
-  j.motion = t.n_moving ? r.spare.motion.get<const double>() : nullptr;
+  j.centre = gb.centre.get<const double>(); j.old_geom = r.live.geom.get<const rtc::SphereGeom>();
+  j.motion = t.n_moving ? spare.motion.get<const double>() : nullptr;
   j.plan_large = gb.plan_large.get<const uint8_t>();
   j.range = gb.range.get<rtc::GridRange>(); j.lflag = gb.lflag.get<uint32_t>(); j.lpos = gb.lpos.get<uint32_t>();
   j.count = gb.count.get<uint32_t>(); j.start = gb.start.get<uint32_t>(); j.cursor = gb.cursor.get<uint32_t>();
   j.block_sum = gb.block_sum.get<unsigned long long>(); j.counts = gb.counts.get<rtgb::Counts>();
-  j.geom = r.spare.geom.get<rtc::SphereGeom>();
+  j.geom = spare.geom.get<rtc::SphereGeom>();
   rtgb::Counts cnt;
   RT_HIP_TRY(rtgb::count(j, nullptr));
   RT_HIP_TRY(hipMemcpy(&cnt, gb.counts.p, sizeof cnt, hipMemcpyDeviceToHost));  // the one readback: item total, fullest cell, `large` count
@@ -1887,37 +1914,34 @@ int scene_update(RtHipScene* s, const double* center, const double* center1, boo
   if (!j.all_large && !wide && (cnt.max_count > rtc::CELL_MAX_COUNT || cnt.n_items >= rtc::CELL_START_MASK)) wide = true;
   pc.mark("update.count_kernels_and_readback");
   j.G.n_items = (uint32_t)cnt.n_items; j.G.n_large = (uint32_t)cnt.n_large; j.G.wide = (!j.all_large && wide) ? 1u : 0u;
-  if ((rc = check_wide_tables(j.G.wide, r.n_media, r.n_solids, r.n_quads != 0)) != RT_OK) return rc;
-  if ((rc = room(r.spare.cell_word, (size_t)j.G.n_cells * (j.G.wide ? 16u : 8u))) != RT_OK || (rc = room(r.spare.cell_items, (size_t)j.G.n_items * (j.G.wide ? 4u : 2u))) != RT_OK ||
+  if ((rc = check_wide_tables(j.G.wide, s->res->n_media, s->res->n_solids, s->res->flat.n_quads != 0)) != RT_OK) return rc;
+  if ((rc = room(spare.cell_word, (size_t)j.G.n_cells * (j.G.wide ? 16u : 8u))) != RT_OK || (rc = room(spare.cell_items, (size_t)j.G.n_items * (j.G.wide ? 4u : 2u))) != RT_OK ||
       (rc = room(gb.raw_items, (size_t)j.G.n_items * 4)) != RT_OK || (rc = room(gb.raw_cell, (size_t)j.G.n_items * 4)) != RT_OK ||
-      (rc = room(r.spare.large, (size_t)j.G.n_large * 4)) != RT_OK || (rc = room(r.spare.large_geom, (size_t)j.G.n_large * sizeof(rtc::SphereGeom))) != RT_OK)
+      (rc = room(spare.large, (size_t)j.G.n_large * 4)) != RT_OK || (rc = room(spare.large_geom, (size_t)j.G.n_large * sizeof(rtc::SphereGeom))) != RT_OK)
     return rc;
   j.raw_items = gb.raw_items.get<uint32_t>(); j.raw_cell = gb.raw_cell.get<uint32_t>();
-  j.cell_word = r.spare.cell_word.get<uint32_t>(); j.cell_items = r.spare.cell_items.p;
-  j.large = r.spare.large.get<uint32_t>(); j.large_geom = r.spare.large_geom.get<rtc::SphereGeom>();
+  j.cell_word = spare.cell_word.get<uint32_t>(); j.cell_items = spare.cell_items.p;
+  j.large = spare.large.get<uint32_t>(); j.large_geom = spare.large_geom.get<rtc::SphereGeom>();
   RT_HIP_TRY(rtgb::tables(j, cnt.n_items, cnt.n_large, j.G.wide != 0u, nullptr));
   RT_HIP_TRY(hipDeviceSynchronize());
   pc.mark("update.table_kernels");
-  // every table is built: swap them in (nothing above changed what the scene renders with)
-  r.geom.swap(r.spare.geom); r.cell_word.swap(r.spare.cell_word); r.cell_items.swap(r.spare.cell_items);
-  r.large.swap(r.spare.large); r.large_geom.swap(r.spare.large_geom);
-  if (t.n_moving) r.motion.swap(r.spare.motion);
-  r.n_moving = t.n_moving;
-  r.grid = j.G;
+  // every table is built: swap the generation in (nothing above changed what the scene renders with)
+  spare.n_moving = t.n_moving;
+  spare.grid = j.G;
+  std::swap(r.live, spare);  // (the motion buffers change hands too, moving tables or not: Tables::motion)
   r.spheres.swap(r.next_spheres);
   r.set_mid(t.motion);
-  rc = adopt_tables(s);
+  rc = adopt_tables(s, Moved::spheres);
   pc.mark("update.configuration");
   return rc;
 }
 }  // namespace
 
-// a view follows its scene's update (internal; rt_hip_group_update_spheres): the tables it shares have been rebuilt
-int rt_hip_scene_view_follow(RtHipScene* view) {
+// a view follows its scene's update (internal; rt_hip_group_update_spheres, rt_hip_group_update_flats): the tables it shares have been replaced
+int rt_hip_scene_view_follow(RtHipScene* view, Moved what) {
   if (!view) return fail(RT_ERR_INVALID, "null argument");
-  RT_HIP_TRY(hipSetDevice(view->device));
-  if (view->n_launches && view->in_flight) { RT_HIP_TRY(hipStreamSynchronize(view->last_stream)); view->in_flight = false; }
-  return adopt_tables(view);
+  if (const int rc = make_current_and_drain(view)) return rc;
+  return adopt_tables(view, what);
 }
 
 extern "C" int rt_hip_scene_update_spheres(RtHipScene* s, const double* center, const double* center1) {
@@ -1926,127 +1950,101 @@ extern "C" int rt_hip_scene_update_spheres(RtHipScene* s, const double* center, 
 
 // ------------------------------------------------------------------------------ moving the flat primitives of a resident scene
 namespace {
-// a scene (or a view) takes over the records and the structure its resident now holds: what adopt_tables starts over, and the temporal
-// history (rt_hip_reproject_surface takes a flat id as "not displaced": a moved flat primitive is not followed through the filter)
-int adopt_flats(RtHipScene* s) {
-  s->tp.reset();
-  return adopt_tables(s);
-}
-
 // views_follow: the caller (the group) re-points the views that share this scene's tables itself
 int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags, bool views_follow) {
   if (!s || !quv) return fail(RT_ERR_INVALID, "null argument");
   if (flags & ~(RT_UPDATE_FLATS_REBUILD | RT_UPDATE_FLATS_DEVICE)) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: unknown flag");
-  RtHipScene::Resident& r = *s->res;
-  if (!r.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene has no flat primitive");
-  if (n_quads != r.n_quads)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(r.n_quads) + " flat primitives");
+  RtHipScene::Resident::Flats& f = s->res->flat;
+  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene has no flat primitive");
+  if (n_quads != f.n_quads)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
   if (!views_follow && s->res.use_count() > 1)
     return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene's tables are shared with a view (a group updates through rt_hip_group_update_flats)");
   const bool on_device = (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
   if (on_device)
     if (const int refused = check_aligned(quv, 8, "rt_hip_scene_update_flats: quv must be 8-byte aligned")) return refused;
-  RT_HIP_TRY(hipSetDevice(s->device));
-  if (s->n_launches && s->in_flight) { RT_HIP_TRY(hipStreamSynchronize(s->last_stream)); s->in_flight = false; }
-  if (!rtp::tl_in_group) rtp::reset();
-  rtp::Clock pc;
-  const uint32_t n = n_quads;
-  const bool bvh = r.n_flat_nodes != 0u;
-  bool rebuild = bvh && (flags & RT_UPDATE_FLATS_REBUILD) != 0u;
-  auto room = [](DevBuf& b, size_t bytes) { return b.ensure(bytes ? bytes : 16); };
   int rc;
-  if ((rc = room(r.fspare.quads, ((size_t)n + (bvh ? 1u : 0u)) * sizeof(RtQuadRec))) != RT_OK || (rc = room(r.fb.status, sizeof(rtfb::Status))) != RT_OK ||
-      (!on_device && (rc = room(r.fb.quv, (size_t)n * 72)) != RT_OK) ||
-      (bvh && ((rc = room(r.fb.box, (size_t)n * 48)) != RT_OK || (rc = room(r.fspare.flat_nodes, (size_t)r.n_flat_nodes * sizeof(rtc::FlatNode))) != RT_OK)))
+  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  rtp::Clock pc = rtp::begin();
+  const uint32_t n = n_quads;
+  const bool bvh = f.n_nodes != 0u;
+  bool rebuild = bvh && (flags & RT_UPDATE_FLATS_REBUILD) != 0u;
+  RtHipScene::Resident::Flats::Tables& spare = f.spare;
+  RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
+  if ((rc = room(spare.rec, f.rec_bytes())) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
+      (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK) ||
+      (bvh && ((rc = room(fb.box, (size_t)n * 48)) != RT_OK || (rc = room(spare.nodes, (size_t)f.n_nodes * sizeof(rtc::FlatNode))) != RT_OK)))
     return rc;
-  if (!on_device) RT_HIP_TRY(hipMemcpy(r.fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
+  if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
   pc.mark("update_flats.upload");
-  RtQuadRec* const spare_rec = r.fspare.quads.get<RtQuadRec>() + (bvh ? 1 : 0);
-  const double* const d_lim = r.n_tris ? r.quad_lim.get<const double>() : nullptr;
   rtfb::Job j;
   j.n = n;
-  j.quv = on_device ? quv : r.fb.quv.get<const double>();
-  j.lim = d_lim;
-  j.rec = spare_rec;
-  j.status = r.fb.status.get<rtfb::Status>();
+  j.quv = on_device ? quv : fb.quv.get<const double>();
+  j.lim = f.dev_lim();
+  j.rec = f.first_rec(spare);
+  j.status = fb.status.get<rtfb::Status>();
   if (bvh) {
-    const rtc::FlatTopology& tp = r.flat_topo;
-    j.boxed = r.flat_boxed.get<const uint32_t>(); j.box = r.fb.box.get<double>();
-    j.n_nodes = r.n_flat_nodes; j.n_run = tp.n_run; j.n_leaves = (uint32_t)tp.leaves.size();
-    j.live_nodes = r.flat_nodes.get<const rtc::FlatNode>(); j.order = r.flat_order.get<const uint32_t>();
-    j.leaves = r.flat_leaves.get<const uint32_t>(); j.level_nodes = r.flat_levels.get<const uint32_t>();
+    const rtc::FlatTopology& tp = f.topo;
+    j.boxed = f.boxed.get<const uint32_t>(); j.box = fb.box.get<double>();
+    j.n_nodes = f.n_nodes; j.n_run = tp.n_run; j.n_leaves = (uint32_t)tp.leaves.size();
+    j.live_nodes = f.live.nodes.get<const rtc::FlatNode>(); j.order = f.live.order.get<const uint32_t>();
+    j.leaves = f.leaves.get<const uint32_t>(); j.level_nodes = f.levels.get<const uint32_t>();
     j.level_start = tp.level_start.data(); j.n_levels = (uint32_t)tp.level_start.size() - 1u;
-    j.nodes = r.fspare.flat_nodes.get<rtc::FlatNode>();
+    j.nodes = spare.nodes.get<rtc::FlatNode>();
   }
-  rtc::FlatBvhHeader& h = r.keep_flat_header;  // (the staging of its upload: it lives as long as the scene)
-  auto put_header = [&](const DevBuf& nodes, uint32_t n_nodes, const DevBuf& order) {
-    std::memset(&h, 0, sizeof h);
-    h.nodes = nodes.get<const rtc::FlatNode>(); h.order = order.get<const uint32_t>();
-    h.rec = spare_rec; h.lim = d_lim;
-    h.n_nodes = n_nodes; h.n_quads = n; h.id_base = s->host.n_spheres;
-    return hipMemcpy(r.fspare.quads.p, &h, sizeof h, hipMemcpyHostToDevice);
+  // the spare's header: its own records and nodes, and the order table that goes live with them
+  auto put_header = [&](uint32_t n_nodes, const DevBuf& order) {
+    f.keep_header = f.header(spare, n_nodes, order, s->host.n_spheres);
+    return hipMemcpy(spare.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice);
   };
   RT_HIP_TRY(rtfb::prepare(j, nullptr));
   if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
     RT_HIP_TRY(rtfb::refit(j, nullptr));
-    RT_HIP_TRY(put_header(r.fspare.flat_nodes, r.n_flat_nodes, r.flat_order));  // the spare's header: its own records, the nodes that go live with it
+    RT_HIP_TRY(put_header(f.n_nodes, f.live.order));
   }
   rtfb::Status st;
-  RT_HIP_TRY(hipMemcpy(&st, r.fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the first bad entry of each class, changed flags
+  RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the first bad entry of each class, changed flags
   pc.mark("update_flats.kernels_and_readback");
   if (st.bad_finite != rtfb::NONE || st.bad_degenerate != rtfb::NONE) {  // (creation's loop stops at the first bad entry: the lowest index wins)
     if (st.bad_finite < st.bad_degenerate) return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + ": q, u and v must be finite");
     return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)");
   }
   if (bvh && st.mismatch) rebuild = true;  // an entry became a needle, crossed 2^40, or stopped being one: the order table is another
-  uint32_t n_nodes = r.n_flat_nodes;
-  uint32_t n_always = 0;
+  uint32_t n_nodes = f.n_nodes;
   if (rebuild) {  // the host's build_flat_bvh over the host's records, as creation runs it; the records themselves stay the device's
     const double* host_quv = quv;
     if (on_device) {
-      r.keep_quv.resize(9 * (size_t)n);
-      RT_HIP_TRY(hipMemcpy(r.keep_quv.data(), quv, (size_t)n * 72, hipMemcpyDeviceToHost));
-      host_quv = r.keep_quv.data();
+      f.keep_quv.resize(9 * (size_t)n);
+      RT_HIP_TRY(hipMemcpy(f.keep_quv.data(), quv, (size_t)n * 72, hipMemcpyDeviceToHost));
+      host_quv = f.keep_quv.data();
     }
     rtc::HostTables t;
     t.quads.resize(n);
     for (uint32_t k = 0; k < n; ++k)
       if (rt_quad_prepare(host_quv + 9 * (size_t)k, host_quv + 9 * (size_t)k + 3, host_quv + 9 * (size_t)k + 6, &t.quads[k]))
         return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": the host refuses an entry the device accepted");
-    t.quad_lim = r.host_lim;
+    t.quad_lim = f.host_lim;
     const std::string why = rtc::build_flat_bvh(t);
     if (!why.empty()) return fail(RT_ERR_INVALID, why);
-    r.keep_flat_nodes.assign(t.flat_nodes.begin(), t.flat_nodes.end());
-    r.keep_flat_order.assign(t.flat_order.begin(), t.flat_order.end());
-    n_nodes = (uint32_t)r.keep_flat_nodes.size();
-    n_always = t.flat_always;
+    f.keep_nodes.assign(t.flat_nodes.begin(), t.flat_nodes.end());
+    f.keep_order.assign(t.flat_order.begin(), t.flat_order.end());
+    n_nodes = (uint32_t)f.keep_nodes.size();
     pc.mark("update_flats.host_build");
-    if ((rc = room(r.fspare.flat_nodes, (size_t)n_nodes * sizeof(rtc::FlatNode))) != RT_OK || (rc = room(r.fspare.flat_order, (size_t)n * 4)) != RT_OK) return rc;
-    RT_HIP_TRY(hipMemcpy(r.fspare.flat_nodes.p, r.keep_flat_nodes.data(), (size_t)n_nodes * sizeof(rtc::FlatNode), hipMemcpyHostToDevice));
-    RT_HIP_TRY(hipMemcpy(r.fspare.flat_order.p, r.keep_flat_order.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    RT_HIP_TRY(put_header(r.fspare.flat_nodes, n_nodes, r.fspare.flat_order));
-    if ((rc = upload_flat_topology(r, r.keep_flat_nodes, r.keep_flat_order, n_always)) != RT_OK) return rc;
+    if ((rc = upload_flat_structure(f, spare, f.keep_nodes, f.keep_order, t.flat_always)) != RT_OK) return rc;
+    RT_HIP_TRY(put_header(n_nodes, spare.order));
     pc.mark("update_flats.upload_structure");
   }
   RT_HIP_TRY(hipDeviceSynchronize());
   // everything is built: swap it in (nothing above changed what the scene renders with)
-  r.quads.swap(r.fspare.quads);
-  if (bvh) r.flat_nodes.swap(r.fspare.flat_nodes);
-  if (rebuild) { r.flat_order.swap(r.fspare.flat_order); r.n_flat_nodes = n_nodes; }
-  r.flat_refits = (bvh && !rebuild) ? r.flat_refits + 1u : 0u;
-  rc = adopt_flats(s);
+  f.live.rec.swap(spare.rec);
+  if (bvh) f.live.nodes.swap(spare.nodes);
+  if (rebuild) { f.live.order.swap(spare.order); f.n_nodes = n_nodes; }
+  f.refits = (bvh && !rebuild) ? f.refits + 1u : 0u;
+  rc = adopt_tables(s, Moved::flats);
   pc.mark("update_flats.configuration");
   return rc;
 }
 }  // namespace
-
-// a view follows its scene's flat update (internal; rt_hip_group_update_flats)
-int rt_hip_scene_view_follow_flats(RtHipScene* view) {
-  if (!view) return fail(RT_ERR_INVALID, "null argument");
-  RT_HIP_TRY(hipSetDevice(view->device));
-  if (view->n_launches && view->in_flight) { RT_HIP_TRY(hipStreamSynchronize(view->last_stream)); view->in_flight = false; }
-  return adopt_flats(view);
-}
 
 extern "C" int rt_hip_scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags) {
   return scene_update_flats(s, quv, n_quads, flags, false);
@@ -2055,7 +2053,8 @@ extern "C" int rt_hip_scene_update_flats(RtHipScene* s, const double* quv, uint3
 // diagnostics: one resident table as the kernels read it
 extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* out, size_t cap, size_t* needed) {
   if (!s || !name) return fail(RT_ERR_INVALID, "null argument");
-  const RtHipScene::Resident& r = *s->res;
+  const RtHipScene::Resident::Spheres::Tables& r = s->res->sph.live;
+  const RtHipScene::Resident::Flats& f = s->res->flat;
   const rtc::GridDesc& G = r.grid;
   const void* src = nullptr;
   size_t bytes = 0;
@@ -2066,11 +2065,11 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "large")) { src = r.large.p; bytes = (size_t)G.n_large * 4; }
   else if (!std::strcmp(name, "geom")) { src = r.geom.p; bytes = (size_t)s->host.n_spheres * sizeof(rtc::SphereGeom); }
   else if (!std::strcmp(name, "large_geom")) { src = r.large_geom.p; bytes = (size_t)G.n_large * sizeof(rtc::SphereGeom); }
-  else if (!std::strcmp(name, "motion")) { src = r.motion.p; bytes = r.n_moving ? (size_t)s->host.n_spheres * 32 : 0; }
-  else if (!std::strcmp(name, "quads")) { src = r.n_flat_nodes ? (const void*)(r.quads.get<const RtQuadRec>() + 1) : r.quads.p; bytes = (size_t)r.n_quads * sizeof(RtQuadRec); }
-  else if (!std::strcmp(name, "quad_lim")) { src = r.quad_lim.p; bytes = r.n_tris ? (size_t)r.n_quads * sizeof(double) : 0; }
-  else if (!std::strcmp(name, "flat_bvh")) { src = r.flat_nodes.p; bytes = (size_t)r.n_flat_nodes * sizeof(rtc::FlatNode); }
-  else if (!std::strcmp(name, "flat_bvh_order")) { src = r.flat_order.p; bytes = r.n_flat_nodes ? (size_t)r.n_quads * sizeof(uint32_t) : 0; }
+  else if (!std::strcmp(name, "motion")) { src = r.n_moving ? r.motion.p : nullptr; bytes = r.n_moving ? (size_t)s->host.n_spheres * 32 : 0; }
+  else if (!std::strcmp(name, "quads")) { src = f.first_rec(f.live); bytes = (size_t)f.n_quads * sizeof(RtQuadRec); }
+  else if (!std::strcmp(name, "quad_lim")) { src = f.lim.p; bytes = f.n_tris ? (size_t)f.n_quads * sizeof(double) : 0; }
+  else if (!std::strcmp(name, "flat_bvh")) { src = f.live.nodes.p; bytes = (size_t)f.n_nodes * sizeof(rtc::FlatNode); }
+  else if (!std::strcmp(name, "flat_bvh_order")) { src = f.live.order.p; bytes = f.n_nodes ? (size_t)f.n_quads * sizeof(uint32_t) : 0; }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
   if (needed) *needed = bytes;
   if (!out) return RT_OK;
@@ -2145,7 +2144,7 @@ extern "C" int rt_hip_walk_probe(RtHipScene* s, const double* d_rays, double* d_
 extern "C" int rt_hip_quad_probe(RtHipScene* s, const double* d_rays, const double* d_closest, uint32_t n, uint32_t first_quad, uint32_t n_quads,
                                  int32_t* d_best, double* d_t, double* d_point, double* d_normal, int32_t* d_front, void* stream) {
   if (!s || !d_rays || !d_closest || !d_best || !d_t || !d_point || !d_normal || !d_front) return fail(RT_ERR_INVALID, "null argument");
-  if (first_quad > s->res->n_quads || n_quads > s->res->n_quads - first_quad) return fail(RT_ERR_INVALID, "the range lies outside the scene's quads");
+  if (first_quad > s->res->flat.n_quads || n_quads > s->res->flat.n_quads - first_quad) return fail(RT_ERR_INVALID, "the range lies outside the scene's quads");
   if (!n) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
   hipLaunchKernelGGL(rtk::rt_quad_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, d_rays, d_closest, n, first_quad, n_quads,

@@ -570,7 +570,7 @@ extern "C" int rt_hip_group_update_spheres(RtHipGroup* g, const double* center, 
   if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_update_spheres: a submitted frame is uncollected");
   for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad centres change no rank)
     int rc = scene_update(g->scene[r], center, center1, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r]);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::spheres);
     if (rc != RT_OK) return rc;
   }
   if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
@@ -587,7 +587,7 @@ extern "C" int rt_hip_group_update_flats(RtHipGroup* g, const double* quv, uint3
       if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_update_flats: device memory serves the ranks of one device only");
   for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad geometry changes no rank)
     int rc = scene_update_flats(g->scene[r], quv, n_quads, flags, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow_flats(g->scene2[r]);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
     if (rc != RT_OK) return rc;
   }
   if (!g->device.empty()) (void)hipSetDevice(g->device[0]);

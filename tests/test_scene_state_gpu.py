@@ -24,6 +24,9 @@ SMALL = [((0.0, 0.5, 0.0), 0.5, {"Glass": {"index_of_refraction": 1.5}}),
          ((-2.0, 0.35, -0.3), 0.35, {"Lambertian": {"albedo": [0.3, 0.3, 0.8]}})]
 CENTRES = np.array([(0.0, -100.0, 0.0)] + [c for c, _, _ in SMALL], np.float64)
 MOVED = CENTRES + np.array([(0.0, 0.0, 0.0)] + [(0.3 * (-1) ** i, 0.05 * i, -0.2) for i in range(len(SMALL))])
+# the update_flats case alone adds a flat primitive: a red parallelogram just above the ground, between the spheres and the camera (q, u, v)
+QUV = np.array([[2.2, 0.05, 1.2, 0.0, 0.0, 1.0, 1.2, 0.0, 0.0]], np.float64)
+QUV_MOVED = QUV + np.array([[-0.4, 0.0, 0.3, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]])
 
 
 def _text(centres=CENTRES):
@@ -33,6 +36,14 @@ def _text(centres=CENTRES):
     return json.dumps({"width": W, "height": H, "samples_per_pixel": SPP, "max_depth": DEPTH, "sky": {"texture": ""},
                        "camera": {"look_from": dict(zip("xyz", LOOK_FROM)), "look_at": dict(zip("xyz", LOOK_AT)), "vup": dict(zip("xyz", VUP)),
                                   "vfov": VFOV, "aspect": W / H}, "objects": objs})
+
+
+def _quad(abi, quv):
+    """QUV or QUV_MOVED as the one Lambertian abi.RtQuad a scene is created with"""
+    q = abi.RtQuad(kind=abi.RT_MAT_LAMBERTIAN, reserved=abi.RT_QUAD_SHAPE_PARALLELOGRAM)
+    q.q[:], q.u[:], q.v[:] = quv[0, 0:3], quv[0, 3:6], quv[0, 6:9]
+    q.albedo[:] = [0.9, 0.1, 0.1]
+    return [q]
 
 
 @pytest.fixture(scope="module")
@@ -84,6 +95,7 @@ EVENTS = {
     "option_tile_batch": (_option("tile_batch", 1), KEPT, KEPT, KEPT),
     "option_light_nest_pool": (_option("light_nest_pool", 0), KEPT, KEPT, KEPT),
     "update_spheres": (lambda host, gs, sc: gs.update_spheres(MOVED), DROPPED, DROPPED, KEPT),
+    "update_flats": (lambda host, gs, sc: gs.update_flats(QUV_MOVED), DROPPED, DROPPED, DROPPED),    # (its scene alone has a quad)
     "new_order_key": (_new_order_key, KEPT, KEPT, KEPT),
     "temporal_surface_on": (lambda host, gs, sc: gs.temporal_surface(True), KEPT, KEPT, DROPPED),
     "temporal_surface_unchanged": (lambda host, gs, sc: gs.temporal_surface(False, 0.5), KEPT, KEPT, KEPT),
@@ -111,7 +123,7 @@ def _fill(gs):
 def test_an_event_drops_the_caches_its_row_names_and_no_other(pkg, host, abi, torch_cuda, event):
     apply, accum, adaptive, history = EVENTS[event]
     sc = host.Scene.loads(_text())
-    gs = pkg.hip.HipScene(sc.ptr, 0)
+    gs = pkg.hip.HipScene(sc.ptr, 0, quads=_quad(abi, QUV) if event == "update_flats" else None)
     ref = None
     try:
         before = gs.render_to_host()[0]
@@ -141,6 +153,12 @@ def test_an_event_drops_the_caches_its_row_names_and_no_other(pkg, host, abi, to
             assert not np.array_equal(want, before)     # (the spheres did move in the picture)
             got, want = gs.refine_to_host_denoised(2)[0], ref.refine_to_host_denoised(2)[0]
             assert np.array_equal(got, want), int((got != want).sum())
+        if event == "update_flats":
+            # (tests/test_flat_update_gpu.py compares records and frames at its own sizes; here: the frame behind the dropped state)
+            ref = pkg.hip.HipScene(sc.ptr, 0, quads=_quad(abi, QUV_MOVED))
+            got, want = gs.render_to_host()[0], ref.render_to_host()[0]
+            assert np.array_equal(got, want), int((got != want).sum())
+            assert not np.array_equal(want, before)     # (the quad did move in the picture)
     finally:
         gs.close()
         if ref is not None:
