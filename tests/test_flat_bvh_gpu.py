@@ -177,6 +177,31 @@ def _camera_rays(sc):
     return np.concatenate([np.broadcast_to(o, tgt.shape), tgt - o], axis=2)
 
 
+def surface_rays(sc):
+    """the pixel-centre pinhole rays of the surface record, row by row: (h w) x 6"""
+    w, h = sc.width, sc.height
+    o = np.array(list(sc.cam_origin))
+    u = (np.arange(w) + 0.5) / (w - 1)
+    v = (h - (np.arange(h) + 0.5)) / (h - 1)
+    tgt = np.array(list(sc.cam_lower_left))[None, None, :] + u[None, :, None] * np.array(list(sc.cam_horizontal)) + v[:, None, None] * np.array(list(sc.cam_vertical))
+    return np.concatenate([np.broadcast_to(o, tgt.shape), tgt - o], axis=2).reshape(-1, 6)
+
+
+def walk_witness(sim, flats, rays, id_base):
+    """what the host build's walk does with each ray alone, from its counters: the root's count (0: an inner node), the always-visited
+    entries, and the number of rays rejected at the root (one box test, no entry test), of rays that reach an entry test in a leaf, and
+    of rays that take the out-of-range fallback"""
+    nodes, order, n_always = sim.build(flats)
+    at_root = in_leaf = fallback = 0
+    for r in rays:
+        _, _, cnt = sim.hit(flats, r[None, :], np.array([T_MAX]), True, id_base)
+        assert cnt["rays_bvh"] + cnt["rays_scan"] == 1
+        at_root += cnt["rays_bvh"] == 1 and cnt["box_tests"] == 1 and cnt["entry_tests"] == 0
+        in_leaf += cnt["rays_bvh"] == 1 and cnt["entry_tests"] > 0
+        fallback += cnt["rays_scan"]
+    return dict(nodes=len(nodes), root_count=int(nodes["count"][0]), n_always=n_always, at_root=int(at_root), in_leaf=int(in_leaf), fallback=int(fallback))
+
+
 @pytest.mark.parametrize("name", ["1025", "2048"])
 def test_big_worlds_on_the_host_build(abi, name):
     quv = _big_world(name)

@@ -164,9 +164,12 @@ def test_small_frames_against_the_restatement(pkg, abi, oracle, host, torch_cuda
     gs.close()
 
 
-def _matrix_cfg(hl, medium, solid, moving):
+def _matrix_cfg(hl, medium, solid, moving, mesh=False):
     """a small world for one cell of the QUADS matrix: a floor quad (a Checker in the SOLID cells), a small box, five spheres.  The lit
-    cells keep the sky: under a black one nine tenths of a 2-sample frame are zero, and zeros agree with any reference."""
+    cells keep the sky: under a black one nine tenths of a 2-sample frame are zero, and zeros agree with any reference.  mesh: with
+    test_tri_gpu.TETRA as a "mesh" at object index 3, in front of the box — Lambertian, and the box's Noise in the SOLID cells: 11 flat
+    primitives, 4 of them triangles, so the scene has a limit table and, with more than four entries, a structure with
+    inner nodes (§22)."""
     objs = [
         _quad((-5, -0.5, -5), (10, 0, 0), (0, 0, 10), _chk((0.9, 0.9, 0.9), (0.2, 0.2, 0.2), 1.5) if solid else _lam(0.6, 0.6, 0.6)),
         _obj((0, 0.5, 0), 1.0, _lam(0.8, 0.2, 0.2), (0.2, 0.6, 0.1) if moving else None),
@@ -178,6 +181,9 @@ def _matrix_cfg(hl, medium, solid, moving):
         objs.append(_obj((0, 3.5, 1), 0.8, {"Light": {}}))
     if medium:
         objs.append(_obj((-0.8, -0.2, 1.8), 0.6, _med((0.8, 0.7, 0.6), 2.5)))
+    if mesh:
+        from test_tri_gpu import TETRA, _mesh     # (that module imports this one)
+        objs.insert(3, _mesh(*TETRA, _noi((0.8, 0.7, 0.5), 3.0, "turbulence", 2, 5) if solid else _lam(0.3, 0.7, 0.4)))
     return _cfg(objs)
 
 
@@ -200,15 +206,39 @@ def sweep_key(cell):
     return QUADS | (SOLID if solid else 0) | (MEDIUM if medium else 0) | (MOTION if moving else 0) | (LENS if with_lens else 0) | (HL if hl else 0)
 
 
-def sweep_world(host, cell, width, height, pinhole=False):
+def sweep_world(host, cell, width, height, pinhole=False, mesh=False):
     """(host scene, center1, lens, quads) of one cell at width x height, spp 2, depth 6: _matrix_cfg's world.  pinhole: the same world
-    without the cell's lens."""
+    without the cell's lens.  mesh: the cell's mesh twin (_matrix_cfg), with the cell's seed."""
     hl, with_lens, moving, medium, solid = cell
-    cfg = _matrix_cfg(hl, medium, solid, moving)
+    cfg = _matrix_cfg(hl, medium, solid, moving, mesh)
     if with_lens and not pinhole:
         cfg["camera"].update(aperture=0.5, focus_dist=6.0)
     sc, c1, lens = _load(host, cfg, width, height, 2, 6, seed=2 * SWEEP_CELLS.index(cell))
     return sc, c1, lens, sc.quads()
+
+
+MESH_SWAP = (0.8, 0.0, 1.7)     # from the box's place to the tetrahedron's, along the floor
+
+
+def sweep_mesh_geometries(quads):
+    """(G, G') of a mesh twin's flat primitives as [11, 9] q, u, v rows.  G is the file's.  In G' the tetrahedron's four entries and the
+    box's six have changed places (each group translated by -/+ MESH_SWAP; the floor stays): every leaf box of a structure built over G
+    moves by more than its own size."""
+    assert [int(q.reserved) for q in quads] == [0] + [1] * 4 + [0] * 6, "the floor, the mesh's four triangles, the box's six faces"
+    g = np.array([list(q.q) + list(q.u) + list(q.v) for q in quads], np.float64)
+    moved = g.copy()
+    moved[1:5, :3] -= MESH_SWAP
+    moved[5:11, :3] += MESH_SWAP
+    return g, moved
+
+
+def with_geometry(quads, quv):
+    """a copy of the records with q, u, v from quv's rows"""
+    out = type(quads)()
+    C.memmove(out, quads, C.sizeof(quads))
+    for rec, row in zip(out, quv):
+        rec.q[:], rec.u[:], rec.v[:] = row[0:3].tolist(), row[3:6].tolist(), row[6:9].tolist()
+    return out
 
 
 @pytest.mark.gpu
