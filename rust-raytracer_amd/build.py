@@ -82,7 +82,7 @@ def build_cli(force=False):
     """the `raytracer <config_file> <output_file>` binary (reference main.rs)"""
     out = os.path.join(HERE, "raytracer")
     src = _srcs("csrc/host/main.cpp")
-    deps = src + _srcs("csrc/host/anim_path.h") + [os.path.join(HERE, "librt_host.so"), os.path.join(HERE, "librt_hip.so")]
+    deps = src + _srcs("csrc/host/anim_path.h", "csrc/host/cli_args.h") + [os.path.join(HERE, "librt_host.so"), os.path.join(HERE, "librt_hip.so")]
     if os.path.exists(src[0]) and (force or _newer(out, deps)):
         _run(["g++", *CXXFLAGS, *src, "-o", out, "-L" + HERE, "-lrt_host", "-lrt_hip", "-lpthread", "-Wl,-rpath,$ORIGIN"])
     return out

@@ -8,70 +8,10 @@
 // host buffer) — HIP start-up, table build and scene upload happen before it and are reported under RT_STATS=1.
 // RT_GPUS=N (or "n_gpus" in RtScene) shards the frame over N GPUs inside librt_hip.so (rt_hip_group_*).
 //
-// Superset (SURVEY §8f "animation driver"): `raytracer <config_file> <output_prefix> --frames N
-// [--orbit DEG]` renders N frames to `<output_prefix>_%03d.png` — the file naming main.rs:17
-// keeps commented out and README.md:43-57 / "Make animation" feed to ffmpeg — turning the camera
-// around look_at by DEG per frame (default 360/N).  The scene is uploaded once and stays in HBM;
-// the PNG of frame i is encoded on writer threads (RT_ANIM_WRITERS, default 4) while the GPU renders frame i+1.  With RT_GPUS=G every frame is sharded
-// over the G devices and frames are pipelined two deep (RT_ANIM=sharded, default), or the frames are distributed over the
-// devices, each rendering whole frames (RT_ANIM=frames); RT_STATS=1 prints frames per second and the per-frame kernel / frame / PNG
-// times to stderr (one JSON line).
-//
-// Progressive (`raytracer <config_file> <output_file> --passes K`): the scene's samples per pixel in K contiguous ranges, as even
-// as they come, each added to the scene's accumulator on the GPU (rt_hip_refine_to_host) and the image so far rewritten to
-// <output_file> after every pass (a temporary file in the same directory, then rename: a viewer never sees half a file).  Stderr
-// gets `pass i/K: S samples, kernel X ms`; stdout the same two lines as a one-shot run, `Frame time` over all the passes; the
-// last PNG is the one-shot run's, byte for byte.  One GPU: RT_GPUS > 1 is refused.
-//
-// Adaptive (`raytracer <config_file> <output_file> --adaptive E [--min-spp M]`, M = 16 by default): one adaptive frame
-// (rt_hip_render_adaptive_to_host, DESIGN.md §11) — every pixel tile gets samples until its noise estimate falls below E or it
-// holds the scene's samples per pixel, and each tile is the one-shot frame at its own count, byte for byte.  Stdout as a one-shot
-// run; stderr gets `round i: T tiles at n samples, kernel X ms` per round and what fraction of width x height x spp was traced.
-// One GPU: RT_GPUS > 1 is refused.
-//
-// Denoised (`--denoise`, alone or with `--passes K`): every PNG the run writes is the resolved frame passed through the
-// feature-guided a-trous filter (rt_hip_refine_to_host_denoised, RT_DENOISE_ITERATIONS iterations, the default sigmas; DESIGN.md
-// §12).  The last PNG of `--passes K --denoise` is the `--denoise` run's, byte for byte.  Stdout as a one-shot run.  With --adaptive,
-// or with only one of --frames and --orbit: the usage line.  One GPU: RT_GPUS > 1 is refused.
-//
-// Denoised animation (`--frames N --orbit DEG [--shutter S] --denoise`): the frames of the animation modes below, each
-// tracing a sample range of its own, blended with the previous frame's history where the first-hit surface was on screen one frame ago
-// and filtered spatially (rt_hip_render_frame_temporal_to_host, RT_DENOISE_ITERATIONS iterations) on one resident scene.  The turn per
-// frame must be named: --orbit is required (0 keeps the camera still).  Frame 0 is the `--denoise` one-shot frame, byte for byte.
-// PNGs are written on the writer threads.  One GPU: RT_GPUS > 1 is refused.
-// `--temporal-surface` (DESIGN.md §19; only in this mode) turns on surface tracking: moved spheres keep their history, Metal and Glass
-// pixels get the floor `--temporal-alpha-specular B` on alpha (default RT_TEMPORAL_SURFACE_ALPHA_SPECULAR; needs --temporal-surface).
-// `--temporal-alpha A` (only in this mode) sets alpha_min, the floor everywhere else (default RT_TEMPORAL_ALPHA_MIN, with
-// --temporal-surface RT_TEMPORAL_SURFACE_ALPHA_MIN).  A and B lie in [0, 1]; anything else: the usage line.
-//
-// Thin lens: a scene whose camera has a non-zero "aperture" renders through the lens in every mode above —
-// rt_camera_derive_lens gives the camera on the focus plane and the lens, set next to each other on the resident scene or group
-// (every --frames camera is re-derived so).  RtScene has no lens, so such a one-shot frame goes through a group, not rt_render_rgb8.
-//
-// Motion blur (DESIGN.md §14): a scene whose spheres have "center1" (rt_scene_motion) is created with rt_hip_scene_create_moving /
-// rt_hip_group_create_moving in every mode above, with or without a lens; its one-shot frame goes through a one-frame group too.
-//
-// Quads and boxes (DESIGN.md §20): a scene file that holds a quad or a box (rt_scene_quads) is created with rt_hip_scene_create_quads /
-// rt_hip_group_create_quads in every mode above; its one-shot frame goes through a one-frame group too (RtScene carries no quads).  A
-// quad-free file takes the calls it always took.
-//
-// The structure over the flat primitives (DESIGN.md §22): a file with "flat_bvh": true (rt_scene_flat_bvh) is created with
-// rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh instead, in every mode above; `--flat-bvh` (with any of the modes, or alone)
-// does the same for any file that holds a flat primitive, for A/B runs; on a file without one it changes nothing (there is nothing to build
-// over), and given twice it is refused with the usage line.  The frame is the same in every bit.
-//
-// Moving flat primitives from frame to frame (`--frames N --flat-frames PREFIX`; DESIGN.md §24): frame f takes its flat primitives from the
-// scene file PREFIX%03d.json (only its quads, boxes, triangles and meshes are used; count, shapes and materials must be the base file's —
-// anything else, or an unreadable file, ends the run with a message that names the frame).  The resident scene's flat primitives are moved
-// before every frame (rt_hip_group_update_flats / rt_hip_scene_update_flats: the structure of --flat-bvh is refit on the GPU); as for
-// --shutter no frame is in flight meanwhile, and the next frame's file is read while the frame renders.  Combines with --orbit, --shutter,
-// --flat-bvh, RT_GPUS and RT_ANIM=frames; without --frames, or with --denoise, --passes or --adaptive: the usage line.
-//
-// Moving spheres from frame to frame (`--frames N --shutter S`, 0 <= S <= 1; DESIGN.md §17): a sphere's "center" -> "center1" is its
-// path over the whole animation instead of over one exposure; frame f is exposed from center + dv f / N to center + dv (f + S) / N
-// (anim_path.h), S = 0 giving crisp spheres.  The resident scene's spheres are moved before every frame (rt_hip_group_update_spheres /
-// rt_hip_scene_update_spheres: the grid is rebuilt on the GPU).  A group refuses an update while a frame is in flight, so in this mode
-// frame f is collected before the spheres move for f + 1; its PNG is still written while f + 1 renders.  Only with --frames.
+// The modes beyond the reference's (cli_args.h: the flags, and which may stand together) each have a function below, with the mode's
+// paragraph above it: progressive(), adaptive(), animate() with its three drivers, one_shot().  What every mode shares about a scene
+// file — lens, moving spheres, flat primitives and their structure — is at create(); what every animation driver shares about frame f
+// is Anim::pose() and the two apply()s.
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -85,31 +25,158 @@
 
 #include "../../../include/rt_abi.h"
 #include "anim_path.h"
+#include "cli_args.h"
 
 namespace {
-bool g_flat_bvh = false;  // --flat-bvh
-// the resident scene / group of a scene file: with its quads if it has any, else the calls a quad-free file always took
-int create_scene(const RtSceneFile* sf, int device, RtHipScene** out) {
-  uint32_t n_quads = 0;
-  const RtQuad* quads = rt_scene_quads(sf, &n_quads);
-  if (n_quads && (g_flat_bvh || rt_scene_flat_bvh(sf))) return rt_hip_scene_create_flats_bvh(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, device, out);
-  if (n_quads) return rt_hip_scene_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, device, out);
-  return rt_hip_scene_create_moving(rt_scene_get(sf), rt_scene_motion(sf), device, out);
+using Clock = std::chrono::steady_clock;
+double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+double ms_since(Clock::time_point t) { return ms_between(t, Clock::now()); }
+
+// what a run is made of: the command line and the loaded scene file
+struct Run {
+  const cli::Options& o;
+  RtSceneFile* sf;
+  RtScene* sc;  // rt_scene_get_mut(sf)
+};
+
+// what the run says when it ends early, and its exit status (usage: main.rs:9-12, a normal return; 101: the exit status of a Rust panic)
+int usage(const cli::Options& o) { std::printf("Usage: %s <config_file> <output_file>\n", o.program); return 0; }
+int render_failed(int rc) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
+int write_failed(const char* why) { std::fprintf(stderr, "error writing image: %s\n", why); return 101; }
+// how many GPUs the run asks for: RtScene::n_gpus, else RT_GPUS, else 1 (sc null: before the scene is loaded)
+long gpus_asked(const RtScene* sc) {
+  if (sc && sc->n_gpus) return sc->n_gpus;
+  const char* e = std::getenv("RT_GPUS");
+  return e ? std::strtol(e, nullptr, 10) : 1;
 }
-int create_group(const RtSceneFile* sf, RtHipGroup** out) {
+
+// The resident scene / group of a scene file.  What a scene file may hold beyond the reference's, in every mode:
+// Motion blur (DESIGN.md §14): a scene whose spheres have "center1" (rt_scene_motion) is created with rt_hip_scene_create_moving /
+// rt_hip_group_create_moving, with or without a lens.
+// Quads and boxes (DESIGN.md §20): a scene file that holds a quad or a box (rt_scene_quads) is created with rt_hip_scene_create_quads /
+// rt_hip_group_create_quads.  A quad-free file takes the calls it always took.
+// The structure over the flat primitives (DESIGN.md §22): a file with "flat_bvh": true (rt_scene_flat_bvh) is created with
+// rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh instead; `--flat-bvh` (with any of the modes, or alone)
+// does the same for any file that holds a flat primitive, for A/B runs; on a file without one it changes nothing (there is nothing to build
+// over), and given twice it is refused with the usage line.  The frame is the same in every bit.
+template <class Handle, class Where>
+int create(const Run& r, Where where, Handle** out, int (*moving)(const RtScene*, const double*, Where, Handle**),
+           int (*with_quads)(const RtScene*, const double*, const RtQuad*, uint32_t, Where, Handle**),
+           int (*with_bvh)(const RtScene*, const double*, const RtQuad*, uint32_t, Where, Handle**)) {
   uint32_t n_quads = 0;
-  const RtQuad* quads = rt_scene_quads(sf, &n_quads);
-  if (n_quads && (g_flat_bvh || rt_scene_flat_bvh(sf))) return rt_hip_group_create_flats_bvh(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, 0, out);
-  if (n_quads) return rt_hip_group_create_quads(rt_scene_get(sf), rt_scene_motion(sf), quads, n_quads, 0, out);
-  return rt_hip_group_create_moving(rt_scene_get(sf), rt_scene_motion(sf), 0, out);
+  const RtQuad* quads = rt_scene_quads(r.sf, &n_quads);
+  if (!n_quads) return moving(r.sc, rt_scene_motion(r.sf), where, out);
+  return (r.o.flat_bvh || rt_scene_flat_bvh(r.sf) ? with_bvh : with_quads)(r.sc, rt_scene_motion(r.sf), quads, n_quads, where, out);
 }
+int create_scene(const Run& r, int device, RtHipScene** out) {
+  return create(r, device, out, rt_hip_scene_create_moving, rt_hip_scene_create_quads, rt_hip_scene_create_flats_bvh);
+}
+int create_group(const Run& r, RtHipGroup** out) {  // on RT_GPUS devices (default 1)
+  return create(r, (uint32_t)0, out, rt_hip_group_create_moving, rt_hip_group_create_quads, rt_hip_group_create_flats_bvh);
+}
+
+// Thin lens: a scene whose camera has a non-zero "aperture" renders through the lens in every mode —
+// rt_camera_derive_lens gives the camera on the focus plane and the lens, set next to each other on the resident scene or group
+// (every --frames camera is re-derived so).
+// The scene file's camera with its thin lens, if it has one (aperture != 0): out as rt_camera_derive_lens
+bool lens_camera(const RtSceneFile* sf, double out[20]) {
+  double cam[11], lens[2];
+  rt_scene_camera(sf, cam);
+  rt_scene_lens(sf, lens);
+  if (lens[0] == 0.0) return false;
+  rt_camera_derive_lens(cam, cam + 3, cam + 6, cam[9], cam[10], lens[0], lens[1], out);
+  return true;
+}
+// What progressive() and adaptive() begin with: the scene resident on device 0, through its lens (nothing for a pinhole scene: it keeps
+// RtScene's camera), and the first stdout line (main.rs:18).  0, or the exit status.
+int open_scene(const Run& r, RtHipScene** hs) {
+  double c[20];
+  int rc = create_scene(r, 0, hs);
+  if (rc == RT_OK && lens_camera(r.sf, c)) {
+    rc = rt_hip_set_camera(*hs, c, c + 3, c + 6, c + 9);
+    if (rc == RT_OK) rc = rt_hip_set_lens(*hs, c + 13, c + 16, c[19]);
+  }
+  std::printf("\nRendering %s\n", r.o.output);
+  return rc != RT_OK ? render_failed(rc) : 0;
+}
+std::vector<uint8_t> frame_buffer(const RtScene* sc) { return std::vector<uint8_t>((size_t)sc->width * sc->height * 3); }  // raytracer.rs:254
+
+// Progressive (`raytracer <config_file> <output_file> --passes K`): the scene's samples per pixel in K contiguous ranges, as even
+// as they come, each added to the scene's accumulator on the GPU (rt_hip_refine_to_host) and the image so far rewritten to
+// <output_file> after every pass (a temporary file in the same directory, then rename: a viewer never sees half a file).  Stderr
+// gets `pass i/K: S samples, kernel X ms`; stdout the same two lines as a one-shot run, `Frame time` over all the passes; the
+// last PNG is the one-shot run's, byte for byte.  One GPU: RT_GPUS > 1 is refused.
+//
+// Denoised (`--denoise`, alone or with `--passes K`): every PNG the run writes is the resolved frame passed through the
+// feature-guided a-trous filter (rt_hip_refine_to_host_denoised, RT_DENOISE_ITERATIONS iterations, the default sigmas; DESIGN.md
+// §12).  The last PNG of `--passes K --denoise` is the `--denoise` run's, byte for byte.  Stdout as a one-shot run.  With --adaptive,
+// or with only one of --frames and --orbit: the usage line.  One GPU: RT_GPUS > 1 is refused.  (`--denoise` alone is one pass
+// without the pass lines.)
+int progressive(const Run& r) {
+  const cli::Options& o = r.o;
+  const uint32_t passes = o.passes > 0 ? (uint32_t)o.passes : 1u, spp = r.sc->samples_per_pixel;
+  RtHipScene* hs = nullptr;
+  if (const int status = open_scene(r, &hs)) return status;
+  std::vector<uint8_t> pixels = frame_buffer(r.sc);
+  const std::string tmp = std::string(o.output) + ".part";  // (same directory: rename() replaces the file in one step)
+  double frame_ms = 0.0;
+  int status = 0;
+  for (uint32_t i = 0; i < passes && status == 0; ++i) {
+    const uint32_t count = spp / passes + (i < spp % passes ? 1u : 0u);  // (the first spp % K passes take one sample more)
+    RtStats st{};
+    int rc = o.denoise ? rt_hip_refine_to_host_denoised(hs, count, RT_DENOISE_ITERATIONS, pixels.data(), &st) : rt_hip_refine_to_host(hs, count, pixels.data(), &st);
+    if (rc != RT_OK) { status = render_failed(rc); break; }
+    frame_ms += st.frame_ms;
+    if (o.passes > 0) std::fprintf(stderr, "pass %u/%u: %u samples, kernel %.3f ms\n", i + 1, passes, count, st.kernel_ms);
+    rc = rt_png_write_rgb8(tmp.c_str(), pixels.data(), r.sc->width, r.sc->height);  // raytracer.rs:265
+    if (rc == RT_OK && std::rename(tmp.c_str(), o.output) != 0) rc = RT_ERR_PNG;
+    if (rc != RT_OK) { status = write_failed(rt_host_last_error()); std::remove(tmp.c_str()); }
+    if (i + 1 == passes && status == 0) std::printf("Frame time: %lldms\n", (long long)frame_ms);  // raytracer.rs:263, all the passes
+  }
+  rt_hip_scene_destroy(hs);
+  return status;
+}
+
+// Adaptive (`raytracer <config_file> <output_file> --adaptive E [--min-spp M]`, M = 16 by default): one adaptive frame
+// (rt_hip_render_adaptive_to_host, DESIGN.md §11) — every pixel tile gets samples until its noise estimate falls below E or it
+// holds the scene's samples per pixel, and each tile is the one-shot frame at its own count, byte for byte.  Stdout as a one-shot
+// run; stderr gets `round i: T tiles at n samples, kernel X ms` per round and what fraction of width x height x spp was traced.
+// One GPU: RT_GPUS > 1 is refused.
+int adaptive(const Run& r) {
+  const RtScene* sc = r.sc;
+  RtHipScene* hs = nullptr;
+  if (const int status = open_scene(r, &hs)) return status;
+  std::vector<uint8_t> pixels = frame_buffer(sc);
+  RtStats st{};
+  int status = 0;
+  const int rc = rt_hip_render_adaptive_to_host(hs, r.o.threshold, (uint32_t)r.o.min_spp, pixels.data(), nullptr, &st);
+  if (rc != RT_OK) status = render_failed(rc);
+  else {
+    std::printf("Frame time: %lldms\n", (long long)st.frame_ms);  // raytracer.rs:263
+    const int64_t rounds = rt_hip_scene_query(hs, "adaptive_rounds");
+    char key[64];
+    for (int64_t i = 0; i < rounds; ++i) {
+      int64_t v[3];
+      const char* f[3] = {"adaptive_round_tiles_", "adaptive_round_spp_", "adaptive_round_kernel_us_"};
+      for (int k = 0; k < 3; ++k) { std::snprintf(key, sizeof key, "%s%lld", f[k], (long long)i); v[k] = rt_hip_scene_query(hs, key); }
+      std::fprintf(stderr, "round %lld: %lld tiles at %lld samples, kernel %.3f ms\n", (long long)i, (long long)v[0], (long long)v[1], v[2] / 1000.0);
+    }
+    const double full = (double)sc->width * sc->height * sc->samples_per_pixel;
+    std::fprintf(stderr, "adaptive: %llu samples traced, %.4f of %ux%ux%u, kernel %.3f ms, frame %.3f ms\n", (unsigned long long)st.samples,
+                 full > 0 ? st.samples / full : 0.0, sc->width, sc->height, sc->samples_per_pixel, st.kernel_ms, st.frame_ms);
+    if (rt_png_write_rgb8(r.o.output, pixels.data(), sc->width, sc->height) != RT_OK) status = write_failed(rt_host_last_error());  // raytracer.rs:265
+  }
+  rt_hip_scene_destroy(hs);
+  return status;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ animations
 // --flat-frames PREFIX: frame f takes its flat primitives from the scene file PREFIX%03d.json, read with the ordinary loader;
 // only its rt_scene_quads are used, and they must be the base file's in count, shapes and materials.  load() returns "" and the
 // frame's q, u, v (n x 9), or what is wrong, naming the frame.  (One file at a time: the loader's error text is per process.)
 struct FlatFrames {
   std::string prefix;
   std::vector<RtQuad> base;
-  std::vector<double> quv;  // of the frame loaded last by the sharded animation
   std::mutex mu;
   bool on() const { return !prefix.empty(); }
   std::string load(int f, std::vector<double>& out) {
@@ -134,44 +201,81 @@ struct FlatFrames {
     return why;
   }
 };
-FlatFrames g_flats;
-// camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77 with the scene's
-// lens = {aperture, focus_dist} (rt_scene_lens; aperture 0: the pinhole, out[0..12] = rt_camera_derive's)
-void orbit_camera(const double cam[11], const double lens[2], double orbit_deg, int f, double out[20]) {
-  const double *lf = cam, *la = cam + 3, *up = cam + 6;
-  double k[3];
-  const double kl = std::sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
-  for (int i = 0; i < 3; ++i) k[i] = up[i] / kl;
-  const double th = orbit_deg * f * (3.14159265358979323846264338327950288 / 180.0), c = std::cos(th), s = std::sin(th);
-  const double v[3] = {lf[0] - la[0], lf[1] - la[1], lf[2] - la[2]};
-  const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
-  const double kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
-  double from[3];
-  for (int i = 0; i < 3; ++i) from[i] = la[i] + v[i] * c + kx[i] * s + k[i] * kv * (1.0 - c);
-  rt_camera_derive_lens(from, la, up, cam[9], cam[10], lens[0], lens[1], out);
+
+// Everything about frame f that is host work: what the resident scene or group is told before the frame is rendered.
+struct Pose {
+  double cam[20];             // rt_camera_derive_lens: origin, lower left, horizontal, vertical (+0, 3, 6, 9), the lens' u, v, radius (+13, 16, 19)
+  bool lens = false;          // the scene has a thin lens
+  bool spheres = false;       // --shutter: the spheres move to c -> c1 (n x 3 each)
+  bool flats = false;         // --flat-frames: the flat primitives move to quv (n x 9)
+  std::vector<double> c, c1, quv;
+};
+// One apply per kind of target.  Each keeps the order of calls its drivers always had (camera first on a scene, last on a group).
+// rt_hip_set_camera / rt_hip_group_set_camera refuse null arguments and nothing else, so checking their status changes no run.
+int apply(RtHipScene* hs, const Pose& p) {
+  int rc = rt_hip_set_camera(hs, p.cam, p.cam + 3, p.cam + 6, p.cam + 9);
+  if (rc == RT_OK && p.lens) rc = rt_hip_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
+  if (rc == RT_OK && p.spheres) rc = rt_hip_scene_update_spheres(hs, p.c.data(), p.c1.data());
+  if (rc == RT_OK && p.flats) rc = rt_hip_scene_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), 0u);
+  return rc;
 }
-// the scene file's camera with its thin lens, if it has one (aperture != 0): out as rt_camera_derive_lens
-bool lens_camera(const RtSceneFile* sf, double out[20]) {
-  double cam[11], lens[2];
-  rt_scene_camera(sf, cam);
-  rt_scene_lens(sf, lens);
-  if (lens[0] == 0.0) return false;
-  rt_camera_derive_lens(cam, cam + 3, cam + 6, cam[9], cam[10], lens[0], lens[1], out);
-  return true;
+int apply(RtHipGroup* hs, const Pose& p) {  // (no frame may be in flight while the spheres or the flat primitives move)
+  int rc = p.spheres ? rt_hip_group_update_spheres(hs, p.c.data(), p.c1.data()) : RT_OK;
+  if (rc == RT_OK && p.flats) rc = rt_hip_group_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), 0u);
+  if (rc == RT_OK) rc = rt_hip_group_set_camera(hs, p.cam, p.cam + 3, p.cam + 6, p.cam + 9);
+  if (rc == RT_OK && p.lens) rc = rt_hip_group_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
+  return rc;
 }
-// a resident scene through that lens (nothing for a pinhole scene: it keeps RtScene's camera)
-int set_scene_lens(const RtSceneFile* sf, RtHipScene* hs) {
-  double c[20];
-  if (!lens_camera(sf, c)) return RT_OK;
-  const int rc = rt_hip_set_camera(hs, c, c + 3, c + 6, c + 9);
-  return rc != RT_OK ? rc : rt_hip_set_lens(hs, c + 13, c + 16, c[19]);
-}
-std::string frame_name(const char* prefix, int f) {
-  char name[4096];
-  std::snprintf(name, sizeof name, "%s_%03d.png", prefix, f);  // main.rs:17
-  return name;
-}
-double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// An animation run: what its frames are posed from.
+struct Anim {
+  const Run& r;
+  const int frames;
+  const char* const prefix;  // of <prefix>_%03d.png
+  double cam[11], lens[2];   // the scene file's (rt_scene_camera, rt_scene_lens)
+  FlatFrames flat_files;
+  explicit Anim(const Run& run) : r(run), frames(run.o.frames), prefix(run.o.output) {
+    rt_scene_camera(r.sf, cam);
+    rt_scene_lens(r.sf, lens);
+    flat_files.prefix = r.o.flat_frames;
+  }
+  // camera of frame f: look_from turned about vup around look_at by orbit_deg * f (Rodrigues), then camera.rs:45-77 with the scene's
+  // lens = {aperture, focus_dist} (aperture 0: the pinhole, out[0..12] = rt_camera_derive's)
+  void orbit_camera(int f, double out[20]) const {
+    const double *lf = cam, *la = cam + 3, *up = cam + 6;
+    double k[3];
+    const double kl = std::sqrt(up[0] * up[0] + up[1] * up[1] + up[2] * up[2]);
+    for (int i = 0; i < 3; ++i) k[i] = up[i] / kl;
+    const double th = r.o.orbit_deg() * f * (3.14159265358979323846264338327950288 / 180.0), c = std::cos(th), s = std::sin(th);
+    const double v[3] = {lf[0] - la[0], lf[1] - la[1], lf[2] - la[2]};
+    const double kv = k[0] * v[0] + k[1] * v[1] + k[2] * v[2];
+    const double kx[3] = {k[1] * v[2] - k[2] * v[1], k[2] * v[0] - k[0] * v[2], k[0] * v[1] - k[1] * v[0]};
+    double from[3];
+    for (int i = 0; i < 3; ++i) from[i] = la[i] + v[i] * c + kx[i] * s + k[i] * kv * (1.0 - c);
+    rt_camera_derive_lens(from, la, up, cam[9], cam[10], lens[0], lens[1], out);
+  }
+  // frame f's camera and, with --shutter, its spheres (anim_path.h)
+  void view(int f, Pose& p) const {
+    orbit_camera(f, p.cam);
+    p.lens = lens[0] != 0.0;
+    p.spheres = r.o.shutter >= 0.0;
+    if (!p.spheres) return;
+    p.c.resize(3 * (size_t)r.sc->n_spheres);
+    p.c1.resize(p.c.size());
+    rt_anim_centres(r.sc->spheres, rt_scene_motion(r.sf), r.sc->n_spheres, f, frames, r.o.shutter, p.c.data(), p.c1.data());
+  }
+  // with --flat-frames, frame f's flat primitives from its file: "", or what is wrong with the file
+  std::string flats(int f, Pose& p) {
+    p.flats = flat_files.on();
+    return p.flats ? flat_files.load(f, p.quv) : std::string();
+  }
+  std::string pose(int f, Pose& p) { view(f, p); return flats(f, p); }
+  std::string frame_name(int f) const {
+    char name[4096];
+    std::snprintf(name, sizeof name, "%s_%03d.png", prefix, f);  // main.rs:17
+    return name;
+  }
+};
 
 // What an animation run reports under RT_STATS=1 (one JSON line on stderr): frames per second disk to disk, and per frame the
 // kernel (slowest rank), the frame as the reference times it, and its PNG — which of the two bounds the run is then on the line.
@@ -180,6 +284,11 @@ struct AnimStats {
   std::vector<double> kernel_ms, frame_ms, png_ms;
   double host_us[4] = {0, 0, 0, 0};   // the submitting thread's time, summed over the frames: waiting for a free buffer, camera + submit, collect, stdout + hand-over
   explicit AnimStats(int n) : kernel_ms(n, 0.0), frame_ms(n, 0.0), png_ms(n, 0.0) {}
+  // a rendered frame's two stdout lines, and its times (distinct elements per frame)
+  void frame(const Anim& a, int f, const RtStats& st) {
+    std::printf("\nRendering %s\nFrame time: %lldms\n", a.frame_name(f).c_str(), (long long)st.frame_ms);
+    kernel_ms[f] = st.kernel_ms; frame_ms[f] = st.frame_ms;
+  }
   void report(const char* mode, int frames, unsigned gpus, unsigned writers, double wall_s, double setup_ms) {
     if (!std::getenv("RT_STATS")) return;
     std::string s;
@@ -201,7 +310,7 @@ struct AnimStats {
   }
 };
 
-// PNG writers of an animation: W threads (RT_ANIM_WRITERS, default 4) take finished frames off a queue; a frame's host buffer
+// PNG writers of an animation: W threads take finished frames off a queue; a frame's host buffer (n_buffers of them, owned here)
 // goes back to the free list when its file is on disk.  A frame's PNG is itself deflated in parallel bands (scene.cpp), so one
 // writer keeps up with the headline frame; the second one is for frames whose kernel is shorter than their PNG (the
 // reference's 1 ms test scene).
@@ -210,14 +319,17 @@ struct PngWriters {
   std::mutex mu;
   std::condition_variable cv_job, cv_free;
   std::vector<Job> jobs;            // FIFO (few entries)
+  std::vector<std::vector<uint8_t>> store;
   std::vector<uint8_t*> free_bufs;
   std::vector<std::thread> th;
   bool quit = false;
   int write_rc = RT_OK;
   std::string write_err;
-  PngWriters(unsigned W, const char* prefix, uint32_t w, uint32_t h, AnimStats* stats) {
+  PngWriters(unsigned W, unsigned n_buffers, const Anim& a, AnimStats* stats) : store(n_buffers, frame_buffer(a.r.sc)) {
+    for (auto& b : store) free_bufs.push_back(b.data());
+    const uint32_t w = a.r.sc->width, h = a.r.sc->height;
     for (unsigned i = 0; i < W; ++i)
-      th.emplace_back([this, prefix, w, h, stats]() {
+      th.emplace_back([this, &a, w, h, stats]() {
         for (;;) {
           Job j;
           {
@@ -226,9 +338,9 @@ struct PngWriters {
             if (jobs.empty()) return;
             j = jobs.front(); jobs.erase(jobs.begin());
           }
-          const auto t0 = std::chrono::steady_clock::now();
-          const int rc = rt_png_write_rgb8(frame_name(prefix, j.frame).c_str(), j.px, w, h);
-          const double ms = ms_between(t0, std::chrono::steady_clock::now());
+          const auto t0 = Clock::now();
+          const int rc = rt_png_write_rgb8(a.frame_name(j.frame).c_str(), j.px, w, h);
+          const double ms = ms_since(t0);
           { std::lock_guard<std::mutex> lk(stats->mu); if (j.frame < (int)stats->png_ms.size()) stats->png_ms[j.frame] = ms; }
           std::lock_guard<std::mutex> lk(mu);
           if (rc != RT_OK && write_rc == RT_OK) { write_rc = rc; write_err = rt_host_last_error(); }
@@ -246,7 +358,7 @@ struct PngWriters {
   void give_buffer(uint8_t* b) { std::lock_guard<std::mutex> lk(mu); free_bufs.push_back(b); }
   void push(int frame, uint8_t* px) { { std::lock_guard<std::mutex> lk(mu); jobs.push_back({frame, px}); } cv_job.notify_one(); }
   bool failed() { std::lock_guard<std::mutex> lk(mu); return write_rc != RT_OK; }
-  void finish() {
+  void finish() {  // every frame handed over is on disk, or has failed
     { std::lock_guard<std::mutex> lk(mu); quit = true; }
     cv_job.notify_all();
     for (auto& t : th) t.join();
@@ -264,209 +376,120 @@ unsigned anim_writers() {
   return w;
 }
 
-// Every frame SHARDED over the RT_GPUS devices (rt_hip_group_*), frames pipelined two deep: frame f+1 is submitted before
-// frame f is collected, so f's gather + de-interleave + device-to-host copy run under f+1's kernels, and f's PNG is encoded
-// on the writer threads meanwhile.  2 + W host buffers: two frames in flight + one per writer.
-int animate_sharded(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
-  RtScene* sc = rt_scene_get_mut(sf);
-  RtHipGroup* hs = nullptr;  // the scene resident on RT_GPUS devices (default 1)
-  const auto t_create = std::chrono::steady_clock::now();
-  int rc = create_group(sf, &hs);
-  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
+// RT_ANIM=sharded (default): every frame SHARDED over the RT_GPUS devices (rt_hip_group_*), frames pipelined two deep: frame f+1 is
+// submitted before frame f is collected, so f's gather + de-interleave + device-to-host copy run under f+1's kernels, and f's PNG is
+// encoded on the writer threads (RT_ANIM_WRITERS, default 4) meanwhile.  2 + W host buffers: two frames in flight + one per writer.
+// A group refuses an update while a frame is in flight, so with --shutter or --flat-frames frame f is collected before the scene moves
+// for f + 1; its PNG is still written while f + 1 renders, and the next frame's file is read while the frame renders.
+// p: frame 0's flat primitives, if any.
+int animate_sharded(Anim& a, Pose& p) {
+  RtHipGroup* hs = nullptr;
+  const auto t_create = Clock::now();
+  int rc = create_group(a.r, &hs);
+  if (rc != RT_OK) return render_failed(rc);
   (void)rt_hip_group_set_option(hs, "prepare_host_output", 2);  // (pinned staging for the two frames in flight + the copy path, at set-up: not inside the first submit)
-  const auto t_begin = std::chrono::steady_clock::now();
-  double cam[11], lens[2];
-  rt_scene_camera(sf, cam);
-  rt_scene_lens(sf, lens);
-  const size_t bytes = (size_t)sc->width * sc->height * 3;
+  const auto t_begin = Clock::now();
   const unsigned W = anim_writers();
-  std::vector<std::vector<uint8_t>> store(2 + W, std::vector<uint8_t>(bytes));
-  AnimStats stats(frames);
-  PngWriters writers(W, prefix, sc->width, sc->height, &stats);
-  for (auto& b : store) writers.give_buffer(b.data());
+  AnimStats stats(a.frames);
+  PngWriters writers(W, 2 + W, a, &stats);
   int status = 0;
   std::vector<uint8_t*> in_flight;  // oldest first
-  auto finish = [&](int f) -> bool {  // collect frame f, print its two lines, hand its pixels to the PNG writers
-    RtStats st{};
-    const auto t0 = std::chrono::steady_clock::now();
-    const int rc = rt_hip_group_collect(hs, &st);
-    const auto t1 = std::chrono::steady_clock::now();
-    stats.host_us[2] += ms_between(t0, t1) * 1e3;
-    if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; return false; }
-    std::printf("\nRendering %s\nFrame time: %lldms\n", frame_name(prefix, f).c_str(), (long long)st.frame_ms);
-    stats.kernel_ms[f] = st.kernel_ms; stats.frame_ms[f] = st.frame_ms;
-    uint8_t* px = in_flight.front();
-    in_flight.erase(in_flight.begin());
-    writers.push(f, px);
-    stats.host_us[3] += ms_between(t1, std::chrono::steady_clock::now()) * 1e3;
-    return !writers.failed();
-  };
   int submitted = 0, collected = 0;
-  std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
-  std::string flats_why;          // --flat-frames: what was wrong with a frame's file
-  if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
-  for (int f = 0; f < frames && status == 0 && !writers.failed(); ++f) {
-    double out[20];
-    const auto t0 = std::chrono::steady_clock::now();
+  auto finish_oldest = [&]() -> bool {  // collect frame `collected`, print its two lines, hand its pixels to the PNG writers
+    RtStats st{};
+    const auto t0 = Clock::now();
+    const int rc = rt_hip_group_collect(hs, &st);
+    const auto t1 = Clock::now();
+    stats.host_us[2] += ms_between(t0, t1) * 1e3;
+    if (rc != RT_OK) { status = render_failed(rc); return false; }
+    stats.frame(a, collected, st);
+    writers.push(collected, in_flight.front());
+    in_flight.erase(in_flight.begin());
+    stats.host_us[3] += ms_since(t1) * 1e3;
+    if (writers.failed()) return false;
+    collected++;
+    return true;
+  };
+  const bool scene_moves = p.flats || a.r.o.shutter >= 0.0;
+  std::string flats_why;  // --flat-frames: what was wrong with a frame's file
+  for (int f = 0; f < a.frames && status == 0 && !writers.failed(); ++f) {
+    const auto t0 = Clock::now();
     uint8_t* buf = writers.take_buffer();
-    const auto t1 = std::chrono::steady_clock::now();
-    if (shutter >= 0.0 || g_flats.on()) {  // (no frame may be in flight while the spheres or the flat primitives move: frame f - 1 is collected first, its PNG overlaps)
-      bool ok = true;
-      while (ok && collected < submitted) { ok = finish(collected); if (ok) collected++; }
-      if (!ok) { writers.give_buffer(buf); break; }
-      rc = RT_OK;
-      if (shutter >= 0.0) {
-        rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
-        rc = rt_hip_group_update_spheres(hs, c_f.data(), c1_f.data());
-      }
-      if (rc == RT_OK && g_flats.on()) rc = rt_hip_group_update_flats(hs, g_flats.quv.data(), (uint32_t)g_flats.base.size(), 0u);
-      if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; writers.give_buffer(buf); break; }
-    }
-    orbit_camera(cam, lens, orbit_deg, f, out);
-    rt_hip_group_set_camera(hs, out, out + 3, out + 6, out + 9);
-    rc = lens[0] != 0.0 ? rt_hip_group_set_lens(hs, out + 13, out + 16, out[19]) : RT_OK;
+    const auto t1 = Clock::now();
+    bool ok = true;
+    while (ok && scene_moves && collected < submitted) ok = finish_oldest();  // (frame f - 1 is collected first, its PNG overlaps)
+    if (!ok) { writers.give_buffer(buf); break; }
+    a.view(f, p);
+    rc = apply(hs, p);
     if (rc == RT_OK) rc = rt_hip_group_submit(hs, buf);
     stats.host_us[0] += ms_between(t0, t1) * 1e3;
-    stats.host_us[1] += ms_between(t1, std::chrono::steady_clock::now()) * 1e3;
-    if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; break; }
+    stats.host_us[1] += ms_since(t1) * 1e3;
+    if (rc != RT_OK) { status = render_failed(rc); writers.give_buffer(buf); break; }
     in_flight.push_back(buf);
     submitted++;
-    if (g_flats.on() && f + 1 < frames) {  // (the next frame's file is read and checked while this frame renders)
-      flats_why = g_flats.load(f + 1, g_flats.quv);
-      if (!flats_why.empty()) break;
-    }
-    if (submitted - collected == 2) { if (!finish(collected)) break; collected++; }
+    if (f + 1 < a.frames && !(flats_why = a.flats(f + 1, p)).empty()) break;  // (the next frame's file is read and checked while this frame renders)
+    if (submitted - collected == 2 && !finish_oldest()) break;
   }
-  while (status == 0 && !writers.failed() && collected < submitted) { if (!finish(collected)) break; collected++; }
+  while (status == 0 && !writers.failed() && collected < submitted && finish_oldest()) {}
   if (!flats_why.empty()) { std::fprintf(stderr, "%s\n", flats_why.c_str()); status = 101; }
   writers.finish();
-  stats.report("sharded", collected, rt_hip_group_size(hs), W, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), ms_between(t_create, t_begin));
+  stats.report("sharded", collected, rt_hip_group_size(hs), W, ms_since(t_begin) / 1e3, ms_between(t_create, t_begin));
   rt_hip_group_destroy(hs);
-  if (writers.write_rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", writers.write_err.c_str()); status = 101; }
+  if (writers.write_rc != RT_OK) status = write_failed(writers.write_err.c_str());
   return status;
 }
 
-// --passes K: one resident scene, K refinements of its accumulator, the PNG rewritten after each
-// (denoise: each pass's frame denoised; report_passes false: the one-shot `--denoise` run, no pass lines)
-int progressive(RtSceneFile* sf, const char* filename, uint32_t passes, bool denoise = false, bool report_passes = true) {
-  const RtScene* sc = rt_scene_get(sf);
+// Denoised animation (`--frames N --orbit DEG [--shutter S] --denoise`): the frames of the animation modes, each
+// tracing a sample range of its own, blended with the previous frame's history where the first-hit surface was on screen one frame ago
+// and filtered spatially (rt_hip_render_frame_temporal_to_host, RT_DENOISE_ITERATIONS iterations) on one resident scene.  The turn per
+// frame must be named: --orbit is required (0 keeps the camera still).  Frame 0 is the `--denoise` one-shot frame, byte for byte.
+// Frame f's PNG is encoded on the writer threads while frame f + 1 renders (1 + W host buffers: the frame being rendered + one per
+// writer).  One GPU: RT_GPUS > 1 is refused.
+// `--temporal-surface` (DESIGN.md §19; only in this mode) turns on surface tracking: moved spheres keep their history, Metal and Glass
+// pixels get the floor `--temporal-alpha-specular B` on alpha (default RT_TEMPORAL_SURFACE_ALPHA_SPECULAR; needs --temporal-surface).
+// `--temporal-alpha A` (only in this mode) sets alpha_min, the floor everywhere else (default RT_TEMPORAL_ALPHA_MIN, with
+// --temporal-surface RT_TEMPORAL_SURFACE_ALPHA_MIN).  A and B lie in [0, 1]; anything else: the usage line.
+int animate_temporal(Anim& a) {
+  const cli::Options& o = a.r.o;
   RtHipScene* hs = nullptr;
-  int rc = create_scene(sf, 0, &hs);
-  if (rc == RT_OK) rc = set_scene_lens(sf, hs);
-  std::printf("\nRendering %s\n", filename);  // main.rs:18
-  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
-  std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);
-  const std::string tmp = std::string(filename) + ".part";  // (same directory: rename() replaces the file in one step)
-  const uint32_t spp = sc->samples_per_pixel;
-  double frame_ms = 0.0;
-  int status = 0;
-  for (uint32_t i = 0; i < passes && status == 0; ++i) {
-    const uint32_t count = spp / passes + (i < spp % passes ? 1u : 0u);  // (the first spp % K passes take one sample more)
-    RtStats st{};
-    rc = denoise ? rt_hip_refine_to_host_denoised(hs, count, RT_DENOISE_ITERATIONS, pixels.data(), &st) : rt_hip_refine_to_host(hs, count, pixels.data(), &st);
-    if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; break; }
-    frame_ms += st.frame_ms;
-    if (report_passes) std::fprintf(stderr, "pass %u/%u: %u samples, kernel %.3f ms\n", i + 1, passes, count, st.kernel_ms);
-    rc = rt_png_write_rgb8(tmp.c_str(), pixels.data(), sc->width, sc->height);  // raytracer.rs:265
-    if (rc == RT_OK && std::rename(tmp.c_str(), filename) != 0) rc = RT_ERR_PNG;
-    if (rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error()); std::remove(tmp.c_str()); status = 101; }
-    if (i + 1 == passes && status == 0) std::printf("Frame time: %lldms\n", (long long)frame_ms);  // raytracer.rs:263, all the passes
-  }
-  rt_hip_scene_destroy(hs);
-  return status;
-}
-
-// --frames N --orbit DEG [--shutter S] --denoise: the animation on one resident scene through the temporal host form, frame f's PNG
-// encoded on the writer threads while frame f + 1 renders (1 + W host buffers: the frame being rendered + one per writer)
-// surface: --temporal-surface; alpha, alpha_specular: the two floors, < 0 = not given
-int animate_temporal(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter, bool surface, double alpha, double alpha_specular) {
-  RtScene* sc = rt_scene_get_mut(sf);
-  RtHipScene* hs = nullptr;
-  const auto t_create = std::chrono::steady_clock::now();
-  int rc = create_scene(sf, 0, &hs);
-  if (rc == RT_OK && (surface || alpha >= 0.0)) {
-    const float a_min = alpha >= 0.0 ? (float)alpha : (surface ? RT_TEMPORAL_SURFACE_ALPHA_MIN : RT_TEMPORAL_ALPHA_MIN);
+  const auto t_create = Clock::now();
+  int rc = create_scene(a.r, 0, &hs);
+  if (rc == RT_OK && (o.t_surface || o.t_alpha >= 0.0)) {
+    const float a_min = o.t_alpha >= 0.0 ? (float)o.t_alpha : (o.t_surface ? RT_TEMPORAL_SURFACE_ALPHA_MIN : RT_TEMPORAL_ALPHA_MIN);
     rc = rt_hip_temporal_configure(hs, a_min, RT_TEMPORAL_N_MAX, RT_TEMPORAL_TAU_NORMAL, RT_TEMPORAL_TAU_ALBEDO, RT_TEMPORAL_TAU_INV_DEPTH);
-    if (rc == RT_OK && surface) rc = rt_hip_temporal_surface(hs, 1, alpha_specular >= 0.0 ? (float)alpha_specular : RT_TEMPORAL_SURFACE_ALPHA_SPECULAR);
+    if (rc == RT_OK && o.t_surface) rc = rt_hip_temporal_surface(hs, 1, o.t_alpha_specular >= 0.0 ? (float)o.t_alpha_specular : RT_TEMPORAL_SURFACE_ALPHA_SPECULAR);
   }
-  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
-  const auto t_begin = std::chrono::steady_clock::now();
-  double cam[11], lens[2];
-  rt_scene_camera(sf, cam);
-  rt_scene_lens(sf, lens);
-  const size_t bytes = (size_t)sc->width * sc->height * 3;
+  if (rc != RT_OK) return render_failed(rc);
+  const auto t_begin = Clock::now();
   const unsigned W = anim_writers();
-  std::vector<std::vector<uint8_t>> store(1 + W, std::vector<uint8_t>(bytes));
-  AnimStats stats(frames);
-  PngWriters writers(W, prefix, sc->width, sc->height, &stats);
-  for (auto& b : store) writers.give_buffer(b.data());
-  std::vector<double> c_f, c1_f;  // --shutter: the spheres of the frame
-  if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
+  AnimStats stats(a.frames);
+  PngWriters writers(W, 1 + W, a, &stats);
+  Pose p;
   int status = 0, done = 0;
-  for (int f = 0; f < frames && status == 0 && !writers.failed(); ++f) {
-    double out[20];
+  for (int f = 0; f < a.frames && status == 0 && !writers.failed(); ++f) {
     uint8_t* buf = writers.take_buffer();
-    orbit_camera(cam, lens, orbit_deg, f, out);
-    rc = rt_hip_set_camera(hs, out, out + 3, out + 6, out + 9);
-    if (rc == RT_OK && lens[0] != 0.0) rc = rt_hip_set_lens(hs, out + 13, out + 16, out[19]);
-    if (rc == RT_OK && shutter >= 0.0) {
-      rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
-      rc = rt_hip_scene_update_spheres(hs, c_f.data(), c1_f.data());
-    }
+    a.pose(f, p);  // (no --flat-frames in this mode: nothing to read, nothing that fails)
+    rc = apply(hs, p);
     RtStats st{};
     if (rc == RT_OK) rc = rt_hip_render_frame_temporal_to_host(hs, (uint32_t)f, RT_DENOISE_ITERATIONS, buf, &st);
-    if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; writers.give_buffer(buf); break; }
-    std::printf("\nRendering %s\nFrame time: %lldms\n", frame_name(prefix, f).c_str(), (long long)st.frame_ms);
-    stats.kernel_ms[f] = st.kernel_ms; stats.frame_ms[f] = st.frame_ms;
+    if (rc != RT_OK) { status = render_failed(rc); writers.give_buffer(buf); break; }
+    stats.frame(a, f, st);
     writers.push(f, buf);
     done++;
   }
   writers.finish();
-  stats.report("temporal", done, 1, W, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), ms_between(t_create, t_begin));
+  stats.report("temporal", done, 1, W, ms_since(t_begin) / 1e3, ms_between(t_create, t_begin));
   rt_hip_scene_destroy(hs);
-  if (writers.write_rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", writers.write_err.c_str()); status = 101; }
-  return status;
-}
-
-// --adaptive E [--min-spp M]: one adaptive frame of a resident scene
-int adaptive(RtSceneFile* sf, const char* filename, double threshold, uint32_t min_spp) {
-  const RtScene* sc = rt_scene_get(sf);
-  RtHipScene* hs = nullptr;
-  int rc = create_scene(sf, 0, &hs);
-  if (rc == RT_OK) rc = set_scene_lens(sf, hs);
-  std::printf("\nRendering %s\n", filename);  // main.rs:18
-  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); return 101; }
-  std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);
-  RtStats st{};
-  rc = rt_hip_render_adaptive_to_host(hs, threshold, min_spp, pixels.data(), nullptr, &st);
-  int status = 0;
-  if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status = 101; }
-  if (status == 0) {
-    std::printf("Frame time: %lldms\n", (long long)st.frame_ms);  // raytracer.rs:263
-    const int64_t rounds = rt_hip_scene_query(hs, "adaptive_rounds");
-    char key[64];
-    for (int64_t i = 0; i < rounds; ++i) {
-      int64_t v[3];
-      const char* f[3] = {"adaptive_round_tiles_", "adaptive_round_spp_", "adaptive_round_kernel_us_"};
-      for (int k = 0; k < 3; ++k) { std::snprintf(key, sizeof key, "%s%lld", f[k], (long long)i); v[k] = rt_hip_scene_query(hs, key); }
-      std::fprintf(stderr, "round %lld: %lld tiles at %lld samples, kernel %.3f ms\n", (long long)i, (long long)v[0], (long long)v[1], v[2] / 1000.0);
-    }
-    const double full = (double)sc->width * sc->height * sc->samples_per_pixel;
-    std::fprintf(stderr, "adaptive: %llu samples traced, %.4f of %ux%ux%u, kernel %.3f ms, frame %.3f ms\n", (unsigned long long)st.samples,
-                 full > 0 ? st.samples / full : 0.0, sc->width, sc->height, sc->samples_per_pixel, st.kernel_ms, st.frame_ms);
-    rc = rt_png_write_rgb8(filename, pixels.data(), sc->width, sc->height);  // raytracer.rs:265
-    if (rc != RT_OK) { std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error()); status = 101; }
-  }
-  rt_hip_scene_destroy(hs);
+  if (writers.write_rc != RT_OK) status = write_failed(writers.write_err.c_str());
   return status;
 }
 
 // RT_ANIM=frames: the frames DISTRIBUTED over the devices — device g renders whole frames g, g + G, ... on its own resident
 // scene and host thread (README.md:43-57 renders an animation one process per frame; this is that, with the scene loaded
 // once per device).  No gather, no shard penalty, no per-frame synchronisation between devices; every frame is the bytes the
-// sharded mode produces (Philox is addressed by pixel).  Per device the PNG of a frame is encoded while the next one renders.
-int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, unsigned G, double shutter) {
-  RtScene* sc = rt_scene_get_mut(sf);
+// sharded mode produces (Philox is addressed by pixel).  Per device the PNG of a frame is encoded while the next one renders: one
+// writer and two buffers each.
+int animate_frames(Anim& a, unsigned G) {
   const int ndev = rt_hip_device_count();
   const char* emu = std::getenv("RT_GPUS_EMULATE");
   if (ndev <= 0) { std::fprintf(stderr, "render failed: %s\n", rt_strerror(RT_ERR_NO_DEVICE)); return 101; }
@@ -474,74 +497,106 @@ int animate_frames(RtSceneFile* sf, const char* prefix, int frames, double orbit
     std::fprintf(stderr, "render failed: RT_GPUS = %u but only %d device(s) visible\n", G, ndev);
     return 101;
   }
-  double cam[11], lens[2];
-  rt_scene_camera(sf, cam);
-  rt_scene_lens(sf, lens);
-  const size_t bytes = (size_t)sc->width * sc->height * 3;
-  const uint32_t w = sc->width, h = sc->height;
   std::mutex out_mu;
   std::vector<int> status(G, 0);
-  AnimStats stats(frames);
-  const auto t_begin = std::chrono::steady_clock::now();
+  AnimStats stats(a.frames);
+  const auto t_begin = Clock::now();
   std::vector<std::thread> th;
   for (unsigned g = 0; g < G; ++g)
     th.emplace_back([&, g]() {
+      auto say = [&](auto&& print) { std::lock_guard<std::mutex> lk(out_mu); print(); };  // (one device's lines at a time)
       RtHipScene* hs = nullptr;
-      int rc = create_scene(sf, (int)(g % (unsigned)ndev), &hs);
-      if (rc != RT_OK) { std::lock_guard<std::mutex> lk(out_mu); std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status[g] = 101; return; }
-      std::vector<uint8_t> buf[2] = {std::vector<uint8_t>(bytes), std::vector<uint8_t>(bytes)};
-      std::thread writer;
-      int write_rc = RT_OK, i = 0;
-      std::vector<double> c_f, c1_f, quv_f;  // --shutter: the spheres of the frame; --flat-frames: its flat primitives
-      if (shutter >= 0.0) { c_f.resize(3 * (size_t)sc->n_spheres); c1_f.resize(3 * (size_t)sc->n_spheres); }
-      for (int f = (int)g; f < frames && write_rc == RT_OK; f += (int)G, ++i) {
-        double out[20];
-        orbit_camera(cam, lens, orbit_deg, f, out);
-        rt_hip_set_camera(hs, out, out + 3, out + 6, out + 9);
-        rc = lens[0] != 0.0 ? rt_hip_set_lens(hs, out + 13, out + 16, out[19]) : RT_OK;
-        if (rc == RT_OK && shutter >= 0.0) {
-          rt_anim_centres(sc->spheres, rt_scene_motion(sf), sc->n_spheres, f, frames, shutter, c_f.data(), c1_f.data());
-          rc = rt_hip_scene_update_spheres(hs, c_f.data(), c1_f.data());
-        }
-        if (rc == RT_OK && g_flats.on()) {
-          const std::string why = g_flats.load(f, quv_f);
-          if (!why.empty()) { std::lock_guard<std::mutex> lk(out_mu); std::fprintf(stderr, "%s\n", why.c_str()); status[g] = 101; break; }
-          rc = rt_hip_scene_update_flats(hs, quv_f.data(), (uint32_t)g_flats.base.size(), 0u);
-        }
+      int rc = create_scene(a.r, (int)(g % (unsigned)ndev), &hs);
+      if (rc != RT_OK) { say([&] { status[g] = render_failed(rc); }); return; }
+      PngWriters writers(1, 2, a, &stats);
+      Pose p;
+      for (int f = (int)g; f < a.frames && !writers.failed(); f += (int)G) {
+        const std::string why = a.pose(f, p);
+        if (!why.empty()) { say([&] { std::fprintf(stderr, "%s\n", why.c_str()); status[g] = 101; }); break; }
+        uint8_t* buf = writers.take_buffer();
+        rc = apply(hs, p);
         RtStats st{};
-        if (rc == RT_OK) rc = rt_hip_render_to_host(hs, buf[i & 1].data(), &st);
-        const std::string fname = frame_name(prefix, f);
-        {
-          std::lock_guard<std::mutex> lk(out_mu);
-          if (rc != RT_OK) { std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error()); status[g] = 101; }
-          else std::printf("\nRendering %s\nFrame time: %lldms\n", fname.c_str(), (long long)st.frame_ms);
-        }
-        if (rc != RT_OK) break;
-        stats.kernel_ms[f] = st.kernel_ms; stats.frame_ms[f] = st.frame_ms;  // (distinct elements per thread)
-        if (writer.joinable()) writer.join();
-        const uint8_t* px = buf[i & 1].data();
-        writer = std::thread([fname, px, w, h, f, &write_rc, &stats]() {
-          const auto t0 = std::chrono::steady_clock::now();
-          write_rc = rt_png_write_rgb8(fname.c_str(), px, w, h);
-          stats.png_ms[f] = ms_between(t0, std::chrono::steady_clock::now());
-        });
+        if (rc == RT_OK) rc = rt_hip_render_to_host(hs, buf, &st);
+        if (rc != RT_OK) { say([&] { status[g] = render_failed(rc); }); writers.give_buffer(buf); break; }
+        say([&] { stats.frame(a, f, st); });
+        writers.push(f, buf);
       }
-      if (writer.joinable()) writer.join();
-      if (write_rc != RT_OK) { std::lock_guard<std::mutex> lk(out_mu); std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error()); status[g] = 101; }
+      writers.finish();
+      if (writers.write_rc != RT_OK) say([&] { status[g] = write_failed(writers.write_err.c_str()); });
       rt_hip_scene_destroy(hs);
     });
   for (auto& t : th) t.join();
-  stats.report("frames", frames, G, 1, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(), 0.0);
+  stats.report("frames", a.frames, G, 1, ms_since(t_begin) / 1e3, 0.0);
   for (int s : status) if (s) return s;
   return 0;
 }
 
+// Animation (SURVEY §8f "animation driver"): `raytracer <config_file> <output_prefix> --frames N [--orbit DEG]` renders N frames to
+// `<output_prefix>_%03d.png` — the file naming main.rs:17 keeps commented out and README.md:43-57 / "Make animation" feed to ffmpeg —
+// turning the camera around look_at by DEG per frame (default 360/N).  The scene is uploaded once and stays in HBM; the PNG of frame i
+// is encoded on writer threads while the GPU renders frame i+1.  With RT_GPUS=G every frame is sharded over the G devices
+// (RT_ANIM=sharded, default), or the frames are distributed over the devices, each rendering whole frames (RT_ANIM=frames);
+// RT_STATS=1 prints frames per second and the per-frame kernel / frame / PNG times to stderr (one JSON line).
+//
+// Moving spheres from frame to frame (`--frames N --shutter S`, 0 <= S <= 1; DESIGN.md §17): a sphere's "center" -> "center1" is its
+// path over the whole animation instead of over one exposure; frame f is exposed from center + dv f / N to center + dv (f + S) / N
+// (anim_path.h), S = 0 giving crisp spheres.  The resident scene's spheres are moved before every frame (rt_hip_group_update_spheres /
+// rt_hip_scene_update_spheres: the grid is rebuilt on the GPU).  Only with --frames; without the flag every frame exposes the scene
+// file's center -> center1.
+//
+// Moving flat primitives from frame to frame (`--frames N --flat-frames PREFIX`; DESIGN.md §24): frame f takes its flat primitives from the
+// scene file PREFIX%03d.json (only its quads, boxes, triangles and meshes are used; count, shapes and materials must be the base file's —
+// anything else, or an unreadable file, ends the run with a message that names the frame).  The resident scene's flat primitives are moved
+// before every frame (rt_hip_group_update_flats / rt_hip_scene_update_flats: the structure of --flat-bvh is refit on the GPU).  Combines
+// with --orbit, --shutter, --flat-bvh, RT_GPUS and RT_ANIM=frames; without --frames, or with --denoise, --passes or --adaptive: the usage line.
+int animate(const Run& r) {
+  Anim a(r);
+  if (r.o.mode == cli::DENOISED_ANIMATION) return animate_temporal(a);
+  Pose first;
+  if (a.flat_files.on()) {  // (frame 0's file is read and checked before anything is created on a device)
+    uint32_t n_quads = 0;
+    const RtQuad* quads = rt_scene_quads(r.sf, &n_quads);
+    if (!n_quads) { std::fprintf(stderr, "--flat-frames: the scene has no flat primitive\n"); return 101; }
+    a.flat_files.base.assign(quads, quads + n_quads);
+    const std::string why = a.flats(0, first);
+    if (!why.empty()) { std::fprintf(stderr, "%s\n", why.c_str()); return 101; }
+  }
+  const char* mode = std::getenv("RT_ANIM");
+  if (mode && !std::strcmp(mode, "frames")) {
+    const unsigned G = (unsigned)gpus_asked(r.sc);
+    if (G < 1 || G > 1024) { std::fprintf(stderr, "render failed: RT_GPUS must be a positive device count\n"); return 101; }
+    return animate_frames(a, G);
+  }
+  if (mode && std::strcmp(mode, "sharded")) { std::fprintf(stderr, "RT_ANIM must be sharded (default) or frames\n"); return 101; }
+  return animate_sharded(a, first);
+}
+
+// The HIP runtime takes 50 - 200 ms to come up (its first call) — as long as the reference's three 2 - 3 MP JPEG textures take to
+// decode.  A thread makes that first call while the main thread reads and parses the scene (SURVEY §8 f3: at 13 ms a frame the host
+// pipeline IS the wall time).
+std::thread g_hip_init;
+double g_hip_init_ms = 0.0;
+void start_hip_init() {
+  g_hip_init = std::thread([]() {
+    const auto t0 = Clock::now();
+    const int n = rt_hip_device_count();
+    // ... and the context + code object of every device the run will use (RT_GPUS, default 1): rt_hip_scene_create finds them up
+    const long want = gpus_asked(nullptr);
+    std::vector<std::thread> per_device;  // (side by side: a context takes ~30 ms each)
+    for (int d = 1; d < n && d < want; ++d) per_device.emplace_back([d]() { (void)rt_hip_device_warm(d); });
+    if (n > 0) (void)rt_hip_device_warm(0);
+    for (auto& t : per_device) t.join();
+    g_hip_init_ms = ms_since(t0);
+  });
+}
+void join_hip_init() { if (g_hip_init.joinable()) g_hip_init.join(); }
+
 // rt_render_rgb8 for a scene with a thin lens, moving spheres or quads (RtScene carries none of them): the same one-frame group, with the
 // lens camera c (rt_camera_derive_lens; null: RtScene's pinhole), the spheres' centres at shutter close and the quads of the scene file
-int render_group_rgb8(const RtSceneFile* sf, const double* c, uint8_t* out_rgb8, RtStats* stats) {
-  const auto t0 = std::chrono::steady_clock::now();
+int render_group_rgb8(const Run& r, const double* c, uint8_t* out_rgb8, RtStats* stats) {
+  const auto t0 = Clock::now();
   RtHipGroup* g = nullptr;
-  int rc = create_group(sf, &g);
+  int rc = create_group(r, &g);
   if (rc != RT_OK) return rc;
   (void)rt_hip_group_set_option(g, "tile_order", 1);  // (one frame: no later frame could use a learned order — rt_render_rgb8's setting)
   if (c) {
@@ -549,178 +604,37 @@ int render_group_rgb8(const RtSceneFile* sf, const double* c, uint8_t* out_rgb8,
     if (rc == RT_OK) rc = rt_hip_group_set_lens(g, c + 13, c + 16, c[19]);
   }
   if (rc == RT_OK) rc = rt_hip_group_set_option(g, "prepare_host_output", 1);
-  const double setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const double setup_ms = ms_since(t0);
   if (rc == RT_OK) rc = rt_hip_group_render_to_host(g, out_rgb8, stats);
   if (rc == RT_OK && stats) stats->setup_ms = setup_ms;
   rt_hip_group_destroy(g);
   return rc;
 }
 
-// shutter < 0: no --shutter (every frame exposes the scene file's center -> center1)
-int animate(RtSceneFile* sf, const char* prefix, int frames, double orbit_deg, double shutter) {
-  if (g_flats.on()) {  // (frame 0's file is read and checked before anything is created on a device)
-    uint32_t n_quads = 0;
-    const RtQuad* quads = rt_scene_quads(sf, &n_quads);
-    if (!n_quads) { std::fprintf(stderr, "--flat-frames: the scene has no flat primitive\n"); return 101; }
-    g_flats.base.assign(quads, quads + n_quads);
-    const std::string why = g_flats.load(0, g_flats.quv);
-    if (!why.empty()) { std::fprintf(stderr, "%s\n", why.c_str()); return 101; }
-  }
-  const char* mode = std::getenv("RT_ANIM");
-  if (mode && !std::strcmp(mode, "frames")) {
-    const RtScene* sc = rt_scene_get(sf);
-    unsigned G = sc->n_gpus;
-    if (G == 0) { const char* e = std::getenv("RT_GPUS"); G = e ? (unsigned)std::strtoul(e, nullptr, 10) : 1u; }
-    if (G < 1 || G > 1024) { std::fprintf(stderr, "render failed: RT_GPUS must be a positive device count\n"); return 101; }
-    return animate_frames(sf, prefix, frames, orbit_deg, G, shutter);
-  }
-  if (mode && std::strcmp(mode, "sharded")) { std::fprintf(stderr, "RT_ANIM must be sharded (default) or frames\n"); return 101; }
-  return animate_sharded(sf, prefix, frames, orbit_deg, shutter);
-}
-}  // namespace
-
-// The HIP runtime takes 50 - 200 ms to come up (its first call) — as long as the reference's three 2 - 3 MP JPEG textures take to
-// decode.  A thread makes that first call while the main thread reads and parses the scene (SURVEY §8 f3: at 13 ms a frame the host
-// pipeline IS the wall time).
-std::thread g_hip_init;
-double g_hip_init_ms = 0.0;
-
-int run(int argc, char** argv) {
-  const auto t_main = std::chrono::steady_clock::now();
-  int frames = 0;
-  long passes = 0, min_spp = 16;
-  double orbit = 0.0, threshold = 0.0, shutter = -1.0, t_alpha = -1.0, t_alpha_specular = -1.0;
-  bool orbit_given = false, bad_args = argc < 3, adapt = false, min_spp_given = false, denoise = false, t_surface = false;
-  for (int i = 3; i < argc && !bad_args; ++i) {
-    if (!std::strcmp(argv[i], "--frames") && i + 1 < argc) frames = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
-    else if (!std::strcmp(argv[i], "--flat-bvh")) { bad_args = g_flat_bvh; g_flat_bvh = true; }  // (given twice: the usage line)
-    else if (!std::strcmp(argv[i], "--flat-frames") && i + 1 < argc) { bad_args = g_flats.on() || !argv[i + 1][0]; g_flats.prefix = argv[++i]; }
-    else if (!std::strcmp(argv[i], "--temporal-surface")) t_surface = true;
-    else if ((!std::strcmp(argv[i], "--temporal-alpha") || !std::strcmp(argv[i], "--temporal-alpha-specular")) && i + 1 < argc) {
-      double& dst = std::strcmp(argv[i], "--temporal-alpha") ? t_alpha_specular : t_alpha;
-      char* end = nullptr;
-      dst = std::strtod(argv[++i], &end);
-      if (end == argv[i] || *end != '\0' || !(dst >= 0.0 && dst <= 1.0)) bad_args = true;
-    }
-    else if (!std::strcmp(argv[i], "--orbit") && i + 1 < argc) { orbit = std::atof(argv[++i]); orbit_given = true; }
-    else if (!std::strcmp(argv[i], "--shutter") && i + 1 < argc) {
-      char* end = nullptr;
-      shutter = std::strtod(argv[++i], &end);
-      if (end == argv[i] || *end != '\0' || !(shutter >= 0.0 && shutter <= 1.0)) bad_args = true;
-    } else if (!std::strcmp(argv[i], "--passes") && i + 1 < argc) {
-      char* end = nullptr;
-      passes = std::strtol(argv[++i], &end, 10);
-      if (end == argv[i] || *end != '\0' || passes < 1) bad_args = true;
-    } else if (!std::strcmp(argv[i], "--adaptive") && i + 1 < argc) {
-      char* end = nullptr;
-      threshold = std::strtod(argv[++i], &end);
-      adapt = true;
-      if (end == argv[i] || *end != '\0' || !(threshold >= 0.0) || std::isinf(threshold)) bad_args = true;
-    } else if (!std::strcmp(argv[i], "--min-spp") && i + 1 < argc) {
-      char* end = nullptr;
-      min_spp = std::strtol(argv[++i], &end, 10);
-      min_spp_given = true;
-      if (end == argv[i] || *end != '\0' || min_spp < 1 || min_spp > 0xFFFFFFFFl) bad_args = true;
-    } else bad_args = true;
-  }
-  auto usage = [&]() { std::printf("Usage: %s <config_file> <output_file>\n", argv[0]); return 0; };
-  const bool temporal = denoise && frames > 0 && orbit_given;  // (a denoised animation names its turn per frame)
-  if (!temporal && (t_surface || t_alpha >= 0.0 || t_alpha_specular >= 0.0)) bad_args = true;  // (the three flags of the denoised animation alone)
-  if (t_alpha_specular >= 0.0 && !t_surface) bad_args = true;
-  if (g_flats.on() && (frames <= 0 || denoise || passes > 0 || adapt)) bad_args = true;  // (moved flat primitives are not followed by the temporal filter)
-  if (bad_args || (shutter >= 0.0 && (frames <= 0 || passes > 0 || adapt || (denoise && !temporal))) || (passes > 0 && (frames != 0 || orbit_given)) || (adapt && (passes > 0 || frames != 0 || orbit_given)) || (min_spp_given && !adapt) ||
-      (denoise && (adapt || ((frames != 0 || orbit_given) && !temporal))) || (argc - (g_flat_bvh ? 1 : 0) > 3 && passes == 0 && !adapt && frames <= 0 && !denoise))
-    return usage();  // main.rs:9-12: usage line, normal return
-  // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
-  // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X
-  // (tools/microbench/setup_costs.hip) — to move 80 KB of tables in and 2.9 MB of pixels out once.  With HSA_ENABLE_SDMA=0 the
-  // runtime copies with kernels on the compute queue that exists anyway (same copy times at these sizes, measured).  Only here:
-  // an animation keeps the engines — its copies run UNDER the next frame's kernel, which leaves a copy kernel no registers.
-  // A value the user set is left alone.
-  if (frames == 0) setenv("HSA_ENABLE_SDMA", "0", 0);
-  g_hip_init = std::thread([]() {
-    const auto t0 = std::chrono::steady_clock::now();
-    const int n = rt_hip_device_count();
-    // ... and the context + code object of every device the run will use (RT_GPUS, default 1): rt_hip_scene_create finds them up
-    const char* e = std::getenv("RT_GPUS");
-    long want = e ? std::strtol(e, nullptr, 10) : 1;
-    if (want < 1) want = 1;
-    std::vector<std::thread> per_device;  // (side by side: a context takes ~30 ms each)
-    for (int d = 1; d < n && d < want; ++d) per_device.emplace_back([d]() { (void)rt_hip_device_warm(d); });
-    if (n > 0) (void)rt_hip_device_warm(0);
-    for (auto& t : per_device) t.join();
-    g_hip_init_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  });
-  auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-  RtSceneFile* sf = nullptr;
-  int rc = rt_scene_load_file(argv[1], &sf);
-  if (rc != RT_OK) {
-    std::fprintf(stderr, "%s\n", rt_host_last_error());
-    return 101;
-  }
-  RtScene* sc = rt_scene_get_mut(sf);
-  if (const char* seed = std::getenv("RT_SEED")) sc->seed = std::strtoull(seed, nullptr, 0);
-  if (passes > 0 || denoise) {
-    int status = 0;
-    const char* e = std::getenv("RT_GPUS");
-    if ((unsigned long)passes > sc->samples_per_pixel) status = usage();
-    else if (sc->n_gpus > 1 || (e && std::strtol(e, nullptr, 10) > 1)) {
-      if (denoise) std::fprintf(stderr, "--denoise renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no denoised form)\n");
-      else std::fprintf(stderr, "--passes renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no progressive form)\n");
-      status = 101;
-    } else {
-      if (g_hip_init.joinable()) g_hip_init.join();
-      if (temporal) status = animate_temporal(sf, argv[2], frames, orbit, shutter, t_surface, t_alpha, t_alpha_specular);
-      else status = passes > 0 ? progressive(sf, argv[2], (uint32_t)passes, denoise) : progressive(sf, argv[2], 1u, true, false);
-    }
-    rt_scene_free(sf);
-    return status;
-  }
-  if (adapt) {
-    int status = 0;
-    const char* e = std::getenv("RT_GPUS");
-    if (sc->n_gpus > 1 || (e && std::strtol(e, nullptr, 10) > 1)) {
-      std::fprintf(stderr, "--adaptive renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no adaptive form)\n");
-      status = 101;
-    } else {
-      if (g_hip_init.joinable()) g_hip_init.join();
-      status = adaptive(sf, argv[2], threshold, (uint32_t)min_spp);
-    }
-    rt_scene_free(sf);
-    return status;
-  }
-  if (frames > 0) {
-    if (g_hip_init.joinable()) g_hip_init.join();
-    const int status = animate(sf, argv[2], frames, orbit_given ? orbit : 360.0 / frames, shutter);
-    rt_scene_free(sf);
-    return status;
-  }
-  const char* filename = argv[2];
+// The reference's run: one frame, one PNG.  RtScene has no lens, no moving spheres and no quads, so the one-shot frame of a scene file
+// with any of them goes through a one-frame group, not rt_render_rgb8.
+int one_shot(const Run& r, Clock::time_point t_main) {
+  const RtScene* sc = r.sc;
   const double load_done_ms = ms_since(t_main);
-  std::printf("\nRendering %s\n", filename);  // main.rs:18
-  std::vector<uint8_t> pixels((size_t)sc->width * sc->height * 3);  // raytracer.rs:254
+  std::printf("\nRendering %s\n", r.o.output);  // main.rs:18
+  std::vector<uint8_t> pixels = frame_buffer(sc);
   RtStats st{};
-  const auto t_hip = std::chrono::steady_clock::now();
-  if (g_hip_init.joinable()) g_hip_init.join();  // (what of the runtime's start-up the load did not cover)
+  const auto t_hip = Clock::now();
+  join_hip_init();  // (what of the runtime's start-up the load did not cover)
   const double hip_wait_ms = ms_since(t_hip), hip_init_ms = g_hip_init_ms;
   double cam_lens[20];
-  const bool lens = lens_camera(sf, cam_lens);
+  const bool lens = lens_camera(r.sf, cam_lens);
   uint32_t n_quads = 0;
-  (void)rt_scene_quads(sf, &n_quads);
-  rc = lens || rt_scene_motion(sf) || n_quads ? render_group_rgb8(sf, lens ? cam_lens : nullptr, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
-  if (rc != RT_OK) {
-    std::fprintf(stderr, "render failed: %s: %s\n", rt_strerror(rc), rt_hip_last_error());
-    rt_scene_free(sf);
-    return 101;
-  }
+  (void)rt_scene_quads(r.sf, &n_quads);
+  int rc = lens || rt_scene_motion(r.sf) || n_quads ? render_group_rgb8(r, lens ? cam_lens : nullptr, pixels.data(), &st) : rt_render_rgb8(sc, pixels.data(), &st);
+  if (rc != RT_OK) return render_failed(rc);
   std::printf("Frame time: %lldms\n", (long long)st.frame_ms);  // raytracer.rs:263
-  const auto t_png = std::chrono::steady_clock::now();
-  rc = rt_png_write_rgb8(filename, pixels.data(), sc->width, sc->height);  // raytracer.rs:265
+  const auto t_png = Clock::now();
+  rc = rt_png_write_rgb8(r.o.output, pixels.data(), sc->width, sc->height);  // raytracer.rs:265
   const double png_ms = ms_since(t_png);
   if (std::getenv("RT_STATS")) {  // where a drop-in user's wall time goes: main() entered -> PNG on disk
     double lt[4] = {0, 0, 0, 0};
-    rt_scene_load_timings(sf, lt);
+    rt_scene_load_timings(r.sf, lt);
     std::fprintf(stderr, "{\"samples\":%llu,\"segments\":%llu,\"sphere_tests\":%llu,\"exact_tests\":%llu,\"n_gpus\":%u,\"kernel_ms\":%.3f,"
                          "\"gather_ms\":%.3f,\"frame_ms\":%.3f,\"setup_ms\":%.3f,\"msamples_per_s\":%.3f,"
                          "\"load_ms\":%.3f,\"read_ms\":%.3f,\"json_ms\":%.3f,\"jpeg_ms\":%.3f,\"hip_init_ms\":%.3f,\"hip_wait_ms\":%.3f,\"png_ms\":%.3f,\"main_ms\":%.3f,"
@@ -731,12 +645,53 @@ int run(int argc, char** argv) {
                  st.group_us[0], st.group_us[1], st.group_us[2], st.group_us[3], st.group_us[4], st.group_us[5], st.group_us[6], st.group_us[7],
                  rt_hip_setup_profile());
   }
-  rt_scene_free(sf);
-  if (rc != RT_OK) {
-    std::fprintf(stderr, "error writing image: %s\n", rt_host_last_error());
+  return rc != RT_OK ? write_failed(rt_host_last_error()) : 0;
+}
+
+// the modes that render on one GPU, when the run asks for more (0: go on)
+int refuse_many_gpus(const Run& r) {
+  const bool animation = r.o.mode == cli::ANIMATION, one = r.o.mode == cli::ONE_SHOT;
+  if (animation || one || gpus_asked(r.sc) <= 1) return 0;
+  const char* flag = r.o.denoise ? "denoise" : (r.o.adaptive ? "adaptive" : "passes");
+  const char* form = r.o.denoise ? "denoised" : (r.o.adaptive ? "adaptive" : "progressive");
+  std::fprintf(stderr, "--%s renders on one GPU: unset RT_GPUS (the multi-GPU group calls have no %s form)\n", flag, form);
+  return 101;
+}
+int dispatch(const Run& r, Clock::time_point t_main) {
+  if (r.o.passes > 0 && (unsigned long)r.o.passes > r.sc->samples_per_pixel) return usage(r.o);
+  if (const int status = refuse_many_gpus(r)) return status;
+  if (r.o.mode == cli::ONE_SHOT) return one_shot(r, t_main);
+  join_hip_init();
+  switch (r.o.mode) {
+    case cli::ADAPTIVE: return adaptive(r);
+    case cli::ANIMATION: case cli::DENOISED_ANIMATION: return animate(r);
+    default: return progressive(r);  // --passes K, --denoise, or both
+  }
+}
+}  // namespace
+
+int run(int argc, char** argv) {
+  const auto t_main = Clock::now();
+  const cli::Options o = cli::parse(argc, argv);
+  if (o.mode == cli::USAGE) return usage(o);
+  // One frame per process (the reference's way, main.rs:7-20): the runtime's copy engines are hardware queues it creates at
+  // their FIRST use — 7.8 ms for the first host-to-device copy, 7.8 ms for the first device-to-host copy on MI355X
+  // (tools/microbench/setup_costs.hip) — to move 80 KB of tables in and 2.9 MB of pixels out once.  With HSA_ENABLE_SDMA=0 the
+  // runtime copies with kernels on the compute queue that exists anyway (same copy times at these sizes, measured).  Only here:
+  // an animation keeps the engines — its copies run UNDER the next frame's kernel, which leaves a copy kernel no registers.
+  // A value the user set is left alone.
+  if (o.frames == 0) setenv("HSA_ENABLE_SDMA", "0", 0);
+  start_hip_init();
+  RtSceneFile* sf = nullptr;
+  if (rt_scene_load_file(o.config, &sf) != RT_OK) {
+    std::fprintf(stderr, "%s\n", rt_host_last_error());
     return 101;
   }
-  return 0;
+  const Run r{o, sf, rt_scene_get_mut(sf)};
+  if (const char* seed = std::getenv("RT_SEED")) r.sc->seed = std::strtoull(seed, nullptr, 0);
+  const int status = dispatch(r, t_main);
+  rt_scene_free(sf);
+  return status;
 }
 
 // Everything the process owes the world is on disk or in the pipe when run() returns: stdout / stderr are flushed and the process
@@ -744,7 +699,7 @@ int run(int argc, char** argv) {
 // RT_FAST_EXIT=0 takes the ordinary way out.
 int main(int argc, char** argv) {
   const int status = run(argc, argv);
-  if (g_hip_init.joinable()) g_hip_init.join();
+  join_hip_init();
   std::fflush(stdout);
   std::fflush(stderr);
   const char* fe = std::getenv("RT_FAST_EXIT");

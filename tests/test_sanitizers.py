@@ -63,3 +63,13 @@ def test_png_writer_under_sanitizers(tmp_path):
                  extra=("-fopenmp", "-lz", "-lpthread"))
     out = _run([exe, "5", str(tmp_path / "f.png")], 600)
     assert "ok 81 files" in out
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_cli_argument_parser_under_sanitizers(tmp_path):
+    """csrc/host/cli_args.h alone (tests/cliargs/cli_args_main.cpp) over every row of tests/golden/cli_accept.json under ASan + UBSan: the
+    argument lists that end in a flag without its value, the empty values, the values out of range"""
+    from test_cli_args import check, fixture_rows, run_parser
+    exe = _build(tmp_path, "cli_args_main", ["tests/cliargs/cli_args_main.cpp"])
+    rows = fixture_rows()
+    check(rows, run_parser(exe, rows, env=ENV))
