@@ -3,7 +3,7 @@
  *
  * These entry points exist in librt_hip_probe.so only (the same sources as librt_hip.so compiled with -DRT_TEST_PROBES;
  * rust-raytracer_amd/build.py) — the product library exports none of them.  tests/test_gpu_parity.py, tests/test_walk_rays_gpu.py,
- * tests/test_quad_rays_gpu.py and tools/diag.py bind them; a host that replaces raytracer.rs:260-262 needs include/rt_abi.h alone.
+ * tests/test_quad_rays_gpu.py, tests/test_medium_rays_gpu.py, tests/test_solid_points_gpu.py and tools/diag.py bind them; a host that replaces raytracer.rs:260-262 needs include/rt_abi.h alone.
  */
 #ifndef RT_ABI_TEST_H
 #define RT_ABI_TEST_H
@@ -63,6 +63,28 @@ int rt_hip_walk_probe(RtHipScene*, const double* d_rays, double* d_t, int32_t* d
  * component of a ray or a closest: the quad test is arithmetic alone.  All d_* are device pointers. */
 int rt_hip_quad_probe(RtHipScene*, const double* d_rays, const double* d_closest, uint32_t n, uint32_t first_quad, uint32_t n_quads,
                       int32_t* d_best, double* d_t, double* d_point, double* d_normal, int32_t* d_front, void* stream);
+/* The media and solid-texture code on the device (tests/test_medium_rays_gpu.py, tests/test_solid_points_gpu.py).  Their
+ * contract is the bits of csrc/common/rt_neg_log.h and csrc/common/rt_solid.h: every output below must equal the host build of the same
+ * headers (tests/lanesim) bit for bit.  All d_* are device pointers; n = 0 is allowed and launches nothing.
+ * rt_hip_neg_log_probe: rt_neg_log of n doubles.  Any double is a valid argument (0 -> +inf, negative and NaN -> NaN, +inf -> -inf).
+ * rt_hip_solid_fn_probe: rt_solid_noise(p, seed) -> d_noise[i], rt_solid_noise_factor(p, mode, octaves, seed) -> d_factor[i] and
+ * rt_solid_checker_odd(p) -> d_checker_odd[i] (0 / 1) of the n points d_p[3i .. 3i+2], which are already in the sphere's frame and scaled;
+ * each of the three outputs may be null.  Any double is a valid coordinate.  mode 0..2 (noise, turbulence, marble) and octaves 1..16, else
+ * RT_ERR_INVALID.
+ * rt_hip_solid_probe: rt_core.h solid_albedo — the colour a hit attenuates by — of the n world-space points d_points[3i .. 3i+2] on sphere
+ * `sphere` of the scene, with that sphere's own centre and material record: d_rgb[3i .. 3i+2] (f32).  A sphere that is neither Checker nor
+ * Noise, or an index >= the scene's spheres, is RT_ERR_INVALID.
+ * rt_hip_medium_probe: hit_world as a MEDIUM kernel runs it for one segment — hit_world_grid with the medium candidate, then the flat
+ * primitives of a scene that has some — of n rays d_rays[6i .. 6i+5] = {origin[3], direction[3]}, one per thread.  Ray i has the RNG address
+ * (pixel i, sample 0, node d_node[i], the scene's seed) and is taken at shutter time d_tau[i] (f32; null: 0; read only by a scene that
+ * moves).  d_t / d_best = its (t, object id); a miss leaves t = f64::MAX and best = -1.  d_work (optional) = n x {exact sphere tests, grid
+ * steps}.  A scene without media is RT_ERR_INVALID.  Any double is a valid component of a ray. */
+int rt_hip_neg_log_probe(const double* d_x, double* d_out, uint32_t n, void* stream);
+int rt_hip_solid_fn_probe(const double* d_p, uint32_t mode, uint32_t octaves, uint32_t seed, double* d_noise, double* d_factor, int32_t* d_checker_odd,
+                          uint32_t n, void* stream);
+int rt_hip_solid_probe(RtHipScene*, uint32_t sphere, const double* d_points, float* d_rgb, uint32_t n, void* stream);
+int rt_hip_medium_probe(RtHipScene*, const double* d_rays, const float* d_tau, const uint32_t* d_node, double* d_t, int32_t* d_best, uint32_t* d_work,
+                        uint32_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2159,4 +2159,48 @@ extern "C" int rt_hip_quot_probe(const double* d_x, const double* d_y, double* d
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }
+
+// csrc/common/rt_neg_log.h and rt_solid.h as the device evaluates them (see rtk::rt_neg_log_probe, rtk::rt_solid_fn_probe)
+extern "C" int rt_hip_neg_log_probe(const double* d_x, double* d_out, uint32_t n, void* stream) {
+  if (!d_x || !d_out) return fail(RT_ERR_INVALID, "null argument");
+  if (!n) return RT_OK;
+  hipLaunchKernelGGL(rtk::rt_neg_log_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_x, d_out, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+extern "C" int rt_hip_solid_fn_probe(const double* d_p, uint32_t mode, uint32_t octaves, uint32_t seed, double* d_noise, double* d_factor,
+                                     int32_t* d_checker_odd, uint32_t n, void* stream) {
+  if (!d_p) return fail(RT_ERR_INVALID, "null argument");
+  if (mode > RT_SOLID_MODE_MARBLE || octaves < 1u || octaves > RT_SOLID_MAX_OCTAVES) return fail(RT_ERR_INVALID, "mode 0..2 and 1..16 octaves");
+  if (!n) return RT_OK;
+  hipLaunchKernelGGL(rtk::rt_solid_fn_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_p, mode, octaves, seed, d_noise, d_factor,
+                     d_checker_odd, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// rt_core.h solid_albedo of n world-space points on one Checker or Noise sphere of the scene (see rtk::rt_solid_probe)
+extern "C" int rt_hip_solid_probe(RtHipScene* s, uint32_t sphere, const double* d_points, float* d_rgb, uint32_t n, void* stream) {
+  if (!s || !d_points || !d_rgb) return fail(RT_ERR_INVALID, "null argument");
+  const std::vector<RtSphere>& sp = s->res->sph.spheres;
+  if (sphere >= sp.size() || sphere >= s->dev.n_spheres) return fail(RT_ERR_INVALID, "the sphere index lies outside the scene");
+  if (sp[sphere].kind != RT_MAT_CHECKER && sp[sphere].kind != RT_MAT_NOISE) return fail(RT_ERR_INVALID, "the sphere is neither Checker nor Noise");
+  if (!n) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_solid_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, sphere, d_points, d_rgb, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// hit_world with the medium candidate of n rays on the device, one per thread, through the scene's tables (see rtk::rt_medium_probe)
+extern "C" int rt_hip_medium_probe(RtHipScene* s, const double* d_rays, const float* d_tau, const uint32_t* d_node, double* d_t, int32_t* d_best,
+                                   uint32_t* d_work, uint32_t n, void* stream) {
+  if (!s || !d_rays || !d_node || !d_t || !d_best) return fail(RT_ERR_INVALID, "null argument");
+  if (!s->dev.medium) return fail(RT_ERR_INVALID, "the scene has no media");
+  if (!n) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_medium_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, d_rays, d_tau, d_node, d_t, d_best, d_work, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
 #endif  // RT_TEST_PROBES

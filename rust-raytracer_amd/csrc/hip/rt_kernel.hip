@@ -1551,6 +1551,60 @@ __global__ void rt_quot_probe(const double* x, const double* y, double* out_quot
   out_rsqrt[i] = rt_fast_rsqrt(x[i]);
   if (out_div) out_div[i] = rt_div_inrange(x[i], y[i]);
 }
+
+// The media and solid-texture code on the device (tests/test_medium_rays_gpu.py, tests/test_solid_points_gpu.py): their
+// contract is the bits of csrc/common/rt_neg_log.h and csrc/common/rt_solid.h, which the host build and the restatements pin.
+// rt_neg_log (the free-flight logarithm) of n doubles as the device evaluates it
+__global__ void rt_neg_log_probe(const double* x, double* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = rt_neg_log(x[i]);
+}
+// rt_solid_noise, rt_solid_noise_factor and rt_solid_checker_odd of n points already in the sphere's frame and scaled (3 doubles each); each
+// output is optional.  The f64 factor itself: solid_albedo's rounding of f * albedo to f32 would hide a one-ulp difference.
+__global__ void rt_solid_fn_probe(const double* p, uint32_t mode, uint32_t octaves, uint32_t seed, double* out_noise, double* out_factor,
+                                  int32_t* out_checker_odd, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double px = p[3 * i], py = p[3 * i + 1], pz = p[3 * i + 2];
+  if (out_noise) out_noise[i] = rt_solid_noise(px, py, pz, seed);
+  if (out_factor) out_factor[i] = rt_solid_noise_factor(px, py, pz, mode, octaves, seed);
+  if (out_checker_odd) out_checker_odd[i] = rt_solid_checker_odd(px, py, pz);
+}
+// solid_albedo (rt_core.h) — the cold by-value call the kernels make — of n world-space points on sphere `sphere` (a Checker or Noise
+// sphere: the entry point checks), with the sphere's own centre and SphereMat record: out_rgb = n x 3 f32
+__global__ void rt_solid_probe(const DevScene sc, uint32_t sphere, const double* points, float* out_rgb, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const SphereGeom g = sc.geom[sphere];
+  const Rgb c = solid_albedo(v3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), v3(g.cx, g.cy, g.cz), sc.mat[sphere]);
+  out_rgb[3 * i] = c.r; out_rgb[3 * i + 1] = c.g; out_rgb[3 * i + 2] = c.b;
+}
+// hit_world with the medium candidate (hit_world_grid<true> with a MediumCtx, then the flat primitives of a scene that has some) of n
+// rays, one per thread, through the scene's tables — the motion tables at shutter time tau[i] (null: 0) in a scene that moves.  Ray i has
+// the RNG address (pixel i, sample 0, node[i], the scene's seed): tests/lanesim/lane_sim.h hit_rays<true, QUADS> on the device.  out_t /
+// out_best = (closest, best) with closest-so-far = f64::MAX; out_work (optional) = exact tests and grid steps.  The scene has media (the
+// entry point checks): sc.medium is not null.
+template <class Tables>
+__device__ void medium_probe_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, const MediumCtx& mc, double& closest, int& best, uint32_t& n_exact,
+                                 uint32_t& n_steps) {
+  hit_world_grid<true>(sc, tb, o, d, closest, best, n_exact, n_steps, &mc);
+  if (sc.n_quads) { const HitCB r = flats_hit(sc, o, d, closest, best); closest = r.closest; best = r.best; }
+}
+__global__ void rt_medium_probe(const DevScene sc, const double* rays, const float* tau, const uint32_t* node, double* out_t, int32_t* out_best,
+                                uint32_t* out_work, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+  const GlobalTables tb{sc.geom, sc.matc};
+  const MediumCtx mc{sc.medium, RngAddr{i, 0u, sc.seed_lo, sc.seed_hi}, node[i]};
+  double closest = T_MAX;
+  int best = -1;
+  uint32_t n_exact = 0, n_steps = 0;
+  if (sc.motion) medium_probe_ray(sc, motion_tables(tb, sc.motion, tau ? tau[i] : 0.0f), o, d, mc, closest, best, n_exact, n_steps);
+  else medium_probe_ray(sc, tb, o, d, mc, closest, best, n_exact, n_steps);
+  out_t[i] = closest; out_best[i] = best;
+  if (out_work) { out_work[2 * i] = n_exact; out_work[2 * i + 1] = n_steps; }
+}
 #endif  // RT_TEST_PROBES
 #endif  // !RT_KERNEL_SET
 

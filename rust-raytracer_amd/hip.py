@@ -122,6 +122,10 @@ def _bind(path, probes):
         L.rt_hip_render_rays_probe.argtypes = [C.c_void_p] * 6 + [C.POINTER(abi.RtStats)]
         L.rt_hip_walk_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
         L.rt_hip_quad_probe.argtypes = [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p] * 6
+        L.rt_hip_neg_log_probe.argtypes = [C.c_void_p] * 2 + [C.c_uint32, C.c_void_p]
+        L.rt_hip_solid_fn_probe.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p]
+        L.rt_hip_solid_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rt_hip_medium_probe.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p]
     for name in (() if os.environ.get("RT_SKIP_LAYOUT_CHECK") else ("RtSphere", "RtQuad", "RtTexture", "RtScene", "RtRowTiles", "RtStats", "RtGroupInfo", "RtGroupRank")):   # the binding's own layout check
         if L.rt_abi_sizeof(name.encode()) != C.sizeof(getattr(abi, name)):
             raise ImportError(f"{path}: sizeof({name}) = {L.rt_abi_sizeof(name.encode())} but abi.py has "
@@ -491,6 +495,18 @@ class HipScene:
         first_quad + n_quads - 1, then object_surface of the accepted id (device pointers), enqueued on `stream`"""
         _check(self._L.rt_hip_quad_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_closest), n, first_quad, n_quads, C.c_void_p(d_best), C.c_void_p(d_t),
                                          C.c_void_p(d_point), C.c_void_p(d_normal), C.c_void_p(d_front), C.c_void_p(stream or None)), self._L)
+
+    def solid_probe(self, sphere, d_points, d_rgb, n, stream=0):
+        """(probe library only) rt_hip_solid_probe: solid_albedo of n world-space points (n x 3 f64) on the Checker or Noise sphere `sphere`
+        -> d_rgb (n x 3 f32; device pointers), enqueued on `stream`"""
+        _check(self._L.rt_hip_solid_probe(self._h, sphere, C.c_void_p(d_points), C.c_void_p(d_rgb), n, C.c_void_p(stream or None)), self._L)
+
+    def medium_probe(self, d_rays, d_node, d_t, d_best, n, d_tau=0, d_work=0, stream=0):
+        """(probe library only) rt_hip_medium_probe: hit_world with the medium candidate of n rays, ray i at the RNG address (pixel i, sample
+        0, d_node[i]) and shutter time d_tau[i] (f32; 0: time 0) -> d_t, d_best, d_work (optional, n x 2 u32; device pointers), enqueued on
+        `stream`"""
+        _check(self._L.rt_hip_medium_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_tau or None), C.c_void_p(d_node), C.c_void_p(d_t), C.c_void_p(d_best),
+                                           C.c_void_p(d_work or None), n, C.c_void_p(stream or None)), self._L)
 
     def close(self):
         if self._h:

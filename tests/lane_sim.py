@@ -46,6 +46,7 @@ class LaneSim:
         L.medium_tables.argtypes = [S, P, P, P, P]
         L.medium_cell_lists.argtypes = [S, P, u32]
         L.medium_neg_log_v.argtypes = [P, u64, P]
+        L.medium_terms_v.argtypes = [P, P, P, P, u64, u64, P]
         L.solid_checker_v.argtypes = [P, u64, P]
         L.solid_noise_v.argtypes = [P, u64, u32, P]
         L.solid_factor_v.argtypes = [P, u64, u32, u32, u32, P]
@@ -53,7 +54,7 @@ class LaneSim:
         L.quad_prepare_v.argtypes = [P, u64, P, P]
         L.quad_hit_v.argtypes = [P, P, P, u64] + [P] * 5
         L.quad_box.argtypes = [P] * 3
-        for f in (L.lane_sim_tables_error, L.medium_neg_log_v, L.solid_checker_v, L.solid_noise_v, L.solid_factor_v, L.quad_prepare_v, L.quad_box):
+        for f in (L.lane_sim_tables_error, L.medium_neg_log_v, L.medium_terms_v, L.solid_checker_v, L.solid_noise_v, L.solid_factor_v, L.quad_prepare_v, L.quad_box):
             f.restype = None
 
     @staticmethod
@@ -150,6 +151,15 @@ class LaneSim:
 
     def medium_neg_log_v(self, x):
         return self._vec(self.L.medium_neg_log_v, np.float64, x)
+
+    def medium_terms_v(self, rays, spheres, density, addr, seed):
+        """what medium_hit decides on for n (ray, sphere {centre, radius}, density, address {pixel, node, sphere index}) -> n x 8 {disc, t1,
+        t2, inside, u, dist, fast, stage} (lane_sim.cpp medium_terms_v; stage 0: no disc, 1: no t_in < t2, 2: dist > inside, 3: a candidate)"""
+        rays, spheres, density, addr = _arr(rays), _arr(spheres), _arr(density), _arr(addr, np.uint32)
+        assert rays.shape == (len(rays), 6) and spheres.shape == (len(rays), 4) and density.shape == (len(rays),) and addr.shape == (len(rays), 3)
+        out = np.zeros((len(rays), 8))
+        self.L.medium_terms_v(rays.ctypes.data, spheres.ctypes.data, density.ctypes.data, addr.ctypes.data, seed, len(rays), out.ctypes.data)
+        return out
 
     def solid_checker_v(self, p):
         return self._vec(self.L.solid_checker_v, np.int32, p)

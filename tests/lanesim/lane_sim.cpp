@@ -151,6 +151,40 @@ extern "C" void medium_neg_log_v(const double* x, uint64_t n, double* out) {
   for (uint64_t i = 0; i < n; ++i) out[i] = rt_neg_log(x[i]);
 }
 
+// What medium_hit (rt_core.h) decides on, for tests/medium_rays.py to aim its rays with and to state its classes' conditions on: the
+// functions medium_hit calls, in its order, for n (ray, sphere, density) triples.  rays = n x 6, spheres = n x 4 {centre, radius}, addr = n x 3
+// {pixel, node, sphere index}.  out = n x 8: {disc, t1, t2, inside, u, dist, |d|^2 takes ray_consts' fast path (1 / 0), stage}, stage = 0: disc
+// is not >= 0; 1: not t_in < t2; 2: not dist <= inside; 3: a candidate (t_in + dist / len).  The answer itself the tests take from
+// hit_world, which calls medium_hit.
+extern "C" void medium_terms_v(const double* rays, const double* spheres, const double* density, const uint32_t* addr, uint64_t seed, uint64_t n, double* out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    double* r = out + 8 * i;
+    for (int k = 0; k < 8; ++k) r[k] = 0.0;
+    const RayK rk = ray_consts(d);
+    r[6] = rk.fast ? 1.0 : 0.0;
+    const V3 oc = sub(o, v3(spheres[4 * i], spheres[4 * i + 1], spheres[4 * i + 2]));
+    const double half_b = dot(oc, d);
+    const double c = length_squared(oc) - spheres[4 * i + 3] * spheres[4 * i + 3];
+    const double disc = (half_b * half_b) - (rk.a * c);
+    r[0] = disc;
+    if (!(disc >= 0.0)) continue;
+    const double sq = rt_sqrt(disc);
+    const double t1 = ((-half_b) - sq) / rk.a, t2 = ((-half_b) + sq) / rk.a;
+    const double t_in = t1 > T_MIN ? t1 : T_MIN;
+    r[1] = t1; r[2] = t2; r[7] = 1.0;
+    if (!(t_in < t2)) continue;
+    const double len = rt_sqrt(rk.a);
+    const double inside = (t2 - t_in) * len;
+    const U4 w = rng(RngAddr{addr[3 * i], 0u, (uint32_t)seed, (uint32_t)(seed >> 32)}, addr[3 * i + 1], MEDIUM_SLOT | addr[3 * i + 2]);
+    const double u = u01_53(w.x, w.y);
+    const double dist = rt_neg_log(1.0 - u) / density[i];
+    r[3] = inside; r[4] = u; r[5] = dist; r[7] = 2.0;
+    if (!(dist <= inside)) continue;
+    r[7] = 3.0;
+  }
+}
+
 // ------------------------------------------------------------------ rt_solid.h: p = n x 3 points already in the sphere's frame and scaled
 extern "C" void solid_checker_v(const double* p, uint64_t n, int32_t* out) {
   for (uint64_t i = 0; i < n; ++i) out[i] = rt_solid_checker_odd(p[3 * i], p[3 * i + 1], p[3 * i + 2]);

@@ -35,7 +35,8 @@ def test_every_declared_symbol_is_exported_by_its_library(pkg):
         if n not in HOST_SYMS:
             assert hasattr(probe, n), f"{n} not exported by the probe library"
     lab = declared_functions("rt_abi_test.h")
-    assert len(lab) == 10 and "rt_hip_quad_probe" in lab and not (lab & names), sorted(lab)
+    assert len(lab) == 14 and not (lab & names), sorted(lab)
+    assert {"rt_hip_quad_probe", "rt_hip_neg_log_probe", "rt_hip_solid_fn_probe", "rt_hip_solid_probe", "rt_hip_medium_probe"} <= lab, sorted(lab)
     for n in sorted(lab):
         assert hasattr(probe, n), f"{n} not exported by librt_hip_probe.so"
         assert not hasattr(hip, n) and not hasattr(host, n), f"{n} is exported by a product library"

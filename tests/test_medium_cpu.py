@@ -1,6 +1,7 @@
-"""Participating media without a GPU: the schema, rt_neg_log built for the host, and rt_tables.h + hit_world_grid with
-media (tests/lanesim, a g++ build) against a brute force of the contract restated in tests/medium_mini.py."""
-import ctypes as C
+"""Participating media without a GPU: the schema, rt_neg_log built for the host against the restatement and against
+correctly rounded values (tests/golden/neg_log_cr.npz), and rt_tables.h + hit_world_grid with media (tests/lanesim, a g++ build) against a
+brute force of the contract restated in tests/medium_mini.py — on the adversarial walk worlds and on the ray classes of
+tests/medium_rays.py, whose conditions are stated here and which tests/test_medium_rays_gpu.py puts through the device."""
 import json
 import math
 import os
@@ -11,6 +12,7 @@ import pytest
 import adversarial_rays as AR
 import lane_sim
 import medium_mini as MM
+import medium_rays as MR
 import mini_oracle as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,106 +71,89 @@ def medium_walk(abi):
     return lane_sim.load(abi)
 
 
-# rt_neg_log's error against the platform's log, measured on the argument set below: 1.000 ulp at worst.  The routine's
-# own analysis promises below 1 ulp; asserted with one ulp of margin.
-NEG_LOG_MAX_ULP = 2.0
+NEG_LOG_FIXTURE = os.path.join(ROOT, "tests", "golden", "neg_log_cr.npz")
 
 
-def test_neg_log_bits_accuracy_and_zero(medium_walk):
-    """the host build of rt_neg_log is the Python restatement bit for bit on 10^6 arguments 1 - k 2^-53 (random k over every
-    magnitude, the smallest and the largest k) and the extremes; within NEG_LOG_MAX_ULP of math.log; +0.0 at 1.0"""
+def neg_log_arguments():
+    """the 10^6 arguments of the bit test (and of the device's): 1 - k 2^-53 with random k over every magnitude, the smallest and the largest
+    k, and the extremes"""
     rng = np.random.default_rng(1503)
     k = np.concatenate([rng.integers(1, 1 << 53, 600_000, dtype=np.uint64),
                         (rng.integers(1, 1 << 53, 300_000, dtype=np.uint64) >> rng.integers(0, 52, 300_000).astype(np.uint64)) | np.uint64(1),
                         np.arange(1, 50_001, dtype=np.uint64), np.uint64((1 << 53) - 1) - np.arange(0, 50_000, dtype=np.uint64)])
     x = 1.0 - k.astype(np.float64) * 2.0 ** -53      # (exact: k < 2^53, and 1 - k 2^-53 is a multiple of 2^-53 below 1)
-    x = np.concatenate([x, [2.0 ** -53, 1.0 - 2.0 ** -53, 1.0, 0.5, 2.0 ** -0.5, np.nextafter(2.0 ** -0.5, 0.0)]])
+    return np.concatenate([x, [2.0 ** -53, 1.0 - 2.0 ** -53, 1.0, 0.5, 2.0 ** -0.5, np.nextafter(2.0 ** -0.5, 0.0)]])
+
+
+def neg_log_fixture():
+    """-> the fixture's arguments, the correctly rounded -ln x, (true value - rounded) / ulp(rounded), [(category, count)]"""
+    z = np.load(NEG_LOG_FIXTURE)
+    return z["x_bits"].view(np.float64), z["neg_log"], z["residual_ulp"].astype(np.float64), [(c.split(":")[0], int(c.split(":")[1])) for c in z["categories"].tolist()]
+
+
+def neg_log_error_ulp(out, cr, residual):
+    """the error of `out` against the TRUE -ln x, in ulps of the correctly rounded value: out - cr is exact for neighbouring doubles, and the
+    true value is cr + residual ulps"""
+    return np.abs((out - cr) / np.spacing(np.abs(cr)) - residual)
+
+
+def test_neg_log_bits_accuracy_and_zero(medium_walk):
+    """the host build of rt_neg_log is the Python restatement bit for bit on 10^6 arguments 1 - k 2^-53 (random k over every
+    magnitude, the smallest and the largest k) and the extremes, and on the arguments of tests/golden/neg_log_cr.npz; against that
+    fixture's correctly rounded values (mpmath at 200 bits) its error stays below 1 ulp, the header's own claim; the special values are
+    exact"""
+    x = neg_log_arguments()
     assert len(x) >= 1_000_000 and (x > 0.0).all()
     out = medium_walk.medium_neg_log_v(x)
-    worst = 0.0
     for xi, oi in zip(x.tolist(), out.tolist()):
         r = MM.neg_log(xi)
         assert r == oi and math.copysign(1.0, r) == math.copysign(1.0, oi), (xi, r, oi)
-        if xi != 1.0:
-            ref = -math.log(xi)
-            worst = max(worst, abs(oi - ref) / math.ulp(ref))
-    print(f"rt_neg_log: worst error against math.log {worst:.3f} ulp over {len(x)} arguments")
-    assert worst <= NEG_LOG_MAX_ULP, worst
-    res = medium_walk.medium_neg_log_v(np.array([1.0]))
-    assert res[0] == 0.0 and math.copysign(1.0, res[0]) == 1.0 and math.copysign(1.0, MM.neg_log(1.0)) == 1.0
+    fx, cr, residual, cats = neg_log_fixture()
+    assert 25_000 <= len(fx) <= 60_000 and os.path.getsize(NEG_LOG_FIXTURE) < 512 * 1024 and (np.abs(residual) <= 0.5).all()
+    assert dict(cats)["smallest"] == 5000 and dict(cats)["largest"] == 5000 and dict(cats)["sqrt2"] == 5 * 53 and dict(cats)["subnormal"] == 10
+    fo = medium_walk.medium_neg_log_v(fx)
+    for xi, oi in zip(fx.tolist(), fo.tolist()):
+        r = MM.neg_log(xi)
+        assert r == oi and math.copysign(1.0, r) == math.copysign(1.0, oi), (xi, r, oi)
+    err = neg_log_error_ulp(fo, cr, residual)
+    at = int(np.argmax(err))
+    print(f"rt_neg_log: worst error against the true value {err[at]:.3f} ulp at {float(fx[at]).hex()} over {len(fx)} arguments; "
+          f"{100.0 * (fo == cr).mean():.1f} % correctly rounded")
+    k = 0
+    for name, count in cats:
+        print(f"  {name}: worst {err[k:k + count].max():.3f} ulp, {100.0 * (fo[k:k + count] == cr[k:k + count]).mean():.1f} % correctly rounded")
+        k += count
+    assert err.max() < 1.0, (err[at], float(fx[at]).hex())
+    with np.errstate(all="ignore"):
+        sp = medium_walk.medium_neg_log_v(np.array([0.0, -0.0, -1.0, -5e-324, -np.inf, np.nan, np.inf, 1.0]))
+    assert sp[0] == np.inf and sp[1] == np.inf and np.isnan(sp[2:6]).all() and sp[6] == -np.inf
+    assert sp[7] == 0.0 and math.copysign(1.0, sp[7]) == 1.0 and math.copysign(1.0, MM.neg_log(1.0)) == 1.0
+    assert MM.neg_log(0.0) == math.inf and math.isnan(MM.neg_log(-1.0)) and math.isnan(MM.neg_log(math.nan)) and MM.neg_log(math.inf) == -math.inf
 
 
-def _inside_rays(rng, centres, radii, media, count):
-    """rays whose origin lies deep inside a medium (within 0.4 r of its centre: cells fully inside the ball for the big ones), short
-    and long directions"""
-    rays = np.zeros((count, 6))
-    for k in range(count):
-        j = int(media[k % len(media)])
-        n = rng.standard_normal(3); n /= np.linalg.norm(n)
-        rays[k, :3] = centres[j] + n * radii[j] * rng.uniform(0.0, 0.4)
-        rays[k, 3:] = rng.standard_normal(3) * 10.0 ** rng.uniform(-2, 2)
-    return rays
+def test_neg_log_fixture_is_what_its_generator_writes():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_neg_log_fixture", os.path.join(ROOT, "tests", "golden", "make_neg_log_fixture.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.fixture_bytes()[0] == open(NEG_LOG_FIXTURE, "rb").read()
 
 
-def _through_rays(rng, centres, radii, media, count):
-    """rays from outside aimed through the heart of a medium: with a small density the candidate lies several cells past the first
-    cell that lists the sphere"""
-    rays = np.zeros((count, 6))
-    for k in range(count):
-        j = int(media[k % len(media)])
-        n = rng.standard_normal(3); n /= np.linalg.norm(n)
-        o = centres[j] + n * radii[j] * rng.uniform(1.5, 6.0)
-        rays[k, :3] = o
-        rays[k, 3:] = (centres[j] + rng.uniform(-0.3, 0.3, 3) * radii[j] - o) * rng.uniform(0.2, 2.0)
-    return rays
-
-
-WALK_WORLDS = {
-    # (adversarial world, moving, environment): static / moving media, the packed tables and the wide ones
-    "static": (0, False, {}),
-    "static_ground": (1, False, {}),
-    "big_radii": (3, False, {}),
-    "moving": (0, True, {}),
-    "moving_layer": (4, True, {}),
-    "wide_tables": (0, False, {"RT_GRID_WIDE": "1"}),
-    "thin_cells": (3, False, {"RT_GRID_N": "48,48,48"}),
-}
+WALK_WORLDS = MR.WALK_WORLDS          # (the worlds, their ray tables and the two ray helpers live in tests/medium_rays.py: the device test walks them too)
 
 
 @pytest.mark.parametrize("name", sorted(WALK_WORLDS))
 def test_grid_walk_with_media_equals_brute_force(abi, medium_walk, monkeypatch, name):
     """hit_world_grid with a MediumCtx (CPU build) against the brute force of the contract, bit for bit on (t, index): the ray families
     of tests/adversarial_rays.py, rays that start deep inside a medium, and rays whose candidate lies cells past the first listing"""
-    wi, moving, env = WALK_WORLDS[name]
-    for k, v in env.items():
+    wd = MR.WalkWorld(abi, name)
+    for k, v in wd.env.items():
         monkeypatch.setenv(k, v)
-    rng = np.random.default_rng(9100 + sorted(WALK_WORLDS).index(name))
-    sc, spheres, n = AR.adversarial_world(abi, rng, wi)
-    sc.seed = 0x1234567 + wi
-    tot = len(spheres)
-    # a quarter of the ordinary spheres become media (positive radius), some thin and some dense; three of them are made BIG so
-    # that they cover many cells, interior ones included
-    media = [i for i in range(n) if i % 4 == 1]
-    for i in media:
-        spheres[i].radius = abs(spheres[i].radius)
-        spheres[i].kind = abi.RT_MAT_MEDIUM
-        spheres[i].fuzz_or_ior = float(10.0 ** rng.uniform(-1.5, 1.5))
-        spheres[i].albedo[:] = [0.5, 0.5, 0.5]
-    for i in media[:3]:
-        spheres[i].radius = spheres[i].radius * 4.0 + 1.0
-        spheres[i].fuzz_or_ior = float(rng.uniform(0.05, 0.3))
-    c0, radii = AR.sphere_arrays(spheres, tot)
-    dens = np.array([spheres[i].fuzz_or_ior if spheres[i].kind == abi.RT_MAT_MEDIUM else 0.0 for i in range(tot)])
-    c1 = c0.copy()
-    if moving:
-        for i in range(n):
-            if i % 3 != 2:
-                c1[i] = c0[i] + rng.uniform(-0.7, 0.7, 3)
-    c1c = np.ascontiguousarray(c1) if moving else None
-    rc, info, listed, is_large = medium_walk.medium_tables(sc, c1c)
+    sc, n, media, moving, c0, radii, dens = wd.sc, wd.n, wd.media, wd.moving, wd.c0, wd.radii, wd.dens
+    rc, info, listed, is_large = medium_walk.medium_tables(sc, wd.c1c)
     assert rc == 0
     assert info[0] == len(media) and info[1] > 0, "the world must be gridded and know its media"
-    assert bool(info[6]) == ("RT_GRID_WIDE" in env)
+    assert bool(info[6]) == ("RT_GRID_WIDE" in wd.env)
     # interior cells are kept: a big static medium in the grid is listed in about as many cells as its ball overlaps
     if not moving:
         cell = (c0[:n].max(0) - c0[:n].min(0) + 2 * np.abs(radii[:n]).max()) / info[1:4]
@@ -176,26 +161,12 @@ def test_grid_walk_with_media_equals_brute_force(abi, medium_walk, monkeypatch, 
             if not is_large[i]:
                 ball_cells = 4.0 / 3.0 * math.pi * radii[i] ** 3 / float(np.prod(cell))
                 assert listed[i] >= 0.5 * ball_cells, (i, listed[i], ball_cells)
-    dv = np.where(c1 == c0, -0.0, c1 - c0)
-    blocks = []
-    for tau in ([0.0] if not moving else [0.0, 1.0 - 2.0 ** -24, float(np.float32(rng.integers(0, 1 << 24) * 2.0 ** -24))]):
-        ct = c0 + dv * np.float64(tau)
-        moved = (abi.RtSphere * tot)()
-        C.memmove(moved, spheres, C.sizeof(moved))
-        for i in range(tot):
-            moved[i].center[:] = list(ct[i])
-        per = 84 if moving else 210
-        rays = np.concatenate([AR.ray_table(rng, moved, n, per, list(range(AR.FAMILIES)))[0],
-                               _inside_rays(rng, ct, radii, media, per // 3), _through_rays(rng, ct, radii, media, per // 3)])
-        blocks.append((tau, ct, rays))
-    rays = np.ascontiguousarray(np.concatenate([b[2] for b in blocks]))
-    tau_v = np.concatenate([np.full(len(b[2]), b[0], np.float32) for b in blocks])
-    nodes = np.ascontiguousarray(rng.choice(np.array([0, 1, 7, 0x80000002, 0xFFFFFFFE], np.uint32), len(rays)))
-    rc, best, t, work = medium_walk.hit_world_v(sc, rays, c1c, tau=tau_v, node=nodes)
+    rays, nodes = wd.rays, wd.nodes
+    rc, best, t, work = medium_walk.hit_world_v(sc, rays, wd.c1c, tau=wd.tau, node=nodes)
     assert rc == 0
     k = 0
     n_medium_hits = 0
-    for tau, ct, rr in blocks:
+    for tau, ct, rr in wd.blocks:
         # (the brute force addresses ray i of the whole table: pixel = its index there)
         idx = np.arange(k, k + len(rr))
         bb, tb = _brute_at(rr, idx, nodes[k:k + len(rr)], ct, radii, dens, sc.seed)
@@ -208,13 +179,114 @@ def test_grid_walk_with_media_equals_brute_force(abi, medium_walk, monkeypatch, 
     assert (work[:, 1] > 2).mean() > 0.1                          # (and the walks do step through cells)
 
 
-def _brute_at(rays, pixels, nodes, centres, radii, dens, seed):
+# ------------------------------------------------------------------ the classes of tests/medium_rays.py (the device test's tables)
+def _class_stats(cls, abi, L):
+    ref = MR.class_reference(cls, abi, L)
+    T = ref.terms
+    return ref, T, T[:, 7], ref.best >= 0
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+@pytest.mark.parametrize("cls", MR.CLASSES)
+def test_class_tables_straddle_their_decisions(abi, medium_walk, cls):
+    """the conditions tests/medium_rays.py's classes are drawn for, on the host build: hit_world_v's answer and medium_terms_v's figures for
+    the sphere each ray is aimed at (stage 0: no discriminant, 1: not t_in < t2, 2: dist > inside, 3: a candidate)"""
+    worlds = MR.class_worlds(cls, medium_walk)
+    assert len(worlds) == MR.N_W and all(w.rays.shape == (MR.N_R, 6) and set(w.nodes.tolist()) <= set(MR.NODES.tolist()) for w in worlds)
+    assert len({w.seed for w in worlds}) == MR.N_W and any(w.seed >> 32 for w in worlds)
+    assert set(np.concatenate([w.nodes for w in worlds]).tolist()) == set(MR.NODES.tolist())
+    assert all(1 <= int(w.is_medium().sum()) <= 2 for w in worlds) or cls == "boundary_density"
+    ref, T, stage, hit = _class_stats(cls, abi, medium_walk)
+    n = len(stage)
+    assert n == MR.N_W * MR.N_R
+    took = ref.took.mean()
+    print(f"{cls}: {100 * took:.1f} % of the rays take a medium, {100 * hit.mean():.1f} % hit; stages {[round(float((stage == k).mean()), 3) for k in range(4)]}")
+    finite = np.concatenate([np.isfinite(w.rays).all(axis=1) for w in worlds])
+    assert finite.all() == (cls != "non_finite")
+    if cls in MR.FRAME_CLASSES:
+        assert all(np.abs(w.rays).max() < 1e3 for w in worlds), "a frame may be given these rays"
+    if cls == "generic":
+        assert 0.05 < took < 0.95
+        inside = np.concatenate([np.linalg.norm(w.rays[:, :3] - w.spheres4()[:, :3], axis=1) < w.spheres4()[:, 3] for w in worlds])
+        assert 0.3 < inside.mean() < 0.7, "origins outside and inside"
+    if cls == "tangent":
+        assert (T[:, 0] >= 0.0).mean() >= 0.20 and (T[:, 0] < 0.0).mean() >= 0.20, ((T[:, 0] >= 0.0).mean(), (T[:, 0] < 0.0).mean())
+        assert (T[:, 0] == 0.0).sum() >= 5000 and ((np.abs(T[:, 0]) < 2.0 ** -1022) & (T[:, 0] != 0.0)).sum() >= 5000, "discriminants that are 0, and denormal ones"
+        assert took >= 0.1, "and where there is a chord, the dense medium takes the ray"
+    if cls == "surface_origin":
+        has = stage >= 1
+        above = has & (T[:, 1] > MR.T_MIN)
+        assert has.all() and above.mean() >= 0.20 and (has & ~above).mean() >= 0.20 and (stage == 1).mean() >= 0.10, (above.mean(), (stage == 1).mean())
+        ulps1, ulps2 = np.abs(T[:, 1] - MR.T_MIN) / np.spacing(MR.T_MIN), np.abs(T[:, 2] - MR.T_MIN) / np.spacing(MR.T_MIN)
+        assert (ulps1 <= 4.0).mean() >= 0.15 and (ulps2 <= 4.0).mean() >= 0.10 and (T[:, 1] == MR.T_MIN).any() and (T[:, 2] == MR.T_MIN).any()
+        fam = np.concatenate([w.notes["fam"] for w in worlds])
+        assert ((T[:, 2] - np.maximum(T[:, 1], 0.0)) < MR.T_MIN)[fam == 2].mean() > 0.9, "the short chords are shorter than T_MIN"
+    if cls == "boundary_density":
+        aimed = np.concatenate([w.notes["aimed"] for w in worlds])
+        assert aimed.mean() > 0.99 and (stage == 3).mean() >= 0.30 and (stage == 2).mean() >= 0.30, ((stage == 3).mean(), (stage == 2).mean())
+        off = (T[:, 5] - T[:, 3]) / np.spacing(T[:, 3])
+        assert (np.abs(off[aimed]) <= 8.0).all() and (off[aimed] == 0.0).mean() >= 0.1, "dist lies within a few ulps of the chord, and on it"
+        assert all(len(w.objs) == MR.N_R for w in worlds)
+    if cls == "magnitudes":
+        assert (T[:, 6] == 0.0).mean() >= 0.10 and took >= 0.05, ((T[:, 6] == 0.0).mean(), took)
+        assert (ref.took & (T[:, 6] == 0.0)).sum() >= 1000, "rays on ray_consts' slow path do take media"
+    if cls == "occluder_inside":
+        assert hit.mean() > 0.9 and 0.30 <= ref.took[hit].mean() <= 0.70, ref.took[hit].mean()
+    if cls == "nested":
+        inner = np.concatenate([np.full(MR.N_R, w.notes["inner"]) for w in worlds])
+        assert (ref.best == inner).mean() >= 0.15 and (hit & (ref.best != inner)).mean() >= 0.15 and (~hit).mean() >= 0.02
+        assert all((ref.best[w * MR.N_R:(w + 1) * MR.N_R] == k).any() for w in range(MR.N_W) for k in (0, 1)), "in either table order"
+    if cls in ("tangent", "surface_origin"):       # one medium and nothing else: hit_world takes it exactly where medium_terms_v has a candidate
+        assert np.array_equal(ref.took, (stage == 3) & (T[:, 5] > 0.0))
+
+
+SUBSET_PER_WORLD = 20            # rays 0, 50, 100 ... of every world: 2 000 inputs of a class, all of its worlds among them
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+@pytest.mark.parametrize("cls", MR.CLASSES)
+def test_new_classes_host_build_equals_the_restatement(abi, medium_walk, cls):
+    """hit_world_v (the host build of hit_world_grid<true>) against the brute force over tests/medium_mini.py's medium_candidate on 20 rays of
+    each of the class's 100 worlds: (index, bits of t).  Every world carries its class's edge, so every world is in the subset."""
+    ref = MR.class_reference(cls, abi, medium_walk)
+    rows = np.arange(0, MR.N_R, MR.N_R // SUBSET_PER_WORLD)
+    checked = took = 0
+    for w, wd in enumerate(MR.class_worlds(cls, medium_walk)):
+        centres = np.array([o[0] for o in wd.objs], np.float64)
+        radii = np.array([o[1] for o in wd.objs], np.float64)
+        dens = np.array([o[3] if o[2] == "medium" else 0.0 for o in wd.objs], np.float64)
+        bb, tb = _brute_at(wd.rays[rows], rows, wd.nodes[rows], centres, radii, dens, wd.seed, sparse=True)
+        g_b, g_t = ref.best[w * MR.N_R + rows], ref.t[w * MR.N_R + rows]
+        bad = np.nonzero((g_b != bb) | (g_t.view(np.uint64) != tb.view(np.uint64)))[0]
+        assert len(bad) == 0, (cls, w, rows[bad[:5]], g_b[bad[:5]], bb[bad[:5]], g_t[bad[:5]], tb[bad[:5]])
+        checked += len(rows)
+        took += int((dens[np.maximum(bb, 0)] > 0.0)[bb >= 0].sum())
+    assert checked >= 2000
+    if cls != "non_finite":
+        assert took >= 0.05 * checked, took
+
+
+def _disc_ok(o, d, centres, radii):
+    """where Sphere::hit's discriminant is >= 0 (n x m), with sphere_hit_t's operations: where a medium can have a candidate at all"""
+    dx, dy, dz = (d[:, k:k + 1] for k in range(3))
+    a = (dx * dx + dy * dy) + dz * dz
+    ocx, ocy, ocz = (o[:, k:k + 1] - centres[None, :, k] for k in range(3))
+    half_b = (ocx * dx + ocy * dy) + ocz * dz
+    c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - radii[None, :] * radii[None, :]
+    return (half_b * half_b) - (a * c) >= 0.0
+
+
+def _brute_at(rays, pixels, nodes, centres, radii, dens, seed, sparse=False):
+    """sparse: the restatement runs only where numpy finds a discriminant >= 0 (it returns None elsewhere: a world of 1 000 media)"""
     n = len(rays)
-    t_all = AR.sphere_hit_t(rays[:, :3], rays[:, 3:], centres, radii)
+    with np.errstate(all="ignore"):
+        t_all = AR.sphere_hit_t(rays[:, :3], rays[:, 3:], centres, radii)
+        may = _disc_ok(rays[:, :3], rays[:, 3:], centres, radii) if sparse else np.ones((n, len(radii)), bool)
     k0, k1 = seed & M.M32, (seed >> 32) & M.M32
     for j in np.nonzero(dens > 0.0)[0]:
         c, r, den = tuple(float(v) for v in centres[j]), float(radii[j]), float(dens[j])
-        for i in range(n):
+        t_all[:, j] = np.inf
+        for i in np.nonzero(may[:, j])[0]:
             w = M.philox4x32_10(int(pixels[i]), 0, int(nodes[i]), MM.MEDIUM_SLOT | int(j), k0, k1)
             t = MM.medium_candidate(tuple(float(v) for v in rays[i, :3]), tuple(float(v) for v in rays[i, 3:]), c, r, den, M.u01_53(w[0], w[1]))
             t_all[i, j] = t if (t is not None and t > MM.T_MIN) else np.inf

@@ -1,5 +1,6 @@
 """Solid textures without a GPU: the schema, csrc/common/rt_solid.h built for the host against the restatement of
-tests/solid_mini.py bit for bit and against properties that need no restatement, and a CPU build of the SOLID lane code
+tests/solid_mini.py bit for bit (on the point classes of tests/solid_points.py, which tests/test_solid_points_gpu.py puts through the
+device) and against properties that need no restatement, and a CPU build of the SOLID lane code
 (tests/lanesim, a g++ build) against SolidMini on the frames of the GPU parity test."""
 import json
 import math
@@ -10,6 +11,8 @@ import pytest
 
 import lane_sim
 import solid_mini as SM
+import solid_points as SP
+from solid_points import MODES, mixed as _points      # (the point table this file always drew: now class `mixed` of tests/solid_points.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOLID_SCENE = os.path.join(ROOT, "scenes", "cover_solid_1200x800_spp128.json")
@@ -106,28 +109,6 @@ def solid_sim(abi):
     return lane_sim.load(abi)
 
 
-def _points(rng, n):
-    """n points: mostly a few cells around the origin (negative coordinates included), some on lattice planes (t_c = 0), some of every
-    magnitude, some around +-2^31 and +-2^52, some non-finite"""
-    p = rng.uniform(-40.0, 40.0, (n, 3))
-    k = n // 10
-    p[:k] = np.round(p[:k]) + rng.uniform(0.0, 1.0, (k, 3)) * (rng.random((k, 3)) < 0.5)                 # whole coordinates
-    p[k:2 * k] = rng.standard_normal((k, 3)) * 10.0 ** rng.uniform(-8, 12, (k, 1))                      # every magnitude
-    edge = np.array([2.0 ** 31, -2.0 ** 31, np.nextafter(2.0 ** 31, 0.0), -np.nextafter(2.0 ** 31, 0.0), np.nextafter(2.0 ** 31, np.inf),
-                     2.0 ** 31 - 0.5, -2.0 ** 31 + 0.5, 2.0 ** 30, 2.0 ** 52, -2.0 ** 52, np.nextafter(2.0 ** 52, 0.0), -np.nextafter(2.0 ** 52, 0.0),
-                     2.0 ** 52 - 1.0, 2.0 ** 52 + 2.0, 2.0 ** 53, -2.0 ** 63, np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-310, -1e-310, -1.0, 1.0, 0.5])
-    m = 2 * k
-    sel = rng.integers(0, len(edge), (k, 3))
-    p[m:m + k] = np.where(rng.random((k, 3)) < 0.4, edge[sel], p[m:m + k])
-    for j, e in enumerate(edge):                        # every edge value on every axis at least once
-        for c in range(3):
-            p[m + k + 3 * j + c, c] = e
-    return p
-
-
-MODES = [(SM.MODE_NOISE, 7), (SM.MODE_TURBULENCE, 1), (SM.MODE_TURBULENCE, 16), (SM.MODE_MARBLE, 1), (SM.MODE_MARBLE, 16)]
-
-
 @pytest.mark.parametrize("mode,octaves", MODES)
 def test_host_build_equals_the_restatement_bit_for_bit(solid_sim, mode, octaves):
     """>= 10^5 points per mode through rt_solid_noise_factor: 105 000 for noise, 2 x 52 500 for turbulence and for marble (octaves 1 and
@@ -157,6 +138,115 @@ def test_noise_and_checker_equal_the_restatement_bit_for_bit(solid_sim):
     want = np.array([SM.checker_parity(tuple(pt)) for pt in p.tolist()], np.int32)
     assert np.array_equal(got, want), np.nonzero(got != want)[0][:5]
     assert 0.3 < got.mean() < 0.6
+
+
+# ------------------------------------------------------------------ the classes of tests/solid_points.py (the device test's tables)
+# sha256 of mixed(default_rng(seed), n) as this file drew it before the function moved: the tables of the two tests above
+MIXED_SHA256 = {(1616, 100_000): "a24b2baf6490555a6c70e917d7749be9d7910143dd87bdd676ec8635604cb955",
+                (1607, 105_000): "b823fd8923660997caf5f10c301eb27fa3f38266668f211adc623bd35bc4acdc",
+                (1611, 52_500): "85808833db5195fd118c36f2118fcbdcea3e911795b953d715c133cf12dad32e",
+                (1626, 52_500): "a230baeda3219d58db5bd7fb50ad5225b5d3ef26e8f46c81c2fb4fc94e84a1d4",
+                (1621, 52_500): "57a3546c3736619c16ebd6b8914e6d2de6cfc412c65492e845d278c208ca09bb",
+                (1636, 52_500): "b1a22df66c657147495ce059821f4ef0c854ea2bb9a62a677e2829992f6ffcd0"}
+
+
+def test_mixed_is_the_table_this_file_always_drew():
+    import hashlib
+    for (seed, n), want in MIXED_SHA256.items():
+        assert hashlib.sha256(_points(np.random.default_rng(seed), n).tobytes()).hexdigest() == want, (seed, n)
+    assert {(1600 + 10 * m + o, 105_000 if m == SM.MODE_NOISE else 52_500) for m, o in MODES} | {(1616, 100_000)} == set(MIXED_SHA256)
+    assert SP.class_points("mixed").tobytes() == _points(np.random.default_rng(1616), 100_000).tobytes()
+
+
+def test_class_tables_reach_their_edges():
+    """the conditions tests/solid_points.py states for its classes, in numpy on the tables themselves"""
+    for cls in SP.CLASSES:
+        p = SP.class_points(cls)
+        assert len(p) >= 100_000 and p.shape[1] == 3 and not p.flags.writeable, cls
+        assert len(SP.subset(cls)) >= 2000 and np.isin(SP.edge_rows(cls), SP.subset(cls)).all(), cls
+    # tiny_negative: -2^-k on one axis or on all; t = p - floor(p) is exactly 1.0 from k = 54 on and below 1.0 up to k = 53
+    p, k, ax = SP.class_points("tiny_negative"), SP.tiny_k(), SP.tiny_axes()
+    assert set(k[:SP.TINY_ROUND].tolist()) == set(range(1, 1075)) and (ax.sum(axis=1) == 3).sum() == len(p) // 4
+    assert (p[ax] == np.repeat(-np.ldexp(1.0, -k), ax.sum(axis=1))).all() and (np.floor(p[ax]) == -1.0).all()
+    t = (p - np.floor(p))
+    one = (t == 1.0) & ax
+    assert (one.any(axis=1) == (k >= 54)).all() and (t[ax & (k <= 53)[:, None]] < 1.0).all() and not (t[~ax] >= 1.0).any()
+    assert (k >= 54).mean() >= 0.25 and (k <= 52).mean() >= 0.25, ((k >= 54).mean(), (k <= 52).mean())
+    # octave_overflow: the first octave whose |p 2^j| reaches 2^31 is j at and one ulp outside 2^(31 - j), and j + 1 one ulp inside it
+    p = SP.class_points("octave_overflow")
+    j, sign, side, axis = (np.tile(a, SP.OCT_ROUNDS) for a in SP.octave_layout())
+    big = np.abs(p).max(axis=1)
+    assert (big == np.abs(p[np.arange(len(p)), axis])).all()
+    first = np.full(len(p), 99)
+    for o in range(17, -1, -1):
+        first[big * 2.0 ** o >= SP.TWO31] = np.minimum(first[big * 2.0 ** o >= SP.TWO31], o)
+    assert (first[side >= 0] == j[side >= 0]).all() and (first[side < 0] == j[side < 0] + 1).all()
+    for octaves in (1, 8, 16):
+        for o in range(octaves):
+            assert ((first == o) & (side >= 0)).sum() >= 1000 and ((j == o) & (side < 0) & (first == o + 1)).sum() >= 500, (octaves, o)
+    # int32_wrap: floors at the ends of the int32 range with the three fractions; i + 1 wraps to 0x80000000 where floor = 2^31 - 1
+    p = SP.class_points("int32_wrap")
+    f = np.floor(p)
+    at = np.isin(f, SP.WRAP_FLOORS)
+    assert at.any(axis=1).all() and np.isin((p - f)[at], SP.WRAP_FRACS).all()
+    assert {(a, b) for a, b in zip(f[at].tolist(), (p - f)[at].tolist())} == {(a, b) for a in SP.WRAP_FLOORS.tolist() for b in SP.WRAP_FRACS.tolist()}
+    inside = (np.abs(p) < SP.TWO31).all(axis=1)
+    wraps = inside & ((f.astype(np.int64) + 1) == 2 ** 31).any(axis=1)
+    assert wraps.mean() >= 0.10 and (inside & (f == -SP.TWO31).any(axis=1)).mean() >= 0.05, (wraps.mean(), inside.mean())
+    # lattice_marble: x, y whole, z whole or -2^-k; the phase's x - floor(x) is 0, just below 1.0, and rounds to 1.0
+    p = SP.class_points("lattice_marble")
+    z = p[:, 2]
+    assert (p[:, :2] == np.rint(p[:, :2])).all() and ((z == np.rint(z)) | ((z < 0.0) & (z >= -2.0 ** -70))).all()
+    assert {0.0, 1.0, -1.0, SP.TWO31 - 1.0, 1.0 - SP.TWO31} <= set(z.tolist()) and np.signbit(z[z == 0.0]).any() and not np.signbit(z[z == 0.0]).all()
+    x, s = SP.marble_phase(p)
+    near = np.isin(z, SP.near_whole_phases())
+    assert (s == 0.0).sum() >= 10 and (s == 1.0).sum() >= 1000 and (x[s == 1.0] < 0.0).all()
+    assert ((s < 1.0) & (s >= 1.0 - 2.0 ** -20) & near).sum() >= 1000 and ((s > 0.0) & (s <= 2.0 ** -20) & near).sum() >= 1000
+    assert (np.abs(x[near] - np.rint(x[near])) <= 4.0 * np.spacing(np.abs(x[near]))).all() and near.sum() >= 10_000
+    # checker_planes: the parity flips across the pairs below 2^52; everything at or beyond it is even
+    p = SP.class_points("checker_planes")
+    m = SP.PLANE_PAIRS
+    par = SP.numpy_parity(p)
+    flips = par[:m] != par[m:]
+    beyond = (np.abs(np.floor(p)) >= SP.TWO52).any(axis=1)
+    assert flips.mean() >= 0.45 and flips[106:SP.PLANE_BELOW].all(), flips.mean()
+    just_below = (p == np.nextafter(SP.TWO52, 0.0)).any(axis=1)           # (one ulp below +2^52 itself: 2^52 - 1/2, whose parity still counts)
+    assert beyond[m + SP.PLANE_BELOW:].all() and (beyond | just_below)[SP.PLANE_BELOW:m].all() and not par[beyond].any() and beyond.mean() >= 0.3
+    assert just_below.any() and par[just_below & ~beyond].any()
+    mags = np.abs(p[m:]).max(axis=1)
+    assert all(((mags >= 2.0 ** e) & (mags < 2.0 ** (e + 4))).sum() >= 100 for e in range(8, 52, 4))
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")
+@pytest.mark.parametrize("cls", [c for c in SP.CLASSES if c != "mixed"])
+def test_new_classes_host_build_equals_the_restatement_bit_for_bit(solid_sim, cls):
+    """>= 2 000 points of the class, the rows that carry its edge among them: rt_solid_noise_factor in every mode of the class, each set in
+    thirds over the three seeds; rt_solid_noise under each seed on a third; the checker parity — host build against tests/solid_mini.py, signs
+    of zero included.  lattice_marble: N is exactly 0 on the whole table, which is what makes its phase the one the table test looked at."""
+    p = SP.class_points(cls)
+    q = p[SP.subset(cls)]
+    assert len(q) >= 2000
+    same = lambda w, g: w == g and math.copysign(1.0, w) == math.copysign(1.0, g)
+    for mode, octaves in SP.class_modes(cls):
+        for j, seed in enumerate(SP.SEEDS):
+            part = q[j::3]
+            got = solid_sim.solid_factor_v(part, mode, octaves, seed)
+            for pt, g in zip(part.tolist(), got.tolist()):
+                assert same(SM.factor(tuple(pt), mode, octaves, seed), g), (cls, pt, mode, octaves, seed, g)
+    for j, seed in enumerate(SP.SEEDS):
+        part = q[j::3]
+        got = solid_sim.solid_noise_v(part, seed)
+        for pt, g in zip(part.tolist(), got.tolist()):
+            assert same(SM.noise(tuple(pt), seed), g), (cls, pt, seed, g)
+    got = solid_sim.solid_checker_v(q)
+    assert got.tolist() == [SM.checker_parity(tuple(pt)) for pt in q.tolist()]
+    assert np.array_equal(solid_sim.solid_checker_v(p), SP.numpy_parity(p)), "the table test's parity is the header's"
+    if cls == "lattice_marble":
+        for seed in SP.SEEDS:
+            assert not solid_sim.solid_noise_v(p, seed).any()
+            assert not solid_sim.solid_factor_v(p, SM.MODE_TURBULENCE, 16, seed).any()
+    if cls == "tiny_negative":          # where t rounds to 1.0 the point takes the far corner's value: still a number in range
+        assert np.isfinite(solid_sim.solid_noise_v(p, 0)).all() and np.abs(solid_sim.solid_noise_v(p, 0)).max() <= 1.5
 
 
 def test_noise_properties_without_the_restatement(solid_sim):
