@@ -270,6 +270,12 @@ const double* rt_scene_motion(const RtSceneFile*);
  * vertex, a degenerate (collinear) triangle (naming its face), mixed or duplicate keys, "center1"; more than RT_MAX_QUADS entries in
  * total is RT_ERR_UNSUPPORTED. */
 const RtQuad* rt_scene_quads(const RtSceneFile*, uint32_t* n);
+/* Shading normals (an extension too): "normals" inside a "mesh" (one [x, y, z] per vertex) or beside a "triangle" (three),
+ * or "smooth": true inside a "mesh" (per vertex the sum of cross(u_f, v_f) over the faces that use it, in face order).  *n x 9 f64, the
+ * normals at q, q + u, q + v of every entry of rt_scene_quads as written — not normalised; nine zeros for an entry without — what
+ * rt_hip_scene_set_flat_normals takes.  NULL and 0 when no entry has normals.  Owned by the RtSceneFile.  rt_scene_to_json writes a
+ * triangle that has normals as its exact q, u, v with "shape": "triangle" and "normals": load -> write -> load is bit for bit. */
+const double* rt_scene_flat_normals(const RtSceneFile*, uint32_t* n);
 /* The structure over the flat primitives (an extension too): a top-level "flat_bvh": true beside "camera" and "objects"
  * asks for rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh and lifts the loader's cap from RT_MAX_QUADS to RT_MAX_FLATS_BVH
  * (the entry that crosses it is still named by its objects[i]).  1 for such a file, 0 when the key is false or absent: today's behaviour.
@@ -484,6 +490,23 @@ int rt_hip_scene_update_spheres(RtHipScene*, const double* center, const double*
 #define RT_UPDATE_FLATS_REBUILD 1u   /* build the structure anew on the host: tables byte for byte creation's */
 #define RT_UPDATE_FLATS_DEVICE  2u   /* quv is device memory on the scene's device */
 int rt_hip_scene_update_flats(RtHipScene*, const double* quv, uint32_t n_quads, uint32_t flags);
+/* Shading normals on the triangles of a resident scene (the arithmetic is csrc/common/rt_flat_normal.h, bit for bit).
+ * normals = n_quads x 9 f64 in entry order: the normals at q, q + u and q + v of every entry, any length (they are normalised once,
+ * here); nine zeros: the entry shades flat.  n_quads must be the scene's.  NULL removes them: the scene is then, table for table and bit
+ * for bit, one that never had any.  Only shading changes: the hit test, t, ids, ties and front_face (the geometric normal's) are what
+ * they were, and a hit whose interpolated normal is degenerate, points through the face or away from the incoming ray takes the
+ * geometric normal.  The frames, rt_hip_render_aovs (the normal of the first hit) and the denoisers follow; the surface record of
+ * rt_hip_render_surface keeps what it held.  No kernel key changes: rt_hip_scene_query "last_kernel" is what it was.
+ * flags: 0, or RT_UPDATE_FLATS_DEVICE (normals is device memory on the scene's device, 8-byte aligned; only the status crosses back).
+ * Blocking; waits for the scene's unfinished launch and drops what rt_hip_scene_update_flats drops.  Scenes of
+ * rt_hip_scene_create_quads and rt_hip_scene_create_flats_bvh.  rt_hip_scene_update_flats and rt_hip_scene_update_spheres keep the
+ * normals as set (the per-hit side test makes stale normals safe; the caller sets new ones after moving geometry).
+ * rt_hip_scene_query "flat_normals" = the entries that have normals (0: none); rt_hip_scene_table "flat_normals" = the 72-byte records
+ * (unit vectors; empty without normals).  Every error is RT_ERR_INVALID: a null scene; another flag; n_quads different from the scene's;
+ * a scene without flat primitives; a vector that is not finite or whose squared length is zero, subnormal or not finite
+ * ("quad k: normal ..."), non-zero normals on a parallelogram ("quad k: normal ..."; of all bad entries the lowest k is reported); a
+ * scene whose tables a live view shares (rt_hip_group_set_flat_normals).  After any error the scene renders exactly as before. */
+int rt_hip_scene_set_flat_normals(RtHipScene*, const double* normals, uint32_t n_quads, uint32_t flags);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
  * camera of a resident scene — the four vectors of camera.rs:52-63 — without touching its tables,
  * and render whole frames of it into a host buffer (internal device framebuffer, blocking). */
@@ -807,6 +830,8 @@ int rt_hip_group_update_spheres(RtHipGroup*, const double* center, const double*
 /* rt_hip_scene_update_flats on every rank (each rank's tables are updated once; its second view follows them).  RT_ERR_INVALID while a
  * submitted frame is uncollected, and for RT_UPDATE_FLATS_DEVICE in a group whose ranks are on more than one device. */
 int rt_hip_group_update_flats(RtHipGroup*, const double* quv, uint32_t n_quads, uint32_t flags);
+/* rt_hip_scene_set_flat_normals on every rank, under the same two conditions. */
+int rt_hip_group_set_flat_normals(RtHipGroup*, const double* normals, uint32_t n_quads, uint32_t flags);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
  * tile height; *tile_rows_out receives that height (2) */

@@ -33,6 +33,7 @@
 #endif
 #include "../common/rt_solid.h"  // the one checker and lattice noise of the solid textures
 #include "../common/rt_quad.h"   // the one quad test
+#include "../common/rt_flat_normal.h"  // the one shading normal of a triangle
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__ __forceinline__
@@ -177,14 +178,18 @@ struct QuadView {
 // So DevScene keeps its size and the kernel arguments their offsets — every kernel without the QUADS arm is the code object it was —
 // and flats_hit_bvh takes ONE pointer and scalars: o, d and a 16-byte QuadView fill the 16 argument registers of quads_hit's call
 // exactly, and any aggregate beyond them travels through scratch (measured: DESIGN.md §22).
+// Shading normals: a scene whose n_tris carries FLAT_NORMALS_BIT has the header too — with or without the structure — and
+// in it the table of 72-byte records (rt_flat_normal.h), one per entry in ENTRY order.  Without the bit no kernel looks for it.
 constexpr uint32_t FLAT_BVH_BIT = 0x80000000u;
+constexpr uint32_t FLAT_NORMALS_BIT = 0x40000000u;
 struct alignas(16) FlatBvhHeader {
   const FlatNode* nodes;
   const uint32_t* order;
   const RtQuadRec* rec;
   const double* lim;      // null in a scene without a triangle
   uint32_t n_nodes, n_quads, id_base, pad0;
-  uint64_t pad[10];
+  const double* normals;  // [n_quads][9], null in a scene without shading normals
+  uint64_t pad[9];
 };
 static_assert(sizeof(FlatBvhHeader) == sizeof(RtQuadRec), "the header takes the slot of one record in front of the records");
 // The rays the structure takes (DESIGN.md §22 "Preconditions"): every component finite, |o_k| <= 2^40, |d_k| <= 2^100 (a zero, a
@@ -1169,6 +1174,16 @@ RT_HD HitCB flats_hit(const DevScene& sc, V3 o, V3 d, double closest, int best) 
   if (sc.n_tris & FLAT_BVH_BIT) return flats_hit_bvh(o, d, reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, closest, best);
   return quads_hit(o, d, sc.quads, sc.n_quads, sc.n_spheres, closest, best);
 }
+// The shading normal of a hit at P on the entry of record *q whose normals are the 72 bytes at rec (rt_flat_normal.h): cold
+// and by value like quads_hit — two pointers, d and P are the sixteen argument registers — so that the cross products, the square root
+// and the divisions stay out of the path loop's register budget.  Per lane: the lanes of a wave hit unrelated entries, the record is an
+// ordinary vector load, and an entry without normals returns after its first 24 bytes.
+RT_HD_COLD V3 flat_shading_normal(const RtQuadRec* q, const double* rec, V3 d, V3 P) {
+  const double dd[3] = {d.x, d.y, d.z}, pp[3] = {P.x, P.y, P.z};
+  double n[3];
+  (void)rt_flat_normal_shade(*q, rec, dd, pp, n);
+  return v3(n[0], n[1], n[2]);
+}
 // What a hit on object idx records and the SphereGeom scatter sees: a sphere's (surface_at), or in the QUADS arm for idx >= n_spheres
 // quad idx - n_spheres: no division, the stored N; its "centre" — the frame of a solid's pattern — is Q.
 template <bool QUADS, class Tables>
@@ -1181,6 +1196,8 @@ RT_HD Surface object_surface(const DevScene& sc, const Tables& tb, V3 o, V3 d, d
       const V3 N = v3(q.n[0], q.n[1], q.n[2]);
       s.front_face = dot(d, N) < 0.0;
       s.normal = s.front_face ? N : neg(N);
+      if (sc.n_tris & FLAT_NORMALS_BIT)  // (§25; sc is a kernel argument: wave-uniform)
+        s.normal = flat_shading_normal(&q, (reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1)->normals + 9u * (size_t)(idx - sc.n_spheres), d, s.point);
       g.cx = q.q[0]; g.cy = q.q[1]; g.cz = q.q[2]; g.r = 0.0;
       return s;
     }

@@ -125,5 +125,17 @@ struct Job {
 hipError_t prepare(const Job& j, hipStream_t stream);
 hipError_t refit(const Job& j, hipStream_t stream);
 
+// Shading normals (rt_hip_scene_set_flat_normals): per entry, its 72-byte record by rt_flat_normal.h rt_flat_normal_prepare.
+// The status block is prepare()'s: bad_finite = the lowest entry with a refused vector, bad_degenerate = the lowest parallelogram that
+// carries normals, mismatch = the entries that have normals.  The records go into a spare table, like everything here.
+struct NormalJob {
+  uint32_t n = 0;
+  const double* in = nullptr;    // [n][9] the caller's n0, n1, n2
+  const double* lim = nullptr;   // [n] or null: a scene of parallelograms
+  double* out = nullptr;         // [n][9]
+  Status* status = nullptr;
+};
+hipError_t normals(const NormalJob& j, hipStream_t stream);
+
 }  // namespace rtfb
 #endif

@@ -91,9 +91,41 @@ __global__ void __launch_bounds__(BLOCK) flat_refit_level(Job j, uint32_t begin,
   store_node(j.nodes + i, lo, hi, j.live_nodes[i]);
 }
 
+// per entry: its record of shading normals into the spare table (rt_flat_normal.h: the host's bits); only a triangle may carry any
+__global__ void __launch_bounds__(BLOCK) flat_normals_prepare(NormalJob j) {
+  __shared__ uint32_t smooth;   // of this workgroup: one global atomic per workgroup
+  if (threadIdx.x == 0) smooth = 0u;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < j.n) {
+    const double* p = j.in + 9 * (size_t)i;
+    double in[9], out[9];
+    for (int k = 0; k < 9; ++k) in[k] = p[k];
+    const int kind = rt_flat_normal_prepare(in, out);
+    const bool triangle = j.lim && j.lim[i] == 1.0;
+    if (kind == RT_FLAT_NORMAL_BAD) atomicMin(&j.status->bad_finite, i);
+    else if (kind == RT_FLAT_NORMAL_SMOOTH && !triangle) atomicMin(&j.status->bad_degenerate, i);
+    else {
+      double* o = j.out + 9 * (size_t)i;
+      for (int k = 0; k < 9; ++k) o[k] = out[k];
+      if (kind == RT_FLAT_NORMAL_SMOOTH) atomicAdd(&smooth, 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && smooth) atomicAdd(&j.status->mismatch, smooth);
+}
+
 uint32_t blocks_for(uint32_t n) { return (n + BLOCK - 1) / BLOCK; }
 
 }  // namespace
+
+hipError_t normals(const NormalJob& j, hipStream_t stream) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(j.status, 0xFF, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;   // NONE, NONE
+  if ((e = hipMemsetAsync(&j.status->mismatch, 0, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+  if (j.n) hipLaunchKernelGGL(flat_normals_prepare, dim3(blocks_for(j.n)), dim3(BLOCK), 0, stream, j);
+  return hipGetLastError();
+}
 
 hipError_t prepare(const Job& j, hipStream_t stream) {
   hipError_t e;

@@ -187,6 +187,10 @@ struct RtHipScene {
       } live, spare;           // (a refit keeps the live order table: only a rebuild swaps it)
       DevBuf lim;              // [n_quads] the limit of alpha + beta per entry; unallocated in a scene without a triangle
       uint32_t n_quads = 0, n_tris = 0, n_nodes = 0;  // (n_nodes: of the live structure; 0: none, every segment scans the records)
+      // shading normals (rt_hip_scene_set_flat_normals): [n_quads][9] the records of rt_flat_normal.h and the table the next
+      // call builds into; n_normals: the entries that have normals, 0: no table — the scene is one that never had any
+      DevBuf normals, normals_spare;
+      uint32_t n_normals = 0;
       // what a refit needs of the structure as built (rt_flat_build.h FlatTopology), on the device and on the host: topo's vectors are the staging of their uploads
       DevBuf boxed, leaves, levels;
       rtc::FlatTopology topo;
@@ -198,7 +202,7 @@ struct RtHipScene {
       rtc::FlatBvhHeader keep_header{};
       uint32_t refits = 0;     // the updates applied by refit since the structure was last built
       // the first record of a generation as the kernels see it (DevScene::quads.rec): behind the header, where there is a structure
-      uint32_t header_recs() const { return n_nodes ? 1u : 0u; }  // the record slots the header takes
+      uint32_t header_recs() const { return (n_nodes || n_normals) ? 1u : 0u; }  // the record slots the header takes (§25: the normals' pointer lives in it)
       RtQuadRec* first_rec(const Tables& t) const { return t.rec.get<RtQuadRec>() + header_recs(); }
       size_t rec_bytes() const { return ((size_t)n_quads + header_recs()) * sizeof(RtQuadRec); }  // of Tables::rec
       const double* dev_lim() const { return n_tris ? lim.get<const double>() : nullptr; }
@@ -208,6 +212,7 @@ struct RtHipScene {
         h.nodes = t.nodes.get<const rtc::FlatNode>(); h.order = order.get<const uint32_t>();
         h.rec = first_rec(t); h.lim = dev_lim();
         h.n_nodes = t_n_nodes; h.n_quads = n_quads; h.id_base = id_base;
+        h.normals = n_normals ? normals.get<const double>() : nullptr;
         return h;
       }
     } flat;
@@ -236,7 +241,8 @@ struct RtHipScene {
       d.motion = t.n_moving ? t.motion.get<const double>() : nullptr;
       d.quads.rec = flat.n_quads ? flat.first_rec(flat.live) : nullptr; d.quads.lim = flat.dev_lim();
       d.n_quads = flat.n_quads;
-      d.n_tris = flat.n_tris | (flat.n_nodes ? rtc::FLAT_BVH_BIT : 0u);  // (§22: the bit says that the header lies in front of quads.rec[0])
+      d.n_tris = flat.n_tris | (flat.n_nodes ? rtc::FLAT_BVH_BIT : 0u) |  // (§22: the bit says that the header lies in front of quads.rec[0])
+                 (flat.n_normals ? rtc::FLAT_NORMALS_BIT : 0u);             // (§25: ... and that it names a table of shading normals)
       d.mat = mat.get<const rtc::SphereMat>(); d.matc = matc.get<const rtc::MatCore>();
       d.lights = lights.get<const uint32_t>(); d.medium = n_media ? medium.get<const double>() : nullptr;
       d.tex = tex.get<const uint8_t>(); d.sky = sky.get<const uint8_t>();
@@ -1243,6 +1249,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
   if (!std::strcmp(key, "triangles")) return (int64_t)s->res->flat.n_tris;      // of "quads", the entries of shape triangle
   if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->flat.n_nodes;  // nodes of the structure over the flat primitives; 0: none
+  if (!std::strcmp(key, "flat_normals")) return (int64_t)s->res->flat.n_normals;  // entries that carry shading normals; 0: none
   if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat.refits;  // updates applied by refit since the structure was last built
   if (!std::strcmp(key, "quads")) return (int64_t)s->res->flat.n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
   if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
@@ -2001,7 +2008,7 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
   if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
     RT_HIP_TRY(rtfb::refit(j, nullptr));
     RT_HIP_TRY(put_header(f.n_nodes, f.live.order));
-  }
+  } else if (!bvh && f.header_recs()) RT_HIP_TRY(put_header(0u, f.live.order));  // (§25: a scan with shading normals keeps their header)
   rtfb::Status st;
   RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the first bad entry of each class, changed flags
   pc.mark("update_flats.kernels_and_readback");
@@ -2050,6 +2057,72 @@ extern "C" int rt_hip_scene_update_flats(RtHipScene* s, const double* quv, uint3
   return scene_update_flats(s, quv, n_quads, flags, false);
 }
 
+// ------------------------------------------------------------------------------ shading normals on the triangles of a resident scene
+namespace {
+// The records are made on the device from host or device input alike (rt_flat_build.hip: one code path, one table).  The table's address
+// travels in the FlatBvhHeader in front of the records: a scan scene gains that slot with its first normals and loses it with the last, its
+// records copied device to device into the spare generation; a scene with the structure has the slot already.  Everything that can fail
+// runs before anything the scene renders with changes.
+int scene_set_flat_normals(RtHipScene* s, const double* normals, uint32_t n_quads, uint32_t flags, bool views_follow) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (flags & ~RT_UPDATE_FLATS_DEVICE) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: unknown flag");
+  RtHipScene::Resident::Flats& f = s->res->flat;
+  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: the scene has no flat primitive");
+  if (n_quads != f.n_quads)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
+  if (!views_follow && s->res.use_count() > 1)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: the scene's tables are shared with a view (a group sets them through rt_hip_group_set_flat_normals)");
+  const bool on_device = normals && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
+  if (on_device)
+    if (const int refused = check_aligned(normals, 8, "rt_hip_scene_set_flat_normals: normals must be 8-byte aligned")) return refused;
+  int rc;
+  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  const uint32_t n = n_quads;
+  uint32_t count = 0;
+  if (normals) {
+    RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
+    if ((rc = room(f.normals_spare, (size_t)n * 72)) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
+        (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK))
+      return rc;
+    if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, normals, (size_t)n * 72, hipMemcpyHostToDevice));
+    rtfb::NormalJob j;
+    j.n = n; j.in = on_device ? normals : fb.quv.get<const double>(); j.lim = f.dev_lim();
+    j.out = f.normals_spare.get<double>(); j.status = fb.status.get<rtfb::Status>();
+    RT_HIP_TRY(rtfb::normals(j, nullptr));
+    rtfb::Status st;
+    RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the lowest bad entry of each class, the count
+    if (st.bad_finite != rtfb::NONE || st.bad_degenerate != rtfb::NONE) {
+      if (st.bad_finite < st.bad_degenerate)
+        return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + ": normal vectors must be finite, with a squared length that is finite, normal and not zero");
+      return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": normal vectors on a parallelogram (only triangles interpolate)");
+    }
+    count = st.mismatch;
+  }
+  // the record slots the header takes before and after: they differ only in a scan scene that gains or loses its table
+  const uint32_t had = f.header_recs(), has = (f.n_nodes || count) ? 1u : 0u;
+  RtHipScene::Resident::Flats::Tables& spare = f.spare;
+  if (has != had) {
+    if ((rc = room(spare.rec, ((size_t)n + has) * sizeof(RtQuadRec))) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(spare.rec.get<RtQuadRec>() + has, f.first_rec(f.live), (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
+    RT_HIP_TRY(hipDeviceSynchronize());
+  }
+  // everything is built: swap it in
+  if (has != had) f.live.rec.swap(spare.rec);
+  if (count) f.normals.swap(f.normals_spare);
+  f.n_normals = count;
+  if (has) {
+    f.keep_header = f.header(f.live, f.n_nodes, f.live.order, s->host.n_spheres);
+    RT_HIP_TRY(hipMemcpy(f.live.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice));
+  }
+  RT_HIP_TRY(hipDeviceSynchronize());
+  return adopt_tables(s, Moved::flats);
+}
+}  // namespace
+
+extern "C" int rt_hip_scene_set_flat_normals(RtHipScene* s, const double* normals, uint32_t n_quads, uint32_t flags) {
+  return scene_set_flat_normals(s, normals, n_quads, flags, false);
+}
+
 // diagnostics: one resident table as the kernels read it
 extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* out, size_t cap, size_t* needed) {
   if (!s || !name) return fail(RT_ERR_INVALID, "null argument");
@@ -2069,6 +2142,7 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "quads")) { src = f.first_rec(f.live); bytes = (size_t)f.n_quads * sizeof(RtQuadRec); }
   else if (!std::strcmp(name, "quad_lim")) { src = f.lim.p; bytes = f.n_tris ? (size_t)f.n_quads * sizeof(double) : 0; }
   else if (!std::strcmp(name, "flat_bvh")) { src = f.live.nodes.p; bytes = (size_t)f.n_nodes * sizeof(rtc::FlatNode); }
+  else if (!std::strcmp(name, "flat_normals")) { src = f.normals.p; bytes = f.n_normals ? (size_t)f.n_quads * 72u : 0; }
   else if (!std::strcmp(name, "flat_bvh_order")) { src = f.live.order.p; bytes = f.n_nodes ? (size_t)f.n_quads * sizeof(uint32_t) : 0; }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
   if (needed) *needed = bytes;

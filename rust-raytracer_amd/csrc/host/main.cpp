@@ -59,6 +59,12 @@ long gpus_asked(const RtScene* sc) {
 // rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh instead; `--flat-bvh` (with any of the modes, or alone)
 // does the same for any file that holds a flat primitive, for A/B runs; on a file without one it changes nothing (there is nothing to build
 // over), and given twice it is refused with the usage line.  The frame is the same in every bit.
+// Shading normals: a file whose triangles or meshes carry "normals" (rt_scene_flat_normals) has them set right after creation
+// (rt_hip_scene_set_flat_normals / rt_hip_group_set_flat_normals); a file without any takes the calls it always took.
+int set_normals(RtHipScene* h, const double* n, uint32_t k) { return rt_hip_scene_set_flat_normals(h, n, k, 0u); }
+int set_normals(RtHipGroup* h, const double* n, uint32_t k) { return rt_hip_group_set_flat_normals(h, n, k, 0u); }
+void destroy(RtHipScene* h) { rt_hip_scene_destroy(h); }
+void destroy(RtHipGroup* h) { rt_hip_group_destroy(h); }
 template <class Handle, class Where>
 int create(const Run& r, Where where, Handle** out, int (*moving)(const RtScene*, const double*, Where, Handle**),
            int (*with_quads)(const RtScene*, const double*, const RtQuad*, uint32_t, Where, Handle**),
@@ -66,7 +72,11 @@ int create(const Run& r, Where where, Handle** out, int (*moving)(const RtScene*
   uint32_t n_quads = 0;
   const RtQuad* quads = rt_scene_quads(r.sf, &n_quads);
   if (!n_quads) return moving(r.sc, rt_scene_motion(r.sf), where, out);
-  return (r.o.flat_bvh || rt_scene_flat_bvh(r.sf) ? with_bvh : with_quads)(r.sc, rt_scene_motion(r.sf), quads, n_quads, where, out);
+  int rc = (r.o.flat_bvh || rt_scene_flat_bvh(r.sf) ? with_bvh : with_quads)(r.sc, rt_scene_motion(r.sf), quads, n_quads, where, out);
+  uint32_t n_normals = 0;
+  const double* normals = rt_scene_flat_normals(r.sf, &n_normals);
+  if (rc == RT_OK && normals && (rc = set_normals(*out, normals, n_normals)) != RT_OK) { destroy(*out); *out = nullptr; }
+  return rc;
 }
 int create_scene(const Run& r, int device, RtHipScene** out) {
   return create(r, device, out, rt_hip_scene_create_moving, rt_hip_scene_create_quads, rt_hip_scene_create_flats_bvh);
@@ -174,12 +184,15 @@ int adaptive(const Run& r) {
 // --flat-frames PREFIX: frame f takes its flat primitives from the scene file PREFIX%03d.json, read with the ordinary loader;
 // only its rt_scene_quads are used, and they must be the base file's in count, shapes and materials.  load() returns "" and the
 // frame's q, u, v (n x 9), or what is wrong, naming the frame.  (One file at a time: the loader's error text is per process.)
+// Shading normals: a frame file has normals on exactly the entries the base file has; they are the frame's (n x 9, empty
+// for a scene without any).
 struct FlatFrames {
   std::string prefix;
   std::vector<RtQuad> base;
+  std::vector<double> base_normals;   // the base file's rt_scene_flat_normals, empty without
   std::mutex mu;
   bool on() const { return !prefix.empty(); }
-  std::string load(int f, std::vector<double>& out) {
+  std::string load(int f, std::vector<double>& out, std::vector<double>& normals) {
     std::lock_guard<std::mutex> lk(mu);
     char path[4096];
     std::snprintf(path, sizeof path, "%s%03d.json", prefix.c_str(), f);
@@ -197,6 +210,17 @@ struct FlatFrames {
         why = which + "flat primitive " + std::to_string(k) + " has another material than the scene's";
       std::memcpy(&out[9 * (size_t)k], q[k].q, 72);
     }
+    uint32_t nn = 0;
+    const double* fn = rt_scene_flat_normals(ff, &nn);
+    normals.clear();
+    if (why.empty() && fn) normals.assign(fn, fn + 9 * (size_t)nn);
+    auto has = [](const std::vector<double>& t, size_t k) {
+      bool any = false;
+      for (int c = 0; c < 9 && !t.empty(); ++c) any = any || t[9 * k + c] != 0.0;
+      return any;
+    };
+    for (size_t k = 0; why.empty() && k < base.size(); ++k)
+      if (has(normals, k) != has(base_normals, k)) why = which + "flat primitive " + std::to_string(k) + (has(base_normals, k) ? " has no normals, the scene's has" : " has normals, the scene's has none");
     rt_scene_free(ff);
     return why;
   }
@@ -209,6 +233,7 @@ struct Pose {
   bool spheres = false;       // --shutter: the spheres move to c -> c1 (n x 3 each)
   bool flats = false;         // --flat-frames: the flat primitives move to quv (n x 9)
   std::vector<double> c, c1, quv;
+  std::vector<double> normals;  // --flat-frames: the frame's shading normals (n x 9), set after its flat primitives; empty: the scene has none
 };
 // One apply per kind of target.  Each keeps the order of calls its drivers always had (camera first on a scene, last on a group).
 // rt_hip_set_camera / rt_hip_group_set_camera refuse null arguments and nothing else, so checking their status changes no run.
@@ -217,11 +242,13 @@ int apply(RtHipScene* hs, const Pose& p) {
   if (rc == RT_OK && p.lens) rc = rt_hip_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
   if (rc == RT_OK && p.spheres) rc = rt_hip_scene_update_spheres(hs, p.c.data(), p.c1.data());
   if (rc == RT_OK && p.flats) rc = rt_hip_scene_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), 0u);
+  if (rc == RT_OK && p.flats && !p.normals.empty()) rc = rt_hip_scene_set_flat_normals(hs, p.normals.data(), (uint32_t)(p.normals.size() / 9), 0u);
   return rc;
 }
 int apply(RtHipGroup* hs, const Pose& p) {  // (no frame may be in flight while the spheres or the flat primitives move)
   int rc = p.spheres ? rt_hip_group_update_spheres(hs, p.c.data(), p.c1.data()) : RT_OK;
   if (rc == RT_OK && p.flats) rc = rt_hip_group_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), 0u);
+  if (rc == RT_OK && p.flats && !p.normals.empty()) rc = rt_hip_group_set_flat_normals(hs, p.normals.data(), (uint32_t)(p.normals.size() / 9), 0u);
   if (rc == RT_OK) rc = rt_hip_group_set_camera(hs, p.cam, p.cam + 3, p.cam + 6, p.cam + 9);
   if (rc == RT_OK && p.lens) rc = rt_hip_group_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
   return rc;
@@ -267,7 +294,7 @@ struct Anim {
   // with --flat-frames, frame f's flat primitives from its file: "", or what is wrong with the file
   std::string flats(int f, Pose& p) {
     p.flats = flat_files.on();
-    return p.flats ? flat_files.load(f, p.quv) : std::string();
+    return p.flats ? flat_files.load(f, p.quv, p.normals) : std::string();
   }
   std::string pose(int f, Pose& p) { view(f, p); return flats(f, p); }
   std::string frame_name(int f) const {
@@ -558,6 +585,8 @@ int animate(const Run& r) {
     const RtQuad* quads = rt_scene_quads(r.sf, &n_quads);
     if (!n_quads) { std::fprintf(stderr, "--flat-frames: the scene has no flat primitive\n"); return 101; }
     a.flat_files.base.assign(quads, quads + n_quads);
+    uint32_t n_normals = 0;
+    if (const double* nr = rt_scene_flat_normals(r.sf, &n_normals)) a.flat_files.base_normals.assign(nr, nr + 9 * (size_t)n_normals);
     const std::string why = a.flats(0, first);
     if (!why.empty()) { std::fprintf(stderr, "%s\n", why.c_str()); return 101; }
   }

@@ -200,6 +200,10 @@ struct RtSceneFile {
   // interleaving of the two kinds — is_quad[j]: the j-th object written is the next quad, else the next sphere
   std::vector<RtQuad> quads;
   std::vector<uint8_t> is_quad;
+  // shading normals: [quads.size()][9] the normals at q, q + u, q + v of every entry AS WRITTEN (not normalised), nine +0.0
+  // for an entry without; n_normals: the entries that have them (0: rt_scene_flat_normals is NULL)
+  std::vector<double> normals;
+  size_t n_normals = 0;
   // the structure over the flat primitives: the file's top-level "flat_bvh": true (rt_scene_flat_bvh; written back only when true)
   bool flat_bvh = false;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
@@ -471,12 +475,25 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           if (o.find(k)) bad(std::string("mixed keys: `") + k + "` of a quad beside `" + form + "`");
       if (int(is_box) + int(is_tri) + int(is_mesh) > 1) bad("mixed keys: only one of `box`, `triangle`, `mesh`");
       if (o.find("center1")) bad(is_tri || is_mesh ? std::string("a ") + form + " cannot move (center1)" : std::string("a quad cannot move (center1)"));
-      const Value* f[5] = {};
-      struct Flat { double g[9]; uint32_t shape; };
+      const Value* f[6] = {};
+      struct Flat { double g[9]; uint32_t shape; double nrm[9]; bool smooth; };
+      // shading normals: a vector as written, finite and not all zero; prepare normalises it
+      auto as_normal = [&](const Value& v, const std::string& what, double out[3]) {
+        try {
+          as_point(v, "a normal", out);
+        } catch (const SchemaError& e) {
+          bad(what + ": " + e.msg);
+        }
+        for (int k = 0; k < 3; ++k)
+          if (!rt_quad_finite(out[k])) bad(what + ": a normal must be finite");
+        const double nn = rt_quad_dot(out, out);
+        if (!(nn >= 2.2250738585072014e-308 && rt_quad_finite(nn))) bad(what + ": the squared length of a normal must be finite, normal and not zero");
+      };
       std::vector<Flat> geo;
       std::vector<std::string> label;   // what a degenerate entry is called
       const Value* mat_v = nullptr;
       if (is_box) {
+        if (o.find("normals")) bad("normals: a box takes no normals (only triangles interpolate)");
         struct_fields(o, "Box", {"box", "material"}, f);
         const Value* b[2];
         struct_fields(*f[0], "box", {"min", "max"}, b);
@@ -487,29 +504,49 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           if (!(mn[k] < mx[k])) bad("box: min must be below max on every axis");
         double six[6][9];
         rt_box_quads(mn, mx, six);
-        for (int i = 0; i < 6; ++i) { Flat fl; std::memcpy(fl.g, six[i], sizeof fl.g); fl.shape = RT_QUAD_SHAPE_PARALLELOGRAM; geo.push_back(fl); label.push_back("quad"); }
+        for (int i = 0; i < 6; ++i) { Flat fl{}; std::memcpy(fl.g, six[i], sizeof fl.g); fl.shape = RT_QUAD_SHAPE_PARALLELOGRAM; geo.push_back(fl); label.push_back("quad"); }
         mat_v = f[1];
       } else if (is_tri || is_mesh) {
-        auto from_corners = [&](const double a[3], const double b[3], const double c[3], const std::string& name) {
-          Flat fl;
+        // na, nb, nc: the normals at the three corners, or all null
+        auto from_corners = [&](const double a[3], const double b[3], const double c[3], const std::string& name, const double* na = nullptr,
+                                const double* nb = nullptr, const double* nc = nullptr) {
+          Flat fl{};
           for (int k = 0; k < 3; ++k) { fl.g[k] = a[k]; fl.g[3 + k] = b[k] - a[k]; fl.g[6 + k] = c[k] - a[k]; }
           fl.shape = RT_QUAD_SHAPE_TRIANGLE;
+          fl.smooth = na != nullptr;
+          if (na)
+            for (int k = 0; k < 3; ++k) { fl.nrm[k] = na[k]; fl.nrm[3 + k] = nb[k]; fl.nrm[6 + k] = nc[k]; }
           geo.push_back(fl); label.push_back(name);
         };
         if (is_tri) {
-          struct_fields(o, "Triangle", {"triangle", "material"}, f);
+          struct_fields(o, "Triangle", {"triangle", "material", "normals"}, f, {false, false, true});
           if (f[0]->kind != Value::Array || f[0]->items.size() != 3) bad("triangle: expected three vertices");
-          double c[3][3];
+          double c[3][3], nv[3][3];
           for (int i = 0; i < 3; ++i) as_point(*f[0]->items[i], "triangle vertex", c[i]);
-          from_corners(c[0], c[1], c[2], "triangle");
+          if (f[2]) {
+            if (f[2]->kind != Value::Array || f[2]->items.size() != 3) bad("triangle.normals: expected 3 normals");
+            for (int i = 0; i < 3; ++i) as_normal(*f[2]->items[i], "triangle normal " + std::to_string(i), nv[i]);
+            from_corners(c[0], c[1], c[2], "triangle", nv[0], nv[1], nv[2]);
+          } else from_corners(c[0], c[1], c[2], "triangle");
         } else {
           struct_fields(o, "Mesh", {"mesh", "material"}, f);
-          const Value* mv[2];
+          const Value* mv[4];
           if (f[0]->kind != Value::Object) bad("mesh: expected a map with `vertices` and `faces`");
-          struct_fields(*f[0], "mesh", {"vertices", "faces"}, mv);
+          struct_fields(*f[0], "mesh", {"vertices", "faces", "normals", "smooth"}, mv, {false, false, true, true});
           if (mv[0]->kind != Value::Array) bad("mesh.vertices: expected a sequence of points");
           if (mv[1]->kind != Value::Array) bad("mesh.faces: expected a sequence of index triples");
+          if (mv[2] && mv[3]) bad("mixed keys: `smooth` beside `normals` in a mesh");
+          if (mv[3] && mv[3]->kind != Value::Bool) bad("mesh.smooth: expected a boolean");
+          const bool smooth = mv[3] && mv[3]->b;
+          std::vector<double> vnorm;   // one normal per vertex: the file's, or (smooth) the sum of cross(u_f, v_f) over the faces that use it
+          if (mv[2]) {
+            if (mv[2]->kind != Value::Array || mv[2]->items.size() != mv[0]->items.size())
+              bad("mesh.normals: expected " + std::to_string(mv[0]->items.size()) + " normals");
+            vnorm.resize(3 * mv[2]->items.size());
+            for (size_t i = 0; i < mv[2]->items.size(); ++i) as_normal(*mv[2]->items[i], "mesh normal " + std::to_string(i), &vnorm[3 * i]);
+          }
           std::vector<double> vert(3 * mv[0]->items.size());
+          std::vector<size_t> face_ix;   // (smooth: the faces' vertex indices, three per face)
           for (size_t i = 0; i < mv[0]->items.size(); ++i) {
             try {
               as_point(*mv[0]->items[i], "a mesh vertex", &vert[3 * i]);
@@ -532,14 +569,38 @@ void build_scene(const Value& root, RtSceneFile& sf) {
               if (v >= mv[0]->items.size()) bad(fname + ": index " + face.items[k]->text + " out of range (the mesh has " + std::to_string(mv[0]->items.size()) + " vertices)");
               ix[k] = size_t(v);
             }
-            from_corners(&vert[3 * ix[0]], &vert[3 * ix[1]], &vert[3 * ix[2]], fname);
+            if (mv[2]) from_corners(&vert[3 * ix[0]], &vert[3 * ix[1]], &vert[3 * ix[2]], fname, &vnorm[3 * ix[0]], &vnorm[3 * ix[1]], &vnorm[3 * ix[2]]);
+            else from_corners(&vert[3 * ix[0]], &vert[3 * ix[1]], &vert[3 * ix[2]], fname);
+            if (smooth) face_ix.insert(face_ix.end(), ix, ix + 3);
+          }
+          if (smooth) {  // in face order, component-wise, one f64 add per face; unnormalised
+            vnorm.assign(vert.size(), 0.0);
+            const size_t first = geo.size() - face_ix.size() / 3;
+            for (size_t fi = 0; fi < face_ix.size() / 3; ++fi) {
+              double n[3];
+              rt_quad_cross(geo[first + fi].g + 3, geo[first + fi].g + 6, n);
+              for (int c = 0; c < 3; ++c)
+                for (int k = 0; k < 3; ++k) vnorm[3 * face_ix[3 * fi + c] + k] += n[k];
+            }
+            for (size_t fi = 0; fi < face_ix.size() / 3; ++fi) {
+              Flat& fl = geo[first + fi];
+              fl.smooth = true;
+              for (int c = 0; c < 3; ++c) {
+                const size_t v = face_ix[3 * fi + c];
+                const double* n = &vnorm[3 * v];
+                const double nn = rt_quad_dot(n, n);
+                if (!(nn >= 2.2250738585072014e-308 && rt_quad_finite(nn)))
+                  bad("mesh vertex " + std::to_string(v) + ": smooth: the sum of its faces' normals is zero or not finite");
+                for (int k = 0; k < 3; ++k) fl.nrm[3 * c + k] = n[k];
+              }
+            }
           }
         }
         mat_v = f[1];
       } else {
         (void)is_quad;
-        struct_fields(o, "Quad", {"q", "u", "v", "material", "shape"}, f, {false, false, false, false, true});
-        Flat fl;
+        struct_fields(o, "Quad", {"q", "u", "v", "material", "shape", "normals"}, f, {false, false, false, false, true, true});
+        Flat fl{};
         as_point(*f[0], "Quad.q", fl.g);
         as_point(*f[1], "Quad.u", fl.g + 3);
         as_point(*f[2], "Quad.v", fl.g + 6);
@@ -548,6 +609,12 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           if (f[4]->kind != Value::String) bad("shape: expected a string");
           if (f[4]->text == "triangle") fl.shape = RT_QUAD_SHAPE_TRIANGLE;
           else if (f[4]->text != "parallelogram") bad("unknown shape `" + f[4]->text + "`, expected one of `parallelogram`, `triangle`");
+        }
+        if (const Value* nv = f[5]) {  // (§25: what rt_scene_to_json writes — a triangle's exact q, u, v beside its normals; only triangles interpolate)
+          if (fl.shape != RT_QUAD_SHAPE_TRIANGLE) bad("normals: a parallelogram takes no normals (only triangles interpolate)");
+          if (nv->kind != Value::Array || nv->items.size() != 3) bad("normals: expected 3 normals");
+          for (int i = 0; i < 3; ++i) as_normal(*nv->items[i], "normal " + std::to_string(i), fl.nrm + 3 * i);
+          fl.smooth = true;
         }
         geo.push_back(fl); label.push_back(fl.shape == RT_QUAD_SHAPE_TRIANGLE ? "triangle" : "quad");
         mat_v = f[3];
@@ -578,6 +645,8 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         }
         sf.quads.push_back(q);
         sf.is_quad.push_back(1);
+        for (int k = 0; k < 9; ++k) sf.normals.push_back(geo[i].smooth ? geo[i].nrm[k] : 0.0);
+        if (geo[i].smooth) sf.n_normals++;
       }
     } catch (const SchemaError& e) {
       bad(e.msg.rfind(which, 0) == 0 ? e.msg : which + ": " + e.msg);
@@ -704,7 +773,12 @@ std::string scene_json(const RtSceneFile& sf) {
     if (sf.is_quad[j]) {
       const RtQuad& q = sf.quads[iq++];
       // (§21: a triangle carries its shape; a parallelogram is written as it always was, so a file without a triangle keeps its bytes)
-      o += "{\"q\":" + point(q.q) + ",\"u\":" + point(q.u) + ",\"v\":" + point(q.v) + (q.reserved == RT_QUAD_SHAPE_TRIANGLE ? ",\"shape\":\"triangle\"" : "") + ",\"material\":{";
+      o += "{\"q\":" + point(q.q) + ",\"u\":" + point(q.u) + ",\"v\":" + point(q.v) + (q.reserved == RT_QUAD_SHAPE_TRIANGLE ? ",\"shape\":\"triangle\"" : "");
+      const double* nr = &sf.normals[9 * (iq - 1)];  // (§25: a triangle with its normals as written; any other entry keeps its bytes)
+      bool smooth = false;
+      for (int k = 0; k < 9; ++k) smooth = smooth || nr[k] != 0.0;
+      if (smooth) o += ",\"normals\":[" + point(nr) + "," + point(nr + 3) + "," + point(nr + 6) + "]";
+      o += ",\"material\":{";
     } else {
       o += "{\"center\":" + point(s.center);
       if (sf.has_center1[i]) o += ",\"center1\":" + point(&sf.center1[3 * i]);
@@ -808,6 +882,11 @@ extern "C" const RtQuad* rt_scene_quads(const RtSceneFile* sf, uint32_t* n) {
   const bool any = sf && !sf->quads.empty();
   if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
   return any ? sf->quads.data() : nullptr;
+}
+extern "C" const double* rt_scene_flat_normals(const RtSceneFile* sf, uint32_t* n) {
+  const bool any = sf && sf->n_normals != 0;
+  if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
+  return any ? sf->normals.data() : nullptr;
 }
 extern "C" int rt_scene_flat_bvh(const RtSceneFile* sf) { return sf && sf->flat_bvh ? 1 : 0; }
 extern "C" void rt_free(void* p) { std::free(p); }

@@ -56,6 +56,8 @@ def _bind(path, probes):
     L.rt_hip_scene_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rt_hip_scene_update_flats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_group_update_flats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_scene_set_flat_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_group_set_flat_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_scene_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rt_hip_group_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
@@ -208,7 +210,7 @@ def _flat_geometry(quv, device, rebuild):
     return C.c_void_p(a.ctypes.data), a.shape[0], flags, a
 
 
-TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order")   # the names rt_hip_scene_table knows
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order", "flat_normals")   # the names rt_hip_scene_table knows
 
 
 def _quads_array(quads):
@@ -265,6 +267,17 @@ class HipScene:
         the device; rebuild=True (or a change of the set of entries outside its preconditions) builds it anew on the host.  Blocking."""
         p, n, flags, keep = _flat_geometry(quv, self.device, rebuild)
         _check(self._L.rt_hip_scene_update_flats(self._h, p, n, flags), self._L)
+        del keep
+
+    def set_flat_normals(self, normals):
+        """rt_hip_scene_set_flat_normals: shading normals on the scene's triangles — [n_quads, 9] float64 (the normals at q,
+        q + u, q + v per entry; nine zeros: a flat entry), a numpy array or a CUDA torch tensor as for update_flats; None removes them.
+        Blocking."""
+        if normals is None:
+            _check(self._L.rt_hip_scene_set_flat_normals(self._h, None, int(self.query("quads")), 0), self._L)
+            return
+        p, n, flags, keep = _flat_geometry(normals, self.device, False)
+        _check(self._L.rt_hip_scene_set_flat_normals(self._h, p, n, flags), self._L)
         del keep
 
     def table(self, name):
@@ -554,6 +567,16 @@ class HipGroup:
         several devices); no submitted frame may be uncollected"""
         p, n, flags, keep = _flat_geometry(quv, None, rebuild)
         _check(self._L.rt_hip_group_update_flats(self._h, p, n, flags), self._L)
+        del keep
+
+    def set_flat_normals(self, normals, n_quads=None):
+        """rt_hip_group_set_flat_normals: HipScene.set_flat_normals on every rank (through host memory); None removes them and needs
+        n_quads, the scene's count"""
+        if normals is None:
+            _check(self._L.rt_hip_group_set_flat_normals(self._h, None, int(n_quads), 0), self._L)
+            return
+        p, n, flags, keep = _flat_geometry(normals, None, False)
+        _check(self._L.rt_hip_group_set_flat_normals(self._h, p, n, flags), self._L)
         del keep
 
     def set_option(self, key, value):

@@ -46,6 +46,8 @@ def lib():
         L.rt_scene_motion.restype = C.POINTER(C.c_double)
         L.rt_scene_quads.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.rt_scene_quads.restype = C.POINTER(abi.RtQuad)
+        L.rt_scene_flat_normals.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.rt_scene_flat_normals.restype = C.POINTER(C.c_double)
         L.rt_scene_flat_bvh.argtypes = [C.c_void_p]
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
@@ -117,6 +119,16 @@ class Scene:
         out = (abi.RtQuad * n.value)()
         C.memmove(out, p, C.sizeof(out))
         return out
+
+    def flat_normals(self):
+        """shading normals: an [n_quads, 9] float64 numpy array (a copy) — the normals at q, q + u, q + v of every entry of
+        quads() as the file wrote them, nine zeros for an entry without — or None for a file without any (rt_scene_flat_normals)"""
+        import numpy as np
+        n = C.c_uint32(0)
+        p = lib().rt_scene_flat_normals(self._h, C.byref(n))
+        if not p or not n.value:
+            return None
+        return np.ctypeslib.as_array(p, shape=(n.value, 9)).copy()
 
     def flat_bvh(self):
         """the structure over the flat primitives: True for a file with "flat_bvh": true (rt_scene_flat_bvh)"""
