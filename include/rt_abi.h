@@ -429,7 +429,13 @@ int rt_hip_wait(RtHipScene*, RtStats* stats);
 /* Options of a resident scene: (key, value) pairs, out-of-range values and unknown keys are RT_ERR_INVALID.  The keys, their
  * ranges and defaults are tabulated in INTEGRATION.md §5 ("samples_per_pixel", "max_depth", "seed" override the scene's
  * values; "variant" 1 = the reference's brute force; the rest shape the work distribution and never the image).
- * rt_hip_group_set_option forwards to every rank's scene and takes "spin_us" itself. */
+ * rt_hip_group_set_option forwards to every rank's scene and takes "spin_us" itself.
+ * "flat_build" (DESIGN.md §26): who builds the structure over the flat primitives when rt_hip_scene_update_flats is called with
+ * RT_UPDATE_FLATS_REBUILD.  0 (default): the host, as ever.  1: the device — the order table from one sort per tree depth, the boxes from
+ * the refit, the same four tables byte for byte.  Any other value is RT_ERR_INVALID; a scene without the structure accepts the option and
+ * nothing changes.  Measured on an MI355X (profiles/flat_device_build_time.json): 2^18 entries 67 ms on the host, 4.6 ms on the device
+ * (3.8 ms from a device tensor); 6 405 entries 1.27 ms against 0.90 ms.  The device won at both sizes; smaller scenes were not measured,
+ * and there a build is a few launch overheads either way. */
 int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
 /* What a resident scene was built into (diagnostics): "n_spheres", "n_lights", "grid_cells" (padded cell table, 8 B each),
  * "grid_items" (u16 each), "grid_wide" (1: more than 65 535 spheres — 16-byte cells, u32 items), "grid_large" (spheres every ray tests), "table_bytes" (geometry + material cores + cell table +
@@ -444,7 +450,8 @@ int rt_hip_set_option(RtHipScene*, const char* key, int64_t value);
  * (spheres of kind RT_MAT_MEDIUM), "solids" (spheres and quads of kind RT_MAT_CHECKER or RT_MAT_NOISE), "quads" (rt_hip_scene_create_quads; both shapes),
  * "triangles" (the entries of shape RT_QUAD_SHAPE_TRIANGLE among them), "flat_bvh" (nodes of the structure over the flat primitives,
  * rt_hip_scene_create_flats_bvh; 0: none), "flat_refits" (rt_hip_scene_update_flats calls applied by refit since the structure was last built:
- * 0 after creation and after a rebuild).  -1 for an unknown key. */
+ * 0 after creation and after a rebuild), "flat_build" (the option of that name), "flat_device_builds" (rebuilds whose order table the
+ * device built, since creation).  -1 for an unknown key. */
 int64_t rt_hip_scene_query(const RtHipScene*, const char* key);
 /* Diagnostics: a copy of one resident table, as the kernels read it.  name: "grid" (the GridDesc bytes), "cell_word", "cell_items",
  * "large", "geom", "large_geom", "motion" (empty for a static scene), "quads" (RtQuadRec of csrc/common/rt_quad.h, 128 B each: q, u, v, N, w,
@@ -474,12 +481,15 @@ int rt_hip_scene_update_spheres(RtHipScene*, const double* center, const double*
  * the union of its entries' padded boxes and an inner node's the union of its children's (min and max are exact: the union over all
  * entries below it), always-visited leaves keep their infinite boxes; refitting back to the geometry of the last build restores that
  * build's node table byte for byte.  The frame of such a scene is the full scan's in every bit whatever the tree looks like, so a refit
- * scene renders what a rebuilt one renders; what a refit costs is tree quality, never a bit.  The structure is REBUILT on the host — all
+ * scene renders what a rebuilt one renders; what a refit costs is tree quality, never a bit.  The structure is REBUILT — all
  * four flat tables then byte for byte creation's — when flags holds RT_UPDATE_FLATS_REBUILD, or when the set of entries outside the
- * padding's preconditions differs from the resident one (an entry became a needle, crossed 2^40, or stopped being one).
+ * padding's preconditions differs from the resident one (an entry became a needle, crossed 2^40, or stopped being one).  The rebuild
+ * runs on the host, or with rt_hip_set_option "flat_build" 1 on the device (nothing but the status crosses back, and
+ * "flat_device_builds" counts it); the rebuild that a changed set of such entries forces always runs on the host, whatever the option
+ * says — the counts the tree's shape follows from are others then.
  * rt_hip_scene_query "flat_refits" counts the updates applied by refit since the last build (0 after creation or a rebuild): a caller
  * decides with it when to pay for a rebuild.  RT_UPDATE_FLATS_DEVICE: quv is device memory on the scene's device (8-byte aligned): an
- * update by refit then crosses no PCIe but the status readback; a rebuild copies the geometry back to the host first.
+ * update by refit or by a device build then crosses no PCIe but the status readback; a rebuild on the host copies the geometry back first.
  * Every error is RT_ERR_INVALID, with creation's wording where creation has one: a null argument; an unknown flag; n_quads different
  * from the scene's; a scene without flat primitives; a non-finite component ("quad k: ..."); a degenerate entry ("quad k: ..."; of all bad
  * entries the lowest k is reported); a scene whose tables a live view shares (rt_hip_group_update_flats).  After any error the scene
@@ -487,7 +497,7 @@ int rt_hip_scene_update_spheres(RtHipScene*, const double* center, const double*
  * tile order, the progressive accumulator with its cached AOVs, the adaptive rounds) and the temporal history (as rt_hip_temporal_reset:
  * moved flat primitives are not followed through the temporal filter).  rt_hip_scene_update_spheres afterwards keeps the moved flat
  * primitives, and a flat update keeps moved spheres.  Device buffers are allocated by the first update and reused from then on. */
-#define RT_UPDATE_FLATS_REBUILD 1u   /* build the structure anew on the host: tables byte for byte creation's */
+#define RT_UPDATE_FLATS_REBUILD 1u   /* build the structure anew (on the host; option "flat_build" 1: on the device): tables byte for byte creation's */
 #define RT_UPDATE_FLATS_DEVICE  2u   /* quv is device memory on the scene's device */
 int rt_hip_scene_update_flats(RtHipScene*, const double* quv, uint32_t n_quads, uint32_t flags);
 /* Shading normals on the triangles of a resident scene (the arithmetic is csrc/common/rt_flat_normal.h, bit for bit).

@@ -91,7 +91,8 @@ def build_cli(force=False):
 # The translation units of librt_hip.so as (object name, source, defines): rt_hip_api.hip with kernel set 0 (the megakernel instantiations
 # with key >> 6 == 0, csrc/hip/rt_kernel.hip) and everything else; rt_kernel_set.hip once for each of the sets 1 - 15 (MOTION, DESIGN.md §14;
 # MEDIUM, §15; SOLID, §16; QUADS, §20: the sets 8 - 15, eight kernels each); the device grid build of rt_hip_scene_update_spheres (§17: a few
-# small kernels); the records and the refit of rt_hip_scene_update_flats (§24: three small kernels).
+# small kernels); the records and the refit of rt_hip_scene_update_flats (§24: three small kernels) and the order
+# table built on the device (§26: four small kernels and rocprim's merge sort).
 HIP_UNITS = ([("rt_hip_api", "csrc/hip/rt_hip_api.hip", ["-DRT_KERNEL_SET_SPLIT"])]
              + [("rt_kernel_set%d" % k, "csrc/hip/rt_kernel_set.hip", ["-DRT_KERNEL_SET=%d" % k]) for k in range(1, 16)]
              + [("rt_grid_build", "csrc/hip/rt_grid_build.hip", []), ("rt_flat_build", "csrc/hip/rt_flat_build.hip", [])])

@@ -1,8 +1,9 @@
 // rt_flat_build.h — the per-entry expressions of the structure over the flat primitives, shared by the host builder
 // (rt_tables.h build_flat_bvh: what rt_hip_scene_create_flats_bvh runs) and the device code that moves the flat primitives of a resident
-// scene (rt_flat_build.hip: what rt_hip_scene_update_flats runs), the static topology the refit needs, and the device
-// code's entry points.  Both sides compile these f64 expressions without contraction (-ffp-contract=off); every operation in them is
-// correctly rounded or exact (+ - * / sqrt fabs compare), so they give the same bits on both.
+// scene (rt_flat_build.hip: what rt_hip_scene_update_flats runs), the static topology the refit needs, the split of the
+// builder as RT_HD functions (what the device build of the order table shares with it, §26), and the device code's entry points.  Both
+// sides compile these f64 expressions without contraction (-ffp-contract=off); every operation in them is correctly rounded or exact
+// (+ - * / sqrt fabs compare), so they give the same bits on both.
 #pragma once
 #include <vector>
 
@@ -83,6 +84,68 @@ inline void flat_topology(const std::vector<FlatNode>& nodes, const std::vector<
     if (!nodes[i].count) tp.level_nodes[cursor[height[i] - 1u]++] = i;
 }
 
+// ------------------------------------------------------------------ the order table, built anew
+// build_flat_bvh's split, restated so that the host builder and the device build (rt_flat_build.hip build()) run the same expressions.
+// The boxed entries, m of them, start in index order at the positions 0 .. m-1; a range [a, b) of more than FLAT_LEAF_MAX positions is
+// split at a + (b - a) / 2 into the (b - a) / 2 smallest entries under (centre along the axis, entry index) and the others.  Only the two
+// halves AS SETS matter: the next split orders each half again and a leaf ends up in index order.
+constexpr uint32_t FLAT_LEAF_MAX = 4;
+RT_HD double flat_centre(double lo, double hi) { return 0.5 * lo + 0.5 * hi; }   // two products, one sum, no contraction
+// the longest axis of the extent [clo, chi] of a range's centres: axis 0 unless a later one is STRICTLY longer
+RT_HD int flat_split_axis(const double clo[3], const double chi[3]) {
+  int axis = 0;
+  for (int k = 1; k < 3; ++k) if (chi[k] - clo[k] > chi[axis] - clo[axis]) axis = k;
+  return axis;
+}
+// the strict total order of a split: centres compared as doubles (-0.0 == 0.0: the index decides), ties by entry index
+RT_HD bool flat_split_less(double cx, uint32_t x, double cy, uint32_t y) { return cx < cy || (cx == cy && x < y); }
+
+// The range that position p (< m) lies in after `depth` splits, by count alone: [a, b) and r, its number among the ranges of that depth
+// (the path from the root, left = 0).  The descent stops at a leaf.  Every range of a depth has floor or ceil of m / 2^depth positions,
+// so while one of them is above FLAT_LEAF_MAX the depth before had none below 2 * FLAT_LEAF_MAX: all 2^depth ranges exist and r < 2^depth.
+struct FlatRange { uint32_t a, b, r; };
+RT_HD FlatRange flat_range_at(uint32_t p, uint32_t m, uint32_t depth) {
+  FlatRange g = {0u, m, 0u};
+  for (uint32_t d = 0; d < depth && g.b - g.a > FLAT_LEAF_MAX; ++d) {
+    const uint32_t mid = g.a + (g.b - g.a) / 2u;
+    if (p < mid) { g.b = mid; g.r = 2u * g.r; } else { g.a = mid; g.r = 2u * g.r + 1u; }
+  }
+  return g;
+}
+// the depths that have a range to split: the largest range of a depth is ceil(the depth before's / 2).  At most 30 for any 32-bit m.
+RT_HD uint32_t flat_build_depths(uint32_t m) {
+  uint32_t d = 0;
+  for (uint32_t s = m; s > FLAT_LEAF_MAX; s = s / 2u + (s & 1u)) ++d;
+  return d;
+}
+constexpr uint32_t FLAT_DEPTH_ALL = 32;   // flat_range_at(p, m, FLAT_DEPTH_ALL): the leaf of position p
+
+// What one entry carries through the sort of one depth: the range it is in, its centre along that range's axis (0.0 in a range that is
+// a leaf already: it keeps its place, in index order), itself.  flat_item_less is the comparator (range, key, index).
+struct alignas(16) FlatBuildItem { double key; uint32_t seg, idx; };
+static_assert(sizeof(FlatBuildItem) == 16, "an item of the device build is 16 bytes");
+RT_HD bool flat_item_less(const FlatBuildItem& x, const FlatBuildItem& y) {
+  return x.seg < y.seg || (x.seg == y.seg && flat_split_less(x.key, x.idx, y.key, y.idx));
+}
+// A double as a 64-bit word whose unsigned order is the doubles' order (-0.0 below +0.0: an extent's zero may come out with either
+// sign, which neither chi - clo nor the comparison above can see), and back: the device forms a range's min and max with integer atomics.
+RT_HD unsigned long long flat_ordered_bits(double x) {
+  unsigned long long b;
+  __builtin_memcpy(&b, &x, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+RT_HD double flat_from_ordered_bits(unsigned long long b) {
+  b = (b >> 63) ? (b & 0x7FFFFFFFFFFFFFFFull) : ~b;
+  double x;
+  __builtin_memcpy(&x, &b, 8);
+  return x;
+}
+// a leaf's entries into index order (count <= FLAT_LEAF_MAX)
+RT_HD void flat_leaf_sort(uint32_t* v, uint32_t count) {
+  for (uint32_t i = 1; i < count; ++i)
+    for (uint32_t k = i; k > 0 && v[k] < v[k - 1]; --k) { const uint32_t t = v[k]; v[k] = v[k - 1]; v[k - 1] = t; }
+}
+
 }  // namespace rtc
 
 #if defined(__HIPCC__)
@@ -124,6 +187,25 @@ struct Job {
 
 hipError_t prepare(const Job& j, hipStream_t stream);
 hipError_t refit(const Job& j, hipStream_t stream);
+
+// The order table built anew on the device, from the boxes prepare() left: per depth with a range to split, each range's
+// centre extent, each entry's key, ONE sort of all boxed entries under (range, key, index); then every leaf into index order.  The node
+// skeleton does not change (it follows from the counts), so a refit() over the new order table completes the structure.  Nothing is
+// sized from what a kernel computed: launches, loops and offsets follow from n and m alone.
+struct BuildJob {
+  uint32_t n = 0, m = 0;                    // entries; those with a box (the always-visited run holds the other n - m)
+  const double* box = nullptr;              // [n][6] prepare()'s
+  const uint32_t* start = nullptr;          // [m] the boxed entries in index order
+  const uint32_t* live_order = nullptr;     // [n] the always-visited run is copied from it
+  rtc::FlatBuildItem* item = nullptr;       // [m] scratch
+  unsigned long long* extent = nullptr;     // build_extent_bytes(m) of scratch
+  void* sort_tmp = nullptr;                 // build_sort_bytes(m) of scratch
+  size_t sort_bytes = 0;
+  uint32_t* order = nullptr;                // [n] the spare order table
+};
+size_t build_extent_bytes(uint32_t m);
+hipError_t build_sort_bytes(uint32_t m, size_t* bytes);
+hipError_t build(const BuildJob& b, hipStream_t stream);
 
 // Shading normals (rt_hip_scene_set_flat_normals): per entry, its 72-byte record by rt_flat_normal.h rt_flat_normal_prepare.
 // The status block is prepare()'s: bad_finite = the lowest entry with a refused vector, bad_degenerate = the lowest parallelogram that

@@ -6,6 +6,7 @@
 // hands a box from one workgroup to another inside a launch (the L2s of the XCDs are not coherent with each other and a CU's L1 is not
 // refreshed by another CU's stores; a stale box would be a silently wrong frame).  min and max are exact, so the union does not depend on
 // the order it is formed in and equals the host builder's.  Plain global atomics and vector stores only.
+// Behind the refit: the order table built anew on the device, for a rebuild the caller asks for.
 #include <hip/hip_runtime.h>
 
 #include "rt_flat_build.h"
@@ -150,3 +151,142 @@ hipError_t refit(const Job& j, hipStream_t stream) {
 }
 
 }  // namespace rtfb
+
+// ------------------------------------------------------------------ the order table built anew
+// build_flat_bvh's splits, depth by depth, all ranges of a depth at once.  A position's range follows from the counts (rt_flat_build.h
+// flat_range_at): no table of ranges, nothing sized from what a kernel wrote.  Per depth three steps, each a launch of its own — the
+// kernel boundary is again the only hand-over between workgroups: flat_build_extent forms every range's centre extent with 64-bit
+// integer atomics on order-preserving bit patterns (min and max are exact: the arrival order cannot show); flat_build_keys gives every
+// entry its range and its centre along the range's axis; a merge sort under flat_item_less puts each range's smaller half in front.
+// (The wave intrinsics and the device-wide sort are the compiler's for the GPU only: the kernel-language emulation the CPU tests compile
+// this file against stops here, and tests/flatbuild drives the same RT_HD expressions with plain loops.)
+#ifdef __HIPCC__
+#include <rocprim/device/device_merge_sort.hpp>
+
+namespace rtfb {
+namespace {
+
+// the centre of entry e along axis a; an entry prepare() refused has no box (the update is dropped after the readback): any finite key
+__device__ __forceinline__ double build_centre(const BuildJob& b, uint32_t e, int a) {
+  const double c = rtc::flat_centre(b.box[6 * (size_t)e + a], b.box[6 * (size_t)e + 3 + a]);
+  return fabs(c) <= 0x1p1000 ? c : 0.0;
+}
+__device__ __forceinline__ unsigned long long* build_extent_of(const BuildJob& b, uint32_t depth, uint32_t r) {
+  return b.extent + 6 * ((((size_t)1 << depth) - 1u) + r);   // depth d's 2^d ranges lie behind those of the depths above
+}
+
+__global__ void __launch_bounds__(BLOCK) flat_build_start(BuildJob b) {
+  const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+  if (p >= b.m) return;
+  const uint32_t e = b.start[p];
+  rtc::FlatBuildItem it;
+  it.key = 0.0; it.seg = 0u; it.idx = e < b.n ? e : 0u;
+  b.item[p] = it;
+}
+
+// per position: its entry's centre into the extent of its range, {min x, y, z, ~max x, y, z} as ordered bits, all by atomicMin (the
+// words start as all ones).  A wave whose lanes share one range — every wave of a range of 128 positions or more but two — reduces
+// across its lanes first and issues six atomics, not 384.
+__global__ void __launch_bounds__(BLOCK) flat_build_extent(BuildJob b, uint32_t depth) {
+  const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+  rtc::FlatRange g = {0u, 0u, NONE};
+  bool live = false;
+  if (p < b.m) {
+    g = rtc::flat_range_at(p, b.m, depth);
+    live = g.b - g.a > rtc::FLAT_LEAF_MAX;
+  }
+  unsigned long long w[6];
+  for (int k = 0; k < 6; ++k) w[k] = ~0ull;
+  if (live) {
+    const uint32_t e = b.item[p].idx;
+    if (e < b.n)
+      for (int a = 0; a < 3; ++a) {
+        const unsigned long long o = rtc::flat_ordered_bits(build_centre(b, e, a));
+        w[a] = o; w[3 + a] = ~o;
+      }
+  }
+  const unsigned long long mask = __ballot(live);
+  if (!mask) return;
+  const int first = __ffsll((long long)mask) - 1;
+  const uint32_t r0 = (uint32_t)__shfl((int)g.r, first);
+  if (__all(!live || g.r == r0)) {
+    for (int k = 0; k < 6; ++k)
+      for (int s = 32; s > 0; s >>= 1) {
+        const unsigned long long o = __shfl_xor(w[k], s);
+        w[k] = o < w[k] ? o : w[k];
+      }
+    if ((int)(threadIdx.x & 63u) == first) {
+      unsigned long long* x = build_extent_of(b, depth, r0);
+      for (int k = 0; k < 6; ++k) atomicMin(x + k, w[k]);
+    }
+  } else if (live) {
+    unsigned long long* x = build_extent_of(b, depth, g.r);
+    for (int k = 0; k < 6; ++k) atomicMin(x + k, w[k]);
+  }
+}
+
+// per position: the item the sort of this depth orders.  In a range that is a leaf already the key is 0.0: its entries fall into index order.
+__global__ void __launch_bounds__(BLOCK) flat_build_keys(BuildJob b, uint32_t depth) {
+  const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+  if (p >= b.m) return;
+  const rtc::FlatRange g = rtc::flat_range_at(p, b.m, depth);
+  rtc::FlatBuildItem it = b.item[p];
+  it.seg = g.r; it.key = 0.0;
+  if (g.b - g.a > rtc::FLAT_LEAF_MAX && it.idx < b.n) {
+    const unsigned long long* x = build_extent_of(b, depth, g.r);
+    double clo[3], chi[3];
+    for (int a = 0; a < 3; ++a) { clo[a] = rtc::flat_from_ordered_bits(x[a]); chi[a] = rtc::flat_from_ordered_bits(~x[3 + a]); }
+    it.key = build_centre(b, it.idx, rtc::flat_split_axis(clo, chi));
+  }
+  b.item[p] = it;
+}
+
+// per position, the first of each leaf working: the leaf's up to 4 entries into index order, behind the always-visited run
+__global__ void __launch_bounds__(BLOCK) flat_build_leaves(BuildJob b) {
+  const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+  if (p >= b.m) return;
+  const rtc::FlatRange g = rtc::flat_range_at(p, b.m, rtc::FLAT_DEPTH_ALL);
+  if (p != g.a) return;
+  const uint32_t count = g.b - g.a < rtc::FLAT_LEAF_MAX ? g.b - g.a : rtc::FLAT_LEAF_MAX;
+  uint32_t v[rtc::FLAT_LEAF_MAX];
+  for (uint32_t k = 0; k < count; ++k) v[k] = b.item[g.a + k].idx;
+  rtc::flat_leaf_sort(v, count);
+  uint32_t* out = b.order + (b.n - b.m) + g.a;
+  for (uint32_t k = 0; k < count; ++k) out[k] = v[k];
+}
+
+struct ItemLess {
+  __host__ __device__ bool operator()(const rtc::FlatBuildItem& x, const rtc::FlatBuildItem& y) const { return rtc::flat_item_less(x, y); }
+};
+
+}  // namespace
+
+size_t build_extent_bytes(uint32_t m) { return 48u * ((((size_t)1 << rtc::flat_build_depths(m)) - 1u) + 1u); }
+hipError_t build_sort_bytes(uint32_t m, size_t* bytes) {
+  rtc::FlatBuildItem* none = nullptr;
+  *bytes = 0;
+  return m ? rocprim::merge_sort(nullptr, *bytes, none, none, (size_t)m, ItemLess()) : hipSuccess;
+}
+
+hipError_t build(const BuildJob& b, hipStream_t stream) {
+  hipError_t e;
+  if (b.m > b.n) return hipErrorInvalidValue;
+  const uint32_t run = b.n - b.m, depths = rtc::flat_build_depths(b.m);
+  // the always-visited run is in entry order and its set did not change (a changed set is Status::mismatch: the host builds)
+  if (run && (e = hipMemcpyAsync(b.order, b.live_order, (size_t)run * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream)) != hipSuccess) return e;
+  if (!b.m) return hipSuccess;
+  if ((e = hipMemsetAsync(b.extent, 0xFF, build_extent_bytes(b.m), stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(flat_build_start, dim3(blocks_for(b.m)), dim3(BLOCK), 0, stream, b);
+  for (uint32_t d = 0; d < depths; ++d) {
+    hipLaunchKernelGGL(flat_build_extent, dim3(blocks_for(b.m)), dim3(BLOCK), 0, stream, b, d);
+    hipLaunchKernelGGL(flat_build_keys, dim3(blocks_for(b.m)), dim3(BLOCK), 0, stream, b, d);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t bytes = b.sort_bytes;
+    if ((e = rocprim::merge_sort(b.sort_tmp, bytes, b.item, b.item, (size_t)b.m, ItemLess(), stream)) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(flat_build_leaves, dim3(blocks_for(b.m)), dim3(BLOCK), 0, stream, b);
+  return hipGetLastError();
+}
+
+}  // namespace rtfb
+#endif

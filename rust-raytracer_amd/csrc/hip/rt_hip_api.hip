@@ -194,7 +194,13 @@ struct RtHipScene {
       // what a refit needs of the structure as built (rt_flat_build.h FlatTopology), on the device and on the host: topo's vectors are the staging of their uploads
       DevBuf boxed, leaves, levels;
       rtc::FlatTopology topo;
-      struct Scratch { DevBuf quv, box, status; } scratch;  // the device code's: the geometry as uploaded, a box per entry, the status block
+      // the device code's: the geometry as uploaded, a box per entry, the status block; the device build's (§26) items, range extents, sort storage
+      struct Scratch { DevBuf quv, box, status, item, extent, sort_tmp; } scratch;
+      // the device build starts from the boxed entries in index order: resident from the first device build after each host build on
+      DevBuf start;
+      std::vector<uint32_t> keep_start;
+      bool start_ready = false;
+      uint32_t device_builds = 0;   // order tables built on the device since creation
       // on the host: the limits (a rebuild runs build_flat_bvh) and the staging of a rebuild's uploads, kept like the texels below
       std::vector<double> host_lim, keep_quv;
       std::vector<rtc::FlatNode> keep_nodes;
@@ -267,6 +273,7 @@ struct RtHipScene {
     int light_nest_pool = 1; // "light_nest_pool" option: 0 = nested light activations always go through the HBM overflow (tests)
     int chunk_spp = 0;       // 0 = automatic
     int tile_batch = 0;      // 0 = automatic; else tiles a workgroup takes from the queue per atomic, 1..64
+    int flat_build = 0;      // "flat_build" option: who builds the order table when rt_hip_scene_update_flats is asked to rebuild: 0 the host, 1 the device
   } opt;
 
   // What a launch writes — each scene and view has its own.
@@ -460,6 +467,7 @@ int upload_flat_structure(RtHipScene::Resident::Flats& f, RtHipScene::Resident::
   int rc;
   if ((rc = upload(g.nodes, nodes)) != RT_OK || (rc = upload(g.order, order)) != RT_OK) return rc;
   rtc::flat_topology(nodes, order, n_always, f.topo);
+  f.start_ready = false;
   if ((rc = upload(f.boxed, f.topo.boxed)) != RT_OK || (rc = upload(f.leaves, f.topo.leaves)) != RT_OK) return rc;
   return upload(f.levels, f.topo.level_nodes);
 }
@@ -662,6 +670,7 @@ extern "C" int rt_hip_set_option(RtHipScene* s, const char* key, int64_t value) 
   if (!std::strcmp(key, "light_nest_pool")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "light_nest_pool must be 0 or 1"); s->opt.light_nest_pool = (int)value; return RT_OK; }
   if (!std::strcmp(key, "force_lit")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "force_lit must be 0 or 1"); s->opt.force_lit = (int)value; return RT_OK; }  // (diagnostics: an unlit scene through the lit kernels — what their code costs the ordinary lanes, profiles/r04_run5_lit_sections.log)
   if (!std::strcmp(key, "tile_batch")) { if (value < 0 || value > 64) return fail(RT_ERR_INVALID, "tile_batch must be 0..64"); s->opt.tile_batch = (int)value; return RT_OK; }
+  if (!std::strcmp(key, "flat_build")) { if (value < 0 || value > 1) return fail(RT_ERR_INVALID, "flat_build must be 0 (the host builds) or 1 (the device builds)"); s->opt.flat_build = (int)value; return RT_OK; }
   if (!std::strcmp(key, "chunk_spp")) { if (value < 0) return fail(RT_ERR_INVALID, "chunk_spp must be >= 0"); s->opt.chunk_spp = (int)value; return RT_OK; }
   if (!std::strcmp(key, "samples_per_pixel") || !std::strcmp(key, "max_depth")) {
     if (value < 0 || value > (int64_t)0xFFFFFFFFll) return fail(RT_ERR_INVALID, std::string(key) + " must be in 0 .. 2^32-1");
@@ -1251,6 +1260,8 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->flat.n_nodes;  // nodes of the structure over the flat primitives; 0: none
   if (!std::strcmp(key, "flat_normals")) return (int64_t)s->res->flat.n_normals;  // entries that carry shading normals; 0: none
   if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat.refits;  // updates applied by refit since the structure was last built
+  if (!std::strcmp(key, "flat_build")) return (int64_t)s->opt.flat_build;  // the option: 1: a rebuild the caller asks for runs on the device
+  if (!std::strcmp(key, "flat_device_builds")) return (int64_t)s->res->flat.device_builds;  // order tables built on the device since creation
   if (!std::strcmp(key, "quads")) return (int64_t)s->res->flat.n_quads;         // flat parallelograms (rt_hip_scene_create_quads)
   if (!std::strcmp(key, "last_kernel")) return (int64_t)s->last_kernel;   // QUADS 512 | SOLID 256 | MEDIUM 128 | MOTION 64 | LENS 32 | ACCUM 16 | WIDE 8 | HL 4 | SIMPLE 2 | LDS 1; -1 before the first launch
   if (!std::strcmp(key, "media")) return (int64_t)s->res->n_media;         // spheres of kind RT_MAT_MEDIUM
@@ -1976,12 +1987,27 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
   const uint32_t n = n_quads;
   const bool bvh = f.n_nodes != 0u;
   bool rebuild = bvh && (flags & RT_UPDATE_FLATS_REBUILD) != 0u;
+  const bool device_build = rebuild && s->opt.flat_build == 1;   // (§26: the order table on the device; a changed refused set still goes to the host)
   RtHipScene::Resident::Flats::Tables& spare = f.spare;
   RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
   if ((rc = room(spare.rec, f.rec_bytes())) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
       (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK) ||
       (bvh && ((rc = room(fb.box, (size_t)n * 48)) != RT_OK || (rc = room(spare.nodes, (size_t)f.n_nodes * sizeof(rtc::FlatNode))) != RT_OK)))
     return rc;
+  rtfb::BuildJob bj;
+  if (device_build) {  // the boxed entries in index order, uploaded once per host build; scratch and the spare order table, allocated once
+    if (!f.start_ready) {
+      f.keep_start.clear();
+      for (uint32_t k = 0; k < n; ++k) if (f.topo.boxed[k]) f.keep_start.push_back(k);
+      if ((rc = upload(f.start, f.keep_start)) != RT_OK) return rc;
+      f.start_ready = true;
+    }
+    bj.n = n; bj.m = (uint32_t)f.keep_start.size();
+    RT_HIP_TRY(rtfb::build_sort_bytes(bj.m, &bj.sort_bytes));
+    if ((rc = room(spare.order, (size_t)n * sizeof(uint32_t))) != RT_OK || (rc = room(fb.item, (size_t)bj.m * sizeof(rtc::FlatBuildItem))) != RT_OK ||
+        (rc = room(fb.extent, rtfb::build_extent_bytes(bj.m))) != RT_OK || (rc = room(fb.sort_tmp, bj.sort_bytes)) != RT_OK)
+      return rc;
+  }
   if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
   pc.mark("update_flats.upload");
   rtfb::Job j;
@@ -2005,7 +2031,15 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
     return hipMemcpy(spare.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice);
   };
   RT_HIP_TRY(rtfb::prepare(j, nullptr));
-  if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
+  if (device_build) {  // (enqueued before the readback too: the order table into the spare, then the refit over it — the skeleton is the live one)
+    bj.box = fb.box.get<const double>(); bj.start = f.start.get<const uint32_t>(); bj.live_order = f.live.order.get<const uint32_t>();
+    bj.item = fb.item.get<rtc::FlatBuildItem>(); bj.extent = fb.extent.get<unsigned long long>(); bj.sort_tmp = fb.sort_tmp.p;
+    bj.order = spare.order.get<uint32_t>();
+    RT_HIP_TRY(rtfb::build(bj, nullptr));
+    j.order = bj.order;
+    RT_HIP_TRY(rtfb::refit(j, nullptr));
+    RT_HIP_TRY(put_header(f.n_nodes, spare.order));
+  } else if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
     RT_HIP_TRY(rtfb::refit(j, nullptr));
     RT_HIP_TRY(put_header(f.n_nodes, f.live.order));
   } else if (!bvh && f.header_recs()) RT_HIP_TRY(put_header(0u, f.live.order));  // (§25: a scan with shading normals keeps their header)
@@ -2017,8 +2051,9 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
     return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)");
   }
   if (bvh && st.mismatch) rebuild = true;  // an entry became a needle, crossed 2^40, or stopped being one: the order table is another
+  const bool built = device_build && !st.mismatch;  // the device's order table stands; with a mismatch the counts are others: the host builds
   uint32_t n_nodes = f.n_nodes;
-  if (rebuild) {  // the host's build_flat_bvh over the host's records, as creation runs it; the records themselves stay the device's
+  if (rebuild && !built) {  // the host's build_flat_bvh over the host's records, as creation runs it; the records themselves stay the device's
     const double* host_quv = quv;
     if (on_device) {
       f.keep_quv.resize(9 * (size_t)n);
@@ -2047,6 +2082,7 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
   if (bvh) f.live.nodes.swap(spare.nodes);
   if (rebuild) { f.live.order.swap(spare.order); f.n_nodes = n_nodes; }
   f.refits = (bvh && !rebuild) ? f.refits + 1u : 0u;
+  if (built) f.device_builds++;
   rc = adopt_tables(s, Moved::flats);
   pc.mark("update_flats.configuration");
   return rc;

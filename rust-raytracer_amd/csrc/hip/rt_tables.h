@@ -576,7 +576,7 @@ inline std::string build_flat_bvh(HostTables& t) {
   for (uint32_t k = 0; k < n; ++k) {
     Box& b = box[k];
     if (flat_entry_box(t.quads[k], t.quad_lim.empty() ? 2.0 : t.quad_lim[k], b.lo, b.hi)) {
-      for (int a = 0; a < 3; ++a) b.c[a] = 0.5 * b.lo[a] + 0.5 * b.hi[a];
+      for (int a = 0; a < 3; ++a) b.c[a] = flat_centre(b.lo[a], b.hi[a]);
       idx.push_back(k);
     } else always.push_back(k);
   }
@@ -608,19 +608,17 @@ inline std::string build_flat_bvh(HostTables& t) {
         }
       }
       nd.pad = 0u;
-      if (b - a <= 4) {
+      if (b - a <= FLAT_LEAF_MAX) {
         std::sort(idx.begin() + a, idx.begin() + b);
         nd.first = (uint32_t)t.flat_order.size(); nd.count = (uint32_t)(b - a); nd.skip = (uint32_t)me + 1u;
         for (size_t i = a; i < b; ++i) t.flat_order.push_back(idx[i]);
         t.flat_nodes.push_back(nd);
         return;
       }
-      int axis = 0;
-      for (int k = 1; k < 3; ++k) if (chi[k] - clo[k] > chi[axis] - clo[axis]) axis = k;
+      const int axis = flat_split_axis(clo, chi);
       const size_t mid = a + (b - a) / 2;
       std::nth_element(idx.begin() + a, idx.begin() + mid, idx.begin() + b, [&](uint32_t x, uint32_t y) {
-        const double cx = box[x].c[axis], cy = box[y].c[axis];
-        return cx < cy || (cx == cy && x < y);
+        return flat_split_less(box[x].c[axis], x, box[y].c[axis], y);
       });
       nd.first = 0u; nd.count = 0u; nd.skip = 0u;
       t.flat_nodes.push_back(nd);

@@ -31,6 +31,7 @@ struct Options {
   bool denoise = false;          // --denoise
   bool flat_bvh = false;         // --flat-bvh
   std::string flat_frames;       // --flat-frames PREFIX; empty: not given
+  long flat_rebuild = 0;         // --flat-rebuild K >= 1: every K-th frame's update rebuilds the structure, on the device; 0: not given
   bool t_surface = false;        // --temporal-surface
   double t_alpha = -1.0;         // --temporal-alpha A in [0, 1]; < 0: not given
   double t_alpha_specular = -1.0;  // --temporal-alpha-specular B in [0, 1]; < 0: not given
@@ -55,6 +56,7 @@ inline bool allowed(const Options& o, Mode mode) {
       {o.min_spp_given, in(ADAPTIVE), true},                     // = needs --adaptive
       {o.denoise, in(PROGRESSIVE, DENOISED_ONE_SHOT, DENOISED_ANIMATION), true},
       {!o.flat_frames.empty(), in(ANIMATION), true},             // (moved flat primitives are not followed by the temporal filter)
+      {o.flat_rebuild > 0, in(ANIMATION), !o.flat_frames.empty()},  // = needs --flat-frames (and a structure scene: run()'s check)
       {o.t_surface, in(DENOISED_ANIMATION), true},
       {o.t_alpha >= 0.0, in(DENOISED_ANIMATION), true},
       {o.t_alpha_specular >= 0.0, in(DENOISED_ANIMATION), o.t_surface},
@@ -71,7 +73,7 @@ inline bool whole(const char* s, long& v) { char* end = nullptr; v = std::strtol
 inline bool real(const char* s, double& v) { char* end = nullptr; v = std::strtod(s, &end); return end != s && *end == '\0'; }
 inline bool unit_interval(const char* s, double& v) { return real(s, v) && v >= 0.0 && v <= 1.0; }
 
-// The last occurrence of a flag wins, but --flat-bvh or --flat-frames given twice is refused.  A flag without its value, an unknown flag, a
+// The last occurrence of a flag wins, but --flat-bvh, --flat-frames or --flat-rebuild given twice is refused.  A flag without its value, an unknown flag, a
 // malformed or out-of-range value: mode USAGE.  (--frames goes through atoi and --orbit through atof: `--frames x` is `--frames 0`.)
 inline Options parse(int argc, char** argv) {
   Options o;
@@ -91,6 +93,7 @@ inline Options parse(int argc, char** argv) {
     if (is("--frames")) { o.frames = std::atoi(v); o.frames_given = true; }
     else if (is("--orbit")) { o.orbit = std::atof(v); o.orbit_given = true; }
     else if (is("--flat-frames")) { ok = o.flat_frames.empty() && v[0]; o.flat_frames = v; }
+    else if (is("--flat-rebuild")) ok = o.flat_rebuild == 0 && whole(v, o.flat_rebuild) && o.flat_rebuild >= 1 && o.flat_rebuild <= 0x7FFFFFFFl;
     else if (is("--temporal-alpha")) ok = unit_interval(v, o.t_alpha);
     else if (is("--temporal-alpha-specular")) ok = unit_interval(v, o.t_alpha_specular);
     else if (is("--shutter")) ok = unit_interval(v, o.shutter);

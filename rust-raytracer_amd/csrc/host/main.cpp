@@ -232,6 +232,7 @@ struct Pose {
   bool lens = false;          // the scene has a thin lens
   bool spheres = false;       // --shutter: the spheres move to c -> c1 (n x 3 each)
   bool flats = false;         // --flat-frames: the flat primitives move to quv (n x 9)
+  uint32_t flat_flags = 0;    // --flat-rebuild K: RT_UPDATE_FLATS_REBUILD on every K-th frame's update
   std::vector<double> c, c1, quv;
   std::vector<double> normals;  // --flat-frames: the frame's shading normals (n x 9), set after its flat primitives; empty: the scene has none
 };
@@ -241,13 +242,13 @@ int apply(RtHipScene* hs, const Pose& p) {
   int rc = rt_hip_set_camera(hs, p.cam, p.cam + 3, p.cam + 6, p.cam + 9);
   if (rc == RT_OK && p.lens) rc = rt_hip_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
   if (rc == RT_OK && p.spheres) rc = rt_hip_scene_update_spheres(hs, p.c.data(), p.c1.data());
-  if (rc == RT_OK && p.flats) rc = rt_hip_scene_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), 0u);
+  if (rc == RT_OK && p.flats) rc = rt_hip_scene_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), p.flat_flags);
   if (rc == RT_OK && p.flats && !p.normals.empty()) rc = rt_hip_scene_set_flat_normals(hs, p.normals.data(), (uint32_t)(p.normals.size() / 9), 0u);
   return rc;
 }
 int apply(RtHipGroup* hs, const Pose& p) {  // (no frame may be in flight while the spheres or the flat primitives move)
   int rc = p.spheres ? rt_hip_group_update_spheres(hs, p.c.data(), p.c1.data()) : RT_OK;
-  if (rc == RT_OK && p.flats) rc = rt_hip_group_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), 0u);
+  if (rc == RT_OK && p.flats) rc = rt_hip_group_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), p.flat_flags);
   if (rc == RT_OK && p.flats && !p.normals.empty()) rc = rt_hip_group_set_flat_normals(hs, p.normals.data(), (uint32_t)(p.normals.size() / 9), 0u);
   if (rc == RT_OK) rc = rt_hip_group_set_camera(hs, p.cam, p.cam + 3, p.cam + 6, p.cam + 9);
   if (rc == RT_OK && p.lens) rc = rt_hip_group_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
@@ -294,6 +295,7 @@ struct Anim {
   // with --flat-frames, frame f's flat primitives from its file: "", or what is wrong with the file
   std::string flats(int f, Pose& p) {
     p.flats = flat_files.on();
+    p.flat_flags = (r.o.flat_rebuild > 0 && f > 0 && f % r.o.flat_rebuild == 0) ? RT_UPDATE_FLATS_REBUILD : 0u;
     return p.flats ? flat_files.load(f, p.quv, p.normals) : std::string();
   }
   std::string pose(int f, Pose& p) { view(f, p); return flats(f, p); }
@@ -415,6 +417,7 @@ int animate_sharded(Anim& a, Pose& p) {
   int rc = create_group(a.r, &hs);
   if (rc != RT_OK) return render_failed(rc);
   (void)rt_hip_group_set_option(hs, "prepare_host_output", 2);  // (pinned staging for the two frames in flight + the copy path, at set-up: not inside the first submit)
+  if (a.r.o.flat_rebuild > 0 && (rc = rt_hip_group_set_option(hs, "flat_build", 1)) != RT_OK) { rt_hip_group_destroy(hs); return render_failed(rc); }
   const auto t_begin = Clock::now();
   const unsigned W = anim_writers();
   AnimStats stats(a.frames);
@@ -534,6 +537,7 @@ int animate_frames(Anim& a, unsigned G) {
       auto say = [&](auto&& print) { std::lock_guard<std::mutex> lk(out_mu); print(); };  // (one device's lines at a time)
       RtHipScene* hs = nullptr;
       int rc = create_scene(a.r, (int)(g % (unsigned)ndev), &hs);
+      if (rc == RT_OK && a.r.o.flat_rebuild > 0 && (rc = rt_hip_set_option(hs, "flat_build", 1)) != RT_OK) { rt_hip_scene_destroy(hs); hs = nullptr; }
       if (rc != RT_OK) { say([&] { status[g] = render_failed(rc); }); return; }
       PngWriters writers(1, 2, a, &stats);
       Pose p;
@@ -576,6 +580,9 @@ int animate_frames(Anim& a, unsigned G) {
 // anything else, or an unreadable file, ends the run with a message that names the frame).  The resident scene's flat primitives are moved
 // before every frame (rt_hip_group_update_flats / rt_hip_scene_update_flats: the structure of --flat-bvh is refit on the GPU).  Combines
 // with --orbit, --shutter, --flat-bvh, RT_GPUS and RT_ANIM=frames; without --frames, or with --denoise, --passes or --adaptive: the usage line.
+// `--flat-rebuild K` (only with --flat-frames, K >= 1): the update of every K-th frame (f % K == 0, f > 0) carries
+// RT_UPDATE_FLATS_REBUILD and the scene's option "flat_build" is 1 — the structure is built anew on the device instead of refit.  The scene
+// must have the structure.  A rebuild changes how fast the frames trace, never what they are: the PNGs are those of the run without the flag.
 int animate(const Run& r) {
   Anim a(r);
   if (r.o.mode == cli::DENOISED_ANIMATION) return animate_temporal(a);
@@ -589,6 +596,10 @@ int animate(const Run& r) {
     if (const double* nr = rt_scene_flat_normals(r.sf, &n_normals)) a.flat_files.base_normals.assign(nr, nr + 9 * (size_t)n_normals);
     const std::string why = a.flats(0, first);
     if (!why.empty()) { std::fprintf(stderr, "%s\n", why.c_str()); return 101; }
+    if (r.o.flat_rebuild > 0 && !(r.o.flat_bvh || rt_scene_flat_bvh(r.sf))) {
+      std::fprintf(stderr, "--flat-rebuild: the scene has no structure over its flat primitives (\"flat_bvh\": true in the file, or --flat-bvh)\n");
+      return 101;
+    }
   }
   const char* mode = std::getenv("RT_ANIM");
   if (mode && !std::strcmp(mode, "frames")) {

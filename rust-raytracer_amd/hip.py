@@ -264,7 +264,8 @@ class HipScene:
     def update_flats(self, quv, rebuild=False):
         """rt_hip_scene_update_flats: move the flat primitives to quv — [n_quads, 9] float64 (q, u, v per entry), a numpy
         array or a CUDA torch tensor; a contiguous tensor on the scene's device is read where it is (no PCIe).  The structure is refit on
-        the device; rebuild=True (or a change of the set of entries outside its preconditions) builds it anew on the host.  Blocking."""
+        the device; rebuild=True (or a change of the set of entries outside its preconditions) builds it anew: on the host, or with
+        set_option("flat_build", 1) and an unchanged set on the device.  Blocking."""
         p, n, flags, keep = _flat_geometry(quv, self.device, rebuild)
         _check(self._L.rt_hip_scene_update_flats(self._h, p, n, flags), self._L)
         del keep

@@ -3,7 +3,8 @@
 
     python tools/codeobj_stats.py [--brief] [extra hipcc flags ...]  > profiles/rNN_codeobj.txt
 
-Compiles rt_hip_api.hip and rt_grid_build.hip (the device grid build) for gfx950 with the product's flags (+ extras) and -save-temps into a scratch directory
+Compiles rt_hip_api.hip, rt_grid_build.hip (the device grid build) and rt_flat_build.hip (the flat primitives moved and their
+structure refit or built anew, §24 and §26) for gfx950 with the product's flags (+ extras) and -save-temps into a scratch directory
 and prints one line per kernel: VGPRs, SGPRs, spilled VGPRs / SGPRs, scratch bytes per lane, code size, and a static
 instruction census of the megakernel instantiations (v_mov share: the copies at control-flow joins).
 --brief: the register, spill and scratch figures alone, for before / after pairs that are compared line by line.  No GPU needed."""
@@ -14,7 +15,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(ROOT, "rust-raytracer_amd", "csrc", "hip", f) for f in ("rt_hip_api.hip", "rt_grid_build.hip")]
+SRCS = [os.path.join(ROOT, "rust-raytracer_amd", "csrc", "hip", f) for f in ("rt_hip_api.hip", "rt_grid_build.hip", "rt_flat_build.hip")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DRT_WAVES_PER_EU=4"]
 
 
