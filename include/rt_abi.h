@@ -91,7 +91,7 @@ typedef struct RtSphere {
 /* A quad (an extension of the schema; the reference has no such object and its loader rejects the file): the flat
  * parallelogram q + a u + b v, 0 <= a, b <= 1, two-sided.  The material fields mean what they mean in RtSphere; a quad may be
  * Lambertian, Metal, Glass, Checker or Noise (the solid's pattern in the quad's frame: centre = q).  Texture, Light and Medium quads
- * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads do not move within a frame (no center1); rt_hip_scene_update_flats moves them between frames.
+ * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads do not move within a frame (no center1) unless rt_hip_scene_set_flat_motion gives them a displacement over the shutter; rt_hip_scene_update_flats moves them between frames.
  * Triangles: `reserved` carries the SHAPE of the flat primitive, RT_QUAD_SHAPE_PARALLELOGRAM (0, the quad above) or
  * RT_QUAD_SHAPE_TRIANGLE (1): the points q + a u + b v with 0 <= a, 0 <= b, a + b <= 1, two-sided.  Everything else about the entry —
  * its place in the order, its id, its materials, the refusals — is a quad's.  A value above 1 is RT_ERR_INVALID (`quad k: bad shape`). */
@@ -276,6 +276,12 @@ const RtQuad* rt_scene_quads(const RtSceneFile*, uint32_t* n);
  * rt_hip_scene_set_flat_normals takes.  NULL and 0 when no entry has normals.  Owned by the RtSceneFile.  rt_scene_to_json writes a
  * triangle that has normals as its exact q, u, v with "shape": "triangle" and "normals": load -> write -> load is bit for bit. */
 const double* rt_scene_flat_normals(const RtSceneFile*, uint32_t* n);
+/* Motion within the frame (an extension too): an optional "move": [dx, dy, dz] (or {"x", "y", "z"}) on the object map of a
+ * quad, a "triangle", a "box" or a "mesh" — a box or a mesh gives it to every face.  *n x 3 f64, the displacement over the open shutter
+ * of every entry of rt_scene_quads as written, three zeros for an entry without — what rt_hip_scene_set_flat_motion takes.  NULL and 0
+ * when no object has the key.  Owned by the RtSceneFile.  A duplicate key or a non-finite value is a load error naming objects[i];
+ * rt_scene_to_json writes the key only where the file had it: load -> write -> load is bit for bit. */
+const double* rt_scene_flat_motion(const RtSceneFile*, uint32_t* n);
 /* The structure over the flat primitives (an extension too): a top-level "flat_bvh": true beside "camera" and "objects"
  * asks for rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh and lifts the loader's cap from RT_MAX_QUADS to RT_MAX_FLATS_BVH
  * (the entry that crosses it is still named by its objects[i]).  1 for such a file, 0 when the key is false or absent: today's behaviour.
@@ -517,6 +523,25 @@ int rt_hip_scene_update_flats(RtHipScene*, const double* quv, uint32_t n_quads, 
  * ("quad k: normal ..."), non-zero normals on a parallelogram ("quad k: normal ..."; of all bad entries the lowest k is reported); a
  * scene whose tables a live view shares (rt_hip_group_set_flat_normals).  After any error the scene renders exactly as before. */
 int rt_hip_scene_set_flat_normals(RtHipScene*, const double* normals, uint32_t n_quads, uint32_t flags);
+/* Flat primitives that move while the shutter is open (the arithmetic is csrc/common/rt_flat_motion.h, bit for bit).
+ * move = n_quads x 3 f64 in entry order: the displacement m of every entry over the open shutter.  At the shutter time tau of a sample
+ * (DESIGN.md §14's: the same draw, the same value for every segment of the sample) the entry is the same primitive translated by m tau;
+ * u, v and the normal do not change.  The pattern of a Checker or Noise entry and the weights of its shading normals ride with it.  An
+ * entry of three zeros is tested on exactly the bits it has in a scene without motion.  n_quads must be the scene's.  NULL, or all
+ * zeros, removes the motion: the scene is then, table for table and bit for bit, one that never had any.  A scene with a moving entry
+ * selects the MOTION kernels (rt_hip_scene_query "last_kernel"), with or without a moving sphere; "motion" keeps counting spheres.
+ * The boxes of the structure are swept (the union of the entry's box at both ends of its motion): the call refits them, or builds the
+ * structure anew when an end of a motion takes an entry into or out of the always-visited set, exactly as rt_hip_scene_update_flats
+ * does, and the frame stays the full scan's in every bit.  rt_hip_scene_update_flats keeps the motion as set and boxes the new geometry
+ * with it.  rt_hip_temporal / rt_hip_reproject keep treating a flat primitive as not displaced between frames.
+ * flags: 0, or RT_UPDATE_FLATS_DEVICE (move is device memory on the scene's device, 8-byte aligned; only the status crosses back).
+ * Blocking; waits for the scene's unfinished launch and drops what rt_hip_scene_update_flats drops.
+ * rt_hip_scene_query "flat_motion" = the entries that move (0: none); rt_hip_scene_table "flat_motion" = the 32-byte records
+ * {m0, m1, m2, dot(N, m)}, four -0.0 for an entry that does not move (empty without motion).  Every error is RT_ERR_INVALID: a null
+ * scene; another flag; n_quads different from the scene's; a scene without flat primitives; a component of m, or a q + m, that is not
+ * finite ("quad k: ..."; of all bad entries the lowest k is reported); a scene whose tables a live view shares
+ * (rt_hip_group_set_flat_motion).  After any error the scene renders exactly as before. */
+int rt_hip_scene_set_flat_motion(RtHipScene*, const double* move, uint32_t n_quads, uint32_t flags);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
  * camera of a resident scene — the four vectors of camera.rs:52-63 — without touching its tables,
  * and render whole frames of it into a host buffer (internal device framebuffer, blocking). */
@@ -842,6 +867,8 @@ int rt_hip_group_update_spheres(RtHipGroup*, const double* center, const double*
 int rt_hip_group_update_flats(RtHipGroup*, const double* quv, uint32_t n_quads, uint32_t flags);
 /* rt_hip_scene_set_flat_normals on every rank, under the same two conditions. */
 int rt_hip_group_set_flat_normals(RtHipGroup*, const double* normals, uint32_t n_quads, uint32_t flags);
+/* rt_hip_scene_set_flat_motion on every rank, under the same two conditions. */
+int rt_hip_group_set_flat_motion(RtHipGroup*, const double* move, uint32_t n_quads, uint32_t flags);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
  * tile height; *tile_rows_out receives that height (2) */

@@ -101,7 +101,7 @@ HIP_DEPS = tuple(dict.fromkeys(u for _, u, _ in HIP_UNITS)) + (
     "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h", "csrc/hip/rt_grid_build.h",
     "csrc/hip/rt_flat_build.h",
     "csrc/common/rt_atan2.h", "csrc/common/rt_neg_log.h", "csrc/common/rt_solid.h", "csrc/common/rt_quad.h",
-    "csrc/common/rt_flat_normal.h")
+    "csrc/common/rt_flat_normal.h", "csrc/common/rt_flat_motion.h")
 
 
 def kernel_src_hash():

@@ -34,6 +34,7 @@
 #include "../common/rt_solid.h"  // the one checker and lattice noise of the solid textures
 #include "../common/rt_quad.h"   // the one quad test
 #include "../common/rt_flat_normal.h"  // the one shading normal of a triangle
+#include "../common/rt_flat_motion.h"  // the one flat primitive at a shutter time
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__ __forceinline__
@@ -181,7 +182,10 @@ struct QuadView {
 // Shading normals: a scene whose n_tris carries FLAT_NORMALS_BIT has the header too — with or without the structure — and
 // in it the table of 72-byte records (rt_flat_normal.h), one per entry in ENTRY order.  Without the bit no kernel looks for it.
 constexpr uint32_t FLAT_BVH_BIT = 0x80000000u;
+// Motion: a scene whose n_tris carries FLAT_MOTION_BIT has the header too, and in it the table of 32-byte records
+// (rt_flat_motion.h), one per entry in ENTRY order.  Only the MOTION instantiations look for the bit.
 constexpr uint32_t FLAT_NORMALS_BIT = 0x40000000u;
+constexpr uint32_t FLAT_MOTION_BIT = 0x20000000u;
 struct alignas(16) FlatBvhHeader {
   const FlatNode* nodes;
   const uint32_t* order;
@@ -189,7 +193,8 @@ struct alignas(16) FlatBvhHeader {
   const double* lim;      // null in a scene without a triangle
   uint32_t n_nodes, n_quads, id_base, pad0;
   const double* normals;  // [n_quads][9], null in a scene without shading normals
-  uint64_t pad[9];
+  const double* motion;   // [n_quads][4], null in a scene whose flat primitives do not move within a frame
+  uint64_t pad[8];
 };
 static_assert(sizeof(FlatBvhHeader) == sizeof(RtQuadRec), "the header takes the slot of one record in front of the records");
 // The rays the structure takes (DESIGN.md §22 "Preconditions"): every component finite, |o_k| <= 2^40, |d_k| <= 2^100 (a zero, a
@@ -1075,19 +1080,29 @@ RT_HD Surface surface_at(V3 o, V3 d, double t, const SphereGeom& g, double inv_r
 // loop is bounded by n_nodes whatever the tables hold.  A ray outside the preconditions (flat_ray_ok) takes the scan, here, per lane.
 // Cold, like quads_hit.  Called from flats_hit, never from quads_hit: the scan's call and body stay what they were.  Its arguments are
 // o, d and scalars: all in registers.
-RT_HD_COLD HitCB flats_hit_bvh(V3 o, V3 d, const FlatBvhHeader* header, double closest, int best) {
+// MOVING: the same scan and the same walk with every entry at the lane's shutter time tau (rt_flat_motion.h: the entry's
+// record at tau through the same test; the boxes are swept, rt_flat_build.h flat_entry_box_swept) — ONE body for both, so a fix to the
+// traversal is made once; use_bvh 0 sends every ray through the scan ("variant" 1, or a scene without the structure).  With MOVING false
+// the body is flats_hit_bvh's as it was.
+template <bool MOVING>
+RT_HD HitCB flats_walk(V3 o, V3 d, const FlatBvhHeader* header, uint32_t use_bvh, double tau, double closest, int best) {
   struct { const FlatNode* nodes; const uint32_t* order; uint32_t n_nodes; } bvh = {header->nodes, header->order, header->n_nodes};
+  const double* motion = MOVING ? header->motion : nullptr;
+  (void)motion; (void)tau; (void)use_bvh;
   const QuadView quads{header->rec, header->lim};
   const uint32_t n_quads = header->n_quads, id_base = header->id_base;
   HitCB r; r.closest = closest; r.best = best;
   const double oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-  if (!flat_ray_ok(oo, dd)) {
+  if ((MOVING && !use_bvh) || !flat_ray_ok(oo, dd)) {
     RT_FLAT_COUNT(rays_scan);
     for (uint32_t k = 0; k < n_quads; ++k) {
       const RtQuadRec q = quads.rec[k];
       const double lk = quads.lim ? quads.lim[k] : 2.0;
       double t, P[3];
-      if (rt_flat_hit(q, lk, oo, dd, r.closest, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+      bool hit;
+      if constexpr (MOVING) hit = rt_flat_motion_hit_tie(q, lk, motion + 4u * (size_t)k, tau, oo, dd, r.closest, false, &t, P);
+      else hit = rt_flat_hit(q, lk, oo, dd, r.closest, &t, P);
+      if (hit) { r.closest = t; r.best = (int)(id_base + k); }
     }
     return r;
   }
@@ -1117,11 +1132,17 @@ RT_HD_COLD HitCB flats_hit_bvh(V3 o, V3 d, const FlatBvhHeader* header, double c
       const bool tie_ok = r.best >= (int)id_base && (uint32_t)r.best - id_base > k;
       double t, P[3];
       RT_FLAT_COUNT(entry_tests);
-      if (rt_flat_hit_tie(q, lk, oo, dd, r.closest, tie_ok, &t, P)) { r.closest = t; r.best = (int)(id_base + k); }
+      bool hit;
+      if constexpr (MOVING) hit = rt_flat_motion_hit_tie(q, lk, motion + 4u * (size_t)k, tau, oo, dd, r.closest, tie_ok, &t, P);
+      else hit = rt_flat_hit_tie(q, lk, oo, dd, r.closest, tie_ok, &t, P);
+      if (hit) { r.closest = t; r.best = (int)(id_base + k); }
     }
     i = nd.count ? nd.skip : i + 1u;
   }
   return r;
+}
+RT_HD_COLD HitCB flats_hit_bvh(V3 o, V3 d, const FlatBvhHeader* header, double closest, int best) {
+  return flats_walk<false>(o, d, header, 1u, 0.0, closest, best);
 }
 RT_HD_COLD HitCB quads_hit(V3 o, V3 d, QuadView quads, uint32_t n_quads, uint32_t id_base, double closest, int best) {
   HitCB r; r.closest = closest; r.best = best;
@@ -1174,6 +1195,40 @@ RT_HD HitCB flats_hit(const DevScene& sc, V3 o, V3 d, double closest, int best) 
   if (sc.n_tris & FLAT_BVH_BIT) return flats_hit_bvh(o, d, reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, closest, best);
   return quads_hit(o, d, sc.quads, sc.n_quads, sc.n_spheres, closest, best);
 }
+// What the QUADS arms of the MOTION instantiations call: ONE cold entry point — the call site those kernels always had —
+// that takes the scan, the structure, or, in a scene whose flat primitives move within the frame (FLAT_MOTION_BIT: wave-uniform), the
+// moving walk at the lane's shutter time: per lane, with vector loads, since tau differs from lane to lane.
+RT_HD_COLD HitCB flats_hit_shutter(V3 o, V3 d, QuadView quads, uint32_t n_quads, uint32_t id_base, uint32_t n_tris, float tau, double closest, int best) {
+  const FlatBvhHeader* header = reinterpret_cast<const FlatBvhHeader*>(quads.rec) - 1;
+  if (n_tris & FLAT_MOTION_BIT) return flats_walk<true>(o, d, header, n_tris & FLAT_BVH_BIT, (double)tau, closest, best);
+  if (n_tris & FLAT_BVH_BIT) return flats_hit_bvh(o, d, header, closest, best);
+  return quads_hit(o, d, quads, n_quads, id_base, closest, best);
+}
+// The shutter time a table type carries: MotionTables' tau — the MOTION instantiations hand one to every function that takes tables —
+// and none for every other type.
+template <class T> struct TablesTau { static constexpr bool kHas = false; };
+template <class Base> struct TablesTau<MotionTables<Base>> { static constexpr bool kHas = true; };
+// flats_hit for a caller that holds tables: flats_hit_shutter where the tables carry a tau, otherwise flats_hit as it was.
+template <class Tables>
+RT_HD HitCB flats_hit(const DevScene& sc, const Tables& tb, V3 o, V3 d, double closest, int best) {
+  if constexpr (TablesTau<Tables>::kHas) return flats_hit_shutter(o, d, sc.quads, sc.n_quads, sc.n_spheres, sc.n_tris, (float)tb.tau, closest, best);
+  else return flats_hit(sc, o, d, closest, best);
+}
+// The surface of a hit on entry k in a MOTION instantiation, for a scene whose header names shading normals (§25), motion records (§27) or
+// both: the hit normal and the entry's origin at tau — the frame of a solid pattern.  Cold: the ONE call those kernels make beside the
+// plain path, where flat_shading_normal's was.
+struct FlatShutterSurface { V3 normal, q; };
+RT_HD_COLD FlatShutterSurface flat_surface_shutter(const FlatBvhHeader* header, uint32_t k, uint32_t n_tris, float tau, V3 d, V3 P) {
+  RtQuadRec at = header->rec[k];
+  if (n_tris & FLAT_MOTION_BIT) rt_flat_motion_at(header->rec[k], header->motion + 4u * (size_t)k, (double)tau, &at);
+  const double dd[3] = {d.x, d.y, d.z}, pp[3] = {P.x, P.y, P.z};
+  double n[3];
+  if (n_tris & FLAT_NORMALS_BIT) (void)rt_flat_normal_shade(at, header->normals + 9u * (size_t)k, dd, pp, n);
+  else (void)rt_quad_normal(at, dd, n);
+  FlatShutterSurface s;
+  s.normal = v3(n[0], n[1], n[2]); s.q = v3(at.q[0], at.q[1], at.q[2]);
+  return s;
+}
 // The shading normal of a hit at P on the entry of record *q whose normals are the 72 bytes at rec (rt_flat_normal.h): cold
 // and by value like quads_hit — two pointers, d and P are the sixteen argument registers — so that the cross products, the square root
 // and the divisions stay out of the path loop's register budget.  Per lane: the lanes of a wave hit unrelated entries, the record is an
@@ -1195,6 +1250,15 @@ RT_HD Surface object_surface(const DevScene& sc, const Tables& tb, V3 o, V3 d, d
       s.point = add(o, muls(d, t));                                // ray.rs:18-20: the P the test formed
       const V3 N = v3(q.n[0], q.n[1], q.n[2]);
       s.front_face = dot(d, N) < 0.0;
+      if constexpr (TablesTau<Tables>::kHas) {
+        if (sc.n_tris & (FLAT_MOTION_BIT | FLAT_NORMALS_BIT)) {  // (§25, §27; wave-uniform: everything that uses q as a frame uses q at tau)
+          const FlatShutterSurface ms = flat_surface_shutter(reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, idx - sc.n_spheres, sc.n_tris,
+                                                             (float)tb.tau, d, s.point);
+          s.normal = ms.normal;
+          g.cx = ms.q.x; g.cy = ms.q.y; g.cz = ms.q.z; g.r = 0.0;
+          return s;
+        }
+      }
       s.normal = s.front_face ? N : neg(N);
       if (sc.n_tris & FLAT_NORMALS_BIT)  // (§25; sc is a kernel argument: wave-uniform)
         s.normal = flat_shading_normal(&q, (reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1)->normals + 9u * (size_t)(idx - sc.n_spheres), d, s.point);
@@ -2157,7 +2221,7 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
       const MediumCtx mc{sc.medium, L.ra, L.node};  // (the camera segment: node 0)
       hit_world_grid<true>(sc, tb, L.o, L.d, closest, best, n_exact, n_steps, &mc);
     } else hit_world_grid(sc, tb, L.o, L.d, closest, best, n_exact, n_steps);
-    if constexpr (QUADS) { const HitCB r = flats_hit(sc, L.o, L.d, closest, best); closest = r.closest; best = r.best; }
+    if constexpr (QUADS) { const HitCB r = flats_hit(sc, tb, L.o, L.d, closest, best); closest = r.closest; best = r.best; }
     float a[3];
     if (best < 0) {  // raytracer.rs:133-163: the sky the ray sees
       const Rgb c = sky_color(sc, L.d, tex_oob);
@@ -2358,7 +2422,7 @@ RT_HD SurfRec surface_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, uint
     const MediumCtx mc{sc.medium, RngAddr{pixel, 0u, sc.seed_lo, sc.seed_hi}, 0u};
     hit_world_grid<true>(sc, tb, o, d, closest, best, n_exact, n_steps, &mc);
   } else hit_world_grid(sc, tb, o, d, closest, best, n_exact, n_steps);
-  if constexpr (QUADS) { const HitCB q = flats_hit(sc, o, d, closest, best); closest = q.closest; best = q.best; }
+  if constexpr (QUADS) { const HitCB q = flats_hit(sc, tb, o, d, closest, best); closest = q.closest; best = q.best; }
   SurfRec r;
   r.id = SURFACE_NONE; r.kind = SURFACE_NONE; r.t = 0.0;
   if (best >= 0) { r.id = (uint32_t)best; r.kind = tb.mat((uint32_t)best).kind; r.t = closest; }

@@ -47,6 +47,21 @@ RT_HD bool flat_entry_box(const RtQuadRec& r, double lim, double lo[3], double h
   return pad > 0.0;
 }
 
+// The box of an entry that moves within the frame (rec: its record of rt_flat_motion.h, null: it does not move): the union
+// of flat_entry_box of its record at q and at q (+) m, one addition per component; false when either is outside the preconditions.  An
+// entry at shutter time tau is the record at q + fl(m tau): between the two ends up to one rounding of a coordinate, which the pad of
+// either end covers many orders over.  A still entry's box is flat_entry_box's in every bit.
+RT_HD bool flat_entry_box_swept(const RtQuadRec& r, double lim, const double* rec, double lo[3], double hi[3]) {
+  if (!flat_entry_box(r, lim, lo, hi)) return false;
+  if (!rec || !rt_flat_motion_present(rec)) return true;
+  RtQuadRec end;
+  rt_flat_motion_end(r, rec, &end);
+  double lo1[3], hi1[3];
+  if (!flat_entry_box(end, lim, lo1, hi1)) return false;
+  for (int k = 0; k < 3; ++k) { lo[k] = flat_min(lo[k], lo1[k]); hi[k] = flat_max(hi[k], hi1[k]); }
+  return true;
+}
+
 // What a refit needs of a built structure and what follows from entry counts alone (build_flat_bvh splits at the median BY COUNT): which
 // entries have a box (1) and which sit in the always-visited run (0); the bounded leaves; the inner nodes grouped by height (a leaf has
 // height 0, an inner node one more than the taller of its children, node i + 1 and node nodes[i + 1].skip), the nodes of height h being
@@ -161,7 +176,7 @@ struct Status {              // what prepare() leaves in Job::status
   uint32_t bad_finite;       // the lowest entry with a non-finite component, or NONE
   uint32_t bad_degenerate;   // the lowest degenerate entry, or NONE
   uint32_t mismatch;         // entries whose boxed / refused flag differs from the resident one: the structure must be built anew
-  uint32_t pad;
+  uint32_t pad;              // entries that move within the frame (Job::move makes their records), or 0
 };
 
 struct Job {
@@ -170,6 +185,10 @@ struct Job {
   const double* quv = nullptr;              // [n][9] the new q, u, v
   const double* lim = nullptr;              // [n] or null: a scene of parallelograms
   const uint32_t* boxed = nullptr;          // [n] the resident flags (FlatTopology::boxed); null: a scene without the structure
+  uint32_t quv_stride = 9;                  // doubles from one entry's q to the next's: 9, or 16 for the records of a resident scene
+  const double* move = nullptr;             // the displacement m of every entry over the shutter (§27), move_stride doubles apart (3: a
+  uint32_t move_stride = 3;                 //   caller's; 4: a resident motion table, whose Dm is made anew); null: nothing moves
+  double* motion = nullptr;                 // [n][4] the spare motion table (rt_flat_motion.h); written when move is not null
   // outputs of prepare()
   RtQuadRec* rec = nullptr;                 // [n] the spare records
   double* box = nullptr;                    // [n][6] lo, hi of every boxed entry (scratch); null without the structure

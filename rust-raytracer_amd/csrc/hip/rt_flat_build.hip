@@ -32,22 +32,35 @@ __device__ __forceinline__ void store_node(rtc::FlatNode* dst, const double lo[3
 
 // per entry: its record into the spare records; with the structure, its padded box and whether its flag is still the resident one
 __global__ void __launch_bounds__(BLOCK) flat_prepare(Job j) {
-  __shared__ uint32_t changed;   // of this workgroup: one global atomic per workgroup, not per lane
-  if (threadIdx.x == 0) changed = 0u;
+  __shared__ uint32_t changed, moved;   // of this workgroup: one global atomic per workgroup, not per lane
+  if (threadIdx.x == 0) { changed = 0u; moved = 0u; }
   __syncthreads();
   const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
   if (i < j.n) {
-    const double* p = j.quv + 9 * (size_t)i;
+    const double* p = j.quv + j.quv_stride * (size_t)i;
     const double q[3] = {p[0], p[1], p[2]}, u[3] = {p[3], p[4], p[5]}, v[3] = {p[6], p[7], p[8]};
     RtQuadRec r;
     const int bad = rt_quad_prepare(q, u, v, &r);
-    if (bad == 1) atomicMin(&j.status->bad_finite, i);
+    double mrec[4];
+    int kind = RT_FLAT_MOTION_STILL;
+    if (!bad && j.move) {  // (§27: the entry's motion record beside its record; a refused displacement counts as a non-finite entry)
+      const double* mp = j.move + j.move_stride * (size_t)i;
+      const double m[3] = {mp[0], mp[1], mp[2]};
+      kind = rt_flat_motion_prepare(r, m, mrec);
+    }
+    if (bad == 1 || kind == RT_FLAT_MOTION_BAD) atomicMin(&j.status->bad_finite, i);
     else if (bad) atomicMin(&j.status->bad_degenerate, i);
     else {
       store_rec(j.rec + i, r);
+      if (j.move) {
+        double2* mo = reinterpret_cast<double2*>(j.motion + 4 * (size_t)i);
+        mo[0] = make_double2(mrec[0], mrec[1]);
+        mo[1] = make_double2(mrec[2], mrec[3]);
+        if (kind == RT_FLAT_MOTION_MOVING) atomicAdd(&moved, 1u);
+      }
       if (j.box) {
         double lo[3], hi[3];
-        const bool ok = rtc::flat_entry_box(r, j.lim ? j.lim[i] : 2.0, lo, hi);
+        const bool ok = rtc::flat_entry_box_swept(r, j.lim ? j.lim[i] : 2.0, j.move ? mrec : nullptr, lo, hi);
         double2* b = reinterpret_cast<double2*>(j.box + 6 * (size_t)i);
         b[0] = make_double2(lo[0], lo[1]);
         b[1] = make_double2(lo[2], hi[0]);
@@ -58,6 +71,7 @@ __global__ void __launch_bounds__(BLOCK) flat_prepare(Job j) {
   }
   __syncthreads();
   if (threadIdx.x == 0 && changed) atomicAdd(&j.status->mismatch, changed);
+  if (threadIdx.x == 0 && moved) atomicAdd(&j.status->pad, moved);
 }
 
 // per bounded leaf: the union of the boxes of its up to 4 entries

@@ -191,11 +191,16 @@ struct RtHipScene {
       // call builds into; n_normals: the entries that have normals, 0: no table — the scene is one that never had any
       DevBuf normals, normals_spare;
       uint32_t n_normals = 0;
+      // motion within the frame (rt_hip_scene_set_flat_motion): [n_quads][4] the records of rt_flat_motion.h and the table the
+      // next call or update builds into; n_moving: the entries that move, 0: no table — the scene is one that never had any.  still: the
+      // all -0.0 dv table [n_spheres][4] the MOTION kernels read in a scene whose only movers are flat primitives (§14: a static sphere's bits).
+      DevBuf motion, motion_spare, still;
+      uint32_t n_moving = 0;
       // what a refit needs of the structure as built (rt_flat_build.h FlatTopology), on the device and on the host: topo's vectors are the staging of their uploads
       DevBuf boxed, leaves, levels;
       rtc::FlatTopology topo;
       // the device code's: the geometry as uploaded, a box per entry, the status block; the device build's (§26) items, range extents, sort storage
-      struct Scratch { DevBuf quv, box, status, item, extent, sort_tmp; } scratch;
+      struct Scratch { DevBuf quv, box, status, item, extent, sort_tmp, move, rec_tmp; } scratch;
       // the device build starts from the boxed entries in index order: resident from the first device build after each host build on
       DevBuf start;
       std::vector<uint32_t> keep_start;
@@ -208,7 +213,7 @@ struct RtHipScene {
       rtc::FlatBvhHeader keep_header{};
       uint32_t refits = 0;     // the updates applied by refit since the structure was last built
       // the first record of a generation as the kernels see it (DevScene::quads.rec): behind the header, where there is a structure
-      uint32_t header_recs() const { return (n_nodes || n_normals) ? 1u : 0u; }  // the record slots the header takes (§25: the normals' pointer lives in it)
+      uint32_t header_recs() const { return (n_nodes || n_normals || n_moving) ? 1u : 0u; }  // the record slots the header takes (§25, §27: the normals' and the motion's pointers live in it)
       RtQuadRec* first_rec(const Tables& t) const { return t.rec.get<RtQuadRec>() + header_recs(); }
       size_t rec_bytes() const { return ((size_t)n_quads + header_recs()) * sizeof(RtQuadRec); }  // of Tables::rec
       const double* dev_lim() const { return n_tris ? lim.get<const double>() : nullptr; }
@@ -219,6 +224,7 @@ struct RtHipScene {
         h.rec = first_rec(t); h.lim = dev_lim();
         h.n_nodes = t_n_nodes; h.n_quads = n_quads; h.id_base = id_base;
         h.normals = n_normals ? normals.get<const double>() : nullptr;
+        h.motion = n_moving ? motion.get<const double>() : nullptr;
         return h;
       }
     } flat;
@@ -244,11 +250,13 @@ struct RtHipScene {
       d.geom = t.geom.get<const rtc::SphereGeom>(); d.cell_word = t.cell_word.get<const uint32_t>();
       d.cell_items = t.cell_items.get<const uint16_t>(); d.large = t.large.get<const uint32_t>();
       d.large_geom = t.large_geom.get<const rtc::SphereGeom>();
-      d.motion = t.n_moving ? t.motion.get<const double>() : nullptr;
+      // (§27: flat primitives that move select the MOTION kernels too; without a moving sphere those read the all -0.0 table)
+      d.motion = t.n_moving ? t.motion.get<const double>() : (flat.n_moving ? flat.still.get<const double>() : nullptr);
       d.quads.rec = flat.n_quads ? flat.first_rec(flat.live) : nullptr; d.quads.lim = flat.dev_lim();
       d.n_quads = flat.n_quads;
       d.n_tris = flat.n_tris | (flat.n_nodes ? rtc::FLAT_BVH_BIT : 0u) |  // (§22: the bit says that the header lies in front of quads.rec[0])
-                 (flat.n_normals ? rtc::FLAT_NORMALS_BIT : 0u);             // (§25: ... and that it names a table of shading normals)
+                 (flat.n_normals ? rtc::FLAT_NORMALS_BIT : 0u) |            // (§25: ... and that it names a table of shading normals)
+                 (flat.n_moving ? rtc::FLAT_MOTION_BIT : 0u);               // (§27: ... and a table of motion records)
       d.mat = mat.get<const rtc::SphereMat>(); d.matc = matc.get<const rtc::MatCore>();
       d.lights = lights.get<const uint32_t>(); d.medium = n_media ? medium.get<const double>() : nullptr;
       d.tex = tex.get<const uint8_t>(); d.sky = sky.get<const uint8_t>();
@@ -1258,6 +1266,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "lds_tables")) return (int64_t)s->last_lds_tables;
   if (!std::strcmp(key, "triangles")) return (int64_t)s->res->flat.n_tris;      // of "quads", the entries of shape triangle
   if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->flat.n_nodes;  // nodes of the structure over the flat primitives; 0: none
+  if (!std::strcmp(key, "flat_motion")) return (int64_t)s->res->flat.n_moving;  // entries that move within the frame; 0: none
   if (!std::strcmp(key, "flat_normals")) return (int64_t)s->res->flat.n_normals;  // entries that carry shading normals; 0: none
   if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat.refits;  // updates applied by refit since the structure was last built
   if (!std::strcmp(key, "flat_build")) return (int64_t)s->opt.flat_build;  // the option: 1: a rebuild the caller asks for runs on the device
@@ -1969,20 +1978,26 @@ extern "C" int rt_hip_scene_update_spheres(RtHipScene* s, const double* center, 
 // ------------------------------------------------------------------------------ moving the flat primitives of a resident scene
 namespace {
 // views_follow: the caller (the group) re-points the views that share this scene's tables itself
-int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags, bool views_follow) {
-  if (!s || !quv) return fail(RT_ERR_INVALID, "null argument");
-  if (flags & ~(RT_UPDATE_FLATS_REBUILD | RT_UPDATE_FLATS_DEVICE)) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: unknown flag");
+// set_move (rt_hip_scene_set_flat_motion): the same update with the geometry the scene has — quv is null, the live records
+// are the input — and `move`, [n_quads][3] in host or (RT_UPDATE_FLATS_DEVICE) device memory, null: all zeros, as the displacements.
+// Without set_move the motion stays as set: its records are made anew beside the new geometry's (Dm follows the new normal).
+int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags, bool views_follow, const double* move = nullptr,
+                       bool set_move = false) {
+  const std::string who = set_move ? "rt_hip_scene_set_flat_motion" : "rt_hip_scene_update_flats";
+  if (!s || (!quv && !set_move)) return fail(RT_ERR_INVALID, "null argument");
+  if (flags & ~((set_move ? 0u : RT_UPDATE_FLATS_REBUILD) | RT_UPDATE_FLATS_DEVICE)) return fail(RT_ERR_INVALID, who + ": unknown flag");
   RtHipScene::Resident::Flats& f = s->res->flat;
-  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene has no flat primitive");
+  if (!f.n_quads) return fail(RT_ERR_INVALID, who + ": the scene has no flat primitive");
   if (n_quads != f.n_quads)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
+    return fail(RT_ERR_INVALID, who + ": n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
   if (!views_follow && s->res.use_count() > 1)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_update_flats: the scene's tables are shared with a view (a group updates through rt_hip_group_update_flats)");
-  const bool on_device = (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
+    return fail(RT_ERR_INVALID, who + ": the scene's tables are shared with a view (a group updates through " + (set_move ? "rt_hip_group_set_flat_motion)" : "rt_hip_group_update_flats)"));
+  const bool on_device = (set_move ? move != nullptr : true) && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
   if (on_device)
-    if (const int refused = check_aligned(quv, 8, "rt_hip_scene_update_flats: quv must be 8-byte aligned")) return refused;
+    if (const int refused = check_aligned(set_move ? move : quv, 8, set_move ? "rt_hip_scene_set_flat_motion: move must be 8-byte aligned" : "rt_hip_scene_update_flats: quv must be 8-byte aligned")) return refused;
   int rc;
   if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  if (set_move && !move && !f.n_moving) return RT_OK;   // nothing moves and nothing shall: the scene is what it was
   rtp::Clock pc = rtp::begin();
   const uint32_t n = n_quads;
   const bool bvh = f.n_nodes != 0u;
@@ -1990,10 +2005,25 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
   const bool device_build = rebuild && s->opt.flat_build == 1;   // (§26: the order table on the device; a changed refused set still goes to the host)
   RtHipScene::Resident::Flats::Tables& spare = f.spare;
   RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
-  if ((rc = room(spare.rec, f.rec_bytes())) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
-      (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK) ||
+  // (§27) with_move: this update makes a motion table; slot: the record slots the header takes in the spare generation — one for sure while
+  // a motion table may come out of it (a scan scene that ends up without one is compacted after the readback)
+  const bool with_move = set_move || f.n_moving != 0u;
+  const uint32_t slot = (f.n_nodes || f.n_normals || with_move) ? 1u : 0u;
+  uint32_t moving = set_move ? 0u : f.n_moving;   // the entries that move once this update is in: known after the readback
+  if ((rc = room(spare.rec, ((size_t)n + slot) * sizeof(RtQuadRec))) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
+      (!set_move && !on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK) ||
+      (with_move && (rc = room(f.motion_spare, (size_t)n * 32)) != RT_OK) ||
+      (set_move && !on_device && (rc = room(fb.move, (size_t)n * 24)) != RT_OK) ||
       (bvh && ((rc = room(fb.box, (size_t)n * 48)) != RT_OK || (rc = room(spare.nodes, (size_t)f.n_nodes * sizeof(rtc::FlatNode))) != RT_OK)))
     return rc;
+  if (with_move) {  // the MOTION kernels' dv table while no sphere moves, now or after a later rt_hip_scene_update_spheres: every word -0.0
+    const size_t words = 4 * (size_t)(s->host.n_spheres ? s->host.n_spheres : 1u);
+    if (f.still.cap < words * 8) {
+      if ((rc = room(f.still, words * 8)) != RT_OK) return rc;
+      const std::vector<double> still(words, -0.0);
+      RT_HIP_TRY(hipMemcpy(f.still.p, still.data(), words * 8, hipMemcpyHostToDevice));
+    }
+  }
   rtfb::BuildJob bj;
   if (device_build) {  // the boxed entries in index order, uploaded once per host build; scratch and the spare order table, allocated once
     if (!f.start_ready) {
@@ -2008,13 +2038,21 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
         (rc = room(fb.extent, rtfb::build_extent_bytes(bj.m))) != RT_OK || (rc = room(fb.sort_tmp, bj.sort_bytes)) != RT_OK)
       return rc;
   }
-  if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
+  if (!set_move && !on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
+  if (set_move && !on_device) {
+    if (move) RT_HIP_TRY(hipMemcpy(fb.move.p, move, (size_t)n * 24, hipMemcpyHostToDevice));
+    else RT_HIP_TRY(hipMemset(fb.move.p, 0, (size_t)n * 24));
+  }
   pc.mark("update_flats.upload");
   rtfb::Job j;
   j.n = n;
-  j.quv = on_device ? quv : fb.quv.get<const double>();
+  if (set_move) { j.quv = reinterpret_cast<const double*>(f.first_rec(f.live)); j.quv_stride = 16u; }  // (a record begins with its q, u, v)
+  else j.quv = on_device ? quv : fb.quv.get<const double>();
+  if (set_move) { j.move = on_device ? move : fb.move.get<const double>(); j.move_stride = 3u; }
+  else if (with_move) { j.move = f.motion.get<const double>(); j.move_stride = 4u; }
+  if (with_move) j.motion = f.motion_spare.get<double>();
   j.lim = f.dev_lim();
-  j.rec = f.first_rec(spare);
+  j.rec = spare.rec.get<RtQuadRec>() + slot;
   j.status = fb.status.get<rtfb::Status>();
   if (bvh) {
     const rtc::FlatTopology& tp = f.topo;
@@ -2028,6 +2066,8 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
   // the spare's header: its own records and nodes, and the order table that goes live with them
   auto put_header = [&](uint32_t n_nodes, const DevBuf& order) {
     f.keep_header = f.header(spare, n_nodes, order, s->host.n_spheres);
+    f.keep_header.rec = spare.rec.get<RtQuadRec>() + slot;
+    f.keep_header.motion = moving ? f.motion_spare.get<const double>() : nullptr;   // (the table that goes live with these records)
     return hipMemcpy(spare.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice);
   };
   RT_HIP_TRY(rtfb::prepare(j, nullptr));
@@ -2041,30 +2081,40 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
     RT_HIP_TRY(put_header(f.n_nodes, spare.order));
   } else if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
     RT_HIP_TRY(rtfb::refit(j, nullptr));
-    RT_HIP_TRY(put_header(f.n_nodes, f.live.order));
-  } else if (!bvh && f.header_recs()) RT_HIP_TRY(put_header(0u, f.live.order));  // (§25: a scan with shading normals keeps their header)
+    if (!set_move) RT_HIP_TRY(put_header(f.n_nodes, f.live.order));
+  } else if (!bvh && slot && !set_move) RT_HIP_TRY(put_header(0u, f.live.order));  // (§25, §27: a scan with shading normals or motion keeps their header)
   rtfb::Status st;
   RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the first bad entry of each class, changed flags
   pc.mark("update_flats.kernels_and_readback");
   if (st.bad_finite != rtfb::NONE || st.bad_degenerate != rtfb::NONE) {  // (creation's loop stops at the first bad entry: the lowest index wins)
-    if (st.bad_finite < st.bad_degenerate) return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + ": q, u and v must be finite");
+    if (st.bad_finite < st.bad_degenerate)
+      return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + (with_move ? ": q, u, v, the displacement and q + displacement must be finite" : ": q, u and v must be finite"));
     return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)");
   }
-  if (bvh && st.mismatch) rebuild = true;  // an entry became a needle, crossed 2^40, or stopped being one: the order table is another
+  if (with_move) moving = st.pad;
+  if (bvh && st.mismatch) rebuild = true;  // an entry became a needle, crossed 2^40 (§27: at either end of its motion), or stopped being one: the order table is another
+  // (§27: the header of a new motion table names it only now that the count is known)
+  if (set_move && slot && !rebuild) RT_HIP_TRY(put_header(bvh ? f.n_nodes : 0u, f.live.order));
   const bool built = device_build && !st.mismatch;  // the device's order table stands; with a mismatch the counts are others: the host builds
   uint32_t n_nodes = f.n_nodes;
   if (rebuild && !built) {  // the host's build_flat_bvh over the host's records, as creation runs it; the records themselves stay the device's
     const double* host_quv = quv;
-    if (on_device) {
+    if (on_device && !set_move) {  // (set_move: quv is null, the records come from the device below)
       f.keep_quv.resize(9 * (size_t)n);
       RT_HIP_TRY(hipMemcpy(f.keep_quv.data(), quv, (size_t)n * 72, hipMemcpyDeviceToHost));
       host_quv = f.keep_quv.data();
     }
     rtc::HostTables t;
     t.quads.resize(n);
-    for (uint32_t k = 0; k < n; ++k)
-      if (rt_quad_prepare(host_quv + 9 * (size_t)k, host_quv + 9 * (size_t)k + 3, host_quv + 9 * (size_t)k + 6, &t.quads[k]))
-        return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": the host refuses an entry the device accepted");
+    if (set_move) RT_HIP_TRY(hipMemcpy(t.quads.data(), j.rec, (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToHost));  // (the records as they are)
+    else
+      for (uint32_t k = 0; k < n; ++k)
+        if (rt_quad_prepare(host_quv + 9 * (size_t)k, host_quv + 9 * (size_t)k + 3, host_quv + 9 * (size_t)k + 6, &t.quads[k]))
+          return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": the host refuses an entry the device accepted");
+    if (moving) {  // (§27: the builder sweeps the boxes with the records the device just made)
+      t.flat_motion.resize(4 * (size_t)n);
+      RT_HIP_TRY(hipMemcpy(t.flat_motion.data(), f.motion_spare.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    }
     t.quad_lim = f.host_lim;
     const std::string why = rtc::build_flat_bvh(t);
     if (!why.empty()) return fail(RT_ERR_INVALID, why);
@@ -2076,9 +2126,16 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
     RT_HIP_TRY(put_header(n_nodes, spare.order));
     pc.mark("update_flats.upload_structure");
   }
+  if (slot && !(f.n_nodes || f.n_normals || moving)) {  // (§27: a scan scene that lost its last table loses the header's slot: the records alone)
+    if ((rc = room(fb.rec_tmp, (size_t)n * sizeof(RtQuadRec))) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(fb.rec_tmp.p, j.rec, (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
+    spare.rec.swap(fb.rec_tmp);
+  }
   RT_HIP_TRY(hipDeviceSynchronize());
   // everything is built: swap it in (nothing above changed what the scene renders with)
   f.live.rec.swap(spare.rec);
+  if (with_move) f.motion.swap(f.motion_spare);
+  f.n_moving = moving;
   if (bvh) f.live.nodes.swap(spare.nodes);
   if (rebuild) { f.live.order.swap(spare.order); f.n_nodes = n_nodes; }
   f.refits = (bvh && !rebuild) ? f.refits + 1u : 0u;
@@ -2091,6 +2148,10 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
 
 extern "C" int rt_hip_scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags) {
   return scene_update_flats(s, quv, n_quads, flags, false);
+}
+// flat primitives that move within the frame: an update of the geometry the scene has, with other displacements
+extern "C" int rt_hip_scene_set_flat_motion(RtHipScene* s, const double* move, uint32_t n_quads, uint32_t flags) {
+  return scene_update_flats(s, nullptr, n_quads, flags, false, move, true);
 }
 
 // ------------------------------------------------------------------------------ shading normals on the triangles of a resident scene
@@ -2135,7 +2196,7 @@ int scene_set_flat_normals(RtHipScene* s, const double* normals, uint32_t n_quad
     count = st.mismatch;
   }
   // the record slots the header takes before and after: they differ only in a scan scene that gains or loses its table
-  const uint32_t had = f.header_recs(), has = (f.n_nodes || count) ? 1u : 0u;
+  const uint32_t had = f.header_recs(), has = (f.n_nodes || count || f.n_moving) ? 1u : 0u;
   RtHipScene::Resident::Flats::Tables& spare = f.spare;
   if (has != had) {
     if ((rc = room(spare.rec, ((size_t)n + has) * sizeof(RtQuadRec))) != RT_OK) return rc;
@@ -2178,6 +2239,7 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "quads")) { src = f.first_rec(f.live); bytes = (size_t)f.n_quads * sizeof(RtQuadRec); }
   else if (!std::strcmp(name, "quad_lim")) { src = f.lim.p; bytes = f.n_tris ? (size_t)f.n_quads * sizeof(double) : 0; }
   else if (!std::strcmp(name, "flat_bvh")) { src = f.live.nodes.p; bytes = (size_t)f.n_nodes * sizeof(rtc::FlatNode); }
+  else if (!std::strcmp(name, "flat_motion")) { src = f.motion.p; bytes = f.n_moving ? (size_t)f.n_quads * 32u : 0; }
   else if (!std::strcmp(name, "flat_normals")) { src = f.normals.p; bytes = f.n_normals ? (size_t)f.n_quads * 72u : 0; }
   else if (!std::strcmp(name, "flat_bvh_order")) { src = f.live.order.p; bytes = f.n_nodes ? (size_t)f.n_quads * sizeof(uint32_t) : 0; }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);

@@ -610,6 +610,22 @@ extern "C" int rt_hip_group_set_flat_normals(RtHipGroup* g, const double* normal
   return RT_OK;
 }
 
+// motion of the flat primitives within the frame on every rank's scene (rt_hip_scene_set_flat_motion), under the same two conditions
+extern "C" int rt_hip_group_set_flat_motion(RtHipGroup* g, const double* move, uint32_t n_quads, uint32_t flags) {
+  if (!g) return fail(RT_ERR_INVALID, "null argument");
+  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_motion: a submitted frame is uncollected");
+  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
+    for (uint32_t r = 1; r < g->G; ++r)
+      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_motion: device memory serves the ranks of one device only");
+  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: a bad displacement changes no rank)
+    int rc = scene_update_flats(g->scene[r], nullptr, n_quads, flags, true, move, true);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
+    if (rc != RT_OK) return rc;
+  }
+  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
+  return RT_OK;
+}
+
 namespace rtg { void prepare_staging(RtHipGroup* g, int n_frames); }
 extern "C" int rt_hip_group_set_option(RtHipGroup* g, const char* key, int64_t value) {
   if (!g || !key) return fail(RT_ERR_INVALID, "null argument");

@@ -953,7 +953,13 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
       }
     }
     if constexpr (QUADS) {  // (4) the quads, behind every sphere: quad k is object n_spheres + k
-      if (has_ray) { const HitCB r = flats_hit(sc, L.o, L.d, closest, best); closest = r.closest; best = r.best; }
+      if (has_ray) {
+        HitCB r;
+        // (§27: the MOTION kernels' one cold call takes the scan, the structure or, where flat primitives move within the frame, the walk at the lane's tau)
+        if constexpr (MOTION) r = flats_hit_shutter(L.o, L.d, sc.quads, sc.n_quads, sc.n_spheres, sc.n_tris, tau, closest, best);
+        else r = flats_hit(sc, L.o, L.d, closest, best);
+        closest = r.closest; best = r.best;
+      }
     }
   };
 
@@ -1588,7 +1594,7 @@ template <class Tables>
 __device__ void medium_probe_ray(const DevScene& sc, const Tables& tb, V3 o, V3 d, const MediumCtx& mc, double& closest, int& best, uint32_t& n_exact,
                                  uint32_t& n_steps) {
   hit_world_grid<true>(sc, tb, o, d, closest, best, n_exact, n_steps, &mc);
-  if (sc.n_quads) { const HitCB r = flats_hit(sc, o, d, closest, best); closest = r.closest; best = r.best; }
+  if (sc.n_quads) { const HitCB r = flats_hit(sc, tb, o, d, closest, best); closest = r.closest; best = r.best; }
 }
 __global__ void rt_medium_probe(const DevScene sc, const double* rays, const float* tau, const uint32_t* node, double* out_t, int32_t* out_best,
                                 uint32_t* out_work, uint32_t n) {

@@ -76,6 +76,9 @@ struct HostTables {
   // ... and, for the CPU builds of the lane code, the records again behind a FlatBvhHeader (rt_core.h): what DevScene::quads.rec points
   // into when the structure is bound (bind_host_tables fills the header; the device's copy is laid out the same way)
   std::vector<RtQuadRec> flat_blob;
+  // flat primitives that move within the frame: [n_quads][4] the records of rt_flat_motion.h, which build_flat_bvh sweeps
+  // the boxes with; EMPTY when none moves: every table is then what it was
+  std::vector<double> flat_motion;
 };
 
 // The box a sphere's centre can occupy over the shutter, axis k (rt_grid_build.h grid_sphere_box: the static box, or the swept one).
@@ -575,7 +578,7 @@ inline std::string build_flat_bvh(HostTables& t) {
   std::vector<uint32_t> always, idx;
   for (uint32_t k = 0; k < n; ++k) {
     Box& b = box[k];
-    if (flat_entry_box(t.quads[k], t.quad_lim.empty() ? 2.0 : t.quad_lim[k], b.lo, b.hi)) {
+    if (flat_entry_box_swept(t.quads[k], t.quad_lim.empty() ? 2.0 : t.quad_lim[k], t.flat_motion.empty() ? nullptr : &t.flat_motion[4 * (size_t)k], b.lo, b.hi)) {
       for (int a = 0; a < 3; ++a) b.c[a] = flat_centre(b.lo[a], b.hi[a]);
       idx.push_back(k);
     } else always.push_back(k);
@@ -726,6 +729,7 @@ inline void bind_host_tables(const HostTables& t, DevScene& d) {
     std::memset(&h, 0, sizeof h);
     h.nodes = t.flat_nodes.data(); h.order = t.flat_order.data(); h.rec = t.flat_blob.data() + 1; h.lim = d.quads.lim;
     h.n_nodes = (uint32_t)t.flat_nodes.size(); h.n_quads = d.n_quads; h.id_base = d.n_spheres;
+    if (!t.flat_motion.empty()) { h.motion = t.flat_motion.data(); d.n_tris |= FLAT_MOTION_BIT; }  // (§27)
     std::memcpy(const_cast<RtQuadRec*>(t.flat_blob.data()), &h, sizeof h);
     d.quads.rec = t.flat_blob.data() + 1;
     d.n_tris |= FLAT_BVH_BIT;

@@ -204,6 +204,11 @@ struct RtSceneFile {
   // for an entry without; n_normals: the entries that have them (0: rt_scene_flat_normals is NULL)
   std::vector<double> normals;
   size_t n_normals = 0;
+  // motion within the frame: [quads.size()][3] the "move" of every entry as written, three +0.0 for an entry without;
+  // has_move: the entries whose object had the key (what rt_scene_to_json writes it for); n_move: their count (0: rt_scene_flat_motion is NULL)
+  std::vector<double> move;
+  std::vector<uint8_t> has_move;
+  size_t n_move = 0;
   // the structure over the flat primitives: the file's top-level "flat_bvh": true (rt_scene_flat_bvh; written back only when true)
   bool flat_bvh = false;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
@@ -619,6 +624,24 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         geo.push_back(fl); label.push_back(fl.shape == RT_QUAD_SHAPE_TRIANGLE ? "triangle" : "quad");
         mat_v = f[3];
       }
+      // motion within the frame: an optional "move" beside any of the four forms; a box or a mesh gives it to every face
+      const Value* move_v = nullptr;
+      if (o.kind == Value::Object)
+        for (auto& mb : o.members)
+          if (mb.first == "move") {
+            if (move_v) bad("duplicate field `move`");
+            move_v = mb.second.get();
+          }
+      double move[3] = {0.0, 0.0, 0.0};
+      if (move_v) {
+        try {
+          as_point(*move_v, "move", move);
+        } catch (const SchemaError& e) {
+          bad("move: " + e.msg);
+        }
+        for (int k = 0; k < 3; ++k)
+          if (!rt_quad_finite(move[k])) bad("move: a displacement must be finite");
+      }
       const Value& m = *mat_v;
       if (m.kind == Value::Object && m.members.size() == 1)
         for (const char* k : {"Texture", "Light", "Medium"})
@@ -647,6 +670,12 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         sf.is_quad.push_back(1);
         for (int k = 0; k < 9; ++k) sf.normals.push_back(geo[i].smooth ? geo[i].nrm[k] : 0.0);
         if (geo[i].smooth) sf.n_normals++;
+        for (int k = 0; k < 3; ++k) {
+          if (move_v && !rt_quad_finite(q.q[k] + move[k])) bad(label[i] + ": move: q + move must be finite");
+          sf.move.push_back(move[k]);
+        }
+        sf.has_move.push_back(move_v ? 1 : 0);
+        if (move_v) sf.n_move++;
       }
     } catch (const SchemaError& e) {
       bad(e.msg.rfind(which, 0) == 0 ? e.msg : which + ": " + e.msg);
@@ -778,6 +807,7 @@ std::string scene_json(const RtSceneFile& sf) {
       bool smooth = false;
       for (int k = 0; k < 9; ++k) smooth = smooth || nr[k] != 0.0;
       if (smooth) o += ",\"normals\":[" + point(nr) + "," + point(nr + 3) + "," + point(nr + 6) + "]";
+      if (sf.has_move[iq - 1]) o += ",\"move\":" + point(&sf.move[3 * (iq - 1)]);  // (§27: only where the file had the key)
       o += ",\"material\":{";
     } else {
       o += "{\"center\":" + point(s.center);
@@ -882,6 +912,11 @@ extern "C" const RtQuad* rt_scene_quads(const RtSceneFile* sf, uint32_t* n) {
   const bool any = sf && !sf->quads.empty();
   if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
   return any ? sf->quads.data() : nullptr;
+}
+extern "C" const double* rt_scene_flat_motion(const RtSceneFile* sf, uint32_t* n) {
+  const bool any = sf && sf->n_move != 0;
+  if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
+  return any ? sf->move.data() : nullptr;
 }
 extern "C" const double* rt_scene_flat_normals(const RtSceneFile* sf, uint32_t* n) {
   const bool any = sf && sf->n_normals != 0;

@@ -48,6 +48,8 @@ def lib():
         L.rt_scene_quads.restype = C.POINTER(abi.RtQuad)
         L.rt_scene_flat_normals.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.rt_scene_flat_normals.restype = C.POINTER(C.c_double)
+        L.rt_scene_flat_motion.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.rt_scene_flat_motion.restype = C.POINTER(C.c_double)
         L.rt_scene_flat_bvh.argtypes = [C.c_void_p]
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
@@ -129,6 +131,16 @@ class Scene:
         if not p or not n.value:
             return None
         return np.ctypeslib.as_array(p, shape=(n.value, 9)).copy()
+
+    def flat_motion(self):
+        """motion within the frame: an [n_quads, 3] float64 numpy array (a copy) — the "move" of every entry of quads() as
+        the file wrote it, three zeros for an entry without — or None for a file without the key (rt_scene_flat_motion)"""
+        import numpy as np
+        n = C.c_uint32(0)
+        p = lib().rt_scene_flat_motion(self._h, C.byref(n))
+        if not p or not n.value:
+            return None
+        return np.ctypeslib.as_array(p, shape=(n.value, 3)).copy()
 
     def flat_bvh(self):
         """the structure over the flat primitives: True for a file with "flat_bvh": true (rt_scene_flat_bvh)"""
