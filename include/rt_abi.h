@@ -91,7 +91,8 @@ typedef struct RtSphere {
 /* A quad (an extension of the schema; the reference has no such object and its loader rejects the file): the flat
  * parallelogram q + a u + b v, 0 <= a, b <= 1, two-sided.  The material fields mean what they mean in RtSphere; a quad may be
  * Lambertian, Metal, Glass, Checker or Noise (the solid's pattern in the quad's frame: centre = q).  Texture, Light and Medium quads
- * are RT_ERR_INVALID: a quad has no (u, v) map, the light loop aims at sphere centres, a medium needs a volume.  Quads do not move within a frame (no center1) unless rt_hip_scene_set_flat_motion gives them a displacement over the shutter; rt_hip_scene_update_flats moves them between frames.
+ * are RT_ERR_INVALID: a quad has no (u, v) map, a medium needs a volume, and a quad cannot be a Light MATERIAL (emission:
+ * rt_hip_scene_set_flat_lights).  Quads do not move within a frame (no center1) unless rt_hip_scene_set_flat_motion gives them a displacement over the shutter; rt_hip_scene_update_flats moves them between frames.
  * Triangles: `reserved` carries the SHAPE of the flat primitive, RT_QUAD_SHAPE_PARALLELOGRAM (0, the quad above) or
  * RT_QUAD_SHAPE_TRIANGLE (1): the points q + a u + b v with 0 <= a, 0 <= b, a + b <= 1, two-sided.  Everything else about the entry —
  * its place in the order, its id, its materials, the refusals — is a quad's.  A value above 1 is RT_ERR_INVALID (`quad k: bad shape`). */
@@ -282,6 +283,13 @@ const double* rt_scene_flat_normals(const RtSceneFile*, uint32_t* n);
  * when no object has the key.  Owned by the RtSceneFile.  A duplicate key or a non-finite value is a load error naming objects[i];
  * rt_scene_to_json writes the key only where the file had it: load -> write -> load is bit for bit. */
 const double* rt_scene_flat_motion(const RtSceneFile*, uint32_t* n);
+/* Area lights (an extension too): an optional "emit": [r, g, b] (or {"x", "y", "z"}) on the object map of a quad, a
+ * "triangle", a "box" or a "mesh" — a box or a mesh gives it to every face.  *n x 3 f32, the emission of every entry of rt_scene_quads as
+ * written, three zeros for an entry without — what rt_hip_scene_set_flat_lights takes.  NULL and 0 when no object has the key.  Owned by
+ * the RtSceneFile.  A duplicate key, a component that is not finite or outside [0, 1], "emit" on a sphere, or "emit" together with a
+ * non-zero "move" is a load error naming objects[i]; rt_scene_to_json writes the key only where the file had it: load -> write -> load is
+ * bit for bit. */
+const float* rt_scene_flat_emit(const RtSceneFile*, uint32_t* n);
 /* The structure over the flat primitives (an extension too): a top-level "flat_bvh": true beside "camera" and "objects"
  * asks for rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh and lifts the loader's cap from RT_MAX_QUADS to RT_MAX_FLATS_BVH
  * (the entry that crosses it is still named by its objects[i]).  1 for such a file, 0 when the key is false or absent: today's behaviour.
@@ -542,6 +550,29 @@ int rt_hip_scene_set_flat_normals(RtHipScene*, const double* normals, uint32_t n
  * finite ("quad k: ..."; of all bad entries the lowest k is reported); a scene whose tables a live view shares
  * (rt_hip_group_set_flat_motion).  After any error the scene renders exactly as before. */
 int rt_hip_scene_set_flat_motion(RtHipScene*, const double* move, uint32_t n_quads, uint32_t flags);
+/* Area lights: the flat primitives of a resident scene that EMIT.  emit: n_quads x 3 f32 in entry order, host memory.  An
+ * entry of three zeros does not emit; any other entry is an emitter: it scatters as the reference's Light does (no scattered ray,
+ * materials.rs:65-69), its colour is `emit` instead of (1, 1, 1), from both faces; its own material is ignored while it emits and is what
+ * the entry is again when emission is removed.  Every component is finite and in [0, 1].  The light list is the Light spheres in object
+ * order (rt_find_lights), then the emitters in entry order; n_lights, in the trigger thresholds and the division of raytracer.rs:100,
+ * 111-113, is the total.  A Light sphere is aimed at as before, at its centre; an emitter is SAMPLED: each light ray aims at a fresh point
+ * of it — one Philox draw at slot 0xFFFFFFFF of the light ray's node, T = (Q + u a) + v b, a triangle folding a + b > 1 back
+ * (csrc/common/rt_flat_light.h holds the contract step by step) — so a flat lamp casts a penumbra.  Q, u, v are read from the entry's
+ * resident record when aiming: after rt_hip_scene_update_flats the lamp is aimed at where it now is.  A later call replaces the whole
+ * table; NULL, or all zeros, removes emission: the scene is then, table for table and bit for bit, one that never had any.  A scene can
+ * gain or lose its lit kernels with the call (rt_hip_scene_query "last_kernel"); rt_hip_scene_update_spheres, rt_hip_scene_update_flats,
+ * rt_hip_scene_set_flat_normals and the BVH builds keep emission as set.
+ * flags: 0, or RT_UPDATE_FLATS_DEVICE (emit is device memory on the scene's device, 4-byte aligned; it is copied back and checked on the host).
+ * Blocking; waits for the scene's unfinished launch and drops what rt_hip_scene_update_flats drops.
+ * rt_hip_scene_query "flat_lights" = the emitters, "n_lights" = the total; rt_hip_scene_table "flat_lights" = the emitters' entry indices
+ * (u32) in light order, empty without.  RT_ERR_UNSUPPORTED: more than RT_MAX_FLAT_LIGHTS emitters (every sampling hit shoots one ray per
+ * light; a lamp is a few faces, not a mesh).  RT_ERR_INVALID: a null scene; another flag; n_quads different from the scene's; a scene
+ * without flat primitives; a component of emit that is not finite or lies outside [0, 1] ("quad k: ...", the lowest k); an emitter whose
+ * displacement (rt_hip_scene_set_flat_motion) is not zero — a Light sphere cannot move either, and rt_hip_scene_set_flat_motion refuses
+ * to move an emitter likewise; a scene whose tables a live view shares (rt_hip_group_set_flat_lights).  After any error the scene renders
+ * exactly as before. */
+#define RT_MAX_FLAT_LIGHTS 32u
+int rt_hip_scene_set_flat_lights(RtHipScene*, const float* emit, uint32_t n_quads, uint32_t flags);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
  * camera of a resident scene — the four vectors of camera.rs:52-63 — without touching its tables,
  * and render whole frames of it into a host buffer (internal device framebuffer, blocking). */
@@ -869,6 +900,8 @@ int rt_hip_group_update_flats(RtHipGroup*, const double* quv, uint32_t n_quads, 
 int rt_hip_group_set_flat_normals(RtHipGroup*, const double* normals, uint32_t n_quads, uint32_t flags);
 /* rt_hip_scene_set_flat_motion on every rank, under the same two conditions. */
 int rt_hip_group_set_flat_motion(RtHipGroup*, const double* move, uint32_t n_quads, uint32_t flags);
+/* rt_hip_scene_set_flat_lights on every rank, under the same two conditions. */
+int rt_hip_group_set_flat_lights(RtHipGroup*, const float* emit, uint32_t n_quads, uint32_t flags);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
  * tile height; *tile_rows_out receives that height (2) */

@@ -26,6 +26,7 @@ class RtQuad(C.Structure):
 
 
 RT_MAX_QUADS = 1024
+RT_MAX_FLAT_LIGHTS = 32
 RT_MAX_FLATS_BVH = 1 << 20   # with the structure of DESIGN.md §22 (rt_hip_scene_create_flats_bvh)
 RT_QUAD_SHAPE_PARALLELOGRAM, RT_QUAD_SHAPE_TRIANGLE = 0, 1   # RtQuad.reserved: the shape of a flat primitive
 RT_UPDATE_FLATS_REBUILD, RT_UPDATE_FLATS_DEVICE = 1, 2       # flags of rt_hip_scene_update_flats

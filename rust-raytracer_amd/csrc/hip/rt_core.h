@@ -34,6 +34,7 @@
 #include "../common/rt_solid.h"  // the one checker and lattice noise of the solid textures
 #include "../common/rt_quad.h"   // the one quad test
 #include "../common/rt_flat_normal.h"  // the one shading normal of a triangle
+#include "../common/rt_flat_light.h"   // the aim at an emitting flat primitive
 #include "../common/rt_flat_motion.h"  // the one flat primitive at a shutter time
 
 #if defined(__HIPCC__)
@@ -186,6 +187,10 @@ constexpr uint32_t FLAT_BVH_BIT = 0x80000000u;
 // (rt_flat_motion.h), one per entry in ENTRY order.  Only the MOTION instantiations look for the bit.
 constexpr uint32_t FLAT_NORMALS_BIT = 0x40000000u;
 constexpr uint32_t FLAT_MOTION_BIT = 0x20000000u;
+// Emission: a scene whose n_tris carries FLAT_LIGHTS_BIT has emitting flat primitives: DevScene::lights names them behind the
+// Light spheres as object ids n_spheres + k, and their `mat` / `matc` records are of kind Light with the colour `emit`.  No header slot: the aim
+// reads the entry's own record.  Only the lit QUADS instantiations look for the bit.
+constexpr uint32_t FLAT_LIGHTS_BIT = 0x10000000u;
 struct alignas(16) FlatBvhHeader {
   const FlatNode* nodes;
   const uint32_t* order;
@@ -401,6 +406,8 @@ RT_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint3
 //                              call leaves over, so a lit kernel decides `draw > threshold` without a second Philox stream —
 //                              the low word (slot 0) matters only when the high word alone leaves the comparison open (2^-32)
 //   node NODE_CAMERA, slot 1+a: attempt a of the thin lens's point in the unit disc (lens_disc): (.x, .y), then (.z, .w)
+//   node c, slot 0xFFFFFFFF  : c = child_node(n, j) of a light ray aimed at an emitting flat primitive: .x.y and .z.w the two coordinates of
+//                              its point on the entry (rt_flat_light.h); otherwise only the 2^32-th attempt of the slots above
 //   node NODE_TIME, slot 0   : .x = the sample's shutter time tau = (.x >> 8) * 2^-24 (motion blur, sample_time)
 // (NODE_CAMERA and NODE_TIME are odd: never a child_node value, which are even)
 constexpr uint32_t NODE_CAMERA = 0xFFFFFFFFu;
@@ -1988,23 +1995,50 @@ RT_HD bool lane_continue_main(const DevScene& sc, LaneT& L, V3 point, V3 out_dir
   return false;
 }
 
+// The point of an emitting flat primitive that the light ray of RNG node `node` aims at (rt_flat_light.h): ONE Philox draw at
+// the node's slot RT_FLAT_LIGHT_SLOT and six f64 operations per component triple, on the entry's RESIDENT record — the lamp is where
+// rt_hip_scene_update_flats last put it.  Cold and by value like quads_hit: the draw and the nine doubles stay out of the path loop's
+// register budget.  Per lane: the lanes of a wave aim at unrelated lights; the record is an ordinary vector load (72 of its 128 bytes).
+RT_HD_COLD V3 flat_light_point(const RtQuadRec* q, const double* lim, RngAddr ra, uint32_t node) {
+  const U4 w = rng(ra, node, RT_FLAT_LIGHT_SLOT);
+  const uint32_t words[4] = {w.x, w.y, w.z, w.w};
+  double T[3];
+  rt_flat_light_aim(q->q, q->u, q->v, lim != nullptr && *lim == 1.0, words, T);
+  return v3(T[0], T[1], T[2]);
+}
 // aim the current ray at light j of frame `top` (raytracer.rs:104-106)
-template <class Tables, class LaneT>
+// QUADS: in a scene with emitting flat primitives (FLAT_LIGHTS_BIT; sc is a kernel argument: wave-uniform) the light list
+// names them behind the Light spheres as object ids n_spheres + k, and such a light is aimed at through flat_light_point.  A compile-time
+// arm: without it the function is the code it was.
+template <bool QUADS = false, class Tables, class LaneT>
 RT_HD void lane_aim_light(const DevScene& sc, const Tables& tb, LaneT& L) {
   LightFrame& f = light_frame(L.ls).cur;
+  if constexpr (QUADS) {
+    if (sc.n_tris & FLAT_LIGHTS_BIT) {
+      const uint32_t li = sc.lights[f.j];
+      if (li >= sc.n_spheres) {
+        const uint32_t k = li - sc.n_spheres, node = child_node(f.node, f.j);
+        L.o = f.P;
+        L.d = sub(flat_light_point(sc.quads.rec + k, sc.quads.lim ? sc.quads.lim + k : nullptr, L.ra, node), f.P);
+        L.node = node;
+        L.in_light |= 1u;
+        return;
+      }
+    }
+  }
   L.o = f.P;
   L.d = sub(tb.light_centre(sc, f.j), f.P);
   L.node = child_node(f.node, f.j);
   L.in_light |= 1u;
 }
 // a nested light ray produced colour tc: hand it to its parent activation(s) (:107-113)
-template <class Tables, class LaneT>
+template <bool QUADS = false, class Tables, class LaneT>
 RT_HD bool lane_light_return(const DevScene& sc, const Tables& tb, LaneT& L, Rgb tc) {
   for (;;) {
     LightFrame& f = light_frame(L.ls).cur;
     f.acc[0] += f.a[0] * tc.r; f.acc[1] += f.a[1] * tc.g; f.acc[2] += f.a[2] * tc.b;
     f.j += 1;
-    if (f.j < sc.n_lights) { lane_aim_light(sc, tb, L); return false; }
+    if (f.j < sc.n_lights) { lane_aim_light<QUADS>(sc, tb, L); return false; }
     float light[3] = {f.acc[0], f.acc[1], f.acc[2]};
     if (sc.n_lights != 1u) {  // raytracer.rs:112-114 `/= lights.len() as f32`: x / 1.0 is x — one light (every shipped scene) skips three IEEE divisions (wave-uniform branch)
       const float nl = (float)sc.n_lights;
@@ -2100,6 +2134,9 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
       const int st = scatter<MEDIUM, SOLID>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
       if (st != SCATTER_RAY) {  // :124 Light: its colour; :127-131 absorbed: black
         if (st == SCATTER_EMIT) col = rgb(att[0], att[1], att[2]);
+        if constexpr (QUADS) {  // (§28: a flat primitive of kind Light is an emitter: its record's colour is `emit`)
+          if (st == SCATTER_EMIT && (uint32_t)idx >= sc.n_spheres) col = rgb(m.albedo[0], m.albedo[1], m.albedo[2]);
+        }
         act = light_ray ? ACT_RETURN : ACT_FINISH;
       } else {
         // raytracer.rs:92-102: sample the lights?  Camera path: depth > max_depth-2 <=> k < 2 (and max_depth >= 2, usize
@@ -2129,12 +2166,12 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
         LightFrame& f = light_frame(L.ls).cur;
         f.P = point; f.a[0] = att[0]; f.a[1] = att[1]; f.a[2] = att[2];
         f.acc[0] = f.acc[1] = f.acc[2] = 0.0f; f.j = 0; f.node = L.node;
-        lane_aim_light(sc, tb, L);
+        lane_aim_light<QUADS>(sc, tb, L);
       }
     }
     __builtin_amdgcn_wave_barrier();
     RT_SHADE_MARK(2);
-    if (act == ACT_RETURN) result = lane_light_return(sc, tb, L, col) ? LANE_FINISHED : LANE_CONTINUE;
+    if (act == ACT_RETURN) result = lane_light_return<QUADS>(sc, tb, L, col) ? LANE_FINISHED : LANE_CONTINUE;
     __builtin_amdgcn_wave_barrier();
     RT_SHADE_MARK(3);
     if (act == ACT_FINISH) { lane_finish_sample(sc, L, col); result = LANE_FINISHED; }
@@ -2152,10 +2189,10 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
       LightFrame& f = light_frame(L.ls).cur;
       f.P = point; f.a[0] = att[0]; f.a[1] = att[1]; f.a[2] = att[2];
       f.acc[0] = f.acc[1] = f.acc[2] = 0.0f; f.j = 0; f.node = L.node;
-      lane_aim_light(sc, tb, L);
+      lane_aim_light<QUADS>(sc, tb, L);
       return LANE_CONTINUE;
     }
-    if (act == ACT_RETURN) return lane_light_return(sc, tb, L, col) ? LANE_FINISHED : LANE_CONTINUE;
+    if (act == ACT_RETURN) return lane_light_return<QUADS>(sc, tb, L, col) ? LANE_FINISHED : LANE_CONTINUE;
     if (act == ACT_FINISH) { lane_finish_sample(sc, L, col); return LANE_FINISHED; }
     return lane_continue_main(sc, L, point, out_dir, zero3, att) ? LANE_FINISHED : LANE_CONTINUE;
 #endif
@@ -2233,7 +2270,8 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
       if constexpr (QUADS) { m = tb.mat((uint32_t)best); h = object_surface<true>(sc, tb, L.o, L.d, closest, (uint32_t)best, m.inv_r, g); }
       else { g = tb.geom((uint32_t)best); m = tb.mat((uint32_t)best); h = surface_at(L.o, L.d, closest, g, m.inv_r); }
       a[0] = m.albedo[0]; a[1] = m.albedo[1]; a[2] = m.albedo[2];
-      if (m.kind == RT_MAT_GLASS || m.kind == RT_MAT_LIGHT) a[0] = a[1] = a[2] = 1.0f;  // (Glass: white; Light emits (1, 1, 1), materials.rs:65-69)
+      if (QUADS && m.kind == RT_MAT_LIGHT && (uint32_t)best >= sc.n_spheres) { }  // (§28: an emitting flat primitive reports its `emit`, the record's colour)
+      else if (m.kind == RT_MAT_GLASS || m.kind == RT_MAT_LIGHT) a[0] = a[1] = a[2] = 1.0f;  // (Glass: white; Light emits (1, 1, 1), materials.rs:65-69)
       else if (m.kind == RT_MAT_TEXTURE) {
         const UV uv = sphere_uv_for_texel(h.point, g, sc.mat, (uint32_t)best);
         const Rgb c = texture_albedo(sc, sc.mat[best], uv.u, uv.v, tex_oob);

@@ -228,8 +228,15 @@ struct RtHipScene {
         return h;
       }
     } flat;
-    // Materials, lights, media, textures and sky: uploaded at creation, never replaced.
+    // Materials, lights, media, textures and sky: uploaded at creation, never replaced — but for emission (rt_hip_scene_set_flat_lights,
+    // DESIGN.md §28), which rewrites the emitters' records of `mat` and `matc` and the light list: the Light spheres, then the emitters as
+    // object ids n_spheres + k.  On the host for that: the flat primitives' records as created (what an entry is again when it stops
+    // emitting), the Light spheres, and the emitters' entry indices in light order (empty: the scene is one that never had any).
     DevBuf mat, matc, lights;
+    std::vector<rtc::SphereMat> keep_flat_mat;
+    std::vector<rtc::MatCore> keep_flat_matc;
+    std::vector<uint32_t> sphere_lights, flat_lights;
+    uint32_t n_lights() const { return (uint32_t)(sphere_lights.size() + flat_lights.size()); }
     DevBuf medium;           // participating media: [n] density per sphere, 0 = no medium (HostTables::medium); unallocated without media
     uint32_t n_media = 0;
     uint32_t n_solids = 0;   // solid textures: Checker and Noise spheres (and quads); their parameters are in the `mat` records
@@ -256,7 +263,12 @@ struct RtHipScene {
       d.n_quads = flat.n_quads;
       d.n_tris = flat.n_tris | (flat.n_nodes ? rtc::FLAT_BVH_BIT : 0u) |  // (§22: the bit says that the header lies in front of quads.rec[0])
                  (flat.n_normals ? rtc::FLAT_NORMALS_BIT : 0u) |            // (§25: ... and that it names a table of shading normals)
-                 (flat.n_moving ? rtc::FLAT_MOTION_BIT : 0u);               // (§27: ... and a table of motion records)
+                 (flat.n_moving ? rtc::FLAT_MOTION_BIT : 0u) |              // (§27: ... and a table of motion records)
+                 (flat_lights.empty() ? 0u : rtc::FLAT_LIGHTS_BIT);         // (§28: the light list names emitting flat primitives)
+      // (§28: the light count and what fill_dev_scene derives from it, by its operations: emission can change them after creation)
+      d.n_lights = n_lights();
+      d.light_thr[0] = 1.0 - (double)d.n_lights * 0.1;
+      d.light_thr[1] = 1.0 - (double)d.n_lights * 0.05;
       d.mat = mat.get<const rtc::SphereMat>(); d.matc = matc.get<const rtc::MatCore>();
       d.lights = lights.get<const uint32_t>(); d.medium = n_media ? medium.get<const double>() : nullptr;
       d.tex = tex.get<const uint8_t>(); d.sky = sky.get<const uint8_t>();
@@ -571,6 +583,11 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   auto r = std::make_shared<RtHipScene::Resident>();
   r->device = device;
   r->has_lights = !t.lights.empty();
+  r->sphere_lights = t.lights;
+  if (n_quads) {  // (§28: what rt_hip_scene_set_flat_lights puts back when an entry stops emitting)
+    r->keep_flat_mat.assign(t.mat.begin() + scene->n_spheres, t.mat.end());
+    r->keep_flat_matc.assign(t.matc.begin() + scene->n_spheres, t.matc.end());
+  }
   r->simple_colour = t.simple_colour;
   RtHipScene::Resident::Spheres::Tables& live = r->sph.live;
   RtHipScene::Resident::Flats& f = r->flat;
@@ -757,7 +774,8 @@ void launch(RtHipScene* s, const Kernel& k, rtk::KArgs ka, size_t lds_bytes, uin
 
 // LDS budget of a launch: do the tables fit, how big are the light pools, how much dynamic LDS does a workgroup ask for.
 struct LdsPlan { bool lds_tables = false; uint32_t pool_slots = 0, base_slots = 0; size_t lds_bytes = 0; };
-int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPlan* out) {
+// n_lights: the light count the pools are sized for (-1: the scene's own)
+int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPlan* out, int64_t n_lights = -1) {
   // LDS budget.  Tables + tile slots + (lit scenes) the two pools of light records (rt_core.h): frames — held by a lane while
   // it sums over the lights — and, with the short colour map, bases — held from a sample's first light sampling to its end.
   // Expected demand: a camera path starts summing over the n lights with probability ~0.1 n at each of its first two hits
@@ -770,7 +788,7 @@ int plan_lds(const RtHipScene* s, const rtc::GridDesc& G, bool has_lights, LdsPl
   const bool short_map = has_lights && s->res->simple_colour;
   uint32_t pool_slots = 0, base_slots = 0;
   auto size_pools = [&](size_t avail, double* margin) {  // largest x with frames = x f 1024, bases = x b 1024 (multiples of 32, 32 .. 1024) inside `avail`
-    const double n = (double)s->dev.n_lights, den = 2.9 + 0.2 * n * n;
+    const double n = (double)(n_lights < 0 ? s->dev.n_lights : (uint32_t)n_lights), den = 2.9 + 0.2 * n * n;
     const double f = std::max(0.2 * n * n / den, 1.0 / 64.0), b = short_map ? std::min(1.0, std::max(0.2 * n * (n + 2.0) / den, 1.0 / 64.0)) : 0.0;
     auto slots = [&](double x, double share) -> uint32_t {
       if (share == 0.0) return 0u;
@@ -1267,6 +1285,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "triangles")) return (int64_t)s->res->flat.n_tris;      // of "quads", the entries of shape triangle
   if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->flat.n_nodes;  // nodes of the structure over the flat primitives; 0: none
   if (!std::strcmp(key, "flat_motion")) return (int64_t)s->res->flat.n_moving;  // entries that move within the frame; 0: none
+  if (!std::strcmp(key, "flat_lights")) return (int64_t)s->res->flat_lights.size();  // entries that emit; "n_lights" counts them too
   if (!std::strcmp(key, "flat_normals")) return (int64_t)s->res->flat.n_normals;  // entries that carry shading normals; 0: none
   if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat.refits;  // updates applied by refit since the structure was last built
   if (!std::strcmp(key, "flat_build")) return (int64_t)s->opt.flat_build;  // the option: 1: a rebuild the caller asks for runs on the device
@@ -1997,6 +2016,17 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
     if (const int refused = check_aligned(set_move ? move : quv, 8, set_move ? "rt_hip_scene_set_flat_motion: move must be 8-byte aligned" : "rt_hip_scene_update_flats: quv must be 8-byte aligned")) return refused;
   int rc;
   if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  if (set_move && move && !s->res->flat_lights.empty()) {  // (§28: an emitter cannot move, as a Light sphere cannot; only a scene that has one looks)
+    std::vector<double> dev_move;
+    if (on_device) {
+      dev_move.resize(3 * (size_t)n_quads);
+      RT_HIP_TRY(hipMemcpy(dev_move.data(), move, (size_t)n_quads * 24, hipMemcpyDeviceToHost));
+    }
+    const double* m = on_device ? dev_move.data() : move;
+    for (uint32_t k : s->res->flat_lights)   // (entry order: the lowest first)
+      if (!(m[3 * (size_t)k] == 0.0 && m[3 * (size_t)k + 1] == 0.0 && m[3 * (size_t)k + 2] == 0.0))
+        return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": an emitting flat primitive cannot move");
+  }
   if (set_move && !move && !f.n_moving) return RT_OK;   // nothing moves and nothing shall: the scene is what it was
   rtp::Clock pc = rtp::begin();
   const uint32_t n = n_quads;
@@ -2220,6 +2250,68 @@ extern "C" int rt_hip_scene_set_flat_normals(RtHipScene* s, const double* normal
   return scene_set_flat_normals(s, normals, n_quads, flags, false);
 }
 
+// ------------------------------------------------------------------------------ flat primitives that emit
+namespace {
+// The table is small (12 bytes an entry) and checked on the host, from host or device input alike.  What changes on the device: the emitters'
+// records of `mat` and `matc` (kind Light, colour `emit`; every other flat record is put back as created) and the light list; no geometry
+// table, no header slot — the aim reads the entry's own record.  Everything that can be refused is refused before the scene changes.
+int scene_set_flat_lights(RtHipScene* s, const float* emit, uint32_t n_quads, uint32_t flags, bool views_follow) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (flags & ~RT_UPDATE_FLATS_DEVICE) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: unknown flag");
+  RtHipScene::Resident& r = *s->res;
+  RtHipScene::Resident::Flats& f = r.flat;
+  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: the scene has no flat primitive");
+  if (n_quads != f.n_quads)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
+  if (!views_follow && s->res.use_count() > 1)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: the scene's tables are shared with a view (a group sets them through rt_hip_group_set_flat_lights)");
+  const bool on_device = emit && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
+  if (on_device)
+    if (const int refused = check_aligned(emit, 4, "rt_hip_scene_set_flat_lights: emit must be 4-byte aligned")) return refused;
+  int rc;
+  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  const uint32_t n = n_quads, n_spheres = s->host.n_spheres;
+  std::vector<float> table(3 * (size_t)n, 0.0f);   // (a null table: all zeros, no entry emits)
+  if (on_device) RT_HIP_TRY(hipMemcpy(table.data(), emit, (size_t)n * 12, hipMemcpyDeviceToHost));
+  else if (emit) std::memcpy(table.data(), emit, (size_t)n * 12);
+  uint32_t n_emit = 0;
+  const uint32_t bad = rt_flat_light_emit_check(table.data(), n, &n_emit);
+  if (bad != n) return fail(RT_ERR_INVALID, "quad " + std::to_string(bad) + ": every component of emit must be finite and in [0, 1]");
+  if (n_emit > RT_MAX_FLAT_LIGHTS) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_FLAT_LIGHTS (32) emitting flat primitives: every sampling hit shoots one ray per light");
+  if (!n_emit && r.flat_lights.empty()) return RT_OK;   // nothing emits and nothing shall: the scene is what it was
+  // the flat primitives' material records and the light list, on the host (rt_tables.h: the CPU builds of the tests make the same tables)
+  std::vector<rtc::SphereMat> mat;
+  std::vector<rtc::MatCore> matc;
+  std::vector<uint32_t> lights, emitters;
+  rtc::build_flat_lights(r.keep_flat_mat, r.keep_flat_matc, r.sphere_lights, n_spheres, table.data(), mat, matc, lights, emitters);
+  if (n_emit && f.n_moving) {  // an emitter cannot move, as a Light sphere cannot (whichever call comes second refuses)
+    std::vector<double> motion(4 * (size_t)n);
+    RT_HIP_TRY(hipMemcpy(motion.data(), f.motion.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    for (uint32_t k : emitters)
+      if (rt_flat_motion_present(&motion[4 * (size_t)k])) return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": an emitting flat primitive cannot move");
+  }
+  // the pools of the new light count must fit before anything changes (plan_lds reads the count from the scene)
+  {
+    LdsPlan plan;
+    if ((rc = plan_lds(s, s->dev.grid, !lights.empty(), &plan, (int64_t)lights.size())) != RT_OK) return rc;
+  }
+  DevBuf new_lights;   // (the list may grow: a buffer of its own, swapped in; the old one is freed with this frame, the device idle; the copy
+                       //  from pageable memory has returned when upload has)
+  if ((rc = upload(new_lights, lights)) != RT_OK) return rc;
+  RT_HIP_TRY(hipMemcpy(r.mat.get<rtc::SphereMat>() + n_spheres, mat.data(), mat.size() * sizeof(rtc::SphereMat), hipMemcpyHostToDevice));
+  RT_HIP_TRY(hipMemcpy(r.matc.get<rtc::MatCore>() + n_spheres, matc.data(), matc.size() * sizeof(rtc::MatCore), hipMemcpyHostToDevice));
+  RT_HIP_TRY(hipDeviceSynchronize());
+  r.lights.swap(new_lights);
+  r.flat_lights.swap(emitters);
+  r.has_lights = r.n_lights() != 0u;
+  return adopt_tables(s, Moved::flats);
+}
+}  // namespace
+
+extern "C" int rt_hip_scene_set_flat_lights(RtHipScene* s, const float* emit, uint32_t n_quads, uint32_t flags) {
+  return scene_set_flat_lights(s, emit, n_quads, flags, false);
+}
+
 // diagnostics: one resident table as the kernels read it
 extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* out, size_t cap, size_t* needed) {
   if (!s || !name) return fail(RT_ERR_INVALID, "null argument");
@@ -2241,6 +2333,10 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "flat_bvh")) { src = f.live.nodes.p; bytes = (size_t)f.n_nodes * sizeof(rtc::FlatNode); }
   else if (!std::strcmp(name, "flat_motion")) { src = f.motion.p; bytes = f.n_moving ? (size_t)f.n_quads * 32u : 0; }
   else if (!std::strcmp(name, "flat_normals")) { src = f.normals.p; bytes = f.n_normals ? (size_t)f.n_quads * 72u : 0; }
+  else if (!std::strcmp(name, "flat_lights")) { src = s->res->flat_lights.data(); bytes = s->res->flat_lights.size() * sizeof(uint32_t); host = true; }  // (§28: the emitters' entry indices in light order)
+  else if (!std::strcmp(name, "lights")) { src = s->res->lights.p; bytes = (size_t)s->res->n_lights() * sizeof(uint32_t); }
+  else if (!std::strcmp(name, "mat")) { src = s->res->mat.p; bytes = ((size_t)s->host.n_spheres + f.n_quads) * sizeof(rtc::SphereMat); }
+  else if (!std::strcmp(name, "matc")) { src = s->res->matc.p; bytes = ((size_t)s->host.n_spheres + f.n_quads) * sizeof(rtc::MatCore); }
   else if (!std::strcmp(name, "flat_bvh_order")) { src = f.live.order.p; bytes = f.n_nodes ? (size_t)f.n_quads * sizeof(uint32_t) : 0; }
   else return fail(RT_ERR_INVALID, std::string("unknown table ") + name);
   if (needed) *needed = bytes;
@@ -2372,6 +2468,51 @@ extern "C" int rt_hip_medium_probe(RtHipScene* s, const double* d_rays, const fl
   if (!n) return RT_OK;
   RT_HIP_TRY(hipSetDevice(s->device));
   hipLaunchKernelGGL(rtk::rt_medium_probe, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, d_rays, d_tau, d_node, d_t, d_best, d_work, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// The device form of the aim at an emitting flat primitive (include/rt_abi_test_flat_light.h), one activation per thread.
+namespace rtk {
+// activation i = {pixel, sample, node of the hit} shooting light j[i] of the scene: what lane_aim_light's flat arm does — the light list, the
+// entry's resident record and limit, child_node, the cold flat_light_point — and T comes back; a j that is not an emitter gives three NaNs
+__global__ void rt_flat_light_probe(const rtc::DevScene sc, const uint32_t* act, const uint32_t* j, double* T, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  rtc::V3 t = rtc::v3(rtc::rt_nan(), rtc::rt_nan(), rtc::rt_nan());
+  const uint32_t lj = j[i];
+  if (lj < sc.n_lights && sc.lights[lj] >= sc.n_spheres) {
+    const uint32_t k = sc.lights[lj] - sc.n_spheres;
+    const rtc::RngAddr ra{act[3u * i], act[3u * i + 1u], sc.seed_lo, sc.seed_hi};
+    t = rtc::flat_light_point(sc.quads.rec + k, sc.quads.lim ? sc.quads.lim + k : nullptr, ra, rtc::child_node(act[3u * i + 2u], lj));
+  }
+  T[3u * i] = t.x; T[3u * i + 1u] = t.y; T[3u * i + 2u] = t.z;
+}
+// rt_flat_light_aim of activation i on ITS OWN entry quv[i] (q, u, v), shape and four words: the header's arithmetic on crafted tables
+__global__ void rt_flat_light_aim_probe(const double* quv, const int32_t* triangle, const uint32_t* words, double* T, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  rt_flat_light_aim(quv + 9u * (size_t)i, quv + 9u * (size_t)i + 3, quv + 9u * (size_t)i + 6, triangle[i] != 0, words + 4u * (size_t)i, T + 3u * (size_t)i);
+}
+}  // namespace rtk
+extern "C" int rt_hip_flat_light_probe(RtHipScene* s, const double* d_P, const uint32_t* d_pixel_sample_node, const uint32_t* d_j, double* d_T, uint32_t n,
+                                       void* stream) {
+  (void)d_P;   // (the aim point does not depend on where the light ray starts: d = T - P is the caller's subtraction)
+  if (!s || !d_pixel_sample_node || !d_j || !d_T) return fail(RT_ERR_INVALID, "null argument");
+  if (s->res->flat_lights.empty()) return fail(RT_ERR_INVALID, "the scene has no emitting flat primitive");
+  if (!n) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_flat_light_probe, dim3((n + 191) / 192), dim3(192), 0, (hipStream_t)stream, s->dev, d_pixel_sample_node, d_j, d_T, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+// (block: the launch's workgroup size, 1 .. 1024; a test passes one that is not a multiple of 64)
+extern "C" int rt_hip_flat_light_aim_probe(const double* d_quv, const int32_t* d_triangle, const uint32_t* d_words, double* d_T, uint32_t n, uint32_t block,
+                                           void* stream) {
+  if (!d_quv || !d_triangle || !d_words || !d_T) return fail(RT_ERR_INVALID, "null argument");
+  if (block < 1u || block > 1024u) return fail(RT_ERR_INVALID, "block must be 1 .. 1024");
+  if (!n) return RT_OK;
+  hipLaunchKernelGGL(rtk::rt_flat_light_aim_probe, dim3((n + block - 1u) / block), dim3(block), 0, (hipStream_t)stream, d_quv, d_triangle, d_words, d_T, n);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }

@@ -393,6 +393,12 @@ __global__ __launch_bounds__(BLOCK) RT_WAVES_ATTR void rt_megakernel(const KArgs
   if constexpr (HL) {  // centres of the lights: read when a light ray is aimed (raytracer.rs:104-105)
     double* lc = reinterpret_cast<double*>(lds_raw + LIGHT_CENTRES_LDS_OFF);
     const uint32_t nl = sc.n_lights < LIGHT_CENTRES_LDS_MAX ? sc.n_lights : LIGHT_CENTRES_LDS_MAX;
+    if constexpr (QUADS) {  // (§28: an emitting flat primitive, object id >= n_spheres, has no centre: lane_aim_light never reads its slot)
+      for (uint32_t i = threadIdx.x; i < 3u * nl; i += BLOCK) {
+        const uint32_t li = sc.lights[i / 3u];
+        lc[i] = li < sc.n_spheres ? reinterpret_cast<const double*>(sc.geom + li)[i % 3u] : 0.0;
+      }
+    } else
     for (uint32_t i = threadIdx.x; i < 3u * nl; i += BLOCK) lc[i] = reinterpret_cast<const double*>(sc.geom + sc.lights[i / 3u])[i % 3u];
     __syncthreads();
   }

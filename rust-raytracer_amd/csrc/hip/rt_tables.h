@@ -543,6 +543,34 @@ inline std::string build_quads(const RtQuad* quads, uint32_t n_quads, HostTables
   return "";
 }
 
+// The tables of a scene whose flat primitives emit (rt_hip_scene_set_flat_lights; the CPU builds of the tests call it too).
+// In: the flat primitives' material records as created (entry k = object n_spheres + k), the Light spheres in object order, and `emit`,
+// [n][3], already checked (rt_flat_light_emit_check).  Out: the flat records with every emitter's replaced by a record of kind Light whose
+// colour is `emit` and whose other bytes are zero; the light list — the Light spheres, then the emitters in entry order as OBJECT ids; the
+// emitters' entry indices.  A null or all-zero `emit` gives the records as created and the Light spheres alone.
+inline void build_flat_lights(const std::vector<SphereMat>& flat_mat, const std::vector<MatCore>& flat_matc, const std::vector<uint32_t>& sphere_lights,
+                              uint32_t n_spheres, const float* emit, std::vector<SphereMat>& mat, std::vector<MatCore>& matc, std::vector<uint32_t>& lights,
+                              std::vector<uint32_t>& emitters) {
+  mat = flat_mat; matc = flat_matc; lights = sphere_lights;
+  emitters.clear();
+  for (uint32_t k = 0; emit && k < (uint32_t)flat_mat.size(); ++k) {
+    const float* e = emit + 3 * (size_t)k;
+    if (!rt_flat_light_emits(e)) continue;
+    SphereMat m;
+    std::memset(&m, 0, sizeof m);
+    m.albedo[0] = e[0]; m.albedo[1] = e[1]; m.albedo[2] = e[2];
+    m.kind = RT_MAT_LIGHT;
+    mat[k] = m;
+    MatCore mc;
+    std::memset(&mc, 0, sizeof mc);
+    mc.albedo[0] = e[0]; mc.albedo[1] = e[1]; mc.albedo[2] = e[2];
+    mc.kind = RT_MAT_LIGHT;
+    matc[k] = mc;
+    emitters.push_back(k);
+    lights.push_back(n_spheres + k);
+  }
+}
+
 // ------------------------------------------------------------------ the structure over the flat primitives
 // (the padded box of an entry, flat_entry_box, and its constants: rt_flat_build.h — the device code that moves the flat primitives of a
 //  resident scene computes the same boxes)

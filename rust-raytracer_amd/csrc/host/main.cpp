@@ -67,6 +67,10 @@ int set_normals(RtHipGroup* h, const double* n, uint32_t k) { return rt_hip_grou
 // right after creation too (rt_hip_scene_set_flat_motion / rt_hip_group_set_flat_motion) and blurs in every mode a "center1" file blurs in.
 int set_motion(RtHipScene* h, const double* m, uint32_t k) { return rt_hip_scene_set_flat_motion(h, m, k, 0u); }
 int set_motion(RtHipGroup* h, const double* m, uint32_t k) { return rt_hip_group_set_flat_motion(h, m, k, 0u); }
+// Area lights: a file whose quads, triangles, boxes or meshes carry "emit" (rt_scene_flat_emit) has it set right after
+// creation too (rt_hip_scene_set_flat_lights / rt_hip_group_set_flat_lights), before the motion: an emitter may not move.
+int set_lights(RtHipScene* h, const float* e, uint32_t k) { return rt_hip_scene_set_flat_lights(h, e, k, 0u); }
+int set_lights(RtHipGroup* h, const float* e, uint32_t k) { return rt_hip_group_set_flat_lights(h, e, k, 0u); }
 void destroy(RtHipScene* h) { rt_hip_scene_destroy(h); }
 void destroy(RtHipGroup* h) { rt_hip_group_destroy(h); }
 template <class Handle, class Where>
@@ -80,6 +84,9 @@ int create(const Run& r, Where where, Handle** out, int (*moving)(const RtScene*
   uint32_t n_normals = 0;
   const double* normals = rt_scene_flat_normals(r.sf, &n_normals);
   if (rc == RT_OK && normals && (rc = set_normals(*out, normals, n_normals)) != RT_OK) { destroy(*out); *out = nullptr; }
+  uint32_t n_emit = 0;
+  const float* emit = rt_scene_flat_emit(r.sf, &n_emit);
+  if (rc == RT_OK && emit && (rc = set_lights(*out, emit, n_emit)) != RT_OK) { destroy(*out); *out = nullptr; }
   uint32_t n_move = 0;
   const double* move = rt_scene_flat_motion(r.sf, &n_move);
   if (rc == RT_OK && move && (rc = set_motion(*out, move, n_move)) != RT_OK) { destroy(*out); *out = nullptr; }
@@ -198,10 +205,12 @@ struct FlatFrames {
   std::vector<RtQuad> base;
   std::vector<double> base_normals;   // the base file's rt_scene_flat_normals, empty without
   bool moved = false;                 // the base file or some frame file loaded so far has "move" (§27): from then on every frame sets its motion
+  bool lit = false;                   // the base file or some frame file loaded so far has "emit" (§28): from then on every frame sets its emission
   std::mutex mu;
   bool on() const { return !prefix.empty(); }
   // move: the frame file's rt_scene_flat_motion (n x 3; all zeros for a file without the key once `moved`), empty while nothing ever moved
-  std::string load(int f, std::vector<double>& out, std::vector<double>& normals, std::vector<double>& move) {
+  // emit: the frame file's rt_scene_flat_emit (n x 3) likewise
+  std::string load(int f, std::vector<double>& out, std::vector<double>& normals, std::vector<double>& move, std::vector<float>& emit) {
     std::lock_guard<std::mutex> lk(mu);
     char path[4096];
     std::snprintf(path, sizeof path, "%s%03d.json", prefix.c_str(), f);
@@ -235,6 +244,11 @@ struct FlatFrames {
     move.clear();
     if (why.empty() && fm) { move.assign(fm, fm + 3 * (size_t)nm); moved = true; }
     else if (why.empty() && moved) move.assign(3 * base.size(), 0.0);
+    uint32_t ne = 0;
+    const float* fe = rt_scene_flat_emit(ff, &ne);
+    emit.clear();
+    if (why.empty() && fe) { emit.assign(fe, fe + 3 * (size_t)ne); lit = true; }
+    else if (why.empty() && lit) emit.assign(3 * base.size(), 0.0f);
     rt_scene_free(ff);
     return why;
   }
@@ -250,6 +264,7 @@ struct Pose {
   std::vector<double> c, c1, quv;
   std::vector<double> normals;  // --flat-frames: the frame's shading normals (n x 9), set after its flat primitives; empty: the scene has none
   std::vector<double> move;     // --flat-frames: the frame's motion within the frame (n x 3, §27), set after its flat primitives; empty: nothing ever moved
+  std::vector<float> emit;      // --flat-frames: the frame's emission (n x 3, §28), set before its motion; empty: nothing ever emitted
 };
 // One apply per kind of target.  Each keeps the order of calls its drivers always had (camera first on a scene, last on a group).
 // rt_hip_set_camera / rt_hip_group_set_camera refuse null arguments and nothing else, so checking their status changes no run.
@@ -259,14 +274,23 @@ int apply(RtHipScene* hs, const Pose& p) {
   if (rc == RT_OK && p.spheres) rc = rt_hip_scene_update_spheres(hs, p.c.data(), p.c1.data());
   if (rc == RT_OK && p.flats) rc = rt_hip_scene_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), p.flat_flags);
   if (rc == RT_OK && p.flats && !p.normals.empty()) rc = rt_hip_scene_set_flat_normals(hs, p.normals.data(), (uint32_t)(p.normals.size() / 9), 0u);
-  if (rc == RT_OK && p.flats && !p.move.empty()) rc = rt_hip_scene_set_flat_motion(hs, p.move.data(), (uint32_t)(p.move.size() / 3), 0u);
+  // (§28: an emitter may not move, whichever call comes second — and the scene still holds the PREVIOUS frame's tables.  A frame that has
+  //  both first removes the emission, then sets its motion, then its emission: a frame file is valid in itself, so neither call is refused
+  //  for what an earlier frame left behind)
+  if (rc == RT_OK && p.flats && !p.emit.empty() && !p.move.empty()) rc = rt_hip_scene_set_flat_lights(hs, nullptr, (uint32_t)(p.emit.size() / 3), 0u);
+  if (rc == RT_OK && p.flats && !p.emit.empty() && !p.move.empty()) rc = rt_hip_scene_set_flat_motion(hs, p.move.data(), (uint32_t)(p.move.size() / 3), 0u);
+  if (rc == RT_OK && p.flats && !p.emit.empty()) rc = rt_hip_scene_set_flat_lights(hs, p.emit.data(), (uint32_t)(p.emit.size() / 3), 0u);
+  if (rc == RT_OK && p.flats && !p.move.empty() && p.emit.empty()) rc = rt_hip_scene_set_flat_motion(hs, p.move.data(), (uint32_t)(p.move.size() / 3), 0u);
   return rc;
 }
 int apply(RtHipGroup* hs, const Pose& p) {  // (no frame may be in flight while the spheres or the flat primitives move)
   int rc = p.spheres ? rt_hip_group_update_spheres(hs, p.c.data(), p.c1.data()) : RT_OK;
   if (rc == RT_OK && p.flats) rc = rt_hip_group_update_flats(hs, p.quv.data(), (uint32_t)(p.quv.size() / 9), p.flat_flags);
   if (rc == RT_OK && p.flats && !p.normals.empty()) rc = rt_hip_group_set_flat_normals(hs, p.normals.data(), (uint32_t)(p.normals.size() / 9), 0u);
-  if (rc == RT_OK && p.flats && !p.move.empty()) rc = rt_hip_group_set_flat_motion(hs, p.move.data(), (uint32_t)(p.move.size() / 3), 0u);
+  if (rc == RT_OK && p.flats && !p.emit.empty() && !p.move.empty()) rc = rt_hip_group_set_flat_lights(hs, nullptr, (uint32_t)(p.emit.size() / 3), 0u);   // (as above)
+  if (rc == RT_OK && p.flats && !p.emit.empty() && !p.move.empty()) rc = rt_hip_group_set_flat_motion(hs, p.move.data(), (uint32_t)(p.move.size() / 3), 0u);
+  if (rc == RT_OK && p.flats && !p.emit.empty()) rc = rt_hip_group_set_flat_lights(hs, p.emit.data(), (uint32_t)(p.emit.size() / 3), 0u);
+  if (rc == RT_OK && p.flats && !p.move.empty() && p.emit.empty()) rc = rt_hip_group_set_flat_motion(hs, p.move.data(), (uint32_t)(p.move.size() / 3), 0u);
   if (rc == RT_OK) rc = rt_hip_group_set_camera(hs, p.cam, p.cam + 3, p.cam + 6, p.cam + 9);
   if (rc == RT_OK && p.lens) rc = rt_hip_group_set_lens(hs, p.cam + 13, p.cam + 16, p.cam[19]);
   return rc;
@@ -313,7 +337,7 @@ struct Anim {
   std::string flats(int f, Pose& p) {
     p.flats = flat_files.on();
     p.flat_flags = (r.o.flat_rebuild > 0 && f > 0 && f % r.o.flat_rebuild == 0) ? RT_UPDATE_FLATS_REBUILD : 0u;
-    return p.flats ? flat_files.load(f, p.quv, p.normals, p.move) : std::string();
+    return p.flats ? flat_files.load(f, p.quv, p.normals, p.move, p.emit) : std::string();
   }
   std::string pose(int f, Pose& p) { view(f, p); return flats(f, p); }
   std::string frame_name(int f) const {
@@ -612,6 +636,7 @@ int animate(const Run& r) {
     uint32_t n_normals = 0;
     if (const double* nr = rt_scene_flat_normals(r.sf, &n_normals)) a.flat_files.base_normals.assign(nr, nr + 9 * (size_t)n_normals);
     a.flat_files.moved = rt_scene_flat_motion(r.sf, nullptr) != nullptr;
+    a.flat_files.lit = rt_scene_flat_emit(r.sf, nullptr) != nullptr;
     const std::string why = a.flats(0, first);
     if (!why.empty()) { std::fprintf(stderr, "%s\n", why.c_str()); return 101; }
     if (r.o.flat_rebuild > 0 && !(r.o.flat_bvh || rt_scene_flat_bvh(r.sf))) {

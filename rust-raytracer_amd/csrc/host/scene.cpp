@@ -23,6 +23,7 @@
 
 #include "../../../include/rt_abi.h"
 #include "../common/rt_quad.h"
+#include "../common/rt_flat_light.h"
 #include "json.hpp"
 
 extern "C" const char* rt_jpeg_last_error(void);
@@ -209,6 +210,11 @@ struct RtSceneFile {
   std::vector<double> move;
   std::vector<uint8_t> has_move;
   size_t n_move = 0;
+  // area lights: [quads.size()][3] the "emit" of every entry as written, three +0.0 for an entry without; has_emit: the
+  // entries whose object had the key (what rt_scene_to_json writes it for); n_emit: their count (0: rt_scene_flat_emit is NULL)
+  std::vector<float> emit;
+  std::vector<uint8_t> has_emit;
+  size_t n_emit = 0;
   // the structure over the flat primitives: the file's top-level "flat_bvh": true (rt_scene_flat_bvh; written back only when true)
   bool flat_bvh = false;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
@@ -642,6 +648,28 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         for (int k = 0; k < 3; ++k)
           if (!rt_quad_finite(move[k])) bad("move: a displacement must be finite");
       }
+      // area lights: an optional "emit" beside any of the four forms; a box or a mesh gives it to every face
+      const Value* emit_v = nullptr;
+      if (o.kind == Value::Object)
+        for (auto& mb : o.members)
+          if (mb.first == "emit") {
+            if (emit_v) bad("duplicate field `emit`");
+            emit_v = mb.second.get();
+          }
+      float emit[3] = {0.0f, 0.0f, 0.0f};
+      if (emit_v) {
+        double e[3];
+        try {
+          as_point(*emit_v, "emit", e);
+        } catch (const SchemaError& err) {
+          bad("emit: " + err.msg);
+        }
+        for (int k = 0; k < 3; ++k) {
+          if (!(e[k] >= 0.0 && e[k] <= 1.0)) bad("emit: every component must be finite and in [0, 1]");
+          emit[k] = static_cast<float>(e[k]);
+        }
+        if (rt_flat_light_emits(emit) && !(move[0] == 0.0 && move[1] == 0.0 && move[2] == 0.0)) bad("emit: an emitting flat primitive cannot move (`move` is not zero)");
+      }
       const Value& m = *mat_v;
       if (m.kind == Value::Object && m.members.size() == 1)
         for (const char* k : {"Texture", "Light", "Medium"})
@@ -676,6 +704,9 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         }
         sf.has_move.push_back(move_v ? 1 : 0);
         if (move_v) sf.n_move++;
+        for (int k = 0; k < 3; ++k) sf.emit.push_back(emit[k]);
+        sf.has_emit.push_back(emit_v ? 1 : 0);
+        if (emit_v) sf.n_emit++;
       }
     } catch (const SchemaError& e) {
       bad(e.msg.rfind(which, 0) == 0 ? e.msg : which + ": " + e.msg);
@@ -687,6 +718,7 @@ void build_scene(const Value& root, RtSceneFile& sf) {
       ++obj_index;
       continue;
     }
+    if (o->kind == Value::Object && o->find("emit")) bad("objects[" + std::to_string(obj_index) + "]: a sphere takes no `emit` (a sphere that emits is a Light; `emit` is a flat primitive's)");
     RtSphere s{};
     const Value* sp[4] = {};
     // (+ the optional "center1" of a map; the sequence form stays the reference's three fields)
@@ -808,6 +840,7 @@ std::string scene_json(const RtSceneFile& sf) {
       for (int k = 0; k < 9; ++k) smooth = smooth || nr[k] != 0.0;
       if (smooth) o += ",\"normals\":[" + point(nr) + "," + point(nr + 3) + "," + point(nr + 6) + "]";
       if (sf.has_move[iq - 1]) o += ",\"move\":" + point(&sf.move[3 * (iq - 1)]);  // (§27: only where the file had the key)
+      if (sf.has_emit[iq - 1]) o += ",\"emit\":" + albedo(&sf.emit[3 * (iq - 1)]);  // (§28: likewise)
       o += ",\"material\":{";
     } else {
       o += "{\"center\":" + point(s.center);
@@ -917,6 +950,11 @@ extern "C" const double* rt_scene_flat_motion(const RtSceneFile* sf, uint32_t* n
   const bool any = sf && sf->n_move != 0;
   if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
   return any ? sf->move.data() : nullptr;
+}
+extern "C" const float* rt_scene_flat_emit(const RtSceneFile* sf, uint32_t* n) {
+  const bool any = sf && sf->n_emit != 0;
+  if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
+  return any ? sf->emit.data() : nullptr;
 }
 extern "C" const double* rt_scene_flat_normals(const RtSceneFile* sf, uint32_t* n) {
   const bool any = sf && sf->n_normals != 0;

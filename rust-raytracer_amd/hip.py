@@ -60,6 +60,8 @@ def _bind(path, probes):
     L.rt_hip_group_set_flat_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_scene_set_flat_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_group_set_flat_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_scene_set_flat_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_group_set_flat_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_scene_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rt_hip_group_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
@@ -192,27 +194,27 @@ def _centres(n, c, what):
     return (C.c_double * max(1, 3 * n)).from_buffer_copy(a.tobytes() if n else bytes(8))
 
 
-def _flat_geometry(quv, device, rebuild, width=9, what="quv"):
+def _flat_geometry(quv, device, rebuild, width=9, what="quv", dtype="float64"):
     """the arguments of rt_hip_*_update_flats for quv, an [n, 9] float64 numpy array (or anything numpy makes one of) or a CUDA torch
     tensor of that shape and dtype: (pointer, n, flags, what must stay alive over the call).  A contiguous tensor on `device` (an index;
     None: never) is handed over as device memory; any other tensor travels through the host."""
     import numpy as np
     flags = abi.RT_UPDATE_FLATS_REBUILD if rebuild else 0
     if hasattr(quv, "data_ptr") and hasattr(quv, "is_cuda"):   # a torch tensor
-        if quv.dim() != 2 or quv.shape[1] != width or str(quv.dtype) != "torch.float64":
-            raise ValueError(f"{what} must be an [n, {width}] float64 tensor, got {tuple(quv.shape)} {quv.dtype}")
+        if quv.dim() != 2 or quv.shape[1] != width or str(quv.dtype) != "torch." + dtype:
+            raise ValueError(f"{what} must be an [n, {width}] {dtype} tensor, got {tuple(quv.shape)} {quv.dtype}")
         if quv.is_cuda and quv.is_contiguous() and device is not None and quv.device.index == device:
             import torch
             torch.cuda.current_stream(quv.device).synchronize()   # (the library reads on its own stream: what wrote the tensor has finished)
             return C.c_void_p(quv.data_ptr()), quv.shape[0], flags | abi.RT_UPDATE_FLATS_DEVICE, quv
         quv = quv.detach().cpu().numpy()
-    a = np.ascontiguousarray(np.asarray(quv, np.float64))
+    a = np.ascontiguousarray(np.asarray(quv, np.dtype(dtype)))
     if a.ndim != 2 or a.shape[1] != width:
         raise ValueError(f"{what} must be n x {width} values, got shape {a.shape}")
     return C.c_void_p(a.ctypes.data), a.shape[0], flags, a
 
 
-TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order", "flat_normals", "flat_motion")   # the names rt_hip_scene_table knows
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order", "flat_normals", "flat_motion", "flat_lights", "lights", "mat", "matc")   # the names rt_hip_scene_table knows
 
 
 def _quads_array(quads):
@@ -292,6 +294,16 @@ class HipScene:
             return
         p, n, flags, keep = _flat_geometry(move, self.device, False, width=3, what="move")
         _check(self._L.rt_hip_scene_set_flat_motion(self._h, p, n, flags), self._L)
+        del keep
+
+    def set_flat_lights(self, emit):
+        """rt_hip_scene_set_flat_lights: the emission of every flat primitive — [n_quads, 3] float32 in [0, 1] (three
+        zeros: the entry does not emit), a numpy array or a CUDA torch tensor as for update_flats; None removes emission.  Blocking."""
+        if emit is None:
+            _check(self._L.rt_hip_scene_set_flat_lights(self._h, None, int(self.query("quads")), 0), self._L)
+            return
+        p, n, flags, keep = _flat_geometry(emit, self.device, False, width=3, what="emit", dtype="float32")
+        _check(self._L.rt_hip_scene_set_flat_lights(self._h, p, n, flags), self._L)
         del keep
 
     def table(self, name):
@@ -603,6 +615,18 @@ class HipGroup:
             return
         p, n, flags, keep = _flat_geometry(move, None, False, width=3, what="move")
         _check(self._L.rt_hip_group_set_flat_motion(self._h, p, n, flags), self._L)
+        del keep
+
+    def set_flat_lights(self, emit, n_quads=None):
+        """rt_hip_group_set_flat_lights: HipScene.set_flat_lights on every rank (through host memory); None removes emission and needs
+        n_quads, the scene's count"""
+        if emit is None:
+            if n_quads is None:
+                raise ValueError("set_flat_lights(None) needs n_quads, the scene's count")
+            _check(self._L.rt_hip_group_set_flat_lights(self._h, None, int(n_quads), 0), self._L)
+            return
+        p, n, flags, keep = _flat_geometry(emit, None, False, width=3, what="emit", dtype="float32")
+        _check(self._L.rt_hip_group_set_flat_lights(self._h, p, n, flags), self._L)
         del keep
 
     def set_option(self, key, value):
