@@ -91,7 +91,7 @@ typedef struct RtSphere {
 /* A quad (an extension of the schema; the reference has no such object and its loader rejects the file): the flat
  * parallelogram q + a u + b v, 0 <= a, b <= 1, two-sided.  The material fields mean what they mean in RtSphere; a quad may be
  * Lambertian, Metal, Glass, Checker or Noise (the solid's pattern in the quad's frame: centre = q).  Texture, Light and Medium quads
- * are RT_ERR_INVALID: a quad has no (u, v) map, a medium needs a volume, and a quad cannot be a Light MATERIAL (emission:
+ * are RT_ERR_INVALID: a picture comes in beside the material (rt_hip_scene_set_flat_images), a medium needs a volume, and a quad cannot be a Light MATERIAL (emission:
  * rt_hip_scene_set_flat_lights).  Quads do not move within a frame (no center1) unless rt_hip_scene_set_flat_motion gives them a displacement over the shutter; rt_hip_scene_update_flats moves them between frames.
  * Triangles: `reserved` carries the SHAPE of the flat primitive, RT_QUAD_SHAPE_PARALLELOGRAM (0, the quad above) or
  * RT_QUAD_SHAPE_TRIANGLE (1): the points q + a u + b v with 0 <= a, 0 <= b, a + b <= 1, two-sided.  Everything else about the entry —
@@ -123,6 +123,22 @@ typedef struct RtTexture {
   uint64_t nbytes;
   uint32_t width, height; /* decoded size, informational */
 } RtTexture;
+
+/* An image on a flat primitive (rt_hip_scene_set_flat_images): entry k of the table belongs to flat primitive k.  uv: the
+ * texture coordinates (s, t) at Q, at Q + u and at Q + v — a hit's (s, t) is their affine combination, on a parallelogram too; t points up
+ * (t = 1 is the image's top row).  tex_id: an index into the RtScene.textures the scene was created with, whose DECODED width x height
+ * (RtTexture.width / height, nbytes = 3 width height) is the image; RT_FLAT_IMAGE_NONE: no image, the rest of the entry is ignored.
+ * wrap_s, wrap_t: what a coordinate outside [0, 1) does, RT_WRAP_REPEAT (tile) or RT_WRAP_CLAMP (the edge texel).  The fetch is the nearest
+ * texel.  csrc/common/rt_flat_image.h holds the contract step by step. */
+#define RT_FLAT_IMAGE_NONE 0xFFFFFFFFu
+#define RT_WRAP_REPEAT 0u
+#define RT_WRAP_CLAMP 1u
+typedef struct RtFlatImage {
+  double uv[6];
+  uint32_t tex_id;
+  uint32_t wrap_s, wrap_t;
+  uint32_t reserved;  /* must be 0 */
+} RtFlatImage;
 
 /* config.rs:66-75 Config, with the camera already derived (camera.rs:45-77). */
 typedef struct RtScene {
@@ -290,6 +306,15 @@ const double* rt_scene_flat_motion(const RtSceneFile*, uint32_t* n);
  * non-zero "move" is a load error naming objects[i]; rt_scene_to_json writes the key only where the file had it: load -> write -> load is
  * bit for bit. */
 const float* rt_scene_flat_emit(const RtSceneFile*, uint32_t* n);
+/* Images (an extension too): an optional "image": {"pixels": "path.jpg", "wrap": "repeat" | "clamp" | [ws, wt]} on the
+ * object map of a quad, a "triangle", a "box" or a "mesh", with an optional "uvs": beside q/u/v three pairs (s, t) for Q, Q + u, Q + v
+ * (default (0,0), (1,0), (0,1)); beside "triangle" three pairs for a, b, c; inside "mesh" one pair per vertex (required with "image"); a
+ * box takes the default on each face.  The file is decoded like a Texture material's and shares its table (rt_scene_get()->textures).
+ * *n entries in the order of rt_scene_quads — what rt_hip_scene_set_flat_images takes —, tex_id RT_FLAT_IMAGE_NONE for an entry without.
+ * NULL and 0 when no object has the key.  Owned by the RtSceneFile.  "image" on a sphere, "uvs" without "image" or on a box, a duplicate
+ * key, a non-finite component, an unknown wrap, a uv count other than the vertex count, or a material other than Lambertian or Metal is a
+ * load error naming objects[i]; rt_scene_to_json writes the keys only where the file had them: load -> write -> load is bit for bit. */
+const RtFlatImage* rt_scene_flat_images(const RtSceneFile*, uint32_t* n);
 /* The structure over the flat primitives (an extension too): a top-level "flat_bvh": true beside "camera" and "objects"
  * asks for rt_hip_scene_create_flats_bvh / rt_hip_group_create_flats_bvh and lifts the loader's cap from RT_MAX_QUADS to RT_MAX_FLATS_BVH
  * (the entry that crosses it is still named by its objects[i]).  1 for such a file, 0 when the key is false or absent: today's behaviour.
@@ -573,6 +598,25 @@ int rt_hip_scene_set_flat_motion(RtHipScene*, const double* move, uint32_t n_qua
  * exactly as before. */
 #define RT_MAX_FLAT_LIGHTS 32u
 int rt_hip_scene_set_flat_lights(RtHipScene*, const float* emit, uint32_t n_quads, uint32_t flags);
+/* Images: the flat primitives of a resident scene that show a picture.  images: n_quads entries in entry order.  An entry
+ * with an image scatters exactly as its own material does — which must be Lambertian or Metal: its fuzz, its RNG draws, its absorbed /
+ * scattered decision — and its attenuation is the nearest texel at the hit's (s, t) instead of `albedo` (csrc/common/rt_flat_image.h holds
+ * the contract step by step; no index can leave the texture, RtStats.tex_oob is never touched).  An entry that also emits
+ * (rt_hip_scene_set_flat_lights) emits: its own material, image included, is ignored meanwhile.  The first-hit albedo of rt_hip_render_aovs
+ * is the texel too.  A later call replaces the whole table; NULL, or all entries RT_FLAT_IMAGE_NONE, removes the images: the scene is then,
+ * table for table and bit for bit, one that never had any.  No kernel key changes.  The (s, t) are relative to the entry's own frame: an
+ * image rides its entry through rt_hip_scene_update_flats (refit or rebuild) and rt_hip_scene_set_flat_motion, and
+ * rt_hip_scene_update_spheres, rt_hip_scene_set_flat_normals and rt_hip_scene_set_flat_lights keep the images as set.
+ * flags: 0, or RT_UPDATE_FLATS_DEVICE (images is device memory on the scene's device, 8-byte aligned).  The records are made on the device
+ * from either input.  Blocking; waits for the scene's unfinished launch and drops what rt_hip_scene_update_flats drops.
+ * rt_hip_scene_query "flat_images" = the entries with an image; rt_hip_scene_table "flat_images" = the resident records, 64 bytes an entry
+ * ({u32 texel_off, W, H, wrap_s | wrap_t << 1; f64 uv[6]}, W = 0: no image), empty without.
+ * RT_ERR_INVALID: a null scene; another flag; n_quads different from the scene's; a scene without flat primitives; of all bad entries the
+ * lowest k, "quad k: ...": a uv component that is not finite, tex_id >= n_textures, a texture with nbytes != 3 width height or a zero
+ * side, or one outside the 2^31 texels the scene keeps resident as 4-byte texels, a wrap value above 1, reserved != 0, an own material
+ * other than Lambertian or Metal; a scene whose tables a live view shares (rt_hip_group_set_flat_images).  After any error the scene
+ * renders exactly as before. */
+int rt_hip_scene_set_flat_images(RtHipScene*, const RtFlatImage* images, uint32_t n_quads, uint32_t flags);
 /* Animation (the reference's `anim/frame_%03d.png` workflow, README.md:43-57, main.rs:17): move the
  * camera of a resident scene — the four vectors of camera.rs:52-63 — without touching its tables,
  * and render whole frames of it into a host buffer (internal device framebuffer, blocking). */
@@ -902,6 +946,8 @@ int rt_hip_group_set_flat_normals(RtHipGroup*, const double* normals, uint32_t n
 int rt_hip_group_set_flat_motion(RtHipGroup*, const double* move, uint32_t n_quads, uint32_t flags);
 /* rt_hip_scene_set_flat_lights on every rank, under the same two conditions. */
 int rt_hip_group_set_flat_lights(RtHipGroup*, const float* emit, uint32_t n_quads, uint32_t flags);
+/* rt_hip_scene_set_flat_images on every rank, under the same two conditions. */
+int rt_hip_group_set_flat_images(RtHipGroup*, const RtFlatImage* images, uint32_t n_quads, uint32_t flags);
 int rt_hip_group_render_to_host(RtHipGroup*, uint8_t* out_rgb8, RtStats* stats);
 /* the group's layout arithmetic as the library compiled it (no GPU needed): rt_tiles_stacked_row() with the group's
  * tile height; *tile_rows_out receives that height (2) */

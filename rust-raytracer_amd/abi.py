@@ -25,6 +25,20 @@ class RtQuad(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class RtFlatImage(C.Structure):
+    """an image on a flat primitive: (s, t) at q, q + u, q + v; a texture of the scene; the two wrap modes"""
+    _fields_ = [("uv", C.c_double * 6), ("tex_id", C.c_uint32), ("wrap_s", C.c_uint32), ("wrap_t", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RT_FLAT_IMAGE_NONE = 0xFFFFFFFF
+RT_WRAP_REPEAT, RT_WRAP_CLAMP = 0, 1
+
+
+def flat_image(tex_id=RT_FLAT_IMAGE_NONE, uv=(0.0, 0.0, 1.0, 0.0, 0.0, 1.0), wrap_s=RT_WRAP_REPEAT, wrap_t=RT_WRAP_REPEAT):
+    """an RtFlatImage; the defaults: no image / the unit square over the entry's frame, repeating"""
+    return RtFlatImage((C.c_double * 6)(*uv), tex_id, wrap_s, wrap_t, 0)
+
+
 RT_MAX_QUADS = 1024
 RT_MAX_FLAT_LIGHTS = 32
 RT_MAX_FLATS_BVH = 1 << 20   # with the structure of DESIGN.md §22 (rt_hip_scene_create_flats_bvh)

@@ -29,7 +29,8 @@ def _srcs(*rel):
 def build_host(force=False):
     out = os.path.join(HERE, "librt_host.so")
     src = _srcs("csrc/host/scene.cpp", "csrc/host/jpeg.cpp")
-    deps = src + _srcs("csrc/host/json.hpp", "csrc/common/rt_quad.h", "csrc/common/rt_flat_light.h") + [os.path.join(ROOT, "include/rt_abi.h")]
+    deps = src + _srcs("csrc/host/json.hpp", "csrc/common/rt_quad.h", "csrc/common/rt_flat_light.h", "csrc/common/rt_flat_normal.h",
+                      "csrc/common/rt_flat_image.h") + [os.path.join(ROOT, "include/rt_abi.h")]
     if force or _newer(out, deps):
         _run(["g++", *CXXFLAGS, "-shared", *src, "-o", out, "-lz", "-lpthread"])
     return out
@@ -41,7 +42,7 @@ def build_hip(force=False):
     out = os.path.join(HERE, "librt_hip.so")
     probe = os.path.join(HERE, "librt_hip_probe.so")
     deps = _srcs(*HIP_DEPS) + [os.path.join(ROOT, "include/rt_abi.h"), os.path.join(ROOT, "include/rt_abi_test.h"),
-                                 os.path.join(ROOT, "include/rt_abi_test_flat_light.h")]
+                                 os.path.join(ROOT, "include/rt_abi_test_flat_light.h"), os.path.join(ROOT, "include/rt_abi_test_flat_image.h")]
     # (beside the file times: the source hash the libraries on disk were built from — a checkout or a clock that does not move
     #  forward leaves times that say nothing)
     try:
@@ -102,7 +103,7 @@ HIP_DEPS = tuple(dict.fromkeys(u for _, u, _ in HIP_UNITS)) + (
     "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h", "csrc/hip/rt_grid_build.h",
     "csrc/hip/rt_flat_build.h",
     "csrc/common/rt_atan2.h", "csrc/common/rt_neg_log.h", "csrc/common/rt_solid.h", "csrc/common/rt_quad.h",
-    "csrc/common/rt_flat_normal.h", "csrc/common/rt_flat_motion.h", "csrc/common/rt_flat_light.h")
+    "csrc/common/rt_flat_normal.h", "csrc/common/rt_flat_motion.h", "csrc/common/rt_flat_light.h", "csrc/common/rt_flat_image.h")
 
 
 def kernel_src_hash():

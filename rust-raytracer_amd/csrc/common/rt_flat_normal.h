@@ -44,6 +44,15 @@ RT_QUAD_FN int rt_flat_normal_prepare(const double in[9], double out[9]) {
 // a record that has normals: its first vector is a unit vector, never all zero
 RT_QUAD_FN bool rt_flat_normal_present(const double rec[9]) { return !(rec[0] == 0.0 && rec[1] == 0.0 && rec[2] == 0.0); }
 
+// alpha and beta of p = P - Q in the entry's frame: the first steps above, shared with rt_flat_image.h so the two cannot drift
+RT_QUAD_FN void rt_flat_barycentric(const double u[3], const double v[3], const double w[3], const double p[3], double* alpha, double* beta) {
+  double c[3];
+  rt_quad_cross(p, v, c);
+  *alpha = rt_quad_dot(w, c);
+  rt_quad_cross(u, p, c);
+  *beta = rt_quad_dot(w, c);
+}
+
 // The hit normal of a segment of direction d that hit entry r at P; rec: the entry's 72-byte record.  Returns which fallbacks were taken.
 RT_QUAD_FN int rt_flat_normal_shade(const RtQuadRec& r, const double rec[9], const double d[3], const double P[3], double normal[3]) {
   const double N[3] = {r.n[0], r.n[1], r.n[2]};
@@ -52,12 +61,9 @@ RT_QUAD_FN int rt_flat_normal_shade(const RtQuadRec& r, const double rec[9], con
     for (int k = 0; k < 3; ++k) normal[k] = front ? N[k] : -N[k];
     return RT_SHADE_NO_NORMALS;
   }
-  double p[3], c[3], m[3], s[3];
+  double p[3], m[3], s[3], alpha, beta;
   for (int k = 0; k < 3; ++k) p[k] = P[k] - r.q[k];
-  rt_quad_cross(p, r.v, c);
-  const double alpha = rt_quad_dot(r.w, c);
-  rt_quad_cross(r.u, p, c);
-  const double beta = rt_quad_dot(r.w, c);
+  rt_flat_barycentric(r.u, r.v, r.w, p, &alpha, &beta);
   const double gamma = (1.0 - alpha) - beta;
   for (int k = 0; k < 3; ++k) m[k] = (rec[k] * gamma + rec[3 + k] * alpha) + rec[6 + k] * beta;
   const double mm = rt_quad_dot(m, m);

@@ -36,6 +36,7 @@
 #include "../common/rt_flat_normal.h"  // the one shading normal of a triangle
 #include "../common/rt_flat_light.h"   // the aim at an emitting flat primitive
 #include "../common/rt_flat_motion.h"  // the one flat primitive at a shutter time
+#include "../common/rt_flat_image.h"   // the one texel of a hit on a flat primitive with an image
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__ __forceinline__
@@ -191,6 +192,10 @@ constexpr uint32_t FLAT_MOTION_BIT = 0x20000000u;
 // Light spheres as object ids n_spheres + k, and their `mat` / `matc` records are of kind Light with the colour `emit`.  No header slot: the aim
 // reads the entry's own record.  Only the lit QUADS instantiations look for the bit.
 constexpr uint32_t FLAT_LIGHTS_BIT = 0x10000000u;
+// Images: a scene whose n_tris carries FLAT_IMAGES_BIT has the header too, and in it the table of 64-byte records
+// (rt_flat_image.h), one per entry in ENTRY order, and the scene's 4-byte texels (DevScene::tex4).  Only the QUADS instantiations look for
+// the bit, after a scatter that returned a ray.
+constexpr uint32_t FLAT_IMAGES_BIT = 0x08000000u;
 struct alignas(16) FlatBvhHeader {
   const FlatNode* nodes;
   const uint32_t* order;
@@ -199,7 +204,9 @@ struct alignas(16) FlatBvhHeader {
   uint32_t n_nodes, n_quads, id_base, pad0;
   const double* normals;  // [n_quads][9], null in a scene without shading normals
   const double* motion;   // [n_quads][4], null in a scene whose flat primitives do not move within a frame
-  uint64_t pad[8];
+  const RtFlatImageRec* images;  // [n_quads], null in a scene without images (§29)
+  const uint32_t* tex4;          // DevScene::tex4 where `images` is not null
+  uint64_t pad[6];
 };
 static_assert(sizeof(FlatBvhHeader) == sizeof(RtQuadRec), "the header takes the slot of one record in front of the records");
 // The rays the structure takes (DESIGN.md §22 "Preconditions"): every component finite, |o_k| <= 2^40, |d_k| <= 2^100 (a zero, a
@@ -1246,6 +1253,29 @@ RT_HD_COLD V3 flat_shading_normal(const RtQuadRec* q, const double* rec, V3 d, V
   (void)rt_flat_normal_shade(*q, rec, dd, pp, n);
   return v3(n[0], n[1], n[2]);
 }
+// The attenuation of a hit at P on entry k in a scene with images (FLAT_IMAGES_BIT; DESIGN.md §29, rt_flat_image.h): the texel, or a
+// negative red for an entry without an image — known after the record's first 16 bytes — and the caller keeps its own.  `origin` is the
+// entry's origin as object_surface<true> left it in g.cx, g.cy, g.cz: Q, or Q at the sample's shutter time in a MOTION kernel, so the frame
+// of the (s, t) moves with the entry.  Cold and by value like quads_hit — a pointer, an index, origin and P are fifteen argument registers
+// — so the cross products and the two floors stay out of the path loop's register budget.  Per lane: the lanes of a wave hit unrelated
+// entries; the record, the frame vectors and the texel are ordinary vector loads.
+RT_HD_COLD Rgb flat_image_albedo(const FlatBvhHeader* header, uint32_t k, V3 origin, V3 P) {
+  const RtFlatImageRec* rp = header->images + k;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 head = *reinterpret_cast<const uint4*>(rp);
+#else
+  const struct { uint32_t x, y, z, w; } head = {rp->texel_off, rp->W, rp->H, rp->wrap};
+#endif
+  if (head.y == 0u) return rgb(-1.0f, 0.0f, 0.0f);
+  RtFlatImageRec rec;
+  rec.texel_off = head.x; rec.W = head.y; rec.H = head.z; rec.wrap = head.w;
+  for (int c = 0; c < 6; ++c) rec.uv[c] = rp->uv[c];
+  const RtQuadRec* q = header->rec + k;
+  const double O[3] = {origin.x, origin.y, origin.z}, pp[3] = {P.x, P.y, P.z};
+  const double u[3] = {q->u[0], q->u[1], q->u[2]}, v[3] = {q->v[0], q->v[1], q->v[2]}, w[3] = {q->w[0], q->w[1], q->w[2]};
+  const RtFlatImageTexel x = rt_flat_image_texel(rec, O, u, v, w, pp);
+  return rgb_of_texel(header->tex4[x.index]);
+}
 // What a hit on object idx records and the SphereGeom scatter sees: a sphere's (surface_at), or in the QUADS arm for idx >= n_spheres
 // quad idx - n_spheres: no division, the stored N; its "centre" — the frame of a solid's pattern — is Q.
 template <bool QUADS, class Tables>
@@ -2110,6 +2140,12 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
     int st = scatter<MEDIUM, SOLID>(sc, L.ra, L.node, L.d, h, g, m, (uint32_t)idx, out_dir, att, L.n_tex_oob, rnd_pre, glass_u_pre);
     if (st == SCATTER_ABSORBED) { lane_finish_sample(sc, L, rgb(0.f, 0.f, 0.f)); return LANE_FINISHED; }       // :127-131
     if (st == SCATTER_EMIT) { lane_finish_sample(sc, L, rgb(att[0], att[1], att[2])); return LANE_FINISHED; }  // :124
+    if constexpr (QUADS) {  // (§29: an entry with an image attenuates by its texel; sc is a kernel argument: the bit is wave-uniform)
+      if ((sc.n_tris & FLAT_IMAGES_BIT) && (uint32_t)idx >= sc.n_spheres) {
+        const Rgb a = flat_image_albedo(reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, (uint32_t)idx - sc.n_spheres, v3(g.cx, g.cy, g.cz), h.point);
+        if (a.r >= 0.0f) { att[0] = a.r; att[1] = a.g; att[2] = a.b; }
+      }
+    }
     return lane_continue_main(sc, L, h.point, out_dir, zero3, att) ? LANE_FINISHED : LANE_CONTINUE;
   } else {
     // Lit scenes.  First decide what the hit MEANS for the lane; the heavy continuations — hand a colour back to the
@@ -2139,6 +2175,12 @@ RT_HD int lane_shade(const DevScene& sc, const Tables& tb, LaneT& L, int idx, do
         }
         act = light_ray ? ACT_RETURN : ACT_FINISH;
       } else {
+        if constexpr (QUADS) {  // (§29, as in the unlit arm; a pure function of the hit: a LANE_REPEAT looks the same texel up again)
+          if ((sc.n_tris & FLAT_IMAGES_BIT) && (uint32_t)idx >= sc.n_spheres) {
+            const Rgb a = flat_image_albedo(reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, (uint32_t)idx - sc.n_spheres, v3(g.cx, g.cy, g.cz), h.point);
+            if (a.r >= 0.0f) { att[0] = a.r; att[1] = a.g; att[2] = a.b; }
+          }
+        }
         // raytracer.rs:92-102: sample the lights?  Camera path: depth > max_depth-2 <=> k < 2 (and max_depth >= 2, usize
         // wrap); a light ray's own hit: the same test one level down, below the nesting cap
         bool sample = false;
@@ -2280,6 +2322,12 @@ RT_HD void aov_sample(const DevScene& sc, const Tables& tb, const Lane<false>& L
         const Rgb c = solid_albedo(h.point, v3(g.cx, g.cy, g.cz), sc.mat[best]);
         a[0] = c.r; a[1] = c.g; a[2] = c.b;
       } else if (m.kind != RT_MAT_LAMBERTIAN && m.kind != RT_MAT_METAL && !(MEDIUM && m.kind == RT_MAT_MEDIUM)) a[0] = a[1] = a[2] = 0.0f;
+      else if constexpr (QUADS) {  // (§29: the first-hit albedo of an entry with an image is its texel; an emitter was taken above)
+        if ((sc.n_tris & FLAT_IMAGES_BIT) && (uint32_t)best >= sc.n_spheres) {
+          const Rgb c = flat_image_albedo(reinterpret_cast<const FlatBvhHeader*>(sc.quads.rec) - 1, (uint32_t)best - sc.n_spheres, v3(g.cx, g.cy, g.cz), h.point);
+          if (c.r >= 0.0f) { a[0] = c.r; a[1] = c.g; a[2] = c.b; }
+        }
+      }
       acc[3] += 1.0 / closest;
       if (!(MEDIUM && m.kind == RT_MAT_MEDIUM)) { acc[4] += h.normal.x; acc[5] += h.normal.y; acc[6] += h.normal.z; }
       acc[7] += 1.0;

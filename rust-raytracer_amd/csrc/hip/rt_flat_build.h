@@ -238,5 +238,19 @@ struct NormalJob {
 };
 hipError_t normals(const NormalJob& j, hipStream_t stream);
 
+// Images (rt_hip_scene_set_flat_images): per entry, its 64-byte record by rt_flat_image.h rt_flat_image_prepare.  The status
+// block is prepare()'s with another meaning: bad_degenerate = the lowest refused entry or NONE, bad_finite = its RT_FLAT_IMAGE_BAD_* code (a
+// one-thread kernel behind the first looks the reason up again: one readback names entry and reason); mismatch = the entries that have an
+// image.  The records go into a spare table, like everything here.
+struct ImageJob {
+  uint32_t n = 0, n_textures = 0;
+  const RtFlatImage* in = nullptr;        // [n] the caller's
+  const RtFlatImageTex* tex = nullptr;    // [n_textures] the scene's textures (null without any)
+  const uint32_t* kind = nullptr;         // [n] the entries' own materials as created
+  RtFlatImageRec* out = nullptr;          // [n]
+  Status* status = nullptr;
+};
+hipError_t images(const ImageJob& j, hipStream_t stream);
+
 }  // namespace rtfb
 #endif

@@ -130,6 +130,37 @@ __global__ void __launch_bounds__(BLOCK) flat_normals_prepare(NormalJob j) {
   if (threadIdx.x == 0 && smooth) atomicAdd(&j.status->mismatch, smooth);
 }
 
+// per entry: its image record into the spare table (rt_flat_image.h: the host's bits); the lowest refused entry into bad_degenerate
+__global__ void __launch_bounds__(BLOCK) flat_images_prepare(ImageJob j) {
+  __shared__ uint32_t present;   // of this workgroup: one global atomic per workgroup
+  if (threadIdx.x == 0) present = 0u;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i < j.n) {
+    const RtFlatImage in = j.in[i];
+    RtFlatImageRec out;
+    const int kind = rt_flat_image_prepare(in, j.tex, j.n_textures, j.kind[i], &out);
+    if (kind > RT_FLAT_IMAGE_PRESENT) atomicMin(&j.status->bad_degenerate, i);
+    else {
+      uint4* o = reinterpret_cast<uint4*>(j.out + i);
+      double2* od = reinterpret_cast<double2*>(j.out + i);
+      o[0] = make_uint4(out.texel_off, out.W, out.H, out.wrap);
+      for (int k = 0; k < 3; ++k) od[1 + k] = make_double2(out.uv[2 * k], out.uv[2 * k + 1]);
+      if (kind == RT_FLAT_IMAGE_PRESENT) atomicAdd(&present, 1u);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && present) atomicAdd(&j.status->mismatch, present);
+}
+
+// one thread, behind flat_images_prepare on the same stream: why the lowest refused entry was refused, into bad_finite
+__global__ void flat_images_why(ImageJob j) {
+  const uint32_t k = j.status->bad_degenerate;
+  if (threadIdx.x != 0 || blockIdx.x != 0 || k >= j.n) return;
+  RtFlatImageRec out;
+  j.status->bad_finite = (uint32_t)rt_flat_image_prepare(j.in[k], j.tex, j.n_textures, j.kind[k], &out);
+}
+
 uint32_t blocks_for(uint32_t n) { return (n + BLOCK - 1) / BLOCK; }
 
 }  // namespace
@@ -139,6 +170,17 @@ hipError_t normals(const NormalJob& j, hipStream_t stream) {
   if ((e = hipMemsetAsync(j.status, 0xFF, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;   // NONE, NONE
   if ((e = hipMemsetAsync(&j.status->mismatch, 0, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;
   if (j.n) hipLaunchKernelGGL(flat_normals_prepare, dim3(blocks_for(j.n)), dim3(BLOCK), 0, stream, j);
+  return hipGetLastError();
+}
+
+hipError_t images(const ImageJob& j, hipStream_t stream) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(j.status, 0xFF, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;   // no refused entry
+  if ((e = hipMemsetAsync(&j.status->mismatch, 0, 2 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+  if (j.n) {
+    hipLaunchKernelGGL(flat_images_prepare, dim3(blocks_for(j.n)), dim3(BLOCK), 0, stream, j);
+    hipLaunchKernelGGL(flat_images_why, dim3(1), dim3(1), 0, stream, j);
+  }
   return hipGetLastError();
 }
 

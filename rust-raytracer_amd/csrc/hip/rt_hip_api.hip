@@ -196,11 +196,17 @@ struct RtHipScene {
       // all -0.0 dv table [n_spheres][4] the MOTION kernels read in a scene whose only movers are flat primitives (§14: a static sphere's bits).
       DevBuf motion, motion_spare, still;
       uint32_t n_moving = 0;
+      // images (rt_hip_scene_set_flat_images): [n_quads] the records of rt_flat_image.h and the table the next call builds into;
+      // n_images: the entries that have one, 0: no table — the scene is one that never had any.  tex_table: what the prepare kernel knows of
+      // the scene's textures ([n_textures] RtFlatImageTex, uploaded at creation); tex4_dev: Resident::tex4, which the header names beside the records
+      DevBuf images, images_spare, tex_table;
+      uint32_t n_images = 0, n_textures = 0;
+      const uint32_t* tex4_dev = nullptr;
       // what a refit needs of the structure as built (rt_flat_build.h FlatTopology), on the device and on the host: topo's vectors are the staging of their uploads
       DevBuf boxed, leaves, levels;
       rtc::FlatTopology topo;
       // the device code's: the geometry as uploaded, a box per entry, the status block; the device build's (§26) items, range extents, sort storage
-      struct Scratch { DevBuf quv, box, status, item, extent, sort_tmp, move, rec_tmp; } scratch;
+      struct Scratch { DevBuf quv, box, status, item, extent, sort_tmp, move, rec_tmp, kind; } scratch;
       // the device build starts from the boxed entries in index order: resident from the first device build after each host build on
       DevBuf start;
       std::vector<uint32_t> keep_start;
@@ -213,7 +219,7 @@ struct RtHipScene {
       rtc::FlatBvhHeader keep_header{};
       uint32_t refits = 0;     // the updates applied by refit since the structure was last built
       // the first record of a generation as the kernels see it (DevScene::quads.rec): behind the header, where there is a structure
-      uint32_t header_recs() const { return (n_nodes || n_normals || n_moving) ? 1u : 0u; }  // the record slots the header takes (§25, §27: the normals' and the motion's pointers live in it)
+      uint32_t header_recs() const { return (n_nodes || n_normals || n_moving || n_images) ? 1u : 0u; }  // the record slots the header takes (§25, §27, §29: the normals', the motion's and the images' pointers live in it)
       RtQuadRec* first_rec(const Tables& t) const { return t.rec.get<RtQuadRec>() + header_recs(); }
       size_t rec_bytes() const { return ((size_t)n_quads + header_recs()) * sizeof(RtQuadRec); }  // of Tables::rec
       const double* dev_lim() const { return n_tris ? lim.get<const double>() : nullptr; }
@@ -225,6 +231,8 @@ struct RtHipScene {
         h.n_nodes = t_n_nodes; h.n_quads = n_quads; h.id_base = id_base;
         h.normals = n_normals ? normals.get<const double>() : nullptr;
         h.motion = n_moving ? motion.get<const double>() : nullptr;
+        h.images = n_images ? images.get<const RtFlatImageRec>() : nullptr;
+        h.tex4 = n_images ? tex4_dev : nullptr;
         return h;
       }
     } flat;
@@ -264,7 +272,8 @@ struct RtHipScene {
       d.n_tris = flat.n_tris | (flat.n_nodes ? rtc::FLAT_BVH_BIT : 0u) |  // (§22: the bit says that the header lies in front of quads.rec[0])
                  (flat.n_normals ? rtc::FLAT_NORMALS_BIT : 0u) |            // (§25: ... and that it names a table of shading normals)
                  (flat.n_moving ? rtc::FLAT_MOTION_BIT : 0u) |              // (§27: ... and a table of motion records)
-                 (flat_lights.empty() ? 0u : rtc::FLAT_LIGHTS_BIT);         // (§28: the light list names emitting flat primitives)
+                 (flat_lights.empty() ? 0u : rtc::FLAT_LIGHTS_BIT) |        // (§28: the light list names emitting flat primitives)
+                 (flat.n_images ? rtc::FLAT_IMAGES_BIT : 0u);               // (§29: the header names a table of image records and the texels)
       // (§28: the light count and what fill_dev_scene derives from it, by its operations: emission can change them after creation)
       d.n_lights = n_lights();
       d.light_thr[0] = 1.0 - (double)d.n_lights * 0.1;
@@ -654,6 +663,19 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
     if ((rc = upload(r->sky, sky)) != RT_OK) return rc;
   }
   r->keep_tex4.swap(t.tex4); r->keep_sky4.swap(t.sky4);
+  if (n_quads && scene->n_textures) {  // (§29: what rt_hip_scene_set_flat_images' prepare kernel knows of the textures; build_texels' layout)
+    std::vector<RtFlatImageTex> table(scene->n_textures);
+    uint64_t before = 0;
+    for (uint32_t i = 0; i < scene->n_textures; ++i) {
+      const RtTexture& x = scene->textures[i];
+      table[i] = rt_flat_image_tex(x.width, x.height, x.nbytes, before);
+      // (the first texture that does not fit ends the expanded run: every later one is outside too)
+      before = (table[i].ok == RT_FLAT_IMAGE_TEX_FAR || before + x.nbytes / 3 >= (1ull << 31)) ? (1ull << 31) : before + x.nbytes / 3;
+    }
+    if ((rc = upload(f.tex_table, table)) != RT_OK) return rc;
+    f.n_textures = scene->n_textures;
+  }
+  f.tex4_dev = r->tex4.get<const uint32_t>();
   pc.mark("scene.upload_texels");
   RtHipScene* s = new RtHipScene;
   s->device = device;
@@ -1286,6 +1308,7 @@ extern "C" int64_t rt_hip_scene_query(const RtHipScene* s, const char* key) {
   if (!std::strcmp(key, "flat_bvh")) return (int64_t)s->res->flat.n_nodes;  // nodes of the structure over the flat primitives; 0: none
   if (!std::strcmp(key, "flat_motion")) return (int64_t)s->res->flat.n_moving;  // entries that move within the frame; 0: none
   if (!std::strcmp(key, "flat_lights")) return (int64_t)s->res->flat_lights.size();  // entries that emit; "n_lights" counts them too
+  if (!std::strcmp(key, "flat_images")) return (int64_t)s->res->flat.n_images;   // entries that carry an image; 0: none
   if (!std::strcmp(key, "flat_normals")) return (int64_t)s->res->flat.n_normals;  // entries that carry shading normals; 0: none
   if (!std::strcmp(key, "flat_refits")) return (int64_t)s->res->flat.refits;  // updates applied by refit since the structure was last built
   if (!std::strcmp(key, "flat_build")) return (int64_t)s->opt.flat_build;  // the option: 1: a rebuild the caller asks for runs on the device
@@ -2038,7 +2061,7 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
   // (§27) with_move: this update makes a motion table; slot: the record slots the header takes in the spare generation — one for sure while
   // a motion table may come out of it (a scan scene that ends up without one is compacted after the readback)
   const bool with_move = set_move || f.n_moving != 0u;
-  const uint32_t slot = (f.n_nodes || f.n_normals || with_move) ? 1u : 0u;
+  const uint32_t slot = (f.n_nodes || f.n_normals || f.n_images || with_move) ? 1u : 0u;
   uint32_t moving = set_move ? 0u : f.n_moving;   // the entries that move once this update is in: known after the readback
   if ((rc = room(spare.rec, ((size_t)n + slot) * sizeof(RtQuadRec))) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
       (!set_move && !on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK) ||
@@ -2156,7 +2179,7 @@ int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint3
     RT_HIP_TRY(put_header(n_nodes, spare.order));
     pc.mark("update_flats.upload_structure");
   }
-  if (slot && !(f.n_nodes || f.n_normals || moving)) {  // (§27: a scan scene that lost its last table loses the header's slot: the records alone)
+  if (slot && !(f.n_nodes || f.n_normals || f.n_images || moving)) {  // (§27: a scan scene that lost its last table loses the header's slot: the records alone)
     if ((rc = room(fb.rec_tmp, (size_t)n * sizeof(RtQuadRec))) != RT_OK) return rc;
     RT_HIP_TRY(hipMemcpy(fb.rec_tmp.p, j.rec, (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
     spare.rec.swap(fb.rec_tmp);
@@ -2226,7 +2249,7 @@ int scene_set_flat_normals(RtHipScene* s, const double* normals, uint32_t n_quad
     count = st.mismatch;
   }
   // the record slots the header takes before and after: they differ only in a scan scene that gains or loses its table
-  const uint32_t had = f.header_recs(), has = (f.n_nodes || count || f.n_moving) ? 1u : 0u;
+  const uint32_t had = f.header_recs(), has = (f.n_nodes || count || f.n_moving || f.n_images) ? 1u : 0u;
   RtHipScene::Resident::Flats::Tables& spare = f.spare;
   if (has != had) {
     if ((rc = room(spare.rec, ((size_t)n + has) * sizeof(RtQuadRec))) != RT_OK) return rc;
@@ -2312,6 +2335,74 @@ extern "C" int rt_hip_scene_set_flat_lights(RtHipScene* s, const float* emit, ui
   return scene_set_flat_lights(s, emit, n_quads, flags, false);
 }
 
+// ------------------------------------------------------------------------------ images on the flat primitives of a resident scene
+namespace {
+// As the shading normals: the records are made on the device from host or device input alike (rt_flat_build.hip flat_images_prepare), and the
+// table's address — with the texels' — travels in the FlatBvhHeader in front of the records: a scan scene gains that slot with its first
+// image and loses it with the last.  Everything that can fail runs before anything the scene renders with changes.
+int scene_set_flat_images(RtHipScene* s, const RtFlatImage* images, uint32_t n_quads, uint32_t flags, bool views_follow) {
+  if (!s) return fail(RT_ERR_INVALID, "null argument");
+  if (flags & ~RT_UPDATE_FLATS_DEVICE) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: unknown flag");
+  RtHipScene::Resident& r = *s->res;
+  RtHipScene::Resident::Flats& f = r.flat;
+  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: the scene has no flat primitive");
+  if (n_quads != f.n_quads)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
+  if (!views_follow && s->res.use_count() > 1)
+    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: the scene's tables are shared with a view (a group sets them through rt_hip_group_set_flat_images)");
+  const bool on_device = images && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
+  if (on_device)
+    if (const int refused = check_aligned(images, 8, "rt_hip_scene_set_flat_images: images must be 8-byte aligned")) return refused;
+  int rc;
+  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
+  const uint32_t n = n_quads;
+  uint32_t count = 0;
+  if (images) {
+    RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
+    static_assert(sizeof(RtFlatImage) == 64 && sizeof(RtFlatImageRec) == 64, "an image entry and its record are 64 bytes");
+    if ((rc = room(f.images_spare, (size_t)n * sizeof(RtFlatImageRec))) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
+        (rc = room(fb.kind, (size_t)n * sizeof(uint32_t))) != RT_OK || (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK))
+      return rc;
+    if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, images, (size_t)n * sizeof(RtFlatImage), hipMemcpyHostToDevice));
+    std::vector<uint32_t> kind(n);   // (the entries' own materials as created: an emitter's resident record says Light meanwhile)
+    for (uint32_t k = 0; k < n; ++k) kind[k] = r.keep_flat_matc[k].kind;
+    RT_HIP_TRY(hipMemcpy(fb.kind.p, kind.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    rtfb::ImageJob j;
+    j.n = n; j.n_textures = f.n_textures; j.in = on_device ? images : fb.quv.get<const RtFlatImage>();
+    j.tex = f.n_textures ? f.tex_table.get<const RtFlatImageTex>() : nullptr; j.kind = fb.kind.get<const uint32_t>();
+    j.out = f.images_spare.get<RtFlatImageRec>(); j.status = fb.status.get<rtfb::Status>();
+    RT_HIP_TRY(rtfb::images(j, nullptr));
+    rtfb::Status st;
+    RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the lowest refused entry and why, the count
+    if (st.bad_degenerate != rtfb::NONE) return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": " + rt_flat_image_why((int)st.bad_finite));
+    count = st.mismatch;
+  }
+  if (!count && !f.n_images) return RT_OK;   // no entry has an image and none shall: the scene is what it was
+  // the record slots the header takes before and after: they differ only in a scan scene that gains or loses its table
+  const uint32_t had = f.header_recs(), has = (f.n_nodes || f.n_normals || f.n_moving || count) ? 1u : 0u;
+  RtHipScene::Resident::Flats::Tables& spare = f.spare;
+  if (has != had) {
+    if ((rc = room(spare.rec, ((size_t)n + has) * sizeof(RtQuadRec))) != RT_OK) return rc;
+    RT_HIP_TRY(hipMemcpy(spare.rec.get<RtQuadRec>() + has, f.first_rec(f.live), (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
+    RT_HIP_TRY(hipDeviceSynchronize());
+  }
+  // everything is built: swap it in
+  if (has != had) f.live.rec.swap(spare.rec);
+  if (count) f.images.swap(f.images_spare);
+  f.n_images = count;
+  if (has) {
+    f.keep_header = f.header(f.live, f.n_nodes, f.live.order, s->host.n_spheres);
+    RT_HIP_TRY(hipMemcpy(f.live.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice));
+  }
+  RT_HIP_TRY(hipDeviceSynchronize());
+  return adopt_tables(s, Moved::flats);
+}
+}  // namespace
+
+extern "C" int rt_hip_scene_set_flat_images(RtHipScene* s, const RtFlatImage* images, uint32_t n_quads, uint32_t flags) {
+  return scene_set_flat_images(s, images, n_quads, flags, false);
+}
+
 // diagnostics: one resident table as the kernels read it
 extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* out, size_t cap, size_t* needed) {
   if (!s || !name) return fail(RT_ERR_INVALID, "null argument");
@@ -2333,6 +2424,7 @@ extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* o
   else if (!std::strcmp(name, "flat_bvh")) { src = f.live.nodes.p; bytes = (size_t)f.n_nodes * sizeof(rtc::FlatNode); }
   else if (!std::strcmp(name, "flat_motion")) { src = f.motion.p; bytes = f.n_moving ? (size_t)f.n_quads * 32u : 0; }
   else if (!std::strcmp(name, "flat_normals")) { src = f.normals.p; bytes = f.n_normals ? (size_t)f.n_quads * 72u : 0; }
+  else if (!std::strcmp(name, "flat_images")) { src = f.images.p; bytes = f.n_images ? (size_t)f.n_quads * sizeof(RtFlatImageRec) : 0; }
   else if (!std::strcmp(name, "flat_lights")) { src = s->res->flat_lights.data(); bytes = s->res->flat_lights.size() * sizeof(uint32_t); host = true; }  // (§28: the emitters' entry indices in light order)
   else if (!std::strcmp(name, "lights")) { src = s->res->lights.p; bytes = (size_t)s->res->n_lights() * sizeof(uint32_t); }
   else if (!std::strcmp(name, "mat")) { src = s->res->mat.p; bytes = ((size_t)s->host.n_spheres + f.n_quads) * sizeof(rtc::SphereMat); }
@@ -2513,6 +2605,50 @@ extern "C" int rt_hip_flat_light_aim_probe(const double* d_quv, const int32_t* d
   if (block < 1u || block > 1024u) return fail(RT_ERR_INVALID, "block must be 1 .. 1024");
   if (!n) return RT_OK;
   hipLaunchKernelGGL(rtk::rt_flat_light_aim_probe, dim3((n + block - 1u) / block), dim3(block), 0, (hipStream_t)stream, d_quv, d_triangle, d_words, d_T, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// The device form of the image lookup (include/rt_abi_test_flat_image.h), one hit per thread.
+namespace rtk {
+// hit i at P[i] on entry k[i] whose origin is origin[i]: what the arm in lane_shade does — the header in front of the records, the cold
+// flat_image_albedo — and the attenuation comes back; a k outside the entries gives three NaNs
+__global__ void rt_flat_image_probe(const rtc::DevScene sc, const uint32_t* k, const double* origin, const double* P, float* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  rtc::Rgb c = rtc::rgb((float)rtc::rt_nan(), (float)rtc::rt_nan(), (float)rtc::rt_nan());
+  if ((sc.n_tris & rtc::FLAT_IMAGES_BIT) && k[i] < sc.n_quads)
+    c = rtc::flat_image_albedo(reinterpret_cast<const rtc::FlatBvhHeader*>(sc.quads.rec) - 1, k[i], rtc::v3(origin[3u * i], origin[3u * i + 1u], origin[3u * i + 2u]),
+                               rtc::v3(P[3u * i], P[3u * i + 1u], P[3u * i + 2u]));
+  out[3u * i] = c.r; out[3u * i + 1u] = c.g; out[3u * i + 2u] = c.b;
+}
+// rt_flat_image_texel of hit i on ITS OWN record, frame and point: the header's arithmetic on crafted tables
+__global__ void rt_flat_image_texel_probe(const RtFlatImageRec* rec, const double* ouvw, const double* P, uint32_t* texel, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const RtFlatImageRec r = rec[i];
+  if (r.W == 0u || r.H == 0u) { texel[3u * i] = texel[3u * i + 1u] = texel[3u * i + 2u] = 0xFFFFFFFFu; return; }
+  const double* f = ouvw + 12u * (size_t)i;
+  const RtFlatImageTexel x = rt_flat_image_texel(r, f, f + 3, f + 6, f + 9, P + 3u * (size_t)i);
+  texel[3u * i] = x.col; texel[3u * i + 1u] = x.row; texel[3u * i + 2u] = x.index;
+}
+}  // namespace rtk
+extern "C" int rt_hip_flat_image_probe(RtHipScene* s, const uint32_t* d_k, const double* d_origin, const double* d_P, float* d_rgb, uint32_t n, void* stream) {
+  if (!s || !d_k || !d_origin || !d_P || !d_rgb) return fail(RT_ERR_INVALID, "null argument");
+  if (!s->res->flat.n_images) return fail(RT_ERR_INVALID, "the scene has no flat primitive with an image");
+  if (!n) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_flat_image_probe, dim3((n + 191) / 192), dim3(192), 0, (hipStream_t)stream, s->dev, d_k, d_origin, d_P, d_rgb, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+// (block: the launch's workgroup size, 1 .. 1024; a test passes one that is not a multiple of 64)
+extern "C" int rt_hip_flat_image_texel_probe(const void* d_rec, const double* d_ouvw, const double* d_P, uint32_t* d_texel, uint32_t n, uint32_t block, void* stream) {
+  if (!d_rec || !d_ouvw || !d_P || !d_texel) return fail(RT_ERR_INVALID, "null argument");
+  if (block < 1u || block > 1024u) return fail(RT_ERR_INVALID, "block must be 1 .. 1024");
+  if (!n) return RT_OK;
+  hipLaunchKernelGGL(rtk::rt_flat_image_texel_probe, dim3((n + block - 1u) / block), dim3(block), 0, (hipStream_t)stream,
+                     static_cast<const RtFlatImageRec*>(d_rec), d_ouvw, d_P, d_texel, n);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }

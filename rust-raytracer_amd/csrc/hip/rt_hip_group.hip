@@ -642,6 +642,22 @@ extern "C" int rt_hip_group_set_flat_lights(RtHipGroup* g, const float* emit, ui
   return RT_OK;
 }
 
+// images on the flat primitives of every rank's scene (rt_hip_scene_set_flat_images), under the same two conditions
+extern "C" int rt_hip_group_set_flat_images(RtHipGroup* g, const RtFlatImage* images, uint32_t n_quads, uint32_t flags) {
+  if (!g) return fail(RT_ERR_INVALID, "null argument");
+  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_images: a submitted frame is uncollected");
+  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
+    for (uint32_t r = 1; r < g->G; ++r)
+      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_images: device memory serves the ranks of one device only");
+  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: a bad table changes no rank)
+    int rc = scene_set_flat_images(g->scene[r], images, n_quads, flags, true);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
+    if (rc != RT_OK) return rc;
+  }
+  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
+  return RT_OK;
+}
+
 namespace rtg { void prepare_staging(RtHipGroup* g, int n_frames); }
 extern "C" int rt_hip_group_set_option(RtHipGroup* g, const char* key, int64_t value) {
   if (!g || !key) return fail(RT_ERR_INVALID, "null argument");

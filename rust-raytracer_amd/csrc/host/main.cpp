@@ -71,6 +71,10 @@ int set_motion(RtHipGroup* h, const double* m, uint32_t k) { return rt_hip_group
 // creation too (rt_hip_scene_set_flat_lights / rt_hip_group_set_flat_lights), before the motion: an emitter may not move.
 int set_lights(RtHipScene* h, const float* e, uint32_t k) { return rt_hip_scene_set_flat_lights(h, e, k, 0u); }
 int set_lights(RtHipGroup* h, const float* e, uint32_t k) { return rt_hip_group_set_flat_lights(h, e, k, 0u); }
+// Images: a file whose quads, triangles, boxes or meshes carry "image" (rt_scene_flat_images) has them set right after
+// creation too (rt_hip_scene_set_flat_images / rt_hip_group_set_flat_images); they ride their entries through every later update.
+int set_images(RtHipScene* h, const RtFlatImage* im, uint32_t k) { return rt_hip_scene_set_flat_images(h, im, k, 0u); }
+int set_images(RtHipGroup* h, const RtFlatImage* im, uint32_t k) { return rt_hip_group_set_flat_images(h, im, k, 0u); }
 void destroy(RtHipScene* h) { rt_hip_scene_destroy(h); }
 void destroy(RtHipGroup* h) { rt_hip_group_destroy(h); }
 template <class Handle, class Where>
@@ -84,6 +88,9 @@ int create(const Run& r, Where where, Handle** out, int (*moving)(const RtScene*
   uint32_t n_normals = 0;
   const double* normals = rt_scene_flat_normals(r.sf, &n_normals);
   if (rc == RT_OK && normals && (rc = set_normals(*out, normals, n_normals)) != RT_OK) { destroy(*out); *out = nullptr; }
+  uint32_t n_images = 0;
+  const RtFlatImage* images = rt_scene_flat_images(r.sf, &n_images);
+  if (rc == RT_OK && images && (rc = set_images(*out, images, n_images)) != RT_OK) { destroy(*out); *out = nullptr; }
   uint32_t n_emit = 0;
   const float* emit = rt_scene_flat_emit(r.sf, &n_emit);
   if (rc == RT_OK && emit && (rc = set_lights(*out, emit, n_emit)) != RT_OK) { destroy(*out); *out = nullptr; }
@@ -215,6 +222,15 @@ struct FlatFrames {
     char path[4096];
     std::snprintf(path, sizeof path, "%s%03d.json", prefix.c_str(), f);
     const std::string which = "frame " + std::to_string(f) + " (" + path + "): ";
+    // (§29: the images are the base file's and stay; a frame file brings none — looked for in its text, before the loader would decode a JPEG
+    //  per frame: the quoted word is a key of ours alone)
+    if (std::FILE* fp = std::fopen(path, "rb")) {
+      std::string text;
+      char buf[65536];
+      for (size_t got; (got = std::fread(buf, 1, sizeof buf, fp)) > 0;) text.append(buf, got);
+      std::fclose(fp);
+      if (text.find("\"image\"") != std::string::npos) return which + "a frame file takes no `image` (the images are the base file's)";
+    }
     RtSceneFile* ff = nullptr;
     if (rt_scene_load_file(path, &ff) != RT_OK) return which + rt_host_last_error();
     uint32_t n = 0;

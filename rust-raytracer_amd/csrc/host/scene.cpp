@@ -24,6 +24,7 @@
 #include "../../../include/rt_abi.h"
 #include "../common/rt_quad.h"
 #include "../common/rt_flat_light.h"
+#include "../common/rt_flat_image.h"
 #include "json.hpp"
 
 extern "C" const char* rt_jpeg_last_error(void);
@@ -215,6 +216,11 @@ struct RtSceneFile {
   std::vector<float> emit;
   std::vector<uint8_t> has_emit;
   size_t n_emit = 0;
+  // images: [quads.size()] the RtFlatImage of every entry, tex_id RT_FLAT_IMAGE_NONE for an entry without; has_uvs: the
+  // entries whose (s, t) the file wrote (rt_scene_to_json writes "uvs" for those); n_images: the entries with an image (0: rt_scene_flat_images is NULL)
+  std::vector<RtFlatImage> images;
+  std::vector<uint8_t> has_uvs;
+  size_t n_images = 0;
   // the structure over the flat primitives: the file's top-level "flat_bvh": true (rt_scene_flat_bvh; written back only when true)
   bool flat_bvh = false;
   // where the load went (rt_scene_load_timings): reading the file, parsing the JSON text, the longest JPEG decode (they run
@@ -262,6 +268,10 @@ void start_all_decodes(const Value& root, DecodeJobs& jobs) {
   if (!objs || objs->kind != Value::Array) return;
   for (auto& o : objs->items) {
     if (o->kind != Value::Object) continue;
+    if (const Value* im = o->find("image"))   // (§29: the picture on a flat primitive)
+      if (im->kind == Value::Object)
+        if (const Value* px = im->find("pixels"))
+          if (px->kind == Value::String) start_decode(jobs, px->text);
     const Value* m = o->find("material");
     if (!m || m->kind != Value::Object || m->members.size() != 1 || m->members[0].first != "Texture") continue;
     const Value& body = *m->members[0].second;
@@ -487,7 +497,41 @@ void build_scene(const Value& root, RtSceneFile& sf) {
       if (int(is_box) + int(is_tri) + int(is_mesh) > 1) bad("mixed keys: only one of `box`, `triangle`, `mesh`");
       if (o.find("center1")) bad(is_tri || is_mesh ? std::string("a ") + form + " cannot move (center1)" : std::string("a quad cannot move (center1)"));
       const Value* f[6] = {};
-      struct Flat { double g[9]; uint32_t shape; double nrm[9]; bool smooth; };
+      struct Flat { double g[9]; uint32_t shape; double nrm[9]; bool smooth; double uv[6]; };
+      // images: the optional "image" and "uvs" of the object map (a mesh's "uvs" lie inside "mesh": one pair per vertex)
+      const Value *image_v = nullptr, *uvs_v = nullptr;
+      if (o.kind == Value::Object)
+        for (auto& mb : o.members) {
+          if (mb.first == "image") {
+            if (image_v) bad("duplicate field `image`");
+            image_v = mb.second.get();
+          }
+          if (mb.first == "uvs") {
+            if (uvs_v) bad("duplicate field `uvs`");
+            uvs_v = mb.second.get();
+          }
+        }
+      auto as_uv = [&](const Value& v, const std::string& what, double out[2]) {
+        if (v.kind != Value::Array || v.items.size() != 2) bad(what + ": expected a pair [s, t]");
+        for (int k = 0; k < 2; ++k) {
+          try {
+            out[k] = as_f64(*v.items[k], "a texture coordinate");
+          } catch (const SchemaError& e) {
+            bad(what + ": " + e.msg);
+          }
+          if (!rt_quad_finite(out[k])) bad(what + ": a texture coordinate must be finite");
+        }
+      };
+      bool has_uvs = false;
+      double uv3[6] = {0.0, 0.0, 1.0, 0.0, 0.0, 1.0};   // (Q, Q + u, Q + v: the default, the unit square over the entry's frame)
+      if (uvs_v) {
+        if (is_box) bad("uvs: a box takes no uvs (each face takes the default)");
+        if (is_mesh) bad("uvs: a mesh takes its uvs inside `mesh`, one pair per vertex");
+        if (!image_v) bad("uvs: `uvs` without `image`");
+        if (uvs_v->kind != Value::Array || uvs_v->items.size() != 3) bad("uvs: expected 3 uvs");
+        for (int i = 0; i < 3; ++i) as_uv(*uvs_v->items[i], "uv " + std::to_string(i), uv3 + 2 * i);
+        has_uvs = true;
+      }
       // shading normals: a vector as written, finite and not all zero; prepare normalises it
       auto as_normal = [&](const Value& v, const std::string& what, double out[3]) {
         try {
@@ -515,7 +559,7 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           if (!(mn[k] < mx[k])) bad("box: min must be below max on every axis");
         double six[6][9];
         rt_box_quads(mn, mx, six);
-        for (int i = 0; i < 6; ++i) { Flat fl{}; std::memcpy(fl.g, six[i], sizeof fl.g); fl.shape = RT_QUAD_SHAPE_PARALLELOGRAM; geo.push_back(fl); label.push_back("quad"); }
+        for (int i = 0; i < 6; ++i) { Flat fl{}; std::memcpy(fl.g, six[i], sizeof fl.g); fl.shape = RT_QUAD_SHAPE_PARALLELOGRAM; std::memcpy(fl.uv, uv3, sizeof fl.uv); geo.push_back(fl); label.push_back("quad"); }
         mat_v = f[1];
       } else if (is_tri || is_mesh) {
         // na, nb, nc: the normals at the three corners, or all null
@@ -524,6 +568,7 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           Flat fl{};
           for (int k = 0; k < 3; ++k) { fl.g[k] = a[k]; fl.g[3 + k] = b[k] - a[k]; fl.g[6 + k] = c[k] - a[k]; }
           fl.shape = RT_QUAD_SHAPE_TRIANGLE;
+          std::memcpy(fl.uv, uv3, sizeof fl.uv);   // (a "triangle": the three pairs are a's, b's, c's — Q, Q + u, Q + v; a mesh face: set below)
           fl.smooth = na != nullptr;
           if (na)
             for (int k = 0; k < 3; ++k) { fl.nrm[k] = na[k]; fl.nrm[3 + k] = nb[k]; fl.nrm[6 + k] = nc[k]; }
@@ -556,6 +601,24 @@ void build_scene(const Value& root, RtSceneFile& sf) {
             vnorm.resize(3 * mv[2]->items.size());
             for (size_t i = 0; i < mv[2]->items.size(); ++i) as_normal(*mv[2]->items[i], "mesh normal " + std::to_string(i), &vnorm[3 * i]);
           }
+          std::vector<double> vuv;   // (§29: one (s, t) per vertex)
+          {
+            const Value* muv = nullptr;
+            for (auto& mb : f[0]->members)
+              if (mb.first == "uvs") {
+                if (muv) bad("duplicate field `uvs`");
+                muv = mb.second.get();
+              }
+            if (muv && !image_v) bad("mesh.uvs: `uvs` without `image`");
+            if (image_v && !muv) bad("mesh: an `image` needs `uvs`, one pair per vertex");
+            if (muv) {
+              if (muv->kind != Value::Array || muv->items.size() != mv[0]->items.size())
+                bad("mesh.uvs: expected " + std::to_string(mv[0]->items.size()) + " uvs");
+              vuv.resize(2 * muv->items.size());
+              for (size_t i = 0; i < muv->items.size(); ++i) as_uv(*muv->items[i], "mesh uv " + std::to_string(i), &vuv[2 * i]);
+              has_uvs = true;
+            }
+          }
           std::vector<double> vert(3 * mv[0]->items.size());
           std::vector<size_t> face_ix;   // (smooth: the faces' vertex indices, three per face)
           for (size_t i = 0; i < mv[0]->items.size(); ++i) {
@@ -582,6 +645,8 @@ void build_scene(const Value& root, RtSceneFile& sf) {
             }
             if (mv[2]) from_corners(&vert[3 * ix[0]], &vert[3 * ix[1]], &vert[3 * ix[2]], fname, &vnorm[3 * ix[0]], &vnorm[3 * ix[1]], &vnorm[3 * ix[2]]);
             else from_corners(&vert[3 * ix[0]], &vert[3 * ix[1]], &vert[3 * ix[2]], fname);
+            if (!vuv.empty())
+              for (int c = 0; c < 3; ++c) { geo.back().uv[2 * c] = vuv[2 * ix[c]]; geo.back().uv[2 * c + 1] = vuv[2 * ix[c] + 1]; }
             if (smooth) face_ix.insert(face_ix.end(), ix, ix + 3);
           }
           if (smooth) {  // in face order, component-wise, one f64 add per face; unnormalised
@@ -627,6 +692,7 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           for (int i = 0; i < 3; ++i) as_normal(*nv->items[i], "normal " + std::to_string(i), fl.nrm + 3 * i);
           fl.smooth = true;
         }
+        std::memcpy(fl.uv, uv3, sizeof fl.uv);
         geo.push_back(fl); label.push_back(fl.shape == RT_QUAD_SHAPE_TRIANGLE ? "triangle" : "quad");
         mat_v = f[3];
       }
@@ -676,6 +742,32 @@ void build_scene(const Value& root, RtSceneFile& sf) {
           if (m.members[0].first == k) bad(std::string("a quad cannot be a ") + k + " (a quad may be Lambertian, Metal, Glass, Checker or Noise)");
       RtSphere mat{};
       parse_material(m, mat, nullptr);
+      // images: {"pixels": path, "wrap": "repeat" | "clamp" | [ws, wt]}; the file is a Texture material's (load_texture)
+      RtFlatImage image{};
+      image.tex_id = RT_FLAT_IMAGE_NONE;
+      if (image_v) {
+        const Value* iv[2] = {};
+        try {
+          struct_fields(*image_v, "image", {"pixels", "wrap"}, iv, {false, true});
+        } catch (const SchemaError& e) {
+          bad("image: " + e.msg);
+        }
+        if (iv[0]->kind != Value::String) bad("image.pixels: expected a string");
+        auto wrap_of = [&](const Value& v) -> uint32_t {
+          if (v.kind == Value::String && v.text == "repeat") return RT_WRAP_REPEAT;
+          if (v.kind == Value::String && v.text == "clamp") return RT_WRAP_CLAMP;
+          bad("image.wrap: unknown wrap" + (v.kind == Value::String ? " `" + v.text + "`" : std::string()) + ", expected one of `repeat`, `clamp`");
+          return 0u;
+        };
+        if (iv[1]) {
+          if (iv[1]->kind == Value::Array) {
+            if (iv[1]->items.size() != 2) bad("image.wrap: expected a string or a pair [ws, wt]");
+            image.wrap_s = wrap_of(*iv[1]->items[0]); image.wrap_t = wrap_of(*iv[1]->items[1]);
+          } else image.wrap_s = image.wrap_t = wrap_of(*iv[1]);
+        }
+        if (mat.kind != RT_MAT_LAMBERTIAN && mat.kind != RT_MAT_METAL) bad("image: an image needs a Lambertian or Metal material");
+        image.tex_id = load_texture(sf, cache, dj, iv[0]->text);
+      }
       for (size_t i = 0; i < geo.size(); ++i) {
         RtQuad q{};
         std::memcpy(q.q, geo[i].g, 24); std::memcpy(q.u, geo[i].g + 3, 24); std::memcpy(q.v, geo[i].g + 6, 24);
@@ -707,6 +799,10 @@ void build_scene(const Value& root, RtSceneFile& sf) {
         for (int k = 0; k < 3; ++k) sf.emit.push_back(emit[k]);
         sf.has_emit.push_back(emit_v ? 1 : 0);
         if (emit_v) sf.n_emit++;
+        RtFlatImage im = image;
+        if (image_v) { std::memcpy(im.uv, geo[i].uv, sizeof im.uv); sf.n_images++; }
+        sf.images.push_back(im);
+        sf.has_uvs.push_back(image_v && has_uvs ? 1 : 0);
       }
     } catch (const SchemaError& e) {
       bad(e.msg.rfind(which, 0) == 0 ? e.msg : which + ": " + e.msg);
@@ -718,6 +814,8 @@ void build_scene(const Value& root, RtSceneFile& sf) {
       ++obj_index;
       continue;
     }
+    if (o->kind == Value::Object && o->find("image")) bad("objects[" + std::to_string(obj_index) + "]: a sphere takes no `image` (a sphere with a picture is a Texture; `image` is a flat primitive's)");
+    if (o->kind == Value::Object && o->find("uvs")) bad("objects[" + std::to_string(obj_index) + "]: a sphere takes no `uvs`");
     if (o->kind == Value::Object && o->find("emit")) bad("objects[" + std::to_string(obj_index) + "]: a sphere takes no `emit` (a sphere that emits is a Light; `emit` is a flat primitive's)");
     RtSphere s{};
     const Value* sp[4] = {};
@@ -841,6 +939,13 @@ std::string scene_json(const RtSceneFile& sf) {
       if (smooth) o += ",\"normals\":[" + point(nr) + "," + point(nr + 3) + "," + point(nr + 6) + "]";
       if (sf.has_move[iq - 1]) o += ",\"move\":" + point(&sf.move[3 * (iq - 1)]);  // (§27: only where the file had the key)
       if (sf.has_emit[iq - 1]) o += ",\"emit\":" + albedo(&sf.emit[3 * (iq - 1)]);  // (§28: likewise)
+      if (sf.images[iq - 1].tex_id != RT_FLAT_IMAGE_NONE) {  // (§29: likewise; the (s, t) of Q, Q + u, Q + v — the form written here)
+        const RtFlatImage& im = sf.images[iq - 1];
+        auto wrap = [](uint32_t w) { return w == RT_WRAP_CLAMP ? std::string("\"clamp\"") : std::string("\"repeat\""); };
+        o += ",\"image\":{\"pixels\":" + jstr(sf.texture_paths[im.tex_id]) + ",\"wrap\":[" + wrap(im.wrap_s) + "," + wrap(im.wrap_t) + "]}";
+        if (sf.has_uvs[iq - 1])
+          o += ",\"uvs\":[[" + f64s(im.uv[0]) + "," + f64s(im.uv[1]) + "],[" + f64s(im.uv[2]) + "," + f64s(im.uv[3]) + "],[" + f64s(im.uv[4]) + "," + f64s(im.uv[5]) + "]]";
+      }
       o += ",\"material\":{";
     } else {
       o += "{\"center\":" + point(s.center);
@@ -950,6 +1055,11 @@ extern "C" const double* rt_scene_flat_motion(const RtSceneFile* sf, uint32_t* n
   const bool any = sf && sf->n_move != 0;
   if (n) *n = any ? (uint32_t)sf->quads.size() : 0u;
   return any ? sf->move.data() : nullptr;
+}
+extern "C" const RtFlatImage* rt_scene_flat_images(const RtSceneFile* sf, uint32_t* n) {
+  const bool any = sf && sf->n_images != 0;
+  if (n) *n = any ? (uint32_t)sf->images.size() : 0u;
+  return any ? sf->images.data() : nullptr;
 }
 extern "C" const float* rt_scene_flat_emit(const RtSceneFile* sf, uint32_t* n) {
   const bool any = sf && sf->n_emit != 0;

@@ -62,6 +62,8 @@ def _bind(path, probes):
     L.rt_hip_group_set_flat_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_scene_set_flat_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_group_set_flat_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_scene_set_flat_images.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.rt_hip_group_set_flat_images.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
     L.rt_hip_scene_table.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.rt_hip_group_update_spheres.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.rt_render_rgb8.argtypes = [C.POINTER(abi.RtScene), C.c_void_p, C.POINTER(abi.RtStats)]
@@ -214,7 +216,34 @@ def _flat_geometry(quv, device, rebuild, width=9, what="quv", dtype="float64"):
     return C.c_void_p(a.ctypes.data), a.shape[0], flags, a
 
 
-TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order", "flat_normals", "flat_motion", "flat_lights", "lights", "mat", "matc")   # the names rt_hip_scene_table knows
+def _flat_images(images, device):
+    """the arguments of rt_hip_*_set_flat_images: a sequence (or ctypes array) of abi.RtFlatImage, an [n, 64] uint8 numpy array of such
+    records, or an [n, 64] uint8 CUDA torch tensor — contiguous and on `device` it is read where it is: (pointer, n, flags, keep alive)"""
+    import numpy as np
+    size = C.sizeof(abi.RtFlatImage)
+    if hasattr(images, "data_ptr") and hasattr(images, "is_cuda"):   # a torch tensor
+        if images.dim() != 2 or images.shape[1] != size or str(images.dtype) != "torch.uint8":
+            raise ValueError(f"images must be an [n, {size}] uint8 tensor, got {tuple(images.shape)} {images.dtype}")
+        if images.is_cuda and images.is_contiguous() and device is not None and images.device.index == device:
+            import torch
+            torch.cuda.current_stream(images.device).synchronize()
+            return C.c_void_p(images.data_ptr()), images.shape[0], abi.RT_UPDATE_FLATS_DEVICE, images
+        images = images.detach().cpu().numpy()
+    if isinstance(images, np.ndarray):
+        a = np.ascontiguousarray(images, np.uint8)
+        if a.ndim != 2 or a.shape[1] != size:
+            raise ValueError(f"images must be n x {size} bytes, got shape {a.shape}")
+        return C.c_void_p(a.ctypes.data), a.shape[0], 0, a
+    n = len(images)
+    if isinstance(images, C.Array) and images._type_ is abi.RtFlatImage:
+        return C.cast(images, C.c_void_p), n, 0, images
+    arr = (abi.RtFlatImage * max(1, n))()
+    for i, x in enumerate(images):
+        arr[i] = x
+    return C.cast(arr, C.c_void_p), n, 0, arr
+
+
+TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order", "flat_normals", "flat_motion", "flat_lights", "flat_images", "lights", "mat", "matc")   # the names rt_hip_scene_table knows
 
 
 def _quads_array(quads):
@@ -304,6 +333,17 @@ class HipScene:
             return
         p, n, flags, keep = _flat_geometry(emit, self.device, False, width=3, what="emit", dtype="float32")
         _check(self._L.rt_hip_scene_set_flat_lights(self._h, p, n, flags), self._L)
+        del keep
+
+    def set_flat_images(self, images):
+        """rt_hip_scene_set_flat_images (DESIGN.md §29): the image of every flat primitive — n_quads abi.RtFlatImage (abi.flat_image(...);
+        tex_id abi.RT_FLAT_IMAGE_NONE: the entry has none) as a sequence, an [n, 64] uint8 numpy array or a CUDA torch tensor of that
+        shape (read where it is when on the scene's device); None removes the images.  Blocking."""
+        if images is None:
+            _check(self._L.rt_hip_scene_set_flat_images(self._h, None, int(self.query("quads")), 0), self._L)
+            return
+        p, n, flags, keep = _flat_images(images, self.device)
+        _check(self._L.rt_hip_scene_set_flat_images(self._h, p, n, flags), self._L)
         del keep
 
     def table(self, name):
@@ -627,6 +667,18 @@ class HipGroup:
             return
         p, n, flags, keep = _flat_geometry(emit, None, False, width=3, what="emit", dtype="float32")
         _check(self._L.rt_hip_group_set_flat_lights(self._h, p, n, flags), self._L)
+        del keep
+
+    def set_flat_images(self, images, n_quads=None):
+        """rt_hip_group_set_flat_images: HipScene.set_flat_images on every rank (through host memory); None removes the images and needs
+        n_quads, the scene's count"""
+        if images is None:
+            if n_quads is None:
+                raise ValueError("set_flat_images(None) needs n_quads, the scene's count")
+            _check(self._L.rt_hip_group_set_flat_images(self._h, None, int(n_quads), 0), self._L)
+            return
+        p, n, flags, keep = _flat_images(images, None)
+        _check(self._L.rt_hip_group_set_flat_images(self._h, p, n, flags), self._L)
         del keep
 
     def set_option(self, key, value):

@@ -52,6 +52,8 @@ def lib():
         L.rt_scene_flat_motion.restype = C.POINTER(C.c_double)
         L.rt_scene_flat_emit.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.rt_scene_flat_emit.restype = C.POINTER(C.c_float)
+        L.rt_scene_flat_images.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.rt_scene_flat_images.restype = C.POINTER(abi.RtFlatImage)
         L.rt_scene_flat_bvh.argtypes = [C.c_void_p]
         L.rt_find_lights.argtypes = [C.POINTER(abi.RtSphere), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.rt_find_lights.restype = C.c_uint32
@@ -153,6 +155,17 @@ class Scene:
         if not p or not n.value:
             return None
         return np.ctypeslib.as_array(p, shape=(n.value, 3)).copy()
+
+    def flat_images(self):
+        """images: a ctypes array of n_quads abi.RtFlatImage (a copy) — the "image" and "uvs" of every entry of quads(),
+        tex_id abi.RT_FLAT_IMAGE_NONE for an entry without — or None for a file without the key (rt_scene_flat_images)"""
+        n = C.c_uint32(0)
+        p = lib().rt_scene_flat_images(self._h, C.byref(n))
+        if not p or not n.value:
+            return None
+        out = (abi.RtFlatImage * n.value)()
+        C.memmove(out, p, C.sizeof(out))
+        return out
 
     def flat_bvh(self):
         """the structure over the flat primitives: True for a file with "flat_bvh": true (rt_scene_flat_bvh)"""
