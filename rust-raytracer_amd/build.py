@@ -42,7 +42,8 @@ def build_hip(force=False):
     out = os.path.join(HERE, "librt_hip.so")
     probe = os.path.join(HERE, "librt_hip_probe.so")
     deps = _srcs(*HIP_DEPS) + [os.path.join(ROOT, "include/rt_abi.h"), os.path.join(ROOT, "include/rt_abi_test.h"),
-                                 os.path.join(ROOT, "include/rt_abi_test_flat_light.h"), os.path.join(ROOT, "include/rt_abi_test_flat_image.h")]
+                                 os.path.join(ROOT, "include/rt_abi_test_flat_light.h"), os.path.join(ROOT, "include/rt_abi_test_flat_image.h"),
+                                 os.path.join(ROOT, "include/rt_abi_test_flat_motion.h")]
     # (beside the file times: the source hash the libraries on disk were built from — a checkout or a clock that does not move
     #  forward leaves times that say nothing)
     try:

@@ -33,6 +33,8 @@
 // does the result depend on the visiting order.  Any structure over the entries (rt_core.h flats_hit_bvh) returns exactly this: a sphere
 // still beats a flat entry on an equal t, an earlier entry a later one, and a NaN fails every comparison (rt_flat_hit_tie below).
 // PRECONDITION: best_in is what the spheres left — a sphere's id or a miss, never a flat entry's.
+// (The kernels keep to it.  The moving list — rt_core.h flats_walk<true>, scan and structure alike — is probed beyond it, DESIGN.md §30: a flat
+// entry held on entry takes part in the order like any other, so an entry of a SMALLER index takes an equal t from it and nothing else does.)
 //
 // An axis-aligned box (rt_box_quads) with corners min = (x0, y0, z0) and max = (x1, y1, z1), dx = x1 - x0, dy = y1 - y0, dz = z1 - z0
 // (one subtraction each; a negation is exact; every other component is +0.0), is these six quads in this order:

@@ -1097,7 +1097,8 @@ RT_HD Surface surface_at(V3 o, V3 d, double t, const SphereGeom& g, double inv_r
 // MOVING: the same scan and the same walk with every entry at the lane's shutter time tau (rt_flat_motion.h: the entry's
 // record at tau through the same test; the boxes are swept, rt_flat_build.h flat_entry_box_swept) — ONE body for both, so a fix to the
 // traversal is made once; use_bvh 0 sends every ray through the scan ("variant" 1, or a scene without the structure).  With MOVING false
-// the body is flats_hit_bvh's as it was.
+// the body is flats_hit_bvh's as it was.  The moving scan sets tie_ok by the walk's rule: the two agree on ANY hit held on entry, a flat
+// entry's included (the shutter probe hands such hits in; the kernels never do, and for them the flag is never set).
 template <bool MOVING>
 RT_HD HitCB flats_walk(V3 o, V3 d, const FlatBvhHeader* header, uint32_t use_bvh, double tau, double closest, int best) {
   struct { const FlatNode* nodes; const uint32_t* order; uint32_t n_nodes; } bvh = {header->nodes, header->order, header->n_nodes};
@@ -1114,8 +1115,12 @@ RT_HD HitCB flats_walk(V3 o, V3 d, const FlatBvhHeader* header, uint32_t use_bvh
       const double lk = quads.lim ? quads.lim[k] : 2.0;
       double t, P[3];
       bool hit;
-      if constexpr (MOVING) hit = rt_flat_motion_hit_tie(q, lk, motion + 4u * (size_t)k, tau, oo, dd, r.closest, false, &t, P);
-      else hit = rt_flat_hit(q, lk, oo, dd, r.closest, &t, P);
+      if constexpr (MOVING) {
+        // (within rt_quad.h's precondition — a sphere or a miss comes in — false at every k: an entry the scan accepted has a smaller
+        //  index than the next)
+        const bool tie_ok = r.best >= (int)id_base && (uint32_t)r.best - id_base > k;
+        hit = rt_flat_motion_hit_tie(q, lk, motion + 4u * (size_t)k, tau, oo, dd, r.closest, tie_ok, &t, P);
+      } else hit = rt_flat_hit(q, lk, oo, dd, r.closest, &t, P);
       if (hit) { r.closest = t; r.best = (int)(id_base + k); }
     }
     return r;

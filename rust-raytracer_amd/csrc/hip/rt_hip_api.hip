@@ -23,6 +23,7 @@
 #include "rt_tables.h"
 #ifdef RT_TEST_PROBES  // librt_hip_probe.so: the device probes and debug calls of include/rt_abi_test.h (test infrastructure)
 #include "../../../include/rt_abi_test.h"
+#include "../../../include/rt_abi_test_flat_motion.h"
 #endif
 
 namespace {
@@ -2649,6 +2650,52 @@ extern "C" int rt_hip_flat_image_texel_probe(const void* d_rec, const double* d_
   if (!n) return RT_OK;
   hipLaunchKernelGGL(rtk::rt_flat_image_texel_probe, dim3((n + block - 1u) / block), dim3(block), 0, (hipStream_t)stream,
                      static_cast<const RtFlatImageRec*>(d_rec), d_ouvw, d_P, d_texel, n);
+  RT_HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// The device surface of flat primitives that move within the frame (include/rt_abi_test_flat_motion.h), one ray per thread.
+namespace rtk {
+// ray i at shutter time tau[i] (null: 0) with its own closest-so-far and the hit it already holds (null: -1): what a QUADS ∧ MOTION
+// megakernel does for a segment — the motion tables at tau, flats_hit through them (flats_hit_shutter: the scan, the structure or the moving
+// walk behind the scene's bits), then object_surface<true> of a newly accepted flat entry (the cold flat_surface_shutter where the scene has
+// shading normals or motion records) — without the megakernel around it.  out_best is always written; t, P, the normal, front_face and the
+// origin left in g.cx, g.cy, g.cz only for an accepted flat entry that is not the hit the ray came with.
+__global__ void rt_flat_shutter_probe(const rtc::DevScene sc, const double* rays, const float* tau, const double* closest, const int32_t* best_in, uint32_t n,
+                                      int32_t* out_best, double* out_t, double* out_point, double* out_normal, int32_t* out_front, double* out_origin) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const rtc::V3 o = rtc::v3(rays[6u * (size_t)i], rays[6u * (size_t)i + 1u], rays[6u * (size_t)i + 2u]);
+  const rtc::V3 d = rtc::v3(rays[6u * (size_t)i + 3u], rays[6u * (size_t)i + 4u], rays[6u * (size_t)i + 5u]);
+  const rtc::GlobalTables still{sc.geom, sc.matc};
+  const auto tb = rtc::motion_tables(still, sc.motion, tau ? tau[i] : 0.0f);
+  const int held = best_in ? best_in[i] : -1;
+  const rtc::HitCB r = rtc::flats_hit(sc, tb, o, d, closest[i], held);
+  out_best[i] = r.best;
+  // (an id the walk accepted lies in n_spheres .. n_spheres + n_quads - 1; the one that came in may be anything and is never looked up)
+  if (r.best == held || r.best < 0 || (uint32_t)r.best < sc.n_spheres || (uint32_t)r.best - sc.n_spheres >= sc.n_quads) return;
+  rtc::SphereGeom g;
+  const rtc::Surface s = rtc::object_surface<true>(sc, tb, o, d, r.closest, (uint32_t)r.best, 0.0, g);
+  out_t[i] = r.closest;
+  out_point[3u * (size_t)i] = s.point.x; out_point[3u * (size_t)i + 1u] = s.point.y; out_point[3u * (size_t)i + 2u] = s.point.z;
+  out_normal[3u * (size_t)i] = s.normal.x; out_normal[3u * (size_t)i + 1u] = s.normal.y; out_normal[3u * (size_t)i + 2u] = s.normal.z;
+  out_front[i] = s.front_face ? 1 : 0;
+  out_origin[3u * (size_t)i] = g.cx; out_origin[3u * (size_t)i + 1u] = g.cy; out_origin[3u * (size_t)i + 2u] = g.cz;
+}
+}  // namespace rtk
+// (block: the launch's workgroup size, 1 .. 1024.  A scene without motion tables would not select a MOTION kernel, and one without flat
+//  primitives has no records to put a header in front of: both are refused before anything is launched)
+extern "C" int rt_hip_flat_shutter_probe(RtHipScene* s, const double* d_rays, const float* d_tau, const double* d_closest, const int32_t* d_best_in,
+                                         uint32_t n, uint32_t block, int32_t* d_best, double* d_t, double* d_point, double* d_normal, int32_t* d_front,
+                                         double* d_origin, void* stream) {
+  if (!s || !d_rays || !d_closest || !d_best || !d_t || !d_point || !d_normal || !d_front || !d_origin) return fail(RT_ERR_INVALID, "null argument");
+  if (block < 1u || block > 1024u) return fail(RT_ERR_INVALID, "block must be 1 .. 1024");
+  if (!s->res->flat.n_quads || !s->dev.n_quads || !s->dev.quads.rec) return fail(RT_ERR_INVALID, "the scene has no flat primitive");
+  if (!s->dev.motion) return fail(RT_ERR_INVALID, "nothing in the scene moves within the frame: it selects no MOTION kernel");
+  if (!n) return RT_OK;
+  RT_HIP_TRY(hipSetDevice(s->device));
+  hipLaunchKernelGGL(rtk::rt_flat_shutter_probe, dim3((uint32_t)(((uint64_t)n + block - 1u) / block)), dim3(block), 0, (hipStream_t)stream, s->dev, d_rays, d_tau, d_closest,
+                     d_best_in, n, d_best, d_t, d_point, d_normal, d_front, d_origin);
   RT_HIP_TRY(hipGetLastError());
   return RT_OK;
 }

@@ -134,6 +134,7 @@ def _bind(path, probes):
         L.rt_hip_solid_fn_probe.argtypes = [C.c_void_p] + [C.c_uint32] * 3 + [C.c_void_p] * 3 + [C.c_uint32, C.c_void_p]
         L.rt_hip_solid_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rt_hip_medium_probe.argtypes = [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p]
+        L.rt_hip_flat_shutter_probe.argtypes = [C.c_void_p] * 5 + [C.c_uint32] * 2 + [C.c_void_p] * 7   # include/rt_abi_test_flat_motion.h
     for name in (() if os.environ.get("RT_SKIP_LAYOUT_CHECK") else ("RtSphere", "RtQuad", "RtTexture", "RtScene", "RtRowTiles", "RtStats", "RtGroupInfo", "RtGroupRank")):   # the binding's own layout check
         if L.rt_abi_sizeof(name.encode()) != C.sizeof(getattr(abi, name)):
             raise ImportError(f"{path}: sizeof({name}) = {L.rt_abi_sizeof(name.encode())} but abi.py has "
@@ -586,6 +587,16 @@ class HipScene:
         `stream`"""
         _check(self._L.rt_hip_medium_probe(self._h, C.c_void_p(d_rays), C.c_void_p(d_tau or None), C.c_void_p(d_node), C.c_void_p(d_t), C.c_void_p(d_best),
                                            C.c_void_p(d_work or None), n, C.c_void_p(stream or None)), self._L)
+
+    def flat_shutter_probe(self, d_rays, d_closest, n, d_best, d_t, d_point, d_normal, d_front, d_origin, d_tau=0, d_best_in=0, block=192, stream=0):
+        """(probe library only) rt_hip_flat_shutter_probe (include/rt_abi_test_flat_motion.h): flats_hit of n rays through the motion tables
+        at shutter time d_tau[i] (f32; 0: time 0), each with its closest-so-far and the hit it holds (d_best_in, i32; 0: -1), then
+        object_surface<true> of a newly accepted flat entry -> d_best always, d_t, d_point, d_normal, d_front, d_origin on such a hit
+        (device pointers), in workgroups of `block`, enqueued on `stream`"""
+        _check(self._L.rt_hip_flat_shutter_probe(self._h, C.c_void_p(d_rays or None), C.c_void_p(d_tau or None), C.c_void_p(d_closest or None),
+                                                 C.c_void_p(d_best_in or None), n, block, C.c_void_p(d_best or None), C.c_void_p(d_t or None),
+                                                 C.c_void_p(d_point or None), C.c_void_p(d_normal or None), C.c_void_p(d_front or None),
+                                                 C.c_void_p(d_origin or None), C.c_void_p(stream or None)), self._L)
 
     def close(self):
         if self._h:

@@ -38,6 +38,7 @@ class FlatMotionSim:
         L.fm_boxes.argtypes = [P, u32, P, P, P, P]
         L.fm_build.argtypes = [P, u32, P, P, u64, P, P, P]
         L.fm_list_hit.argtypes = [P, u32, P, u32, i32, P, P, P, P, u64, P, P, P]
+        L.fm_list_surface.argtypes = [P, u32, P, P, u32, i32, P, P, P, P, u64] + [P] * 7
         L.fm_render.argtypes = [S, P, P, u32, P, P, i32, P, P, P, P, P]
         L.fm_aovs.argtypes = [S, P, P, u32, P, P, i32, u32, P, P]
 
@@ -85,6 +86,25 @@ class FlatMotionSim:
                                 best.ctypes.data, t.ctypes.data, count.ctypes.data)
         assert rc == 0
         return best, t, dict(zip(COUNTS, (int(c) for c in count)))
+
+    def list_surface(self, flats, move, rays, tau, closest, bvh, id_base=0, best_in=None, normals=None, out=None):
+        """what rt_hip_flat_shutter_probe runs, in the host build: flats_hit through motion_tables at the ray's tau (f32), then
+        object_surface<true> of a newly accepted flat entry -> {best, t, P, normal, front, origin} and the counts.  best is always written;
+        the other outputs keep what `out` (a dict of arrays to write into) held wherever no such hit was accepted — zeros without `out`."""
+        move, rays, closest, normals = _f64(move), _f64(rays), _f64(closest), _f64(normals)
+        tau = None if tau is None else np.ascontiguousarray(tau, np.float32)
+        best_in = None if best_in is None else np.ascontiguousarray(best_in, np.int32)
+        n = len(rays)
+        o = out if out is not None else dict(best=np.zeros(n, np.int32), t=np.zeros(n), P=np.zeros((n, 3)), normal=np.zeros((n, 3)),
+                                             front=np.zeros(n, np.int32), origin=np.zeros((n, 3)))
+        assert all(o[k].flags.c_contiguous and len(o[k]) == n for k in o)
+        assert o["best"].dtype == o["front"].dtype == np.int32 and all(o[k].dtype == np.float64 for k in ("t", "P", "normal", "origin"))
+        count = np.zeros(5, np.uint64)
+        rc = self.L.fm_list_surface(flats, len(flats), _ptr(move), _ptr(normals), id_base, int(bvh), rays.ctypes.data, _ptr(tau), closest.ctypes.data,
+                                    _ptr(best_in), n, o["best"].ctypes.data, o["t"].ctypes.data, o["P"].ctypes.data, o["normal"].ctypes.data,
+                                    o["front"].ctypes.data, o["origin"].ctypes.data, count.ctypes.data)
+        assert rc == 0, rc
+        return o, dict(zip(COUNTS, (int(c) for c in count)))
 
     def _world(self, sc, center1, quads, normals, move):
         s = sc.contents if hasattr(sc, "contents") else sc

@@ -173,6 +173,64 @@ extern "C" int fm_list_hit(const RtQuad* quads, uint32_t n, const double* move, 
   return 0;
 }
 
+// What rt_hip_flat_shutter_probe runs on the device (include/rt_abi_test_flat_motion.h), the same two calls in this build: the arguments of
+// fm_list_hit plus normals (null or n x 9; move may be null too) -> flats_hit through motion_tables at the ray's tau — an f32, widened where
+// the kernels widen it — and, for a newly accepted flat entry, object_surface<true>: t, P, the normal, front_face and the origin left in
+// g.cx, g.cy, g.cz.  out_best is always written, the rest only on such a hit.  The scene is the one rt_hip_scene_set_flat_normals /
+// _set_flat_motion leave: the bits of n_tris behind which the kernels choose, the header in front of the records, a sphere table in which
+// nothing moves.  1: the list was refused; 3: a normal was.
+extern "C" int fm_list_surface(const RtQuad* quads, uint32_t n, const double* move, const double* normals, uint32_t id_base, int bvh, const double* rays,
+                               const float* tau, const double* closest_in, const int32_t* best_in, uint64_t n_rays, int32_t* out_best, double* out_t,
+                               double* out_P, double* out_normal, int32_t* out_front, double* out_origin, uint64_t* count) {
+  HostTables t;
+  uint32_t moving = 0, bad = 0, smooth = 0;
+  if (!n || !build_quads(quads, n, t).empty()) return 1;
+  if (move && motion_table(t.quads, move, t.flat_motion, &moving, &bad)) return 1;
+  if (!moving) t.flat_motion.clear();
+  if (bvh && !build_flat_bvh(t).empty()) return 1;
+  std::vector<double> nrec;
+  if (normals) {
+    nrec.assign(9 * (size_t)n, 0.0);
+    for (uint32_t k = 0; k < n; ++k) {
+      const int kind = rt_flat_normal_prepare(normals + 9 * (size_t)k, &nrec[9 * (size_t)k]);
+      if (kind == RT_FLAT_NORMAL_BAD) return 3;
+      smooth += kind == RT_FLAT_NORMAL_SMOOTH;
+    }
+  }
+  std::vector<RtQuadRec> blob((size_t)n + 1);
+  std::memcpy(blob.data() + 1, t.quads.data(), (size_t)n * sizeof(RtQuadRec));
+  FlatBvhHeader h;
+  std::memset(&h, 0, sizeof h);
+  h.nodes = t.flat_nodes.data(); h.order = t.flat_order.data(); h.rec = blob.data() + 1; h.lim = t.quad_lim.empty() ? nullptr : t.quad_lim.data();
+  h.n_nodes = (uint32_t)t.flat_nodes.size(); h.n_quads = n; h.id_base = id_base;
+  h.normals = smooth ? nrec.data() : nullptr; h.motion = moving ? t.flat_motion.data() : nullptr;
+  std::memcpy(blob.data(), &h, sizeof h);
+  const std::vector<double> still(4 * (size_t)(id_base ? id_base : 1u), -0.0);
+  DevScene ds;
+  std::memset(&ds, 0, sizeof ds);
+  ds.n_spheres = id_base; ds.quads = QuadView{blob.data() + 1, h.lim}; ds.n_quads = n; ds.motion = still.data();
+  ds.n_tris = (bvh ? FLAT_BVH_BIT : 0u) | (smooth ? FLAT_NORMALS_BIT : 0u) | (moving ? FLAT_MOTION_BIT : 0u);
+  const GlobalTables none{nullptr, nullptr};
+  g_flat_bvh_count = FlatBvhCount{0, 0, 0, 0, 0};
+  for (uint64_t i = 0; i < n_rays; ++i) {
+    const V3 o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    const auto tb = motion_tables(none, ds.motion, tau ? tau[i] : 0.0f);
+    const int held = best_in ? best_in[i] : -1;
+    const HitCB r = flats_hit(ds, tb, o, d, closest_in[i], held);
+    out_best[i] = r.best;
+    if (r.best == held || r.best < 0 || (uint32_t)r.best < id_base || (uint32_t)r.best - id_base >= n) continue;
+    SphereGeom g;
+    const Surface s = object_surface<true>(ds, tb, o, d, r.closest, (uint32_t)r.best, 0.0, g);
+    out_t[i] = r.closest;
+    out_P[3 * i] = s.point.x; out_P[3 * i + 1] = s.point.y; out_P[3 * i + 2] = s.point.z;
+    out_normal[3 * i] = s.normal.x; out_normal[3 * i + 1] = s.normal.y; out_normal[3 * i + 2] = s.normal.z;
+    out_front[i] = s.front_face ? 1 : 0;
+    out_origin[3 * i] = g.cx; out_origin[3 * i + 1] = g.cy; out_origin[3 * i + 2] = g.cz;
+  }
+  put_count(count);
+  return 0;
+}
+
 // The frame of the QUADS lane code (MOTION where something moves).  normals: null or n x 9; move: null or n x 3.  info = {DevScene::n_tris,
 // entries that move, the lowest refused entry}.
 extern "C" int fm_render(const RtScene* sc, const double* center1, const RtQuad* quads, uint32_t n_quads, const double* normals, const double* move, int flat_bvh,

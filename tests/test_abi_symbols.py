@@ -40,6 +40,12 @@ def test_every_declared_symbol_is_exported_by_its_library(pkg):
     for n in sorted(lab):
         assert hasattr(probe, n), f"{n} not exported by librt_hip_probe.so"
         assert not hasattr(hip, n) and not hasattr(host, n), f"{n} is exported by a product library"
+    # the probe headers beside it (the pinned header stays at its 14): each function in the probe library and in no product library
+    shutter = declared_functions("rt_abi_test_flat_motion.h")
+    assert shutter == {"rt_hip_flat_shutter_probe"} and not (shutter & (lab | names)), sorted(shutter)
+    for n in sorted(shutter):
+        assert hasattr(probe, n), f"{n} not exported by librt_hip_probe.so"
+        assert not hasattr(hip, n) and not hasattr(host, n), f"{n} is exported by a product library"
     out = subprocess.run(["nm", "-D", "--defined-only", pkg.hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "_probe" not in out and "rt_hip_debug" not in out, [l for l in out.splitlines() if "_probe" in l or "debug" in l]
     # and nothing the product exports is undeclared: every defined rt_* symbol of librt_hip.so is in the header

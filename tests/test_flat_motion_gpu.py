@@ -159,26 +159,11 @@ def test_all_quads_motion_kernels_run_with_the_table(pkg, abi, host, torch_cuda)
 
 # ------------------------------------------------------------------ the device form, bit for bit
 def _device_class_world(abi, cls):
-    """one list per class of tests/quad_rays.py: the class's entries a device scene can hold (filled up to 100 with generic ones; triangles
-    and parallelograms in turn, every other entry moving by about its own size) and all its rays, each with its own tau and moved along
-    with the entry it is aimed at"""
-    import lane_sim
-    rng = np.random.default_rng(5100 + QR.CLASSES.index(cls))
-    quvs, rays, aim = [], [], []
-    for quv, r, _ in QR.device_class_tables(cls, lane_sim.load(abi)):
-        quvs.append(quv); rays.append(r); aim += [len(quvs) - 1] * len(r)
-    if len(quvs) < 100:
-        quvs += list(QR._quads(rng, 100 - len(quvs)))
-    quvs, rays, aim = np.array(quvs), np.concatenate(rays), np.array(aim)
-    n = len(quvs)
-    shapes = (np.arange(n) % 2).astype(np.uint32)
-    move = np.zeros((n, 3))
-    with np.errstate(all="ignore"):
-        move[::2] = (rng.uniform(-1.0, 1.0, (n, 3)) * np.linalg.norm(quvs[:, 3:6], axis=1)[:, None])[::2]
-        tau = (rng.integers(0, 1 << 24, len(rays)).astype(np.float64) * 2.0 ** -24).astype(np.float32)
-        tau[::3], tau[1::3] = 0.0, np.float32(1.0 - 2.0 ** -24)
-        rays[:, :3] = rays[:, :3] + move[aim] * tau[:, None].astype(np.float64)
-    return quvs, shapes, move, rays, tau
+    """one list per class of tests/quad_rays.py (tests/flat_shutter_rays.py full_class_world, which the shutter probe's tests reduce): the
+    class's entries a device scene can hold (filled up to 100 with generic ones; triangles and parallelograms in turn, every other entry
+    moving by about its own size) and all its rays, each with its own tau and moved along with the entry it is aimed at"""
+    import flat_shutter_rays
+    return flat_shutter_rays.full_class_world(abi, cls)[:5]
 
 
 @pytest.mark.gpu
@@ -189,9 +174,10 @@ def test_device_moving_hit_equals_the_host_build(pkg, abi, torch_cuda, cls, bvh)
     """The nine ray classes of tests/quad_rays.py, >= 10^5 rays each, every ray with its own tau, through rt_hip_medium_probe — hit_world of
     the MOTION tables, then flats_hit at the ray's tau; launches of 1 000 threads: 15 waves and a partial one — against the host build of
     the same code (tests/flat_motion_sim.py): the id and every bit of t, through the scan and through the swept structure.
-    WHAT THIS DOES NOT COVER: the probe header is pinned at its 14 functions, so the medium probe serves, and it has no closest-so-far
-    input (every ray starts at f64::MAX) and returns no surface record: P, the normal and front_face of the device form are compared
-    only through the AOV and frame tests above.  The scene's one medium sphere is 10^30 away; a ray that met it is left out and counted."""
+    This probe has no closest-so-far input (every ray starts at f64::MAX) and returns no surface record; tests/test_flat_shutter_gpu.py
+    (rt_hip_flat_shutter_probe) compares those ray by ray: a real closest, a hit already held, and P, the normal, front_face
+    and the origin at tau of the device form, bit for bit.  The scene's one medium sphere is 10^30 away; a ray that met it is left out
+    and counted."""
     from test_quad_rays_gpu import _dev
     quvs, shapes, move, rays, tau = _device_class_world(abi, cls)
     n = len(quvs)
