@@ -101,7 +101,7 @@ HIP_UNITS = ([("rt_hip_api", "csrc/hip/rt_hip_api.hip", ["-DRT_KERNEL_SET_SPLIT"
              + [("rt_grid_build", "csrc/hip/rt_grid_build.hip", []), ("rt_flat_build", "csrc/hip/rt_flat_build.hip", [])])
 # what the units are compiled from: every unit, and the files they include
 HIP_DEPS = tuple(dict.fromkeys(u for _, u, _ in HIP_UNITS)) + (
-    "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h", "csrc/hip/rt_grid_build.h",
+    "csrc/hip/rt_kernel.hip", "csrc/hip/rt_hip_flats.hip", "csrc/hip/rt_hip_group.hip", "csrc/hip/rt_core.h", "csrc/hip/rt_tables.h", "csrc/hip/rt_grid_build.h",
     "csrc/hip/rt_flat_build.h",
     "csrc/common/rt_atan2.h", "csrc/common/rt_neg_log.h", "csrc/common/rt_solid.h", "csrc/common/rt_quad.h",
     "csrc/common/rt_flat_normal.h", "csrc/common/rt_flat_motion.h", "csrc/common/rt_flat_light.h", "csrc/common/rt_flat_image.h")

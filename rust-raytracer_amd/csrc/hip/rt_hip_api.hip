@@ -178,11 +178,14 @@ struct RtHipScene {
       }
     } sph;
     // The flat primitives (quads; triangles, §21), the structure over them (§22: only in a scene that came from
-    // rt_hip_scene_create_flats_bvh) and what rt_hip_scene_update_flats (§24) moves them with.
+    // rt_hip_scene_create_flats_bvh) and what rt_hip_scene_update_flats (§24) moves them with.  The calls that change them are in
+    // rt_hip_flats.hip; all of them go from the live generation to the next through one function (flats_go_live, §24 "One update path"),
+    // which is handed a HeaderState: what the next generation's header names.
     struct Flats {
       struct Tables {
-        // [n_quads] RtQuadRec, their materials are records n_spheres + k of `mat` and `matc`; with the structure: one buffer, the FlatBvhHeader
-        // in front of the records (Flats::first_rec).  Unallocated without quads.
+        // [n_quads] RtQuadRec, their materials are records n_spheres + k of `mat` and `matc`; while the header names anything — the structure
+        // or a table of normals, motion or images (HeaderState::slot) — one buffer, the FlatBvhHeader in front of the records
+        // (Flats::first_rec).  Unallocated without quads.
         DevBuf rec;
         DevBuf nodes, order;   // the structure: [n_nodes] FlatNode and [n_quads] the order table its leaves index
       } live, spare;           // (a refit keeps the live order table: only a rebuild swaps it)
@@ -217,23 +220,30 @@ struct RtHipScene {
       std::vector<double> host_lim, keep_quv;
       std::vector<rtc::FlatNode> keep_nodes;
       std::vector<uint32_t> keep_order;
-      rtc::FlatBvhHeader keep_header{};
+      rtc::FlatBvhHeader keep_header{};   // (the staging of the header's upload: written by flats_go_live alone)
       uint32_t refits = 0;     // the updates applied by refit since the structure was last built
-      // the first record of a generation as the kernels see it (DevScene::quads.rec): behind the header, where there is a structure
-      uint32_t header_recs() const { return (n_nodes || n_normals || n_moving || n_images) ? 1u : 0u; }  // the record slots the header takes (§25, §27, §29: the normals', the motion's and the images' pointers live in it)
-      RtQuadRec* first_rec(const Tables& t) const { return t.rec.get<RtQuadRec>() + header_recs(); }
-      size_t rec_bytes() const { return ((size_t)n_quads + header_recs()) * sizeof(RtQuadRec); }  // of Tables::rec
+      // What a generation's header names: the structure's nodes and order table and the tables of normals, motion and images, each with the
+      // count that says whether it is there, and the buffer behind it — a live one or the spare an update built into.  slot(): the record
+      // slots the header takes in front of the records: one while it names anything, none in a scan scene without a table.
+      struct HeaderState {
+        uint32_t n_nodes = 0, n_normals = 0, n_moving = 0, n_images = 0;
+        const DevBuf *nodes = nullptr, *order = nullptr, *normals = nullptr, *motion = nullptr, *images = nullptr;
+        uint32_t slot() const { return (n_nodes || n_normals || n_moving || n_images) ? 1u : 0u; }
+      };
+      HeaderState state() const { return {n_nodes, n_normals, n_moving, n_images, &live.nodes, &live.order, &normals, &motion, &images}; }  // the live generation's
+      // the first record of a generation as the kernels see it (DevScene::quads.rec): behind the header, where there is one
+      RtQuadRec* first_rec(const Tables& t) const { return t.rec.get<RtQuadRec>() + state().slot(); }
       const double* dev_lim() const { return n_tris ? lim.get<const double>() : nullptr; }
-      // the header in front of generation `t`'s records: they, `t`'s n_nodes nodes, the limits, and the order table that is live beside them
-      rtc::FlatBvhHeader header(const Tables& t, uint32_t t_n_nodes, const DevBuf& order, uint32_t id_base) const {
+      // the header of the generation `st` describes, its records beginning at `rec`
+      rtc::FlatBvhHeader header(const HeaderState& st, const RtQuadRec* rec, uint32_t id_base) const {
         rtc::FlatBvhHeader h{};
-        h.nodes = t.nodes.get<const rtc::FlatNode>(); h.order = order.get<const uint32_t>();
-        h.rec = first_rec(t); h.lim = dev_lim();
-        h.n_nodes = t_n_nodes; h.n_quads = n_quads; h.id_base = id_base;
-        h.normals = n_normals ? normals.get<const double>() : nullptr;
-        h.motion = n_moving ? motion.get<const double>() : nullptr;
-        h.images = n_images ? images.get<const RtFlatImageRec>() : nullptr;
-        h.tex4 = n_images ? tex4_dev : nullptr;
+        h.nodes = st.nodes->get<const rtc::FlatNode>(); h.order = st.order->get<const uint32_t>();
+        h.rec = rec; h.lim = dev_lim();
+        h.n_nodes = st.n_nodes; h.n_quads = n_quads; h.id_base = id_base;
+        h.normals = st.n_normals ? st.normals->get<const double>() : nullptr;
+        h.motion = st.n_moving ? st.motion->get<const double>() : nullptr;
+        h.images = st.n_images ? st.images->get<const RtFlatImageRec>() : nullptr;
+        h.tex4 = st.n_images ? tex4_dev : nullptr;
         return h;
       }
     } flat;
@@ -635,7 +645,7 @@ int scene_create_flats(const RtScene* scene, const double* center1, const RtQuad
   if (flat_bvh) {  // (§22: the records behind their header, one buffer; the header holds the device addresses of the four tables)
     if ((rc = upload_flat_structure(f, f.live, t.flat_nodes, t.flat_order, t.flat_always)) != RT_OK) return rc;
     if ((rc = f.live.rec.ensure(t.flat_blob.size() * sizeof(RtQuadRec))) != RT_OK) return rc;
-    const rtc::FlatBvhHeader h = f.header(f.live, f.n_nodes, f.live.order, scene->n_spheres);
+    const rtc::FlatBvhHeader h = f.header(f.state(), f.first_rec(f.live), scene->n_spheres);
     std::memcpy(t.flat_blob.data(), &h, sizeof h);
     RT_HIP_TRY(hipMemcpy(f.live.rec.p, t.flat_blob.data(), t.flat_blob.size() * sizeof(RtQuadRec), hipMemcpyHostToDevice));
   } else if (n_quads && (rc = upload(f.live.rec, t.quads)) != RT_OK) return rc;
@@ -1917,11 +1927,17 @@ int adopt_tables(RtHipScene* s, Moved what) {
   return configure(s);
 }
 
+// an update of a scene replaces tables its views read: only a caller that re-points them itself (views_follow: the group) may run it while
+// there is a view.  who, through, group_call: the entry point, the message's verb, the group's call of the same name
+int check_not_shared(const RtHipScene* s, bool views_follow, const char* who, const char* through, const char* group_call) {
+  if (views_follow || s->res.use_count() <= 1) return RT_OK;
+  return fail(RT_ERR_INVALID, std::string(who) + ": the scene's tables are shared with a view (a group " + through + " " + group_call + ")");
+}
+
 // views_follow: the caller (the group) re-points the views that share this scene's tables itself
 int scene_update(RtHipScene* s, const double* center, const double* center1, bool views_follow) {
   if (!s || (!center && s->host.n_spheres)) return fail(RT_ERR_INVALID, "null argument");
-  if (!views_follow && s->res.use_count() > 1)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_update_spheres: the scene's tables are shared with a view (a group updates through rt_hip_group_update_spheres)");
+  if (const int refused = check_not_shared(s, views_follow, "rt_hip_scene_update_spheres", "updates through", "rt_hip_group_update_spheres")) return refused;
   int rc;
   if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
   rtp::Clock pc = rtp::begin();
@@ -2018,391 +2034,7 @@ extern "C" int rt_hip_scene_update_spheres(RtHipScene* s, const double* center, 
   return scene_update(s, center, center1, false);
 }
 
-// ------------------------------------------------------------------------------ moving the flat primitives of a resident scene
-namespace {
-// views_follow: the caller (the group) re-points the views that share this scene's tables itself
-// set_move (rt_hip_scene_set_flat_motion): the same update with the geometry the scene has — quv is null, the live records
-// are the input — and `move`, [n_quads][3] in host or (RT_UPDATE_FLATS_DEVICE) device memory, null: all zeros, as the displacements.
-// Without set_move the motion stays as set: its records are made anew beside the new geometry's (Dm follows the new normal).
-int scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags, bool views_follow, const double* move = nullptr,
-                       bool set_move = false) {
-  const std::string who = set_move ? "rt_hip_scene_set_flat_motion" : "rt_hip_scene_update_flats";
-  if (!s || (!quv && !set_move)) return fail(RT_ERR_INVALID, "null argument");
-  if (flags & ~((set_move ? 0u : RT_UPDATE_FLATS_REBUILD) | RT_UPDATE_FLATS_DEVICE)) return fail(RT_ERR_INVALID, who + ": unknown flag");
-  RtHipScene::Resident::Flats& f = s->res->flat;
-  if (!f.n_quads) return fail(RT_ERR_INVALID, who + ": the scene has no flat primitive");
-  if (n_quads != f.n_quads)
-    return fail(RT_ERR_INVALID, who + ": n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
-  if (!views_follow && s->res.use_count() > 1)
-    return fail(RT_ERR_INVALID, who + ": the scene's tables are shared with a view (a group updates through " + (set_move ? "rt_hip_group_set_flat_motion)" : "rt_hip_group_update_flats)"));
-  const bool on_device = (set_move ? move != nullptr : true) && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
-  if (on_device)
-    if (const int refused = check_aligned(set_move ? move : quv, 8, set_move ? "rt_hip_scene_set_flat_motion: move must be 8-byte aligned" : "rt_hip_scene_update_flats: quv must be 8-byte aligned")) return refused;
-  int rc;
-  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
-  if (set_move && move && !s->res->flat_lights.empty()) {  // (§28: an emitter cannot move, as a Light sphere cannot; only a scene that has one looks)
-    std::vector<double> dev_move;
-    if (on_device) {
-      dev_move.resize(3 * (size_t)n_quads);
-      RT_HIP_TRY(hipMemcpy(dev_move.data(), move, (size_t)n_quads * 24, hipMemcpyDeviceToHost));
-    }
-    const double* m = on_device ? dev_move.data() : move;
-    for (uint32_t k : s->res->flat_lights)   // (entry order: the lowest first)
-      if (!(m[3 * (size_t)k] == 0.0 && m[3 * (size_t)k + 1] == 0.0 && m[3 * (size_t)k + 2] == 0.0))
-        return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": an emitting flat primitive cannot move");
-  }
-  if (set_move && !move && !f.n_moving) return RT_OK;   // nothing moves and nothing shall: the scene is what it was
-  rtp::Clock pc = rtp::begin();
-  const uint32_t n = n_quads;
-  const bool bvh = f.n_nodes != 0u;
-  bool rebuild = bvh && (flags & RT_UPDATE_FLATS_REBUILD) != 0u;
-  const bool device_build = rebuild && s->opt.flat_build == 1;   // (§26: the order table on the device; a changed refused set still goes to the host)
-  RtHipScene::Resident::Flats::Tables& spare = f.spare;
-  RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
-  // (§27) with_move: this update makes a motion table; slot: the record slots the header takes in the spare generation — one for sure while
-  // a motion table may come out of it (a scan scene that ends up without one is compacted after the readback)
-  const bool with_move = set_move || f.n_moving != 0u;
-  const uint32_t slot = (f.n_nodes || f.n_normals || f.n_images || with_move) ? 1u : 0u;
-  uint32_t moving = set_move ? 0u : f.n_moving;   // the entries that move once this update is in: known after the readback
-  if ((rc = room(spare.rec, ((size_t)n + slot) * sizeof(RtQuadRec))) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
-      (!set_move && !on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK) ||
-      (with_move && (rc = room(f.motion_spare, (size_t)n * 32)) != RT_OK) ||
-      (set_move && !on_device && (rc = room(fb.move, (size_t)n * 24)) != RT_OK) ||
-      (bvh && ((rc = room(fb.box, (size_t)n * 48)) != RT_OK || (rc = room(spare.nodes, (size_t)f.n_nodes * sizeof(rtc::FlatNode))) != RT_OK)))
-    return rc;
-  if (with_move) {  // the MOTION kernels' dv table while no sphere moves, now or after a later rt_hip_scene_update_spheres: every word -0.0
-    const size_t words = 4 * (size_t)(s->host.n_spheres ? s->host.n_spheres : 1u);
-    if (f.still.cap < words * 8) {
-      if ((rc = room(f.still, words * 8)) != RT_OK) return rc;
-      const std::vector<double> still(words, -0.0);
-      RT_HIP_TRY(hipMemcpy(f.still.p, still.data(), words * 8, hipMemcpyHostToDevice));
-    }
-  }
-  rtfb::BuildJob bj;
-  if (device_build) {  // the boxed entries in index order, uploaded once per host build; scratch and the spare order table, allocated once
-    if (!f.start_ready) {
-      f.keep_start.clear();
-      for (uint32_t k = 0; k < n; ++k) if (f.topo.boxed[k]) f.keep_start.push_back(k);
-      if ((rc = upload(f.start, f.keep_start)) != RT_OK) return rc;
-      f.start_ready = true;
-    }
-    bj.n = n; bj.m = (uint32_t)f.keep_start.size();
-    RT_HIP_TRY(rtfb::build_sort_bytes(bj.m, &bj.sort_bytes));
-    if ((rc = room(spare.order, (size_t)n * sizeof(uint32_t))) != RT_OK || (rc = room(fb.item, (size_t)bj.m * sizeof(rtc::FlatBuildItem))) != RT_OK ||
-        (rc = room(fb.extent, rtfb::build_extent_bytes(bj.m))) != RT_OK || (rc = room(fb.sort_tmp, bj.sort_bytes)) != RT_OK)
-      return rc;
-  }
-  if (!set_move && !on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, quv, (size_t)n * 72, hipMemcpyHostToDevice));  // (the geometry travels once)
-  if (set_move && !on_device) {
-    if (move) RT_HIP_TRY(hipMemcpy(fb.move.p, move, (size_t)n * 24, hipMemcpyHostToDevice));
-    else RT_HIP_TRY(hipMemset(fb.move.p, 0, (size_t)n * 24));
-  }
-  pc.mark("update_flats.upload");
-  rtfb::Job j;
-  j.n = n;
-  if (set_move) { j.quv = reinterpret_cast<const double*>(f.first_rec(f.live)); j.quv_stride = 16u; }  // (a record begins with its q, u, v)
-  else j.quv = on_device ? quv : fb.quv.get<const double>();
-  if (set_move) { j.move = on_device ? move : fb.move.get<const double>(); j.move_stride = 3u; }
-  else if (with_move) { j.move = f.motion.get<const double>(); j.move_stride = 4u; }
-  if (with_move) j.motion = f.motion_spare.get<double>();
-  j.lim = f.dev_lim();
-  j.rec = spare.rec.get<RtQuadRec>() + slot;
-  j.status = fb.status.get<rtfb::Status>();
-  if (bvh) {
-    const rtc::FlatTopology& tp = f.topo;
-    j.boxed = f.boxed.get<const uint32_t>(); j.box = fb.box.get<double>();
-    j.n_nodes = f.n_nodes; j.n_run = tp.n_run; j.n_leaves = (uint32_t)tp.leaves.size();
-    j.live_nodes = f.live.nodes.get<const rtc::FlatNode>(); j.order = f.live.order.get<const uint32_t>();
-    j.leaves = f.leaves.get<const uint32_t>(); j.level_nodes = f.levels.get<const uint32_t>();
-    j.level_start = tp.level_start.data(); j.n_levels = (uint32_t)tp.level_start.size() - 1u;
-    j.nodes = spare.nodes.get<rtc::FlatNode>();
-  }
-  // the spare's header: its own records and nodes, and the order table that goes live with them
-  auto put_header = [&](uint32_t n_nodes, const DevBuf& order) {
-    f.keep_header = f.header(spare, n_nodes, order, s->host.n_spheres);
-    f.keep_header.rec = spare.rec.get<RtQuadRec>() + slot;
-    f.keep_header.motion = moving ? f.motion_spare.get<const double>() : nullptr;   // (the table that goes live with these records)
-    return hipMemcpy(spare.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice);
-  };
-  RT_HIP_TRY(rtfb::prepare(j, nullptr));
-  if (device_build) {  // (enqueued before the readback too: the order table into the spare, then the refit over it — the skeleton is the live one)
-    bj.box = fb.box.get<const double>(); bj.start = f.start.get<const uint32_t>(); bj.live_order = f.live.order.get<const uint32_t>();
-    bj.item = fb.item.get<rtc::FlatBuildItem>(); bj.extent = fb.extent.get<unsigned long long>(); bj.sort_tmp = fb.sort_tmp.p;
-    bj.order = spare.order.get<uint32_t>();
-    RT_HIP_TRY(rtfb::build(bj, nullptr));
-    j.order = bj.order;
-    RT_HIP_TRY(rtfb::refit(j, nullptr));
-    RT_HIP_TRY(put_header(f.n_nodes, spare.order));
-  } else if (bvh && !rebuild) {  // (enqueued before the readback: a refit the status then rejects was written into spares and is dropped)
-    RT_HIP_TRY(rtfb::refit(j, nullptr));
-    if (!set_move) RT_HIP_TRY(put_header(f.n_nodes, f.live.order));
-  } else if (!bvh && slot && !set_move) RT_HIP_TRY(put_header(0u, f.live.order));  // (§25, §27: a scan with shading normals or motion keeps their header)
-  rtfb::Status st;
-  RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the first bad entry of each class, changed flags
-  pc.mark("update_flats.kernels_and_readback");
-  if (st.bad_finite != rtfb::NONE || st.bad_degenerate != rtfb::NONE) {  // (creation's loop stops at the first bad entry: the lowest index wins)
-    if (st.bad_finite < st.bad_degenerate)
-      return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + (with_move ? ": q, u, v, the displacement and q + displacement must be finite" : ": q, u and v must be finite"));
-    return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": degenerate (|cross(u, v)|^2 is zero, subnormal or not finite)");
-  }
-  if (with_move) moving = st.pad;
-  if (bvh && st.mismatch) rebuild = true;  // an entry became a needle, crossed 2^40 (§27: at either end of its motion), or stopped being one: the order table is another
-  // (§27: the header of a new motion table names it only now that the count is known)
-  if (set_move && slot && !rebuild) RT_HIP_TRY(put_header(bvh ? f.n_nodes : 0u, f.live.order));
-  const bool built = device_build && !st.mismatch;  // the device's order table stands; with a mismatch the counts are others: the host builds
-  uint32_t n_nodes = f.n_nodes;
-  if (rebuild && !built) {  // the host's build_flat_bvh over the host's records, as creation runs it; the records themselves stay the device's
-    const double* host_quv = quv;
-    if (on_device && !set_move) {  // (set_move: quv is null, the records come from the device below)
-      f.keep_quv.resize(9 * (size_t)n);
-      RT_HIP_TRY(hipMemcpy(f.keep_quv.data(), quv, (size_t)n * 72, hipMemcpyDeviceToHost));
-      host_quv = f.keep_quv.data();
-    }
-    rtc::HostTables t;
-    t.quads.resize(n);
-    if (set_move) RT_HIP_TRY(hipMemcpy(t.quads.data(), j.rec, (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToHost));  // (the records as they are)
-    else
-      for (uint32_t k = 0; k < n; ++k)
-        if (rt_quad_prepare(host_quv + 9 * (size_t)k, host_quv + 9 * (size_t)k + 3, host_quv + 9 * (size_t)k + 6, &t.quads[k]))
-          return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": the host refuses an entry the device accepted");
-    if (moving) {  // (§27: the builder sweeps the boxes with the records the device just made)
-      t.flat_motion.resize(4 * (size_t)n);
-      RT_HIP_TRY(hipMemcpy(t.flat_motion.data(), f.motion_spare.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-    }
-    t.quad_lim = f.host_lim;
-    const std::string why = rtc::build_flat_bvh(t);
-    if (!why.empty()) return fail(RT_ERR_INVALID, why);
-    f.keep_nodes.assign(t.flat_nodes.begin(), t.flat_nodes.end());
-    f.keep_order.assign(t.flat_order.begin(), t.flat_order.end());
-    n_nodes = (uint32_t)f.keep_nodes.size();
-    pc.mark("update_flats.host_build");
-    if ((rc = upload_flat_structure(f, spare, f.keep_nodes, f.keep_order, t.flat_always)) != RT_OK) return rc;
-    RT_HIP_TRY(put_header(n_nodes, spare.order));
-    pc.mark("update_flats.upload_structure");
-  }
-  if (slot && !(f.n_nodes || f.n_normals || f.n_images || moving)) {  // (§27: a scan scene that lost its last table loses the header's slot: the records alone)
-    if ((rc = room(fb.rec_tmp, (size_t)n * sizeof(RtQuadRec))) != RT_OK) return rc;
-    RT_HIP_TRY(hipMemcpy(fb.rec_tmp.p, j.rec, (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
-    spare.rec.swap(fb.rec_tmp);
-  }
-  RT_HIP_TRY(hipDeviceSynchronize());
-  // everything is built: swap it in (nothing above changed what the scene renders with)
-  f.live.rec.swap(spare.rec);
-  if (with_move) f.motion.swap(f.motion_spare);
-  f.n_moving = moving;
-  if (bvh) f.live.nodes.swap(spare.nodes);
-  if (rebuild) { f.live.order.swap(spare.order); f.n_nodes = n_nodes; }
-  f.refits = (bvh && !rebuild) ? f.refits + 1u : 0u;
-  if (built) f.device_builds++;
-  rc = adopt_tables(s, Moved::flats);
-  pc.mark("update_flats.configuration");
-  return rc;
-}
-}  // namespace
-
-extern "C" int rt_hip_scene_update_flats(RtHipScene* s, const double* quv, uint32_t n_quads, uint32_t flags) {
-  return scene_update_flats(s, quv, n_quads, flags, false);
-}
-// flat primitives that move within the frame: an update of the geometry the scene has, with other displacements
-extern "C" int rt_hip_scene_set_flat_motion(RtHipScene* s, const double* move, uint32_t n_quads, uint32_t flags) {
-  return scene_update_flats(s, nullptr, n_quads, flags, false, move, true);
-}
-
-// ------------------------------------------------------------------------------ shading normals on the triangles of a resident scene
-namespace {
-// The records are made on the device from host or device input alike (rt_flat_build.hip: one code path, one table).  The table's address
-// travels in the FlatBvhHeader in front of the records: a scan scene gains that slot with its first normals and loses it with the last, its
-// records copied device to device into the spare generation; a scene with the structure has the slot already.  Everything that can fail
-// runs before anything the scene renders with changes.
-int scene_set_flat_normals(RtHipScene* s, const double* normals, uint32_t n_quads, uint32_t flags, bool views_follow) {
-  if (!s) return fail(RT_ERR_INVALID, "null argument");
-  if (flags & ~RT_UPDATE_FLATS_DEVICE) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: unknown flag");
-  RtHipScene::Resident::Flats& f = s->res->flat;
-  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: the scene has no flat primitive");
-  if (n_quads != f.n_quads)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
-  if (!views_follow && s->res.use_count() > 1)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_normals: the scene's tables are shared with a view (a group sets them through rt_hip_group_set_flat_normals)");
-  const bool on_device = normals && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
-  if (on_device)
-    if (const int refused = check_aligned(normals, 8, "rt_hip_scene_set_flat_normals: normals must be 8-byte aligned")) return refused;
-  int rc;
-  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
-  const uint32_t n = n_quads;
-  uint32_t count = 0;
-  if (normals) {
-    RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
-    if ((rc = room(f.normals_spare, (size_t)n * 72)) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
-        (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK))
-      return rc;
-    if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, normals, (size_t)n * 72, hipMemcpyHostToDevice));
-    rtfb::NormalJob j;
-    j.n = n; j.in = on_device ? normals : fb.quv.get<const double>(); j.lim = f.dev_lim();
-    j.out = f.normals_spare.get<double>(); j.status = fb.status.get<rtfb::Status>();
-    RT_HIP_TRY(rtfb::normals(j, nullptr));
-    rtfb::Status st;
-    RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the lowest bad entry of each class, the count
-    if (st.bad_finite != rtfb::NONE || st.bad_degenerate != rtfb::NONE) {
-      if (st.bad_finite < st.bad_degenerate)
-        return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_finite) + ": normal vectors must be finite, with a squared length that is finite, normal and not zero");
-      return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": normal vectors on a parallelogram (only triangles interpolate)");
-    }
-    count = st.mismatch;
-  }
-  // the record slots the header takes before and after: they differ only in a scan scene that gains or loses its table
-  const uint32_t had = f.header_recs(), has = (f.n_nodes || count || f.n_moving || f.n_images) ? 1u : 0u;
-  RtHipScene::Resident::Flats::Tables& spare = f.spare;
-  if (has != had) {
-    if ((rc = room(spare.rec, ((size_t)n + has) * sizeof(RtQuadRec))) != RT_OK) return rc;
-    RT_HIP_TRY(hipMemcpy(spare.rec.get<RtQuadRec>() + has, f.first_rec(f.live), (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
-    RT_HIP_TRY(hipDeviceSynchronize());
-  }
-  // everything is built: swap it in
-  if (has != had) f.live.rec.swap(spare.rec);
-  if (count) f.normals.swap(f.normals_spare);
-  f.n_normals = count;
-  if (has) {
-    f.keep_header = f.header(f.live, f.n_nodes, f.live.order, s->host.n_spheres);
-    RT_HIP_TRY(hipMemcpy(f.live.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice));
-  }
-  RT_HIP_TRY(hipDeviceSynchronize());
-  return adopt_tables(s, Moved::flats);
-}
-}  // namespace
-
-extern "C" int rt_hip_scene_set_flat_normals(RtHipScene* s, const double* normals, uint32_t n_quads, uint32_t flags) {
-  return scene_set_flat_normals(s, normals, n_quads, flags, false);
-}
-
-// ------------------------------------------------------------------------------ flat primitives that emit
-namespace {
-// The table is small (12 bytes an entry) and checked on the host, from host or device input alike.  What changes on the device: the emitters'
-// records of `mat` and `matc` (kind Light, colour `emit`; every other flat record is put back as created) and the light list; no geometry
-// table, no header slot — the aim reads the entry's own record.  Everything that can be refused is refused before the scene changes.
-int scene_set_flat_lights(RtHipScene* s, const float* emit, uint32_t n_quads, uint32_t flags, bool views_follow) {
-  if (!s) return fail(RT_ERR_INVALID, "null argument");
-  if (flags & ~RT_UPDATE_FLATS_DEVICE) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: unknown flag");
-  RtHipScene::Resident& r = *s->res;
-  RtHipScene::Resident::Flats& f = r.flat;
-  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: the scene has no flat primitive");
-  if (n_quads != f.n_quads)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
-  if (!views_follow && s->res.use_count() > 1)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_lights: the scene's tables are shared with a view (a group sets them through rt_hip_group_set_flat_lights)");
-  const bool on_device = emit && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
-  if (on_device)
-    if (const int refused = check_aligned(emit, 4, "rt_hip_scene_set_flat_lights: emit must be 4-byte aligned")) return refused;
-  int rc;
-  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
-  const uint32_t n = n_quads, n_spheres = s->host.n_spheres;
-  std::vector<float> table(3 * (size_t)n, 0.0f);   // (a null table: all zeros, no entry emits)
-  if (on_device) RT_HIP_TRY(hipMemcpy(table.data(), emit, (size_t)n * 12, hipMemcpyDeviceToHost));
-  else if (emit) std::memcpy(table.data(), emit, (size_t)n * 12);
-  uint32_t n_emit = 0;
-  const uint32_t bad = rt_flat_light_emit_check(table.data(), n, &n_emit);
-  if (bad != n) return fail(RT_ERR_INVALID, "quad " + std::to_string(bad) + ": every component of emit must be finite and in [0, 1]");
-  if (n_emit > RT_MAX_FLAT_LIGHTS) return fail(RT_ERR_UNSUPPORTED, "more than RT_MAX_FLAT_LIGHTS (32) emitting flat primitives: every sampling hit shoots one ray per light");
-  if (!n_emit && r.flat_lights.empty()) return RT_OK;   // nothing emits and nothing shall: the scene is what it was
-  // the flat primitives' material records and the light list, on the host (rt_tables.h: the CPU builds of the tests make the same tables)
-  std::vector<rtc::SphereMat> mat;
-  std::vector<rtc::MatCore> matc;
-  std::vector<uint32_t> lights, emitters;
-  rtc::build_flat_lights(r.keep_flat_mat, r.keep_flat_matc, r.sphere_lights, n_spheres, table.data(), mat, matc, lights, emitters);
-  if (n_emit && f.n_moving) {  // an emitter cannot move, as a Light sphere cannot (whichever call comes second refuses)
-    std::vector<double> motion(4 * (size_t)n);
-    RT_HIP_TRY(hipMemcpy(motion.data(), f.motion.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-    for (uint32_t k : emitters)
-      if (rt_flat_motion_present(&motion[4 * (size_t)k])) return fail(RT_ERR_INVALID, "quad " + std::to_string(k) + ": an emitting flat primitive cannot move");
-  }
-  // the pools of the new light count must fit before anything changes (plan_lds reads the count from the scene)
-  {
-    LdsPlan plan;
-    if ((rc = plan_lds(s, s->dev.grid, !lights.empty(), &plan, (int64_t)lights.size())) != RT_OK) return rc;
-  }
-  DevBuf new_lights;   // (the list may grow: a buffer of its own, swapped in; the old one is freed with this frame, the device idle; the copy
-                       //  from pageable memory has returned when upload has)
-  if ((rc = upload(new_lights, lights)) != RT_OK) return rc;
-  RT_HIP_TRY(hipMemcpy(r.mat.get<rtc::SphereMat>() + n_spheres, mat.data(), mat.size() * sizeof(rtc::SphereMat), hipMemcpyHostToDevice));
-  RT_HIP_TRY(hipMemcpy(r.matc.get<rtc::MatCore>() + n_spheres, matc.data(), matc.size() * sizeof(rtc::MatCore), hipMemcpyHostToDevice));
-  RT_HIP_TRY(hipDeviceSynchronize());
-  r.lights.swap(new_lights);
-  r.flat_lights.swap(emitters);
-  r.has_lights = r.n_lights() != 0u;
-  return adopt_tables(s, Moved::flats);
-}
-}  // namespace
-
-extern "C" int rt_hip_scene_set_flat_lights(RtHipScene* s, const float* emit, uint32_t n_quads, uint32_t flags) {
-  return scene_set_flat_lights(s, emit, n_quads, flags, false);
-}
-
-// ------------------------------------------------------------------------------ images on the flat primitives of a resident scene
-namespace {
-// As the shading normals: the records are made on the device from host or device input alike (rt_flat_build.hip flat_images_prepare), and the
-// table's address — with the texels' — travels in the FlatBvhHeader in front of the records: a scan scene gains that slot with its first
-// image and loses it with the last.  Everything that can fail runs before anything the scene renders with changes.
-int scene_set_flat_images(RtHipScene* s, const RtFlatImage* images, uint32_t n_quads, uint32_t flags, bool views_follow) {
-  if (!s) return fail(RT_ERR_INVALID, "null argument");
-  if (flags & ~RT_UPDATE_FLATS_DEVICE) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: unknown flag");
-  RtHipScene::Resident& r = *s->res;
-  RtHipScene::Resident::Flats& f = r.flat;
-  if (!f.n_quads) return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: the scene has no flat primitive");
-  if (n_quads != f.n_quads)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: n_quads is " + std::to_string(n_quads) + ", the scene has " + std::to_string(f.n_quads) + " flat primitives");
-  if (!views_follow && s->res.use_count() > 1)
-    return fail(RT_ERR_INVALID, "rt_hip_scene_set_flat_images: the scene's tables are shared with a view (a group sets them through rt_hip_group_set_flat_images)");
-  const bool on_device = images && (flags & RT_UPDATE_FLATS_DEVICE) != 0u;
-  if (on_device)
-    if (const int refused = check_aligned(images, 8, "rt_hip_scene_set_flat_images: images must be 8-byte aligned")) return refused;
-  int rc;
-  if ((rc = make_current_and_drain(s)) != RT_OK) return rc;
-  const uint32_t n = n_quads;
-  uint32_t count = 0;
-  if (images) {
-    RtHipScene::Resident::Flats::Scratch& fb = f.scratch;
-    static_assert(sizeof(RtFlatImage) == 64 && sizeof(RtFlatImageRec) == 64, "an image entry and its record are 64 bytes");
-    if ((rc = room(f.images_spare, (size_t)n * sizeof(RtFlatImageRec))) != RT_OK || (rc = room(fb.status, sizeof(rtfb::Status))) != RT_OK ||
-        (rc = room(fb.kind, (size_t)n * sizeof(uint32_t))) != RT_OK || (!on_device && (rc = room(fb.quv, (size_t)n * 72)) != RT_OK))
-      return rc;
-    if (!on_device) RT_HIP_TRY(hipMemcpy(fb.quv.p, images, (size_t)n * sizeof(RtFlatImage), hipMemcpyHostToDevice));
-    std::vector<uint32_t> kind(n);   // (the entries' own materials as created: an emitter's resident record says Light meanwhile)
-    for (uint32_t k = 0; k < n; ++k) kind[k] = r.keep_flat_matc[k].kind;
-    RT_HIP_TRY(hipMemcpy(fb.kind.p, kind.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    rtfb::ImageJob j;
-    j.n = n; j.n_textures = f.n_textures; j.in = on_device ? images : fb.quv.get<const RtFlatImage>();
-    j.tex = f.n_textures ? f.tex_table.get<const RtFlatImageTex>() : nullptr; j.kind = fb.kind.get<const uint32_t>();
-    j.out = f.images_spare.get<RtFlatImageRec>(); j.status = fb.status.get<rtfb::Status>();
-    RT_HIP_TRY(rtfb::images(j, nullptr));
-    rtfb::Status st;
-    RT_HIP_TRY(hipMemcpy(&st, fb.status.p, sizeof st, hipMemcpyDeviceToHost));  // the one readback: the lowest refused entry and why, the count
-    if (st.bad_degenerate != rtfb::NONE) return fail(RT_ERR_INVALID, "quad " + std::to_string(st.bad_degenerate) + ": " + rt_flat_image_why((int)st.bad_finite));
-    count = st.mismatch;
-  }
-  if (!count && !f.n_images) return RT_OK;   // no entry has an image and none shall: the scene is what it was
-  // the record slots the header takes before and after: they differ only in a scan scene that gains or loses its table
-  const uint32_t had = f.header_recs(), has = (f.n_nodes || f.n_normals || f.n_moving || count) ? 1u : 0u;
-  RtHipScene::Resident::Flats::Tables& spare = f.spare;
-  if (has != had) {
-    if ((rc = room(spare.rec, ((size_t)n + has) * sizeof(RtQuadRec))) != RT_OK) return rc;
-    RT_HIP_TRY(hipMemcpy(spare.rec.get<RtQuadRec>() + has, f.first_rec(f.live), (size_t)n * sizeof(RtQuadRec), hipMemcpyDeviceToDevice));
-    RT_HIP_TRY(hipDeviceSynchronize());
-  }
-  // everything is built: swap it in
-  if (has != had) f.live.rec.swap(spare.rec);
-  if (count) f.images.swap(f.images_spare);
-  f.n_images = count;
-  if (has) {
-    f.keep_header = f.header(f.live, f.n_nodes, f.live.order, s->host.n_spheres);
-    RT_HIP_TRY(hipMemcpy(f.live.rec.p, &f.keep_header, sizeof f.keep_header, hipMemcpyHostToDevice));
-  }
-  RT_HIP_TRY(hipDeviceSynchronize());
-  return adopt_tables(s, Moved::flats);
-}
-}  // namespace
-
-extern "C" int rt_hip_scene_set_flat_images(RtHipScene* s, const RtFlatImage* images, uint32_t n_quads, uint32_t flags) {
-  return scene_set_flat_images(s, images, n_quads, flags, false);
-}
+#include "rt_hip_flats.hip"  // rt_hip_scene_update_flats and rt_hip_scene_set_flat_*: changing the flat primitives of a resident scene
 
 // diagnostics: one resident table as the kernels read it
 extern "C" int rt_hip_scene_table(const RtHipScene* s, const char* name, void* out, size_t cap, size_t* needed) {

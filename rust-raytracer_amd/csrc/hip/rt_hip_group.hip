@@ -564,98 +564,56 @@ extern "C" int rt_hip_group_set_lens(RtHipGroup* g, const double u[3], const dou
   return RT_OK;
 }
 
-// move the spheres of every rank's scene (rt_hip_scene_update_spheres); each rank's tables are built once, its second view follows
+namespace {
+// One update on every rank's scene: each rank's resident tables are replaced once and its second view follows (rt_hip_scene_view_follow).
+// name: the group's call, for its refusals; device_memory: the table is memory of ONE device, which serves the ranks of that device only —
+// a group of several devices takes host memory; what: what the update replaced; per_rank(scene): the scene-level update, views_follow set.
+// The first rank checks the arguments: a bad table changes no rank.
+template <typename PerRank>
+int group_update(RtHipGroup* g, const char* name, bool device_memory, Moved what, PerRank&& per_rank) {
+  if (!g) return fail(RT_ERR_INVALID, "null argument");
+  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, std::string(name) + ": a submitted frame is uncollected");
+  if (device_memory)
+    for (uint32_t r = 1; r < g->G; ++r)
+      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, std::string(name) + ": device memory serves the ranks of one device only");
+  for (uint32_t r = 0; r < g->G; ++r) {
+    int rc = per_rank(g->scene[r]);
+    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], what);
+    if (rc != RT_OK) return rc;
+  }
+  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
+  return RT_OK;
+}
+}  // namespace
+
+// move the spheres of every rank's scene (rt_hip_scene_update_spheres)
 extern "C" int rt_hip_group_update_spheres(RtHipGroup* g, const double* center, const double* center1) {
-  if (!g) return fail(RT_ERR_INVALID, "null argument");
-  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_update_spheres: a submitted frame is uncollected");
-  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad centres change no rank)
-    int rc = scene_update(g->scene[r], center, center1, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::spheres);
-    if (rc != RT_OK) return rc;
-  }
-  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
-  return RT_OK;
+  return group_update(g, "rt_hip_group_update_spheres", false, Moved::spheres, [&](RtHipScene* s) { return scene_update(s, center, center1, true); });
 }
-
-// move the flat primitives of every rank's scene (rt_hip_scene_update_flats); each rank's resident tables are updated once, its second
-// view follows.  quv with RT_UPDATE_FLATS_DEVICE is memory of ONE device: a group of several devices takes host memory.
+// move the flat primitives of every rank's scene (rt_hip_scene_update_flats)
 extern "C" int rt_hip_group_update_flats(RtHipGroup* g, const double* quv, uint32_t n_quads, uint32_t flags) {
-  if (!g) return fail(RT_ERR_INVALID, "null argument");
-  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_update_flats: a submitted frame is uncollected");
-  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
-    for (uint32_t r = 1; r < g->G; ++r)
-      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_update_flats: device memory serves the ranks of one device only");
-  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad geometry changes no rank)
-    int rc = scene_update_flats(g->scene[r], quv, n_quads, flags, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
-    if (rc != RT_OK) return rc;
-  }
-  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
-  return RT_OK;
+  return group_update(g, "rt_hip_group_update_flats", (flags & RT_UPDATE_FLATS_DEVICE) != 0u, Moved::flats,
+                      [&](RtHipScene* s) { return scene_update_flats(s, quv, n_quads, flags, true); });
 }
-
-// shading normals on every rank's scene (rt_hip_scene_set_flat_normals); each rank's table is made once, its second view follows
+// shading normals on every rank's scene (rt_hip_scene_set_flat_normals)
 extern "C" int rt_hip_group_set_flat_normals(RtHipGroup* g, const double* normals, uint32_t n_quads, uint32_t flags) {
-  if (!g) return fail(RT_ERR_INVALID, "null argument");
-  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_normals: a submitted frame is uncollected");
-  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
-    for (uint32_t r = 1; r < g->G; ++r)
-      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_normals: device memory serves the ranks of one device only");
-  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: bad normals change no rank)
-    int rc = scene_set_flat_normals(g->scene[r], normals, n_quads, flags, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
-    if (rc != RT_OK) return rc;
-  }
-  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
-  return RT_OK;
+  return group_update(g, "rt_hip_group_set_flat_normals", (flags & RT_UPDATE_FLATS_DEVICE) != 0u, Moved::flats,
+                      [&](RtHipScene* s) { return scene_set_flat_normals(s, normals, n_quads, flags, true); });
 }
-
-// motion of the flat primitives within the frame on every rank's scene (rt_hip_scene_set_flat_motion), under the same two conditions
+// motion of the flat primitives within the frame on every rank's scene (rt_hip_scene_set_flat_motion)
 extern "C" int rt_hip_group_set_flat_motion(RtHipGroup* g, const double* move, uint32_t n_quads, uint32_t flags) {
-  if (!g) return fail(RT_ERR_INVALID, "null argument");
-  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_motion: a submitted frame is uncollected");
-  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
-    for (uint32_t r = 1; r < g->G; ++r)
-      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_motion: device memory serves the ranks of one device only");
-  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: a bad displacement changes no rank)
-    int rc = scene_update_flats(g->scene[r], nullptr, n_quads, flags, true, move, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
-    if (rc != RT_OK) return rc;
-  }
-  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
-  return RT_OK;
+  return group_update(g, "rt_hip_group_set_flat_motion", (flags & RT_UPDATE_FLATS_DEVICE) != 0u, Moved::flats,
+                      [&](RtHipScene* s) { return scene_set_flat_motion(s, move, n_quads, flags, true); });
 }
-
-// emission of the flat primitives on every rank's scene (rt_hip_scene_set_flat_lights), under the same two conditions
+// emission of the flat primitives on every rank's scene (rt_hip_scene_set_flat_lights)
 extern "C" int rt_hip_group_set_flat_lights(RtHipGroup* g, const float* emit, uint32_t n_quads, uint32_t flags) {
-  if (!g) return fail(RT_ERR_INVALID, "null argument");
-  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_lights: a submitted frame is uncollected");
-  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
-    for (uint32_t r = 1; r < g->G; ++r)
-      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_lights: device memory serves the ranks of one device only");
-  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: a bad table changes no rank)
-    int rc = scene_set_flat_lights(g->scene[r], emit, n_quads, flags, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
-    if (rc != RT_OK) return rc;
-  }
-  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
-  return RT_OK;
+  return group_update(g, "rt_hip_group_set_flat_lights", (flags & RT_UPDATE_FLATS_DEVICE) != 0u, Moved::flats,
+                      [&](RtHipScene* s) { return scene_set_flat_lights(s, emit, n_quads, flags, true); });
 }
-
-// images on the flat primitives of every rank's scene (rt_hip_scene_set_flat_images), under the same two conditions
+// images on the flat primitives of every rank's scene (rt_hip_scene_set_flat_images)
 extern "C" int rt_hip_group_set_flat_images(RtHipGroup* g, const RtFlatImage* images, uint32_t n_quads, uint32_t flags) {
-  if (!g) return fail(RT_ERR_INVALID, "null argument");
-  if (g->n_collected != g->n_submitted) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_images: a submitted frame is uncollected");
-  if ((flags & RT_UPDATE_FLATS_DEVICE) && g->G > 1)
-    for (uint32_t r = 1; r < g->G; ++r)
-      if (g->scene[r]->device != g->scene[0]->device) return fail(RT_ERR_INVALID, "rt_hip_group_set_flat_images: device memory serves the ranks of one device only");
-  for (uint32_t r = 0; r < g->G; ++r) {  // (the first rank checks the arguments: a bad table changes no rank)
-    int rc = scene_set_flat_images(g->scene[r], images, n_quads, flags, true);
-    if (rc == RT_OK && !g->scene2.empty()) rc = rt_hip_scene_view_follow(g->scene2[r], Moved::flats);
-    if (rc != RT_OK) return rc;
-  }
-  if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
-  return RT_OK;
+  return group_update(g, "rt_hip_group_set_flat_images", (flags & RT_UPDATE_FLATS_DEVICE) != 0u, Moved::flats,
+                      [&](RtHipScene* s) { return scene_set_flat_images(s, images, n_quads, flags, true); });
 }
 
 namespace rtg { void prepare_staging(RtHipGroup* g, int n_frames); }

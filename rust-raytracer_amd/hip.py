@@ -244,6 +244,19 @@ def _flat_images(images, device):
     return C.cast(arr, C.c_void_p), n, 0, arr
 
 
+def _flat_call(L, name, handle, args):
+    """one call of rt_hip_{scene,group}_update_flats or ..._set_flat_*: args is what _flat_geometry, _flat_images or _flat_none gave —
+    (pointer, n, flags, what must stay alive until the call has returned)"""
+    p, n, flags, keep = args
+    _check(getattr(L, name)(handle, p, n, flags), L)
+    del keep
+
+
+def _flat_none(n_quads):
+    """the arguments that remove a table: a null pointer and the scene's count"""
+    return None, int(n_quads), 0, None
+
+
 TABLES = ("grid", "cell_word", "cell_items", "large", "geom", "large_geom", "motion", "quads", "quad_lim", "flat_bvh", "flat_bvh_order", "flat_normals", "flat_motion", "flat_lights", "flat_images", "lights", "mat", "matc")   # the names rt_hip_scene_table knows
 
 
@@ -300,52 +313,30 @@ class HipScene:
         array or a CUDA torch tensor; a contiguous tensor on the scene's device is read where it is (no PCIe).  The structure is refit on
         the device; rebuild=True (or a change of the set of entries outside its preconditions) builds it anew: on the host, or with
         set_option("flat_build", 1) and an unchanged set on the device.  Blocking."""
-        p, n, flags, keep = _flat_geometry(quv, self.device, rebuild)
-        _check(self._L.rt_hip_scene_update_flats(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_scene_update_flats", self._h, _flat_geometry(quv, self.device, rebuild))
 
     def set_flat_normals(self, normals):
         """rt_hip_scene_set_flat_normals: shading normals on the scene's triangles — [n_quads, 9] float64 (the normals at q,
         q + u, q + v per entry; nine zeros: a flat entry), a numpy array or a CUDA torch tensor as for update_flats; None removes them.
         Blocking."""
-        if normals is None:
-            _check(self._L.rt_hip_scene_set_flat_normals(self._h, None, int(self.query("quads")), 0), self._L)
-            return
-        p, n, flags, keep = _flat_geometry(normals, self.device, False)
-        _check(self._L.rt_hip_scene_set_flat_normals(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_scene_set_flat_normals", self._h, _flat_none(self.query("quads")) if normals is None else _flat_geometry(normals, self.device, False))
 
     def set_flat_motion(self, move):
         """rt_hip_scene_set_flat_motion: the displacement of every flat primitive over the open shutter — [n_quads, 3]
         float64 (three zeros: the entry does not move), a numpy array or a CUDA torch tensor as for update_flats; None removes the
         motion.  Blocking."""
-        if move is None:
-            _check(self._L.rt_hip_scene_set_flat_motion(self._h, None, int(self.query("quads")), 0), self._L)
-            return
-        p, n, flags, keep = _flat_geometry(move, self.device, False, width=3, what="move")
-        _check(self._L.rt_hip_scene_set_flat_motion(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_scene_set_flat_motion", self._h, _flat_none(self.query("quads")) if move is None else _flat_geometry(move, self.device, False, width=3, what="move"))
 
     def set_flat_lights(self, emit):
         """rt_hip_scene_set_flat_lights: the emission of every flat primitive — [n_quads, 3] float32 in [0, 1] (three
         zeros: the entry does not emit), a numpy array or a CUDA torch tensor as for update_flats; None removes emission.  Blocking."""
-        if emit is None:
-            _check(self._L.rt_hip_scene_set_flat_lights(self._h, None, int(self.query("quads")), 0), self._L)
-            return
-        p, n, flags, keep = _flat_geometry(emit, self.device, False, width=3, what="emit", dtype="float32")
-        _check(self._L.rt_hip_scene_set_flat_lights(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_scene_set_flat_lights", self._h, _flat_none(self.query("quads")) if emit is None else _flat_geometry(emit, self.device, False, width=3, what="emit", dtype="float32"))
 
     def set_flat_images(self, images):
         """rt_hip_scene_set_flat_images (DESIGN.md §29): the image of every flat primitive — n_quads abi.RtFlatImage (abi.flat_image(...);
         tex_id abi.RT_FLAT_IMAGE_NONE: the entry has none) as a sequence, an [n, 64] uint8 numpy array or a CUDA torch tensor of that
         shape (read where it is when on the scene's device); None removes the images.  Blocking."""
-        if images is None:
-            _check(self._L.rt_hip_scene_set_flat_images(self._h, None, int(self.query("quads")), 0), self._L)
-            return
-        p, n, flags, keep = _flat_images(images, self.device)
-        _check(self._L.rt_hip_scene_set_flat_images(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_scene_set_flat_images", self._h, _flat_none(self.query("quads")) if images is None else _flat_images(images, self.device))
 
     def table(self, name):
         """rt_hip_scene_table (diagnostics): the bytes of one resident table (TABLES) as the kernels read it"""
@@ -642,55 +633,33 @@ class HipGroup:
     def update_flats(self, quv, rebuild=False):
         """rt_hip_group_update_flats: HipScene.update_flats on every rank (the geometry travels through host memory: the ranks may be on
         several devices); no submitted frame may be uncollected"""
-        p, n, flags, keep = _flat_geometry(quv, None, rebuild)
-        _check(self._L.rt_hip_group_update_flats(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_group_update_flats", self._h, _flat_geometry(quv, None, rebuild))
 
     def set_flat_normals(self, normals, n_quads=None):
         """rt_hip_group_set_flat_normals: HipScene.set_flat_normals on every rank (through host memory); None removes them and needs
         n_quads, the scene's count"""
-        if normals is None:
-            _check(self._L.rt_hip_group_set_flat_normals(self._h, None, int(n_quads), 0), self._L)
-            return
-        p, n, flags, keep = _flat_geometry(normals, None, False)
-        _check(self._L.rt_hip_group_set_flat_normals(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_group_set_flat_normals", self._h, _flat_none(n_quads) if normals is None else _flat_geometry(normals, None, False))
 
     def set_flat_motion(self, move, n_quads=None):
         """rt_hip_group_set_flat_motion: HipScene.set_flat_motion on every rank (through host memory); None removes the motion and needs
         n_quads, the scene's count"""
-        if move is None:
-            if n_quads is None:
-                raise ValueError("set_flat_motion(None) needs n_quads, the scene's count")
-            _check(self._L.rt_hip_group_set_flat_motion(self._h, None, int(n_quads), 0), self._L)
-            return
-        p, n, flags, keep = _flat_geometry(move, None, False, width=3, what="move")
-        _check(self._L.rt_hip_group_set_flat_motion(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_group_set_flat_motion", self._h, _flat_none(self._count("set_flat_motion", n_quads)) if move is None else _flat_geometry(move, None, False, width=3, what="move"))
 
     def set_flat_lights(self, emit, n_quads=None):
         """rt_hip_group_set_flat_lights: HipScene.set_flat_lights on every rank (through host memory); None removes emission and needs
         n_quads, the scene's count"""
-        if emit is None:
-            if n_quads is None:
-                raise ValueError("set_flat_lights(None) needs n_quads, the scene's count")
-            _check(self._L.rt_hip_group_set_flat_lights(self._h, None, int(n_quads), 0), self._L)
-            return
-        p, n, flags, keep = _flat_geometry(emit, None, False, width=3, what="emit", dtype="float32")
-        _check(self._L.rt_hip_group_set_flat_lights(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_group_set_flat_lights", self._h, _flat_none(self._count("set_flat_lights", n_quads)) if emit is None else _flat_geometry(emit, None, False, width=3, what="emit", dtype="float32"))
 
     def set_flat_images(self, images, n_quads=None):
         """rt_hip_group_set_flat_images: HipScene.set_flat_images on every rank (through host memory); None removes the images and needs
         n_quads, the scene's count"""
-        if images is None:
-            if n_quads is None:
-                raise ValueError("set_flat_images(None) needs n_quads, the scene's count")
-            _check(self._L.rt_hip_group_set_flat_images(self._h, None, int(n_quads), 0), self._L)
-            return
-        p, n, flags, keep = _flat_images(images, None)
-        _check(self._L.rt_hip_group_set_flat_images(self._h, p, n, flags), self._L)
-        del keep
+        _flat_call(self._L, "rt_hip_group_set_flat_images", self._h, _flat_none(self._count("set_flat_images", n_quads)) if images is None else _flat_images(images, None))
+
+    @staticmethod
+    def _count(method, n_quads):
+        if n_quads is None:
+            raise ValueError(f"{method}(None) needs n_quads, the scene's count")
+        return n_quads
 
     def set_option(self, key, value):
         _check(self._L.rt_hip_group_set_option(self._h, key.encode(), int(value)), self._L)
